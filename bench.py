@@ -5,11 +5,16 @@ clip + Adam) of VoiceBox dim 512 / depth 12 / heads 16 on synthetic (B=8 per GPU
     python bench.py --gpus N --steps K --warmup W          (N>1 without a launcher: re-executes itself as N ranks through
                                                             torch.distributed.run; under a launcher it reads RANK / WORLD_SIZE)
 
-Prints ONE JSON line on rank 0 (see the contract in the task description), including
+Prints ONE JSON line on rank 0: `metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` (wall clock of one timed
+step) and the whole-step roofline fraction.  A plain run does only that: set up, warm up, time the K steps, print.  `--full` adds
   roofline     : the dominant kernel's achieved TFLOP/s (algorithmic FLOPs / HIP-event-measured launch time)
-                 against the 2.5 PFLOP/s dense bf16/fp16 MFMA peak, plus the whole-step fraction;
+                 against the 2.5 PFLOP/s dense bf16/fp16 MFMA peak (3 extra in-situ steps + isolated GEMM launches);
+  sample       : train mode, one GPU: the 64-interval sampler under hipGraph (median of three runs);
   cpu_baseline : the CPU oracle (oracle/restate.py, kind "port") timed on this box's host cores on a bounded sample.
 `--mode sample` benchmarks ConditionalFlowMatcherWrapper.sample (64 midpoint intervals = 128 NFE) instead.
+`--dump-outputs DIR` writes what the last timed step computed to DIR/<name>.npy (float32): train mode `loss` and
+`params_sample` (the fp32 master parameters after the step's Adam update, a fixed seeded sample of 8 Mi positions), sample mode
+`sample` (the generated mel frames).  Inputs and weights are seeded: the same arguments give the same inputs in every run.
 """
 import argparse
 import json
@@ -225,6 +230,30 @@ def cpu_baseline(args):
                       f"depth {args.depth}, {cores} threads; 1 warm-up + 3 timed steps; best {best:.2f} s/step, median {med:.2f} s/step"}
 
 
+DUMP_MAX_ELEMS = 8 << 20  # per array: at most two arrays of 32 MiB (float32)
+
+
+def seeded_sample(t, k=DUMP_MAX_ELEMS, seed=0):
+    """The tensor itself if it has at most k elements, else k of its elements at fixed positions (CPU generator, `seed`; sorted,
+    with repeats) -- the same positions in every run, so that two builds can be compared element for element."""
+    if t.numel() <= k:
+        return t.detach()
+    flat = t.detach().reshape(-1)
+    idx = torch.randint(0, flat.numel(), (k,), generator=torch.Generator().manual_seed(seed)).sort().values
+    return flat[idx.to(flat.device)]
+
+
+def dump_outputs(out_dir, arrays):
+    """Writes every (name, tensor) as out_dir/<name>.npy in float32 (float64 stays float64)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        t = seeded_sample(t)
+        t = t if t.dtype == torch.float64 else t.float()
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy())
+
+
 def self_launch(args):
     """`python bench.py --gpus N` without a launcher: re-exec as N ranks through torch.distributed.run on this node (one process per
     GPU, RCCL over xGMI; rendezvous on 127.0.0.1) and pass its output / exit code through."""
@@ -255,8 +284,13 @@ def main():
     ap.add_argument("--intervals", type=int, default=64, help="sample mode: midpoint intervals (NFE = 2x)")
     ap.add_argument("--attn-dropout", type=float, default=0.0, help="not a BASELINE config (the reference's default is 0): A/B only")
     ap.add_argument("--ff-dropout", type=float, default=0.0, help="not a BASELINE config: A/B only")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-sample", action="store_true", help="train mode: skip the 64-interval sample leg")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the in-situ stage table and `roofline`, the 64-interval "
+                         "sample leg (train mode, one GPU) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32; a fixed seeded sample of large outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-sample", action="store_true", help="--full, train mode: skip the 64-interval sample leg")
     ap.add_argument("--grad-comm", default="fp32", choices=["fp32", "bf16"], help="wire dtype of the gradient all-reduce (N > 1)")
     ap.add_argument("--bucket-mb", type=int, default=0, help="gradient all-reduce bucket size in MiB (0: the library default)")
     ap.add_argument("--adaln-exchange", default="auto", choices=["auto", "factors", "materialize"],
@@ -323,12 +357,16 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t)
     loss_val = float(last.float().mean()) if args.mode == "train" else None
+    if args.dump_outputs and rank == 0:  # before --full's extra steps move the parameters on
+        dump_outputs(args.dump_outputs, {"loss": last, "params_sample": ts.fp.flat} if args.mode == "train" else {"sample": last})
 
     # ---- in-situ stage times (every rank runs the extra steps: they contain the collectives); sample mode replays a hipGraph,
     # whose launches do not pass through the runtime again, so its table comes from an eager 2-interval sample
-    if args.mode == "train":
+    # (--full only: a plain run measures the headline figure and nothing else)
+    rows = []
+    if args.full and args.mode == "train":
         rows = in_situ_stage_table(args, step, 3)
-    else:
+    elif args.full:
         # ONE stream, full batch (VBX_SAMPLE_SPLIT=1 for this sampler only): with the two concurrent half-batch streams of the timed
         # run the event brackets of the streams overlap and every launch works on B/2 -- such a table would credit full-batch FLOPs
         # to half-batch launches.  The wall-clock figure of the split run is `value` / sample.fwd_frac.
@@ -387,7 +425,7 @@ def main():
                                "isolated_us": {k: isolated_gemm_us(args, dev, k) for k in ("fwd ff_in", "dgrad to_qkv")},
                                "mfma_us_per_step": round(sum(r["us_per_step"] for r in mf), 1),
                                "kernels": rows}
-        if args.mode == "train" and world == 1 and not args.no_sample:
+        if args.full and args.mode == "train" and world == 1 and not args.no_sample:
             # the other half of BASELINE.json's metric in the same invocation: 64 midpoint intervals = 128 NFE under hipGraph
             steps_pts = args.intervals + 1
             wrapper.sample(cond=x, steps=steps_pts)  # capture + warm-up
@@ -407,7 +445,7 @@ def main():
                                      f"= {args.intervals} midpoint intervals under hipGraph (one stream at dim 512, where the weight-stationary GEMMs own whole "
                                      f"CUs; two concurrent half batches at other widths: solver.py), median of three timed runs after the capture run",
                              "runs_ms": [round(t * 1e3, 2) for t in dts]}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args)
         print(json.dumps(out), flush=True)
     if dist is not None:

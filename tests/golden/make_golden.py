@@ -3,7 +3,7 @@
 
 Run in the build container only (the GPU box has no /root/reference):
     python tests/golden/make_golden.py
-Outputs (committed): tests/golden/{masks,rotary,small,small_gateloop,small_text,transformer,duration,cfg1,cfg4,small_wc,cfg4_wc,cfg5_wc,cfg4_wc_train,cfg4_seeds,cfg3,cfg5_wc_b8,small_dropout,small_dimin,cfg4_seeds_exact,attend_mask4d,transformer_unet,init_stats}.pt
+Outputs (committed): tests/golden/{masks,rotary,small,small_gateloop,small_text,transformer,duration,cfg1,cfg4,small_wc,cfg4_wc,cfg5_wc,cfg4_wc_train,cfg4_seeds,cfg3,cfg5_wc_b8,small_dropout,small_dimin,cfg4_seeds_exact,attend_mask4d,transformer_unet,init_stats,live_reference}.pt
 
 RNG protocol: the reference draws, from the global CPU generator,
 randn_like(x1) -> rand(B) -> uniform_(0.7,1)(B) -> uniform_(0,1)(B) per training
@@ -755,14 +755,32 @@ def gen_init_stats(ref):
     torch.save(out, os.path.join(HERE, "init_stats.pt"))
 
 
+def gen_live_reference(ref):
+    """The reference's own ConditionalFlowMatcherWrapper.forward at dim 64 / depth 2 (num_cond_tokens 5), weights by
+    oracle.restate.init_state_dict(seed=4), its random draws taken from the global generator after torch.manual_seed(5): the loss it
+    returns, for tests/test_oracle.py::test_restatement_vs_live_reference to replay the same draws against."""
+    cfg = restate.Cfg(dim=64, depth=2, heads=2, dim_head=64)
+    state = restate.init_state_dict(cfg, seed=4)
+    vb = ref.VoiceBox(dim=64, num_cond_tokens=5, depth=2, dim_head=64, heads=2, condition_on_text=False)
+    vb.load_state_dict(state, strict=False)
+    wrapper = ref.ConditionalFlowMatcherWrapper(voicebox=vb)
+    x1 = torch.randn(3, 50, 64, generator=torch.Generator().manual_seed(3))
+    torch.manual_seed(5)
+    with torch.no_grad():
+        loss = wrapper(x1)
+    torch.save(dict(x1=x1, loss=loss.detach()), os.path.join(HERE, "live_reference.pt"))
+    print("live_reference: loss", float(loss))
+
+
 if __name__ == "__main__":
     ref = ref_loader.load_reference()
     which = sys.argv[1:] or ["masks", "rotary", "small", "small_gateloop", "small_text", "transformer", "duration", "cfg1", "cfg4",
-                             "small_wc", "cfg4_wc", "cfg5_wc", "cfg4_wc_train", "cfg4_seeds", "cfg3", "cfg5_wc_b8", "small_dropout", "small_dimin", "cfg4_seeds_exact", "attend_mask4d", "transformer_unet", "init_stats"]
+                             "small_wc", "cfg4_wc", "cfg5_wc", "cfg4_wc_train", "cfg4_seeds", "cfg3", "cfg5_wc_b8", "small_dropout", "small_dimin", "cfg4_seeds_exact", "attend_mask4d", "transformer_unet", "init_stats",
+                             "live_reference"]
     for w in which:
         {"masks": gen_masks, "rotary": gen_rotary, "small": gen_small, "small_gateloop": gen_small_gateloop, "small_text": gen_small_text,
          "transformer": gen_transformer, "duration": gen_duration, "cfg1": gen_cfg1, "cfg4": gen_cfg4, "small_wc": gen_small_wc, "cfg4_wc": gen_cfg4_wc,
          "cfg5_wc": gen_cfg5_wc, "cfg4_wc_train": gen_cfg4_wc_train, "cfg4_seeds": gen_cfg4_seeds, "cfg3": gen_cfg3,
          "cfg5_wc_b8": gen_cfg5_wc_b8, "small_dropout": gen_small_dropout, "small_dimin": gen_small_dimin,
          "cfg4_seeds_exact": gen_cfg4_seeds_exact, "attend_mask4d": gen_attend_mask4d, "transformer_unet": gen_transformer_unet,
-         "init_stats": gen_init_stats}[w](ref)
+         "init_stats": gen_init_stats, "live_reference": gen_live_reference}[w](ref)

@@ -23,9 +23,9 @@ case "$1" in
   gemm5|gemm5_sample) V=VBX_GEMM5; S="1 0";;
   *) sed -n 2,17p $0; exit 1;;
 esac
-ARGS="--steps 30 --warmup 8 --no-cpu-baseline --no-sample"
-[ "$1" = gemm5_sample ] && ARGS="--mode sample --steps 3 --warmup 1 --no-cpu-baseline"
-[ "$1" = sample_split ] && ARGS="--mode sample --steps 3 --warmup 1 --no-cpu-baseline"
+ARGS="--full --steps 30 --warmup 8 --no-cpu-baseline --no-sample"
+[ "$1" = gemm5_sample ] && ARGS="--full --mode sample --steps 3 --warmup 1 --no-cpu-baseline"
+[ "$1" = sample_split ] && ARGS="--full --mode sample --steps 3 --warmup 1 --no-cpu-baseline"
 for i in 1 2; do for s in $S; do
   env $V=$s timeout 300 python bench.py $ARGS 2>/dev/null | tail -1 | python -c "
 import sys, json

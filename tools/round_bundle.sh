@@ -7,9 +7,9 @@ T=${1:-r05}
 cd $GRAFT_REPO_ROOT; O=gpurun_out/$T; mkdir -p $O
 timeout 1500 python -m pytest tests -m gpu -q > $O/pytest.log 2>&1; tail -3 $O/pytest.log
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; tail -2 $O/smoke.log
-timeout 600 python bench.py > $O/bench_train.log 2>&1; tail -1 $O/bench_train.log > $O/${T}_bench_train.json; tail -c 700 $O/${T}_bench_train.json
-timeout 300 python bench.py --mode sample --steps 3 --warmup 1 --no-cpu-baseline 2>/dev/null | tail -1 > $O/${T}_bench_sample.json
-timeout 300 python bench.py --dim 1024 --steps 10 --warmup 3 --no-cpu-baseline --no-sample 2>/dev/null | tail -1 > $O/${T}_bench_train_dim1024.json
+timeout 600 python bench.py --full > $O/bench_train.log 2>&1; tail -1 $O/bench_train.log > $O/${T}_bench_train.json; tail -c 700 $O/${T}_bench_train.json
+timeout 300 python bench.py --full --mode sample --steps 3 --warmup 1 --no-cpu-baseline 2>/dev/null | tail -1 > $O/${T}_bench_sample.json
+timeout 300 python bench.py --full --dim 1024 --steps 10 --warmup 3 --no-cpu-baseline --no-sample 2>/dev/null | tail -1 > $O/${T}_bench_train_dim1024.json
 python - <<PY
 import json
 for n in ("${T}_bench_train","${T}_bench_sample","${T}_bench_train_dim1024"):
@@ -20,9 +20,9 @@ for n in ("${T}_bench_train","${T}_bench_sample","${T}_bench_train_dim1024"):
         print(n, "ERR", e)
 PY
 R=$GRAFT_REPO_ROOT; export TMPDIR=/tmp; cd /tmp
-B="python $R/bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-sample"
+B="python $R/bench.py --full --steps 4 --warmup 2 --no-cpu-baseline --no-sample"
 timeout 300 rocprofv3 --kernel-trace --stats -d $R/$O/prof_train -o run -- $B > $R/$O/prof_train.log 2>&1
-timeout 300 rocprofv3 --kernel-trace --stats -d $R/$O/prof_sample -o run -- python $R/bench.py --mode sample --steps 1 --warmup 0 --intervals 8 --no-cpu-baseline > $R/$O/prof_sample.log 2>&1
+timeout 300 rocprofv3 --kernel-trace --stats -d $R/$O/prof_sample -o run -- python $R/bench.py --full --mode sample --steps 1 --warmup 0 --intervals 8 --no-cpu-baseline > $R/$O/prof_sample.log 2>&1
 timeout 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $R/$O/pmc_fetch -o run -- $B > $R/$O/pmc_fetch.log 2>&1
 timeout 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $R/$O/pmc_write -o run -- $B > $R/$O/pmc_write.log 2>&1
 timeout 300 rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA SQ_INSTS_VALU SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT GRBM_GUI_ACTIVE --output-format csv -d $R/$O/pmc_mfma -o run -- $B > $R/$O/pmc_mfma.log 2>&1
