@@ -144,7 +144,11 @@ int vbx_rmsnorm_bwd(const float* x, const float* gamma, long gb_stride, const vo
  * so that q16 . k16 is directly the exponent of exp2 -- the kernels fold the softmax statistics into the MFMA accumulator
  * (csrc/attn_bwd_fold.inc) and have no per-element scale multiply left.  The to_qkv epilogue writes it that way
  * (vbx_gemm_desc.q_prescale); a caller with plain fp32 q multiplies before rounding to fp16.  qb (the bf16 backward operand)
- * stays UNSCALED; `scale` remains the multiplier of dq / dk, which are gradients w.r.t. the unscaled q / k. */
+ * stays UNSCALED; `scale` remains the multiplier of dq / dk, which are gradients w.r.t. the unscaled q / k.
+ * MASKS: a masked key gets weight 0.  A batch whose mask is all False follows attend.py:126 (masked_fill with -finfo.max, then
+ * softmax), i.e. a UNIFORM softmax over all Np keys (logits taken as 0): out_i = sum_j keep_ij * rk * v_j / Np (keep = 1, rk = 1
+ * without dropout), lse = log2(Np), dv_j = sum_i keep_ij * rk * dO_i / Np, dq = dk = 0 (and, in the fused backward, a zero d(q, k)
+ * block and zero gamma partials).  Every forward and backward entry point, vbx_attn_fwd_f32* included, implements this. */
 float vbx_attn_q_prescale(float scale);
 int vbx_attn_fwd(const void* q16, const void* k16, const void* v16 /* fp16 */, const uint8_t* mask,
                  void* out16 /* fp16 [B,Np,H*64] */, void* out_bf16 /* optional bf16 copy (backward operand) */,

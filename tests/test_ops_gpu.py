@@ -13,6 +13,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from attn_check import attn_inputs, max_err, qpre, rel_err, rot_tables  # noqa: F401
 from oracle import restate
 
 pytestmark = pytest.mark.gpu
@@ -35,15 +36,6 @@ def st():
 
 def bf(x):
     return x.to(torch.bfloat16)
-
-
-def rel_err(got, ref):
-    got, ref = got.double().cpu(), ref.double().cpu()
-    return float((got - ref).norm() / ref.norm().clamp(min=1e-30))
-
-
-def max_err(got, ref):
-    return float((got.double().cpu() - ref.double().cpu()).abs().max())
 
 
 # ----------------------------------------------------------------------------- hardware probes
@@ -180,12 +172,6 @@ def test_gemm_tn_geglu_rowmap(L):
         if f < Fd:
             exp[f if w < 64 else Fd + f] = ref_packed[p]
     assert rel_err(dst, exp) < 1e-5
-
-
-def rot_tables(Np, R):
-    pos = torch.cat((torch.full((R,), -10000, dtype=torch.long), torch.arange(Np - R)))
-    fr = restate.rotary_freqs(pos, 64, 50000.0)
-    return fr, fr[:, :32].cos().contiguous(), fr[:, :32].sin().contiguous()
 
 
 @pytest.mark.parametrize("Bsz,Np,H,D,qknorm", [(2, 56, 2, 64, True), (2, 1040, 4, 256, True), (1, 40, 2, 128, False),
@@ -399,25 +385,6 @@ def bwd_variant(request, L):
     L.lib().vbx_attn_bwd_select(request.param)
     yield request.param
     L.lib().vbx_attn_bwd_select(0)
-
-
-def qpre(L, q16, scale):
-    """The kernels' q operand and the q the exact reference must see (include/vbx.h, attention contract since round 5): q16 carries
-    scale * log2(e), i.e. the kernel computes with fp16(q * c) -- the reference with that value divided by c in fp64."""
-    c = L.lib().vbx_attn_q_prescale(scale)
-    qs = (q16.float() * c).half()
-    return qs, qs.double() / c
-
-
-def attn_inputs(Bsz, H, Np, seed, qnorm=8.0):
-    g = torch.Generator().manual_seed(seed)
-    q = torch.randn(Bsz, H, Np, 64, generator=g)
-    k = torch.randn(Bsz, H, Np, 64, generator=g)
-    if qnorm:
-        q = q / q.norm(dim=-1, keepdim=True) * qnorm
-        k = k / k.norm(dim=-1, keepdim=True) * qnorm
-    v = torch.randn(Bsz, H, Np, 64, generator=g)
-    return q.half(), k.half(), v.half()
 
 
 @pytest.mark.parametrize("Bsz,H,Np,scale,masked", [(1, 2, 64, 10.0, False), (2, 2, 1040, 10.0, False),

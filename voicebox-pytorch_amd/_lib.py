@@ -50,6 +50,7 @@ _PROTOS = {
     "vbx_attn_fwd_dropout": [P, P, P, P, P, P, P, I, I, I, F, P, F, P],
     "vbx_attn_bwd_dropout": [P, P, P, P, P, P, P, I, P, P, P, P, P, P, I, I, I, I, F, P, P, F, P],
     "vbx_attn_bwd_fused_tiles": [I],
+    "vbx_attn_bwd_fused_dropout": [P, P, P, P, P, P, P, I, P, P, P, P, P, P, P, P, P, F, P, I, P, I, I, I, F, P, P, P, F, P],
     "vbx_qknorm_rope_bwd": [P, P, P, P, P, P, P, P, P, P, F, P, I, P, I, I, I, F, P],
     "vbx_qknorm_rope_bwd_gpart_rows": [I],
     "vbx_pack_embed_input": [P, P, P, P, P, I, I, I, P],
@@ -109,6 +110,7 @@ _PROTOS = {
     "vbx_pack_weight3": [P, I, I, P, I, I, I, I, P],
     "vbx_qknorm_rope_f32": [P, I, I, I, F, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, F, P],
     "vbx_attn_fwd_f32": [P, P, P, P, P, P, P, P, I, I, I, F, P],
+    "vbx_attn_fwd_f32_dropout": [P, P, P, P, P, P, P, P, I, I, I, F, P, F, P],
     "vbx_geglu_f32": [P, P, P, P, P, L, I, P],
     "vbx_adaln_proj_f32": [P, P, P, P, I, I, I, I, P],
     "vbx_probe_tr16": [P, P, P, P],

@@ -1002,7 +1002,75 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_kernel_dma(const AttnBwdArgs 
 
 #include "attn_bwd_fold.inc"
 
+// ============================================================================ fully masked batches
+// A batch whose key mask is all False: attend.py:126 fills every logit with -finfo.max, so its softmax is UNIFORM over the Np keys
+// (the logits are taken as 0): out_i = sum_j keep_ij * rk * v_j / Np, lse = log2(Np); dv_j = sum_i keep_ij * rk * dO_i / Np, and
+// dq = dk = 0 (masked_fill blocks their gradient).  The main kernels see no valid key in such a batch: their P is 0, so they write
+// zero dq / dk / dv, zero outputs and lse 1e30.  This pass runs after them on the same stream, only when a mask is given, and
+// rewrites those batches.  A workgroup owns 64 rows x 64 columns of one (b, h); it scans mask[b, :Np] and exits if any key is valid.
+//   forward:  rows = queries, x = v [B,H,Np,64] (fp32 or fp16), keep bits from bits_rm ([bh][query][key words])
+//   backward: rows = keys,    x = dO [B,Np,H*64] (bf16),        keep bits from bits_cm ([bh][key][query words])
+// XK: 0 fp32, 1 fp16, 2 bf16 elements of x.
+template <int XK, bool DROP>
+__global__ __launch_bounds__(256) void attn_empty_batch_kernel(const void* __restrict__ x, long xs_b, long xs_h, long xs_s,
+                                                               const uint8_t* __restrict__ mask, int H, int Np,
+                                                               const unsigned* __restrict__ bits, int W2, float rkeep,
+                                                               float* __restrict__ o32, u16* __restrict__ o16, u16* __restrict__ ob,
+                                                               long o_ld, float* __restrict__ lse) {
+  const int b = blockIdx.z, h = blockIdx.y, bh = b * H + h;
+  int any = 0;
+  for (int j = threadIdx.x; j < Np; j += 256) any |= mask[(long)b * Np + j];
+  if (__syncthreads_or(any)) return;
+  const int r = blockIdx.x * 64 + (threadIdx.x >> 2), c0 = (threadIdx.x & 3) * 16;
+  const unsigned* brow = DROP ? bits + ((long)bh * Np + min(r, Np - 1)) * W2 : nullptr;
+  const long xb = b * xs_b + h * xs_h + c0;
+  float acc[16];
+#pragma unroll
+  for (int e = 0; e < 16; e++) acc[e] = 0.f;
+  for (int s = 0; s < Np; s++) {
+    if (DROP && !((brow[s >> 5] >> (s & 31)) & 1u)) continue;
+    const long i = xb + s * xs_s;
+#pragma unroll
+    for (int e = 0; e < 16; e++)
+      acc[e] += XK == 0 ? reinterpret_cast<const float*>(x)[i + e]
+                        : (XK == 1 ? f16_to_f32(reinterpret_cast<const u16*>(x)[i + e]) : bf16_to_f32(reinterpret_cast<const u16*>(x)[i + e]));
+  }
+  if (r >= Np) return;
+  const float sc = (DROP ? rkeep : 1.f) / (float)Np;
+#pragma unroll
+  for (int e = 0; e < 16; e++) acc[e] *= sc;
+  const long o = ((long)b * Np + r) * o_ld + h * 64 + c0;
+#pragma unroll
+  for (int e = 0; e < 16; e += 4) {
+    if (o32) *reinterpret_cast<float4*>(o32 + o + e) = make_float4(acc[e], acc[e + 1], acc[e + 2], acc[e + 3]);
+    if (o16) *reinterpret_cast<uint2*>(o16 + o + e) = make_uint2(pack_f16x2(acc[e], acc[e + 1]), pack_f16x2(acc[e + 2], acc[e + 3]));
+    if (ob) *reinterpret_cast<uint2*>(ob + o + e) = make_uint2(pack_bf16x2(acc[e], acc[e + 1]), pack_bf16x2(acc[e + 2], acc[e + 3]));
+  }
+  if (lse && c0 == 0) lse[(long)bh * Np + r] = log2f((float)Np);
+}
+
 }  // namespace
+
+// The launch of attn_empty_batch_kernel (also used by precise.hip).  xk 0 / 1: forward, x = v fp32 / fp16 [B,H,Np,64], outputs
+// token-major at row stride o_ld, bits = bits_rm; xk 2: backward, x = dO bf16 [B,Np,H*64], ob = dv at row stride o_ld, bits = bits_cm.
+int attn_empty_batch_fixup(int xk, const void* x, const uint8_t* mask, int B, int H, int Np, const void* bits, float p, float* o32,
+                           void* o16, void* ob, long o_ld, float* lse, void* stream) {
+  const long I = (long)H * 64;
+  const long xs_b = (long)Np * I, xs_h = xk == 2 ? 64 : (long)Np * 64, xs_s = xk == 2 ? I : 64;
+  const int W2 = vbx_dropout_bits_words(Np);
+  const float rk = bits ? vbx_dropout_keep_scale(p) : 1.f;
+  const dim3 grid(cdiv(Np, 64), H, B);
+  const unsigned* bw = (const unsigned*)bits;
+#define VBX_EMPTY_LAUNCH(XK, DROP)                                                                                                 \
+  hipLaunchKernelGGL((attn_empty_batch_kernel<XK, DROP>), grid, dim3(256), 0, (hipStream_t)stream, x, xs_b, xs_h, xs_s, mask, H, Np, \
+                     bw, W2, rk, o32, (u16*)o16, (u16*)ob, o_ld, lse)
+  if (xk == 0) { if (bits) VBX_EMPTY_LAUNCH(0, true); else VBX_EMPTY_LAUNCH(0, false); }
+  else if (xk == 1) { if (bits) VBX_EMPTY_LAUNCH(1, true); else VBX_EMPTY_LAUNCH(1, false); }
+  else { if (bits) VBX_EMPTY_LAUNCH(2, true); else VBX_EMPTY_LAUNCH(2, false); }
+#undef VBX_EMPTY_LAUNCH
+  VBX_LAUNCH_CHECK();
+  return 0;
+}
 
 #ifdef VBX_ATTN_TRACE
 extern "C" int vbx_debug_attn_trace(void* buf) {  // diagnostic build only: buf = [2][8192][4] u64 (forward | backward launches, by blockIdx), null to stop
@@ -1042,7 +1110,7 @@ static int attn_fwd_impl(const void* q16, const void* k16, const void* v, const 
                        (const u16*)k16, (const u16*)v, mask, (u16*)out, (u16*)out_bf16, lse, H, Np, QK_UNIT, BH, xmap,
                        (const unsigned*)drop_bits_rm, vbx_dropout_bits_words(Np), vbx_dropout_keep_scale(drop_p));
     VBX_LAUNCH_CHECK();
-    return 0;
+    return mask ? attn_empty_batch_fixup(1, v, mask, B, H, Np, drop_bits_rm, drop_p, nullptr, out, out_bf16, (long)H * 64, lse, stream) : 0;
   }
 #ifdef VBX_ATTN_DIAG
   if (getenv("VBX_FWD_ABL3") && atoi(getenv("VBX_FWD_ABL3")) != 0) {
@@ -1065,7 +1133,7 @@ static int attn_fwd_impl(const void* q16, const void* k16, const void* v, const 
   hipLaunchKernelGGL(attn_fwd_kernel_v3, grid, dim3(256), A3ST * ASTAGE, (hipStream_t)stream, (const u16*)q16, (const u16*)k16,
                      (const u16*)v, mask, (u16*)out, (u16*)out_bf16, lse, H, Np, QK_UNIT, BH, xmap);
   VBX_LAUNCH_CHECK();
-  return 0;
+  return mask ? attn_empty_batch_fixup(1, v, mask, B, H, Np, nullptr, 0.f, nullptr, out, out_bf16, (long)H * 64, lse, stream) : 0;
 }
 #ifdef VBX_ATTN_STEPTRACE
 extern "C" int vbx_debug_attn_steptrace(void* buf) {
@@ -1147,7 +1215,8 @@ static int attn_bwd_impl(const void* q16, const void* k16, const void* qb, const
   else if (fold) hipLaunchKernelGGL(attn_bwd_kernel_fold, dim3(2 * grid.x), dim3(256), BWD_DMA_LDS, st, a);
   else hipLaunchKernelGGL(attn_bwd_kernel_dma<false>, dim3(2 * grid.x), dim3(256), BWD_DMA_LDS, st, a);
   VBX_LAUNCH_CHECK();
-  return 0;
+  // a fully masked batch: dv of the uniform softmax (its dq / dk, and the fused path's d(q, k) and gamma partials, are already 0)
+  return mask ? attn_empty_batch_fixup(2, dout, mask, B, H, Np, drop.cm, drop.p, nullptr, nullptr, dv, dv_ld, nullptr, stream) : 0;
 }
 
 extern "C" int vbx_attn_bwd(const void* q16, const void* k16, const void* qb, const void* kb, const void* v,

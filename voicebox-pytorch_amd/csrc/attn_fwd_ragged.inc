@@ -5,7 +5,8 @@
 //                                                                                        lane's four S^T values, already in place)
 // The running maximum of a query is shared by the wave's four key groups (two shuffles per tile); the row sum stays per lane until
 // the end.  The four waves' (m, l, O^T) meet in LDS and 256 threads write the R output rows.  Same ring / barrier / DMA schedule as
-// the full tiles.  Reference semantics: attend.py:119-137 (masked keys -> -inf, a fully masked row -> zeros).
+// the full tiles.  Reference semantics: attend.py:119-137 (masked keys -> -inf).  A fully masked row
+// (l = 0) is written as zeros with lse 1e30 here; the reference's softmax is uniform there, which attn_empty_batch_kernel writes after.
 {
   const int qi = lane & 15, g = lane >> 4;
   const int qb0 = co.tile * 128;

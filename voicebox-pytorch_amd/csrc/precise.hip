@@ -24,6 +24,8 @@
 
 int vbx_rmsnorm_fwd_multi(const float* x, const float* gamma, const float* beta, long gb_stride, void* y_bf16, void* y_f16,
                           float* y_f32, int B, int Np, int n0, int rows_per_batch, int D, void* stream);  // norm.hip
+int attn_empty_batch_fixup(int xk, const void* x, const uint8_t* mask, int B, int H, int Np, const void* bits, float p, float* o32,
+                           void* o16, void* ob, long o_ld, float* lse, void* stream);  // attn.hip: a fully masked batch (uniform softmax)
 
 namespace {
 
@@ -323,7 +325,7 @@ extern "C" int vbx_attn_fwd_f32_dropout(const float* q, const float* k, const fl
                      lse, H, Np, scale * 1.44269504088896340736f, (const unsigned*)bits_rm, vbx_dropout_bits_words(Np),
                      vbx_dropout_keep_scale(p));
   VBX_LAUNCH_CHECK();
-  return 0;
+  return mask ? attn_empty_batch_fixup(0, v, mask, B, H, Np, bits_rm, p, out32, out16, out_bf16, (long)H * 64, lse, stream) : 0;
 }
 extern "C" int vbx_attn_fwd_f32(const float* q, const float* k, const float* v, const uint8_t* mask, float* out32, void* out16,
                                 void* out_bf16, float* lse, int B, int H, int Np, float scale, void* stream) {
@@ -331,7 +333,7 @@ extern "C" int vbx_attn_fwd_f32(const float* q, const float* k, const float* v, 
   hipLaunchKernelGGL(attn_fwd_f32_kernel<false>, dim3(cdiv(Np, 256), B * H), dim3(256), 0, ST, q, k, v, mask, out32, (u16*)out16,
                      (u16*)out_bf16, lse, H, Np, scale * 1.44269504088896340736f, (const unsigned*)nullptr, 0, 1.0f);
   VBX_LAUNCH_CHECK();
-  return 0;
+  return mask ? attn_empty_batch_fixup(0, v, mask, B, H, Np, nullptr, 0.f, out32, out16, out_bf16, (long)H * 64, lse, stream) : 0;
 }
 extern "C" int vbx_geglu_f32(const float* h1, float* g32, void* g16, void* g_bf16, void* h1_bf16, long M, int Fp, void* stream) {
   VBX_REQUIRE(h1 && g32 && M > 0 && Fp > 0 && Fp % 64 == 0, "vbx_geglu_f32: bad args (Fp must be a multiple of 64)");
