@@ -339,6 +339,56 @@ int vbx_counter_add(int* counter, int inc, void* stream);
  * 12) are evaluated once per sample() into table [2 * intervals][L][G] (G = 4 * D: gamma1 | beta1 | gamma2 | beta2 of a layer); this
  * copies the slice of time point 2 * counter + slot into the runtime's ada [L][B][G] (vbx_io.ada_table makes vbx_model_forward do it). */
 int vbx_ada_select(float* ada, int L, int B, int G, const float* table, const int* counter, int slot, void* stream);
+/* the same with `stride` time points per interval: row stride * counter + slot, 0 <= slot < stride (vbx_io.ada_stride) */
+int vbx_ada_select_rows(float* ada, int L, int B, int G, const float* table, const int* counter, int stride, int slot, void* stream);
+/* ------------------------------------------------------------------ ODE solvers (csrc/ode.hip; solver.py RKSampler / Dopri5Sampler)
+ * torchdiffeq.odeint's euler, rk4 (3/8 rule) and dopri5 (call site voicebox_pytorch.py:1295; restated in tests/ode_ref.py -- parity
+ * with the library UNPINNED).  States are fp32 [n] (n = B * N * D, a multiple of 4, 16-byte aligned); k is a HOST array of S <= 7
+ * device pointers (the stage derivatives), read at launch -- captured graphs keep them.  Nothing here reads a host scalar that
+ * changes between replays: fixed grids index device tables with a device counter, dopri5 reads its fp64 step state.
+ * Fixed grids: out = y + sum_j c_j k_j, c_j = table[(stride * counter[0] + row) * ld + j] (one row per stage input and one for the
+ * step's weights; RKSampler builds them on the host in fp32), and times[b] = table[stride * counter[0] + slot] for every b. */
+#define VBX_ODE_MAX_STAGES 7
+int vbx_ode_combine(float* out, const float* y, const float* const* k, int S, const float* table, int ld, const int* counter,
+                    int stride, int row, long n, void* stream);
+int vbx_ode_stage_time(float* times, int B, const float* table, const int* counter, int stride, int slot, void* stream);
+/* dopri5 step state: VBX_DP_STATE doubles of device memory.  The host writes T (= t0), TEND, ATOL, RTOL and zeroes the rest before
+ * the initial step; afterwards only vbx_ode_norm's controller writes it.  T / DT: start and size of the next attempt (fp64); T0 / T1
+ * / DT32: the last accepted step (DT32 = fp32(dt)); H0 / D1: initial-step intermediates; NFE, ACCEPTED, REJECTED: counts; LAST: the
+ * last attempt was accepted; DONE: T >= TEND; BAD: 1 non-finite error norm, 2 step-size underflow (the host raises). */
+enum {
+  VBX_DP_T = 0, VBX_DP_DT, VBX_DP_T0, VBX_DP_T1, VBX_DP_DT32, VBX_DP_RATIO, VBX_DP_H0, VBX_DP_D1, VBX_DP_NFE, VBX_DP_ACCEPTED,
+  VBX_DP_REJECTED, VBX_DP_LAST, VBX_DP_DONE, VBX_DP_BAD, VBX_DP_ATOL, VBX_DP_RTOL, VBX_DP_TEND, VBX_DP_STATE = 20
+};
+/* out = y + sum_j (beta_j * fp32(state[dt_slot])) k_j, beta a HOST array of S fp32 tableau entries; dt_slot VBX_DP_DT (a stage input)
+ * or VBX_DP_H0 (the initial-step probe y0 + h0 f0, beta = {1}) */
+int vbx_ode_combine_dp(float* out, const float* y, const float* const* k, const float* beta, int S, const double* state, int dt_slot,
+                       long n, void* stream);
+/* times[b] = STAGE: fp32(T) + alpha * fp32(DT) in fp32; END (c = 1): the fp32 value below fp32(T + DT) (torchdiffeq Perturb.PREV);
+ * PROBE: fp32(T + H0) */
+enum { VBX_ODE_TIME_TABLE = 0, VBX_ODE_TIME_STAGE = 1, VBX_ODE_TIME_END = 2, VBX_ODE_TIME_PROBE = 3 };
+int vbx_ode_stage_time_dp(float* times, int B, const double* state, float alpha, int mode, void* stream);
+/* RMS norms over the whole state and the step-size control, deterministic, two launches: per-workgroup fp64 partial sums of squares
+ * into slab (vbx_ode_norm_slab_doubles(n) doubles), then one workgroup sums it in a fixed order and updates state.
+ *   ERROR (S = 7, c = the error weights): ratio = rms(err / (atol + rtol max(|y0|, |y1|))), err = sum_j (c_j fp32(DT)) k_j, not
+ *     stored; accept iff ratio <= 1 (T0, T1, DT32, T advance; DONE), DT *= min(10, max(0.9 ratio^-1/5, ratio < 1 ? 1 : 0.2)) (x10
+ *     at ratio 0); NFE += 6 nfe_per_eval.
+ *   INIT0 (S = 1, k = {f0}): d0 = rms(y0 / scale), d1 = rms(f0 / scale), scale = atol + |y0| rtol -> H0 = d0 < 1e-5 || d1 < 1e-5 ?
+ *     1e-6 : 0.01 d0 / d1 (fp32); NFE += nfe_per_eval.
+ *   INIT1 (S = 2, k = {f0, f1}): d2 = rms((f1 - f0) / scale) / H0 -> DT = min(100 H0, (0.01 / max(d1, d2))^1/5) (1e-3 H0, at least
+ *     1e-6, when both are <= 1e-15); NFE += nfe_per_eval. */
+enum { VBX_ODE_NORM_ERROR = 0, VBX_ODE_NORM_INIT0 = 1, VBX_ODE_NORM_INIT1 = 2 };
+enum { VBX_ODE_CTRL_STEP = 0, VBX_ODE_CTRL_INIT0 = 1, VBX_ODE_CTRL_INIT1 = 2 };
+long vbx_ode_norm_slab_doubles(long n);
+int vbx_ode_norm(double* state, double* slab, int mode, const float* y0, const float* y1, const float* const* k, const float* c, int S,
+                 long n, int nfe_per_eval, void* stream);
+/* after an attempt: if LAST && !DONE, y <- y1 and k1 <- k7 (first-same-as-last); the last accepted step stays for vbx_ode_dense */
+int vbx_ode_commit(float* y, float* k1, const float* y1, const float* k7, const double* state, long n, void* stream);
+/* dense output at TEND inside the last accepted step [T0, T1] (torchdiffeq _interp_fit / _interp_evaluate): y_mid = y0 + sum_j
+ * (mid_j DT32) k_j, then the quartic through y0, y_mid, y1 with slopes DT32 k1 and DT32 k7, at x = fp32((TEND - T0) / (T1 - T0));
+ * k = k1 .. k7, mid a HOST array of 7 fp32 */
+int vbx_ode_dense(float* out, const float* y0, const float* y1, const float* const* k, const float* mid, const double* state, long n,
+                  void* stream);
 /* Occupies `stream` with one idle wave for `us` microseconds (0 .. 10000).  The sampler integrates the two halves of a batch as two
  * graphs on two streams and starts the second one ~60 us late, so that different kernels of the two forwards overlap (attention
  * beside GEMMs) instead of the same ones: 16 intervals 81.7 -> 80.1 ms (tools/sample_offset.py). */
@@ -545,6 +595,7 @@ typedef struct {
   const float* ada_table;       /* inference only, or NULL: precomputed adaLN projections [2 * intervals][L][4 * D] (vbx_ada_select); */
   const int* ada_counter;       /* the forward then skips the time embedding and the projection GEMV and takes time point         */
   int ada_slot;                 /* 2 * ada_counter[0] + ada_slot of the table (`times` is not read)                              */
+  int ada_stride;               /* time points per interval of ada_table: row ada_stride * ada_counter[0] + ada_slot; 0 means 2 (midpoint) */
 } vbx_io;
 
 size_t vbx_model_wpack_bytes(const vbx_model* m);

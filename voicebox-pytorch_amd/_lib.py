@@ -100,6 +100,14 @@ _PROTOS = {
     "vbx_axpy_ctr": [P, P, P, P, I, P, L, P],
     "vbx_counter_add": [P, I, P],
     "vbx_ada_select": [P, I, I, I, P, P, I, P],
+    "vbx_ada_select_rows": [P, I, I, I, P, P, I, I, P],
+    "vbx_ode_combine": [P, P, P, I, P, I, P, I, I, L, P],
+    "vbx_ode_combine_dp": [P, P, P, P, I, P, I, L, P],
+    "vbx_ode_stage_time": [P, I, P, P, I, I, P],
+    "vbx_ode_stage_time_dp": [P, I, P, F, I, P],
+    "vbx_ode_norm": [P, P, I, P, P, P, P, I, L, I, P],
+    "vbx_ode_commit": [P, P, P, P, P, L, P],
+    "vbx_ode_dense": [P, P, P, P, P, P, L, P],
     "vbx_stream_delay": [F, P],
     "vbx_pack_weight": [P, I, I, P, P, I, I, I, I, P],
     "vbx_pack_bias": [P, I, P, I, I, I, P],
@@ -157,13 +165,15 @@ def lib():
     l.vbx_attn_q_prescale.restype = F
     l.vbx_adaln_dtemb_all_scratch_floats.argtypes = [I, I, I, I]
     l.vbx_adaln_dtemb_all_scratch_floats.restype = C.c_long
+    l.vbx_ode_norm_slab_doubles.argtypes = [L]
+    l.vbx_ode_norm_slab_doubles.restype = C.c_long
     _lib = l
     return l
 
 
 def exported_symbols():
     return sorted(_PROTOS) + ["vbx_last_error", "vbx_attn_bwd_scratch_bytes", "vbx_dropout_keep_scale", "vbx_attn_q_prescale",
-                              "vbx_adaln_dtemb_all_scratch_floats"]  # + the stage-level entries bound in engine.py
+                              "vbx_adaln_dtemb_all_scratch_floats", "vbx_ode_norm_slab_doubles"]  # + the stage-level entries bound in engine.py
 
 
 def ptr(t):

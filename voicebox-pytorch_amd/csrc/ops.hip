@@ -1155,9 +1155,9 @@ __global__ void ode_set_time_kernel(float* __restrict__ times, int B, const floa
 // ada[l][b][:] = table[2 * counter + slot][l][:] for every b: the adaLN projections of one ODE time point, precomputed for the whole
 // grid (every batch element of a sampling call shares the time, so the table has no batch axis); G = floats per layer (4 * D)
 __global__ void ada_select_kernel(float* __restrict__ ada, int L, int B, int G, const float* __restrict__ table,
-                                  const int* __restrict__ counter, int slot) {
+                                  const int* __restrict__ counter, int stride, int slot) {
   const long n4 = (long)L * G / 4;
-  const float4* src = reinterpret_cast<const float4*>(table + (long)(2 * counter[0] + slot) * L * G);
+  const float4* src = reinterpret_cast<const float4*>(table + (long)(stride * counter[0] + slot) * L * G);
   const int g4 = G / 4;
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
     const float4 v = src[i];
@@ -2007,7 +2007,16 @@ extern "C" int vbx_ode_set_time(float* times, int B, const float* table, const i
 }
 extern "C" int vbx_ada_select(float* ada, int L, int B, int G, const float* table, const int* counter, int slot, void* stream) {
   VBX_REQUIRE(ada && table && counter && L > 0 && B > 0 && G > 0 && G % 4 == 0 && (slot == 0 || slot == 1), "vbx_ada_select: bad args");
-  hipLaunchKernelGGL(ada_select_kernel, dim3(grid_for((long)L * G / 4, 256)), dim3(256), 0, ST, ada, L, B, G, table, counter, slot);
+  hipLaunchKernelGGL(ada_select_kernel, dim3(grid_for((long)L * G / 4, 256)), dim3(256), 0, ST, ada, L, B, G, table, counter, 2, slot);
+  VBX_LAUNCH_CHECK();
+  return 0;
+}
+extern "C" int vbx_ada_select_rows(float* ada, int L, int B, int G, const float* table, const int* counter, int stride, int slot,
+                                   void* stream) {
+  VBX_REQUIRE(ada && table && counter && L > 0 && B > 0 && G > 0 && G % 4 == 0 && stride >= 1 && slot >= 0 && slot < stride,
+              "vbx_ada_select_rows: bad args");
+  hipLaunchKernelGGL(ada_select_kernel, dim3(grid_for((long)L * G / 4, 256)), dim3(256), 0, ST, ada, L, B, G, table, counter, stride,
+                     slot);
   VBX_LAUNCH_CHECK();
   return 0;
 }

@@ -584,6 +584,9 @@ def is_probably_audio_from_shape(t):  # voicebox_pytorch.py:1119-1120
     return exists(t) and (t.ndim == 2 or (t.ndim == 3 and t.shape[1] == 1))
 
 
+ODE_METHODS = ("euler", "midpoint", "rk4", "dopri5")  # torchdiffeq methods the device solvers serve (solver.py)
+
+
 class ConditionalFlowMatcherWrapper(nn.Module):
     def __init__(self, voicebox, text_to_semantic=None, duration_predictor=None, sigma=0., ode_atol=1e-5, ode_rtol=1e-5,
                  use_torchode=False, torchdiffeq_ode_method='midpoint', torchode_method_klass=None, cond_drop_prob=0.):
@@ -603,14 +606,16 @@ class ConditionalFlowMatcherWrapper(nn.Module):
             assert self.condition_on_text, 'a duration predictor aligns phoneme ids for a text-conditioned VoiceBox'
         if use_torchode:
             raise NotImplementedError("the adaptive torchode/Tsit5 path is replaced by the built-in fixed-step midpoint solver")
-        if torchdiffeq_ode_method != 'midpoint':
-            raise NotImplementedError("only the fixed-grid midpoint method (the reference default) is built")
+        if torchdiffeq_ode_method not in ODE_METHODS:
+            raise NotImplementedError(f"torchdiffeq_ode_method={torchdiffeq_ode_method!r} is not built; the device solvers serve "
+                                      f"{', '.join(repr(m) for m in ODE_METHODS)}")
         self.text_to_semantic = None
         self.duration_predictor = duration_predictor  # a submodule, as in the reference (:1147): its weights are in state_dict()
         self.cond_drop_prob = cond_drop_prob
         self.use_torchode = False
-        self.odeint_kwargs = dict(atol=ode_atol, rtol=ode_rtol, method=torchdiffeq_ode_method)  # atol/rtol: unused by fixed grids
+        self.odeint_kwargs = dict(atol=ode_atol, rtol=ode_rtol, method=torchdiffeq_ode_method)  # atol/rtol: read by dopri5 only
         self._samplers = {}
+        self.last_sample_stats = None  # {"method", "nfe", "accepted", "rejected"} of the last sample() call
 
     @property
     def device(self):
@@ -627,9 +632,11 @@ class ConditionalFlowMatcherWrapper(nn.Module):
     def sample(self, *, cond=None, texts=None, text_token_ids=None, semantic_token_ids=None, phoneme_ids=None,
                cond_mask=None, steps=3, cond_scale=1., decode_to_audio=True, decode_to_codes=False,
                max_semantic_token_ids=2048, spec_decode=False, spec_decode_gamma=5, use_graph=True):
-        """voicebox_pytorch.py:1175-1330 with torchdiffeq's fixed-grid midpoint replaced by the built-in solver
-        (solver.py): `steps` time points on linspace(0,1,steps) -> 2*(steps-1) function evaluations."""
-        from .solver import MidpointSampler
+        """voicebox_pytorch.py:1175-1330 with torchdiffeq.odeint replaced by the built-in device solvers (solver.py), per
+        torchdiffeq_ode_method: 'midpoint' (the default), 'euler' and 'rk4' on the fixed grid linspace(0, 1, steps) -- 2, 1 and 4
+        function evaluations per interval -- or the adaptive 'dopri5' with ode_atol / ode_rtol (steps does not change its result).
+        Counts of the call: self.last_sample_stats."""
+        from .solver import Dopri5Sampler, MidpointSampler, RKSampler
 
         if is_probably_audio_from_shape(cond):
             raise NotImplementedError("raw-audio conditioning needs an audio codec (out of scope)")
@@ -669,7 +676,9 @@ class ConditionalFlowMatcherWrapper(nn.Module):
         y0 = torch.randn_like(cond) if y0 is None else y0.to(dev, torch.float32)
         B, N, _ = cond.shape
         T = cond_token_ids.shape[-1] if exists(cond_token_ids) else 0
-        key = (B, N, steps, bool(use_graph), T, float(cond_scale) != 1., precise_enabled())
+        method, guided = self.odeint_kwargs["method"], float(cond_scale) != 1.
+        atol, rtol = float(self.odeint_kwargs["atol"]), float(self.odeint_kwargs["rtol"])
+        key = (B, N, steps, bool(use_graph), T, guided, precise_enabled(), method) + ((atol, rtol) if method == "dopri5" else ())
         fp = self.voicebox.flat_params()
         # a re-flatten (.to(), dtype change) frees the buffer whose addresses the cached hipGraphs captured: drop them
         self._samplers = {k: s for k, s in self._samplers.items() if s.flat_gen == fp.flat_gen and s.eng.fp is fp}
@@ -677,9 +686,19 @@ class ConditionalFlowMatcherWrapper(nn.Module):
         if smp is None:
             if len(self._samplers) >= 2:
                 self._samplers.pop(next(iter(self._samplers)))
-            smp = MidpointSampler(self.voicebox, B, N, steps, use_graph=use_graph, tokens=T, guided=float(cond_scale) != 1.)
+            if method == "midpoint":
+                smp = MidpointSampler(self.voicebox, B, N, steps, use_graph=use_graph, tokens=T, guided=guided)
+            elif method == "dopri5":
+                smp = Dopri5Sampler(self.voicebox, B, N, steps, use_graph=use_graph, tokens=T, guided=guided, atol=atol, rtol=rtol)
+            else:
+                smp = RKSampler(self.voicebox, B, N, steps, method, use_graph=use_graph, tokens=T, guided=guided)
             self._samplers[key] = smp
-        return smp.run(y0, cond, cond_mask, cond_token_ids=cond_token_ids, cond_scale=float(cond_scale))
+        out = smp.run(y0, cond, cond_mask, cond_token_ids=cond_token_ids, cond_scale=float(cond_scale))
+        if method == "midpoint":
+            self.last_sample_stats = {"method": method, "nfe": smp.nfe, "accepted": steps - 1, "rejected": 0}
+        else:
+            self.last_sample_stats = smp.stats()
+        return out
 
     def forward(self, x1, *, mask=None, semantic_token_ids=None, phoneme_ids=None, cond=None, cond_mask=None,
                 input_sampling_rate=None):  # voicebox_pytorch.py:1332-1427

@@ -244,3 +244,228 @@ class MidpointSampler:
                     with self._cu_share():
                         self._interval()
         return self.y.clone()
+
+
+# ------------------------------------------------------------------------------------------------ euler / rk4 / dopri5
+# torchdiffeq.odeint's other methods (call site voicebox_pytorch.py:1295), restated in tests/ode_ref.py -- parity with the library
+# UNPINNED, as for midpoint (oracle/ref_loader.py).  Kernels: csrc/ode.hip (include/vbx.h "ODE solvers").
+import ctypes as _C
+
+# Fixed-grid explicit RK tableaus: (c, a, b) -- stage times t0 + c dt (c = 1: t1 itself), stage inputs y0 + dt sum_j a_ij k_j, step
+# dy = dt sum_j b_j k_j.  rk4 is torchdiffeq's 3/8 rule (rk4_alt_step_func), not the classic RK4.
+FIXED_TABLEAUS = {
+    "euler": ((0.0,), (), (1.0,)),
+    "rk4": ((0.0, 1 / 3, 2 / 3, 1.0), ((1 / 3,), (-1 / 3, 1.0), (1.0, -1.0, 1.0)), (0.125, 0.375, 0.375, 0.125)),
+}
+
+
+def fixed_grid_tables(method, steps):
+    """Host fp32 tables of a fixed-grid method on t = linspace(0, 1, steps): stage times [intervals * S] (t0 + dt * c; c = 1 is t1
+    itself) and coefficients [intervals * S, S]: per interval, rows 0 .. S-2 the stage inputs' dt * a_ij, row S-1 the step's dt * b_j."""
+    c, a, b = FIXED_TABLEAUS[method]
+    S = len(b)
+    t = torch.linspace(0, 1, steps)
+    t0, t1 = t[:-1], t[1:]
+    dt = t1 - t0
+    times = [t0 if ci == 0 else (t1 if ci == 1 else t0 + dt * ci) for ci in c]
+    rows = []
+    for coefs in list(a) + [b]:
+        r = torch.zeros(steps - 1, S)
+        for j, v in enumerate(coefs):
+            r[:, j] = dt * v
+        rows.append(r)
+    return torch.stack(times, dim=1).reshape(-1).contiguous(), torch.stack(rows, dim=1).reshape(-1, S).contiguous()
+
+
+def _f32(vals):
+    return [float(v) for v in torch.tensor(vals, dtype=torch.float64).float()]
+
+
+# torchdiffeq's Dormand-Prince-Shampine tableau (rk_common / dopri5), as the solver holds it: cast to the state's dtype (fp32)
+DP_ALPHA = _f32([1 / 5, 3 / 10, 4 / 5, 8 / 9, 1.0, 1.0])
+DP_BETA = [_f32(r) for r in ([1 / 5], [3 / 40, 9 / 40], [44 / 45, -56 / 15, 32 / 9],
+                             [19372 / 6561, -25360 / 2187, 64448 / 6561, -212 / 729],
+                             [9017 / 3168, -355 / 33, 46732 / 5247, 49 / 176, -5103 / 18656],
+                             [35 / 384, 0, 500 / 1113, 125 / 192, -2187 / 6784, 11 / 84])]
+DP_C_ERROR = _f32([35 / 384 - 1951 / 21600, 0, 500 / 1113 - 22642 / 50085, 125 / 192 - 451 / 720, -2187 / 6784 + 12231 / 42400,
+                   11 / 84 - 649 / 6300, -1. / 60.])
+DP_C_MID = _f32([6025192743 / 30085553152 / 2, 0, 51252292925 / 65400821598 / 2, -2691868925 / 45128329728 / 2,
+                 187940372067 / 1594534317056 / 2, -1776094331 / 19743644256 / 2, 11237099 / 235043384 / 2])
+
+# include/vbx.h: the dopri5 step state record and the ODE kernel modes
+(DP_T, DP_DT, DP_T0, DP_T1, DP_DT32, DP_RATIO, DP_H0, DP_D1, DP_NFE, DP_ACCEPTED, DP_REJECTED, DP_LAST, DP_DONE, DP_BAD, DP_ATOL,
+ DP_RTOL, DP_TEND) = range(17)
+DP_STATE = 20
+TIME_STAGE, TIME_END, TIME_PROBE = 1, 2, 3
+NORM_ERROR, NORM_INIT0, NORM_INIT1 = 0, 1, 2
+
+
+def _ptrs(ts):
+    return (_C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+
+
+def _floats(vals):
+    return (_C.c_float * len(vals))(*vals)
+
+
+class _SamplerEval:
+    """One function evaluation of the sampler into `out`: the forward, or under classifier-free guidance the conditioned and the
+    fully dropped forward mixed as null + (logits - null) * scale (forward_with_cond_scale, voicebox_pytorch.py:972-985)."""
+
+    def _eval(self, p, x, out, slot=0):
+        p.eng.dropout_active = False  # sampling is eval (:1268)
+        ada = (self.ada_tab, p.counter, slot, self.ada_stride) if self.ada_tab is not None else None
+        if not self.tokens:
+            p.eng.forward(x, p.cond, p.cmask, p.times, pred_out=out, ada=ada)
+            return
+        vb = self.vb
+        p.eng.forward(x, p.cond, p.cmask, p.times, pred_out=out, text=(p.ids, vb.null_cond_id, None, vb.null_cond), ada=ada)
+        if self.guided:
+            st, n = _lib.current_stream, out.numel()
+            p.eng.forward(x, p.cond, p.cmask, p.times, pred_out=p.f_null,
+                          text=(p.ids, vb.null_cond_id, p.drop_all, vb.null_cond), ada=ada)
+            _lib.call("vbx_axpy_dev", out, p.f_null, self.g_table, 0, p.f_diff, n, st())   # logits - null
+            _lib.call("vbx_axpy_dev", p.f_null, p.f_diff, self.g_table, 1, out, n, st())   # null + scale * diff
+
+
+class RKSampler(_SamplerEval, MidpointSampler):
+    """torchdiffeq's fixed-grid euler and rk4 (FixedGridODESolver: the grid is t = linspace(0, 1, steps), y1 = y0 + dy per interval)
+    on MidpointSampler's machinery: the concurrent half batches (split, per-part counters, _cu_share), one captured interval graph
+    replayed steps - 1 times, and the adaLN table -- here of every STAGE time, S per interval (vbx_io.ada_stride = S).  The stage
+    times and the coefficients dt * a_ij, dt * b_j are formed on the host in fp32 torch arithmetic (t0 + dt * c; c = 1 is t1 itself)
+    and live in device tables [intervals * S] / [intervals * S][S] indexed by the part's device counter."""
+
+    def __init__(self, voicebox, B, N, steps, method, use_graph=True, tokens=0, guided=False, split=None):
+        if method not in FIXED_TABLEAUS:
+            raise ValueError(f"RKSampler: no fixed-grid tableau {method!r} (have {sorted(FIXED_TABLEAUS)})")
+        super().__init__(voicebox, B, N, steps, use_graph=use_graph, tokens=tokens, guided=guided, split=split)
+        self.method = method
+        S = self.S = self.ada_stride = len(FIXED_TABLEAUS[method][2])
+        dev = self.y.device
+        t_table, c_table = fixed_grid_tables(method, steps)
+        self.t_table, self.c_table = t_table.to(dev), c_table.to(dev)
+        # stage derivatives: k1 is MidpointSampler's f, the stage inputs go to its ymid
+        ks = [self.f] + [torch.zeros_like(self.y) for _ in range(S - 1)]
+        for i, p in enumerate(self.parts):
+            sl = slice(i * p.B, (i + 1) * p.B)
+            p.k = [k[sl] for k in ks]
+        self.ks = ks
+        self.nfe = S * (steps - 1) * (2 if self.guided else 1)
+
+    def _interval_part(self, p):
+        st = _lib.current_stream
+        n = p.y.numel()
+        S = self.S
+        for s in range(S):
+            x = p.y
+            if s:
+                x = p.ymid
+                _lib.call("vbx_ode_combine", x, p.y, _ptrs(p.k[:s]), s, self.c_table, S, p.counter, S, s - 1, n, st())
+            if self.ada_tab is None:
+                _lib.call("vbx_ode_stage_time", p.times, p.B, self.t_table, p.counter, S, s, st())
+            self._eval(p, x, p.k[s], s)
+        _lib.call("vbx_ode_combine", p.y, p.y, _ptrs(p.k), S, self.c_table, S, p.counter, S, S - 1, n, st())
+        _lib.call("vbx_counter_add", p.counter, 1, st())
+
+    def stats(self):
+        return {"method": self.method, "nfe": self.nfe, "accepted": self.steps - 1, "rejected": 0}
+
+
+class Dopri5Sampler(_SamplerEval, MidpointSampler):
+    """torchdiffeq's adaptive dopri5 (RKAdaptiveStepsizeODESolver with the Dormand-Prince-Shampine tableau, FSAL, order 5), t from 0
+    to 1 with tolerances atol / rtol.  The RMS error norm couples the whole batch: ONE stream (split 1).  The stage times are not
+    known in advance, so every forward evaluates its own adaLN projections (no table).  The initial step (f0, the probe, h) runs
+    eagerly; one attempt -- 6 forwards, the stage combinations, the two-launch error norm with the controller and the commit -- is
+    captured as a graph (the first attempt runs eagerly and warms up every kernel).  The host replays it and reads the 160-byte
+    step state back after each attempt (one small synchronisation per 6 function evaluations) until t >= 1, then evaluates the
+    dense-output quartic of the last accepted step at t = 1 (steps are not clipped: the last one overshoots).  `steps` does not
+    change the result (only the final time point is returned)."""
+
+    def __init__(self, voicebox, B, N, steps, use_graph=True, tokens=0, guided=False, atol=1e-5, rtol=1e-5, max_attempts=10000):
+        super().__init__(voicebox, B, N, steps, use_graph=use_graph, tokens=tokens, guided=guided, split=1)
+        self.method = "dopri5"
+        self.use_ada_table = False
+        self.ada_stride = 0
+        self.atol, self.rtol, self.max_attempts = float(atol), float(rtol), int(max_attempts)
+        dev = self.y.device
+        self.ks = [self.f] + [torch.zeros_like(self.y) for _ in range(6)]  # k1 .. k7
+        self.y1 = torch.zeros_like(self.y)
+        self.out = torch.zeros_like(self.y)
+        self.state = torch.zeros(DP_STATE, dtype=torch.float64, device=dev)
+        self.slab = torch.zeros(_lib.lib().vbx_ode_norm_slab_doubles(self.y.numel()), dtype=torch.float64, device=dev)
+        self.mult = 2 if self.guided else 1
+        self.last_stats = None
+
+    def _attempt(self):
+        p, st, n = self.parts[0], _lib.current_stream, self.y.numel()
+        for i in range(6):
+            x = self.y1 if i == 5 else self.ymid  # the last stage input is the 5th-order solution y1 (c_sol == beta[-1])
+            _lib.call("vbx_ode_combine_dp", x, self.y, _ptrs(self.ks[:i + 1]), _floats(DP_BETA[i]), i + 1, self.state, DP_DT, n, st())
+            mode = TIME_END if DP_ALPHA[i] == 1.0 else TIME_STAGE
+            _lib.call("vbx_ode_stage_time_dp", p.times, self.B, self.state, DP_ALPHA[i], mode, st())
+            self._eval(p, x, self.ks[i + 1])
+        _lib.call("vbx_ode_norm", self.state, self.slab, NORM_ERROR, self.y, self.y1, _ptrs(self.ks), _floats(DP_C_ERROR), 7, n,
+                  self.mult, st())
+        _lib.call("vbx_ode_commit", self.y, self.ks[0], self.y1, self.ks[6], self.state, n, st())
+
+    def _initial(self):
+        """_select_initial_step: f0 = f(0, y0), d0 / d1, the probe f1 = f(h0, y0 + h0 f0), d2 -> the first dt."""
+        p, st, n = self.parts[0], _lib.current_stream, self.y.numel()
+        init = torch.zeros(DP_STATE, dtype=torch.float64)
+        init[DP_T], init[DP_TEND], init[DP_ATOL], init[DP_RTOL] = 0.0, 1.0, self.atol, self.rtol
+        self.state.copy_(init)
+        p.times.fill_(0.0)
+        self._eval(p, self.y, self.ks[0])
+        _lib.call("vbx_ode_norm", self.state, self.slab, NORM_INIT0, self.y, None, _ptrs(self.ks[:1]), None, 1, n, self.mult, st())
+        _lib.call("vbx_ode_combine_dp", self.ymid, self.y, _ptrs(self.ks[:1]), _floats([1.0]), 1, self.state, DP_H0, n, st())
+        _lib.call("vbx_ode_stage_time_dp", p.times, self.B, self.state, 0.0, TIME_PROBE, st())
+        self._eval(p, self.ymid, self.ks[1])
+        _lib.call("vbx_ode_norm", self.state, self.slab, NORM_INIT1, self.y, None, _ptrs(self.ks[:2]), None, 2, n, self.mult, st())
+
+    def _capture(self):
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            self._attempt()
+        self.graph = g
+
+    def run(self, y0, cond=None, cond_mask=None, cond_token_ids=None, cond_scale=1.0):
+        if cond is not None:
+            self.cond.copy_(cond)
+        if cond_mask is not None:
+            self.cmask.copy_(cond_mask.to(self.cmask.device))
+        else:
+            self.cmask.fill_(True)
+        if self.tokens:
+            self.ids.copy_(cond_token_ids.to(self.ids.device))
+        if self.guided:
+            self.g_table[1] = float(cond_scale)
+        self.eng.bind_params()
+        self.y.copy_(y0)
+        self._initial()
+        attempts = 0
+        while True:
+            if attempts:
+                s = self.state.tolist()  # the one synchronisation per attempt
+                if s[DP_BAD]:
+                    what = "non-finite values in the state or its error estimate" if s[DP_BAD] == 1 else "underflow in dt"
+                    raise RuntimeError(f"dopri5: {what} at t = {s[DP_T]!r} (dt {s[DP_DT]!r}, error ratio {s[DP_RATIO]!r})")
+                if s[DP_DONE]:
+                    break
+                if attempts >= self.max_attempts:
+                    raise RuntimeError(f"dopri5: {attempts} attempts (max_attempts) without reaching t = 1: t = {s[DP_T]!r}, "
+                                       f"dt = {s[DP_DT]!r}")
+            if self.use_graph and attempts:
+                if self.graph is None:
+                    self._capture()
+                self.graph.replay()
+            else:
+                self._attempt()
+            attempts += 1
+        _lib.call("vbx_ode_dense", self.out, self.y, self.y1, _ptrs(self.ks), _floats(DP_C_MID), self.state, self.y.numel(),
+                  _lib.current_stream())
+        self.last_stats = {"method": "dopri5", "nfe": int(s[DP_NFE]), "accepted": int(s[DP_ACCEPTED]), "rejected": int(s[DP_REJECTED])}
+        self.nfe = self.last_stats["nfe"]
+        return self.out.clone()
+
+    def stats(self):
+        return dict(self.last_stats)
