@@ -238,6 +238,39 @@ int vbx_pack_embed_input(const float* x, const float* cond, const uint8_t* cond_
 int vbx_pack_embed_input_text(const float* x, const float* cond, const uint8_t* cond_mask, const uint8_t* drop_mask,
                               const float* null_cond, const long* ids, int T, const float* table, int E, long null_id,
                               void* out_f16, void* out_bf16, int B, int N, int D, void* stream);
+/* Codec-latent models (vbx_model.Lc): the to_embed operand rows [ x' | cond_emb | cond' ] (fp16, + bf16 when out_bf16), width 2*D + E:
+ *   x'    = x . W^T + b                                                    x, cond fp32 [B*N, L];  W = proj_in.weight [D, L]
+ *   cond' = drop[b] ? null_cond : (cond_mask[row] ? 0 : cond . W^T + b)     (:1000-1006, :1035, :1043-1048; null_cond is D wide)
+ * One launch, both products on the matrix cores against one weight panel: w_f16 is the fp16 copy of W, [D, Kp] row-major with
+ * Kp = vbx_proj_in_kp(L) (= L + 1 rounded up to 32) and zeros in columns L .. Kp-1; bias / null_cond fp32.  The cond_emb columns are
+ * NOT written (vbx_embed_text_cols).  xc_bf16 (training, may be NULL): the operand of the weight gradient, bf16 [2*B*N, Kp] = x rows
+ * then cond rows, the cond rows that pass no gradient (cond_mask set, dropped sample) zeroed, column L = 1 on every row that counts:
+ * dY^T . xc with dY = [dx' ; dcond'] is [ d(proj_in.weight) | d(proj_in.bias) ] (vbx_proj_in_wgrad_reduce). */
+int vbx_proj_in_kp(int L);
+int vbx_proj_in_embed(const float* x, const float* cond, const void* w_f16, const float* bias, const uint8_t* cond_mask,
+                      const uint8_t* drop_mask, const float* null_cond, void* out_f16, void* out_bf16, void* xc_bf16, int B, int N,
+                      int L, int D, int E, void* stream);
+/* columns [col0, col0 + E) of the same rows (row stride ld): cond_emb as vbx_pack_embed_input_text computes it */
+int vbx_embed_text_cols(const uint8_t* drop_mask, const long* ids, int T, const float* table, int E, long null_id, void* out_f16,
+                        void* out_bf16, int B, int N, int col0, int ld, void* stream);
+/* split-K slabs [splits][D][Kp] of dY^T . xc  ->  dw fp32 [D, L], db fp32 [D] */
+int vbx_proj_in_wgrad_reduce(const float* slabs, int splits, int D, int L, float* dw, float* db, void* stream);
+/* vbx_masked_mse_fwd / _bwd with the prediction (and d(pred), bf16, pad columns zeroed) in rows of ldp >= D floats, any D */
+int vbx_masked_mse_fwd_ld(const float* pred, int ldp, const float* target, const uint8_t* loss_mask, float* per_b, float* loss, int B,
+                          int N, int D, void* stream);
+int vbx_masked_mse_bwd_ld(const float* pred, int ldp, const float* target, const uint8_t* loss_mask, const float* per_b,
+                          const float* gscale, void* dpred_bf16, int B, int N, int D, void* stream);
+/* dst [rows, cols] = src[:, 0:cols] (row stride ld_src) */
+int vbx_copy_cols_f32(const float* src, int ld_src, float* dst, long rows, int cols, void* stream);
+/* Log-mel front end (LogMelCodec.encode; the arithmetic of MelVoco.encode, voicebox_pytorch.py:518-541, torchaudio defaults):
+ * out fp32 [B, 1 + T / hop, n_mels] from audio fp32 [B, T], T > n_fft / 2: centred frames with reflect padding, times window[n_fft]
+ * (the periodic Hann window of win_length samples centred in n_fft, zeros around it), fp32 FFT in the LDS (n_fft a power of two in
+ * 256 .. 2048; tw_re / tw_im [n_fft / 2] = cos / -sin(2 pi k / n_fft), built in fp64), power spectrum, mel filter m = the run of
+ * fb_len[m] weights fb_w[fb_off[m] ..] over the bins from fb_start[m] (fb_start[m] + fb_len[m] <= n_fft / 2 + 1), then
+ * 10 log10(max(., 1e-10)) when log_out.  One launch. */
+int vbx_logmel(const float* audio, float* out, const float* window, const float* tw_re, const float* tw_im, const int* fb_start,
+               const int* fb_len, const int* fb_off, const float* fb_w, int B, long T, int n_fft, int hop, int n_mels, int log_out,
+               void* stream);
 /* the same rows unrounded (fp32 [B*N, 2*D + E]): precise mode's to_embed operand */
 int vbx_embed_input_text_f32(const float* x, const float* cond, const uint8_t* cond_mask, const uint8_t* drop_mask,
                              const float* null_cond, const long* ids, int T, const float* table, int E, long null_id,
@@ -514,7 +547,8 @@ int vbx_clip_coef(const float* sumsq, float max_norm, float inv_world, float* co
  * bf16 weight arena and the activation arena (sizes from the *_bytes queries). */
 enum { VBX_P_SINW = 0, VBX_P_T1W, VBX_P_T1B, VBX_P_EMBW, VBX_P_EMBB, VBX_P_CONVW, VBX_P_CONVB, VBX_P_REG, VBX_P_FNG,
        VBX_P_PREDW,
-       VBX_P_CEMB /* to_cond_emb.weight [num_cond_tokens + 1, E], read only when vbx_model.E > 0 */, VBX_NG };
+       VBX_P_CEMB /* to_cond_emb.weight [num_cond_tokens + 1, E], read only when vbx_model.E > 0 */,
+       VBX_P_PINW /* proj_in.weight [D, Lc] and */, VBX_P_PINB /* proj_in.bias [D], read only when vbx_model.Lc > 0 */, VBX_NG };
 /* per layer; the four adaLN weights, and the four adaLN biases, must be contiguous in this order; so must the GateLoop
  * post-LayerNorm weight and bias (GLLNW, GLLNB).  The four GL* slots are read only when vbx_model.gateloop != 0. */
 enum { VBX_L_G1W = 0, VBX_L_B1W, VBX_L_G2W, VBX_L_B2W, VBX_L_G1B, VBX_L_B1B, VBX_L_G2B, VBX_L_B2B, VBX_L_QG, VBX_L_KG,
@@ -570,6 +604,12 @@ typedef struct {
                              stored, one float per block -- the gradient norm then needs no second pass over those tensors (their
                              flat ranges: vbx_model_sq_partials).  Meaningful only when the norm is taken over THIS backward's
                              gradient (no accumulation, no exchange in between). */
+  int Lc;                 /* latent_dim of a codec-latent model whose latent width differs from D (VoiceBox(audio_enc_dec = codec),
+                             voicebox_pytorch.py:911-914, 964-966, 1000-1006), 0 = none.  x / cond / target / pred are Lc wide (8 .. 1024,
+                             any value); proj_in = Linear(Lc, D) at VBX_P_PINW / VBX_P_PINB is applied to x and to cond by
+                             vbx_proj_in_embed, to_embed is Linear(2*D + E, D), to_pred Linear(D, Lc), null_cond is D wide.  Din must be
+                             0 or D.  Operand copies are zero-padded inside the arenas (proj_in K to vbx_proj_in_kp(Lc), to_pred N to a
+                             multiple of 8).  Not served by precise mode. */
 } vbx_model;
 
 typedef struct {

@@ -56,6 +56,14 @@ _PROTOS = {
     "vbx_pack_embed_input": [P, P, P, P, P, I, I, I, P],
     "vbx_pack_embed_input_text": [P, P, P, P, P, P, I, P, I, L, P, P, I, I, I, P],
     "vbx_cond_emb_bwd": [P, I, P, I, P, L, P, I, I, I, P],
+    "vbx_proj_in_kp": [I],
+    "vbx_proj_in_embed": [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, P],
+    "vbx_embed_text_cols": [P, P, I, P, I, L, P, P, I, I, I, I, P],
+    "vbx_proj_in_wgrad_reduce": [P, I, I, I, P, P, P],
+    "vbx_masked_mse_fwd_ld": [P, I, P, P, P, P, I, I, I, P],
+    "vbx_masked_mse_bwd_ld": [P, I, P, P, P, P, P, I, I, I, P],
+    "vbx_copy_cols_f32": [P, I, P, L, I, P],
+    "vbx_logmel": [P, P, P, P, P, P, P, P, P, I, L, I, I, I, I, P],
     "vbx_pack_phoneme_input": [P, P, I, P, I, P, P, P, P, I, I, I, P],
     "vbx_rowdot": [P, P, P, P, L, I, P],
     "vbx_stack_input": [P, P, P, I, I, I, I, P],

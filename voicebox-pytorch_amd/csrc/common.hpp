@@ -64,6 +64,19 @@ VBX_DEV float f16_to_f32(u16 v) { return (float)__builtin_bit_cast(_Float16, v);
 VBX_DEV unsigned pack_f16x2(float lo, float hi) { return (unsigned)f32_to_f16(lo) | ((unsigned)f32_to_f16(hi) << 16); }
 VBX_DEV unsigned pack_f16x2_sat(float lo, float hi) { return (unsigned)f32_to_f16_sat(lo) | ((unsigned)f32_to_f16_sat(hi) << 16); }
 
+// frame n of N -> the two of T source tokens and their weight: F.interpolate(..., mode='bilinear', align_corners=False) along one
+// axis (interpolate_1d, voicebox_pytorch.py:89-107): src = max(T/N * (n + 0.5) - 0.5, 0); i0 = floor(src); i1 = i0 + (i0 < T-1)
+VBX_DEV void interp_src(int n, int N, int T, int& i0, int& i1, float& lam) {
+  if (T == N) { i0 = i1 = n; lam = 0.f; return; }
+  const float scale = (float)T / (float)N;
+  float src = scale * ((float)n + 0.5f) - 0.5f;
+  src = src < 0.f ? 0.f : src;
+  i0 = (int)src;
+  if (i0 > T - 1) i0 = T - 1;
+  i1 = i0 + (i0 < T - 1 ? 1 : 0);
+  lam = src - (float)i0;
+}
+
 // Start-phase stagger (experiment, VBX_GEMM_STAGGER=<us>): workgroups that become co-resident on a CU at launch run their
 // k-loops and their epilogues in lockstep -- the matrix pipes idle while every CU stores and the memory system idles while every
 // CU multiplies (tools/native/gemm_trace.cpp).  Delaying the workgroups of launch slot s (blockIdx / #CUs) by s * ticks (100 MHz

@@ -59,16 +59,7 @@ __global__ void pack_embed_kernel(const float* __restrict__ x, const float* __re
 // cond_emb = to_cond_emb(where(drop[b], null_id, ids))  resized from T tokens to N frames (:1050-1066); the resize is
 // F.interpolate(..., mode='bilinear', align_corners=False) over the frame axis (interpolate_1d, :89-107):
 //   src = max(T/N * (n + 0.5) - 0.5, 0);  i0 = floor(src);  i1 = i0 + (i0 < T-1);  lam = src - i0;  (1-lam) e[i0] + lam e[i1]
-VBX_DEV void interp_src(int n, int N, int T, int& i0, int& i1, float& lam) {
-  if (T == N) { i0 = i1 = n; lam = 0.f; return; }
-  const float scale = (float)T / (float)N;
-  float src = scale * ((float)n + 0.5f) - 0.5f;
-  src = src < 0.f ? 0.f : src;
-  i0 = (int)src;
-  if (i0 > T - 1) i0 = T - 1;
-  i1 = i0 + (i0 < T - 1 ? 1 : 0);
-  lam = src - (float)i0;
-}
+// (interp_src: common.hpp)
 __global__ void pack_embed_text_kernel(const float* __restrict__ x, const float* __restrict__ cond, const uint8_t* __restrict__ cmask,
                                        const uint8_t* __restrict__ drop, const float* __restrict__ null_cond,
                                        const long* __restrict__ ids, int T, const float* __restrict__ table, int E, long null_id,

@@ -37,6 +37,9 @@ struct Carver {
 
 struct Dims {
   int B, N, R, Np, D, H, I, F, Fp, Th, L, ks, J, E, Ke, Din;  // Din = data width (dim_in), Ke = to_embed input width 2*Din + E
+  // codec-latent models (vbx_model.Lc): Lc = latent width, Kp = padded K of proj_in; Do = width of target / pred (Lc, else Din),
+  // Dop = Do rounded up to 8 (rows of the to_pred operand copy, row stride of the prediction inside the arena)
+  int Lc, Kp, Do, Dop;
   long M, M0;
 };
 Dims dims_of(const vbx_model* m) {
@@ -44,6 +47,8 @@ Dims dims_of(const vbx_model* m) {
   d.B = m->B; d.N = m->N; d.R = m->R; d.Np = m->N + m->R; d.D = m->D; d.H = m->H; d.I = m->H * 64;
   d.Din = m->Din > 0 ? m->Din : m->D;
   d.E = m->E; d.Ke = 2 * d.Din + m->E;
+  d.Lc = m->Lc; d.Kp = d.Lc ? vbx_proj_in_kp(d.Lc) : 0;
+  d.Do = d.Lc ? d.Lc : d.Din; d.Dop = (d.Do + 7) / 8 * 8;
   d.F = m->F; d.Fp = ((m->F + 63) / 64) * 64; d.Th = m->Th; d.L = m->L; d.ks = m->ksize; d.J = m->L * 4 * m->D;
   d.M = (long)d.B * d.Np; d.M0 = (long)d.B * d.N;
   return d;
@@ -56,7 +61,8 @@ struct WLayer {
   float* b1;
 };
 struct WPack {
-  u16 *embh, *embb, *pred, *predh, *adah;  // embb: bf16 copy of to_embed (dgrad into cond_emb, text-conditioned models only)
+  u16 *embh, *embb, *pred, *predh, *adah;  // embb: bf16 copy of to_embed (dgrad into cond_emb / into proj_in: text / codec models only)
+  u16* pinh = nullptr;                     // fp16 copy of proj_in.weight [D, Kp], zero-padded (codec-latent models)
   float* bada;
   std::vector<WLayer> layer;
   size_t bytes;
@@ -65,9 +71,10 @@ void carve_wpack(const vbx_model* m, WPack& w) {
   const Dims d = dims_of(m);
   Carver c(m->wpack);
   w.embh = c.take<u16>((size_t)d.D * d.Ke);
-  w.embb = d.E ? c.take<u16>((size_t)d.D * d.Ke) : nullptr;
-  w.pred = c.take<u16>((size_t)d.Din * d.D);
-  w.predh = c.take<u16>((size_t)d.Din * d.D);
+  w.embb = (d.E || d.Lc) ? c.take<u16>((size_t)d.D * d.Ke) : nullptr;
+  w.pred = c.take<u16>((size_t)d.Dop * d.D);
+  w.predh = c.take<u16>((size_t)d.Dop * d.D);
+  if (d.Lc) w.pinh = c.take<u16>((size_t)d.D * d.Kp);
   w.adah = c.take<u16>((size_t)d.J * d.Th);
   w.bada = c.take<float>(d.J);
   w.layer.resize(d.L);
@@ -101,6 +108,7 @@ struct ALayer {
 };
 struct Acts {
   u16 *embed_in, *embed_inh;
+  u16 *xcb = nullptr, *dxc = nullptr;  // codec-latent models, training: bf16 [2 M0, Kp] operand / [2 M0, D] gradient of proj_in
   float *e, *four, *pre, *temb, *ada;
   std::vector<float*> xs;  // residual snapshots
   // u-net skip connections (vbx_model.unet): xc[l] = combined input of layer l >= L/2, cat16 / catb = the combiner's [M, 2D] operand
@@ -256,7 +264,7 @@ void carve_acts(const vbx_model* m, Acts& a) {
   }
   a.hf = tr ? c.take<u16>((size_t)d.M0 * d.D) : nullptr;
   a.hfh = c.take<u16>((size_t)d.M0 * d.D);
-  a.pred = c.take<float>((size_t)d.M0 * d.Din);
+  a.pred = c.take<float>((size_t)d.M0 * d.Dop);
   a.per_b = c.take<float>(vbx_masked_mse_scratch_floats(d.B));
   if (tr) {
     a.dx = c.take<float>((size_t)d.M * d.D);
@@ -277,7 +285,8 @@ void carve_acts(const vbx_model* m, Acts& a) {
       if (n > sf) sf = n;
     };
     upd(3 * d.I, d.D, d.M); upd(d.D, d.I, d.M); upd(2 * d.Fp, d.D, d.M); upd(d.D, d.Fp, d.M);
-    upd(d.D, d.Ke, d.M0); upd(d.Din, d.D, d.M0);
+    upd(d.D, d.Ke, d.M0); upd(d.Dop, d.D, d.M0);
+    if (d.Lc) upd(d.D, d.Kp, 2 * d.M0);
     if (m->gateloop) upd(3 * d.D, d.D, d.M);
     if (m->unet) upd(d.D, 2 * d.D, d.M);
     a.slab_floats = sf;
@@ -310,12 +319,16 @@ void carve_acts(const vbx_model* m, Acts& a) {
     a.dpre = c.take<float>((size_t)d.M0 * d.D);
     a.de = c.take<float>((size_t)d.M0 * d.D);
     a.deb = c.take<u16>((size_t)d.M0 * d.D);
-    a.dpb = c.take<u16>((size_t)d.M0 * d.Din);
+    a.dpb = c.take<u16>((size_t)d.M0 * d.Dop);
     a.wpart = c.take<float>((size_t)vbx_convpos_bwd_chunks(d.B, d.N) * d.D * 64);
     a.tscratch = c.take<float>((size_t)vbx_time_embed_bwd_scratch_floats(d.B, d.D));
     a.gl_ds = m->gateloop ? c.take<float>((size_t)d.M * d.D) : nullptr;
     a.gl_dp = m->gateloop ? c.take<u16>((size_t)d.M * 3 * d.D) : nullptr;
     a.demb = d.E ? c.take<u16>((size_t)d.M0 * d.E) : nullptr;
+    if (d.Lc) {
+      a.xcb = c.take<u16>((size_t)2 * d.M0 * d.Kp);
+      a.dxc = c.take<u16>((size_t)2 * d.M0 * d.D);
+    }
     a.dxb2 = c.take<u16>((size_t)d.M * d.D);  // always carved: the arena layout must not depend on run-time tuning knobs
     a.attn_scratch = c.take<char>(vbx_attn_bwd_scratch_bytes(d.B, d.H, d.Np));
     if (m->unet) {
@@ -387,6 +400,9 @@ int check_model(const vbx_model* m) {
   }
   VBX_REQUIRE(!m->plain_norm || m->stack_only, "vbx_model: plain_norm is only used by the standalone stack (VoiceBox is adaptive)");
   VBX_REQUIRE(m->Din >= 0 && m->Din % 8 == 0 && (m->Din == 0 || !m->stack_only), "vbx_model: dim_in must be a multiple of 8 (got %d)", m->Din);
+  VBX_REQUIRE(m->Lc == 0 || (m->Lc >= 8 && m->Lc <= 1024 && !m->stack_only && (m->Din == 0 || m->Din == m->D)),
+              "vbx_model: latent_dim must be in 8 .. 1024 and dim_in equal to dim (got latent_dim %d, dim_in %d)", m->Lc, m->Din);
+  VBX_REQUIRE(!(m->Lc && m->precise), "vbx_model: precise mode does not serve codec-latent models (proj_in)");
   VBX_REQUIRE(m->attn_dropout >= 0.f && m->attn_dropout < 1.f && m->ff_dropout >= 0.f && m->ff_dropout < 1.f, "vbx_model: dropout must be in [0, 1)");
   VBX_REQUIRE(!m->unet || (m->stack_only && m->L % 2 == 0 && !m->precise),
               "vbx_model: u-net skip connections belong to the standalone stack (even depth); VoiceBox never enables them");
@@ -533,7 +549,8 @@ extern "C" int vbx_model_pack_weights(const vbx_model* m, void* stream) {
   const long* G = m->off;
   if (!m->stack_only) {
     CK(vbx_pack_weight(P + G[VBX_P_EMBW], d.D, d.Ke, w.embb, w.embh, d.D, d.Ke, 0, 0, stream));
-    CK(vbx_pack_weight(P + G[VBX_P_PREDW], d.Din, d.D, w.pred, w.predh, d.Din, d.D, 0, 0, stream));
+    CK(vbx_pack_weight(P + G[VBX_P_PREDW], d.Do, d.D, w.pred, w.predh, d.Dop, d.D, 0, 0, stream));
+    if (d.Lc) CK(vbx_pack_weight(P + G[VBX_P_PINW], d.D, d.Lc, nullptr, w.pinh, d.D, d.Kp, 0, 0, stream));
   }
   for (int l = 0; l < d.L; l++) {
     const long* o = m->off + VBX_NG + (long)l * VBX_NL;
@@ -628,7 +645,16 @@ extern "C" int vbx_model_forward(const vbx_model* m, const vbx_io* io, void* str
     return VBX_EINVAL;
   }
   // to_embed(cat(x, cond * ~cond_mask))   (voicebox_pytorch.py:1035,1075-1078)
-  if (d.E) {
+  if (d.Lc) {
+    // proj_in on x and on cond, cond mask / CFG drop / null_cond in its epilogue, straight into the to_embed operand   (:1000-1048)
+    CK(vbx_proj_in_embed(io->x, io->cond, w.pinh, P + G[VBX_P_PINB], io->cond_mask, io->drop_mask, io->null_cond, a.embed_inh,
+                         a.embed_in, a.xcb, d.B, d.N, d.Lc, d.D, d.E, stream));
+    if (d.E) {
+      VBX_REQUIRE(io->cond_ids && io->T > 0, "vbx_model_forward: a text-conditioned model needs cond_ids");
+      CK(vbx_embed_text_cols(io->drop_mask, io->cond_ids, io->T, P + G[VBX_P_CEMB], d.E, io->null_id, a.embed_inh, a.embed_in, d.B,
+                             d.N, d.D, d.Ke, stream));
+    }
+  } else if (d.E) {
     VBX_REQUIRE(io->cond_ids && io->T > 0, "vbx_model_forward: a text-conditioned model needs cond_ids");
     CK(vbx_pack_embed_input_text(io->x, io->cond, io->cond_mask, io->drop_mask, io->null_cond, io->cond_ids, io->T,
                                  P + G[VBX_P_CEMB], d.E, io->null_id, a.embed_inh, a.embed_in, d.B, d.N, d.Din, stream));
@@ -710,9 +736,15 @@ extern "C" int vbx_model_forward(const vbx_model* m, const vbx_io* io, void* str
                                stream);
   // strip registers, final RMSNorm, to_pred   (:476-479, :1092)
   CK(vbx_rmsnorm_fwd(a.xs[(m->gateloop ? 3 : 2) * d.L], P + G[VBX_P_FNG], nullptr, 0, a.hf, a.hfh, d.B, d.Np, d.R, d.N, d.D, stream));
+  if (d.Dop != d.Do) {  // a latent width that is not a multiple of 8: the product lands in padded rows of the arena
+    CK(gemm_nt(a.hfh, d.D, w.predh, d.D, (int)d.M0, d.Dop, d.D, VBX_EPI_F32, a.pred, d.Dop, nullptr, nullptr, nullptr, nullptr, st));
+    if (io->pred) CK(vbx_copy_cols_f32(a.pred, d.Dop, io->pred, d.M0, d.Do, stream));
+    if (io->target) CK(vbx_masked_mse_fwd_ld(a.pred, d.Dop, io->target, io->loss_mask, a.per_b, io->loss, d.B, d.N, d.Do, stream));
+    return 0;
+  }
   float* pred = io->pred ? io->pred : a.pred;
-  CK(gemm_nt(a.hfh, d.D, w.predh, d.D, (int)d.M0, d.Din, d.D, VBX_EPI_F32, pred, d.Din, nullptr, nullptr, nullptr, nullptr, st));
-  if (io->target) CK(vbx_masked_mse_fwd(pred, io->target, io->loss_mask, a.per_b, io->loss, d.B, d.N, d.Din, stream));
+  CK(gemm_nt(a.hfh, d.D, w.predh, d.D, (int)d.M0, d.Do, d.D, VBX_EPI_F32, pred, d.Do, nullptr, nullptr, nullptr, nullptr, st));
+  if (io->target) CK(vbx_masked_mse_fwd(pred, io->target, io->loss_mask, a.per_b, io->loss, d.B, d.N, d.Do, stream));
   return 0;
 }
 
@@ -734,9 +766,12 @@ static int backward_head_impl(const vbx_model* m, const vbx_io* io, const float*
     CK(vbx_pack_weight(io->target, (int)d.M0, d.D, a.dhn, nullptr, (int)d.M0, d.D, 0, 0, stream));
   } else {
     const float* pred = io->pred ? io->pred : a.pred;
-    CK(vbx_masked_mse_bwd(pred, io->target, io->loss_mask, a.per_b, gscale, nullptr, a.dpb, d.B, d.N, d.Din, stream));
-    CK(wgrad(a.dpb, d.Din, a.hf, d.D, d.Din, d.D, d.M0, a.slabs, Gd + G[VBX_P_PREDW], d.Din, d.D, 0, 0, st));
-    CK(gemm_nn_bf16(a.dpb, d.Din, w.pred, d.D, (int)d.M0, d.D, d.Din, a.dhn, d.D, st));
+    if (d.Dop != d.Do)
+      CK(vbx_masked_mse_bwd_ld(a.pred, d.Dop, io->target, io->loss_mask, a.per_b, gscale, a.dpb, d.B, d.N, d.Do, stream));
+    else
+      CK(vbx_masked_mse_bwd(pred, io->target, io->loss_mask, a.per_b, gscale, nullptr, a.dpb, d.B, d.N, d.Do, stream));
+    CK(wgrad(a.dpb, d.Dop, a.hf, d.D, d.Dop, d.D, d.M0, a.slabs, Gd + G[VBX_P_PREDW], d.Do, d.D, 0, 0, st));
+    CK(gemm_nn_bf16(a.dpb, d.Dop, w.pred, d.D, (int)d.M0, d.D, d.Dop, a.dhn, d.D, st));
   }
   // gradient wrt the last residual snapshot: zero at the register rows, final-norm backward elsewhere
   if (hipMemsetAsync(a.dx, 0, (size_t)d.M * d.D * sizeof(float), st) != hipSuccess ||
@@ -1072,6 +1107,20 @@ static int backward_embed_impl(const vbx_model* m, const vbx_io* io, void* strea
     }
     CK(vbx_cond_emb_bwd(a.demb, d.E, io->cond_ids, io->T, io->drop_mask, io->null_id, Gd + G[VBX_P_CEMB], d.B, d.N, d.E, stream));
   }
+  if (d.Lc) {
+    // d(x') and d(cond') = de . W_embed[:, 0:D] / [:, D+E:], stacked [2 M0, D]; the rows of cond that pass no gradient are zero in the
+    // packed operand a.xcb, whose column Lc carries the bias:  [ d(proj_in.weight) | d(proj_in.bias) ] = dxc^T . xcb   (:1000-1006)
+    WPack w;
+    carve_wpack(m, w);
+    CK(gemm_nn_bf16(a.deb, d.D, w.embb, d.Ke, (int)d.M0, d.D, d.D, a.dxc, d.D, st));
+    CK(gemm_nn_bf16(a.deb, d.D, w.embb + d.D + d.E, d.Ke, (int)d.M0, d.D, d.D, a.dxc + (size_t)d.M0 * d.D, d.D, st));
+    CK(wgrad_join(st));  // a.slabs: the to_embed weight gradient above may still be reading it on the side stream
+    vbx_gemm_desc g{};
+    g.mode = VBX_GEMM_TN; g.epilogue = VBX_EPI_SPLITK; g.M = d.D; g.N = d.Kp; g.K = (int)(2 * d.M0); g.lda = d.D; g.ldb = d.Kp;
+    g.A = a.dxc; g.B = a.xcb; g.C = a.slabs; g.splits = wgrad_splits(d.D, d.Kp, 2 * d.M0);
+    CK(vbx_gemm(&g, st));
+    CK(vbx_proj_in_wgrad_reduce(a.slabs, g.splits, d.D, d.Lc, Gd + G[VBX_P_PINW], Gd + G[VBX_P_PINB], stream));
+  }
   CK(vbx_colsum_f32(a.de, (int)d.M0, d.D, d.D, Gd + G[VBX_P_EMBB], a.cs_scratch, stream));
   CK(vbx_time_embed_bwd(io->times, P + G[VBX_P_SINW], P + G[VBX_P_T1W], a.four, a.pre, a.dtemb, Gd + G[VBX_P_SINW],
                         Gd + G[VBX_P_T1W], Gd + G[VBX_P_T1B], a.tscratch, d.B, d.D, d.Th, stream));
@@ -1114,7 +1163,8 @@ extern "C" int vbx_model_adam_segments(const vbx_model* m, long n_flat, vbx_adam
   };
   if (!m->stack_only) {
     add(G[VBX_P_EMBW], d.D, d.Ke, w.embb, w.embh, nullptr, d.Ke, 0, 0);
-    add(G[VBX_P_PREDW], d.Din, d.D, w.pred, w.predh, nullptr, d.D, 0, 0);
+    add(G[VBX_P_PREDW], d.Do, d.D, w.pred, w.predh, nullptr, d.D, 0, 0);
+    if (d.Lc) add(G[VBX_P_PINW], d.D, d.Lc, nullptr, w.pinh, nullptr, d.Kp, 0, 0);
   }
   for (int l = 0; l < d.L; l++) {
     const long* o = m->off + VBX_NG + (long)l * VBX_NL;

@@ -427,6 +427,7 @@ class TrainStep:
         vb, w = self.vb, self.wrapper
         dev = self.fp.flat.device
         st = _lib.current_stream
+        x1, _ = w.encode_raw_audio(x1)  # a wave batch of a codec model (voicebox_pytorch.py:1349-1371); latents pass through
         x1 = x1.to(dev, torch.float32).contiguous()
         B, N, _ = x1.shape
         if mask is not None:
@@ -551,7 +552,8 @@ class TrainStep:
                       float(self.betas[0]), float(self.betas[1]), float(self.eps), self.steps, self.coef, st())
 
     def step(self, x1, mask=None, lr=None, cond_token_ids=None):
-        """x1: (B_local, frames, dim) on this rank's GPU (cond_token_ids (B_local, tokens) for a text-conditioned model).
+        """x1: (B_local, frames, dim) on this rank's GPU, or a wave batch (B_local, samples) for a model built with audio_enc_dec
+        (cond_token_ids (B_local, tokens) for a text-conditioned model).
         Returns the (un-synchronised) local loss tensor."""
         # --- backward with overlapped gradient exchange
         factors = self.adaln_factors_apply(batch=int(x1.shape[0])) and os.environ.get("VBX_FUSED_ADAM", "1") != "0"

@@ -10,7 +10,7 @@ from . import _lib
 from ._lib import P, I, F
 
 # enum mirrors of include/vbx.h
-G_NAMES = ["SINW", "T1W", "T1B", "EMBW", "EMBB", "CONVW", "CONVB", "REG", "FNG", "PREDW", "CEMB"]
+G_NAMES = ["SINW", "T1W", "T1B", "EMBW", "EMBB", "CONVW", "CONVB", "REG", "FNG", "PREDW", "CEMB", "PINW", "PINB"]
 L_NAMES = ["G1W", "B1W", "G2W", "B2W", "G1B", "B1B", "G2B", "B2B", "QG", "KG", "QKVW", "OUTW", "FF1W", "FF1B", "FF2W", "FF2B",
            "GLG", "GLW", "GLLNW", "GLLNB", "N1G", "N2G", "SKW", "SKB"]
 NG, NL = len(G_NAMES), len(L_NAMES)
@@ -21,7 +21,7 @@ class VbxModel(C.Structure):
                 ("qk_norm", I), ("attn_scale", F), ("training", I), ("params", P), ("grads", P), ("off", P),
                 ("wpack", P), ("act", P), ("rot_cos", P), ("rot_sin", P), ("gateloop", I),
                 ("stack_only", I), ("E", I), ("V1", I), ("plain_norm", I), ("attn_dropout", F), ("ff_dropout", F), ("Din", I),
-                ("precise", I), ("wpack3", P), ("pscratch", P), ("unet", I), ("skip_scale", F), ("adaln_factors", I), ("defer_reduce", I), ("sq_partials", P)]
+                ("precise", I), ("wpack3", P), ("pscratch", P), ("unet", I), ("skip_scale", F), ("adaln_factors", I), ("defer_reduce", I), ("sq_partials", P), ("Lc", I)]
 
 
 class VbxIO(C.Structure):
@@ -146,7 +146,7 @@ class FlatParams:
         order = ["PREDW", "FNG"]
         for l in reversed(range(depth)):
             order += [f"L{l}.{n}" for n in L_NAMES if f"L{l}.{n}" in named_slots]
-        tail = ["EMBW", "EMBB", "CEMB", "CONVW", "CONVB", "REG", "SINW", "T1W", "T1B"]
+        tail = ["EMBW", "EMBB", "PINW", "PINB", "CEMB", "CONVW", "CONVB", "REG", "SINW", "T1W", "T1B"]
         order += tail
         self.order = [s for s in order if s in named_slots]
         self.slots = named_slots
@@ -254,7 +254,8 @@ class Engine:
         m.Din = int(cfg.get("Din", 0) or 0)  # data width (dim_in); 0 = D
         m.unet = 1 if cfg.get("unet") else 0
         m.skip_scale = float(cfg.get("skip_scale", 2 ** -0.5))
-        self.Din = m.Din or cfg["D"]
+        m.Lc = int(cfg.get("Lc", 0) or 0)  # latent width of a codec-latent model (proj_in); 0 = none
+        self.Din = m.Lc or m.Din or cfg["D"]  # width of x / cond / target / pred
         self.has_dropout = m.attn_dropout > 0. or m.ff_dropout > 0.
         self.dropout_active = False  # nn.Dropout semantics: the owning module sets this to its .training flag before a forward
         self.off_table = flat.offset_table()

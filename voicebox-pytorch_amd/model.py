@@ -398,8 +398,19 @@ class VoiceBox(nn.Module):
             'number of conditioning tokens must be specified (whether phonemes or semantic token ids) if training conditional voicebox'
         if condition_on_text and dim_cond_emb % 8 != 0:
             raise NotImplementedError("dim_cond_emb must be a multiple of 8 (16-byte GEMM rows)")
-        if exists(audio_enc_dec):
-            raise NotImplementedError("audio codecs are out of scope of the hot path: feed latents directly")
+        latent_dim = None
+        if exists(audio_enc_dec):  # any nn.Module with the AudioEncoderDecoder members (codec.py); inheritance is not required
+            missing = [n for n in ("encode", "decode", "latent_dim", "sampling_rate", "downsample_factor") if not hasattr(audio_enc_dec, n)]
+            if not isinstance(audio_enc_dec, nn.Module) or missing:
+                raise TypeError(f"audio_enc_dec must be an nn.Module with encode / decode / latent_dim / sampling_rate / "
+                                f"downsample_factor (missing: {missing})")
+            latent_dim = int(audio_enc_dec.latent_dim)
+            if latent_dim != dim:
+                if dim_in != dim:
+                    raise ValueError(f"dim_in ({dim_in}) must be None or dim ({dim}) when audio_enc_dec.latent_dim ({latent_dim}) differs "
+                                     "from dim: proj_in maps the latents to dim, and to_embed takes 2 * dim_in of them")
+                if not 8 <= latent_dim <= 1024:
+                    raise NotImplementedError(f"audio_enc_dec.latent_dim must be in 8 .. 1024 (got {latent_dim})")
         if dim_in % 8 != 0:  # data width of x / cond / target / pred (e.g. 80 mel bins into a dim-512 model, :905,938,964)
             raise NotImplementedError("dim_in must be a multiple of 8 (16-byte rows of the to_embed / to_pred operands)")
         if dim_head != 64:
@@ -408,8 +419,9 @@ class VoiceBox(nn.Module):
             raise NotImplementedError("dim must be a multiple of 64 (<= 2048) and heads even")
         if conv_pos_embed_kernel_size % 2 != 1 or not 1 <= conv_pos_embed_kernel_size <= 31:
             raise NotImplementedError("conv_pos_embed_kernel_size must be odd (as in the reference, :211) and <= 31")
-        self.audio_enc_dec = None
-        self.proj_in = nn.Identity()
+        self.audio_enc_dec = audio_enc_dec
+        codec_proj = exists(latent_dim) and latent_dim != dim  # voicebox_pytorch.py:911-914
+        self.proj_in = nn.Linear(latent_dim, dim) if codec_proj else nn.Identity()
         self.sinu_pos_emb = nn.Sequential(LearnedSinusoidalPosEmb(dim), nn.Linear(dim, time_hidden_dim), nn.SiLU())
         if not condition_on_text:  # voicebox_pytorch.py:922-926
             dim_cond_emb = 0
@@ -429,13 +441,14 @@ class VoiceBox(nn.Module):
                                        attn_qk_norm=attn_qk_norm, num_register_tokens=num_register_tokens,
                                        adaptive_rmsnorm=True, adaptive_rmsnorm_cond_dim_in=time_hidden_dim,
                                        use_gateloop_layers=use_gateloop_layers)
-        self.to_pred = nn.Linear(dim, dim_in, bias=False)
+        self.to_pred = nn.Linear(dim, latent_dim if exists(latent_dim) else dim_in, bias=False)  # :964-966
         self._cfg = dict(D=dim, H=heads, L=depth, F=int(dim * ff_mult * 2 / 3), Th=time_hidden_dim,
                          R=int(num_register_tokens), ksize=conv_pos_embed_kernel_size, qk_norm=bool(attn_qk_norm),
                          attn_scale=10.0 if attn_qk_norm else dim_head ** -0.5, theta=50000.0,
                          gateloop=bool(use_gateloop_layers), E=dim_cond_emb,
                          V1=(num_cond_tokens + 1) if condition_on_text else 0,
-                         attn_dropout=float(attn_dropout), ff_dropout=float(ff_dropout), Din=int(dim_in))
+                         attn_dropout=float(attn_dropout), ff_dropout=float(ff_dropout), Din=int(dim_in),
+                         Lc=int(latent_dim) if codec_proj else 0)
         self._flat = None
         self._engines = {}
 
@@ -449,6 +462,8 @@ class VoiceBox(nn.Module):
             s["REG"] = t.register_tokens
         if self.condition_on_text:
             s["CEMB"] = self.to_cond_emb.weight
+        if self._cfg["Lc"]:
+            s["PINW"], s["PINB"] = self.proj_in.weight, self.proj_in.bias
         t._layer_slots(s)
         return s
 
@@ -471,6 +486,9 @@ class VoiceBox(nn.Module):
             raise _lib.VbxError("VoiceBox compute runs only on an MI355X (gfx950) through libvbx_hip.so; "
                                 f"parameters are on '{dev}' and there is no CPU fallback")
         precise = precise_enabled()
+        if precise and self._cfg["Lc"]:
+            raise NotImplementedError("precise mode does not serve codec-latent models (audio_enc_dec with latent_dim != dim: the "
+                                      "proj_in product runs on the fast path only) -- leave precise mode to call them")
         # key[2] carries the mode: 0/1 = inference/training on the fast path, 2/3 = the same in precise mode (own arenas)
         tkey = int(bool(training)) + (2 if precise else 0)
         key = (B, N, tkey) if slot == 0 else (B, N, tkey, slot)
@@ -638,8 +656,11 @@ class ConditionalFlowMatcherWrapper(nn.Module):
         Counts of the call: self.last_sample_stats."""
         from .solver import Dopri5Sampler, MidpointSampler, RKSampler
 
-        if is_probably_audio_from_shape(cond):
-            raise NotImplementedError("raw-audio conditioning needs an audio codec (out of scope)")
+        codec = self.voicebox.audio_enc_dec
+        if is_probably_audio_from_shape(cond):  # :1192-1201
+            assert exists(codec), 'audio_enc_dec must be set on VoiceBox to condition on raw audio'
+            codec.eval()
+            cond = codec.encode(cond.to(self.device))
         num_cond_inputs = sum(map(exists, (texts, text_token_ids, semantic_token_ids, phoneme_ids)))
         assert num_cond_inputs <= 1
         cond_token_ids = None
@@ -662,8 +683,10 @@ class ConditionalFlowMatcherWrapper(nn.Module):
             if exists(cond):  # curtail_or_pad(cond, cond_target_length) (:109-119, :1253)
                 n = cond.shape[-2]
                 cond = cond[..., :target_len, :] if n > target_len else torch.nn.functional.pad(cond, (0, 0, 0, target_len - n))
-            else:
-                raise NotImplementedError("cond = None needs audio_enc_dec.latent_dim (codecs are out of scope): pass cond")
+            else:  # :1258-1259
+                if not exists(codec):
+                    raise NotImplementedError("cond = None needs audio_enc_dec.latent_dim: build VoiceBox with audio_enc_dec, or pass cond")
+                cond = torch.zeros((cond_token_ids.shape[0], target_len, codec.latent_dim), device=dev)
         else:
             assert num_cond_inputs == 0, 'no conditioning inputs should be given if not conditioning on text'
             if cond_scale != 1.:
@@ -698,12 +721,34 @@ class ConditionalFlowMatcherWrapper(nn.Module):
             self.last_sample_stats = {"method": method, "nfe": smp.nfe, "accepted": steps - 1, "rejected": 0}
         else:
             self.last_sample_stats = smp.stats()
-        return out
+        if decode_to_codes and exists(codec):  # :1324-1330
+            return codec.decode_to_codes(out)
+        if not decode_to_audio or not exists(codec):
+            return out
+        return codec.decode(out)
+
+    def encode_raw_audio(self, x1, cond=None, input_sampling_rate=None):
+        """voicebox_pytorch.py:1349-1371: a 2-D tensor, or a 3-D one with a middle dimension of 1, is a wave -- encoded by the codec
+        (in eval mode, without gradients).  Latents pass through."""
+        in_raw, cond_raw = is_probably_audio_from_shape(x1), is_probably_audio_from_shape(cond)
+        if not (in_raw or cond_raw):
+            return x1, cond
+        codec = self.voicebox.audio_enc_dec
+        assert exists(codec), 'audio_enc_dec must be set on VoiceBox to train directly on raw audio'
+        if exists(input_sampling_rate) and input_sampling_rate != codec.sampling_rate:
+            raise NotImplementedError(f"input_sampling_rate {input_sampling_rate} differs from the codec's {codec.sampling_rate}: "
+                                      "resampling is not built, resample the waves first")
+        with torch.no_grad():
+            codec.eval()
+            if in_raw:
+                x1 = codec.encode(x1.to(self.device))
+            if cond_raw:
+                cond = codec.encode(cond.to(self.device))
+        return x1, cond
 
     def forward(self, x1, *, mask=None, semantic_token_ids=None, phoneme_ids=None, cond=None, cond_mask=None,
                 input_sampling_rate=None):  # voicebox_pytorch.py:1332-1427
-        if is_probably_audio_from_shape(x1) or is_probably_audio_from_shape(cond):
-            assert exists(self.voicebox.audio_enc_dec), 'audio_enc_dec must be set on VoiceBox to train directly on raw audio'
+        x1, cond = self.encode_raw_audio(x1, cond, input_sampling_rate)
         assert self.condition_on_text or not (exists(semantic_token_ids) or exists(phoneme_ids)), \
             'semantic or phoneme ids should not be passed in if not conditioning on text'
         dev = self.device

@@ -1,7 +1,7 @@
 """VoiceBoxTrainer-compatible driver over the native data-parallel step.
 
-Mirrors voicebox_pytorch/trainer.py:60-321 for training on LATENTS (the audio codec / raw-wave front end is out of the hot
-path's scope): same constructor keywords, `train_step` / `train` / `save` / `load`, the same learning-rate rule (linear warm-up,
+Mirrors voicebox_pytorch/trainer.py:60-321: the dataset yields latents (frames, dim) or, for a model built with
+audio_enc_dec, waves (samples,) that the codec encodes inside the step; same constructor keywords, `train_step` / `train` / `save` / `load`, the same learning-rate rule (linear warm-up,
 then one CosineAnnealingLR step per training step, :231-253), gradient accumulation with a deferred exchange (= accelerator.no_sync
 on all but the last micro-batch, :258-272), global-norm clipping (:274-275), Adam(betas=(0.9, 0.99)) (optimizer.py:10-35), rank-0
 validation and checkpoints in the reference's format `{'model', 'optim', 'scheduler'}` (:191-197) -- `optim` is a
@@ -233,7 +233,7 @@ class VoiceBoxTrainer(nn.Module):
         return self.lr
 
     def _model_kwargs(self, batch):
-        """(latents,) or (latents, cond_token_ids): the second column feeds a text-conditioned model as semantic ids."""
+        """(latents or waves,) or (latents or waves, cond_token_ids): the second column feeds a text-conditioned model as semantic ids."""
         x = batch[0]
         if len(batch) > 1 and self.cfm_wrapper.condition_on_text:
             return x, dict(cond_token_ids=batch[1])
