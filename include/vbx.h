@@ -83,19 +83,13 @@ typedef struct {
   void* C3;                 /* EPI_GEGLU: optional bf16 copy of C [M,ldc] (wgrad operand) */
   float q_prescale;         /* EPI_QKV: q16 is written as q-hat * q_prescale (vbx_attn_q_prescale(scale): the attention kernels'
                              * contract); <= 0 means 1.  qb / k16 / kb are never scaled. */
-  /* EPI_BF16, NN mode, optional (round 5): this GEMM is the dgrad of Attention.to_out (C = dO bf16 [B*Np, H*64]) and the attention
-   * backward's delta[b,h,n] = sum_d dO[b,n,h*64+d] * O[b,n,h*64+d] is written as a by-product (then pass out = NULL to vbx_attn_bwd*).
-   * delta_o: the forward output O, fp16, same [M, ldc] layout as C; needs Np, H with N = H*64.  VBX_EUNSUPPORTED when the tile that
-   * would serve this shape has no such epilogue (call again without, and let vbx_attn_bwd* run its own pass). */
-  const void* delta_o;
-  float* delta;
 } vbx_gemm_desc;
 
 int vbx_gemm(const vbx_gemm_desc* d, void* stream);
 /* Tuning knob (results are identical up to fp32 summation order): which tile serves vbx_gemm / the grouped launch.
  * 0 automatic per shape (default; environment VBX_GEMM_PATH=<n> presets it), 1 the 128-wide kernels only, 2 the 256 x 256
- * 8-wave kernel (gemm3.hip) wherever it can serve, 3 the 128 x 256 two-workgroups-per-CU kernel (gemm4.hip) wherever it can.
- * Not thread safe; call before launching work. */
+ * 8-wave kernel (gemm3.hip) wherever it can serve, 3 the 128 x 256 two-workgroups-per-CU kernel (gemm4.hip) wherever it can,
+ * 4 = 0 with the weight-stationary kernel (gemm5.hip) on even when VBX_GEMM5=0.  Not thread safe; call before launching work. */
 int vbx_gemm_select(int path);
 /* Round 6: to_qkv and FeedForward-in at K = 512 (NT, VBX_EPI_QKV / VBX_EPI_GEGLU, every backward copy or none) run on the
  * WEIGHT-STATIONARY kernel (csrc/gemm5.hip): one 4-wave workgroup per CU keeps a 256-feature weight panel in its registers and walks
@@ -105,6 +99,19 @@ int vbx_gemm_select(int path);
  * (0 = all; process-global, read at launch, i.e. baked into a captured graph).  VBX_GEMM5=0 / vbx_gemm_select(1): the tiled kernels.
  * vbx_gemm_select(4): as 0 with this kernel forced on even when VBX_GEMM5=0. */
 int vbx_gemm5_cu_limit(int n);
+/* Which kernel vbx_gemm would launch for this descriptor right now (selected path, VBX_GEMM5, CU count of the current device and
+ * vbx_gemm5_cu_limit, 16-byte alignment of A / B): one of VBX_GEMM_KERNEL_*, or the negative error code vbx_gemm would return.
+ * Launches nothing; pointer fields are only tested for null and for alignment, so a caller without buffers passes placeholders.
+ * The rules live in one function, csrc/gemm_route.hpp. */
+enum {
+  VBX_GEMM_KERNEL_GEMM3 = 3,   /* gemm3.hip: 256 x 256 tile, 8 waves */
+  VBX_GEMM_KERNEL_GEMM4 = 4,   /* gemm4.hip: 128 x 256 tile, two workgroups per CU */
+  VBX_GEMM_KERNEL_GEMM5 = 5,   /* gemm5.hip: weight-stationary, one workgroup per CU */
+  VBX_GEMM_KERNEL_BM64 = 64,   /* gemm.hip: 64 x 128 tile */
+  VBX_GEMM_KERNEL_BM128 = 128, /* gemm.hip: 128 x 128 tile (every TN / split-K launch outside gemm3) */
+  VBX_GEMM_KERNEL_BM160 = 160  /* gemm.hip: 160 x 128 tile, 64-deep k-steps */
+};
+int vbx_gemm_route(const vbx_gemm_desc* d);
 /* n (1..4) TN / VBX_EPI_SPLITK GEMMs in ONE launch of the 256 x 256 tile (same slab layout and results as n vbx_gemm calls):
  * the four weight-gradient GEMMs of a layer are 8-24 such tiles each; together, with 3 K-splits, they fill 198 CUs (92 us in
  * situ against 4 x 38 us as separate 128-wide launches).  With vbx_gemm_select(1) it falls back to n separate launches. */
@@ -169,7 +176,7 @@ int vbx_attn_bwd_select(int variant);
 int vbx_attn_bwd_variant(void); /* always 1 (two-body) since round 6 */
 int vbx_attn_bwd(const void* q16, const void* k16, const void* qb, const void* kb, const void* v,
                  const uint8_t* mask, const void* out /* forward output [B,Np,H*64]; NULL: `delta` already holds rowsum(dO * O)
-                                                         (vbx_gemm_desc.delta) and the pass that computes it is skipped */, int out_is_f16,
+                                                         (the caller's own) and the pass that computes it is skipped */, int out_is_f16,
                  const void* dout, const float* lse, float* delta, float* dq, float* dk, void* dv, int dv_ld, int B, int H,
                  int Np, float scale, void* scratch, void* stream);
 /* backward of MultiheadRMSNorm + rotary (voicebox_pytorch.py:286-287,199): consumes dq/dk fp32

@@ -350,6 +350,18 @@ def test_gemm_tile_lds_layout_emulation(tmp_path, which):
     assert out.returncode == 0 and "ok" in out.stdout, out.stdout[-2000:]
 
 
+def test_gemm_route_of_every_model_gemm(tmp_path):
+    """csrc/gemm_route.hpp, the one function that decides which kernel serves a vbx_gemm descriptor, compiled for the host: every GEMM
+    the model issues (forward, the five dgrads, the weight gradients) at dim 512 / 1024, full and half batch, vbx_gemm_select 0-4,
+    VBX_GEMM5 on / off, against the kernels written down from the launches before the rules were gathered there."""
+    import subprocess
+
+    exe = str(tmp_path / "gemm_route_check")
+    subprocess.check_call(["g++", "-O1", "-std=c++17", os.path.join(ROOT, "tests", "native", "gemm_route_check.cpp"), "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True)
+    assert out.returncode == 0 and "ok" in out.stdout, out.stdout[-3000:]
+
+
 def test_weights_key_sees_every_kind_of_parameter_write():
     """ADVICE r1 (high / medium): the packed-operand cache key must change when parameters change through PyTorch (the views have
     their own version counters) and when native code bumps the epoch; a re-flatten must change flat_gen (cached hipGraphs)."""

@@ -1504,12 +1504,17 @@ def test_sampler_concurrent_halves_equal_single_stream(golden, monkeypatch):
         monkeypatch.setenv("VBX_SAMPLE_SPLIT", "1")
         assert MidpointSampler(vb, B, N, 5).split == 1
         monkeypatch.delenv("VBX_SAMPLE_SPLIT")
-        # dim 512: the weight-stationary to_qkv / FeedForward-in kernel owns whole CUs -> one stream by default (two with VBX_GEMM5=0)
+        # dim 512: the weight-stationary to_qkv / FeedForward-in kernel owns whole CUs -> one stream by default (two with the tiled
+        # kernels selected: the sampler asks the library which kernel serves its to_qkv, vbx_gemm_route)
         import voicebox_pytorch_amd as vbx512
+        from voicebox_pytorch_amd import _lib
         vb512 = vbx512.VoiceBox(dim=512, num_cond_tokens=10, depth=2, dim_head=64, heads=8, condition_on_text=False).to(dev).eval()
         assert MidpointSampler(vb512, 4, 64, 3).split == 1
-        monkeypatch.setenv("VBX_GEMM5", "0")
-        assert MidpointSampler(vb512, 4, 64, 3).split == 2
+        _lib.call("vbx_gemm_select", 1)
+        try:
+            assert MidpointSampler(vb512, 4, 64, 3).split == 2
+        finally:
+            _lib.call("vbx_gemm_select", 0)
 
 
 def test_sampler_adaln_table_is_bit_identical_and_follows_weight_updates(golden, monkeypatch):

@@ -14,6 +14,7 @@ P, I, L, F = C.c_void_p, C.c_int, C.c_long, C.c_float
 
 VBX_GEMM_NT, VBX_GEMM_NN, VBX_GEMM_TN = 0, 1, 2
 VBX_EPI_BF16, VBX_EPI_F32, VBX_EPI_QKV, VBX_EPI_GEGLU, VBX_EPI_SPLITK = 0, 1, 2, 3, 4
+VBX_GEMM_KERNEL_GEMM5 = 5  # vbx_gemm_route: the weight-stationary kernel (one workgroup per CU)
 
 
 class GemmDesc(C.Structure):
@@ -22,7 +23,7 @@ class GemmDesc(C.Structure):
         ("A", P), ("B", P), ("C", P), ("bias", P), ("resid", P), ("C2", P), ("splits", I),
         ("Np", I), ("H", I), ("qk_scale", F), ("q_gamma", P), ("k_gamma", P), ("rot_cos", P), ("rot_sin", P),
         ("q16", P), ("k16", P), ("qb", P), ("kb", P), ("v", P), ("q_rnorm", P), ("k_rnorm", P), ("f16", I), ("v16", P), ("C3", P),
-        ("q_prescale", F), ("delta_o", P), ("delta", P),
+        ("q_prescale", F),
     ]
 
 
@@ -32,6 +33,7 @@ _PROTOS = {
     "vbx_check_device": [I],
     "vbx_gemm": [C.POINTER(GemmDesc), P],
     "vbx_gemm_select": [I],
+    "vbx_gemm_route": [C.POINTER(GemmDesc)],
     "vbx_gemm5_cu_limit": [I],
     "vbx_prof_enable": [I],
     "vbx_gemm_tn_splitk_grouped": [C.POINTER(GemmDesc), I, P],
@@ -204,4 +206,12 @@ def call(name, *args):
     rc = getattr(l, name)(*conv)
     if rc != 0:
         raise VbxError(f"{name} failed (rc={rc}): {l.vbx_last_error().decode()}")
+    return rc
+
+
+def call_value(name, *args):
+    """Entry points that answer with a non-negative value (vbx_gemm_route): raises on a negative return."""
+    rc = getattr(lib(), name)(*args)
+    if rc < 0:
+        raise VbxError(f"{name} failed (rc={rc}): {lib().vbx_last_error().decode()}")
     return rc

@@ -1191,7 +1191,7 @@ static int attn_bwd_impl(const void* q16, const void* k16, const void* qb, const
   }
   const long chunks = (long)B * Np * H * 8;
   if (!out) {
-    // delta was written by the to_out dgrad's epilogue (vbx_gemm_desc.delta): no pass of its own
+    // the caller has already written delta: no pass of its own
   } else if (out_is_f16)
     hipLaunchKernelGGL(attn_delta_kernel<true>, dim3(cdiv(chunks, 256)), dim3(256), 0, st, (const u16*)out, (const u16*)dout,
                        delta, H, Np, chunks);

@@ -167,16 +167,18 @@ __host__ __device__ inline int geglu_row_unmap(int p, int F) {
   return (w < 64) ? f : F + f;
 }
 
-// gemm3.hip: the 256 x 256 tile path (same descriptor contract as vbx_gemm; VBX_EUNSUPPORTED = "not served, use gemm.hip")
+// vbx_gemm (gemm.hip) validates a descriptor, asks gemm_route.hpp which kernel serves it and hands it to that kernel's entry point:
+// gemm3.hip (256 x 256 tile), gemm4.hip (128 x 256 tile, two workgroups per CU; NT / NN), gemm5.hip (weight-stationary; NT, K = 512).
+// They launch what they are given: a descriptor the route would not send them is the caller's error.
 int vbx_gemm3(const vbx_gemm_desc* d, hipStream_t st);
 int vbx_gemm3_tn_splitk_grouped(const vbx_gemm_desc* descs, int n, hipStream_t st);
-// gemm4.hip: the 128 x 256 tile, two workgroups per CU (NT / NN descriptors)
 int vbx_gemm4(const vbx_gemm_desc* d, hipStream_t st);
-// gemm5.hip: the weight-stationary kernel (NT, K = 512, QKV / GEGLU epilogues)
 int vbx_gemm5(const vbx_gemm_desc* d, hipStream_t st);
-// 0: automatic choice per shape (default), 1: gemm.hip kernels only, 2: gemm3 wherever it can serve, 3: gemm4 wherever it can
-// serve (VBX_GEMM_PATH=<n> presets it; VBX_GEMM3=0 is the same as 1)
+int vbx_gemm5_cus();  // CUs a gemm5 launch may use on the current device (vbx_gemm5_cu_limit applied); < 0: an error code
+// vbx_gemm_select / VBX_GEMM_PATH: 0 automatic choice per shape (default), 1 gemm.hip kernels only, 2 gemm3 wherever it can serve,
+// 3 gemm4 wherever it can serve, 4 = 0 with gemm5 on whatever VBX_GEMM5 says
 int vbx_gemm_path();
+int vbx_gemm_stagger();  // VBX_GEMM_STAGGER (diagnostic): start-phase stagger of co-resident workgroups, in percent of a k-step
 
 // precise.hip: the exact-operand forward (vbx_model.precise).  runtime.hip hands over the tensors of its own arenas that the
 // precise forward fills for the loss and for the (unchanged) backward; null pointers = not kept (inference).

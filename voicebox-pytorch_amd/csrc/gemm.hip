@@ -7,6 +7,7 @@
 // ever exist in HBM.  The fp32 C tile is staged through LDS so every epilogue stores 16/32 B per lane.
 #include "common.hpp"
 #include "reduce_roles.hpp"
+#include "gemm_route.hpp"
 #include "gemm3_layout.hpp"  // g3::kc_slot / g3::kc_byte: the 128-byte-row K-contiguous layout shared with the one-round 64-deep tile
 #include <stdlib.h>
 #include <type_traits>
@@ -713,76 +714,42 @@ struct EpiQKV {
   }
 };
 
+// one of gemm.hip's three tiles, as gemm_route.hpp chose (kernel = VBX_GEMM_KERNEL_BM160 / BM64 / BM128; TN: BM128 only)
 template <int MA, int MB, bool F16 = false, class Epi>
-int launch(GemmParams p, const Epi& epi, int splits, hipStream_t st) {
-  static bool attr_set = false;  // >48 KiB dynamic LDS needs the opt-in once per kernel
-  auto kern128 = gemm_kernel_v2<MA, MB, Epi, F16, 128>;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern128), hipFuncAttributeMaxDynamicSharedMemorySize, GEMM2_LDS);
-    attr_set = true;
-  }
+int launch(GemmParams p, const Epi& epi, int splits, int kernel, hipStream_t st) {
   const int tiles_n = cdiv(p.N, BN);
-  // Tried and removed (numbers from the same-run A/Bs): 128x256 tiles with 4 waves of 64x128 -- main loop 30 % faster in a K
-  // sweep (727 -> 935 TF/s), isolated to_qkv / FeedForward-in launches 3-8 % faster, train step 1 % SLOWER (2 instead of 3
-  // workgroups per CU, the ~14 us VALU epilogues overlap less); the same tile with 8 waves of 64x64 -- back-to-back launches
-  // 16 % faster (FeedForward-in 45.4 -> 38.3 us), 128-forward sample 3 % SLOWER (375 -> 387 ms); 160-row tiles with a 3-slot
-  // ring for the wide GEMMs -- sample 1.5 % slower.  GEMM variants have to be judged in situ.
+  auto opt_in = [](const void* k, int lds, bool& done) {  // >48 KiB dynamic LDS needs the opt-in once per kernel
+    if (!done) (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    done = true;
+  };
   if constexpr (MA == 0) {
-    // one-round 160-row tiles when 128-row tiles would put two on a few CUs (see gemm_kernel_bm160).  VBX_GEMM_BM160=0/1: A/B.
-    static const char* b160 = getenv("VBX_GEMM_BM160");
-    const long t128 = (long)p.tiles_m * tiles_n, t160 = (long)cdiv(p.M, 160) * tiles_n;
-    static const bool all160 = getenv("VBX_GEMM_BM160ALL") != nullptr;  // experiment: also the multi-round GEMMs
-    // Also for half a batch (the sampler integrates the two halves concurrently, solver.py): 104 such workgroups, one per CU --
-    // two of these launches from the two streams then share the chip (16-interval sample 82.7 -> 79.1 ms in the same run against
-    // the 64- / 128-row tiles of gemm_kernel_v2).  VBX_BM160_MIN=<tiles>: smallest one-round grid served (257 = full batches only).
-    static const long min160 = getenv("VBX_BM160_MIN") ? atol(getenv("VBX_BM160_MIN")) : 96;
-    // k-loop-dominated GEMMs with a light epilogue (K >= 1024, plain bf16 / fp32 stores) also run on the 64-deep tile when they
-    // need MORE than one round of 160-row tiles -- the N = 1024 GEMMs of the dim-1024 model (BASELINE config 3): dgrad
-    // FeedForward-in 155 -> 132 us, FeedForward-out 96 -> 80 us, train step 20.08 -> 19.65 ms in the same run.  VBX_BM160_MULTI=0: A/B.
-    static const bool multi160 = !(getenv("VBX_BM160_MULTI") && atoi(getenv("VBX_BM160_MULTI")) == 0);
-    constexpr int multi_k = 1024;  // at K = 512 the same tile loses to the 128 x 256 tile (dgrad FeedForward-out 27.8 vs 20.6 us)
-    const bool light = std::is_same<Epi, EpiBF16>::value || std::is_same<Epi, EpiF32>::value;
-    const bool use160 = (b160 ? atoi(b160) != 0 : true) && splits == 1 &&
-                        ((t128 > 256 && (t160 <= 256 || all160)) || (t160 <= 256 && t160 >= min160) ||
-                         (multi160 && light && p.K >= multi_k && t160 > 256));
-    if (use160) {
+    if (kernel == VBX_GEMM_KERNEL_BM160) {
       static bool attr9 = false;
       auto k9 = gemm_kernel_bm160k64<MB, Epi, F16>;
-      if (!attr9) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k9), hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_V9_LDS);
-        attr9 = true;
-      }
+      opt_in(reinterpret_cast<const void*>(k9), GEMM_V9_LDS, attr9);
       p.tiles_m = cdiv(p.M, 160);
       hipLaunchKernelGGL(k9, dim3(p.tiles_m * tiles_n), dim3(512), GEMM_V9_LDS, st, p, epi);
       VBX_LAUNCH_CHECK();
       return 0;
     }
-  }
-  {
-    bool small = false;
-    if constexpr (MA == 0) {
-      // N = dim GEMMs (out-proj, ff-out, dgrads into the residual width): fewer than ~1.5 workgroups per CU with
-      // 128-row tiles -> halve the tile height (64x128) to fill the chip.  VBX_GEMM_BM64=0/1 forces it (A/B runs).
-      static const char* force = getenv("VBX_GEMM_BM64");
-      // measured (same run): NN dgrads 410 -> 500 TF, NT out-proj (K=1024) +8 %, NT ff-out (K=1408) -5 %
-      small = force ? (atoi(force) != 0) : ((long)p.tiles_m * tiles_n * splits < 384 && (MB == 1 || p.K <= 1024));
-      if (small) {
-        static bool attr64 = false;
-        auto kern64 = gemm_kernel_v2<MA, MB, Epi, F16, 64>;
-        if (!attr64) {
-          (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern64), hipFuncAttributeMaxDynamicSharedMemorySize, GEMM2_LDS);
-          attr64 = true;
-        }
-        p.tiles_m = cdiv(p.M, 64);
-        hipLaunchKernelGGL(kern64, dim3(p.tiles_m * tiles_n, splits), dim3(256), GEMM2_LDS, st, p, epi);
-      }
+    if (kernel == VBX_GEMM_KERNEL_BM64) {
+      static bool attr64 = false;
+      auto kern64 = gemm_kernel_v2<MA, MB, Epi, F16, 64>;
+      opt_in(reinterpret_cast<const void*>(kern64), GEMM2_LDS, attr64);
+      p.tiles_m = cdiv(p.M, 64);
+      hipLaunchKernelGGL(kern64, dim3(p.tiles_m * tiles_n, splits), dim3(256), GEMM2_LDS, st, p, epi);
+      VBX_LAUNCH_CHECK();
+      return 0;
     }
-    // Tried (round 2, session 3): a 64-deep / two-stage / two-workgroups-per-CU form of this kernel for the NT GEMMs (128-byte
-    // operand rows, the recipe that took the one-round tile from 45 to 36 us): to_qkv 52.4 -> 50.4 us back to back, but the train
-    // step 9.93 -> 10.05 ms and the 16-interval sample 83.2 -> 87.9 ms in the same run -- the third co-resident workgroup (its
-    // epilogue under the others' k-loops) is worth more than the cheaper staging.  Removed.
-    if (!small) hipLaunchKernelGGL(kern128, dim3(p.tiles_m * tiles_n, splits), dim3(256), GEMM2_LDS, st, p, epi);
   }
+  // Tried (round 2, session 3): a 64-deep / two-stage / two-workgroups-per-CU form of this kernel for the NT GEMMs (128-byte
+  // operand rows, the recipe that took the one-round tile from 45 to 36 us): to_qkv 52.4 -> 50.4 us back to back, but the train
+  // step 9.93 -> 10.05 ms and the 16-interval sample 83.2 -> 87.9 ms in the same run -- the third co-resident workgroup (its
+  // epilogue under the others' k-loops) is worth more than the cheaper staging.  Removed.
+  static bool attr_set = false;
+  auto kern128 = gemm_kernel_v2<MA, MB, Epi, F16, 128>;
+  opt_in(reinterpret_cast<const void*>(kern128), GEMM2_LDS, attr_set);
+  hipLaunchKernelGGL(kern128, dim3(p.tiles_m * tiles_n, splits), dim3(256), GEMM2_LDS, st, p, epi);
   VBX_LAUNCH_CHECK();
   return 0;
 }
@@ -819,12 +786,15 @@ __global__ __launch_bounds__(256) void splitk_reduce_multi_kernel(vbx_skr_jobs j
 
 }  // namespace
 
+int vbx_gemm_stagger() {
+  static const int stagger = getenv("VBX_GEMM_STAGGER") ? (int)(atof(getenv("VBX_GEMM_STAGGER")) * 100.0) : 0;
+  return stagger;
+}
 static int g_gemm_path = -1;
 int vbx_gemm_path() {
   if (g_gemm_path < 0) {
     const char* e = getenv("VBX_GEMM_PATH");
-    const char* e3 = getenv("VBX_GEMM3");
-    g_gemm_path = e ? atoi(e) : ((e3 && atoi(e3) == 0) ? 1 : 0);
+    g_gemm_path = e ? atoi(e) : 0;
     if (g_gemm_path < 0 || g_gemm_path > 4) g_gemm_path = 0;
   }
   return g_gemm_path;
@@ -834,74 +804,71 @@ extern "C" int vbx_gemm_select(int path) {
   g_gemm_path = path;
   return 0;
 }
-// Which tile serves a descriptor.  Automatic choice (measured in situ on the model's shapes, bench.py's stage table):
-//  * the layer's four split-K weight gradients run as ONE grouped gemm3 launch (runtime.hip): 92 us against 4 x 38 us;
-//  * the other NT / NN GEMMs stay on the 128-wide kernels except the two cases below: at K = dim = 512 a tile's k-loop
-//    (12-14 us for 256 x 256) is followed by a VALU-bound epilogue of the same order (qk-norm + rotary 10-13 us, GEGLU 5.5 us:
-//    tools/native/gemm_trace.cpp) during which the matrix pipes idle; three independent 128 x 128 workgroups per CU overlap the
-//    two phases better than one 256 x 256 or two lock-stepped 128 x 256 workgroups (a start-phase stagger of the co-resident
-//    workgroups, VBX_GEMM_STAGGER, did not help either); the N = dim GEMMs have too few wide tiles.
-//    Paths 2 / 3 force them for measurements (tools/native/gemm3_check).
-static int gemm_tile_fallback(const vbx_gemm_desc* d);
-static int gemm_tile_for(const vbx_gemm_desc* d) {
-  const int path = vbx_gemm_path();
-  if (path == 2) return 3;
-  if (path == 1) return 1;
-  // K = 512 linear layers with a row-wise epilogue (to_qkv, FeedForward-in): the weight-stationary kernel (gemm5.hip).  VBX_GEMM5=0: A/B.
-  static const bool g5 = !(getenv("VBX_GEMM5") && atoi(getenv("VBX_GEMM5")) == 0);
-  if ((g5 || path == 4) && path != 3 && d->mode == VBX_GEMM_NT && d->K == 512 &&
-      (d->epilogue == VBX_EPI_QKV || d->epilogue == VBX_EPI_GEGLU || (d->epilogue == VBX_EPI_BF16 && !d->f16 && !d->bias && d->N >= 512)))
-    return 5;
-  return gemm_tile_fallback(d);
-}
-static int gemm_tile_fallback(const vbx_gemm_desc* d) {  // the LDS-tiled kernels' choice (everything gemm5 does not serve)
-  const int path = vbx_gemm_path();
-  if (path == 2) return 3;
-  if (path == 1) return 1;
-  const bool ntnn = d->mode == VBX_GEMM_NT || d->mode == VBX_GEMM_NN;
-  if (path == 3) return ntnn ? 4 : 1;
-  // inference-mode FeedForward-in (GEGLU epilogue writing only the fp16 activations: no pre-activation copy, no bf16 copy) is the
-  // one wide GEMM where the 128 x 256 two-per-CU tile wins: 34.1 us against 40.7 us back to back.  VBX_GEMM4_FFIN=0: A/B.
-  static const bool ffin4 = !(getenv("VBX_GEMM4_FFIN") && atoi(getenv("VBX_GEMM4_FFIN")) == 0);
-  if (ffin4 && d->epilogue == VBX_EPI_GEGLU && d->mode == VBX_GEMM_NT && !d->C2 && !d->C3 &&
-      (long)cdiv(d->M, 128) * cdiv(d->N, 256) >= 256)
-    return 4;
-  // The K = dim dgrads into wide outputs (NN, plain bf16 epilogue: the to_out and FeedForward-out dgrads, N = 1024 / 1408) run on
-  // the 128 x 256 tile since its epilogue stores whole rows through LDS (gemm_epi3.hpp): in the train step 24.8 -> 21.9 us and
-  // 26.9 -> 25.6 us per launch, step 10.60 -> 10.48 ms in the same run.  VBX_GEMM4_DGRAD=0: A/B.  (The training FeedForward-in
-  // on the same tile: 55.5 vs 55.7 us -- no change, it stays on the 128-wide kernel.)
-  static const bool dgrad4 = !(getenv("VBX_GEMM4_DGRAD") && atoi(getenv("VBX_GEMM4_DGRAD")) == 0);
-  if (dgrad4 && d->epilogue == VBX_EPI_BF16 && d->mode == VBX_GEMM_NN && d->K <= 512 &&
-      (long)cdiv(d->M, 128) * cdiv(d->N, 256) >= 256)
-    return 4;
-  // (Tried: to_qkv of HALF a batch -- 792 tiles of 128 x 128 on 768 slots, 24 of them alone at the end -- as 396 tiles of 128 x 256
-  //  in one round: 16-interval sample 83.2 vs 83.1 ms.  The other half batch's stream already fills that tail.)
-  // (Tried: the 256 x 256 tile for the wide K = dim GEMMs of HALF a batch -- 17 x 12 / 17 x 11 tiles fit the chip in one round, and in
-  //  the sampler the other half batch's stream could fill its epilogue phases: 16-interval sample 80.2 -> 80.5-82.8 ms.  No.)
-  // (Tried: gemm3 for K >= 1024 with >= 256 tiles -- the dim-1024 model's to_qkv / FeedForward-in / FeedForward dgrad.  Back to
-  //  back it wins (K sweep: K = 1024 68 vs 78 us); in the dim-1024 train step it lost 1.5 % in the same run, 21.1 -> 21.4 ms.)
-  return 1;
-}
 
-extern "C" int vbx_gemm(const vbx_gemm_desc* d, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
+// what a descriptor must satisfy whichever kernel serves it
+static int gemm_validate(const vbx_gemm_desc* d) {
   VBX_REQUIRE(d && d->A && d->B, "vbx_gemm: null operand");
   VBX_REQUIRE(d->M > 0 && d->N > 0 && d->K > 0, "vbx_gemm: bad dims M=%d N=%d K=%d", d->M, d->N, d->K);
   VBX_REQUIRE(d->lda % 8 == 0 && d->ldb % 8 == 0, "vbx_gemm: leading dims must be multiples of 8 (16-byte rows)");
   VBX_REQUIRE(d->N % 8 == 0, "vbx_gemm: N must be a multiple of 8");
-  int tile = gemm_tile_for(d);
-  if (tile == 5) {
-    const int rc = vbx_gemm5(d, st);
-    if (rc != VBX_EUNSUPPORTED) return rc;
-    tile = gemm_tile_fallback(d);
+  if (d->mode == VBX_GEMM_NT) VBX_REQUIRE(d->K % 8 == 0, "vbx_gemm NT: K must be a multiple of 8");
+  if (d->mode == VBX_GEMM_TN) VBX_REQUIRE(d->M % 8 == 0, "vbx_gemm TN: M must be a multiple of 8");
+  const bool ntnn = d->mode == VBX_GEMM_NT || d->mode == VBX_GEMM_NN;
+  bool known = false;
+  switch (d->epilogue) {
+    case VBX_EPI_BF16:
+    case VBX_EPI_F32:
+      known = ntnn;
+      if (known) VBX_REQUIRE(d->C && d->ldc % 8 == 0, "vbx_gemm BF16 / F32: bad C/ldc");
+      break;
+    case VBX_EPI_QKV:
+      VBX_REQUIRE(d->mode == VBX_GEMM_NT, "vbx_gemm QKV: NT only");
+      VBX_REQUIRE(d->H > 0 && d->N == 3 * d->H * 64, "vbx_gemm QKV: need N == 3*H*64");
+      VBX_REQUIRE(d->Np > 0 && d->M % d->Np == 0, "vbx_gemm QKV: M must be B*Np");
+      VBX_REQUIRE(d->q16 && d->k16 && (d->v || d->v16) && d->rot_cos && d->rot_sin, "vbx_gemm QKV: null output/table");
+      VBX_REQUIRE(d->qk_scale <= 0.f || (d->q_gamma && d->k_gamma), "vbx_gemm QKV: qk-norm needs gammas");
+      known = true;
+      break;
+    case VBX_EPI_GEGLU:
+      VBX_REQUIRE(d->mode == VBX_GEMM_NT, "vbx_gemm GEGLU: NT only");
+      VBX_REQUIRE(d->N % 128 == 0 && d->bias && d->C, "vbx_gemm GEGLU: N must be a multiple of 128, bias/C required");
+      known = true;
+      break;
+    case VBX_EPI_SPLITK:
+      VBX_REQUIRE(d->mode == VBX_GEMM_TN && d->C && d->splits >= 1, "vbx_gemm SPLITK: TN only");
+      known = true;
+      break;
+    default: break;
   }
-  if (d->delta) {  // only the 128 x 256 tile's row-staged epilogue produces the attention delta (gemm_epi3.hpp): serve it there or say no
-    if (tile != 4) return VBX_EUNSUPPORTED;
-    return vbx_gemm4(d, st);
+  if (!known) {
+    vbx_set_error("vbx_gemm: unsupported mode/epilogue combination (%d,%d)", d->mode, d->epilogue);
+    return VBX_EUNSUPPORTED;
   }
-  if (tile == 3 || tile == 4) {
-    const int rc = tile == 3 ? vbx_gemm3(d, st) : vbx_gemm4(d, st);
-    if (rc != VBX_EUNSUPPORTED) return rc;
+  return 0;
+}
+
+static int gemm_route_now(const vbx_gemm_desc* d) {
+  static const bool g5 = !(getenv("VBX_GEMM5") && atoi(getenv("VBX_GEMM5")) == 0);  // VBX_GEMM5=0: the tiled kernels (A/B)
+  const int cus = vbx_gemm5_cus();
+  if (cus < 0) return cus;
+  return gemm_route::route(d, gemm_route::Facts{vbx_gemm_path(), g5, cus});
+}
+extern "C" int vbx_gemm_route(const vbx_gemm_desc* d) {
+  const int rc = gemm_validate(d);
+  return rc ? rc : gemm_route_now(d);
+}
+
+extern "C" int vbx_gemm(const vbx_gemm_desc* d, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  const int rc = gemm_validate(d);
+  if (rc) return rc;
+  const int kernel = gemm_route_now(d);
+  switch (kernel) {
+    case VBX_GEMM_KERNEL_GEMM5: return vbx_gemm5(d, st);
+    case VBX_GEMM_KERNEL_GEMM3: return vbx_gemm3(d, st);
+    case VBX_GEMM_KERNEL_GEMM4: return vbx_gemm4(d, st);
+    case VBX_GEMM_KERNEL_BM160: case VBX_GEMM_KERNEL_BM64: case VBX_GEMM_KERNEL_BM128: break;
+    default: return kernel;  // an error code
   }
   GemmParams p;
   p.A = (const u16*)d->A; p.B = (const u16*)d->B;
@@ -909,67 +876,47 @@ extern "C" int vbx_gemm(const vbx_gemm_desc* d, void* stream) {
   p.kchunk = d->K; p.tiles_m = cdiv(d->M, BM);
   static const int abl = getenv("VBX_GEMM_ABL") ? atoi(getenv("VBX_GEMM_ABL")) : 0;
   p.abl = abl;
-  static const int stagger = getenv("VBX_GEMM_STAGGER") ? (int)(atof(getenv("VBX_GEMM_STAGGER")) * 100.0) : 0;
-  p.stagger = stagger;
-  if (d->mode == VBX_GEMM_NT) VBX_REQUIRE(d->K % 8 == 0, "vbx_gemm NT: K must be a multiple of 8");
-  if (d->mode == VBX_GEMM_TN) VBX_REQUIRE(d->M % 8 == 0, "vbx_gemm TN: M must be a multiple of 8");
-
+  p.stagger = vbx_gemm_stagger();
+  const bool nt = d->mode == VBX_GEMM_NT;
   switch (d->epilogue) {
     case VBX_EPI_BF16: {
-      VBX_REQUIRE(d->C && d->ldc % 8 == 0, "vbx_gemm BF16: bad C/ldc");
       EpiBF16 e{(u16*)d->C, d->ldc, d->bias};
-      if (d->mode == VBX_GEMM_NT) return launch<0, 0>(p, e, 1, st);
-      if (d->mode == VBX_GEMM_NN) return launch<0, 1>(p, e, 1, st);
-      break;
+      return nt ? launch<0, 0>(p, e, 1, kernel, st) : launch<0, 1>(p, e, 1, kernel, st);
     }
     case VBX_EPI_F32: {
-      VBX_REQUIRE(d->C && d->ldc % 8 == 0, "vbx_gemm F32: bad C/ldc");
       EpiF32 e{(float*)d->C, d->ldc, d->bias, d->resid, (u16*)d->C2};
-      if (d->mode == VBX_GEMM_NT && d->f16) return launch<0, 0, true>(p, e, 1, st);
-      if (d->mode == VBX_GEMM_NT) return launch<0, 0>(p, e, 1, st);
-      if (d->mode == VBX_GEMM_NN) return launch<0, 1>(p, e, 1, st);
-      break;
+      if (nt && d->f16) return launch<0, 0, true>(p, e, 1, kernel, st);
+      return nt ? launch<0, 0>(p, e, 1, kernel, st) : launch<0, 1>(p, e, 1, kernel, st);
     }
     case VBX_EPI_QKV: {
-      VBX_REQUIRE(d->mode == VBX_GEMM_NT, "vbx_gemm QKV: NT only");
-      VBX_REQUIRE(d->H > 0 && d->H % 2 == 0 && d->N == 3 * d->H * 64, "vbx_gemm QKV: need even H and N == 3*H*64");
-      VBX_REQUIRE(d->Np > 0 && d->M % d->Np == 0, "vbx_gemm QKV: M must be B*Np");
-      VBX_REQUIRE(d->q16 && d->k16 && (d->v || d->v16) && d->rot_cos && d->rot_sin, "vbx_gemm QKV: null output/table");
-      VBX_REQUIRE(d->qk_scale <= 0.f || (d->q_gamma && d->k_gamma), "vbx_gemm QKV: qk-norm needs gammas");
+      VBX_REQUIRE(d->H % 2 == 0, "vbx_gemm QKV: the tiled kernels need an even H");
       EpiQKV e{d->Np, d->H, d->qk_scale, d->q_gamma, d->k_gamma, d->rot_cos, d->rot_sin,
                (u16*)d->q16, (u16*)d->k16, (u16*)d->qb, (u16*)d->kb, (u16*)d->v, d->q_rnorm, d->k_rnorm, (u16*)d->v16,
                d->q_prescale > 0.f ? d->q_prescale : 1.0f};
-      if (d->f16) return launch<0, 0, true>(p, e, 1, st);
-      return launch<0, 0>(p, e, 1, st);
+      return d->f16 ? launch<0, 0, true>(p, e, 1, kernel, st) : launch<0, 0>(p, e, 1, kernel, st);
     }
     case VBX_EPI_GEGLU: {
-      VBX_REQUIRE(d->mode == VBX_GEMM_NT, "vbx_gemm GEGLU: NT only");
-      VBX_REQUIRE(d->N % 128 == 0 && d->bias && d->C, "vbx_gemm GEGLU: N must be a multiple of 128, bias/C required");
       EpiGEGLU e{(u16*)d->C, d->ldc, d->bias, (u16*)d->C2, d->N, (u16*)d->C3, d->f16};
-      if (d->f16) return launch<0, 0, true>(p, e, 1, st);
-      return launch<0, 0>(p, e, 1, st);
+      return d->f16 ? launch<0, 0, true>(p, e, 1, kernel, st) : launch<0, 0>(p, e, 1, kernel, st);
     }
-    case VBX_EPI_SPLITK: {
-      VBX_REQUIRE(d->mode == VBX_GEMM_TN && d->C && d->splits >= 1, "vbx_gemm SPLITK: TN only");
-      int kc = cdiv(cdiv(d->K, d->splits), BK) * BK;
-      p.kchunk = kc;
+    default: {  // VBX_EPI_SPLITK
+      p.kchunk = cdiv(cdiv(d->K, d->splits), BK) * BK;
       EpiSplitK e{(float*)d->C};
-      return launch<1, 1>(p, e, d->splits, st);
+      return launch<1, 1>(p, e, d->splits, kernel, st);
     }
-    default: break;
   }
-  vbx_set_error("vbx_gemm: unsupported mode/epilogue combination (%d,%d)", d->mode, d->epilogue);
-  return VBX_EUNSUPPORTED;
 }
 
 extern "C" int vbx_gemm_tn_splitk_grouped(const vbx_gemm_desc* descs, int n, void* stream) {
   VBX_REQUIRE(descs && n >= 1 && n <= 4, "vbx_gemm_tn_splitk_grouped: 1..4 jobs");
-  if (vbx_gemm_path() != 1) {  // one launch of the 256 x 256 tile over all jobs (gemm3.hip)
-    const int rc = vbx_gemm3_tn_splitk_grouped(descs, n, (hipStream_t)stream);
-    if (rc != VBX_EUNSUPPORTED) return rc;
-  }
-  for (int i = 0; i < n; i++) {  // 128-wide kernels: one launch per job
+  for (int i = 0; i < n; i++) {
     VBX_REQUIRE(descs[i].mode == VBX_GEMM_TN && descs[i].epilogue == VBX_EPI_SPLITK, "vbx_gemm_tn_splitk_grouped: job %d is not TN / SPLITK", i);
+    const int rc = gemm_validate(&descs[i]);
+    if (rc) return rc;
+  }
+  // one launch of the 256 x 256 tile over all jobs (gemm3.hip) unless the 128-wide kernels are selected: then one launch per job
+  if (vbx_gemm_path() != 1) return vbx_gemm3_tn_splitk_grouped(descs, n, (hipStream_t)stream);
+  for (int i = 0; i < n; i++) {
     const int rc = vbx_gemm(&descs[i], stream);
     if (rc) return rc;
   }

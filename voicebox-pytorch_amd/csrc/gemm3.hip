@@ -376,16 +376,13 @@ int launch3(G3Params p, const Epi& epi, int splits, hipStream_t st) {
 
 // n (1..4) TN / VBX_EPI_SPLITK GEMMs in one launch of the 256 x 256 tile (slab layout and results as n vbx_gemm calls)
 int vbx_gemm3_tn_splitk_grouped(const vbx_gemm_desc* descs, int n, hipStream_t st) {
-  if (!descs || n < 1 || n > G3_MAX_JOBS) return VBX_EUNSUPPORTED;
+  VBX_REQUIRE(descs && n >= 1 && n <= G3_MAX_JOBS, "gemm3 grouped: 1..%d jobs", G3_MAX_JOBS);
   G3Group<Epi3SplitK> g;
   g.n = n;
   int items = 0;
   for (int i = 0; i < G3_MAX_JOBS; i++) {
     const vbx_gemm_desc* d = descs + (i < n ? i : 0);
-    if (i < n) {
-      if (d->mode != VBX_GEMM_TN || d->epilogue != VBX_EPI_SPLITK || !d->A || !d->B || !d->C || d->splits < 1) return VBX_EUNSUPPORTED;
-      if (d->M <= 0 || d->N <= 0 || d->K <= 0 || d->lda % 8 || d->ldb % 8 || d->N % 8 || d->M % 8) return VBX_EUNSUPPORTED;
-    }
+    VBX_REQUIRE(d->mode == VBX_GEMM_TN && d->epilogue == VBX_EPI_SPLITK, "gemm3 grouped: job %d is not TN / SPLITK", i);
     G3Params& p = g.p[i];
     p.A = (const u16*)d->A; p.B = (const u16*)d->B;
     p.M = d->M; p.N = d->N; p.K = d->K; p.lda = d->lda; p.ldb = d->ldb;
@@ -412,55 +409,38 @@ int vbx_gemm3_tn_splitk_grouped(const vbx_gemm_desc* descs, int n, hipStream_t s
   return 0;
 }
 
-// Same contract as vbx_gemm (include/vbx.h); returns VBX_EUNSUPPORTED for descriptors this tile does not serve so that the caller
-// can fall back to the 128-wide kernels of gemm.hip.
+// A validated descriptor that gemm_route.hpp sent here (wide_tile_serves)
 int vbx_gemm3(const vbx_gemm_desc* d, hipStream_t st) {
-  if (!d || !d->A || !d->B || d->M <= 0 || d->N <= 0 || d->K <= 0) return VBX_EUNSUPPORTED;
-  if (d->lda % 8 || d->ldb % 8 || d->N % 8 || d->K % 8) return VBX_EUNSUPPORTED;
-  if (d->mode == VBX_GEMM_TN && d->M % 8) return VBX_EUNSUPPORTED;
   G3Params p;
   p.A = (const u16*)d->A; p.B = (const u16*)d->B;
   p.M = d->M; p.N = d->N; p.K = d->K; p.lda = d->lda; p.ldb = d->ldb;
   p.kchunk = d->K; p.tiles_m = cdiv(d->M, BM);
+  const bool nt = d->mode == VBX_GEMM_NT;
   switch (d->epilogue) {
     case VBX_EPI_BF16: {
-      if (!d->C || d->ldc % 8) return VBX_EUNSUPPORTED;
       Epi3BF16 e{(u16*)d->C, d->ldc, d->bias};
-      if (d->mode == VBX_GEMM_NT && !d->f16) return launch3<0, 0>(p, e, 1, st);
-      if (d->mode == VBX_GEMM_NN) return launch3<0, 1>(p, e, 1, st);
-      break;
+      return nt ? launch3<0, 0>(p, e, 1, st) : launch3<0, 1>(p, e, 1, st);
     }
     case VBX_EPI_F32: {
-      if (!d->C || d->ldc % 8) return VBX_EUNSUPPORTED;
       Epi3F32 e{(float*)d->C, d->ldc, d->bias, d->resid, (u16*)d->C2};
-      if (d->mode == VBX_GEMM_NT && d->f16) return launch3<0, 0, true>(p, e, 1, st);
-      if (d->mode == VBX_GEMM_NT) return launch3<0, 0>(p, e, 1, st);
-      if (d->mode == VBX_GEMM_NN) return launch3<0, 1>(p, e, 1, st);
-      break;
+      if (nt && d->f16) return launch3<0, 0, true>(p, e, 1, st);
+      return nt ? launch3<0, 0>(p, e, 1, st) : launch3<0, 1>(p, e, 1, st);
     }
     case VBX_EPI_QKV: {
-      if (d->mode != VBX_GEMM_NT || d->H <= 0 || d->H % 2 || d->N != 3 * d->H * 64 || d->Np <= 0 || d->M % d->Np) return VBX_EUNSUPPORTED;
-      if (!d->q16 || !d->k16 || !(d->v || d->v16) || !d->rot_cos || !d->rot_sin) return VBX_EUNSUPPORTED;
-      if (d->qk_scale > 0.f && !(d->q_gamma && d->k_gamma)) return VBX_EUNSUPPORTED;
+      VBX_REQUIRE(d->H % 2 == 0, "vbx_gemm QKV: the tiled kernels need an even H");
       Epi3QKV e{d->Np, d->H, d->qk_scale, d->q_gamma, d->k_gamma, d->rot_cos, d->rot_sin,
                 (u16*)d->q16, (u16*)d->k16, (u16*)d->qb, (u16*)d->kb, (u16*)d->v, d->q_rnorm, d->k_rnorm, (u16*)d->v16,
                 d->q_prescale > 0.f ? d->q_prescale : 1.0f};
-      if (d->f16) return launch3<0, 0, true>(p, e, 1, st);
-      return launch3<0, 0>(p, e, 1, st);
+      return d->f16 ? launch3<0, 0, true>(p, e, 1, st) : launch3<0, 0>(p, e, 1, st);
     }
     case VBX_EPI_GEGLU: {
-      if (d->mode != VBX_GEMM_NT || d->N % 128 || !d->bias || !d->C) return VBX_EUNSUPPORTED;
       Epi3GEGLU e{(u16*)d->C, d->ldc, d->bias, (u16*)d->C2, d->N, (u16*)d->C3, d->f16};
-      if (d->f16) return launch3<0, 0, true>(p, e, 1, st);
-      return launch3<0, 0>(p, e, 1, st);
+      return d->f16 ? launch3<0, 0, true>(p, e, 1, st) : launch3<0, 0>(p, e, 1, st);
     }
-    case VBX_EPI_SPLITK: {
-      if (d->mode != VBX_GEMM_TN || !d->C || d->splits < 1) return VBX_EUNSUPPORTED;
+    default: {  // VBX_EPI_SPLITK
       p.kchunk = cdiv(cdiv(d->K, d->splits), BK) * BK;
       Epi3SplitK e{(float*)d->C};
       return launch3<1, 1>(p, e, d->splits, st);
     }
-    default: break;
   }
-  return VBX_EUNSUPPORTED;
 }

@@ -216,53 +216,34 @@ int launch4(const G4Params& p, const Epi& epi, hipStream_t st) {
 
 }  // namespace
 
-// Same contract as vbx_gemm (include/vbx.h) for NT / NN descriptors; VBX_EUNSUPPORTED = not served here.
+// A validated NT / NN descriptor that gemm_route.hpp sent here (wide_tile_serves)
 int vbx_gemm4(const vbx_gemm_desc* d, hipStream_t st) {
-  if (!d || !d->A || !d->B || d->M <= 0 || d->N <= 0 || d->K <= 0) return VBX_EUNSUPPORTED;
-  if (d->lda % 8 || d->ldb % 8 || d->N % 8 || d->K % 8) return VBX_EUNSUPPORTED;
-  if (d->mode != VBX_GEMM_NT && d->mode != VBX_GEMM_NN) return VBX_EUNSUPPORTED;
-  static const int stagger = getenv("VBX_GEMM_STAGGER") ? (int)(atof(getenv("VBX_GEMM_STAGGER")) * 100.0) : 0;
   static const int late = getenv("VBX_GEMM_LATE_DMA") ? atoi(getenv("VBX_GEMM_LATE_DMA")) : 1;
-  G4Params p{(const u16*)d->A, (const u16*)d->B, d->M, d->N, d->K, d->lda, d->ldb, stagger, late};
+  G4Params p{(const u16*)d->A, (const u16*)d->B, d->M, d->N, d->K, d->lda, d->ldb, vbx_gemm_stagger(), late};
+  const bool nt = d->mode == VBX_GEMM_NT;
   switch (d->epilogue) {
     case VBX_EPI_BF16: {
-      if (!d->C || d->ldc % 8) return VBX_EUNSUPPORTED;
-      if (d->delta) {  // dgrad of to_out with the attention backward's delta as a by-product (gemm_epi3.hpp::Epi3BF16Delta)
-        if (d->mode != VBX_GEMM_NN || d->bias || !d->delta_o || d->H <= 0 || d->Np <= 0 || d->N != d->H * 64 || d->M % d->Np)
-          return VBX_EUNSUPPORTED;
-        Epi3BF16Delta e{(u16*)d->C, d->ldc, (const u16*)d->delta_o, d->delta, d->H, d->Np};
-        return launch4<0, 1>(p, e, st);
-      }
       Epi3BF16 e{(u16*)d->C, d->ldc, d->bias};
-      if (d->mode == VBX_GEMM_NT && !d->f16) return launch4<0, 0>(p, e, st);
-      if (d->mode == VBX_GEMM_NN) return launch4<0, 1>(p, e, st);
-      break;
+      return nt ? launch4<0, 0>(p, e, st) : launch4<0, 1>(p, e, st);
     }
     case VBX_EPI_F32: {
-      if (!d->C || d->ldc % 8) return VBX_EUNSUPPORTED;
       Epi3F32 e{(float*)d->C, d->ldc, d->bias, d->resid, (u16*)d->C2};
-      if (d->mode == VBX_GEMM_NT && d->f16) return launch4<0, 0, true>(p, e, st);
-      if (d->mode == VBX_GEMM_NT) return launch4<0, 0>(p, e, st);
-      if (d->mode == VBX_GEMM_NN) return launch4<0, 1>(p, e, st);
-      break;
+      if (nt && d->f16) return launch4<0, 0, true>(p, e, st);
+      return nt ? launch4<0, 0>(p, e, st) : launch4<0, 1>(p, e, st);
     }
     case VBX_EPI_QKV: {
-      if (d->mode != VBX_GEMM_NT || d->H <= 0 || d->H % 2 || d->N != 3 * d->H * 64 || d->Np <= 0 || d->M % d->Np) return VBX_EUNSUPPORTED;
-      if (!d->q16 || !d->k16 || !(d->v || d->v16) || !d->rot_cos || !d->rot_sin) return VBX_EUNSUPPORTED;
-      if (d->qk_scale > 0.f && !(d->q_gamma && d->k_gamma)) return VBX_EUNSUPPORTED;
+      VBX_REQUIRE(d->H % 2 == 0, "vbx_gemm QKV: the tiled kernels need an even H");
       Epi3QKV e{d->Np, d->H, d->qk_scale, d->q_gamma, d->k_gamma, d->rot_cos, d->rot_sin,
                 (u16*)d->q16, (u16*)d->k16, (u16*)d->qb, (u16*)d->kb, (u16*)d->v, d->q_rnorm, d->k_rnorm, (u16*)d->v16,
                 d->q_prescale > 0.f ? d->q_prescale : 1.0f};
-      if (d->f16) return launch4<0, 0, true>(p, e, st);
-      return launch4<0, 0>(p, e, st);
+      return d->f16 ? launch4<0, 0, true>(p, e, st) : launch4<0, 0>(p, e, st);
     }
     case VBX_EPI_GEGLU: {
-      if (d->mode != VBX_GEMM_NT || d->N % 128 || !d->bias || !d->C) return VBX_EUNSUPPORTED;
       Epi3GEGLU e{(u16*)d->C, d->ldc, d->bias, (u16*)d->C2, d->N, (u16*)d->C3, d->f16};
-      if (d->f16) return launch4<0, 0, true>(p, e, st);
-      return launch4<0, 0>(p, e, st);
+      return d->f16 ? launch4<0, 0, true>(p, e, st) : launch4<0, 0>(p, e, st);
     }
     default: break;
   }
+  vbx_set_error("vbx_gemm4: epilogue %d is not served by the 128 x 256 tile", d->epilogue);
   return VBX_EUNSUPPORTED;
 }

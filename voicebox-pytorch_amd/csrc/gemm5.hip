@@ -751,22 +751,25 @@ int launch5k(const G5Params& p, const Epi& epi, int grid, hipStream_t st) {
   return 0;
 }
 int g5_cu_limit = 0;  // vbx_gemm5_cu_limit
+int g5_device_cus() {  // CU count of the current device, cached per device id (first asked in the warm-up, before any graph capture)
+  static int ncu[64] = {};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
+  if (!ncu[dev]) {
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, dev) != hipSuccess) return 0;
+    ncu[dev] = prop.multiProcessorCount;
+  }
+  return ncu[dev];
+}
 template <class Epi>
 int launch5(const vbx_gemm_desc* d, const Epi& epi, int nslab, bool train, hipStream_t st) {
-  static int ncu = 0;
-  if (!ncu) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return VBX_EUNSUPPORTED;
-    ncu = prop.multiProcessorCount;
-  }
+  const int ncu = g5_device_cus(), cus = vbx_gemm5_cus();
   G5Params p;
   p.A = (const u16*)d->A; p.W = (const u16*)d->B; p.M = d->M; p.lda = d->lda; p.ldb = d->ldb;
   p.nslab = nslab; p.npan = cdiv(nslab, 4); p.nrb = cdiv(d->M, 32);
-  if (((long)d->M + 32) * d->lda * 2 >= (1L << 31)) return VBX_EUNSUPPORTED;
   p.abytes = (unsigned)((((long)d->M - 1) * d->lda + G5_K) * 2);
-  const int cus = (g5_cu_limit > 0 && g5_cu_limit < ncu) ? g5_cu_limit : ncu;
-  if (p.npan > cus || d->M >= (1 << 22)) return VBX_EUNSUPPORTED;
+  VBX_REQUIRE(cus > 0 && p.npan <= cus, "vbx_gemm5: %d weight panels on %d CUs", p.npan, cus);
   p.wpp = cus / p.npan;
   if (p.wpp > p.nrb) p.wpp = p.nrb;
   int grid = p.npan * p.wpp;
@@ -804,37 +807,31 @@ extern "C" int vbx_gemm5_cu_limit(int n) {
   g5_cu_limit = n;
   return 0;
 }
+int vbx_gemm5_cus() {
+  const int ncu = g5_device_cus();
+  VBX_REQUIRE(ncu > 0, "vbx_gemm5: cannot read the CU count of the current device");
+  return (g5_cu_limit > 0 && g5_cu_limit < ncu) ? g5_cu_limit : ncu;
+}
 #ifdef VBX_G5_TRACE
 extern "C" int vbx_debug_gemm5_trace(void* buf) { return hipMemcpyToSymbol(HIP_SYMBOL(g5_trace_buf), &buf, sizeof(buf)) == hipSuccess ? 0 : -1; }
 #endif
-// Serves NT descriptors with K = 512 and the QKV / GEGLU epilogues; VBX_EUNSUPPORTED = "not mine" (vbx_gemm then uses the LDS-tiled kernels).
+// A validated NT descriptor with K = 512 that gemm_route.hpp sent here (gemm5_serves)
 int vbx_gemm5(const vbx_gemm_desc* d, hipStream_t st) {
-  if (d->mode != VBX_GEMM_NT || d->K != G5_K || d->lda % 8 || d->ldb % 8 || d->M < 1) return VBX_EUNSUPPORTED;
-  if ((reinterpret_cast<size_t>(d->A) | reinterpret_cast<size_t>(d->B)) & 15) return VBX_EUNSUPPORTED;
   if (d->epilogue == VBX_EPI_QKV) {
-    if (!(d->H > 0 && d->N == 3 * d->H * 64 && d->Np > 0 && d->M % d->Np == 0)) return VBX_EUNSUPPORTED;
-    if (!(d->q16 && d->k16 && d->v16 && d->rot_cos && d->rot_sin)) return VBX_EUNSUPPORTED;
-    if (d->qk_scale > 0.f && !(d->q_gamma && d->k_gamma)) return VBX_EUNSUPPORTED;
-    if ((long)d->M * d->H * 64 >= (1L << 31)) return VBX_EUNSUPPORTED;
-    const int ntrain = (d->qb != nullptr) + (d->kb != nullptr) + (d->v != nullptr) + (d->q_rnorm != nullptr) + (d->k_rnorm != nullptr);
-    if (ntrain != 0 && ntrain != 5) return VBX_EUNSUPPORTED;  // all of the backward's copies or none
+    const bool train = d->qb != nullptr;  // all of the backward's copies or none
     Epi5QKV e{d->Np, d->H, d->qk_scale, d->q_gamma, d->k_gamma, d->rot_cos, d->rot_sin,
               (u16*)d->q16, (u16*)d->k16, (u16*)d->qb, (u16*)d->kb, (u16*)d->v, d->q_rnorm, d->k_rnorm, (u16*)d->v16,
               d->q_prescale > 0.f ? d->q_prescale : 1.0f, 1.0f / (float)d->Np};
-    return launch5(d, e, d->N / 64, ntrain == 5, st);
+    return launch5(d, e, d->N / 64, train, st);
   }
   if (d->epilogue == VBX_EPI_GEGLU) {
-    if (d->N % 128 || !d->bias || !d->C || d->ldc % 8) return VBX_EUNSUPPORTED;
-    if ((d->C2 != nullptr) != (d->C3 != nullptr)) return VBX_EUNSUPPORTED;
-    if ((long)d->M * d->N >= (1L << 31) || (long)d->M * d->ldc >= (1L << 31)) return VBX_EUNSUPPORTED;
     Epi5GEGLU e{(u16*)d->C, d->ldc, d->bias, (u16*)d->C2, d->N, (u16*)d->C3};
     return launch5(d, e, d->N / 64, d->C2 != nullptr, st);
   }
   if (d->epilogue == VBX_EPI_BF16) {
-    if (d->bias || !d->C || d->ldc % 8 || d->N % 64 || d->delta || d->f16) return VBX_EUNSUPPORTED;
-    if ((long)d->M * d->ldc >= (1L << 31)) return VBX_EUNSUPPORTED;
     Epi5BF16 e{(u16*)d->C, d->ldc, d->N};
     return launch5(d, e, cdiv(d->N, 64), false, st);
   }
+  vbx_set_error("vbx_gemm5: epilogue %d is not served by the weight-stationary kernel", d->epilogue);
   return VBX_EUNSUPPORTED;
 }

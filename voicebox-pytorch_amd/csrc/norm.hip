@@ -160,8 +160,8 @@ __global__ __launch_bounds__(256) void rmsnorm_fwd_lean_kernel(const float* __re
 // u = x/|x| ; y = sqrt(D) u*gamma + beta
 // dgamma[b] += sqrt(D) u*dy ; dbeta[b] += dy ; du = sqrt(D) gamma*dy ; dx = (du - u (u.du)) / |x|
 // grid (chunks, B); each block handles RB_ROWS rows of one batch; partials -> part[b][chunk][2][D]
-// RB_ROWS rows per block: 16 (default) or 8 (VBX_RMS_BWD_ROWS=8; one row per wave, twice the blocks -- measured in the same
-// run: train step 12.75 -> 12.99 ms, the doubled partial records cost more than the extra parallelism buys)
+// RB_ROWS rows per block: 16 (tried 8 -- one row per wave, twice the blocks -- in the same run: train step 12.75 -> 12.99 ms, the
+// doubled partial records cost more than the extra parallelism buys)
 // NB_WAVES = waves per block of the backward kernel (16-row chunk -> 2 rows per wave with 8 waves; 4 waves when the
 // [NB_WAVES][3][D] fp32 reduction buffer of 8 waves would exceed the 160 KiB of LDS, i.e. D > 1664)
 template <int NB_WAVES, int RB_ROWS, int NC>
@@ -509,23 +509,22 @@ __global__ __launch_bounds__(256) void qknorm_rope_bwd_kernel(const float* __res
 
 }  // namespace
 
+static bool rms_lean() {  // VBX_RMS_LEAN=0: the generic kernels also at the widths the lean ones serve (tests, A/B)
+  static const bool lean = !(getenv("VBX_RMS_LEAN") && atoi(getenv("VBX_RMS_LEAN")) == 0);
+  return lean;
+}
 static int rmsnorm_fwd_launch(const float* x, const float* gamma, const float* beta, long gb_stride, void* y_bf16, void* y_f16,
                               float* y_f32, int B, int Np, int n0, int rows_per_batch, int D, void* stream) {
   VBX_REQUIRE(x && gamma && (y_bf16 || y_f16 || y_f32), "vbx_rmsnorm_fwd: null pointer");
   VBX_REQUIRE(D % 4 == 0 && D <= 2048 && D > 0, "vbx_rmsnorm_fwd: D must be a multiple of 4 and <= 2048 (got %d)", D);
   VBX_REQUIRE(B > 0 && rows_per_batch > 0 && n0 >= 0 && n0 + rows_per_batch <= Np, "vbx_rmsnorm_fwd: bad row range");
   const long rows = (long)B * rows_per_batch;
-  static const int rpw = getenv("VBX_RMS_ROWS") ? atoi(getenv("VBX_RMS_ROWS")) : 1;  // A/B: rows per wave in flight (2: 9 -> 14 us)
-  int blocks = cdiv(rows, 4 * (rpw == 2 ? 2 : 1));
+  int blocks = cdiv(rows, 4);  // one row per wave in flight (two: 9 -> 14 us, removed)
   if (blocks > 4096) blocks = 4096;
-#define VBX_RF_LAUNCH2(NC_)                                                                                                      \
-  hipLaunchKernelGGL((rmsnorm_fwd_kernel<2, NC_>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, gamma, beta, gb_stride, \
-                     (u16*)y_bf16, (u16*)y_f16, B, Np, n0, rows_per_batch, D, y_f32)
 #define VBX_RF_LAUNCH1(NC_)                                                                                                      \
   hipLaunchKernelGGL((rmsnorm_fwd_kernel<1, NC_>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, gamma, beta, gb_stride, \
                      (u16*)y_bf16, (u16*)y_f16, B, Np, n0, rows_per_batch, D, y_f32)
-  static const bool lean = !(getenv("VBX_RMS_LEAN") && atoi(getenv("VBX_RMS_LEAN")) == 0);  // 0: A/B against the generic kernel
-  if (lean && (D == 512 || D == 1024 || D == 2048)) {
+  if (rms_lean() && (D == 512 || D == 1024 || D == 2048)) {
     const dim3 lgrid(cdiv(rows_per_batch, 4), B);
 #define VBX_RF_LAUNCHL(NC_)                                                                                                          \
   hipLaunchKernelGGL((rmsnorm_fwd_lean_kernel<NC_>), lgrid, dim3(256), 0, (hipStream_t)stream, x, gamma, beta, gb_stride, (u16*)y_bf16, \
@@ -537,10 +536,8 @@ static int rmsnorm_fwd_launch(const float* x, const float* gamma, const float* b
     VBX_LAUNCH_CHECK();
     return 0;
   }
-  if (rpw == 2) VBX_NC_DISPATCH(D, VBX_RF_LAUNCH2);
-  else VBX_NC_DISPATCH(D, VBX_RF_LAUNCH1);
+  VBX_NC_DISPATCH(D, VBX_RF_LAUNCH1);
 #undef VBX_RF_LAUNCH1
-#undef VBX_RF_LAUNCH2
   VBX_LAUNCH_CHECK();
   return 0;
 }
@@ -558,14 +555,8 @@ extern "C" int vbx_rmsnorm_fwd_f32(const float* x, const float* gamma, const flo
   return rmsnorm_fwd_launch(x, gamma, beta, gb_stride, nullptr, nullptr, y_f32, B, Np, n0, rows_per_batch, D, stream);
 }
 
-static int rb_rows() {
-  static const int r = [] {
-    const int v = getenv("VBX_RMS_BWD_ROWS") ? atoi(getenv("VBX_RMS_BWD_ROWS")) : 16;
-    return (v == 8 || v == 32) ? v : 16;
-  }();
-  return r;
-}
-extern "C" int vbx_rmsnorm_bwd_chunks(int rows_per_batch) { return cdiv(rows_per_batch, rb_rows()); }
+constexpr int RB_ROWS = 16;  // rows per workgroup of the norm backward = rows per partial record
+extern "C" int vbx_rmsnorm_bwd_chunks(int rows_per_batch) { return cdiv(rows_per_batch, RB_ROWS); }
 
 extern "C" int vbx_rmsnorm_bwd(const float* x, const float* gamma, long gb_stride, const void* dy_bf16, const float* dx_in,
                                float* dx_out, void* dxb_bf16, float* part, float* colpart, int B, int Np, int n0,
@@ -573,12 +564,11 @@ extern "C" int vbx_rmsnorm_bwd(const float* x, const float* gamma, long gb_strid
   VBX_REQUIRE(x && gamma && dy_bf16 && dx_out && part, "vbx_rmsnorm_bwd: null pointer");
   VBX_REQUIRE(D % 4 == 0 && D <= 2048 && D > 0, "vbx_rmsnorm_bwd: D must be a multiple of 4 and <= 2048 (got %d)", D);
   VBX_REQUIRE(B > 0 && rows_per_batch > 0 && n0 >= 0 && n0 + rows_per_batch <= Np, "vbx_rmsnorm_bwd: bad row range");
-  dim3 grid(cdiv(rows_per_batch, rb_rows()), B);
+  dim3 grid(cdiv(rows_per_batch, RB_ROWS), B);
   VBX_REQUIRE(!colpart || dx_in, "vbx_rmsnorm_bwd: column sums need dx_in");
   const bool eight = (size_t)8 * 3 * D * sizeof(float) <= 160 * 1024;
   const size_t lds = (size_t)(eight ? 8 : 4) * 3 * D * sizeof(float);
-  static const bool lean = !(getenv("VBX_RMS_LEAN") && atoi(getenv("VBX_RMS_LEAN")) == 0);  // 0: A/B against the generic kernel
-  if (lean && rb_rows() == 16 && (D == 512 || D == 1024)) {  // (D = 2048: the [8][3][D] reduction buffer exceeds the LDS, generic path)
+  if (rms_lean() && (D == 512 || D == 1024)) {  // (D = 2048: the [8][3][D] reduction buffer exceeds the LDS, generic path)
 #define VBX_RB_LAUNCHL(NC_)                                                                                                          \
   do {                                                                                                                               \
     static bool attr_ = false;                                                                                                       \
@@ -613,12 +603,8 @@ extern "C" int vbx_rmsnorm_bwd(const float* x, const float* gamma, long gb_strid
     else if (D <= 1024) VBX_RB_LAUNCH_NC(W, R, 4);                         \
     else VBX_RB_LAUNCH_NC(W, R, 8);                                        \
   } while (0)
-  if (eight && rb_rows() == 8) VBX_RB_LAUNCH(8, 8);
-  else if (eight && rb_rows() == 32) VBX_RB_LAUNCH(8, 32);
-  else if (eight) VBX_RB_LAUNCH(8, 16);
-  else if (rb_rows() == 8) VBX_RB_LAUNCH(4, 8);
-  else if (rb_rows() == 32) VBX_RB_LAUNCH(4, 32);
-  else VBX_RB_LAUNCH(4, 16);
+  if (eight) VBX_RB_LAUNCH(8, RB_ROWS);
+  else VBX_RB_LAUNCH(4, RB_ROWS);
 #undef VBX_RB_LAUNCH_NC
 #undef VBX_RB_LAUNCH
   VBX_LAUNCH_CHECK();

@@ -665,7 +665,7 @@ __global__ __launch_bounds__(256) void adaln_bwd_kernel(const float* __restrict_
   else adaln_bwd_w_role(temb, dada, dw, dbias, B, Th, J, blockIdx.y - ADA_SLICES);
 }
 
-// v2 of the same launch (default; VBX_ADALN_BWD=1 selects the kernel above for the A/B): the compiler turned v1's per-batch
+// v2 of the same launch (what runs whenever J fits its LDS slices; the kernel above serves larger J): the compiler turned v1's per-batch
 // guards into scalar branches with a wait after every load (one exposed memory round trip per row of the slice -- the
 // d(time_emb) blocks were the kernel's critical path at ~20 us).  Here the block's dada values sit in LDS, batch rows
 // beyond B carry a zero weight instead of a branch, and ADA_TG weight rows are requested before the first is consumed.
@@ -1835,9 +1835,8 @@ extern "C" int vbx_adaln_proj_bwd_scratch_floats(int B, int Th, int J) { return 
 extern "C" int vbx_adaln_proj_bwd(const float* temb, const void* w_bf16, const float* dada, float* dw, float* dbias,
                                   float* dtemb, float* scratch, int B, int Th, int J, int accumulate_dtemb, void* stream) {
   VBX_REQUIRE(temb && w_bf16 && dada && dbias && dtemb && scratch && Th % 8 == 0, "vbx_adaln_proj_bwd: bad args");  // dw NULL: factor form (vbx_model.adaln_factors)
-  static const int ver = getenv("VBX_ADALN_BWD") ? atoi(getenv("VBX_ADALN_BWD")) : 2;
   const dim3 grid(cdiv(Th / 4, 256), cdiv(J, ADA_WROWS) + ADA_SLICES);
-  if (ver != 1 && J <= ADA_SLICES * ADA_PER_MAX)
+  if (J <= ADA_SLICES * ADA_PER_MAX)  // (larger J: the first version of the kernel)
     hipLaunchKernelGGL(adaln_bwd_kernel_v2, grid, dim3(256), 0, ST, temb, (const u16*)w_bf16, dada, dw, dbias, scratch, B, Th, J);
   else
     hipLaunchKernelGGL(adaln_bwd_kernel, grid, dim3(256), 0, ST, temb, (const u16*)w_bf16, dada, dw, dbias, scratch, B, Th, J);

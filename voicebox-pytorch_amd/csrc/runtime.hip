@@ -136,48 +136,9 @@ struct Acts {
 // profiled launches: with W = tiles*s workgroups the busiest CU gets n = ceil(W/256) of them, which (n <= 3) run concurrently and
 // share the CU's L2->LDS stream -- a lone workgroup reaches ~60 % of the rate three reach together, two ~85 %; each k-step of 32
 // costs ~0.27 us per resident workgroup at full rate; the fp32 slabs cost a write + a read of s*I*J*4 bytes at ~4 TB/s.
-// VBX_WGRAD_TARGET=<workgroups> restores the plain "about that many workgroups" rule (A/B).
-// The four weight-gradient GEMMs of a layer run as ONE grouped launch at the end of the layer's backward
-// (vbx_gemm_tn_splitk_grouped; by default on the 256 x 256 tile of gemm3.hip) instead of four launches interleaved with the dgrads:
-// separately they are 8-24 tiles each.  VBX_GROUP_WGRAD=0 restores the separate launches (A/B); with VBX_GEMM3=0 the default is off.
-bool group_wgrad() {
-  static const char* e = getenv("VBX_GROUP_WGRAD");
-  if (e) return atoi(e) == 1;
-  return vbx_gemm_path() != 1;
-}
-struct WgradGroup {
-  vbx_gemm_desc d[4];
-  int n = 0;
-};
-
-// K splits of the grouped launch on 256 x 256 tiles: every job gets the same count, chosen so that the layer's tiles x splits
-// fill the 256 CUs once (dim 512: 24 + 8 + 22 + 12 = 66 tiles -> 3 splits = 198 workgroups of ~44 k-tiles).
-int wgrad_splits3(const Dims& d) {
-  static const long fixed = getenv("VBX_WGRAD_SPLITS3") ? atol(getenv("VBX_WGRAD_SPLITS3")) : 0;
-  auto t = [](long I, long J) { return ((I + 255) / 256) * ((J + 255) / 256); };
-  const long tiles = t(3 * d.I, d.D) + t(d.D, d.I) + t(2 * d.Fp, d.D) + t(d.D, d.Fp);
-  long s = fixed > 0 ? fixed : 256 / tiles;
-  const long smax = (d.M + 1023) / 1024;  // at least 16 k-tiles per workgroup
-  if (s > smax) s = smax;
-  if (s > 16) s = 16;
-  if (s < 1) s = 1;
-  return (int)s;
-}
-
 int wgrad_splits(long I, long J, long K) {
   const long tiles = ((I + 127) / 128) * ((J + 127) / 128);
   const long smax = (K + 511) / 512;
-  static const long target = getenv("VBX_WGRAD_TARGET") ? atol(getenv("VBX_WGRAD_TARGET")) : 0;
-  static const long fixed = getenv("VBX_WGRAD_SPLITS") ? atol(getenv("VBX_WGRAD_SPLITS")) : 0;  // A/B: the same split count for every
-  if (fixed > 0) return (int)(fixed > smax ? smax : (fixed > 16 ? 16 : fixed));                  // weight gradient (with VBX_GROUP_WGRAD=1
-                                                                                                 // occupancy no longer needs many splits)
-  if (target > 0) {
-    long s = (target + tiles - 1) / tiles;
-    if (s > smax) s = smax;
-    if (s > 16) s = 16;
-    if (s < 1) s = 1;
-    return (int)s;
-  }
   int best = 1;
   double best_cost = 1e30;
   for (int s = 1; s <= 16 && s <= smax; s++) {
@@ -191,6 +152,23 @@ int wgrad_splits(long I, long J, long K) {
     if (cost < best_cost) { best_cost = cost; best = s; }
   }
   return best;
+}
+
+// The four weight-gradient GEMMs of a layer run as ONE grouped launch at the end of the layer's backward
+// (vbx_gemm_tn_splitk_grouped, on the 256 x 256 tile of gemm3.hip) instead of four launches interleaved with the dgrads: separately
+// they are 8-24 tiles each.  With the 128-wide kernels selected (vbx_gemm_select(1)) they stay separate launches.
+bool group_wgrad() { return vbx_gemm_path() != 1; }
+struct WgradGroup {
+  vbx_gemm_desc d[4];
+  int n = 0;
+};
+// K splits of the grouped launch: every job gets the same count, chosen so that the layer's tiles x splits fill the 256 CUs once
+// (dim 512: 24 + 8 + 22 + 12 = 66 tiles -> 3 splits = 198 workgroups of ~44 k-tiles).
+int wgrad_splits3(const Dims& d) {
+  auto t = [](long I, long J) { return ((I + 255) / 256) * ((J + 255) / 256); };
+  const long tiles = t(3 * d.I, d.D) + t(d.D, d.I) + t(2 * d.Fp, d.D) + t(d.D, d.Fp);
+  const long smax = (d.M + 1023) / 1024;  // at least 16 k-tiles per workgroup
+  return (int)std::max(1L, std::min({256 / tiles, smax, 16L}));
 }
 
 void carve_acts(const vbx_model* m, Acts& a) {
@@ -429,97 +407,23 @@ int gemm_nn_bf16(const u16* A, int lda, const u16* Bw, int ldb, int M, int N, in
   g.A = A; g.B = Bw; g.C = C;
   return vbx_gemm(&g, st);
 }
-// Weight gradients are leaves of the backward graph: nothing downstream in the layer needs them, so they CAN run on a side stream
-// (forked from / joined to the caller's stream with events) to fill the CUs the dependent chain leaves idle.  Opt-in
-// (VBX_WGRAD_STREAM=1): measured in the same run the train step got 4 % SLOWER (14.40 -> 14.97 ms) -- the split-K GEMMs and the
-// dgrad / attention kernels they overlap with are all bound by the same L2->LDS stream, so concurrency only adds contention.
-// One side stream per process, in-order, so the shared split-K slab buffer needs no extra protection.  wgrad_join() makes the
-// caller's stream wait for everything issued so far: called before a kernel overwrites an operand a pending wgrad reads
-// (a.dxb) and at the end of every stage entry point (the caller may all-reduce / apply the gradients right after it returns).
-struct SideStream {
-  hipStream_t s = nullptr;
-  hipEvent_t fork = nullptr, done = nullptr;
-  bool pending = false, ok = false;
-};
-SideStream& side_stream() {
-  static thread_local SideStream ss;
-  static const bool enabled = getenv("VBX_WGRAD_STREAM") && atoi(getenv("VBX_WGRAD_STREAM")) != 0;
-  if (enabled && !ss.s) {
-    ss.ok = hipStreamCreateWithFlags(&ss.s, hipStreamNonBlocking) == hipSuccess &&
-            hipEventCreateWithFlags(&ss.fork, hipEventDisableTiming) == hipSuccess &&
-            hipEventCreateWithFlags(&ss.done, hipEventDisableTiming) == hipSuccess;
-  }
-  return ss;
-}
-// Forward: the time embedding + the adaLN projections of the whole stack (a 100 MB weight stream, ~40 us, HBM-bound) do not depend
-// on the frame embedding (pack + to_embed GEMM + conv), so they CAN run on their own stream between a fork and a join event --
-// also under hipGraph capture, where the two become parallel branches.  Opt-in (VBX_TIME_BRANCH=1): measured in the same run
-// the 128-forward sample got 1 % slower (365 -> 369 ms) and the train step 1.6 % slower (12.90 -> 13.12 ms).
-struct TimeBranch {
-  hipStream_t s = nullptr;
-  hipEvent_t fork = nullptr, done = nullptr;
-  bool ok = false;
-};
-TimeBranch& time_branch() {
-  static thread_local TimeBranch tb;
-  static const bool enabled = getenv("VBX_TIME_BRANCH") && atoi(getenv("VBX_TIME_BRANCH")) != 0;
-  if (enabled && !tb.s) {
-    tb.ok = hipStreamCreateWithFlags(&tb.s, hipStreamNonBlocking) == hipSuccess &&
-            hipEventCreateWithFlags(&tb.fork, hipEventDisableTiming) == hipSuccess &&
-            hipEventCreateWithFlags(&tb.done, hipEventDisableTiming) == hipSuccess;
-  }
-  return tb;
-}
-int wgrad_join(hipStream_t st) {
-  SideStream& ss = side_stream();
-  if (!ss.ok || !ss.pending) return 0;
-  if (hipStreamWaitEvent(st, ss.done, 0) != hipSuccess) {
-    vbx_set_error("wgrad_join: hipStreamWaitEvent failed");
-    return VBX_EINVAL;
-  }
-  ss.pending = false;
-  return 0;
-}
-// dW[I,J] = P[K,I]^T . Q[K,J]  -> grads (fp32, reference layout [dst_rows, dst_cols])
+// dW[I,J] = P[K,I]^T . Q[K,J]  -> grads (fp32, reference layout [dst_rows, dst_cols]).  On its own: split-K GEMM + slab reduction, now.
+// Inside a layer (defer: the layer's reduce jobs; grp: its grouped GEMM launch, null when the GEMMs stay separate launches) the
+// reduction -- and with grp the GEMM too -- is only recorded and runs at the layer's end; sq = vbx_skr_job.sq of that reduction.
 int wgrad(const u16* P, int ldp, const u16* Q, int ldq, int I, int J, long K, float* slabs, float* dst, int dst_rows,
           int dst_cols, int rowmap, int F, hipStream_t st, vbx_skr_jobs* defer = nullptr, WgradGroup* grp = nullptr, int group_splits = 0,
-          float* sq = nullptr /* vbx_skr_job.sq of the deferred reduction */) {
+          float* sq = nullptr) {
+  const bool deferred = defer && J % 4 == 0 && defer->n < VBX_SKR_MAX;
+  const bool grouped = grp && deferred && grp->n < 4;
   vbx_gemm_desc g{};
-  const bool grouped = grp && defer && J % 4 == 0 && defer->n < VBX_SKR_MAX && grp->n < 4;
-  const int splits = (grouped && group_splits > 0) ? group_splits : wgrad_splits(I, J, K);
   g.mode = VBX_GEMM_TN; g.epilogue = VBX_EPI_SPLITK; g.M = I; g.N = J; g.K = (int)K; g.lda = ldp; g.ldb = ldq;
-  g.A = P; g.B = Q; g.C = slabs; g.splits = splits;
-  if (grouped) {  // GEMM and reduction both deferred to the layer's end
-    grp->d[grp->n++] = g;
-    vbx_skr_job& jb = defer->job[defer->n++];
-    jb.slabs = slabs; jb.dst = dst; jb.splits = splits; jb.M = I; jb.N = J; jb.dst_rows = dst_rows; jb.dst_cols = dst_cols;
-    jb.dst_ld = dst_cols; jb.rowmap = rowmap; jb.F = F; jb.sq = sq;
-    return 0;
-  }
-  SideStream& ss = side_stream();
-  hipStream_t run = st;
-  if (ss.ok) {
-    if (hipEventRecord(ss.fork, st) != hipSuccess || hipStreamWaitEvent(ss.s, ss.fork, 0) != hipSuccess) {
-      vbx_set_error("wgrad: fork to the side stream failed");
-      return VBX_EINVAL;
-    }
-    run = ss.s;
-  }
-  { ProfScope ps("wgrad (separate)", run); CK(vbx_gemm(&g, run)); }
-  if (defer && J % 4 == 0 && defer->n < VBX_SKR_MAX) {  // reduced later, together with the layer's other weight gradients
-    vbx_skr_job& jb = defer->job[defer->n++];
-    jb.slabs = slabs; jb.dst = dst; jb.splits = splits; jb.M = I; jb.N = J; jb.dst_rows = dst_rows; jb.dst_cols = dst_cols;
-    jb.dst_ld = dst_cols; jb.rowmap = rowmap; jb.F = F; jb.sq = sq;
-  } else {
-    CK(vbx_splitk_reduce(slabs, splits, I, J, dst, dst_rows, dst_cols, dst_cols, rowmap, F, 0, run));
-  }
-  if (ss.ok) {
-    if (hipEventRecord(ss.done, ss.s) != hipSuccess) {
-      vbx_set_error("wgrad: event record on the side stream failed");
-      return VBX_EINVAL;
-    }
-    ss.pending = true;
-  }
+  g.A = P; g.B = Q; g.C = slabs; g.splits = (grouped && group_splits > 0) ? group_splits : wgrad_splits(I, J, K);
+  if (grouped) grp->d[grp->n++] = g;
+  else { ProfScope ps("wgrad (separate)", st); CK(vbx_gemm(&g, st)); }
+  if (!deferred) return vbx_splitk_reduce(slabs, g.splits, I, J, dst, dst_rows, dst_cols, dst_cols, rowmap, F, 0, st);
+  vbx_skr_job& jb = defer->job[defer->n++];
+  jb.slabs = slabs; jb.dst = dst; jb.splits = g.splits; jb.M = I; jb.N = J; jb.dst_rows = dst_rows; jb.dst_cols = dst_cols;
+  jb.dst_ld = dst_cols; jb.rowmap = rowmap; jb.F = F; jb.sq = sq;
   return 0;
 }
 
@@ -621,28 +525,15 @@ extern "C" int vbx_model_forward(const vbx_model* m, const vbx_io* io, void* str
     CK(vbx_stack_input(io->x, d.R ? P + G[VBX_P_REG] : nullptr, a.xs[0], d.B, d.N, d.R, d.D, stream));
     if (!m->plain_norm) CK(vbx_adaln_proj_fwd(io->cond, w.adah, w.bada, a.ada, d.B, d.Th, d.J, 4 * d.D, stream));
   } else {
-  // time embedding + every adaLN projection of the stack   (:1082, :273) -- on the side branch when available
-  TimeBranch& tb = time_branch();
-  void* tstream = stream;
-  if (tb.ok) {
-    if (hipEventRecord(tb.fork, st) != hipSuccess || hipStreamWaitEvent(tb.s, tb.fork, 0) != hipSuccess) {
-      vbx_set_error("vbx_model_forward: fork of the time branch failed");
-      return VBX_EINVAL;
-    }
-    tstream = tb.s;
-  }
+  // time embedding + every adaLN projection of the stack   (:1082, :273)
   if (io->ada_table) {  // sampler: the projections of this time point were evaluated once for the whole grid (vbx_ada_select)
     VBX_REQUIRE(!tr && io->ada_counter, "vbx_model_forward: ada_table is an inference-only input and needs ada_counter");
     CK(vbx_ada_select_rows(a.ada, d.L, d.B, 4 * d.D, io->ada_table, io->ada_counter, io->ada_stride ? io->ada_stride : 2, io->ada_slot,
-                           tstream));
+                           stream));
   } else {
   CK(vbx_time_embed_fwd(io->times, P + G[VBX_P_SINW], P + G[VBX_P_T1W], P + G[VBX_P_T1B], a.four, a.pre, a.temb, d.B, d.D,
-                        d.Th, tstream));
-  CK(vbx_adaln_proj_fwd(a.temb, w.adah, w.bada, a.ada, d.B, d.Th, d.J, 4 * d.D, tstream));
-  }
-  if (tb.ok && hipEventRecord(tb.done, tb.s) != hipSuccess) {
-    vbx_set_error("vbx_model_forward: event record on the time branch failed");
-    return VBX_EINVAL;
+                        d.Th, stream));
+  CK(vbx_adaln_proj_fwd(a.temb, w.adah, w.bada, a.ada, d.B, d.Th, d.J, 4 * d.D, stream));
   }
   // to_embed(cat(x, cond * ~cond_mask))   (voicebox_pytorch.py:1035,1075-1078)
   if (d.Lc) {
@@ -666,10 +557,6 @@ extern "C" int vbx_model_forward(const vbx_model* m, const vbx_io* io, void* str
   // conv_embed(x) + x, register tokens in place   (:1080, :422-425)
   CK(vbx_convpos_fwd(a.e, P + G[VBX_P_CONVW], P + G[VBX_P_CONVB], io->attn_mask, d.R ? P + G[VBX_P_REG] : nullptr, a.xs[0],
                      d.B, d.N, d.R, d.D, d.ks, stream));
-  if (tb.ok && hipStreamWaitEvent(st, tb.done, 0) != hipSuccess) {  // join: the layers read a.ada
-    vbx_set_error("vbx_model_forward: join of the time branch failed");
-    return VBX_EINVAL;
-  }
   }
 
   for (int l = 0; l < d.L; l++) {
@@ -748,7 +635,7 @@ extern "C" int vbx_model_forward(const vbx_model* m, const vbx_io* io, void* str
   return 0;
 }
 
-static int backward_head_impl(const vbx_model* m, const vbx_io* io, const float* gscale, void* stream) {
+extern "C" int vbx_model_backward_head(const vbx_model* m, const vbx_io* io, const float* gscale, void* stream) {
   CK(check_model(m));
   VBX_REQUIRE(m->training && m->grads && io && io->target && (m->stack_only || io->loss_mask),
               "vbx_model_backward_head: needs a training forward");
@@ -786,12 +673,7 @@ static int backward_head_impl(const vbx_model* m, const vbx_io* io, const float*
   return 0;
 }
 
-// the four split-K weight-gradient reductions of a layer are deferred into one launch (own slab region each); VBX_BATCH_WGRAD=0: A/B
-static bool batch_wgrad_on() {
-  static const bool on = !(getenv("VBX_BATCH_WGRAD") && atoi(getenv("VBX_BATCH_WGRAD")) == 0) && !side_stream().ok;
-  return on;
-}
-// vbx_model.sq_partials: blocks of the layer's four deferred reductions in the order backward_layer_impl issues them
+// vbx_model.sq_partials: blocks of the layer's four deferred weight-gradient reductions in the order the layer's backward issues them
 struct SqLayout { long off[4], per_layer; };  // FeedForward-out, FeedForward-in, to_out, to_qkv
 static SqLayout sq_layout(const Dims& d) {
   SqLayout q;
@@ -804,7 +686,6 @@ static SqLayout sq_layout(const Dims& d) {
 }
 extern "C" long vbx_model_sq_partials(const vbx_model* m, long* ranges) {
   if (check_model(m) != 0) return 0;
-  if (!batch_wgrad_on()) return 0;
   const Dims d = dims_of(m);
   if (ranges) {
     for (int l = 0; l < d.L; l++) {  // the flat layout holds them in this order (engine.py L_NAMES / VBX_L_*)
@@ -821,9 +702,107 @@ extern "C" long vbx_model_sq_partials(const vbx_model* m, long* ranges) {
   return sq_layout(d).per_layer * d.L;
 }
 
-static int backward_layer_impl(const vbx_model* m, const vbx_io* io, int l, void* stream) {
+// One layer's backward, as the model's configuration fixes it (the launch order is a function of vbx_model alone):
+//   FeedForward half   dgrad ff_out, [dropout], GEGLU backward + bias partials, dgrad ff_in, norm backward            4-5 launches
+//   attention half     dgrad to_out, attention backward (delta + one pass), dgrad to_qkv, norm backward               5 launches
+//   weight gradients   the four split-K GEMMs as one grouped launch + one slab reduction (between dgrad to_qkv and the norm backward)
+//   small reductions   every partial record of the layer in one launch -- or, deferred, of all layers when layer 0 is done
+//   tails              GateLoop block, u-net skip combiner, adaLN projections
+// Which of the model-dependent forms apply:
+struct LayerPlan {
+  bool ada_all;  // adaLN weight gradients in factor form: nothing of the projections' backward is left per layer (bias gradient: two
+                 // jobs of the layer's reduce; d(time_emb): one launch for all layers after layer 0)
+  bool defer;    // vbx_model.defer_reduce: the layer's partial records stay in its own region and layer 0 reduces every layer's.
+                 // GateLoop re-uses npart for its own immediate reductions and the u-net combiner cs_scratch: those models reduce per
+                 // layer; so does the per-layer adaLN backward (materialised weight gradients), which consumes dada_l right away.
+};
+static LayerPlan layer_plan(const vbx_model* m) {
+  LayerPlan p;
+  p.ada_all = m->adaln_factors && !m->plain_norm;
+  p.defer = m->defer_reduce && !m->gateloop && !m->unet && (m->plain_norm || p.ada_all);
+  return p;
+}
+
+// the small reductions of layer ll whose partial records sit in region `region` of the arena (at most 8 jobs)
+static void layer_reduce_jobs(const vbx_model* m, const Dims& d, const Acts& a, const LayerPlan& pl, int ll, int region, vbx_mr_jobs& jb) {
+  auto add = [&](const float* src, float* dst, int rows, int cols, long row_stride, int batches, long sbs, long dbs, int dst_len,
+                 int rowmap, int F) {
+    vbx_mr_job& j = jb.job[jb.n++];
+    j.src = src; j.dst = dst; j.rows = rows; j.cols = cols; j.row_stride = row_stride; j.batches = batches;
+    j.src_bstride = sbs; j.dst_bstride = dbs; j.dst_len = dst_len; j.rowmap = rowmap; j.F = F;
+  };
+  float* Gd = m->grads;
+  const long* ol = m->off + VBX_NG + (long)ll * VBX_NL;
+  const int chunks = vbx_rmsnorm_bwd_chunks(d.Np);
+  const long rec = 2L * d.D;
+  float* dada_ll = a.dada + (size_t)ll * d.B * 4 * d.D;
+  const float* np1 = a.npart + region * a.np_stride;
+  const float* np2 = a.npart2 + region * a.np_stride;
+  const float* cp = a.cpart + region * a.cp_stride;
+  const float* gp = a.gpart + region * a.gp_stride;
+  const float* cs = pl.defer ? a.cs_layers + region * a.cs_stride : a.cs_scratch;
+  if (m->plain_norm) {  // d(gamma) = first half of the records, summed over batch and chunks
+    add(np1, Gd + ol[VBX_L_N2G], d.B * chunks, d.D, rec, 1, 0, 0, d.D, 0, 0);
+    add(np2, Gd + ol[VBX_L_N1G], d.B * chunks, d.D, rec, 1, 0, 0, d.D, 0, 0);
+  } else {              // per-batch d(gamma | beta) of the two adaLN norms -> dada_l [B][g1 b1 g2 b2]
+    add(np1, dada_ll + 2 * d.D, chunks, 2 * d.D, rec, d.B, (long)chunks * rec, 4L * d.D, 2 * d.D, 0, 0);
+    add(np2, dada_ll, chunks, 2 * d.D, rec, d.B, (long)chunks * rec, 4L * d.D, 2 * d.D, 0, 0);
+  }
+  if (pl.ada_all) {  // factor form: the projections' bias gradient sum_b dada[b][j] is the same records summed over batch as well
+    add(np1, Gd + ol[VBX_L_G1B] + 2 * d.D, d.B * chunks, 2 * d.D, rec, 1, 0, 0, 2 * d.D, 0, 0);
+    add(np2, Gd + ol[VBX_L_G1B], d.B * chunks, 2 * d.D, rec, 1, 0, 0, 2 * d.D, 0, 0);
+  }
+  add(cp, Gd + ol[VBX_L_FF2B], d.B * chunks, d.D, d.D, 1, 0, 0, d.D, 0, 0);                               // FeedForward[3].bias
+  add(cs, Gd + ol[VBX_L_FF1B], vbx_geglu_bwd_colsum_slabs(), 2 * d.Fp, 2L * d.Fp, 1, 0, 0, 2 * d.F, 1, d.F);   // FeedForward[0].bias
+  if (m->qk_norm) {
+    const int rows = d.B * vbx_attn_bwd_fused_tiles(d.Np);
+    add(gp, Gd + ol[VBX_L_QG], rows, d.H * 64, d.H * 64L, 1, 0, 0, d.H * 64, 0, 0);
+    add(gp + (size_t)rows * d.H * 64, Gd + ol[VBX_L_KG], rows, d.H * 64, d.H * 64L, 1, 0, 0, d.H * 64, 0, 0);
+  }
+}
+
+// GateLoop block of layer l: a.dx is the gradient of x_gl = LayerNorm(s) + x0; the residual branch stays in a.dx
+static int backward_gateloop(const vbx_model* m, const Dims& d, const WPack& w, const Acts& a, int l, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  const float* P = m->params;
+  float* Gd = m->grads;
+  const long* o = m->off + VBX_NG + (long)l * VBX_NL;
+  const ALayer& y = a.layer[l];
+  const int chunks = vbx_rmsnorm_bwd_chunks(d.Np), ln_chunks = (d.Np + 15) / 16;
+  CK(vbx_layernorm_bwd(y.gls, P + o[VBX_L_GLLNW], a.dx, a.gl_ds, a.npart, d.B, d.Np, d.D, 1e-5f, stream));
+  CK(vbx_reduce_norm_partials(a.npart, a.tscratch, 2 * d.D, d.B, ln_chunks, d.D, 0, stream));  // [B][dw|db]
+  CK(vbx_sum_rows_f32(a.tscratch, d.B, 2 * d.D, Gd + o[VBX_L_GLLNW], 2 * d.D, 0, stream));
+  CK(vbx_gateloop_scan_bwd(y.glp, y.glh, a.gl_ds, a.gl_dp, d.B, d.Np, d.D, stream));
+  CK(gemm_nn_bf16(a.gl_dp, 3 * d.D, w.layer[l].glw, d.D, (int)d.M, d.D, 3 * d.D, a.dhn, d.D, st));
+  CK(wgrad(a.gl_dp, 3 * d.D, y.hg, d.D, 3 * d.D, d.D, d.M, a.slabs, Gd + o[VBX_L_GLW], 3 * d.D, d.D, 0, 0, st));
+  CK(vbx_rmsnorm_bwd(layer_input(m, a, l), P + o[VBX_L_GLG], 0, a.dhn, a.dx, a.dx, a.dxb, a.npart, nullptr, d.B, d.Np, 0, d.Np, d.D, stream));
+  CK(vbx_reduce_norm_partials(a.npart, a.tscratch, 2 * d.D, d.B, chunks, d.D, 0, stream));
+  CK(vbx_sum_rows_f32(a.tscratch, d.B, 2 * d.D, Gd + o[VBX_L_GLG], d.D, 0, stream));
+  return 0;
+}
+
+// u-net: a.dx = d(input of layer l).  Second half: through the skip combiner -- d(bias), dW = dx^T . cat, d(cat) = dx . W -> d(x) | d(skip)
+// (:458-463); first half: the layer's input also fed the combiner of layer L-1-l
+static int backward_unet(const vbx_model* m, const Dims& d, const WPack& w, const Acts& a, int l, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (l < d.L / 2) return vbx_unet_addskip(a.dx, a.dxb, a.dskip[l], d.M * d.D, stream);
+  float* Gd = m->grads;
+  const long* o = m->off + VBX_NG + (long)l * VBX_NL;
+  const int S = m->gateloop ? 3 : 2, p = d.L - 1 - l, M = (int)d.M;
+  CK(vbx_colsum_f32(a.dx, M, d.D, d.D, Gd + o[VBX_L_SKB], a.cs_scratch, stream));
+  CK(vbx_unet_cat(a.xs[S * l], a.xs[S * p], m->skip_scale, nullptr, a.catb, d.M, d.D, stream));
+  CK(wgrad(a.dxb, d.D, a.catb, 2 * d.D, d.D, 2 * d.D, d.M, a.slabs, Gd + o[VBX_L_SKW], d.D, 2 * d.D, 0, 0, st));
+  vbx_gemm_desc g{};
+  g.mode = VBX_GEMM_NN; g.epilogue = VBX_EPI_F32; g.M = M; g.N = 2 * d.D; g.K = d.D; g.lda = d.D; g.ldb = 2 * d.D; g.ldc = 2 * d.D;
+  g.A = a.dxb; g.B = w.layer[l].skw; g.C = a.dcat;
+  CK(vbx_gemm(&g, stream));
+  return vbx_unet_split(a.dcat, m->skip_scale, a.dx, a.dxb, a.dskip[p], d.M, d.D, stream);
+}
+
+extern "C" int vbx_model_backward_layer(const vbx_model* m, const vbx_io* io, int l, void* stream) {
   CK(check_model(m));
   VBX_REQUIRE(m->training && m->grads && l >= 0 && l < m->L, "vbx_model_backward_layer: bad layer / not training");
+  VBX_REQUIRE(io || !(m->ff_dropout > 0.f || m->attn_dropout > 0.f), "vbx_model_backward_layer: a model with dropout needs the forward's io");
   hipStream_t st = (hipStream_t)stream;
   const Dims d = dims_of(m);
   WPack w;
@@ -834,243 +813,106 @@ static int backward_layer_impl(const vbx_model* m, const vbx_io* io, int l, void
   float* Gd = m->grads;
   const long* o = m->off + VBX_NG + (long)l * VBX_NL;
   const ALayer& y = a.layer[l];
+  const WLayer& wl = w.layer[l];
   const float* ada_l = a.ada + (size_t)l * d.B * 4 * d.D;
   float* dada_l = a.dada + (size_t)l * d.B * 4 * d.D;
-  const int chunks = vbx_rmsnorm_bwd_chunks(d.Np), ln_chunks = (d.Np + 15) / 16;
   const int M = (int)d.M;
   const int S = m->gateloop ? 3 : 2;
   const float* x_in = m->gateloop ? a.xs[S * l + 1] : layer_input(m, a, l);   // input of the attention block
   const float* x_mid = a.xs[S * l + S - 1];  // input of the feed-forward block
+  const bool drop_on = io && io->dropout != 0;
+  const uint8_t* attn_mask_p = io ? io->attn_mask_p : nullptr;
+  const float* q_gamma = m->qk_norm ? P + o[VBX_L_QG] : nullptr;
+  const float* k_gamma = m->qk_norm ? P + o[VBX_L_KG] : nullptr;
+  // adaptive norms: gamma | beta come from the layer's adaLN projections [B][g1 b1 g2 b2], row stride 4 D; plain: one gamma vector
+  const float* g1 = m->plain_norm ? P + o[VBX_L_N1G] : ada_l;
+  const float* g2 = m->plain_norm ? P + o[VBX_L_N2G] : ada_l + 2 * d.D;
+  const long gstride = m->plain_norm ? 0 : 4 * d.D;
 
-  static const bool batched = !(getenv("VBX_BATCH_REDUCE") && atoi(getenv("VBX_BATCH_REDUCE")) == 0);  // 0: one launch per reduction (A/B)
-  // adaLN weight gradients in factor form: nothing of the projections' backward is left per layer (bias gradient: two jobs of the
-  // batched reduce; d(time_emb): one launch for all layers after layer 0) -- VBX_ADALN_BWD_ALL=0: the per-layer launch (A/B)
-  static const bool ada_all_env = !(getenv("VBX_ADALN_BWD_ALL") && atoi(getenv("VBX_ADALN_BWD_ALL")) == 0);
-  const bool ada_all = ada_all_env && batched && m->adaln_factors && !m->plain_norm;
-  // vbx_model.defer_reduce: this layer's partial records stay in its own region; layer 0 reduces every layer's (VBX_DEFER_REDUCE=0: A/B).
-  // GateLoop re-uses npart for its own immediate reductions and the u-net combiner cs_scratch: those models reduce per layer.
-  static const bool defer_env = !(getenv("VBX_DEFER_REDUCE") && atoi(getenv("VBX_DEFER_REDUCE")) == 0);
-  // The per-layer adaLN backward (materialised weight gradients) consumes dada_l right away: it needs the per-layer reduce too.
-  const bool defer = defer_env && batched && m->defer_reduce && !m->gateloop && !m->unet && (m->plain_norm || ada_all);
-  const int rr = defer ? l : 0;
+  const LayerPlan pl = layer_plan(m);
+  const int rr = pl.defer ? l : 0;  // region of this layer's partial records
   float* const npart = a.npart + rr * a.np_stride;
   float* const npart2 = a.npart2 + rr * a.np_stride;
   float* const cpart = a.cpart + rr * a.cp_stride;
   float* const gpart = a.gpart + rr * a.gp_stride;
-  float* const csl = defer ? a.cs_layers + rr * a.cs_stride : a.cs_scratch;  // GEGLU-backward column-sum slabs
-  const bool batch_wg = batch_wgrad_on();
-  const SqLayout sql = sq_layout(d);
-  float* const sqb = (m->sq_partials && batch_wg) ? m->sq_partials + (long)l * sql.per_layer : nullptr;
-  auto sq_at = [&](int i) { return sqb ? sqb + sql.off[i] : nullptr; };
+  float* const csl = pl.defer ? a.cs_layers + rr * a.cs_stride : a.cs_scratch;  // GEGLU-backward column-sum slabs
+  // the layer's four weight gradients: slab reductions recorded in wj (one launch, own slab region each); the GEMMs recorded in wgg
+  // (one grouped launch) unless the 128-wide kernels are selected -- then each is launched where it is recorded
   vbx_skr_jobs wj{};
-  vbx_skr_jobs* wjp = batch_wg ? &wj : nullptr;
   WgradGroup wgg;
-  WgradGroup* wgp = (batch_wg && group_wgrad() && a.dxb2) ? &wgg : nullptr;
-  const int gs = (wgp && vbx_gemm_path() != 1) ? wgrad_splits3(d) : 0;  // split count of the grouped 256-tile launch
+  WgradGroup* wgp = group_wgrad() ? &wgg : nullptr;
+  const int gs = wgp ? wgrad_splits3(d) : 0;
   u16* dxb_attn = wgp ? a.dxb2 : a.dxb;  // bf16 dx entering the attention half (see Acts::dxb2)
   const size_t sfl = a.slab_floats;
-  // ---- FeedForward
-  { ProfScope ps("dgrad ff_out", st); CK(gemm_nn_bf16(a.dxb, d.D, w.layer[l].w2, d.Fp, M, d.Fp, d.D, a.dg, d.Fp, st)); }
-  CK(wgrad(a.dxb, d.D, y.g, d.Fp, d.D, d.Fp, d.M, a.slabs, Gd + o[VBX_L_FF2W], d.D, d.F, 0, 0, st, wjp, wgp, gs, sq_at(0)));
-  VBX_REQUIRE(io || !(m->ff_dropout > 0.f || m->attn_dropout > 0.f), "vbx_model_backward_layer: a model with dropout needs the forward's io");
-  const bool drop_on = io && io->dropout != 0;
+  const SqLayout sql = sq_layout(d);
+  float* const sqb = m->sq_partials ? m->sq_partials + (long)l * sql.per_layer : nullptr;
+  auto sq_at = [&](int i) { return sqb ? sqb + sql.off[i] : nullptr; };
+
+  // ---- FeedForward half
+  { ProfScope ps("dgrad ff_out", st); CK(gemm_nn_bf16(a.dxb, d.D, wl.w2, d.Fp, M, d.Fp, d.D, a.dg, d.Fp, st)); }
+  CK(wgrad(a.dxb, d.D, y.g, d.Fp, d.D, d.Fp, d.M, a.slabs, Gd + o[VBX_L_FF2W], d.D, d.F, 0, 0, st, &wj, wgp, gs, sq_at(0)));
   if (drop_on && m->ff_dropout > 0.f)  // the same mask on the gradient of the GEGLU output
     CK(vbx_dropout_rows(nullptr, a.dg, d.M, d.Fp, d.Fp, io->drop_seed, 2u * l + 1u, m->ff_dropout, stream));
-  if (batched) {  // gated-GELU backward + FeedForward[0].bias partials in one pass (reduced below)
-    CK(vbx_geglu_bwd_colsum(y.h1, a.dg, a.dh1, M, d.Fp, csl, stream));
-  } else {
-    CK(vbx_geglu_bwd(y.h1, a.dg, a.dh1, M, d.Fp, stream));
-    CK(vbx_colsum_bf16(a.dh1, M, 2 * d.Fp, 2 * d.Fp, Gd + o[VBX_L_FF1B], 2 * d.F, 1, d.F, a.cs_scratch, stream));
-  }
-  { ProfScope ps("dgrad ff_in", st); CK(gemm_nn_bf16(a.dh1, 2 * d.Fp, w.layer[l].w1, d.D, M, d.D, 2 * d.Fp, a.dhn, d.D, st)); }
-  CK(wgrad(a.dh1, 2 * d.Fp, y.hn2, d.D, 2 * d.Fp, d.D, d.M, a.slabs + sfl, Gd + o[VBX_L_FF1W], 2 * d.F, d.D, 1, d.F, st, wjp, wgp, gs, sq_at(1)));
+  CK(vbx_geglu_bwd_colsum(y.h1, a.dg, a.dh1, M, d.Fp, csl, stream));  // gated-GELU backward + FeedForward[0].bias partials in one pass
+  { ProfScope ps("dgrad ff_in", st); CK(gemm_nn_bf16(a.dh1, 2 * d.Fp, wl.w1, d.D, M, d.D, 2 * d.Fp, a.dhn, d.D, st)); }
+  CK(wgrad(a.dh1, 2 * d.Fp, y.hn2, d.D, 2 * d.Fp, d.D, d.M, a.slabs + sfl, Gd + o[VBX_L_FF1W], 2 * d.F, d.D, 1, d.F, st, &wj, wgp, gs, sq_at(1)));
   // (the column sums of the incoming dx -- FeedForward[3].bias gradient -- ride along in the same pass)
-  CK(wgrad_join(st));  // the FeedForward-out wgrad reads a.dxb, which the norm backward below overwrites
-  if (m->plain_norm) {
-    CK(vbx_rmsnorm_bwd(x_mid, P + o[VBX_L_N2G], 0, a.dhn, a.dx, a.dx, dxb_attn, npart, cpart, d.B, d.Np, 0, d.Np, d.D, stream));
-    if (!batched) {
-      CK(vbx_reduce_norm_partials(npart, a.tscratch, 2 * d.D, d.B, chunks, d.D, 0, stream));
-      CK(vbx_sum_rows_f32(a.tscratch, d.B, 2 * d.D, Gd + o[VBX_L_N2G], d.D, 0, stream));
-    }
-  } else {
-    CK(vbx_rmsnorm_bwd(x_mid, ada_l + 2 * d.D, 4 * d.D, a.dhn, a.dx, a.dx, dxb_attn, npart, cpart, d.B, d.Np, 0, d.Np, d.D,
-                       stream));
-    if (!batched) CK(vbx_reduce_norm_partials(npart, dada_l + 2 * d.D, 4 * d.D, d.B, chunks, d.D, 0, stream));
-  }
-  if (!batched) CK(vbx_reduce_col_partials(cpart, Gd + o[VBX_L_FF2B], a.tscratch, d.B, chunks, d.D, stream));
-  // ---- Attention
-  // delta = rowsum(dO * O) of the attention backward rides in this GEMM's epilogue when the tile serving it has one (128 x 256 tile:
-  // gemm_epi3.hpp::Epi3BF16Delta); otherwise the attention entry point runs its own pass over O and dO.
-  // MEASURED (round 5, same box, in situ): the GEMM 21.4 -> 33.4 us per launch against 5 us saved in the attention stage -- the row
-  // stage's 16 read-backs per wave each gain a dependent 16-byte load, three lane exchanges and a division on the critical path of a
-  // tile that has only two workgroups per CU to hide them.  A loser by 7 us per layer: OFF by default, VBX_DELTA_FUSED=1 re-enables it.
-  static const bool delta_fused = getenv("VBX_DELTA_FUSED") && atoi(getenv("VBX_DELTA_FUSED")) != 0;
-  bool have_delta = false;
-  {
-    ProfScope ps("dgrad to_out", st);
-    vbx_gemm_desc g{};
-    g.mode = VBX_GEMM_NN; g.epilogue = VBX_EPI_BF16; g.M = M; g.N = d.I; g.K = d.D; g.lda = d.D; g.ldb = d.I; g.ldc = d.I;
-    g.A = dxb_attn; g.B = w.layer[l].out; g.C = a.dO;
-    int rc = VBX_EUNSUPPORTED;
-    if (delta_fused && vbx_attn_bwd_variant() != 2) {
-      g.delta_o = y.oh; g.delta = a.delta; g.H = d.H; g.Np = d.Np;
-      rc = vbx_gemm(&g, st);
-      have_delta = rc == 0;
-    }
-    if (rc == VBX_EUNSUPPORTED) {
-      g.delta_o = nullptr; g.delta = nullptr;
-      rc = vbx_gemm(&g, st);
-    }
-    CK(rc);
-  }
-  const u16* attn_out = have_delta ? nullptr : y.oh;  // NULL: a.delta is already there
-  CK(wgrad(dxb_attn, d.D, y.o, d.I, d.D, d.I, d.M, a.slabs + 2 * sfl, Gd + o[VBX_L_OUTW], d.D, d.I, 0, 0, st, wjp, wgp, gs, sq_at(2)));
-  static const bool fused_qk = !(getenv("VBX_ATTN_FUSED_QKBWD") && atoi(getenv("VBX_ATTN_FUSED_QKBWD")) == 0);  // 0: A/B
-  if (fused_qk) {
-    ProfScope ps("bwd attention", st);
-    CK(vbx_attn_bwd_fused_dropout(y.q16, y.k16, y.qb, y.kb, y.v, io ? io->attn_mask_p : nullptr, attn_out, 1, a.dO, y.lse, a.delta, y.qrn,
-                                  y.krn, m->qk_norm ? P + o[VBX_L_QG] : nullptr, m->qk_norm ? P + o[VBX_L_KG] : nullptr, m->rot_cos,
-                                  m->rot_sin, m->qk_norm ? 8.0f : 0.0f, a.dqkv, 3 * d.I, gpart, d.B, d.H, d.Np, m->attn_scale,
-                                  a.attn_scratch, drop_on ? y.dbr : nullptr, y.dbc, m->attn_dropout, stream));
-    if (m->qk_norm && !batched) {
-      const int rows = d.B * vbx_attn_bwd_fused_tiles(d.Np);
-      CK(vbx_sum_rows_f32(gpart, rows, (long)d.H * 64, Gd + o[VBX_L_QG], (long)d.H * 64, 0, stream));
-      CK(vbx_sum_rows_f32(gpart + (size_t)rows * d.H * 64, rows, (long)d.H * 64, Gd + o[VBX_L_KG], (long)d.H * 64, 0, stream));
-    }
-  } else {
-    if (y.dbr && drop_on)
-      CK(vbx_attn_bwd_dropout(y.q16, y.k16, y.qb, y.kb, y.v, io ? io->attn_mask_p : nullptr, attn_out, 1, a.dO, y.lse, a.delta, a.dq, a.dk,
-                              a.dqkv + 2 * d.I, 3 * d.I, d.B, d.H, d.Np, m->attn_scale, y.dbr, y.dbc, m->attn_dropout, stream));
-    else
-      CK(vbx_attn_bwd(y.q16, y.k16, y.qb, y.kb, y.v, io ? io->attn_mask_p : nullptr, attn_out, 1, a.dO, y.lse, a.delta, a.dq, a.dk,
-                      a.dqkv + 2 * d.I, 3 * d.I, d.B, d.H, d.Np, m->attn_scale, a.attn_scratch, stream));
-    CK(vbx_qknorm_rope_bwd(a.dq, a.dk, y.q16, y.k16, y.qrn, y.krn, m->qk_norm ? P + o[VBX_L_QG] : nullptr,
-                           m->qk_norm ? P + o[VBX_L_KG] : nullptr, m->rot_cos, m->rot_sin, m->qk_norm ? 8.0f : 0.0f, a.dqkv,
-                           3 * d.I, gpart, d.B, d.H, d.Np, vbx_attn_q_prescale(m->attn_scale), stream));
-    if (m->qk_norm) {
-      const int rows = vbx_qknorm_rope_bwd_gpart_rows(d.B);
-      CK(vbx_sum_rows_f32(gpart, rows, (long)d.H * 64, Gd + o[VBX_L_QG], (long)d.H * 64, 0, stream));
-      CK(vbx_sum_rows_f32(gpart + (size_t)rows * d.H * 64, rows, (long)d.H * 64, Gd + o[VBX_L_KG], (long)d.H * 64, 0, stream));
-    }
-  }
-  { ProfScope ps("dgrad to_qkv", st); CK(gemm_nn_bf16(a.dqkv, 3 * d.I, w.layer[l].qkv, d.D, M, d.D, 3 * d.I, a.dhn, d.D, st)); }
-  CK(wgrad(a.dqkv, 3 * d.I, y.hn1, d.D, 3 * d.I, d.D, d.M, a.slabs + 3 * sfl, Gd + o[VBX_L_QKVW], 3 * d.I, d.D, 0, 0, st, wjp, wgp, gs, sq_at(3)));
-  if (wgg.n) { ProfScope ps("wgrad (4 GEMMs)", st); CK(vbx_gemm_tn_splitk_grouped(wgg.d, wgg.n, stream)); }  // every operand is still live here (a.dxb: see dxb_attn)
-  // VBX_LAYER_REDUCE=1: the slab reduction rides in the layer's batched reduce launch below (vbx_layer_reduce, bit-identical).
-  // MEASURED (round 5, two interleaved runs per arm on one box): 9.95-10.02 vs 9.85-9.93 ms per step -- the 16 us of slab traffic now
-  // sit behind the norm backward instead of overlapping the drain of the weight-gradient GEMM.  A loser: OFF by default.
-  static const bool fuse_red_env = getenv("VBX_LAYER_REDUCE") && atoi(getenv("VBX_LAYER_REDUCE")) != 0;
-  const bool fuse_red = fuse_red_env && batched && wj.n > 0 && !defer;
-  if (wj.n && !fuse_red) { ProfScope ps("wgrad slab reduce", st); CK(vbx_splitk_reduce_multi(&wj, stream)); }
-  CK(wgrad_join(st));  // the to_out wgrad reads a.dxb, which the norm backward below overwrites
-  if (m->plain_norm) {
-    CK(vbx_rmsnorm_bwd(x_in, P + o[VBX_L_N1G], 0, a.dhn, a.dx, a.dx, a.dxb, npart2, nullptr, d.B, d.Np, 0, d.Np, d.D, stream));
-    if (!batched) {
-      CK(vbx_reduce_norm_partials(npart2, a.tscratch, 2 * d.D, d.B, chunks, d.D, 0, stream));
-      CK(vbx_sum_rows_f32(a.tscratch, d.B, 2 * d.D, Gd + o[VBX_L_N1G], d.D, 0, stream));
-    }
-  } else {
-    CK(vbx_rmsnorm_bwd(x_in, ada_l, 4 * d.D, a.dhn, a.dx, a.dx, a.dxb, npart2, nullptr, d.B, d.Np, 0, d.Np, d.D, stream));
-    if (!batched) CK(vbx_reduce_norm_partials(npart2, dada_l, 4 * d.D, d.B, chunks, d.D, 0, stream));
-  }
-  if (batched) {
-    // ---- every small reduction of the layer in ONE launch (they cost ~0.5 ms per step as separate launches); deferred: layer 0
-    // issues the jobs of ALL layers, six layers per launch
-    vbx_mr_jobs jb{};
-    auto add = [&](const float* src, float* dst, int rows, int cols, long row_stride, int batches, long sbs, long dbs, int dst_len,
-                   int rowmap, int F) {
-      vbx_mr_job& j = jb.job[jb.n++];
-      j.src = src; j.dst = dst; j.rows = rows; j.cols = cols; j.row_stride = row_stride; j.batches = batches;
-      j.src_bstride = sbs; j.dst_bstride = dbs; j.dst_len = dst_len; j.rowmap = rowmap; j.F = F;
-    };
-    const long rec = 2L * d.D;
-    auto layer_jobs = [&](int ll, int region) {  // at most 8 jobs
-      const long* ol = m->off + VBX_NG + (long)ll * VBX_NL;
-      float* dada_ll = a.dada + (size_t)ll * d.B * 4 * d.D;
-      const float* np1 = a.npart + region * a.np_stride;
-      const float* np2 = a.npart2 + region * a.np_stride;
-      const float* cp = a.cpart + region * a.cp_stride;
-      const float* gp = a.gpart + region * a.gp_stride;
-      const float* cs = defer ? a.cs_layers + region * a.cs_stride : a.cs_scratch;
-      if (m->plain_norm) {  // d(gamma) = first half of the records, summed over batch and chunks
-        add(np1, Gd + ol[VBX_L_N2G], d.B * chunks, d.D, rec, 1, 0, 0, d.D, 0, 0);
-        add(np2, Gd + ol[VBX_L_N1G], d.B * chunks, d.D, rec, 1, 0, 0, d.D, 0, 0);
-      } else {              // per-batch d(gamma | beta) of the two adaLN norms -> dada_l [B][g1 b1 g2 b2]
-        add(np1, dada_ll + 2 * d.D, chunks, 2 * d.D, rec, d.B, (long)chunks * rec, 4L * d.D, 2 * d.D, 0, 0);
-        add(np2, dada_ll, chunks, 2 * d.D, rec, d.B, (long)chunks * rec, 4L * d.D, 2 * d.D, 0, 0);
-      }
-      if (ada_all) {  // factor form: the projections' bias gradient sum_b dada[b][j] is the same records summed over batch as well
-        add(np1, Gd + ol[VBX_L_G1B] + 2 * d.D, d.B * chunks, 2 * d.D, rec, 1, 0, 0, 2 * d.D, 0, 0);
-        add(np2, Gd + ol[VBX_L_G1B], d.B * chunks, 2 * d.D, rec, 1, 0, 0, 2 * d.D, 0, 0);
-      }
-      add(cp, Gd + ol[VBX_L_FF2B], d.B * chunks, d.D, d.D, 1, 0, 0, d.D, 0, 0);                               // FeedForward[3].bias
-      add(cs, Gd + ol[VBX_L_FF1B], vbx_geglu_bwd_colsum_slabs(), 2 * d.Fp, 2L * d.Fp, 1, 0, 0, 2 * d.F, 1, d.F);   // FeedForward[0].bias
-      if (fused_qk && m->qk_norm) {
-        const int rows = d.B * vbx_attn_bwd_fused_tiles(d.Np);
-        add(gp, Gd + ol[VBX_L_QG], rows, d.H * 64, d.H * 64L, 1, 0, 0, d.H * 64, 0, 0);
-        add(gp + (size_t)rows * d.H * 64, Gd + ol[VBX_L_KG], rows, d.H * 64, d.H * 64L, 1, 0, 0, d.H * 64, 0, 0);
-      }
-    };
-    if (!defer) {
-      layer_jobs(l, 0);
-      if (fuse_red) { ProfScope ps("layer reduce (fused)", st); CK(vbx_layer_reduce(&wj, &jb, stream)); }
-      else CK(vbx_multi_reduce(&jb, stream));
-    } else if (l == 0) {
-      ProfScope ps("partials reduce (all)", st);
-      for (int ll = d.L - 1; ll >= 0; ll--) {
-        layer_jobs(ll, ll);
-        if (jb.n + 8 > VBX_MR_MAX || ll == 0) {
-          CK(vbx_multi_reduce(&jb, stream));
-          jb.n = 0;
-        }
+  CK(vbx_rmsnorm_bwd(x_mid, g2, gstride, a.dhn, a.dx, a.dx, dxb_attn, npart, cpart, d.B, d.Np, 0, d.Np, d.D, stream));
+
+  // ---- attention half
+  // (Tried: delta = rowsum(dO * O) in the epilogue of the to_out dgrad; removed, numbers in docs/history.md.  The attention entry
+  // point runs its own pass over O and dO.)
+  { ProfScope ps("dgrad to_out", st); CK(gemm_nn_bf16(dxb_attn, d.D, wl.out, d.I, M, d.I, d.D, a.dO, d.I, st)); }
+  CK(wgrad(dxb_attn, d.D, y.o, d.I, d.D, d.I, d.M, a.slabs + 2 * sfl, Gd + o[VBX_L_OUTW], d.D, d.I, 0, 0, st, &wj, wgp, gs, sq_at(2)));
+  { ProfScope ps("bwd attention", st);
+    CK(vbx_attn_bwd_fused_dropout(y.q16, y.k16, y.qb, y.kb, y.v, attn_mask_p, y.oh, 1, a.dO, y.lse, a.delta, y.qrn, y.krn, q_gamma, k_gamma,
+                                  m->rot_cos, m->rot_sin, m->qk_norm ? 8.0f : 0.0f, a.dqkv, 3 * d.I, gpart, d.B, d.H, d.Np, m->attn_scale,
+                                  a.attn_scratch, drop_on ? y.dbr : nullptr, y.dbc, m->attn_dropout, stream)); }
+  { ProfScope ps("dgrad to_qkv", st); CK(gemm_nn_bf16(a.dqkv, 3 * d.I, wl.qkv, d.D, M, d.D, 3 * d.I, a.dhn, d.D, st)); }
+  CK(wgrad(a.dqkv, 3 * d.I, y.hn1, d.D, 3 * d.I, d.D, d.M, a.slabs + 3 * sfl, Gd + o[VBX_L_QKVW], 3 * d.I, d.D, 0, 0, st, &wj, wgp, gs, sq_at(3)));
+
+  // ---- the layer's weight gradients: every operand is still live here (a.dxb: see dxb_attn)
+  // (Tried: the slab reduction inside the small-reductions launch below, vbx_layer_reduce; removed, numbers in docs/history.md.)
+  if (wgg.n) { ProfScope ps("wgrad (4 GEMMs)", st); CK(vbx_gemm_tn_splitk_grouped(wgg.d, wgg.n, stream)); }
+  if (wj.n) { ProfScope ps("wgrad slab reduce", st); CK(vbx_splitk_reduce_multi(&wj, stream)); }
+  CK(vbx_rmsnorm_bwd(x_in, g1, gstride, a.dhn, a.dx, a.dx, a.dxb, npart2, nullptr, d.B, d.Np, 0, d.Np, d.D, stream));
+
+  // ---- every small reduction of the layer in ONE launch (they cost ~0.5 ms per step as separate launches); deferred: layer 0
+  // issues the jobs of ALL layers, as many layers per launch as fit
+  vbx_mr_jobs jb{};
+  if (!pl.defer) {
+    layer_reduce_jobs(m, d, a, pl, l, 0, jb);
+    CK(vbx_multi_reduce(&jb, stream));
+  } else if (l == 0) {
+    ProfScope ps("partials reduce (all)", st);
+    for (int ll = d.L - 1; ll >= 0; ll--) {
+      layer_reduce_jobs(m, d, a, pl, ll, ll, jb);
+      if (jb.n + 8 > VBX_MR_MAX || ll == 0) {
+        CK(vbx_multi_reduce(&jb, stream));
+        jb.n = 0;
       }
     }
   }
-  if (m->gateloop) {
-    // ---- GateLoop: a.dx is the gradient of x_gl = LayerNorm(s) + x0; the residual branch stays in a.dx
-    CK(vbx_layernorm_bwd(y.gls, P + o[VBX_L_GLLNW], a.dx, a.gl_ds, a.npart, d.B, d.Np, d.D, 1e-5f, stream));
-    CK(vbx_reduce_norm_partials(a.npart, a.tscratch, 2 * d.D, d.B, ln_chunks, d.D, 0, stream));  // [B][dw|db]
-    CK(vbx_sum_rows_f32(a.tscratch, d.B, 2 * d.D, Gd + o[VBX_L_GLLNW], 2 * d.D, 0, stream));
-    CK(vbx_gateloop_scan_bwd(y.glp, y.glh, a.gl_ds, a.gl_dp, d.B, d.Np, d.D, stream));
-    CK(gemm_nn_bf16(a.gl_dp, 3 * d.D, w.layer[l].glw, d.D, M, d.D, 3 * d.D, a.dhn, d.D, st));
-    CK(wgrad(a.gl_dp, 3 * d.D, y.hg, d.D, 3 * d.D, d.D, d.M, a.slabs, Gd + o[VBX_L_GLW], 3 * d.D, d.D, 0, 0, st));
-    CK(vbx_rmsnorm_bwd(layer_input(m, a, l), P + o[VBX_L_GLG], 0, a.dhn, a.dx, a.dx, a.dxb, a.npart, nullptr, d.B, d.Np, 0, d.Np, d.D, stream));
-    CK(vbx_reduce_norm_partials(a.npart, a.tscratch, 2 * d.D, d.B, chunks, d.D, 0, stream));
-    CK(vbx_sum_rows_f32(a.tscratch, d.B, 2 * d.D, Gd + o[VBX_L_GLG], d.D, 0, stream));
-  }
-  if (m->unet && l >= d.L / 2) {
-    // ---- skip combiner: a.dx = d(combined input).  d(bias), dW = dx^T . cat, d(cat) = dx . W -> d(x) | d(skip)   (:458-463)
-    const int p = d.L - 1 - l;
-    CK(vbx_colsum_f32(a.dx, M, d.D, d.D, Gd + o[VBX_L_SKB], a.cs_scratch, stream));
-    CK(vbx_unet_cat(a.xs[S * l], a.xs[S * p], m->skip_scale, nullptr, a.catb, d.M, d.D, stream));
-    CK(wgrad(a.dxb, d.D, a.catb, 2 * d.D, d.D, 2 * d.D, d.M, a.slabs, Gd + o[VBX_L_SKW], d.D, 2 * d.D, 0, 0, st));
-    vbx_gemm_desc g{};
-    g.mode = VBX_GEMM_NN; g.epilogue = VBX_EPI_F32; g.M = M; g.N = 2 * d.D; g.K = d.D; g.lda = d.D; g.ldb = 2 * d.D; g.ldc = 2 * d.D;
-    g.A = a.dxb; g.B = w.layer[l].skw; g.C = a.dcat;
-    CK(vbx_gemm(&g, stream));
-    CK(wgrad_join(st));  // the combiner's wgrad reads a.dxb, rewritten next
-    CK(vbx_unet_split(a.dcat, m->skip_scale, a.dx, a.dxb, a.dskip[p], d.M, d.D, stream));
-  } else if (m->unet) {
-    // the input of a first-half layer also fed the combiner of layer L-1-l
-    CK(vbx_unet_addskip(a.dx, a.dxb, a.dskip[l], d.M * d.D, stream));
-  }
+
+  // ---- tails
+  if (m->gateloop) CK(backward_gateloop(m, d, w, a, l, stream));
+  if (m->unet) CK(backward_unet(m, d, w, a, l, stream));
   if (m->plain_norm) return 0;
-  // ---- this layer's adaLN projections (their 4 weights / 4 biases are contiguous): dW, dbias, and d(time_emb) +=
+  // this layer's adaLN projections (their 4 weights / 4 biases are contiguous): dW, dbias, and d(time_emb) +=
   // (adaln_factors: the weight gradient dada_l^T . temb is not materialised -- include/vbx.h, vbx_adam_adaln_factors)
-  if (ada_all) {
+  if (pl.ada_all) {
     if (l == 0) {  // the layers run L-1 .. 0: every dada_l is in place
       ProfScope ps("adaLN dtemb (all)", st);
       CK(vbx_adaln_dtemb_all(w.adah, a.dada, a.dtemb, a.ada_scratch, d.L, d.B, d.Th, 4 * d.D, stream));
     }
     return 0;
   }
-  CK(vbx_adaln_proj_bwd(m->stack_only ? io->cond : a.temb, w.adah + (size_t)l * 4 * d.D * d.Th, dada_l,
-                        m->adaln_factors ? nullptr : Gd + o[VBX_L_G1W], Gd + o[VBX_L_G1B], a.dtemb,
-                        a.ada_scratch, d.B, d.Th, 4 * d.D, l == d.L - 1 ? 0 : 1, stream));
-  return 0;
+  return vbx_adaln_proj_bwd(m->stack_only ? io->cond : a.temb, w.adah + (size_t)l * 4 * d.D * d.Th, dada_l,
+                            m->adaln_factors ? nullptr : Gd + o[VBX_L_G1W], Gd + o[VBX_L_G1B], a.dtemb,
+                            a.ada_scratch, d.B, d.Th, 4 * d.D, l == d.L - 1 ? 0 : 1, stream);
 }
 
-static int backward_embed_impl(const vbx_model* m, const vbx_io* io, void* stream) {
+extern "C" int vbx_model_backward_embed(const vbx_model* m, const vbx_io* io, void* stream) {
   CK(check_model(m));
   VBX_REQUIRE(m->training && m->grads && io && (m->stack_only ? io->dx != nullptr : io->times != nullptr),
               "vbx_model_backward_embed: needs a training forward");
@@ -1114,7 +956,6 @@ static int backward_embed_impl(const vbx_model* m, const vbx_io* io, void* strea
     carve_wpack(m, w);
     CK(gemm_nn_bf16(a.deb, d.D, w.embb, d.Ke, (int)d.M0, d.D, d.D, a.dxc, d.D, st));
     CK(gemm_nn_bf16(a.deb, d.D, w.embb + d.D + d.E, d.Ke, (int)d.M0, d.D, d.D, a.dxc + (size_t)d.M0 * d.D, d.D, st));
-    CK(wgrad_join(st));  // a.slabs: the to_embed weight gradient above may still be reading it on the side stream
     vbx_gemm_desc g{};
     g.mode = VBX_GEMM_TN; g.epilogue = VBX_EPI_SPLITK; g.M = d.D; g.N = d.Kp; g.K = (int)(2 * d.M0); g.lda = d.D; g.ldb = d.Kp;
     g.A = a.dxc; g.B = a.xcb; g.C = a.slabs; g.splits = wgrad_splits(d.D, d.Kp, 2 * d.M0);
@@ -1125,24 +966,6 @@ static int backward_embed_impl(const vbx_model* m, const vbx_io* io, void* strea
   CK(vbx_time_embed_bwd(io->times, P + G[VBX_P_SINW], P + G[VBX_P_T1W], a.four, a.pre, a.dtemb, Gd + G[VBX_P_SINW],
                         Gd + G[VBX_P_T1W], Gd + G[VBX_P_T1B], a.tscratch, d.B, d.D, d.Th, stream));
   return 0;
-}
-
-// Public backward stages: each returns with every gradient of the stage ordered before later work on the caller's stream
-// (weight gradients run on the side stream, see wgrad()).
-extern "C" int vbx_model_backward_head(const vbx_model* m, const vbx_io* io, const float* gscale, void* stream) {
-  const int rc = backward_head_impl(m, io, gscale, stream);
-  const int rj = wgrad_join((hipStream_t)stream);
-  return rc ? rc : rj;
-}
-extern "C" int vbx_model_backward_layer(const vbx_model* m, const vbx_io* io, int l, void* stream) {
-  const int rc = backward_layer_impl(m, io, l, stream);
-  const int rj = wgrad_join((hipStream_t)stream);
-  return rc ? rc : rj;
-}
-extern "C" int vbx_model_backward_embed(const vbx_model* m, const vbx_io* io, void* stream) {
-  const int rc = backward_embed_impl(m, io, stream);
-  const int rj = wgrad_join((hipStream_t)stream);
-  return rc ? rc : rj;
 }
 
 // Segment table of the fused Adam + repack step (vbx_adam_step_packed): every parameter that vbx_model_pack_weights

@@ -31,6 +31,18 @@ from .engine import precise_enabled
 SPLIT_OFFSET_US = float(os.environ.get("VBX_SAMPLE_OFFSET_US", "60"))  # start delay of the second (third, ...) half-batch stream; 30 .. 250 us measured equal
 
 
+def _to_qkv_owns_cus(cfg, B, N):
+    """Does the library serve the model's inference to_qkv GEMM of a full batch with the weight-stationary kernel?  Asked of the
+    library (vbx_gemm_route: selected path, VBX_GEMM5, shape), not re-derived here; no buffers exist yet, so the pointer fields
+    carry an aligned placeholder."""
+    d, some = _lib.GemmDesc(), 256
+    Np, I = N + cfg["R"], cfg["H"] * 64
+    d.mode, d.epilogue, d.M, d.N, d.K, d.lda, d.ldb, d.f16 = _lib.VBX_GEMM_NT, _lib.VBX_EPI_QKV, B * Np, 3 * I, cfg["D"], cfg["D"], cfg["D"], 1
+    d.Np, d.H, d.qk_scale = Np, cfg["H"], 8.0 if cfg["qk_norm"] else 0.0
+    d.A = d.B = d.q16 = d.k16 = d.v16 = d.rot_cos = d.rot_sin = d.q_gamma = d.k_gamma = some
+    return _lib.call_value("vbx_gemm_route", d) == _lib.VBX_GEMM_KERNEL_GEMM5
+
+
 class _Part:
     """One concurrently integrated slice [lo, hi) of the batch: its engine and its views of the sampler's static buffers."""
 
@@ -46,8 +58,7 @@ class MidpointSampler:
             # kernels 317.5 against 298-303 -- the split was a remedy for THEIR idle phases).  VBX_SAMPLE_SPLIT=1 / 2 overrides.
             env = os.environ.get("VBX_SAMPLE_SPLIT")
             if env is None:
-                g5 = voicebox._cfg["D"] == 512 and os.environ.get("VBX_GEMM5", "1") != "0" and not precise_enabled()
-                env = "1" if g5 else "2"
+                env = "1" if not precise_enabled() and _to_qkv_owns_cus(voicebox._cfg, B, N) else "2"  # (the precise forward has its own GEMMs)
             if env not in ("1", "2"):
                 raise ValueError(f"VBX_SAMPLE_SPLIT must be 1 or 2 (concurrent half batches are the only measured, tested split), got {env!r}")
             split = int(env)
