@@ -278,6 +278,22 @@ int vbx_copy_cols_f32(const float* src, int ld_src, float* dst, long rows, int c
 int vbx_logmel(const float* audio, float* out, const float* window, const float* tw_re, const float* tw_im, const int* fb_start,
                const int* fb_len, const int* fb_off, const float* fb_w, int B, long T, int n_fft, int hop, int n_mels, int log_out,
                void* stream);
+/* Vocoder-free decode (LogMelCodec.mel_to_magnitude / griffin_lim; csrc/griffinlim.hip).
+ * vbx_mel_to_mag: mel fp32 [B, frames, n_mels] (dB when log_in, else power) -> mag fp32 [B, frames, n_bins] (frame-major)
+ *   = sqrt(max(pinv(fb^T) @ P, 0)), P = 10^(mel / 10) or mel; pinv_t [n_mels, n_bins] is the pseudo-inverse (taken in fp64 on the
+ *   host) stored mel-major.
+ * vbx_griffinlim: the torchaudio.functional.griffinlim loop (power = 1, length = None) with m = momentum / (1 + momentum):
+ *   mag [B, frames, n_bins], n_bins = n_fft / 2 + 1; spec_a [B, frames, n_bins, 2] holds the initial unit phasors (re, im) on entry,
+ *   spec_a / spec_b are the two kept spectra and are overwritten; fb [B, frames, win] is the frame buffer; wave [B, (frames - 1) * hop]
+ *   the result; window / tw_re / tw_im as vbx_logmel; renv [(frames - 1) * hop] the reciprocal window-square envelope of the kept
+ *   range.  2 n_iter + 2 launches, no host synchronisation.  Needs 0 < hop <= win <= n_fft, (frames - 1) * hop > n_fft / 2 and
+ *   vbx_griffinlim_lds_bytes(n_fft, win, hop) <= 65536. */
+int vbx_mel_to_mag(const float* mel, float* mag, const float* pinv_t, int B, int frames, int n_mels, int n_bins, int log_in,
+                   void* stream);
+int vbx_griffinlim_lds_bytes(int n_fft, int win, int hop);
+int vbx_griffinlim(const float* mag, float* spec_a, float* spec_b, float* fb, float* wave, const float* window, const float* tw_re,
+                   const float* tw_im, const float* renv, int B, int frames, int n_fft, int win, int hop, int n_iter, float m,
+                   void* stream);
 /* the same rows unrounded (fp32 [B*N, 2*D + E]): precise mode's to_embed operand */
 int vbx_embed_input_text_f32(const float* x, const float* cond, const uint8_t* cond_mask, const uint8_t* drop_mask,
                              const float* null_cond, const long* ids, int T, const float* table, int E, long null_id,

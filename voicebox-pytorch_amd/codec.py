@@ -1,18 +1,24 @@
 """The audio codec interface of VoiceBox(audio_enc_dec=...) (voicebox_pytorch.py:484-499) and LogMelCodec, the one encoder of the
 reference that has no learned weights (MelVoco.encode, :518-541: STFT -> HTK mel filter bank -> dB), served by one native kernel
-(csrc/mel.hip).  Pretrained codecs (EnCodec, Vocos) are downloads and are not part of this package: any nn.Module with the five
+(csrc/mel.hip), and its weight-free decode: least-squares inversion of the filter bank, then Griffin-Lim phase recovery on the device
+(mel_to_magnitude / griffin_lim, csrc/griffinlim.hip).  Pretrained codecs (EnCodec, Vocos) are downloads and are not part of this package: any nn.Module with the five
 members below can be passed as audio_enc_dec, inheritance from AudioEncoderDecoder is not required.
 
 PARITY UNPINNED: torchaudio is not a dependency and no fixture of it exists; LogMelCodec follows the published arithmetic of
 torchaudio.transforms.Spectrogram / MelScale / AmplitudeToDB at their defaults (power=2, center=True, pad_mode='reflect',
-normalized=False, f_min=0, norm=None, mel_scale='htk', top_db=None), restated in fp64 in tests/mel_ref.py.
+normalized=False, f_min=0, norm=None, mel_scale='htk', top_db=None), restated in fp64 in tests/mel_ref.py.  The decode side is
+UNPINNED likewise: griffin_lim follows the published loop of torchaudio.functional.griffinlim (power=1, length=None), restated with
+torch.stft / torch.istft in tests/griffinlim_ref.py; mel_to_magnitude is a least-squares inverse clamped at zero and is NOT
+torchaudio's InverseMelScale.
 """
+import functools
 import math
 
 import torch
 from torch import nn
 
 from . import _lib
+from .masks import take_draw
 
 
 class AudioEncoderDecoder(nn.Module):
@@ -48,28 +54,125 @@ def mel_filter_runs(n_fft, n_mels, sampling_rate, f_max, f_min=0.0):
     return i32(start), i32(length), i32(offset), torch.cat((w, torch.zeros(1, dtype=torch.float64)))
 
 
+def mel_filter_dense(n_fft, n_mels, sampling_rate, f_max):
+    """the same filters as one fp64 matrix [n_fft / 2 + 1, n_mels]"""
+    start, length, offset, weights = mel_filter_runs(n_fft, n_mels, sampling_rate, f_max)
+    fb = torch.zeros(n_fft // 2 + 1, n_mels, dtype=torch.float64)
+    for m in range(n_mels):
+        s, n, o = int(start[m]), int(length[m]), int(offset[m])
+        fb[s:s + n, m] = weights[o:o + n]
+    return fb
+
+
+def _check_stft_args(n_fft, win_length, hop_length):
+    if n_fft & (n_fft - 1) or not 256 <= n_fft <= 2048:
+        raise NotImplementedError(f"n_fft must be a power of two in 256 .. 2048 (got {n_fft})")
+    if not 0 < win_length <= n_fft or hop_length <= 0:
+        raise ValueError("need 0 < win_length <= n_fft, hop_length > 0")
+
+
+def _stft_tables(n_fft, win_length):
+    """fp64: the periodic Hann window of win_length samples centred in n_fft (torch.stft's placement), cos / -sin(2 pi k / n_fft)"""
+    win = torch.zeros(n_fft, dtype=torch.float64)
+    left = (n_fft - win_length) // 2
+    win[left:left + win_length] = torch.hann_window(win_length, periodic=True, dtype=torch.float64)
+    ang = 2.0 * math.pi * torch.arange(n_fft // 2, dtype=torch.float64) / n_fft
+    return win, ang.cos(), -ang.sin()
+
+
+def ola_reciprocal_envelope(n_fft, win_length, hop_length, frames):
+    """1 / (window-square envelope) of torch.istft on the kept range [n_fft / 2, n_fft / 2 + (frames - 1) * hop), fp64.  Raises
+    ValueError where torch.istft does: an envelope <= 1e-11 anywhere on that range (NOLA)."""
+    w2 = _stft_tables(n_fft, win_length)[0] ** 2
+    env = torch.zeros(n_fft + (frames - 1) * hop_length, dtype=torch.float64)
+    for f in range(frames):
+        env[f * hop_length:f * hop_length + n_fft] += w2
+    env = env[n_fft // 2:n_fft // 2 + (frames - 1) * hop_length]
+    if env.numel() == 0 or float(env.min()) <= 1e-11:
+        raise ValueError(f"window overlap-add envelope is zero somewhere (NOLA): win_length {win_length}, hop_length {hop_length}, "
+                         f"n_fft {n_fft}, {frames} frames")
+    return 1.0 / env
+
+
+@functools.lru_cache(maxsize=16)
+def _gl_tables(n_fft, win_length, hop_length, frames, device):
+    win, tw_re, tw_im = _stft_tables(n_fft, win_length)
+    renv = ola_reciprocal_envelope(n_fft, win_length, hop_length, frames)
+    return tuple(t.float().to(device) for t in (win, tw_re, tw_im, renv))
+
+
+def griffin_lim(magnitude, *, n_fft, win_length, hop_length, n_iter=32, momentum=0.99, phase=None):
+    """Griffin-Lim with momentum (Perraudin et al. 2013; the loop of torchaudio.functional.griffinlim at power=1, length=None,
+    PARITY UNPINNED) on the device: magnitude [B, n_fft / 2 + 1, frames] -> wave fp32 [B, (frames - 1) * hop_length].
+
+        m = momentum / (1 + momentum);  A_0 = exp(i phase);  T_0 = 0
+        repeat n_iter times:  R = stft(istft(A_k magnitude));  A = R - m T_k;  A_{k+1} = A / (|A| + 1e-16);  T_{k+1} = R
+        wave = istft(A_n magnitude)
+
+    stft / istft as torch's with center=True, pad_mode='reflect', the periodic Hann window of win_length samples, onesided, not
+    normalized.  `phase` [B, n_fft / 2 + 1, frames] in radians is the initial phase; None takes the `gl_phase` draw of rng_override
+    or, without one, draws it uniformly in [-pi, pi) on the device.  Two launches per iteration, no host synchronisation."""
+    _check_stft_args(n_fft, win_length, hop_length)
+    if magnitude.ndim != 3 or magnitude.shape[1] != n_fft // 2 + 1:
+        raise ValueError(f"griffin_lim takes magnitudes (batch, n_fft / 2 + 1 = {n_fft // 2 + 1}, frames), got {tuple(magnitude.shape)}")
+    if n_iter < 0 or not 0 <= momentum < 1:
+        raise ValueError("need n_iter >= 0 and 0 <= momentum < 1")
+    B, nb, frames = magnitude.shape
+    L = (frames - 1) * hop_length
+    if L <= n_fft // 2:
+        raise RuntimeError(f"reflect padding of n_fft // 2 = {n_fft // 2} samples in the analysis step needs (frames - 1) * hop_length "
+                           f"= {L} to be larger")
+    if magnitude.device.type != "cuda":
+        raise _lib.VbxError(f"griffin_lim runs only on an MI355X (gfx950) through libvbx_hip.so; the magnitude is on '{magnitude.device}'")
+    window, tw_re, tw_im, renv = _gl_tables(n_fft, win_length, hop_length, frames, magnitude.device)  # ValueError: NOLA
+    if _lib.lib().vbx_griffinlim_lds_bytes(n_fft, win_length, hop_length) > 65536:
+        raise NotImplementedError(f"3 * hop_length + win_length = {3 * hop_length + win_length} samples do not fit the LDS beside a "
+                                  f"{n_fft}-point transform")
+    dev = magnitude.device
+    mag = magnitude.detach().to(torch.float32).transpose(1, 2).contiguous()  # frame-major [B, frames, bins]
+    if phase is None:
+        phase = take_draw("gl_phase")
+    if phase is None:
+        phase = (2.0 * torch.rand(B, nb, frames, device=dev) - 1.0) * math.pi
+    if tuple(phase.shape) != (B, nb, frames):
+        raise ValueError(f"phase must have the shape of magnitude {(B, nb, frames)}, got {tuple(phase.shape)}")
+    ph = phase.detach().to(dev).transpose(1, 2).double()
+    spec_a = torch.stack((ph.cos(), ph.sin()), dim=-1).float().contiguous()  # A_0, rounded once from fp64
+    spec_b = torch.empty_like(spec_a)
+    fb = torch.empty(B, frames, win_length, dtype=torch.float32, device=dev)
+    wave = torch.empty(B, L, dtype=torch.float32, device=dev)
+    _lib.call("vbx_griffinlim", mag, spec_a, spec_b, fb, wave, window, tw_re, tw_im, renv, B, frames, n_fft, win_length, hop_length,
+              int(n_iter), float(momentum / (1.0 + momentum)), _lib.current_stream())
+    return wave
+
+
 class LogMelCodec(AudioEncoderDecoder):
     """Constructor of the reference's MelVoco (:501-516) plus `vocoder`: a module mapping mel [B, n_mels, frames] to a wave (Vocos
-    is a download; without one decode raises).  encode runs on the GPU only (csrc/mel.hip), as everything else in this package."""
+    is a download), or "griffin_lim": the weight-free decode griffin_lim(mel_to_magnitude(latents)) with griffin_lim_iters
+    iterations and griffin_lim_momentum.  Without either decode raises.  encode / decode run on the GPU only (csrc/mel.hip,
+    csrc/griffinlim.hip), as everything else in this package."""
 
     def __init__(self, *, log=True, n_mels=100, sampling_rate=24000, f_max=8000, n_fft=1024, win_length=640, hop_length=160,
-                 vocoder=None):
+                 vocoder=None, griffin_lim_iters=32, griffin_lim_momentum=0.99):
         super().__init__()
-        if n_fft & (n_fft - 1) or not 256 <= n_fft <= 2048:
-            raise NotImplementedError(f"n_fft must be a power of two in 256 .. 2048 (got {n_fft})")
-        if not 0 < win_length <= n_fft or hop_length <= 0 or n_mels <= 0:
-            raise ValueError("need 0 < win_length <= n_fft, hop_length > 0, n_mels > 0")
+        _check_stft_args(n_fft, win_length, hop_length)
+        if n_mels <= 0:
+            raise ValueError("need n_mels > 0")
+        if isinstance(vocoder, str) and vocoder != "griffin_lim":
+            raise ValueError(f'vocoder must be None, "griffin_lim" or a module (got "{vocoder}")')
+        if griffin_lim_iters < 0 or not 0 <= griffin_lim_momentum < 1:
+            raise ValueError("need griffin_lim_iters >= 0 and 0 <= griffin_lim_momentum < 1")
         self.log, self.n_mels, self.f_max, self.n_fft, self.win_length, self.hop_length = log, n_mels, f_max, n_fft, win_length, hop_length
         self._sampling_rate = sampling_rate
         self.vocoder = vocoder
-        win = torch.zeros(n_fft, dtype=torch.float64)
-        left = (n_fft - win_length) // 2  # torch.stft centres a short window in n_fft
-        win[left:left + win_length] = torch.hann_window(win_length, periodic=True, dtype=torch.float64)
-        ang = 2.0 * math.pi * torch.arange(n_fft // 2, dtype=torch.float64) / n_fft
+        self.griffin_lim_iters, self.griffin_lim_momentum = griffin_lim_iters, griffin_lim_momentum
+        win, tw_re, tw_im = _stft_tables(n_fft, win_length)
         start, length, offset, weights = mel_filter_runs(n_fft, n_mels, sampling_rate, f_max)
         assert int((start + length).max()) <= n_fft // 2 + 1
-        for name, t in (("window", win.float()), ("tw_re", ang.cos().float()), ("tw_im", (-ang.sin()).float()), ("fb_start", start),
-                        ("fb_len", length), ("fb_off", offset), ("fb_w", weights.float())):
+        # pinv(fb^T) [n_fft / 2 + 1, n_mels], taken once in fp64; stored mel-major so consecutive lanes read consecutive bins
+        pinv_t = torch.linalg.pinv(mel_filter_dense(n_fft, n_mels, sampling_rate, f_max).T).T.contiguous()
+        for name, t in (("window", win.float()), ("tw_re", tw_re.float()), ("tw_im", tw_im.float()), ("fb_start", start),
+                        ("fb_len", length), ("fb_off", offset), ("fb_w", weights.float()), ("mel_pinv_t", pinv_t.float())):
             self.register_buffer(name, t, persistent=False)
 
     @property
@@ -102,9 +205,30 @@ class LogMelCodec(AudioEncoderDecoder):
                   B, T, self.n_fft, self.hop_length, self.n_mels, int(bool(self.log)), _lib.current_stream())
         return out
 
+    def mel_to_magnitude(self, mel):
+        """latents [B, frames, n_mels] (dB if log, else power) -> linear magnitude fp32 [B, n_fft / 2 + 1, frames] (a view of the
+        frame-major buffer the kernel writes): sqrt(max(pinv(fb^T) @ P, 0)) per frame, P = 10^(mel / 10) or mel.  PARITY UNPINNED
+        (not torchaudio's InverseMelScale): the least-squares inverse of the filter bank, clamped at zero."""
+        if mel.ndim != 3 or mel.shape[2] != self.n_mels:
+            raise ValueError(f"mel_to_magnitude takes latents (batch, frames, n_mels = {self.n_mels}), got {tuple(mel.shape)}")
+        if mel.device.type != "cuda":
+            raise _lib.VbxError(f"LogMelCodec.mel_to_magnitude runs only on an MI355X (gfx950) through libvbx_hip.so; the latents are on '{mel.device}'")
+        if self.mel_pinv_t.device != mel.device:
+            self.to(mel.device)
+        mel = mel.detach().to(torch.float32).contiguous()
+        B, frames, _ = mel.shape
+        nb = self.n_fft // 2 + 1
+        mag = torch.empty(B, frames, nb, dtype=torch.float32, device=mel.device)
+        _lib.call("vbx_mel_to_mag", mel, mag, self.mel_pinv_t, B, frames, self.n_mels, nb, int(bool(self.log)), _lib.current_stream())
+        return mag.transpose(1, 2)
+
     def decode(self, mel):
         if self.vocoder is None:
-            raise NotImplementedError("LogMelCodec.decode needs a vocoder (mel [B, n_mels, frames] -> wave): pass vocoder=")
+            raise NotImplementedError('LogMelCodec.decode needs a vocoder (mel [B, n_mels, frames] -> wave): pass vocoder=, or '
+                                      'vocoder="griffin_lim" for the weight-free decode')
+        if isinstance(self.vocoder, str):  # "griffin_lim"
+            return griffin_lim(self.mel_to_magnitude(mel), n_fft=self.n_fft, win_length=self.win_length, hop_length=self.hop_length,
+                               n_iter=self.griffin_lim_iters, momentum=self.griffin_lim_momentum)
         mel = mel.transpose(-1, -2)
         if self.log:
             mel = torch.pow(10.0, 0.05 * mel)  # DB_to_amplitude(ref=1, power=0.5)

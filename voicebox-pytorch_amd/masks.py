@@ -14,7 +14,8 @@ _tls = threading.local()
 @contextlib.contextmanager
 def rng_override(**draws):
     """Inject the training-step RNG draws (test hook; public signatures stay those of the reference).
-    Keys: x0 (:1399), times (:1403), frac_lengths (:1025), rand (:146), y0 (:1289)."""
+    Keys: x0 (:1399), times (:1403), frac_lengths (:1025), rand (:146), y0 (:1289), gl_phase (the initial phase of griffin_lim,
+    [B, n_fft / 2 + 1, frames] in radians)."""
     prev = getattr(_tls, "draws", None)
     _tls.draws = dict(draws)
     try:
