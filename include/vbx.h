@@ -294,6 +294,17 @@ int vbx_griffinlim_lds_bytes(int n_fft, int win, int hop);
 int vbx_griffinlim(const float* mag, float* spec_a, float* spec_b, float* fb, float* wave, const float* window, const float* tw_re,
                    const float* tw_im, const float* renv, int B, int frames, int n_fft, int win, int hop, int n_iter, float m,
                    void* stream);
+/* Sample-rate conversion (voicebox_pytorch_amd.resample; csrc/resample.hip): the polyphase windowed-sinc FIR of
+ * torchaudio.functional.resample for the REDUCED rate pair orig : nw,
+ *   y[r][q * nw + p] = sum_k h[p][k] * x[r][q * orig + k - width],  x = 0 outside [0, L),  p < nw, k < K = 2 * width + orig,
+ * x fp32 [rows, L] (1 <= L <= 2^31 - 1), y fp32 [rows, Lout], Lout <= nw * ceil(L / orig) (the caller keeps ceil(nw * L / orig)).
+ * The bank is passed compacted: start / len int32 [nw] give, per phase, the run of taps that holds every non-zero of h[p][.]
+ * (start[p] + len[p] <= K, len[p] <= run_max), taps fp32 [run_max, nw] holds taps[i][p] = h[p][start[p] + i] (zero past len[p]).
+ * Taps outside a run must be exactly 0.0f in the dense bank, so leaving them out changes nothing.  One launch on `stream`, no
+ * atomics, the same bits on every run.  K <= vbx_resample_max_taps() (a tile's input span is staged in 64 KiB of LDS). */
+int vbx_resample_max_taps(void);
+int vbx_resample(const float* x, float* y, const float* taps, const int* start, const int* len, int rows, long L, long Lout, int orig,
+                 int nw, int width, int K, int run_max, void* stream);
 /* the same rows unrounded (fp32 [B*N, 2*D + E]): precise mode's to_embed operand */
 int vbx_embed_input_text_f32(const float* x, const float* cond, const uint8_t* cond_mask, const uint8_t* drop_mask,
                              const float* null_cond, const long* ids, int T, const float* table, int E, long null_id,

@@ -69,6 +69,8 @@ _PROTOS = {
     "vbx_mel_to_mag": [P, P, P, I, I, I, I, I, P],
     "vbx_griffinlim_lds_bytes": [I, I, I],
     "vbx_griffinlim": [P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, F, P],
+    "vbx_resample_max_taps": [],
+    "vbx_resample": [P, P, P, P, P, I, L, L, I, I, I, I, I, P],
     "vbx_pack_phoneme_input": [P, P, I, P, I, P, P, P, P, I, I, I, P],
     "vbx_rowdot": [P, P, P, P, L, I, P],
     "vbx_stack_input": [P, P, P, I, I, I, I, P],

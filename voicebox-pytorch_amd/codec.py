@@ -9,7 +9,8 @@ torchaudio.transforms.Spectrogram / MelScale / AmplitudeToDB at their defaults (
 normalized=False, f_min=0, norm=None, mel_scale='htk', top_db=None), restated in fp64 in tests/mel_ref.py.  The decode side is
 UNPINNED likewise: griffin_lim follows the published loop of torchaudio.functional.griffinlim (power=1, length=None), restated with
 torch.stft / torch.istft in tests/griffinlim_ref.py; mel_to_magnitude is a least-squares inverse clamped at zero and is NOT
-torchaudio's InverseMelScale.
+torchaudio's InverseMelScale.  resample / Resample (csrc/resample.hip), the sample-rate conversion in front of a codec, are UNPINNED
+too: the published arithmetic of torchaudio.functional.resample, restated in fp64 in tests/resample_ref.py.
 """
 import functools
 import math
@@ -144,6 +145,131 @@ def griffin_lim(magnitude, *, n_fft, win_length, hop_length, n_iter=32, momentum
     _lib.call("vbx_griffinlim", mag, spec_a, spec_b, fb, wave, window, tw_re, tw_im, renv, B, frames, n_fft, win_length, hop_length,
               int(n_iter), float(momentum / (1.0 + momentum)), _lib.current_stream())
     return wave
+
+
+RESAMPLE_METHODS = ("sinc_interp_hann", "sinc_interp_kaiser")
+RESAMPLE_KAISER_BETA = 14.769656459379492
+RESAMPLE_BANK_BYTES = 16 << 20  # a dense fp32 bank above this raises (near-coprime rates)
+
+
+def _check_resample_args(orig_freq, new_freq, lowpass_filter_width, resampling_method):
+    """the argument checks of torchaudio.functional.resample; returns the rate pair reduced by its gcd"""
+    if not (int(orig_freq) == orig_freq and int(new_freq) == new_freq):
+        raise ValueError(f"frequencies must be integral (got orig_freq {orig_freq}, new_freq {new_freq}): round them, or scale both "
+                         "by a common factor")
+    if orig_freq <= 0 or new_freq <= 0:
+        raise ValueError(f"need orig_freq > 0 and new_freq > 0 (got {orig_freq}, {new_freq})")
+    if lowpass_filter_width <= 0:
+        raise ValueError(f"need lowpass_filter_width > 0 (got {lowpass_filter_width})")
+    if resampling_method not in RESAMPLE_METHODS:
+        raise ValueError(f"resampling_method must be one of {RESAMPLE_METHODS} (got {resampling_method!r})")
+    g = math.gcd(int(orig_freq), int(new_freq))
+    return int(orig_freq) // g, int(new_freq) // g
+
+
+def resample_bank(orig_freq, new_freq, lowpass_filter_width=6, rolloff=0.99, resampling_method="sinc_interp_hann", beta=None):
+    """The polyphase windowed-sinc filter bank of torchaudio.functional.resample (PARITY UNPINNED: its published arithmetic) for
+    the gcd-reduced pair orig : new, built in fp64 and rounded once to fp32:
+
+        base = min(orig, new) * rolloff;  width = ceil(lowpass_filter_width * orig / base);  K = 2 * width + orig
+        t = clamp(((k - width) / orig - p / new) * base, +-lowpass_filter_width)
+        h[p][k] = sinc(pi t) * window(t) * base / orig,  window = cos^2(pi t / (2 lpw))  or  i0(beta sqrt(1 - (t / lpw)^2)) / i0(beta)
+
+    Returns (h float32 [new, K], width, start int32 [new], length int32 [new]): [start[p], start[p] + length[p]) is the run that
+    holds every tap of phase p that is not exactly 0.0 in fp32 (with the Hann window everything past the clamp; a Kaiser row has no
+    zeros).  Raises NotImplementedError for a bank above 16 MiB."""
+    orig, new = _check_resample_args(orig_freq, new_freq, lowpass_filter_width, resampling_method)
+    lpw = float(lowpass_filter_width)
+    base = min(orig, new) * float(rolloff)
+    width = int(math.ceil(lpw * orig / base))
+    K = 2 * width + orig
+    if new * K * 4 > RESAMPLE_BANK_BYTES:
+        raise NotImplementedError(f"the filter bank of {orig_freq} -> {new_freq} ({new} phases x {K} taps, {new * K * 4 / 2 ** 20:.1f} MiB) "
+                                  f"is above {RESAMPLE_BANK_BYTES >> 20} MiB: near-coprime rates are not served")
+    k = torch.arange(-width, width + orig, dtype=torch.float64)[None, :] / orig
+    p = torch.arange(new, dtype=torch.float64)[:, None] / new
+    t = ((k - p) * base).clamp_(-lpw, lpw)
+    if resampling_method == "sinc_interp_hann":
+        window = torch.cos(t * (math.pi / (2.0 * lpw))) ** 2
+    else:
+        b = torch.tensor(RESAMPLE_KAISER_BETA if beta is None else float(beta), dtype=torch.float64)
+        window = torch.special.i0(b * torch.sqrt(1.0 - (t / lpw) ** 2)) / torch.special.i0(b)
+    t = t * math.pi
+    sinc = torch.where(t == 0, torch.ones_like(t), torch.sin(t) / t)
+    h = (sinc * window * (base / orig)).float()
+    nz = h != 0
+    has = nz.any(dim=1)
+    first = torch.where(has, nz.int().argmax(dim=1), torch.zeros(new, dtype=torch.int64))
+    last = torch.where(has, K - 1 - nz.flip(1).int().argmax(dim=1), first - 1)
+    return h, width, first.int(), (last - first + 1).int()
+
+
+_resample_tables_cache = {}  # (orig, new, lpw, rolloff, method, beta, device) -> device tables, least recently used first
+
+
+def _resample_tables(orig, new, lpw, rolloff, method, beta, device):
+    """the bank as vbx_resample takes it: run-major taps [run_max, new] (taps[i][p] = h[p][start[p] + i]), start, length, width, K"""
+    key = (orig, new, float(lpw), float(rolloff), method, None if beta is None else float(beta), str(device))
+    hit = _resample_tables_cache.pop(key, None)
+    if hit is None:
+        h, width, start, length = resample_bank(orig, new, lpw, rolloff, method, beta)
+        K = h.shape[1]
+        if K > _lib.lib().vbx_resample_max_taps():
+            raise NotImplementedError(f"a filter of {K} taps ({orig} -> {new}, lowpass_filter_width {lpw}) does not fit the LDS "
+                                      f"(at most {_lib.lib().vbx_resample_max_taps()})")
+        run_max = max(int(length.max()), 1)
+        idx = (start.long()[None, :] + torch.arange(run_max)[:, None]).clamp_(max=K - 1)  # [run_max, new]
+        taps = h.t().gather(0, idx) * (torch.arange(run_max)[:, None] < length[None, :])
+        hit = (taps.contiguous().to(device), start.to(device), length.to(device), width, K, run_max)
+        if len(_resample_tables_cache) >= 8:
+            _resample_tables_cache.pop(next(iter(_resample_tables_cache)))
+    _resample_tables_cache[key] = hit
+    return hit
+
+
+def resample(waveform, orig_freq, new_freq, lowpass_filter_width=6, rolloff=0.99, resampling_method="sinc_interp_hann", beta=None):
+    """torchaudio.functional.resample on the device (csrc/resample.hip, one launch): waveform [..., L] at orig_freq -> [...,
+    ceil(new L / orig)] at new_freq (orig : new reduced by their gcd), bandlimited interpolation with the filter bank of
+    resample_bank.  PARITY UNPINNED: torchaudio is not a dependency and no vector of it is committed; this follows its published
+    arithmetic, restated in fp64 in tests/resample_ref.py.
+
+    Leading dimensions are flattened to rows and restored.  Compute is fp32: other floating dtypes are converted on the way in and
+    the result is converted back.  Equal rates return `waveform` itself and launch nothing.  Banks are cached per (rates, filter
+    arguments, device).  Runs only on the GPU, like griffin_lim; no gradient is taken through it."""
+    orig, new = _check_resample_args(orig_freq, new_freq, lowpass_filter_width, resampling_method)
+    if orig == new:
+        return waveform
+    if not waveform.is_floating_point():
+        raise TypeError(f"resample takes a floating-point waveform (got {waveform.dtype})")
+    if waveform.ndim < 1:
+        raise ValueError("resample takes waveforms (..., samples)")
+    if waveform.device.type != "cuda":
+        raise _lib.VbxError(f"resample runs only on an MI355X (gfx950) through libvbx_hip.so; the waveform is on '{waveform.device}'")
+    taps, start, length, width, K, run_max = _resample_tables(orig, new, lowpass_filter_width, rolloff, resampling_method, beta,
+                                                              waveform.device)
+    lead, L = waveform.shape[:-1], waveform.shape[-1]
+    Lout = -(-new * L // orig)
+    x = waveform.detach().reshape(-1, L).to(torch.float32).contiguous()
+    y = torch.empty(x.shape[0], Lout, dtype=torch.float32, device=x.device)
+    if y.numel():
+        _lib.call("vbx_resample", x, y, taps, start, length, x.shape[0], L, Lout, orig, new, width, K, run_max, _lib.current_stream())
+    return y.reshape(*lead, Lout).to(waveform.dtype)
+
+
+class Resample(nn.Module):
+    """torchaudio.transforms.Resample over resample(): no parameters and no buffers (the banks live in resample's cache), so nothing
+    of it appears in a state_dict()."""
+
+    def __init__(self, orig_freq=16000, new_freq=16000, resampling_method="sinc_interp_hann", lowpass_filter_width=6, rolloff=0.99,
+                 beta=None):
+        super().__init__()
+        _check_resample_args(orig_freq, new_freq, lowpass_filter_width, resampling_method)
+        self.orig_freq, self.new_freq, self.resampling_method = orig_freq, new_freq, resampling_method
+        self.lowpass_filter_width, self.rolloff, self.beta = lowpass_filter_width, rolloff, beta
+
+    def forward(self, waveform):
+        return resample(waveform, self.orig_freq, self.new_freq, self.lowpass_filter_width, self.rolloff, self.resampling_method,
+                        self.beta)
 
 
 class LogMelCodec(AudioEncoderDecoder):

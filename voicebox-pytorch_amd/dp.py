@@ -321,13 +321,13 @@ class TrainStep:
 
     # -- gradient accumulation with a deferred exchange (VoiceBoxTrainer.train_step, trainer.py:258-272: every micro-batch but
     #    the last runs under accelerator.no_sync, the loss is divided by grad_accum_every)
-    def accumulate(self, x1, weight, mask=None, cond_token_ids=None):
+    def accumulate(self, x1, weight, mask=None, cond_token_ids=None, input_sampling_rate=None):
         """forward + backward of one micro-batch; gradients * weight are added to the accumulation buffer (no exchange)."""
         if getattr(self, "gacc", None) is None:
             self.gacc = torch.zeros_like(self.gflat)
             self.acc_coef = torch.zeros(1, device=self.gflat.device)
             self.acc_pending = False
-        loss = self._forward_backward(x1, mask, cond_token_ids, on_stage=None)
+        loss = self._forward_backward(x1, mask, cond_token_ids, on_stage=None, input_sampling_rate=input_sampling_rate)
         self.acc_coef.fill_(float(weight))
         n = self.gflat.numel()
         _lib.call("vbx_axpy_dev", self.gacc, self.gflat, self.acc_coef, 0, self.gacc, n, _lib.current_stream())
@@ -384,7 +384,7 @@ class TrainStep:
                                              dada_all.shape[1], Th, J4, 0, st), "vbx_adaln_expand_dw")
         self._keep_factors = (dada_all, temb_all)  # alive until the launches have run
 
-    def accumulate_last_and_apply(self, x1, weight, mask=None, cond_token_ids=None, lr=None):
+    def accumulate_last_and_apply(self, x1, weight, mask=None, cond_token_ids=None, lr=None, input_sampling_rate=None):
         """The LAST micro-batch of an accumulation window, with the exchange overlapped with its backward (DDP leaves `no_sync`
         for exactly this micro-batch, trainer.py:258-272): as each backward stage completes, its slice of the accumulator is
         folded in (g = acc + weight * g) and the bucketed all-reduce of that slice starts while earlier layers are still running --
@@ -400,7 +400,7 @@ class TrainStep:
             if self.exchange:
                 red.stage_done(i, rng)
 
-        loss = self._forward_backward(x1, mask, cond_token_ids, on_stage=on_stage)
+        loss = self._forward_backward(x1, mask, cond_token_ids, on_stage=on_stage, input_sampling_rate=input_sampling_rate)
         red.finish()
         self._stage_buf = red.stage_buf
         self.gacc.zero_()
@@ -423,11 +423,12 @@ class TrainStep:
             self._stage_buf = red.stage_buf
         self._clip_adam(self._last_eng, lr)
 
-    def _forward_backward(self, x1, mask, cond_token_ids, on_stage, adaln_factors=False, sq_fold=False):
+    def _forward_backward(self, x1, mask, cond_token_ids, on_stage, adaln_factors=False, sq_fold=False, input_sampling_rate=None):
         vb, w = self.vb, self.wrapper
         dev = self.fp.flat.device
         st = _lib.current_stream
-        x1, _ = w.encode_raw_audio(x1)  # a wave batch of a codec model (voicebox_pytorch.py:1349-1371); latents pass through
+        # a wave batch of a codec model (voicebox_pytorch.py:1349-1371), resampled first when the wrapper says so; latents pass through
+        x1, _ = w.encode_raw_audio(x1, None, input_sampling_rate)
         x1 = x1.to(dev, torch.float32).contiguous()
         B, N, _ = x1.shape
         if mask is not None:
@@ -551,9 +552,10 @@ class TrainStep:
             _lib.call("vbx_adam_step", self.fp.flat, self.gflat, self.m, self.v, n, float(lr if lr is not None else self.lr),
                       float(self.betas[0]), float(self.betas[1]), float(self.eps), self.steps, self.coef, st())
 
-    def step(self, x1, mask=None, lr=None, cond_token_ids=None):
+    def step(self, x1, mask=None, lr=None, cond_token_ids=None, input_sampling_rate=None):
         """x1: (B_local, frames, dim) on this rank's GPU, or a wave batch (B_local, samples) for a model built with audio_enc_dec
-        (cond_token_ids (B_local, tokens) for a text-conditioned model).
+        (cond_token_ids (B_local, tokens) for a text-conditioned model); input_sampling_rate: the rate of such waves, for a wrapper built
+        with resample_input=True.
         Returns the (un-synchronised) local loss tensor."""
         # --- backward with overlapped gradient exchange
         factors = self.adaln_factors_apply(batch=int(x1.shape[0])) and os.environ.get("VBX_FUSED_ADAM", "1") != "0"
@@ -562,7 +564,7 @@ class TrainStep:
         # weight gradients for the clip norm); VBX_SUMSQ_FOLD=0: A/B
         fold = factors and not self.exchange and os.environ.get("VBX_SUMSQ_FOLD", "1") != "0"
         loss = self._forward_backward(x1, mask, cond_token_ids, on_stage=red.stage_done if self.exchange else None, adaln_factors=factors,
-                                      sq_fold=fold)
+                                      sq_fold=fold, input_sampling_rate=input_sampling_rate)
         if factors and self.exchange:  # the factors travel (one small all-gather) while the last buckets are still in flight
             self._exchange_adaln_factors(self._last_eng)
         red.finish()

@@ -14,6 +14,7 @@ import torch
 from torch import nn
 
 from . import _lib
+from .codec import resample
 from .engine import Engine, FlatParams, precise_enabled
 from .masks import mask_from_frac_lengths, prob_mask_like, reduce_masks_with_and, take_draw
 
@@ -607,7 +608,7 @@ ODE_METHODS = ("euler", "midpoint", "rk4", "dopri5")  # torchdiffeq methods the 
 
 class ConditionalFlowMatcherWrapper(nn.Module):
     def __init__(self, voicebox, text_to_semantic=None, duration_predictor=None, sigma=0., ode_atol=1e-5, ode_rtol=1e-5,
-                 use_torchode=False, torchdiffeq_ode_method='midpoint', torchode_method_klass=None, cond_drop_prob=0.):
+                 use_torchode=False, torchdiffeq_ode_method='midpoint', torchode_method_klass=None, cond_drop_prob=0., resample_input=False):
         super().__init__()
         assert isinstance(voicebox, VoiceBox)
         self.sigma = sigma
@@ -630,6 +631,9 @@ class ConditionalFlowMatcherWrapper(nn.Module):
         self.text_to_semantic = None
         self.duration_predictor = duration_predictor  # a submodule, as in the reference (:1147): its weights are in state_dict()
         self.cond_drop_prob = cond_drop_prob
+        # resample_input (not a reference keyword): True resamples waves given with an input_sampling_rate other than the codec's
+        # (codec.resample, :1359-1371); False, the default for now, keeps raising for them
+        self.resample_input = bool(resample_input)
         self.use_torchode = False
         self.odeint_kwargs = dict(atol=ode_atol, rtol=ode_rtol, method=torchdiffeq_ode_method)  # atol/rtol: read by dopri5 only
         self._samplers = {}
@@ -729,21 +733,31 @@ class ConditionalFlowMatcherWrapper(nn.Module):
 
     def encode_raw_audio(self, x1, cond=None, input_sampling_rate=None):
         """voicebox_pytorch.py:1349-1371: a 2-D tensor, or a 3-D one with a middle dimension of 1, is a wave -- encoded by the codec
-        (in eval mode, without gradients).  Latents pass through."""
+        (in eval mode, without gradients).  Latents pass through.  With resample_input=True a wave given at an input_sampling_rate
+        other than the codec's is resampled to it first, on this wrapper's device (:1359-1371); equal rates or None launch nothing.
+        sample() keeps the reference's signature: resample its `cond` with voicebox_pytorch_amd.resample beforehand."""
         in_raw, cond_raw = is_probably_audio_from_shape(x1), is_probably_audio_from_shape(cond)
         if not (in_raw or cond_raw):
             return x1, cond
         codec = self.voicebox.audio_enc_dec
         assert exists(codec), 'audio_enc_dec must be set on VoiceBox to train directly on raw audio'
-        if exists(input_sampling_rate) and input_sampling_rate != codec.sampling_rate:
+        differs = exists(input_sampling_rate) and input_sampling_rate != codec.sampling_rate
+        if differs and not self.resample_input:
             raise NotImplementedError(f"input_sampling_rate {input_sampling_rate} differs from the codec's {codec.sampling_rate}: "
-                                      "resampling is not built, resample the waves first")
+                                      "resampling is off for this wrapper -- build it with resample_input=True, or resample the "
+                                      "waves first (voicebox_pytorch_amd.resample)")
         with torch.no_grad():
             codec.eval()
             if in_raw:
-                x1 = codec.encode(x1.to(self.device))
+                x1 = x1.to(self.device)
+                if differs:
+                    x1 = resample(x1, input_sampling_rate, codec.sampling_rate)
+                x1 = codec.encode(x1)
             if cond_raw:
-                cond = codec.encode(cond.to(self.device))
+                cond = cond.to(self.device)
+                if differs:
+                    cond = resample(cond, input_sampling_rate, codec.sampling_rate)
+                cond = codec.encode(cond)
         return x1, cond
 
     def forward(self, x1, *, mask=None, semantic_token_ids=None, phoneme_ids=None, cond=None, cond_mask=None,

@@ -66,10 +66,13 @@ class VoiceBoxTrainer(nn.Module):
                  num_warmup_steps=None, num_epochs=None, lr=3e-4, initial_lr=1e-5, grad_accum_every=1, wd=0., max_grad_norm=0.5,
                  valid_frac=0.05, random_split_seed=42, log_every=10, save_results_every=100, save_model_every=1000,
                  results_folder='./results', force_clear_prev_results=None, split_batches=False, drop_last=False,
-                 accelerate_kwargs: dict = dict(), length_bucket=64):
+                 accelerate_kwargs: dict = dict(), length_bucket=64, input_sampling_rate=None):
         # length_bucket (not a reference keyword): batches of a varying-length dataset are padded with masked frames to the next
         # multiple of it, so that training runs on a handful of activation arenas (dp.TrainStep); 0 = exact lengths
+        # input_sampling_rate (not a reference keyword: its trainer never passes one): the rate of a dataset of waves, handed to
+        # every train and validation step; a wrapper built with resample_input=True resamples them to the codec's rate
         super().__init__()
+        self.input_sampling_rate = input_sampling_rate
         assert isinstance(cfm_wrapper, ConditionalFlowMatcherWrapper)
         self.wd = float(wd)  # > 0: AdamW with decay on the ndim >= 2 parameters (get_optimizer, optimizer.py:10-35)
         self.distributed = dist.is_available() and dist.is_initialized()
@@ -235,9 +238,10 @@ class VoiceBoxTrainer(nn.Module):
     def _model_kwargs(self, batch):
         """(latents or waves,) or (latents or waves, cond_token_ids): the second column feeds a text-conditioned model as semantic ids."""
         x = batch[0]
+        kw = dict(input_sampling_rate=self.input_sampling_rate) if exists(self.input_sampling_rate) else {}
         if len(batch) > 1 and self.cfm_wrapper.condition_on_text:
-            return x, dict(cond_token_ids=batch[1])
-        return x, {}
+            kw['cond_token_ids'] = batch[1]
+        return x, kw
 
     def train_step(self):  # trainer.py:237-313
         steps = int(self.steps.item())
@@ -267,7 +271,8 @@ class VoiceBoxTrainer(nn.Module):
             with torch.inference_mode():
                 self.cfm_wrapper.eval()
                 ids = kw.get('cond_token_ids')
-                valid_loss = self.cfm_wrapper(x.to(self.device), **({'semantic_token_ids': ids.to(self.device)} if ids is not None else {}))
+                valid_loss = self.cfm_wrapper(x.to(self.device), input_sampling_rate=self.input_sampling_rate,
+                                              **({'semantic_token_ids': ids.to(self.device)} if ids is not None else {}))
             self.print(f'{steps}: valid loss {float(valid_loss):0.3f}')
             logs['valid_loss'] = float(valid_loss)
         if not (steps % self.save_model_every):
