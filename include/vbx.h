@@ -395,19 +395,17 @@ int vbx_cfm_inputs(const float* x1, const float* x0, const float* times, float s
 /* y_out = y + coef[idx] * f   (ODE midpoint axpy; coef device-resident so graphs hold no host scalars) */
 int vbx_axpy_dev(const float* y, const float* f, const float* coef, int idx, float* out, long n, void* stream);
 /* hipGraph-replayable ODE step helpers (replace the host-side loop of torchdiffeq.odeint, call site
- * voicebox_pytorch.py:1295): t and dt come from device tables [2*intervals] indexed by a device counter.
- * table slot 0/1 of interval i at table[2*i + slot]. */
-int vbx_ode_set_time(float* times, int B, const float* table, const int* counter, int slot, void* stream);
+ * voicebox_pytorch.py:1295): dt comes from a device table [2*intervals] indexed by a device counter,
+ * slot 0/1 of interval i at table[2*i + slot] (the times likewise: vbx_ode_stage_time with stride 2). */
 int vbx_axpy_ctr(const float* y, const float* f, const float* table, const int* counter, int slot, float* out, long n,
                  void* stream);
 int vbx_counter_add(int* counter, int inc, void* stream);
 /* Sampling: every batch element of a call shares the ODE time, and the grid is known up front, so the time embedding + the adaLN
  * projections of ALL time points (voicebox_pytorch.py:1082, :273 -- a 100 MB weight stream per function evaluation at dim 512 / depth
- * 12) are evaluated once per sample() into table [2 * intervals][L][G] (G = 4 * D: gamma1 | beta1 | gamma2 | beta2 of a layer); this
- * copies the slice of time point 2 * counter + slot into the runtime's ada [L][B][G] (vbx_io.ada_table makes vbx_model_forward do it). */
-int vbx_ada_select(float* ada, int L, int B, int G, const float* table, const int* counter, int slot, void* stream);
-/* the same with `stride` time points per interval: row stride * counter + slot, 0 <= slot < stride (vbx_io.ada_stride) */
-int vbx_ada_select_rows(float* ada, int L, int B, int G, const float* table, const int* counter, int stride, int slot, void* stream);
+ * 12) are evaluated once per sample() into table [stride * intervals][L][G] (G = 4 * D: gamma1 | beta1 | gamma2 | beta2 of a layer; stride >= 1
+ * time points per interval); this copies the slice of time point stride * counter + slot, 0 <= slot < stride, into the runtime's ada
+ * [L][B][G] (vbx_io.ada_table / ada_stride make vbx_model_forward do it). */
+int vbx_ada_select(float* ada, int L, int B, int G, const float* table, const int* counter, int stride, int slot, void* stream);
 /* ------------------------------------------------------------------ ODE solvers (csrc/ode.hip; solver.py RKSampler / Dopri5Sampler)
  * torchdiffeq.odeint's euler, rk4 (3/8 rule) and dopri5 (call site voicebox_pytorch.py:1295; restated in tests/ode_ref.py -- parity
  * with the library UNPINNED).  States are fp32 [n] (n = B * N * D, a multiple of 4, 16-byte aligned); k is a HOST array of S <= 7
@@ -666,10 +664,10 @@ typedef struct {
   float* dcond;                 /* stack_only backward: [B,Th] gradient of the adaptive-norm condition (NULL with plain_norm) */
   int dropout;                  /* 1: apply the model's attn_dropout / ff_dropout in this forward (the module is in train() mode) */
   unsigned long long drop_seed; /* Philox key of this forward's masks (the backward entry points must see the same io) */
-  const float* ada_table;       /* inference only, or NULL: precomputed adaLN projections [2 * intervals][L][4 * D] (vbx_ada_select); */
+  const float* ada_table;       /* inference only, or NULL: precomputed adaLN projections [ada_stride * intervals][L][4 * D] (vbx_ada_select); */
   const int* ada_counter;       /* the forward then skips the time embedding and the projection GEMV and takes time point         */
-  int ada_slot;                 /* 2 * ada_counter[0] + ada_slot of the table (`times` is not read)                              */
-  int ada_stride;               /* time points per interval of ada_table: row ada_stride * ada_counter[0] + ada_slot; 0 means 2 (midpoint) */
+  int ada_slot;                 /* ada_stride * ada_counter[0] + ada_slot of the table (`times` is not read)                     */
+  int ada_stride;               /* time points per interval of ada_table, >= 1 (midpoint 2, euler 1, rk4 4); 0 <= ada_slot < ada_stride */
 } vbx_io;
 
 size_t vbx_model_wpack_bytes(const vbx_model* m);

@@ -1199,10 +1199,11 @@ def test_well_conditioned_sampler_is_tight(golden):
 
 
 def test_ode_step_kernels_reproduce_the_textbook_midpoint_rule():
-    """The device-side ODE helpers the captured interval is made of (vbx_ode_set_time, vbx_axpy_ctr, vbx_counter_add with the
-    sampler's own t / dt tables) integrate y' = (c0 + c1 t) y exactly as the explicit midpoint rule does: the final state is
+    """The device-side ODE helpers the captured interval is made of (vbx_ode_stage_time at stride 2, vbx_axpy_ctr, vbx_counter_add
+    with the sampler's own t / dt tables) integrate y' = (c0 + c1 t) y exactly as the explicit midpoint rule does: the final state is
     y0 times the product of (1 + h a(t + h/2) (1 + h a(t) / 2)) over the grid -- independent of the restated third-party solver."""
     from voicebox_pytorch_amd import _lib as L
+    from voicebox_pytorch_amd.solver import midpoint_tables
 
     c0, c1 = -1.3, 0.7
     st = lambda: torch.cuda.current_stream().cuda_stream
@@ -1210,18 +1211,21 @@ def test_ode_step_kernels_reproduce_the_textbook_midpoint_rule():
         t = torch.linspace(0, 1, steps)
         t0, dt = t[:-1], t[1:] - t[:-1]
         half = 0.5 * dt
-        t_table = torch.stack((t0, t0 + half), dim=1).reshape(-1).contiguous().to(dev)  # exactly solver.MidpointSampler's tables
-        c_table = torch.stack((half, dt), dim=1).reshape(-1).contiguous().to(dev)
+        t_table = torch.stack((t0, t0 + half), dim=1).reshape(-1).contiguous()
+        c_table = torch.stack((half, dt), dim=1).reshape(-1).contiguous()
+        built = midpoint_tables(steps)  # what solver.MidpointSampler puts on the device
+        assert torch.equal(built[0], t_table) and torch.equal(built[1], c_table)
+        t_table, c_table = t_table.to(dev), c_table.to(dev)
         B, n = 2, 4096
         y = torch.linspace(-2, 2, B * n, device=dev).view(B, n).contiguous()
         y0 = y.clone()
         ymid, times = torch.empty_like(y), torch.zeros(B, device=dev)
         counter = torch.zeros(1, dtype=torch.int32, device=dev)
         for _ in range(steps - 1):
-            L.call("vbx_ode_set_time", times, B, t_table, counter, 0, st())
+            L.call("vbx_ode_stage_time", times, B, t_table, counter, 2, 0, st())
             f = (c0 + c1 * times)[:, None] * y
             L.call("vbx_axpy_ctr", y, f.contiguous(), c_table, counter, 0, ymid, y.numel(), st())
-            L.call("vbx_ode_set_time", times, B, t_table, counter, 1, st())
+            L.call("vbx_ode_stage_time", times, B, t_table, counter, 2, 1, st())
             f = (c0 + c1 * times)[:, None] * ymid
             L.call("vbx_axpy_ctr", y, f.contiguous(), c_table, counter, 1, y, y.numel(), st())
             L.call("vbx_counter_add", counter, 1, st())

@@ -111,11 +111,9 @@ _PROTOS = {
     "vbx_masked_mse_bwd": [P, P, P, P, P, P, P, I, I, I, P],
     "vbx_cfm_inputs": [P, P, P, F, P, P, I, L, P],
     "vbx_axpy_dev": [P, P, P, I, P, L, P],
-    "vbx_ode_set_time": [P, I, P, P, I, P],
     "vbx_axpy_ctr": [P, P, P, P, I, P, L, P],
     "vbx_counter_add": [P, I, P],
-    "vbx_ada_select": [P, I, I, I, P, P, I, P],
-    "vbx_ada_select_rows": [P, I, I, I, P, P, I, I, P],
+    "vbx_ada_select": [P, I, I, I, P, P, I, I, P],
     "vbx_ode_combine": [P, P, P, I, P, I, P, I, I, L, P],
     "vbx_ode_combine_dp": [P, P, P, P, I, P, I, L, P],
     "vbx_ode_stage_time": [P, I, P, P, I, I, P],

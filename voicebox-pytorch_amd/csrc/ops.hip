@@ -1138,12 +1138,8 @@ __global__ void axpy_dev_kernel(const float* __restrict__ y, const float* __rest
 
 // device-counter variants for the hipGraph-captured ODE step: the captured kernels read t / dt from
 // device tables indexed by a device counter, so one captured step replays for every interval.
-__global__ void ode_set_time_kernel(float* __restrict__ times, int B, const float* __restrict__ table,
-                                    const int* __restrict__ counter, int slot) {
-  const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b < B) times[b] = table[2 * counter[0] + slot];
-}
-// ada[l][b][:] = table[2 * counter + slot][l][:] for every b: the adaLN projections of one ODE time point, precomputed for the whole
+//
+// ada[l][b][:] = table[stride * counter + slot][l][:] for every b: the adaLN projections of one ODE time point, precomputed for the whole
 // grid (every batch element of a sampling call shares the time, so the table has no batch axis); G = floats per layer (4 * D)
 __global__ void ada_select_kernel(float* __restrict__ ada, int L, int B, int G, const float* __restrict__ table,
                                   const int* __restrict__ counter, int stride, int slot) {
@@ -1989,22 +1985,10 @@ extern "C" int vbx_axpy_dev(const float* y, const float* f, const float* coef, i
   return 0;
 }
 
-extern "C" int vbx_ode_set_time(float* times, int B, const float* table, const int* counter, int slot, void* stream) {
-  VBX_REQUIRE(times && table && counter && (slot == 0 || slot == 1), "vbx_ode_set_time: bad args");
-  hipLaunchKernelGGL(ode_set_time_kernel, dim3(cdiv(B, 64)), dim3(64), 0, ST, times, B, table, counter, slot);
-  VBX_LAUNCH_CHECK();
-  return 0;
-}
-extern "C" int vbx_ada_select(float* ada, int L, int B, int G, const float* table, const int* counter, int slot, void* stream) {
-  VBX_REQUIRE(ada && table && counter && L > 0 && B > 0 && G > 0 && G % 4 == 0 && (slot == 0 || slot == 1), "vbx_ada_select: bad args");
-  hipLaunchKernelGGL(ada_select_kernel, dim3(grid_for((long)L * G / 4, 256)), dim3(256), 0, ST, ada, L, B, G, table, counter, 2, slot);
-  VBX_LAUNCH_CHECK();
-  return 0;
-}
-extern "C" int vbx_ada_select_rows(float* ada, int L, int B, int G, const float* table, const int* counter, int stride, int slot,
-                                   void* stream) {
+extern "C" int vbx_ada_select(float* ada, int L, int B, int G, const float* table, const int* counter, int stride, int slot,
+                              void* stream) {
   VBX_REQUIRE(ada && table && counter && L > 0 && B > 0 && G > 0 && G % 4 == 0 && stride >= 1 && slot >= 0 && slot < stride,
-              "vbx_ada_select_rows: bad args");
+              "vbx_ada_select: bad args");
   hipLaunchKernelGGL(ada_select_kernel, dim3(grid_for((long)L * G / 4, 256)), dim3(256), 0, ST, ada, L, B, G, table, counter, stride,
                      slot);
   VBX_LAUNCH_CHECK();

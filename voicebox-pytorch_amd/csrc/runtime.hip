@@ -527,9 +527,9 @@ extern "C" int vbx_model_forward(const vbx_model* m, const vbx_io* io, void* str
   } else {
   // time embedding + every adaLN projection of the stack   (:1082, :273)
   if (io->ada_table) {  // sampler: the projections of this time point were evaluated once for the whole grid (vbx_ada_select)
-    VBX_REQUIRE(!tr && io->ada_counter, "vbx_model_forward: ada_table is an inference-only input and needs ada_counter");
-    CK(vbx_ada_select_rows(a.ada, d.L, d.B, 4 * d.D, io->ada_table, io->ada_counter, io->ada_stride ? io->ada_stride : 2, io->ada_slot,
-                           stream));
+    VBX_REQUIRE(!tr && io->ada_counter && io->ada_stride >= 1,
+                "vbx_model_forward: ada_table is an inference-only input and needs ada_counter and ada_stride >= 1");
+    CK(vbx_ada_select(a.ada, d.L, d.B, 4 * d.D, io->ada_table, io->ada_counter, io->ada_stride, io->ada_slot, stream));
   } else {
   CK(vbx_time_embed_fwd(io->times, P + G[VBX_P_SINW], P + G[VBX_P_T1W], P + G[VBX_P_T1B], a.four, a.pre, a.temb, d.B, d.D,
                         d.Th, stream));

@@ -433,9 +433,9 @@ class Engine:
     def forward(self, x, cond, cond_mask, times, attn_mask=None, target=None, loss_mask=None, pred_out=None, text=None, ada=None):
         """All tensors on self.device, fp32 contiguous / bool.  Returns the loss tensor (1,) if target is given,
         else the prediction (B,N,D).  text (text-conditioned models): (ids int64 (B,T), null_id, drop_mask bool (B,) or None,
-        null_cond fp32 (D,)).  ada (inference, the sampler): (table fp32 [2 * intervals, L, 4 * D], counter int32 [1], slot[, stride]) --
-        the adaLN projections of every time point of the ODE grid, precomputed (stride time points per interval, 2 if not given);
-        `times` is then not read."""
+        null_cond fp32 (D,)).  ada (inference, the sampler): (table fp32 [stride * intervals, L, 4 * D], counter int32 [1], slot, stride) --
+        the adaLN projections of every time point of the ODE grid, precomputed (stride >= 1 time points per interval, this forward at
+        row stride * counter + slot); `times` is then not read."""
         self.bind_params()
         B, N, D = self.B, self.N, self.Din
         assert x.shape == (B, N, D) and cond.shape == (B, N, D), (tuple(x.shape), tuple(cond.shape), (B, N, D))
@@ -453,8 +453,8 @@ class Engine:
         io.times = times.data_ptr()
         if ada is not None:
             assert target is None and not self.training
-            io.ada_table, io.ada_counter, io.ada_slot = ada[0].data_ptr(), ada[1].data_ptr(), int(ada[2])
-            io.ada_stride = int(ada[3]) if len(ada) > 3 else 0
+            table, counter, slot, stride = ada
+            io.ada_table, io.ada_counter, io.ada_slot, io.ada_stride = table.data_ptr(), counter.data_ptr(), int(slot), int(stride)
         else:
             io.ada_table = io.ada_counter = None
             io.ada_slot = io.ada_stride = 0

@@ -658,7 +658,7 @@ class ConditionalFlowMatcherWrapper(nn.Module):
         torchdiffeq_ode_method: 'midpoint' (the default), 'euler' and 'rk4' on the fixed grid linspace(0, 1, steps) -- 2, 1 and 4
         function evaluations per interval -- or the adaptive 'dopri5' with ode_atol / ode_rtol (steps does not change its result).
         Counts of the call: self.last_sample_stats."""
-        from .solver import Dopri5Sampler, MidpointSampler, RKSampler
+        from .solver import make_sampler
 
         codec = self.voicebox.audio_enc_dec
         if is_probably_audio_from_shape(cond):  # :1192-1201
@@ -713,18 +713,10 @@ class ConditionalFlowMatcherWrapper(nn.Module):
         if smp is None:
             if len(self._samplers) >= 2:
                 self._samplers.pop(next(iter(self._samplers)))
-            if method == "midpoint":
-                smp = MidpointSampler(self.voicebox, B, N, steps, use_graph=use_graph, tokens=T, guided=guided)
-            elif method == "dopri5":
-                smp = Dopri5Sampler(self.voicebox, B, N, steps, use_graph=use_graph, tokens=T, guided=guided, atol=atol, rtol=rtol)
-            else:
-                smp = RKSampler(self.voicebox, B, N, steps, method, use_graph=use_graph, tokens=T, guided=guided)
-            self._samplers[key] = smp
+            smp = self._samplers[key] = make_sampler(method, self.voicebox, B, N, steps, use_graph=use_graph, tokens=T, guided=guided,
+                                                     atol=atol, rtol=rtol)
         out = smp.run(y0, cond, cond_mask, cond_token_ids=cond_token_ids, cond_scale=float(cond_scale))
-        if method == "midpoint":
-            self.last_sample_stats = {"method": method, "nfe": smp.nfe, "accepted": steps - 1, "rejected": 0}
-        else:
-            self.last_sample_stats = smp.stats()
+        self.last_sample_stats = smp.stats()
         if decode_to_codes and exists(codec):  # :1324-1330
             return codec.decode_to_codes(out)
         if not decode_to_audio or not exists(codec):

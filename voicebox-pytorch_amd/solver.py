@@ -1,17 +1,26 @@
-"""Fixed-step midpoint ODE sampler replayed under hipGraph.
+"""ODE samplers on the device: midpoint, euler, rk4 and adaptive dopri5, replayed under hipGraph.
 
-Replaces torchdiffeq.odeint(fn, y0, t, method='midpoint') (call site voicebox_pytorch.py:1295; torchdiffeq
-is third-party, restated in oracle/ref_loader.py): per interval [t_i, t_{i+1}] of t = linspace(0,1,steps)
-    f0 = fn(t_i, y);  f1 = fn(t_i + dt/2, y + f0*dt/2);  y <- y + dt*f1.
-The grid values t_i, dt_i = t_{i+1}-t_i, dt_i/2 and t_i + dt_i/2 are computed on the host with the same
-fp32 torch ops the oracle uses (linspace(0,1,64) has 8 distinct fp32 dt values -- SURVEY 8(c)) and live
-in device tables; ONE interval (2 forwards + 2 axpys) is captured in a hipGraph and replayed steps-1 times,
-a device counter selecting the table row, so no host scalar is baked into the graph.  Only the final
-state is kept (the reference stacks the whole trajectory, voicebox_pytorch.py:1295-1296).
+Replaces torchdiffeq.odeint(fn, y0, t, method=...) (call site voicebox_pytorch.py:1295; torchdiffeq is third-party, restated in
+oracle/ref_loader.py and tests/ode_ref.py -- parity with the library UNPINNED).  Only the final state is kept (the reference stacks
+the whole trajectory, voicebox_pytorch.py:1295-1296).  Kernels: csrc/ops.hip (axpy, counter), csrc/ode.hip (include/vbx.h "ODE solvers").
+
+    _Sampler             what every method needs: the split decision, the engines and parts, the static buffers, the adaLN table,
+                         the input copy-in and ONE function evaluation (_eval: the forward, or the guidance mix of two forwards)
+    _FixedGridSampler    t = linspace(0, 1, steps): ONE interval captured in a hipGraph and replayed steps - 1 times, a device counter
+                         selecting the row of the device tables, so no host scalar is baked into the graph; the concurrent halves
+      MidpointSampler    f0 = fn(t_i, y);  f1 = fn(t_i + dt/2, y + f0*dt/2);  y <- y + dt*f1   (2 forwards + 2 axpys)
+      RKSampler          euler / rk4 from a Butcher tableau (FIXED_TABLEAUS)
+    Dopri5Sampler        adaptive: one attempt captured, the host reads the step state back after each
+    make_sampler         method name -> sampler (model.py's only entry)
+
+The grid values are computed on the host with the same fp32 torch ops the oracle uses (linspace(0,1,64) has 8 distinct fp32 dt values
+-- SURVEY 8(c)).  Midpoint is NOT a third tableau: its step y + f * a runs on vbx_axpy_ctr, a fused multiply-add (csrc/ops.hip, default
+contraction: v_pk_fma_f32), the tableau methods' vbx_ode_combine is a multiply, then an add (csrc/ode.hip, fp contract(off), as torch
+evaluates y0 + dt * f0) -- the tableau form would change the bits of every midpoint sample.
 
 Concurrent halves.  Every kernel of a forward has a ramp, a drain and -- the GEMMs -- a VALU-bound epilogue during which the
 matrix pipes idle (tools/native/gemm_trace.cpp); batch elements are independent in every kernel of the path.  So a batch of
-B >= 4 (even) is integrated as TWO half-batches on two streams (the default except at dim 512, see MidpointSampler.__init__), each with its own engine (activation arena; the packed weights
+B >= 4 (even) is integrated as TWO half-batches on two streams (the default except at dim 512, see _Sampler.__init__), each with its own engine (activation arena; the packed weights
 are shared) and its own captured interval graph: one kernel stream fills the other's holes.  The two integrations never meet
 before the end, and the second stream starts SPLIT_OFFSET_US late, so that different kernels of the two forwards overlap
 (attention beside GEMMs) rather than the same ones.  Measured on the benchmark shape, 16 intervals: one stream 85.7 ms, two
@@ -20,6 +29,7 @@ tools/sample_offset.py); results bit-identical to the single-stream run.  VBX_SA
 Without a graph (use_graph=False) the halves run as fork / join branches per interval.
 """
 import contextlib
+import ctypes as _C
 import os
 
 import torch
@@ -47,10 +57,13 @@ class _Part:
     """One concurrently integrated slice [lo, hi) of the batch: its engine and its views of the sampler's static buffers."""
 
 
-class MidpointSampler:
-    def __init__(self, voicebox, B, N, steps, use_graph=True, tokens=0, guided=False, split=None):
-        assert steps >= 2, "need at least two time points"
-        self.vb, self.B, self.N, self.steps = voicebox, B, N, steps
+class _Sampler:
+    """What every method shares.  grid = (stage times of the whole grid, host fp32 [intervals * stride], stride) of a method that
+    knows its time points up front: self.t_table, and the adaLN projections of all of them are tabulated (self.ada_tab, row
+    ada_stride * counter + slot).  grid = None: every forward evaluates its own projections from p.times."""
+
+    def __init__(self, voicebox, B, N, use_graph=True, tokens=0, guided=False, split=None, grid=None):
+        self.vb, self.B, self.N = voicebox, B, N
         if split is None:
             # Default: two concurrent half batches -- EXCEPT where the weight-stationary kernel serves to_qkv / FeedForward-in (dim 512,
             # csrc/gemm5.hip): it owns whole CUs, the half batches' launches cannot interleave with it, and ONE stream is then both
@@ -63,7 +76,7 @@ class MidpointSampler:
                 raise ValueError(f"VBX_SAMPLE_SPLIT must be 1 or 2 (concurrent half batches are the only measured, tested split), got {env!r}")
             split = int(env)
         if split not in (1, 2):
-            raise ValueError(f"MidpointSampler(split={split}): only 1 (one stream) and 2 (two concurrent half batches) are supported")
+            raise ValueError(f"{type(self).__name__}(split={split}): only 1 (one stream) and 2 (two concurrent half batches) are supported")
         if B < 4 or B % split:
             split = 1
         self.split = split
@@ -75,11 +88,6 @@ class MidpointSampler:
         self.flat_gen = self.eng.fp.flat_gen  # the captured graph bakes in addresses inside this flat parameter buffer
         dev = self.eng.device
         D = voicebox._cfg.get("Lc") or voicebox._cfg.get("Din") or voicebox._cfg["D"]  # the ODE state lives in data space (latent_dim / dim_in)
-        t = torch.linspace(0, 1, steps)  # host fp32, as the CPU oracle
-        t0, dt = t[:-1], t[1:] - t[:-1]
-        half = 0.5 * dt
-        self.t_table = torch.stack((t0, t0 + half), dim=1).reshape(-1).contiguous().to(dev)   # [2*(steps-1)]
-        self.c_table = torch.stack((half, dt), dim=1).reshape(-1).contiguous().to(dev)
         self.y = torch.zeros(B, N, D, device=dev)
         self.ymid = torch.zeros(B, N, D, device=dev)
         self.f = torch.zeros(B, N, D, device=dev)
@@ -102,7 +110,7 @@ class MidpointSampler:
         for i, eng in enumerate(engines):
             p = _Part()
             p.eng, p.B = eng, Bp
-            sl = slice(i * Bp, (i + 1) * Bp)
+            p.sl = sl = slice(i * Bp, (i + 1) * Bp)
             p.y, p.ymid, p.f, p.cond, p.cmask, p.times = self.y[sl], self.ymid[sl], self.f[sl], self.cond[sl], self.cmask[sl], self.times[sl]
             p.counter = self.counters[i:i + 1]
             if self.tokens:
@@ -110,45 +118,76 @@ class MidpointSampler:
             if self.guided:
                 p.f_null, p.f_diff = self.f_null[sl], self.f_diff[sl]
             self.parts.append(p)
-        self.side_streams = [torch.cuda.Stream(device=dev) for _ in range(split - 1)]
-        self.part_streams = [torch.cuda.Stream(device=dev) for _ in range(split)] if split > 1 else []
         # adaLN projections of every time point of the grid, evaluated once per weights version instead of once per function
         # evaluation (a 100 MB weight stream + the time MLP per forward at dim 512 / depth 12): every batch element shares the time.
         # VBX_SAMPLE_ADA_TABLE=0: A/B (per-forward projections, bit-identical results).
-        self.use_ada_table = os.environ.get("VBX_SAMPLE_ADA_TABLE", "1") != "0"
+        self.t_table, self.ada_stride = (grid[0].to(dev), int(grid[1])) if grid is not None else (None, None)
+        self.use_ada_table = grid is not None and os.environ.get("VBX_SAMPLE_ADA_TABLE", "1") != "0"
         self.ada_tab, self.ada_key = None, None
-        self.graph = None       # split == 1: one interval; split > 1: a list, one interval graph per part
+        self.graph = None
         self.use_graph = use_graph
-        self.nfe = 2 * (steps - 1) * (2 if self.guided else 1)
 
-    def _bind(self, p, x, slot):
-        # point the part's engine at the static buffers (x = y or ymid), prediction written to p.f; slot 0 / 1 = t_i / t_i + dt / 2
+    def _load_inputs(self, cond, cond_mask, cond_token_ids, cond_scale):
+        # eval semantics of the reference: cond_mask None -> everything masked -> cond is zeroed (:1028-1035)
+        if cond is not None:
+            self.cond.copy_(cond)
+        if cond_mask is not None:
+            self.cmask.copy_(cond_mask.to(self.cmask.device))
+        else:
+            self.cmask.fill_(True)
+        if self.tokens:
+            self.ids.copy_(cond_token_ids.to(self.ids.device))
+        if self.guided:
+            self.g_table[1] = float(cond_scale)
+        for p in self.parts:
+            p.eng.bind_params()  # re-pack weights if they changed since the last call
+        if self.use_ada_table and not self.vb._cfg.get("plain_norm"):
+            key = self.eng.fp.weights_key()
+            if self.ada_tab is None:
+                self.ada_tab = self.eng.ada_table(self.t_table)  # allocated once: its address is baked into the captured graphs
+                self.ada_key = key
+            elif key != self.ada_key:
+                self.ada_tab.copy_(self.eng.ada_table(self.t_table))
+                self.ada_key = key
+
+    def _eval(self, p, x, out, slot=0):
+        """One function evaluation of part p at x into `out`: the forward, or under classifier-free guidance the conditioned and the
+        fully dropped forward mixed as null + (logits - null) * scale (forward_with_cond_scale, voicebox_pytorch.py:972-985).  The
+        time is row ada_stride * counter + slot of the adaLN table, or without one whatever the caller left in p.times."""
         p.eng.dropout_active = False  # sampling is eval (:1268) whatever mode a later forward of the same shape left on the engine
-        ada = (self.ada_tab, p.counter, slot) if self.ada_tab is not None else None
+        ada = (self.ada_tab, p.counter, slot, self.ada_stride) if self.ada_tab is not None else None
         if not self.tokens:
-            p.eng.forward(x, p.cond, p.cmask, p.times, pred_out=p.f, ada=ada)
+            p.eng.forward(x, p.cond, p.cmask, p.times, pred_out=out, ada=ada)
             return
         vb = self.vb
-        p.eng.forward(x, p.cond, p.cmask, p.times, pred_out=p.f, text=(p.ids, vb.null_cond_id, None, vb.null_cond), ada=ada)
+        p.eng.forward(x, p.cond, p.cmask, p.times, pred_out=out, text=(p.ids, vb.null_cond_id, None, vb.null_cond), ada=ada)
         if self.guided:
-            st, n = _lib.current_stream, p.f.numel()
+            st, n = _lib.current_stream, out.numel()
             p.eng.forward(x, p.cond, p.cmask, p.times, pred_out=p.f_null,
                           text=(p.ids, vb.null_cond_id, p.drop_all, vb.null_cond), ada=ada)
-            _lib.call("vbx_axpy_dev", p.f, p.f_null, self.g_table, 0, p.f_diff, n, st())   # logits - null
-            _lib.call("vbx_axpy_dev", p.f_null, p.f_diff, self.g_table, 1, p.f, n, st())   # null + scale * diff
+            _lib.call("vbx_axpy_dev", out, p.f_null, self.g_table, 0, p.f_diff, n, st())   # logits - null
+            _lib.call("vbx_axpy_dev", p.f_null, p.f_diff, self.g_table, 1, out, n, st())   # null + scale * diff
 
-    def _interval_part(self, p):
-        st = _lib.current_stream
-        n = p.y.numel()
-        if self.ada_tab is None:
-            _lib.call("vbx_ode_set_time", p.times, p.B, self.t_table, p.counter, 0, st())
-        self._bind(p, p.y, 0)
-        _lib.call("vbx_axpy_ctr", p.y, p.f, self.c_table, p.counter, 0, p.ymid, n, st())
-        if self.ada_tab is None:
-            _lib.call("vbx_ode_set_time", p.times, p.B, self.t_table, p.counter, 1, st())
-        self._bind(p, p.ymid, 1)
-        _lib.call("vbx_axpy_ctr", p.y, p.f, self.c_table, p.counter, 1, p.y, n, st())
-        _lib.call("vbx_counter_add", p.counter, 1, st())
+
+class _FixedGridSampler(_Sampler):
+    """A method on t = linspace(0, 1, steps) with S function evaluations per interval.  tables = (stage times [intervals * S],
+    coefficients [intervals * S, ...]), host fp32; the subclass's _interval_part(p) launches one interval of one part, reading row
+    S * p.counter + slot of them, and advances the counter."""
+
+    def __init__(self, voicebox, B, N, steps, method, tables, use_graph=True, tokens=0, guided=False, split=None):
+        S = tables[0].numel() // (steps - 1)
+        super().__init__(voicebox, B, N, use_graph=use_graph, tokens=tokens, guided=guided, split=split, grid=(tables[0], S))
+        self.method, self.steps, self.S = method, steps, S
+        dev = self.y.device
+        self.c_table = tables[1].to(dev)
+        self.side_streams = [torch.cuda.Stream(device=dev) for _ in range(self.split - 1)]
+        self.part_streams = [torch.cuda.Stream(device=dev) for _ in range(self.split)] if self.split > 1 else []
+        self.nfe = S * (steps - 1) * (2 if self.guided else 1)
+        # self.graph: split == 1: one interval; split > 1: a list, one interval graph per part
+
+    def _stage_time(self, p, slot):
+        if self.ada_tab is None:  # plain-norm models, VBX_SAMPLE_ADA_TABLE=0: the forward reads p.times
+            _lib.call("vbx_ode_stage_time", p.times, p.B, self.t_table, p.counter, self.S, slot, _lib.current_stream())
 
     def _interval(self):
         # part 0 on the current stream, the others on side streams between a fork and a join: parallel branches under capture
@@ -180,29 +219,26 @@ class MidpointSampler:
 
     def _capture(self):
         with self._cu_share():
-            self._capture_shared()
-
-    def _capture_shared(self):
-        # warm up on a side stream (one-time kernel attribute calls, weight packing), then capture one interval
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            self.counters.zero_()
-            self._interval()
-        torch.cuda.current_stream().wait_stream(s)
-        torch.cuda.synchronize()
-        if self.split == 1:
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
+            # warm up on a side stream (one-time kernel attribute calls, weight packing), then capture one interval
+            s = torch.cuda.Stream()
+            s.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(s):
+                self.counters.zero_()
                 self._interval()
-            self.graph = g
-        else:
-            self.graph = []
-            for p in self.parts:
+            torch.cuda.current_stream().wait_stream(s)
+            torch.cuda.synchronize()
+            if self.split == 1:
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g):
-                    self._interval_part(p)
-                self.graph.append(g)
+                    self._interval()
+                self.graph = g
+            else:
+                self.graph = []
+                for p in self.parts:
+                    g = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(g):
+                        self._interval_part(p)
+                    self.graph.append(g)
 
     def _replay_parts(self):
         """steps-1 intervals of every part: each part's graph on its own stream, the streams never meet before the end."""
@@ -220,27 +256,7 @@ class MidpointSampler:
             cur.wait_stream(s)
 
     def run(self, y0, cond=None, cond_mask=None, cond_token_ids=None, cond_scale=1.0):
-        # eval semantics of the reference: cond_mask None -> everything masked -> cond is zeroed (:1028-1035)
-        if cond is not None:
-            self.cond.copy_(cond)
-        if cond_mask is not None:
-            self.cmask.copy_(cond_mask.to(self.cmask.device))
-        else:
-            self.cmask.fill_(True)
-        if self.tokens:
-            self.ids.copy_(cond_token_ids.to(self.ids.device))
-        if self.guided:
-            self.g_table[1] = float(cond_scale)
-        for p in self.parts:
-            p.eng.bind_params()  # re-pack weights if they changed since the last call
-        if self.use_ada_table and not self.vb._cfg.get("plain_norm"):
-            key = self.eng.fp.weights_key()
-            if self.ada_tab is None:
-                self.ada_tab = self.eng.ada_table(self.t_table)  # allocated once: its address is baked into the captured graphs
-                self.ada_key = key
-            elif key != self.ada_key:
-                self.ada_tab.copy_(self.eng.ada_table(self.t_table))
-                self.ada_key = key
+        self._load_inputs(cond, cond_mask, cond_token_ids, cond_scale)
         if self.use_graph and self.graph is None:
             self._capture()
         self.y.copy_(y0)
@@ -256,11 +272,39 @@ class MidpointSampler:
                         self._interval()
         return self.y.clone()
 
+    def stats(self):
+        return {"method": self.method, "nfe": self.nfe, "accepted": self.steps - 1, "rejected": 0}
 
-# ------------------------------------------------------------------------------------------------ euler / rk4 / dopri5
-# torchdiffeq.odeint's other methods (call site voicebox_pytorch.py:1295), restated in tests/ode_ref.py -- parity with the library
-# UNPINNED, as for midpoint (oracle/ref_loader.py).  Kernels: csrc/ode.hip (include/vbx.h "ODE solvers").
-import ctypes as _C
+
+def midpoint_tables(steps):
+    """Host fp32 tables of the midpoint rule on t = linspace(0, 1, steps), [2 * intervals] each: times [t0, t0 + dt/2] and
+    coefficients [dt/2, dt] per interval."""
+    assert steps >= 2, "need at least two time points"
+    t = torch.linspace(0, 1, steps)  # host fp32, as the CPU oracle
+    t0, dt = t[:-1], t[1:] - t[:-1]
+    half = 0.5 * dt
+    return (torch.stack((t0, t0 + half), dim=1).reshape(-1).contiguous(),
+            torch.stack((half, dt), dim=1).reshape(-1).contiguous())
+
+
+class MidpointSampler(_FixedGridSampler):
+    """torchdiffeq's fixed-grid midpoint.  Its own step on vbx_axpy_ctr (fused y + f * a), not a tableau: see the module docstring."""
+
+    def __init__(self, voicebox, B, N, steps, use_graph=True, tokens=0, guided=False, split=None):
+        super().__init__(voicebox, B, N, steps, "midpoint", midpoint_tables(steps), use_graph=use_graph, tokens=tokens, guided=guided,
+                         split=split)
+
+    def _interval_part(self, p):
+        st = _lib.current_stream
+        n = p.y.numel()
+        self._stage_time(p, 0)
+        self._eval(p, p.y, p.f, 0)
+        _lib.call("vbx_axpy_ctr", p.y, p.f, self.c_table, p.counter, 0, p.ymid, n, st())
+        self._stage_time(p, 1)
+        self._eval(p, p.ymid, p.f, 1)
+        _lib.call("vbx_axpy_ctr", p.y, p.f, self.c_table, p.counter, 1, p.y, n, st())
+        _lib.call("vbx_counter_add", p.counter, 1, st())
+
 
 # Fixed-grid explicit RK tableaus: (c, a, b) -- stage times t0 + c dt (c = 1: t1 itself), stage inputs y0 + dt sum_j a_ij k_j, step
 # dy = dt sum_j b_j k_j.  rk4 is torchdiffeq's 3/8 rule (rk4_alt_step_func), not the classic RK4.
@@ -275,6 +319,7 @@ def fixed_grid_tables(method, steps):
     itself) and coefficients [intervals * S, S]: per interval, rows 0 .. S-2 the stage inputs' dt * a_ij, row S-1 the step's dt * b_j."""
     c, a, b = FIXED_TABLEAUS[method]
     S = len(b)
+    assert steps >= 2, "need at least two time points"
     t = torch.linspace(0, 1, steps)
     t0, t1 = t[:-1], t[1:]
     dt = t1 - t0
@@ -286,6 +331,43 @@ def fixed_grid_tables(method, steps):
             r[:, j] = dt * v
         rows.append(r)
     return torch.stack(times, dim=1).reshape(-1).contiguous(), torch.stack(rows, dim=1).reshape(-1, S).contiguous()
+
+
+def _ptrs(ts):
+    return (_C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+
+
+def _floats(vals):
+    return (_C.c_float * len(vals))(*vals)
+
+
+class RKSampler(_FixedGridSampler):
+    """torchdiffeq's fixed-grid euler and rk4 (FixedGridODESolver: y1 = y0 + dy per interval).  The stage times and the coefficients
+    dt * a_ij, dt * b_j are formed on the host in fp32 torch arithmetic (fixed_grid_tables) and live in device tables
+    [intervals * S] / [intervals * S][S] indexed by the part's device counter; the adaLN table holds every STAGE time."""
+
+    def __init__(self, voicebox, B, N, steps, method, use_graph=True, tokens=0, guided=False, split=None):
+        if method not in FIXED_TABLEAUS:
+            raise ValueError(f"RKSampler: no fixed-grid tableau {method!r} (have {sorted(FIXED_TABLEAUS)})")
+        super().__init__(voicebox, B, N, steps, method, fixed_grid_tables(method, steps), use_graph=use_graph, tokens=tokens,
+                         guided=guided, split=split)
+        self.ks = [self.f] + [torch.zeros_like(self.y) for _ in range(self.S - 1)]  # stage derivatives; the stage inputs go to ymid
+        for p in self.parts:
+            p.k = [k[p.sl] for k in self.ks]
+
+    def _interval_part(self, p):
+        st = _lib.current_stream
+        n = p.y.numel()
+        S = self.S
+        for s in range(S):
+            x = p.y
+            if s:
+                x = p.ymid
+                _lib.call("vbx_ode_combine", x, p.y, _ptrs(p.k[:s]), s, self.c_table, S, p.counter, S, s - 1, n, st())
+            self._stage_time(p, s)
+            self._eval(p, x, p.k[s], s)
+        _lib.call("vbx_ode_combine", p.y, p.y, _ptrs(p.k), S, self.c_table, S, p.counter, S, S - 1, n, st())
+        _lib.call("vbx_counter_add", p.counter, 1, st())
 
 
 def _f32(vals):
@@ -311,92 +393,19 @@ TIME_STAGE, TIME_END, TIME_PROBE = 1, 2, 3
 NORM_ERROR, NORM_INIT0, NORM_INIT1 = 0, 1, 2
 
 
-def _ptrs(ts):
-    return (_C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
-
-
-def _floats(vals):
-    return (_C.c_float * len(vals))(*vals)
-
-
-class _SamplerEval:
-    """One function evaluation of the sampler into `out`: the forward, or under classifier-free guidance the conditioned and the
-    fully dropped forward mixed as null + (logits - null) * scale (forward_with_cond_scale, voicebox_pytorch.py:972-985)."""
-
-    def _eval(self, p, x, out, slot=0):
-        p.eng.dropout_active = False  # sampling is eval (:1268)
-        ada = (self.ada_tab, p.counter, slot, self.ada_stride) if self.ada_tab is not None else None
-        if not self.tokens:
-            p.eng.forward(x, p.cond, p.cmask, p.times, pred_out=out, ada=ada)
-            return
-        vb = self.vb
-        p.eng.forward(x, p.cond, p.cmask, p.times, pred_out=out, text=(p.ids, vb.null_cond_id, None, vb.null_cond), ada=ada)
-        if self.guided:
-            st, n = _lib.current_stream, out.numel()
-            p.eng.forward(x, p.cond, p.cmask, p.times, pred_out=p.f_null,
-                          text=(p.ids, vb.null_cond_id, p.drop_all, vb.null_cond), ada=ada)
-            _lib.call("vbx_axpy_dev", out, p.f_null, self.g_table, 0, p.f_diff, n, st())   # logits - null
-            _lib.call("vbx_axpy_dev", p.f_null, p.f_diff, self.g_table, 1, out, n, st())   # null + scale * diff
-
-
-class RKSampler(_SamplerEval, MidpointSampler):
-    """torchdiffeq's fixed-grid euler and rk4 (FixedGridODESolver: the grid is t = linspace(0, 1, steps), y1 = y0 + dy per interval)
-    on MidpointSampler's machinery: the concurrent half batches (split, per-part counters, _cu_share), one captured interval graph
-    replayed steps - 1 times, and the adaLN table -- here of every STAGE time, S per interval (vbx_io.ada_stride = S).  The stage
-    times and the coefficients dt * a_ij, dt * b_j are formed on the host in fp32 torch arithmetic (t0 + dt * c; c = 1 is t1 itself)
-    and live in device tables [intervals * S] / [intervals * S][S] indexed by the part's device counter."""
-
-    def __init__(self, voicebox, B, N, steps, method, use_graph=True, tokens=0, guided=False, split=None):
-        if method not in FIXED_TABLEAUS:
-            raise ValueError(f"RKSampler: no fixed-grid tableau {method!r} (have {sorted(FIXED_TABLEAUS)})")
-        super().__init__(voicebox, B, N, steps, use_graph=use_graph, tokens=tokens, guided=guided, split=split)
-        self.method = method
-        S = self.S = self.ada_stride = len(FIXED_TABLEAUS[method][2])
-        dev = self.y.device
-        t_table, c_table = fixed_grid_tables(method, steps)
-        self.t_table, self.c_table = t_table.to(dev), c_table.to(dev)
-        # stage derivatives: k1 is MidpointSampler's f, the stage inputs go to its ymid
-        ks = [self.f] + [torch.zeros_like(self.y) for _ in range(S - 1)]
-        for i, p in enumerate(self.parts):
-            sl = slice(i * p.B, (i + 1) * p.B)
-            p.k = [k[sl] for k in ks]
-        self.ks = ks
-        self.nfe = S * (steps - 1) * (2 if self.guided else 1)
-
-    def _interval_part(self, p):
-        st = _lib.current_stream
-        n = p.y.numel()
-        S = self.S
-        for s in range(S):
-            x = p.y
-            if s:
-                x = p.ymid
-                _lib.call("vbx_ode_combine", x, p.y, _ptrs(p.k[:s]), s, self.c_table, S, p.counter, S, s - 1, n, st())
-            if self.ada_tab is None:
-                _lib.call("vbx_ode_stage_time", p.times, p.B, self.t_table, p.counter, S, s, st())
-            self._eval(p, x, p.k[s], s)
-        _lib.call("vbx_ode_combine", p.y, p.y, _ptrs(p.k), S, self.c_table, S, p.counter, S, S - 1, n, st())
-        _lib.call("vbx_counter_add", p.counter, 1, st())
-
-    def stats(self):
-        return {"method": self.method, "nfe": self.nfe, "accepted": self.steps - 1, "rejected": 0}
-
-
-class Dopri5Sampler(_SamplerEval, MidpointSampler):
+class Dopri5Sampler(_Sampler):
     """torchdiffeq's adaptive dopri5 (RKAdaptiveStepsizeODESolver with the Dormand-Prince-Shampine tableau, FSAL, order 5), t from 0
     to 1 with tolerances atol / rtol.  The RMS error norm couples the whole batch: ONE stream (split 1).  The stage times are not
-    known in advance, so every forward evaluates its own adaLN projections (no table).  The initial step (f0, the probe, h) runs
-    eagerly; one attempt -- 6 forwards, the stage combinations, the two-launch error norm with the controller and the commit -- is
-    captured as a graph (the first attempt runs eagerly and warms up every kernel).  The host replays it and reads the 160-byte
-    step state back after each attempt (one small synchronisation per 6 function evaluations) until t >= 1, then evaluates the
-    dense-output quartic of the last accepted step at t = 1 (steps are not clipped: the last one overshoots).  `steps` does not
-    change the result (only the final time point is returned)."""
+    known in advance, so there is no grid and every forward evaluates its own adaLN projections (no table).  The initial step (f0,
+    the probe, h) runs eagerly; one attempt -- 6 forwards, the stage combinations, the two-launch error norm with the controller
+    and the commit -- is captured as a graph (the first attempt runs eagerly and warms up every kernel).  The host replays it and
+    reads the 160-byte step state back after each attempt (one small synchronisation per 6 function evaluations) until t >= 1, then
+    evaluates the dense-output quartic of the last accepted step at t = 1 (steps are not clipped: the last one overshoots).
+    `steps` does not change the result (only the final time point is returned) and is not kept; with no grid, t_table and
+    ada_stride are None and _eval passes ada=None."""
 
     def __init__(self, voicebox, B, N, steps, use_graph=True, tokens=0, guided=False, atol=1e-5, rtol=1e-5, max_attempts=10000):
-        super().__init__(voicebox, B, N, steps, use_graph=use_graph, tokens=tokens, guided=guided, split=1)
-        self.method = "dopri5"
-        self.use_ada_table = False
-        self.ada_stride = 0
+        super().__init__(voicebox, B, N, use_graph=use_graph, tokens=tokens, guided=guided, split=1, grid=None)
         self.atol, self.rtol, self.max_attempts = float(atol), float(rtol), int(max_attempts)
         dev = self.y.device
         self.ks = [self.f] + [torch.zeros_like(self.y) for _ in range(6)]  # k1 .. k7
@@ -405,7 +414,7 @@ class Dopri5Sampler(_SamplerEval, MidpointSampler):
         self.state = torch.zeros(DP_STATE, dtype=torch.float64, device=dev)
         self.slab = torch.zeros(_lib.lib().vbx_ode_norm_slab_doubles(self.y.numel()), dtype=torch.float64, device=dev)
         self.mult = 2 if self.guided else 1
-        self.last_stats = None
+        self.last_stats = self.nfe = None  # counted on the device: known after a run
 
     def _attempt(self):
         p, st, n = self.parts[0], _lib.current_stream, self.y.numel()
@@ -440,17 +449,7 @@ class Dopri5Sampler(_SamplerEval, MidpointSampler):
         self.graph = g
 
     def run(self, y0, cond=None, cond_mask=None, cond_token_ids=None, cond_scale=1.0):
-        if cond is not None:
-            self.cond.copy_(cond)
-        if cond_mask is not None:
-            self.cmask.copy_(cond_mask.to(self.cmask.device))
-        else:
-            self.cmask.fill_(True)
-        if self.tokens:
-            self.ids.copy_(cond_token_ids.to(self.ids.device))
-        if self.guided:
-            self.g_table[1] = float(cond_scale)
-        self.eng.bind_params()
+        self._load_inputs(cond, cond_mask, cond_token_ids, cond_scale)
         self.y.copy_(y0)
         self._initial()
         attempts = 0
@@ -480,3 +479,13 @@ class Dopri5Sampler(_SamplerEval, MidpointSampler):
 
     def stats(self):
         return dict(self.last_stats)
+
+
+def make_sampler(method, voicebox, B, N, steps, *, use_graph=True, tokens=0, guided=False, atol=1e-5, rtol=1e-5):
+    """The sampler of a torchdiffeq method name (atol / rtol: read by dopri5 only)."""
+    kw = dict(use_graph=use_graph, tokens=tokens, guided=guided)
+    if method == "midpoint":
+        return MidpointSampler(voicebox, B, N, steps, **kw)
+    if method == "dopri5":
+        return Dopri5Sampler(voicebox, B, N, steps, atol=atol, rtol=rtol, **kw)
+    return RKSampler(voicebox, B, N, steps, method, **kw)  # ValueError for a name without a tableau
