@@ -49,7 +49,8 @@ enum {
   VBX_EPI_F32 = 1,        /* C fp32 [M,ldc]   (+bias) (+resid fp32 [M,ldc]) ; optional bf16 copy   */
   VBX_EPI_QKV = 2,        /* to_qkv + MultiheadRMSNorm + rotary (voicebox_pytorch.py:320-328)       */
   VBX_EPI_GEGLU = 3,      /* FeedForward[0] + GEGLU (voicebox_pytorch.py:338-340,345)               */
-  VBX_EPI_SPLITK = 4      /* fp32 partial slabs [splits][M][N] for TN wgrad                        */
+  VBX_EPI_SPLITK = 4,     /* fp32 partial slabs [splits][M][N] for TN wgrad                        */
+  VBX_EPI_GELU = 5        /* C fp16 [M,ldc] = gelu_erf(acc + bias): NT, fp16 operands (f16 = 1), bias required; the 128-wide tiles */
 };
 
 typedef struct {
@@ -294,6 +295,29 @@ int vbx_griffinlim_lds_bytes(int n_fft, int win, int hop);
 int vbx_griffinlim(const float* mag, float* spec_a, float* spec_b, float* fb, float* wave, const float* window, const float* tw_re,
                    const float* tw_im, const float* renv, int B, int frames, int n_fft, int win, int hop, int n_iter, float m,
                    void* stream);
+/* vbx_istft: one torch.istft (center = True, length = None) of mag * phasor -- the synthesis and overlap-add launches of
+ *   vbx_griffinlim alone (what n_iter = 0 runs), without the analysis step's demand on the length: frames >= 2 is enough.
+ *   mag [B, frames, n_bins], spec [B, frames, n_bins, 2] the unit phasors (re, im), read only; fb, wave, window, tw_re, tw_im, renv
+ *   as vbx_griffinlim.  Two launches, the same bits on every run. */
+int vbx_istft(const float* mag, const float* spec, float* fb, float* wave, const float* window, const float* tw_re, const float* tw_im,
+              const float* renv, int B, int frames, int n_fft, int win, int hop, void* stream);
+/* Vocos decoder (voicebox_pytorch_amd.VocosDecoder; csrc/vocos.hip): the kernels around the GEMMs of a ConvNeXt backbone + ISTFT head.
+ * vbx_vocos_kp: Kp = 7 * C rounded up to a multiple of 32, the K of the embedding GEMM.
+ * vbx_vocos_pack_input: features x fp32 [B, C, frames] -> the im2col operand of the 7-tap input convolution, fp16 [B * frames, Kp]:
+ *   column tap * C + c of row (b, t) = x[b, c, t + tap - 3], zero outside [0, frames) of THAT batch element, zero columns from 7 * C
+ *   to Kp; log_in takes log(max(x, 1e-7)) first (the padding stays zero).  The matching weight is W[d, tap * C + c] = w[d, c, tap].
+ *   C <= 512.
+ * vbx_vocos_dwconv_ln: x fp32 [B, frames, D] -> y fp16 [B * frames, D] = LayerNorm_D(conv)(eps, biased variance, two passes) * ln_w
+ *   + ln_b with conv[b, t, d] = conv_bias[d] + sum_k taps[k, d] * x[b, t + k - 3, d] (taps fp32 [7, D], tap-major; zero padding per
+ *   batch element); taps = NULL: the LayerNorm of x itself.  fp32 throughout, one rounding (saturating) to fp16.  D a multiple of
+ *   64, at most 2048.
+ * vbx_vocos_head: h fp32 [rows, ld] (columns [0, n_bins) log-magnitude m, [n_bins, 2 n_bins) phase p) -> mag fp32 [rows, n_bins] =
+ *   min(exp(m), 100) and phasor fp32 [rows, n_bins, 2] = (cos p, sin p), the operands of vbx_istft; libm-accurate exp / sin / cos. */
+int vbx_vocos_kp(int C);
+int vbx_vocos_pack_input(const float* x, void* out_f16, int B, int C, int frames, int log_in, void* stream);
+int vbx_vocos_dwconv_ln(const float* x, const float* taps, const float* conv_bias, const float* ln_w, const float* ln_b, void* y_f16,
+                        int B, int frames, int D, float eps, void* stream);
+int vbx_vocos_head(const float* h, float* mag, float* phasor, long rows, int n_bins, int ld, void* stream);
 /* Sample-rate conversion (voicebox_pytorch_amd.resample; csrc/resample.hip): the polyphase windowed-sinc FIR of
  * torchaudio.functional.resample for the REDUCED rate pair orig : nw,
  *   y[r][q * nw + p] = sum_k h[p][k] * x[r][q * orig + k - width],  x = 0 outside [0, L),  p < nw, k < K = 2 * width + orig,

@@ -13,7 +13,7 @@ LIB_PATH = os.environ.get("VBX_LIB_PATH") or os.path.join(_HERE, "lib", "libvbx_
 P, I, L, F = C.c_void_p, C.c_int, C.c_long, C.c_float
 
 VBX_GEMM_NT, VBX_GEMM_NN, VBX_GEMM_TN = 0, 1, 2
-VBX_EPI_BF16, VBX_EPI_F32, VBX_EPI_QKV, VBX_EPI_GEGLU, VBX_EPI_SPLITK = 0, 1, 2, 3, 4
+VBX_EPI_BF16, VBX_EPI_F32, VBX_EPI_QKV, VBX_EPI_GEGLU, VBX_EPI_SPLITK, VBX_EPI_GELU = 0, 1, 2, 3, 4, 5
 VBX_GEMM_KERNEL_GEMM5 = 5  # vbx_gemm_route: the weight-stationary kernel (one workgroup per CU)
 
 
@@ -69,6 +69,11 @@ _PROTOS = {
     "vbx_mel_to_mag": [P, P, P, I, I, I, I, I, P],
     "vbx_griffinlim_lds_bytes": [I, I, I],
     "vbx_griffinlim": [P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, F, P],
+    "vbx_istft": [P, P, P, P, P, P, P, P, I, I, I, I, I, P],
+    "vbx_vocos_kp": [I],
+    "vbx_vocos_pack_input": [P, P, I, I, I, I, P],
+    "vbx_vocos_dwconv_ln": [P, P, P, P, P, P, I, I, I, F, P],
+    "vbx_vocos_head": [P, P, P, L, I, I, P],
     "vbx_resample_max_taps": [],
     "vbx_resample": [P, P, P, P, P, I, L, L, I, I, I, I, I, P],
     "vbx_pack_phoneme_input": [P, P, I, P, I, P, P, P, P, I, I, I, P],

@@ -1,7 +1,8 @@
 """The audio codec interface of VoiceBox(audio_enc_dec=...) (voicebox_pytorch.py:484-499) and LogMelCodec, the one encoder of the
 reference that has no learned weights (MelVoco.encode, :518-541: STFT -> HTK mel filter bank -> dB), served by one native kernel
 (csrc/mel.hip), and its weight-free decode: least-squares inversion of the filter bank, then Griffin-Lim phase recovery on the device
-(mel_to_magnitude / griffin_lim, csrc/griffinlim.hip).  Pretrained codecs (EnCodec, Vocos) are downloads and are not part of this package: any nn.Module with the five
+(mel_to_magnitude / griffin_lim, csrc/griffinlim.hip).  Pretrained codec weights (EnCodec, Vocos) are downloads and are not part of this
+package; the Vocos decoder NETWORK is (vocos.py: LogMelCodec(vocoder=VocosDecoder.from_checkpoint(path))).  Any nn.Module with the five
 members below can be passed as audio_enc_dec, inheritance from AudioEncoderDecoder is not required.
 
 PARITY UNPINNED: torchaudio is not a dependency and no fixture of it exists; LogMelCodec follows the published arithmetic of
@@ -81,10 +82,11 @@ def _stft_tables(n_fft, win_length):
     return win, ang.cos(), -ang.sin()
 
 
-def ola_reciprocal_envelope(n_fft, win_length, hop_length, frames):
+def ola_reciprocal_envelope(n_fft, win_length, hop_length, frames, window=None):
     """1 / (window-square envelope) of torch.istft on the kept range [n_fft / 2, n_fft / 2 + (frames - 1) * hop), fp64.  Raises
-    ValueError where torch.istft does: an envelope <= 1e-11 anywhere on that range (NOLA)."""
-    w2 = _stft_tables(n_fft, win_length)[0] ** 2
+    ValueError where torch.istft does: an envelope <= 1e-11 anywhere on that range (NOLA).  `window` [n_fft]: a window other than
+    the periodic Hann one (VocosDecoder's buffer)."""
+    w2 = (_stft_tables(n_fft, win_length)[0] if window is None else window.double()) ** 2
     env = torch.zeros(n_fft + (frames - 1) * hop_length, dtype=torch.float64)
     for f in range(frames):
         env[f * hop_length:f * hop_length + n_fft] += w2

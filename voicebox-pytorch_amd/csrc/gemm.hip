@@ -465,6 +465,31 @@ struct EpiBF16 {
 #endif
 template <> struct v9_onechunk<EpiBF16> : std::integral_constant<bool, VBX_V9_ONECHUNK != 0> {};
 
+// Linear + erf-GELU (the ConvNeXt pwconv1 of csrc/vocos.hip): C fp16 = gelu_erf(acc + bias), saturating as every unbounded fp16
+// operand (common.hpp).  The row pass of EpiBF16 with the activation in front of the store.
+struct EpiGELU {
+  u16* C; long ldc; const float* bias;
+  VBX_DEV void operator()(const float* Cs, int m0, int n0, int tid, int, int M, int N, int rows) const {
+    const int cc = tid & 15;
+    const int gc = n0 + cc * 8;
+    float bv[8];
+    gload8(bias + gc, gc < N, bv);
+    retire8(bv);
+    for (int it = 0; it < rows / 16; it++) {
+      const int row = it * 16 + (tid >> 4);
+      const int gr = m0 + row;
+      if (gr < M && gc < N) {
+        float v[8];
+        load8(Cs, row, cc, v);
+#pragma unroll
+        for (int i = 0; i < 8; i++) v[i] = gelu_erf(v[i] + bv[i]);
+        *reinterpret_cast<uint4*>(C + (long)gr * ldc + gc) = pack8_f16_sat(v);
+      }
+    }
+  }
+};
+template <> struct v9_onechunk<EpiGELU> : std::integral_constant<bool, VBX_V9_ONECHUNK != 0> {};
+
 struct EpiF32 {
   float* C; long ldc; const float* bias; const float* resid; u16* C2;
   VBX_DEV void operator()(const float* Cs, int m0, int n0, int tid, int, int M, int N, int rows) const {
@@ -834,6 +859,11 @@ static int gemm_validate(const vbx_gemm_desc* d) {
       VBX_REQUIRE(d->N % 128 == 0 && d->bias && d->C, "vbx_gemm GEGLU: N must be a multiple of 128, bias/C required");
       known = true;
       break;
+    case VBX_EPI_GELU:
+      VBX_REQUIRE(d->mode == VBX_GEMM_NT && d->f16, "vbx_gemm GELU: NT with fp16 operands only");
+      VBX_REQUIRE(d->C && d->ldc % 8 == 0 && d->ldc >= d->N && d->bias, "vbx_gemm GELU: bad C/ldc, bias required");
+      known = true;
+      break;
     case VBX_EPI_SPLITK:
       VBX_REQUIRE(d->mode == VBX_GEMM_TN && d->C && d->splits >= 1, "vbx_gemm SPLITK: TN only");
       known = true;
@@ -898,6 +928,10 @@ extern "C" int vbx_gemm(const vbx_gemm_desc* d, void* stream) {
     case VBX_EPI_GEGLU: {
       EpiGEGLU e{(u16*)d->C, d->ldc, d->bias, (u16*)d->C2, d->N, (u16*)d->C3, d->f16};
       return d->f16 ? launch<0, 0, true>(p, e, 1, kernel, st) : launch<0, 0>(p, e, 1, kernel, st);
+    }
+    case VBX_EPI_GELU: {
+      EpiGELU e{(u16*)d->C, d->ldc, d->bias};
+      return launch<0, 0, true>(p, e, 1, kernel, st);
     }
     default: {  // VBX_EPI_SPLITK
       p.kchunk = cdiv(cdiv(d->K, d->splits), BK) * BK;

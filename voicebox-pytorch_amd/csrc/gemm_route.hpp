@@ -46,8 +46,9 @@ inline bool gemm5_serves(const vbx_gemm_desc* d, int cus) {
 }
 
 // gemm3.hip (256 x 256) and gemm4.hip (128 x 256): every NT / NN combination gemm.hip serves (gemm3 also TN / split-K) except the bf16
-// epilogue on fp16 operands; their LDS-DMA staging needs K in whole 16-byte pieces.
+// epilogue on fp16 operands and the GELU epilogue; their LDS-DMA staging needs K in whole 16-byte pieces.
 inline bool wide_tile_serves(const vbx_gemm_desc* d, int tile) {
+  if (d->epilogue == VBX_EPI_GELU) return false;  // the 128-wide kernels' functor only (gemm.hip EpiGELU)
   if (d->K % 8 || (d->epilogue == VBX_EPI_BF16 && d->mode == VBX_GEMM_NT && d->f16)) return false;
   return tile == VBX_GEMM_KERNEL_GEMM3 || d->mode != VBX_GEMM_TN;
 }

@@ -260,3 +260,25 @@ extern "C" int vbx_griffinlim(const float* mag, float* spec_a, float* spec_b, fl
   VBX_LAUNCH_CHECK();
   return 0;
 }
+
+// One inverse STFT (torch.istft, center = True, length = None) of mag * phasor: the synthesis and overlap-add launches above alone,
+// so nothing of the analysis step's reflect padding is demanded -- two frames are enough (csrc/vocos.hip's last step).
+extern "C" int vbx_istft(const float* mag, const float* spec, float* fb, float* wave, const float* window, const float* tw_re,
+                         const float* tw_im, const float* renv, int B, int frames, int n_fft, int win, int hop, void* stream) {
+  VBX_REQUIRE(mag && spec && fb && wave && window && tw_re && tw_im && renv && B > 0 && B <= 65535, "vbx_istft: bad args");
+  VBX_REQUIRE(n_fft >= 256 && n_fft <= GL_MAX_FFT && (n_fft & (n_fft - 1)) == 0, "vbx_istft: n_fft must be a power of two in 256 .. 2048");
+  VBX_REQUIRE(win > 0 && win <= n_fft && hop > 0 && hop <= win, "vbx_istft: need 0 < hop <= win_length <= n_fft");
+  VBX_REQUIRE(frames > 1 && (long)(frames - 1) * hop + n_fft < 2147483647L, "vbx_istft: need at least two frames");
+  int log2n = 0;
+  while ((1 << log2n) < n_fft) log2n++;
+  const int left = (n_fft - win) / 2;
+  const long L = (long)(frames - 1) * hop;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(gl_synth_kernel, dim3(cdiv(frames, GL_FRAMES), B), dim3(256), sizeof(float) * 4 * fft_ld(n_fft), st,
+                     (const float2*)spec, (const float2*)spec, mag, fb, window, tw_re, tw_im, 0.f, 1, frames, n_fft, log2n, win, left);
+  VBX_LAUNCH_CHECK();
+  hipLaunchKernelGGL(gl_ola_kernel, dim3(cdiv(L, 256), B), dim3(256), 0, st, (const float*)fb, wave, renv, frames, win, left, hop,
+                     n_fft / 2);
+  VBX_LAUNCH_CHECK();
+  return 0;
+}
