@@ -318,6 +318,25 @@ int vbx_vocos_pack_input(const float* x, void* out_f16, int B, int C, int frames
 int vbx_vocos_dwconv_ln(const float* x, const float* taps, const float* conv_bias, const float* ln_w, const float* ln_b, void* y_f16,
                         int B, int frames, int D, float eps, void* stream);
 int vbx_vocos_head(const float* h, float* mag, float* phasor, long rows, int n_bins, int ld, void* stream);
+/* Residual vector quantizer (voicebox_pytorch_amd.ResidualVQ / EncodecVocoCodec; csrc/rvq.hip): the RVQ of an EnCodec-style codec,
+ * codebooks fp32 [Q, K, D].  D a multiple of 8 in 8 .. 256, K in 2 .. 4096 (any value), Q in 1 .. 32, any B * N >= 1; everything
+ * else returns VBX_EINVAL.  Codes are int64, laid out [B, N, Q] (codes_qn = 0) or [B, Q, N] (codes_qn = 1, what the reference's
+ * decode_to_codes returns).  No atomics, no host synchronisation: the same bits on every run.
+ * vbx_rvq_norms: norms fp32 [Q, K] = |c_qk|^2, an fp32 fmaf chain over the D components (error <= (D + 1) 2^-24 |c|^2).
+ * vbx_rvq_encode: x fp32 [B * N, D] -> codes and, unless NULL, quantized fp32 [B * N, D].  Per frame, r_0 = x and for q = 0 .. Q-1:
+ *   code_q = argmin_k norms[q][k] - 2 r_q . c_qk, the LOWEST index on an exact tie;  r_{q+1} = r_q - c_q[code_q] in fp32;
+ *   quantized = c_0[code_0] + c_1[code_1] + ..., summed in that order in fp32.  The search is fp32 throughout (fp32-input MFMA =
+ *   an fmaf chain per dot product, the same component order for every codeword), so for the r_q rebuilt from the earlier codes
+ *     d(code_q) - min_k d(k) <= (D + 2) 2^-23 (|r_q| + max_k |c_qk|)^2,   d(k) = |c_qk|^2 - 2 r_q . c_qk  exactly.
+ *   norms must be vbx_rvq_norms of the same codebooks.  One launch, a workgroup per 32 frames.
+ * vbx_rvq_decode: codes -> out fp32 = sum over q = 0 .. Q-1, in that order in fp32, of c_q[code_q]: row-major [B * N, D]
+ *   (channel_first = 0, the latents) or [B, D, N] (channel_first = 1, what VocosDecoder takes).  An index outside [0, K)
+ *   contributes zero and is never dereferenced. */
+int vbx_rvq_norms(const float* codebooks, float* norms, int Q, int K, int D, void* stream);
+int vbx_rvq_encode(const float* x, const float* codebooks, const float* norms, long* codes, float* quantized, int B, int N, int D,
+                   int K, int Q, int codes_qn, void* stream);
+int vbx_rvq_decode(const long* codes, const float* codebooks, float* out, int B, int N, int D, int K, int Q, int codes_qn,
+                   int channel_first, void* stream);
 /* Sample-rate conversion (voicebox_pytorch_amd.resample; csrc/resample.hip): the polyphase windowed-sinc FIR of
  * torchaudio.functional.resample for the REDUCED rate pair orig : nw,
  *   y[r][q * nw + p] = sum_k h[p][k] * x[r][q * orig + k - width],  x = 0 outside [0, L),  p < nw, k < K = 2 * width + orig,

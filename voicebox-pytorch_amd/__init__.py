@@ -4,7 +4,8 @@ Public API mirrors the reference package (voicebox_pytorch/__init__.py:1-15) for
 VoiceBox, ConditionalFlowMatcherWrapper, Transformer, Attend, DurationPredictor (inference), VoiceBoxTrainer (latents or waves),
 AudioEncoderDecoder / LogMelCodec (the codec interface, the log-mel encoder and its vocoder-free decode), griffin_lim (Griffin-Lim
 phase recovery on the device), resample / Resample (sample-rate conversion on the device, in front of a codec), VocosDecoder (the
-Vocos neural vocoder's decoder on the device; weights are the user's, from a local checkpoint).
+Vocos neural vocoder's decoder on the device; weights are the user's, from a local checkpoint), ResidualVQ / EncodecVocoCodec
+(EnCodec's residual vector quantizer on the device and the reference's EncodecVoco around it: codes in and out).
 """
 from . import _lib  # noqa: F401
 
@@ -14,13 +15,13 @@ try:  # model classes need torch; keep `_lib` importable on its own
     from .model import VoiceBox, ConditionalFlowMatcherWrapper, Transformer, Attend  # noqa: F401
     from .trainer import VoiceBoxTrainer  # noqa: F401
     from .duration import DurationPredictor  # noqa: F401
-    from .codec import AudioEncoderDecoder, LogMelCodec, griffin_lim, resample, Resample  # noqa: F401
+    from .codec import AudioEncoderDecoder, LogMelCodec, griffin_lim, resample, Resample, ResidualVQ, EncodecVocoCodec  # noqa: F401
     from .vocos import VocosDecoder  # noqa: F401
     from .engine import precise_mode, set_precise, precise_enabled  # noqa: F401
 
     __all__ += ["VoiceBox", "ConditionalFlowMatcherWrapper", "Transformer", "Attend", "VoiceBoxTrainer", "DurationPredictor", "mask_from_frac_lengths",
                 "mask_from_start_end_indices", "prob_mask_like", "reduce_masks_with_and", "precise_mode", "set_precise", "precise_enabled",
-                "AudioEncoderDecoder", "LogMelCodec", "griffin_lim", "resample", "Resample", "VocosDecoder"]
+                "AudioEncoderDecoder", "LogMelCodec", "griffin_lim", "resample", "Resample", "VocosDecoder", "ResidualVQ", "EncodecVocoCodec"]
 except ModuleNotFoundError as _e:  # pragma: no cover - only while the package is being bootstrapped
     if "masks" not in str(_e) and "model" not in str(_e):
         raise

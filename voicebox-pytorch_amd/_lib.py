@@ -74,6 +74,9 @@ _PROTOS = {
     "vbx_vocos_pack_input": [P, P, I, I, I, I, P],
     "vbx_vocos_dwconv_ln": [P, P, P, P, P, P, I, I, I, F, P],
     "vbx_vocos_head": [P, P, P, L, I, I, P],
+    "vbx_rvq_norms": [P, P, I, I, I, P],
+    "vbx_rvq_encode": [P, P, P, P, P, I, I, I, I, I, I, P],
+    "vbx_rvq_decode": [P, P, P, I, I, I, I, I, I, I, P],
     "vbx_resample_max_taps": [],
     "vbx_resample": [P, P, P, P, P, I, L, L, I, I, I, I, I, P],
     "vbx_pack_phoneme_input": [P, P, I, P, I, P, P, P, P, I, I, I, P],

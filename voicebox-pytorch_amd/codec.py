@@ -12,6 +12,10 @@ UNPINNED likewise: griffin_lim follows the published loop of torchaudio.function
 torch.stft / torch.istft in tests/griffinlim_ref.py; mel_to_magnitude is a least-squares inverse clamped at zero and is NOT
 torchaudio's InverseMelScale.  resample / Resample (csrc/resample.hip), the sample-rate conversion in front of a codec, are UNPINNED
 too: the published arithmetic of torchaudio.functional.resample, restated in fp64 in tests/resample_ref.py.
+
+ResidualVQ / EncodecVocoCodec (csrc/rvq.hip) are the reference's EncodecVoco (:551-592) around a residual vector quantizer on the device:
+codes in and out, latents from codes, features for a VocosDecoder.  EnCodec's SEANet encoder is not built (encoder= is the user's module)
+and parity with encodec / vocos / vector_quantize_pytorch is UNPINNED likewise (tests/rvq_ref.py restates the arithmetic).
 """
 import functools
 import math
@@ -361,3 +365,224 @@ class LogMelCodec(AudioEncoderDecoder):
         if self.log:
             mel = torch.pow(10.0, 0.05 * mel)  # DB_to_amplitude(ref=1, power=0.5)
         return self.vocoder(mel)
+
+
+RVQ_BANDWIDTH_QUANTIZERS = (2, 4, 8, 16)  # EnCodec 24 kHz: bandwidth ids 0 .. 3 (1.5, 3, 6, 12 kbps) -> codebooks in use
+
+
+def _check_rvq_args(dim, codebook_size, num_quantizers):
+    if dim % 8 or not 8 <= dim <= 256:
+        raise NotImplementedError(f"ResidualVQ: dim must be a multiple of 8 in 8 .. 256 (got {dim})")
+    if not 2 <= codebook_size <= 4096:
+        raise NotImplementedError(f"ResidualVQ: codebook_size must be in 2 .. 4096 (got {codebook_size})")
+    if not 1 <= num_quantizers <= 32:
+        raise NotImplementedError(f"ResidualVQ: num_quantizers must be in 1 .. 32 (got {num_quantizers})")
+
+
+class ResidualVQ(nn.Module):
+    """The residual vector quantizer of an EnCodec-style codec on the device (csrc/rvq.hip): one fp32 buffer `codebooks`
+    [num_quantizers, codebook_size, dim], Euclidean codebooks, inference only.  Per frame, r_0 = x and for each quantizer q
+    code_q = argmin_k |r_q - c_qk|^2 (the lowest index on an exact tie), r_{q+1} = r_q - c_q[code_q]; the quantized frame is
+    c_0[code_0] + c_1[code_1] + ... summed in that order in fp32.  The search is fp32 throughout (include/vbx.h states its contract).
+
+    forward(latents [B, N, dim]) -> (quantized [B, N, dim], codes int64 [B, N, Q], None): the triple the reference unpacks from
+    `self.encodec.rq(latents)` (voicebox_pytorch.py:586-592); encode -> codes; decode(codes) -> latents.
+
+    PARITY UNPINNED: vector_quantize_pytorch / encodec are not dependencies and no fixture of them exists; this follows their
+    published arithmetic, restated in fp64 in tests/rvq_ref.py.  load_state_dict also takes two published layouts:
+    `layers.{q}._codebook.embed` of shape [1, K, dim] or [K, dim] (vector_quantize_pytorch) and a flat [Q' * K, dim] table under
+    `codebook_weights` (Vocos's EncodecFeatures; the first num_quantizers codebooks of a longer table are kept).
+
+    Raises NotImplementedError outside dim a multiple of 8 in 8 .. 256, codebook_size 2 .. 4096, num_quantizers 1 .. 32.  GPU
+    tensors only; float inputs of other dtypes are converted in."""
+
+    def __init__(self, dim=128, codebook_size=1024, num_quantizers=8):
+        super().__init__()
+        _check_rvq_args(dim, codebook_size, num_quantizers)
+        self.dim, self.codebook_size, self.num_quantizers = dim, codebook_size, num_quantizers
+        self.register_buffer("codebooks", torch.randn(num_quantizers, codebook_size, dim))
+        self._norms, self._norms_key = None, None
+
+    # -- state
+    def _stacked(self, state_dict, prefix=""):
+        """`codebooks` [Q, K, dim] from whichever of the three layouts the dict holds under `prefix`, or None"""
+        Q, K, D = self.num_quantizers, self.codebook_size, self.dim
+        if prefix + "codebooks" in state_dict:
+            return state_dict[prefix + "codebooks"]
+        if prefix + "layers.0._codebook.embed" in state_dict:
+            rows = []
+            for q in range(Q):
+                e = state_dict[f"{prefix}layers.{q}._codebook.embed"]
+                rows.append(e[0] if e.ndim == 3 else e)
+            return torch.stack(rows)
+        if prefix + "codebook_weights" in state_dict:
+            flat = state_dict[prefix + "codebook_weights"]
+            if flat.ndim != 2 or flat.shape[1] != D or flat.shape[0] % K or flat.shape[0] < Q * K:
+                raise RuntimeError(f"ResidualVQ: codebook_weights {tuple(flat.shape)} does not hold {Q} codebooks of {K} x {D}")
+            return flat[:Q * K].reshape(Q, K, D)
+        return None
+
+    def _load_from_state_dict(self, state_dict, prefix, *args, **kw):
+        """torch's per-module hook, so the published layouts load at any depth (ResidualVQ.load_state_dict as well as a codec's
+        or a VoiceBox's with `rvq.` in front): they are rewritten to `codebooks` in the copy of the dict torch hands over"""
+        cb = self._stacked(state_dict, prefix)
+        if cb is not None and prefix + "codebooks" not in state_dict:
+            for k in [k for k in state_dict if k.startswith(prefix + "layers.") or k == prefix + "codebook_weights"]:
+                del state_dict[k]
+            state_dict[prefix + "codebooks"] = cb.detach().to(torch.float32)
+        return super()._load_from_state_dict(state_dict, prefix, *args, **kw)
+
+    def _weights_key(self):
+        t = self.codebooks
+        return (t.data_ptr(), 0 if t.is_inference() else t._version)
+
+    def _tables(self, device, who):
+        """(codebooks, |c|^2 table) on `device`; the table is rebuilt when the buffer's storage or version counter changed
+        (copy_, load_state_dict, .to()).  A write through `.data` changes neither: call mark_weights_dirty() after one.
+        As LogMelCodec and VocosDecoder do, a module whose buffer is on another device than the input MOVES there (`self.to`): one
+        ResidualVQ shared by several codecs follows the last input's device."""
+        if device.type != "cuda":
+            raise _lib.VbxError(f"{who} runs only on an MI355X (gfx950) through libvbx_hip.so; the input is on '{device}'")
+        if self.codebooks.device != device:
+            self.to(device)
+        key = self._weights_key()
+        if key != self._norms_key:
+            Q, K, D = self.codebooks.shape
+            norms = torch.empty(Q, K, dtype=torch.float32, device=device)
+            _lib.call("vbx_rvq_norms", self.codebooks, norms, Q, K, D, _lib.current_stream())
+            self._norms, self._norms_key = norms, key
+        return self.codebooks, self._norms
+
+    def mark_weights_dirty(self):
+        self._norms_key = None
+
+    # -- device path
+    def _search(self, latents, *, codes_qn, quantized, who):
+        if latents.ndim != 3 or latents.shape[2] != self.dim:
+            raise ValueError(f"{who} takes latents (batch, frames, dim = {self.dim}), got {tuple(latents.shape)}")
+        if not latents.is_floating_point():
+            raise TypeError(f"{who} takes floating-point latents (got {latents.dtype})")
+        B, N, D = latents.shape
+        if B < 1 or N < 1:
+            raise ValueError(f"{who} needs at least one frame, got {tuple(latents.shape)}")
+        cb, norms = self._tables(latents.device, who)
+        Q, K = self.num_quantizers, self.codebook_size
+        with torch.no_grad():  # plain tensors: the latents may go on into a training step
+            x = latents.detach().to(torch.float32).contiguous()
+            codes = torch.empty((B, Q, N) if codes_qn else (B, N, Q), dtype=torch.int64, device=x.device)
+            quant = torch.empty(B, N, D, dtype=torch.float32, device=x.device) if quantized else None
+            _lib.call("vbx_rvq_encode", x, cb, norms, codes, quant, B, N, D, K, Q, int(codes_qn), _lib.current_stream())
+        return quant, codes
+
+    def _gather(self, codes, *, codes_qn, channel_first, check, who):
+        if codes.ndim != 3 or codes.dtype != torch.int64:
+            raise ValueError(f"{who} takes int64 codes (batch, {'quantizers, frames' if codes_qn else 'frames, quantizers'}), got "
+                             f"{codes.dtype} {tuple(codes.shape)}")
+        B, Qc, N = codes.shape if codes_qn else (codes.shape[0], codes.shape[2], codes.shape[1])
+        if not 1 <= Qc <= self.num_quantizers or B < 1 or N < 1:
+            raise ValueError(f"{who}: codes of {Qc} quantizers x {N} frames for a quantizer of {self.num_quantizers}")
+        cb, _ = self._tables(codes.device, who)
+        K, D = self.codebook_size, self.dim
+        with torch.no_grad():  # plain tensors: the latents may go on into a training step
+            codes = codes.detach().contiguous()
+            if check:
+                lo, hi = torch.aminmax(codes)
+                if int(lo) < 0 or int(hi) >= K:
+                    raise ValueError(f"{who}: codes must lie in [0, {K}) (found {int(lo)} .. {int(hi)})")
+            out = torch.empty((B, D, N) if channel_first else (B, N, D), dtype=torch.float32, device=codes.device)
+            _lib.call("vbx_rvq_decode", codes, cb, out, B, N, D, K, Qc, int(codes_qn), int(channel_first), _lib.current_stream())
+        return out
+
+    def forward(self, latents):
+        quant, codes = self._search(latents, codes_qn=False, quantized=True, who="ResidualVQ")
+        return quant, codes, None
+
+    def encode(self, latents):
+        return self._search(latents, codes_qn=False, quantized=False, who="ResidualVQ.encode")[1]
+
+    def decode(self, codes, check=True):
+        """codes int64 [B, N, Q' <= Q] -> latents fp32 [B, N, dim].  check: one reduction over the codes and a ValueError for an
+        index outside [0, codebook_size); with check=False such an index contributes zero."""
+        return self._gather(codes, codes_qn=False, channel_first=False, check=check, who="ResidualVQ.decode")
+
+
+class EncodecVocoCodec(AudioEncoderDecoder):
+    """The reference's EncodecVoco (voicebox_pytorch.py:551-592) on the device: EnCodec's residual vector quantizer (ResidualVQ) and
+    a Vocos decoder (VocosDecoder) conditioned on EnCodec features.  Latents are the summed codewords [B, frames, rvq.dim].
+
+      decode_to_codes(latents) -> codes int64 [B, Q, frames]        the RVQ search
+      codes_to_latents(codes)  -> latents [B, frames, dim]          EncodecWrapper's get_emb_from_indices
+      codes_to_features(codes) -> features [B, dim, frames]         Vocos.codes_to_features (from feature_rvq when given, else rvq)
+      decode(latents)          -> wave = vocoder(codes_to_features(decode_to_codes(latents))), batched
+      encode(audio)            -> codes_to_latents(decode_to_codes(encoder(audio)))
+
+    EnCodec's SEANet encoder (strided convolutions and an LSTM) is NOT built: `encoder` is the user's module, audio [B, T] ->
+    unquantized latents [B, frames, dim]; without one, encode raises.  Neither weights nor the `encodec` / `vocos` libraries are
+    part of this package; PARITY with them is UNPINNED (tests/rvq_ref.py restates the arithmetic)."""
+
+    def __init__(self, *, rvq, vocoder, encoder=None, feature_rvq=None, sampling_rate=24000, downsample_factor=320):
+        super().__init__()
+        if not isinstance(rvq, ResidualVQ) or (feature_rvq is not None and not isinstance(feature_rvq, ResidualVQ)):
+            raise TypeError("EncodecVocoCodec: rvq (and feature_rvq, when given) must be a ResidualVQ")
+        if feature_rvq is not None and feature_rvq.num_quantizers < rvq.num_quantizers:
+            raise ValueError("EncodecVocoCodec: feature_rvq must hold at least the quantizers of rvq")
+        self.rvq, self.vocoder, self.encoder, self.feature_rvq = rvq, vocoder, encoder, feature_rvq
+        self._sampling_rate, self._downsample_factor = sampling_rate, downsample_factor
+
+    @property
+    def downsample_factor(self):
+        return self._downsample_factor
+
+    @property
+    def latent_dim(self):
+        return self.rvq.dim
+
+    @property
+    def sampling_rate(self):
+        return self._sampling_rate
+
+    @classmethod
+    def from_vocos_checkpoint(cls, path, *, bandwidth_id=2, encoder=None, codebook_size=1024, hop_length=None, sampling_rate=24000):
+        """A LOCAL Vocos-EnCodec state dict (torch.save of the dict, or {'state_dict': ...}): `feature_extractor.codebook_weights`
+        [Q' * codebook_size, dim] becomes the codebooks, of which bandwidth ids 0 .. 3 use the first 2, 4, 8, 16 (capped by what
+        the table holds); the vocoder is built as VocosDecoder.from_checkpoint(path, bandwidth_id=bandwidth_id) builds it, and its
+        limits apply: the one published Vocos-EnCodec model (n_fft 1280, padding="same") is outside them and raises
+        NotImplementedError, so this loader has only been exercised on synthetic files of that layout."""
+        from .vocos import VocosDecoder, read_checkpoint
+
+        sd = read_checkpoint(path)
+        if "feature_extractor.codebook_weights" not in sd:
+            raise KeyError("from_vocos_checkpoint: the state dict has no feature_extractor.codebook_weights (not a Vocos-EnCodec model)")
+        if not 0 <= bandwidth_id < len(RVQ_BANDWIDTH_QUANTIZERS):
+            raise ValueError(f"bandwidth_id must be in 0 .. {len(RVQ_BANDWIDTH_QUANTIZERS) - 1} (got {bandwidth_id})")
+        flat = sd["feature_extractor.codebook_weights"]
+        if flat.ndim != 2 or flat.shape[0] % codebook_size or flat.shape[0] < codebook_size:
+            raise RuntimeError(f"from_vocos_checkpoint: codebook_weights {tuple(flat.shape)} is not a whole number of codebooks of "
+                               f"{codebook_size}")
+        rvq = ResidualVQ(dim=flat.shape[1], codebook_size=codebook_size,
+                         num_quantizers=min(RVQ_BANDWIDTH_QUANTIZERS[bandwidth_id], flat.shape[0] // codebook_size))
+        rvq.load_state_dict({"codebook_weights": flat})
+        vocoder = VocosDecoder.from_state_dict(sd, hop_length=hop_length, bandwidth_id=bandwidth_id)
+        return cls(rvq=rvq, vocoder=vocoder, encoder=encoder, sampling_rate=sampling_rate, downsample_factor=vocoder.hop_length).eval()
+
+    def decode_to_codes(self, latents):
+        return self.rvq._search(latents, codes_qn=True, quantized=False, who="EncodecVocoCodec.decode_to_codes")[1]
+
+    def codes_to_latents(self, codes, check=True):
+        return self.rvq._gather(codes, codes_qn=True, channel_first=False, check=check, who="EncodecVocoCodec.codes_to_latents")
+
+    def codes_to_features(self, codes, check=True):
+        table = self.rvq if self.feature_rvq is None else self.feature_rvq
+        return table._gather(codes, codes_qn=True, channel_first=True, check=check, who="EncodecVocoCodec.codes_to_features")
+
+    def encode(self, audio):
+        if self.encoder is None:
+            raise NotImplementedError("EncodecVocoCodec.encode needs an encoder (audio [B, T] -> latents [B, frames, dim]): EnCodec's "
+                                      "SEANet encoder is not built; pass encoder=")
+        with torch.no_grad():
+            z = self.encoder(audio)
+        return self.codes_to_latents(self.decode_to_codes(z), check=False)
+
+    def decode(self, latents):
+        """the reference loops over the batch and stacks (voicebox_pytorch.py:577-584); the same arithmetic, batched"""
+        return self.vocoder(self.codes_to_features(self.decode_to_codes(latents), check=False))

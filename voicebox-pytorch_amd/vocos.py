@@ -23,6 +23,12 @@ from .codec import _check_stft_args, _stft_tables, ola_reciprocal_envelope
 LN_EPS = 1e-6
 
 
+def read_checkpoint(path):
+    """the state dict of a LOCAL torch.save file: the dict itself or its 'state_dict' entry"""
+    sd = torch.load(path, map_location="cpu", weights_only=True)
+    return sd["state_dict"] if isinstance(sd, dict) and "state_dict" in sd else sd
+
+
 class _ConvNeXtBlock(nn.Module):
     def __init__(self, dim, intermediate_dim, gamma0):
         super().__init__()
@@ -60,7 +66,8 @@ class VocosDecoder(nn.Module):
     features are taken as given unless input_log, which applies log(clamp(x, min=1e-7)) first -- what Vocos's own mel feature
     extractor feeds its backbone (the published vocos-mel-24khz weights expect it, at hop_length 256).
 
-    Raises NotImplementedError for what is not built: padding="same", adanorm_num_embeddings (the EnCodec-conditioned variant),
+    Raises NotImplementedError for what is not built: padding="same", adanorm_num_embeddings (the EnCodec-conditioned variant as a
+    module; from_checkpoint(bandwidth_id=...) loads such a checkpoint for ONE fixed id),
     n_fft outside the powers of two 256 .. 2048, dim not a multiple of 64 or above 2048, intermediate_dim not a multiple of 8,
     input_channels above 512, fewer than two frames, a hop / n_fft pair beyond the LDS of the inverse transform; ValueError, as
     ola_reciprocal_envelope, where window and hop violate NOLA.  GPU tensors only."""
@@ -97,15 +104,35 @@ class VocosDecoder(nn.Module):
         kept = {k: v for k, v in state_dict.items() if not k.startswith("feature_extractor.")}
         return super().load_state_dict(kept, strict=strict, **kw)
 
+    @staticmethod
+    def _fold_adanorm(sd, bandwidth_id):
+        """The EnCodec-conditioned variant's AdaLayerNorm is layer_norm(x) * scale[id] + shift[id] with one id per call: for a
+        fixed id, a plain LayerNorm whose weight / bias are row `id` of the two embedding tables."""
+        out = {}
+        for k, v in sd.items():
+            for emb, name in ((".scale.weight", ".weight"), (".shift.weight", ".bias")):
+                if k.startswith("backbone.") and k.endswith(".norm" + emb):
+                    if not 0 <= bandwidth_id < v.shape[0]:
+                        raise ValueError(f"VocosDecoder: bandwidth_id {bandwidth_id} is outside the {v.shape[0]} rows of {k}")
+                    k, v = k[:-len(emb)] + name, v[bandwidth_id].clone()
+            out[k] = v
+        return out
+
     @classmethod
-    def from_checkpoint(cls, path, *, hop_length=None, input_log=False, padding="center"):
-        """A LOCAL file written by torch.save: a Vocos state dict or {'state_dict': ...}.  The widths are read off the shapes;
-        hop_length is not in a state dict (default n_fft / 4, the published models' ratio)."""
-        sd = torch.load(path, map_location="cpu", weights_only=True)
-        if isinstance(sd, dict) and "state_dict" in sd:
-            sd = sd["state_dict"]
+    def from_checkpoint(cls, path, *, hop_length=None, input_log=False, padding="center", bandwidth_id=None):
+        """A LOCAL file written by torch.save: a Vocos state dict or {'state_dict': ...}; see from_state_dict."""
+        return cls.from_state_dict(read_checkpoint(path), hop_length=hop_length, input_log=input_log, padding=padding,
+                                   bandwidth_id=bandwidth_id)
+
+    @classmethod
+    def from_state_dict(cls, sd, *, hop_length=None, input_log=False, padding="center", bandwidth_id=None):
+        """A Vocos state dict already in memory.  The widths are read off the shapes; hop_length is not in a state dict (default n_fft / 4, the published models' ratio).  bandwidth_id: for the
+        EnCodec-conditioned variant (backbone.norm.scale / .shift embeddings), the one id this decoder is built for; its rows
+        become the LayerNorm weights.  Without it such a dict raises NotImplementedError."""
         if any(k.startswith("backbone.norm.scale") or k.startswith("backbone.norm.shift") for k in sd):
-            raise NotImplementedError("VocosDecoder: adanorm_num_embeddings (the EnCodec-conditioned AdaLayerNorm variant) is not built")
+            if bandwidth_id is None:
+                raise NotImplementedError("VocosDecoder: adanorm_num_embeddings (the EnCodec-conditioned AdaLayerNorm variant) is not built")
+            sd = cls._fold_adanorm(sd, int(bandwidth_id))
         dim, channels, _ = sd["backbone.embed.weight"].shape
         layers = 1 + max(int(k.split(".")[2]) for k in sd if k.startswith("backbone.convnext."))
         n_fft = sd["head.out.weight"].shape[0] - 2
