@@ -734,6 +734,23 @@ int vbx_model_adaln_table(const vbx_model* m, const float* temb, int n, float* a
 int vbx_model_backward_head(const vbx_model* m, const vbx_io* io, const float* gscale, void* stream);
 int vbx_model_backward_layer(const vbx_model* m, const vbx_io* io, int layer, void* stream);
 int vbx_model_backward_embed(const vbx_model* m, const vbx_io* io, void* stream);
+/* Weight gradients beside the dx chain.  Nothing in a layer's backward reads its four weight gradients, so a backward with
+ * vbx_model.defer_reduce = 1 (no GateLoop, no u-net, grouped GEMMs) submits each layer's grouped weight-gradient launch and its slab
+ * reduce to a low-priority side stream of the library (one per device, created on first use), where they fill the CUs that the
+ * next layer's dgrads, norms and attention tail leave idle.  The four operands that the chain would overwrite under them live in
+ * two (dxb: three) copies indexed by layer and the side stream has slab regions of its own; events order the rest
+ * (csrc/wgrad_overlap_plan.hpp).  vbx_model_backward_embed -- always the last call of a backward -- ends with the caller's stream
+ * waiting for the side stream, and vbx_model_backward_head begins with the same wait.  Same kernels, same reduction order:
+ * gradients and sq_partials are bit-identical to the in-line order.  In line instead: every other backward, a capturing stream,
+ * while vbx_prof_enable(1) is on, and with vbx_wgrad_overlap(0) (environment VBX_WGRAD_OVERLAP=0 presets it; 1 = default).
+ * Not thread safe; call between backwards. */
+int vbx_wgrad_overlap(int on);
+/* how many layers this process has submitted to the side stream so far (tests: the path that ran is the path that was meant) */
+int vbx_wgrad_overlap_forks(void);
+/* tests only: one idle wave (vbx_stream_delay) of side_us microseconds in front of every side-stream submission and of main_us at
+ * the start of every layer on the caller's stream, 0 .. 2000 each (0, 0 = off): a missing wait of the schedule then shows as a
+ * wrong gradient even at small shapes. */
+int vbx_wgrad_overlap_delay(float side_us, float main_us);
 
 /* tests/debug only: device pointer of a named tensor inside the activation arena (NULL if unknown) */
 void* vbx_model_debug_ptr(const vbx_model* m, const char* name, int layer);
@@ -786,7 +803,10 @@ int vbx_model_pack_weights_precise(const vbx_model* m, void* stream);
  * ff_in, ff_out, the four dgrads, attention backward, the weight-gradient launch) with a pair of HIP events recorded on the
  * caller's stream, i.e. the launches are timed where they run -- between their real neighbours -- not back to back in
  * isolation.  vbx_prof_collect synchronises on the recorded events, aggregates by label and disables the recording.
- * Not hipGraph-capture safe: do not enable around a capture.  bench.py's roofline.kernels come from here. */
+ * Not hipGraph-capture safe: do not enable around a capture.  bench.py's roofline.kernels come from here.
+ * While enabled the weight gradients run in line on the caller's stream (see vbx_wgrad_overlap): the events bracket launches of
+ * that stream, and the table stays the serial per-stage account -- its "wgrad (4 GEMMs)" row is the launch on its own, and the sum
+ * of the rows exceeds the step that runs with the overlap on. */
 typedef struct {
   char label[24];
   int calls;

@@ -8,12 +8,15 @@
 #          sample_split VBX_SAMPLE_SPLIT   2 1    sampler: two concurrent half batches vs one stream
 #          gemm5       VBX_GEMM5           1 0    weight-stationary to_qkv / FeedForward-in (train step)
 #          gemm5_sample VBX_GEMM5          1 0    the same in the 64-interval sampler
+#          wgrad_overlap VBX_WGRAD_OVERLAP 1 0    weight gradients on the side stream vs in line (the stage columns are the in-line
+#                                                 launches either way: the stage table is taken with the overlap off, include/vbx.h)
 cd ${GRAFT_REPO_ROOT:-$(dirname $0)/..}
 case "$1" in
   sumsq_fold) V=VBX_SUMSQ_FOLD; S="1 0";; attn_fold) V=VBX_ATTN_BWD_FOLD; S="1 0";; factors) V=VBX_ADALN_FACTORS; S="1 0";;
   sample_split) V=VBX_SAMPLE_SPLIT; S="2 1";;
   gemm5|gemm5_sample) V=VBX_GEMM5; S="1 0";;
-  *) sed -n 2,10p $0; exit 1;;
+  wgrad_overlap) V=VBX_WGRAD_OVERLAP; S="1 0";;
+  *) sed -n 2,12p $0; exit 1;;
 esac
 ARGS="--full --steps 30 --warmup 8 --no-cpu-baseline --no-sample"
 [ "$1" = gemm5_sample ] && ARGS="--full --mode sample --steps 3 --warmup 1 --no-cpu-baseline"

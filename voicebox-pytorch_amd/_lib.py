@@ -36,6 +36,9 @@ _PROTOS = {
     "vbx_gemm_route": [C.POINTER(GemmDesc)],
     "vbx_gemm5_cu_limit": [I],
     "vbx_prof_enable": [I],
+    "vbx_wgrad_overlap": [I],
+    "vbx_wgrad_overlap_forks": [],
+    "vbx_wgrad_overlap_delay": [F, F],
     "vbx_gemm_tn_splitk_grouped": [C.POINTER(GemmDesc), I, P],
     "vbx_splitk_reduce": [P, I, I, I, P, I, I, I, I, I, I, P],
     "vbx_rmsnorm_fwd": [P, P, P, L, P, P, I, I, I, I, I, P],

@@ -12,6 +12,7 @@
 // prediction by ~5%; fp16 (2^-11) costs the same MFMA rate and brings that to ~1%.  Every BACKWARD GEMM operand
 // is bf16 (gradients need the exponent range), so in training each saved activation also has a bf16 copy.
 #include "common.hpp"
+#include "wgrad_overlap_plan.hpp"
 #include <stdlib.h>
 #include <algorithm>
 #include <string.h>
@@ -126,6 +127,11 @@ struct Acts {
   u16 *dxb, *dg, *dh1, *dhn, *dO, *dqkv, *deb, *dpb, *gl_dp, *demb;
   char* attn_scratch = nullptr;  // one-pass attention backward: chain flags + running dq sums (vbx_attn_bwd_scratch_bytes)
   u16* dxb2 = nullptr;  // bf16 dx of the attention half, so that FeedForward-out's dx operand survives to the layer's grouped wgrad launch
+  // weight gradients on the side stream (wgrad_overlap_plan.hpp): the copies of the four operands the dx chain would overwrite
+  // under them, indexed by layer (copy 0 = the buffer above; without the copies every entry is that buffer), and the side
+  // stream's own four slab regions
+  u16* copy[wgrad_overlap::BUF_N][wgrad_overlap::kMaxCopies] = {};
+  float* slabs_side = nullptr;
   float* gl_ds;
   size_t slab_floats;
   size_t np_stride = 0, cp_stride = 0, cs_stride = 0, gp_stride = 0;  // floats per layer region of npart / npart2, cpart, cs_layers, gpart
@@ -314,6 +320,17 @@ void carve_acts(const vbx_model* m, Acts& a) {
       a.dcat = c.take<float>((size_t)d.M * 2 * d.D);
       for (int p = 0; p < d.L / 2; p++) a.dskip[p] = c.take<float>((size_t)d.M * d.D);
     }
+    // The copies behind the weight-gradient overlap (dim 512 / 8 x 1024 frames: 115 MB).  As with the partial records above the
+    // layout follows the MODEL only: GateLoop and u-net models never run their weight gradients on the side stream.
+    {
+      using namespace wgrad_overlap;
+      const bool side = !m->gateloop && !m->unet;
+      u16* const first[BUF_N] = {a.dxb, a.dh1, a.dxb2, a.dqkv};
+      const size_t elems[BUF_N] = {(size_t)d.M * d.D, (size_t)d.M * 2 * d.Fp, (size_t)d.M * d.D, (size_t)d.M * 3 * d.I};
+      for (int b = 0; b < BUF_N; b++)
+        for (int k = 0; k < kMaxCopies; k++) a.copy[b][k] = (k == 0 || !side || k >= copies((Buf)b)) ? first[b] : c.take<u16>(elems[b]);
+      a.slabs_side = side ? c.take<float>(4 * sf) : a.slabs;
+    }
   }
   a.bytes = al256(c.off);
 }
@@ -354,6 +371,75 @@ struct ProfScope {
     int rc__ = (x);           \
     if (rc__ != 0) return rc__; \
   } while (0)
+
+// ---- weight gradients on a side stream (vbx_wgrad_overlap, include/vbx.h; the schedule: wgrad_overlap_plan.hpp)
+// One low-priority non-blocking stream and one set of events per device, created on first use and kept for the life of the
+// process.  The events are re-recorded by every layer: a wait takes the record that precedes it in submission order, and the side
+// stream is in order, so a later record of the same event only ever stands for more finished work.
+struct WgoSide {
+  hipStream_t st = nullptr;
+  hipEvent_t ev[wgrad_overlap::EV_N] = {};
+};
+int g_wgo_on = -1;                       // VBX_WGRAD_OVERLAP (default 1) / vbx_wgrad_overlap
+float g_wgo_delay[2] = {0.f, 0.f};       // vbx_wgrad_overlap_delay: side, main (microseconds)
+int g_wgo_forks = 0;                     // vbx_wgrad_overlap_forks
+bool wgo_enabled() {
+  if (g_wgo_on < 0) {
+    const char* e = getenv("VBX_WGRAD_OVERLAP");
+    g_wgo_on = e ? (atoi(e) != 0) : 1;
+  }
+  return g_wgo_on != 0;
+}
+// the current device's side stream; create = false: only if a backward has made one (nullptr otherwise, and on failure with create)
+WgoSide* wgo_side(bool create) {
+  static WgoSide* sides[64] = {};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
+  if (sides[dev] || !create) return sides[dev];
+  WgoSide* s = new WgoSide;
+  int least = 0, greatest = 0;  // "least" is the numerically largest value: the lowest priority
+  const char* pe = getenv("VBX_WGRAD_OVERLAP_PRIORITY");  // measurement only: "default" = same priority as the caller's stream
+  const bool low = !(pe && !strcmp(pe, "default"));
+  bool ok = hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess &&
+            hipStreamCreateWithPriority(&s->st, hipStreamNonBlocking, low ? least : 0) == hipSuccess;
+  for (int i = 0; ok && i < wgrad_overlap::EV_N; i++) ok = hipEventCreateWithFlags(&s->ev[i], hipEventDisableTiming) == hipSuccess;
+  if (!ok) {
+    for (auto e : s->ev) if (e) (void)hipEventDestroy(e);
+    if (s->st) (void)hipStreamDestroy(s->st);
+    delete s;
+    (void)hipGetLastError();
+    return nullptr;
+  }
+  return sides[dev] = s;
+}
+bool capturing(hipStream_t st) {
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  return hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone;
+}
+// executes the plan's record / wait at point p (sd == nullptr: no side stream exists, nothing to order)
+int wgo_sync(WgoSide* sd, hipStream_t main_st, wgrad_overlap::Point p, int l, int L) {
+  if (!sd) return 0;
+  const wgrad_overlap::Sync s = wgrad_overlap::sync_at(p, l, L);
+  if (s.kind == wgrad_overlap::SYNC_NONE) return 0;
+  hipStream_t st = s.stream == wgrad_overlap::MAIN ? main_st : sd->st;
+  const hipError_t e = s.kind == wgrad_overlap::SYNC_RECORD ? hipEventRecord(sd->ev[s.ev], st) : hipStreamWaitEvent(st, sd->ev[s.ev], 0);
+  VBX_REQUIRE(e == hipSuccess, "weight-gradient overlap: event %s failed (%s)", s.kind == wgrad_overlap::SYNC_RECORD ? "record" : "wait",
+              hipGetErrorString(e));
+  return 0;
+}
+// an error return after work went to the side stream must not leave it running under whatever the caller does next
+struct WgoGuard {
+  WgoSide* sd = nullptr;
+  bool forked = false, ok = false;
+  int done(int rc) { ok = rc == 0; return rc; }  // every return after the guard is armed goes through here or through CK
+  ~WgoGuard() {
+    if (forked && !ok && sd) (void)hipStreamSynchronize(sd->st);
+  }
+};
+// LayerPlan::defer (below), for the stages outside the layers: a backward that defers indexes the copies of Acts::copy by layer
+bool defers(const vbx_model* m) { return m->defer_reduce && !m->gateloop && !m->unet && (m->plain_norm || m->adaln_factors); }
+// tests / debug: which copy of dxb / dqkv the most recent backward stage of this arena wrote (vbx_model_debug_ptr)
+struct { const void* act = nullptr; int dxb = 0, dqkv = 0; } g_last_copy;
 
 int check_model(const vbx_model* m) {
   VBX_REQUIRE(m && m->params && m->off && m->wpack && m->act && m->rot_cos && m->rot_sin, "vbx_model: null field");
@@ -648,6 +734,14 @@ extern "C" int vbx_model_backward_head(const vbx_model* m, const vbx_io* io, con
   const float* P = m->params;
   float* Gd = m->grads;
   const long* G = m->off;
+  // nothing of an earlier (possibly abandoned) backward stays in flight on the side stream under this one
+  WgoGuard guard;
+  guard.sd = capturing(st) ? nullptr : wgo_side(false);
+  guard.forked = guard.sd != nullptr;
+  CK(wgo_sync(guard.sd, st, wgrad_overlap::PT_HEAD_BEGIN, -1, d.L));
+  // bf16 dx for layer L - 1: the copy that layer reads (copy 0 = a.dxb unless the layers index their buffers, vbx_model_backward_layer)
+  u16* const dxb = defers(m) ? a.copy[wgrad_overlap::BUF_DXB][wgrad_overlap::dxb_read_copy(d.L - 1)] : a.dxb;
+  g_last_copy.act = m->act; g_last_copy.dxb = (int)(dxb != a.dxb ? wgrad_overlap::dxb_read_copy(d.L - 1) : 0);
   if (m->stack_only) {
     // io->target = d(output) fp32 [B,N,D] -> bf16 operand of the final-norm backward
     CK(vbx_pack_weight(io->target, (int)d.M0, d.D, a.dhn, nullptr, (int)d.M0, d.D, 0, 0, stream));
@@ -662,15 +756,15 @@ extern "C" int vbx_model_backward_head(const vbx_model* m, const vbx_io* io, con
   }
   // gradient wrt the last residual snapshot: zero at the register rows, final-norm backward elsewhere
   if (hipMemsetAsync(a.dx, 0, (size_t)d.M * d.D * sizeof(float), st) != hipSuccess ||
-      hipMemsetAsync(a.dxb, 0, (size_t)d.M * d.D * sizeof(u16), st) != hipSuccess) {
+      hipMemsetAsync(dxb, 0, (size_t)d.M * d.D * sizeof(u16), st) != hipSuccess) {
     vbx_set_error("vbx_model_backward_head: memset failed");
     return VBX_EINVAL;
   }
-  CK(vbx_rmsnorm_bwd(a.xs[(m->gateloop ? 3 : 2) * d.L], P + G[VBX_P_FNG], 0, a.dhn, nullptr, a.dx, a.dxb, a.npart, nullptr, d.B, d.Np, d.R, d.N, d.D,
+  CK(vbx_rmsnorm_bwd(a.xs[(m->gateloop ? 3 : 2) * d.L], P + G[VBX_P_FNG], 0, a.dhn, nullptr, a.dx, dxb, a.npart, nullptr, d.B, d.Np, d.R, d.N, d.D,
                      stream));
   CK(vbx_reduce_norm_partials(a.npart, a.tmp2d, 0, d.B, vbx_rmsnorm_bwd_chunks(d.N), d.D, 1, stream));
   CK(vbx_sum_rows_f32(a.tmp2d, 1, d.D, Gd + G[VBX_P_FNG], d.D, 0, stream));
-  return 0;
+  return guard.done(0);
 }
 
 // vbx_model.sq_partials: blocks of the layer's four deferred weight-gradient reductions in the order the layer's backward issues them
@@ -705,7 +799,12 @@ extern "C" long vbx_model_sq_partials(const vbx_model* m, long* ranges) {
 // One layer's backward, as the model's configuration fixes it (the launch order is a function of vbx_model alone):
 //   FeedForward half   dgrad ff_out, [dropout], GEGLU backward + bias partials, dgrad ff_in, norm backward            4-5 launches
 //   attention half     dgrad to_out, attention backward (delta + one pass), dgrad to_qkv, norm backward               5 launches
-//   weight gradients   the four split-K GEMMs as one grouped launch + one slab reduction (between dgrad to_qkv and the norm backward)
+//   weight gradients   the four split-K GEMMs as one grouped launch + one slab reduction.  Their operands are complete after dgrad
+//                      to_qkv and nothing before the optimizer reads their results: a deferring backward (LayerPlan::defer) submits
+//                      both to the side stream there, where they run beside the norm backward and the next layer's chain
+//                      (wgrad_overlap_plan.hpp: operand copies by layer, events, waits).  In line -- between dgrad to_qkv and the
+//                      norm backward on the caller's stream -- otherwise: per-stage readers, GateLoop, u-net, separate 128-wide
+//                      GEMMs, a capturing stream, vbx_prof_enable, vbx_wgrad_overlap(0)
 //   small reductions   every partial record of the layer in one launch -- or, deferred, of all layers when layer 0 is done
 //   tails              GateLoop block, u-net skip combiner, adaLN projections
 // Which of the model-dependent forms apply:
@@ -719,7 +818,7 @@ struct LayerPlan {
 static LayerPlan layer_plan(const vbx_model* m) {
   LayerPlan p;
   p.ada_all = m->adaln_factors && !m->plain_norm;
-  p.defer = m->defer_reduce && !m->gateloop && !m->unet && (m->plain_norm || p.ada_all);
+  p.defer = defers(m);
   return p;
 }
 
@@ -842,20 +941,39 @@ extern "C" int vbx_model_backward_layer(const vbx_model* m, const vbx_io* io, in
   WgradGroup wgg;
   WgradGroup* wgp = group_wgrad() ? &wgg : nullptr;
   const int gs = wgp ? wgrad_splits3(d) : 0;
-  u16* dxb_attn = wgp ? a.dxb2 : a.dxb;  // bf16 dx entering the attention half (see Acts::dxb2)
+  // A deferring backward takes the four buffers that its weight gradients read from the copy the plan gives layer l, whether the
+  // weight gradients then run on the side stream or in line; every other backward uses copy 0, the one buffer there was.
+  namespace wgo = wgrad_overlap;
+  auto copy_of = [&](wgo::Buf b) { return pl.defer ? a.copy[b][wgo::write_copy(b, l)] : a.copy[b][0]; };
+  u16* const dxb_in = pl.defer ? a.copy[wgo::BUF_DXB][wgo::dxb_read_copy(l)] : a.dxb;  // bf16 dx from the layer above / the head
+  u16* const dxb_out = copy_of(wgo::BUF_DXB);                                          // ... for the layer below
+  u16* const dh1 = copy_of(wgo::BUF_DH1);
+  u16* const dqkv = copy_of(wgo::BUF_DQKV);
+  u16* dxb_attn = wgp ? copy_of(wgo::BUF_DXB2) : dxb_in;  // bf16 dx entering the attention half (see Acts::dxb2)
+  g_last_copy.act = m->act; g_last_copy.dxb = pl.defer ? wgo::write_copy(wgo::BUF_DXB, l) : 0; g_last_copy.dqkv = pl.defer ? wgo::write_copy(wgo::BUF_DQKV, l) : 0;
+  // Side stream: only when the plan's conditions hold (see the table above LayerPlan).  The waits of the plan run whenever a side
+  // stream exists, so in-line and overlapped layers may follow each other in any order.
+  const bool cap = capturing(st);
+  const bool fork = pl.defer && wgp && wgo_enabled() && !g_prof.on && !cap;
+  WgoGuard guard;
+  guard.sd = cap ? nullptr : wgo_side(fork);
+  VBX_REQUIRE(!fork || guard.sd, "vbx_model_backward_layer: could not create the weight-gradient side stream");
+  if (fork && g_wgo_delay[1] > 0.f) CK(vbx_stream_delay(g_wgo_delay[1], stream));
+  CK(wgo_sync(guard.sd, st, wgo::PT_LAYER_BEGIN, l, d.L));
+  float* const slabs = fork ? a.slabs_side : a.slabs;
   const size_t sfl = a.slab_floats;
   const SqLayout sql = sq_layout(d);
   float* const sqb = m->sq_partials ? m->sq_partials + (long)l * sql.per_layer : nullptr;
   auto sq_at = [&](int i) { return sqb ? sqb + sql.off[i] : nullptr; };
 
   // ---- FeedForward half
-  { ProfScope ps("dgrad ff_out", st); CK(gemm_nn_bf16(a.dxb, d.D, wl.w2, d.Fp, M, d.Fp, d.D, a.dg, d.Fp, st)); }
-  CK(wgrad(a.dxb, d.D, y.g, d.Fp, d.D, d.Fp, d.M, a.slabs, Gd + o[VBX_L_FF2W], d.D, d.F, 0, 0, st, &wj, wgp, gs, sq_at(0)));
+  { ProfScope ps("dgrad ff_out", st); CK(gemm_nn_bf16(dxb_in, d.D, wl.w2, d.Fp, M, d.Fp, d.D, a.dg, d.Fp, st)); }
+  CK(wgrad(dxb_in, d.D, y.g, d.Fp, d.D, d.Fp, d.M, slabs, Gd + o[VBX_L_FF2W], d.D, d.F, 0, 0, st, &wj, wgp, gs, sq_at(0)));
   if (drop_on && m->ff_dropout > 0.f)  // the same mask on the gradient of the GEGLU output
     CK(vbx_dropout_rows(nullptr, a.dg, d.M, d.Fp, d.Fp, io->drop_seed, 2u * l + 1u, m->ff_dropout, stream));
-  CK(vbx_geglu_bwd_colsum(y.h1, a.dg, a.dh1, M, d.Fp, csl, stream));  // gated-GELU backward + FeedForward[0].bias partials in one pass
-  { ProfScope ps("dgrad ff_in", st); CK(gemm_nn_bf16(a.dh1, 2 * d.Fp, wl.w1, d.D, M, d.D, 2 * d.Fp, a.dhn, d.D, st)); }
-  CK(wgrad(a.dh1, 2 * d.Fp, y.hn2, d.D, 2 * d.Fp, d.D, d.M, a.slabs + sfl, Gd + o[VBX_L_FF1W], 2 * d.F, d.D, 1, d.F, st, &wj, wgp, gs, sq_at(1)));
+  CK(vbx_geglu_bwd_colsum(y.h1, a.dg, dh1, M, d.Fp, csl, stream));  // gated-GELU backward + FeedForward[0].bias partials in one pass
+  { ProfScope ps("dgrad ff_in", st); CK(gemm_nn_bf16(dh1, 2 * d.Fp, wl.w1, d.D, M, d.D, 2 * d.Fp, a.dhn, d.D, st)); }
+  CK(wgrad(dh1, 2 * d.Fp, y.hn2, d.D, 2 * d.Fp, d.D, d.M, slabs + sfl, Gd + o[VBX_L_FF1W], 2 * d.F, d.D, 1, d.F, st, &wj, wgp, gs, sq_at(1)));
   // (the column sums of the incoming dx -- FeedForward[3].bias gradient -- ride along in the same pass)
   CK(vbx_rmsnorm_bwd(x_mid, g2, gstride, a.dhn, a.dx, a.dx, dxb_attn, npart, cpart, d.B, d.Np, 0, d.Np, d.D, stream));
 
@@ -863,19 +981,32 @@ extern "C" int vbx_model_backward_layer(const vbx_model* m, const vbx_io* io, in
   // (Tried: delta = rowsum(dO * O) in the epilogue of the to_out dgrad; removed, numbers in docs/history.md.  The attention entry
   // point runs its own pass over O and dO.)
   { ProfScope ps("dgrad to_out", st); CK(gemm_nn_bf16(dxb_attn, d.D, wl.out, d.I, M, d.I, d.D, a.dO, d.I, st)); }
-  CK(wgrad(dxb_attn, d.D, y.o, d.I, d.D, d.I, d.M, a.slabs + 2 * sfl, Gd + o[VBX_L_OUTW], d.D, d.I, 0, 0, st, &wj, wgp, gs, sq_at(2)));
+  CK(wgrad(dxb_attn, d.D, y.o, d.I, d.D, d.I, d.M, slabs + 2 * sfl, Gd + o[VBX_L_OUTW], d.D, d.I, 0, 0, st, &wj, wgp, gs, sq_at(2)));
   { ProfScope ps("bwd attention", st);
     CK(vbx_attn_bwd_fused_dropout(y.q16, y.k16, y.qb, y.kb, y.v, attn_mask_p, y.oh, 1, a.dO, y.lse, a.delta, y.qrn, y.krn, q_gamma, k_gamma,
-                                  m->rot_cos, m->rot_sin, m->qk_norm ? 8.0f : 0.0f, a.dqkv, 3 * d.I, gpart, d.B, d.H, d.Np, m->attn_scale,
+                                  m->rot_cos, m->rot_sin, m->qk_norm ? 8.0f : 0.0f, dqkv, 3 * d.I, gpart, d.B, d.H, d.Np, m->attn_scale,
                                   a.attn_scratch, drop_on ? y.dbr : nullptr, y.dbc, m->attn_dropout, stream)); }
-  { ProfScope ps("dgrad to_qkv", st); CK(gemm_nn_bf16(a.dqkv, 3 * d.I, wl.qkv, d.D, M, d.D, 3 * d.I, a.dhn, d.D, st)); }
-  CK(wgrad(a.dqkv, 3 * d.I, y.hn1, d.D, 3 * d.I, d.D, d.M, a.slabs + 3 * sfl, Gd + o[VBX_L_QKVW], 3 * d.I, d.D, 0, 0, st, &wj, wgp, gs, sq_at(3)));
+  { ProfScope ps("dgrad to_qkv", st); CK(gemm_nn_bf16(dqkv, 3 * d.I, wl.qkv, d.D, M, d.D, 3 * d.I, a.dhn, d.D, st)); }
+  CK(wgrad(dqkv, 3 * d.I, y.hn1, d.D, 3 * d.I, d.D, d.M, slabs + 3 * sfl, Gd + o[VBX_L_QKVW], 3 * d.I, d.D, 0, 0, st, &wj, wgp, gs, sq_at(3)));
 
-  // ---- the layer's weight gradients: every operand is still live here (a.dxb: see dxb_attn)
+  // ---- the layer's weight gradients: every operand is still live here (dxb_in: see dxb_attn)
   // (Tried: the slab reduction inside the small-reductions launch below, vbx_layer_reduce; removed, numbers in docs/history.md.)
-  if (wgg.n) { ProfScope ps("wgrad (4 GEMMs)", st); CK(vbx_gemm_tn_splitk_grouped(wgg.d, wgg.n, stream)); }
-  if (wj.n) { ProfScope ps("wgrad slab reduce", st); CK(vbx_splitk_reduce_multi(&wj, stream)); }
-  CK(vbx_rmsnorm_bwd(x_in, g1, gstride, a.dhn, a.dx, a.dx, a.dxb, npart2, nullptr, d.B, d.Np, 0, d.Np, d.D, stream));
+  if (fork) {  // on the side stream, into its own slab regions: beside the norm backward below and the next layer's chain
+    hipStream_t side = guard.sd->st;
+    CK(wgo_sync(guard.sd, st, wgo::PT_FORK, l, d.L));
+    guard.forked = true;
+    g_wgo_forks++;
+    CK(wgo_sync(guard.sd, st, wgo::PT_SIDE_BEGIN, l, d.L));
+    if (g_wgo_delay[0] > 0.f) CK(vbx_stream_delay(g_wgo_delay[0], side));
+    if (wgg.n) CK(vbx_gemm_tn_splitk_grouped(wgg.d, wgg.n, side));
+    CK(wgo_sync(guard.sd, st, wgo::PT_SIDE_GEMM_DONE, l, d.L));
+    if (wj.n) CK(vbx_splitk_reduce_multi(&wj, side));
+    CK(wgo_sync(guard.sd, st, wgo::PT_SIDE_REDUCE_DONE, l, d.L));
+  } else {
+    if (wgg.n) { ProfScope ps("wgrad (4 GEMMs)", st); CK(vbx_gemm_tn_splitk_grouped(wgg.d, wgg.n, stream)); }
+    if (wj.n) { ProfScope ps("wgrad slab reduce", st); CK(vbx_splitk_reduce_multi(&wj, stream)); }
+  }
+  CK(vbx_rmsnorm_bwd(x_in, g1, gstride, a.dhn, a.dx, a.dx, dxb_out, npart2, nullptr, d.B, d.Np, 0, d.Np, d.D, stream));
 
   // ---- every small reduction of the layer in ONE launch (they cost ~0.5 ms per step as separate launches); deferred: layer 0
   // issues the jobs of ALL layers, as many layers per launch as fit
@@ -897,7 +1028,7 @@ extern "C" int vbx_model_backward_layer(const vbx_model* m, const vbx_io* io, in
   // ---- tails
   if (m->gateloop) CK(backward_gateloop(m, d, w, a, l, stream));
   if (m->unet) CK(backward_unet(m, d, w, a, l, stream));
-  if (m->plain_norm) return 0;
+  if (m->plain_norm) return guard.done(0);
   // this layer's adaLN projections (their 4 weights / 4 biases are contiguous): dW, dbias, and d(time_emb) +=
   // (adaln_factors: the weight gradient dada_l^T . temb is not materialised -- include/vbx.h, vbx_adam_adaln_factors)
   if (pl.ada_all) {
@@ -905,11 +1036,11 @@ extern "C" int vbx_model_backward_layer(const vbx_model* m, const vbx_io* io, in
       ProfScope ps("adaLN dtemb (all)", st);
       CK(vbx_adaln_dtemb_all(w.adah, a.dada, a.dtemb, a.ada_scratch, d.L, d.B, d.Th, 4 * d.D, stream));
     }
-    return 0;
+    return guard.done(0);
   }
-  return vbx_adaln_proj_bwd(m->stack_only ? io->cond : a.temb, w.adah + (size_t)l * 4 * d.D * d.Th, dada_l,
+  return guard.done(vbx_adaln_proj_bwd(m->stack_only ? io->cond : a.temb, w.adah + (size_t)l * 4 * d.D * d.Th, dada_l,
                             m->adaln_factors ? nullptr : Gd + o[VBX_L_G1W], Gd + o[VBX_L_G1B], a.dtemb,
-                            a.ada_scratch, d.B, d.Th, 4 * d.D, l == d.L - 1 ? 0 : 1, stream);
+                            a.ada_scratch, d.B, d.Th, 4 * d.D, l == d.L - 1 ? 0 : 1, stream));
 }
 
 extern "C" int vbx_model_backward_embed(const vbx_model* m, const vbx_io* io, void* stream) {
@@ -925,6 +1056,11 @@ extern "C" int vbx_model_backward_embed(const vbx_model* m, const vbx_io* io, vo
   const float* P = m->params;
   float* Gd = m->grads;
   const long* G = m->off;
+  // The last call of a backward: it ends with the caller's stream waiting for the side stream's last slab reduce, so that every
+  // gradient and sq_partials entry is final for whatever the caller submits next.
+  WgoGuard guard;
+  guard.sd = capturing(st) ? nullptr : wgo_side(false);
+  guard.forked = guard.sd != nullptr;
   if (m->stack_only) {
     CK(vbx_stack_input_bwd(a.dx, io->dx, d.R ? Gd + G[VBX_P_REG] : nullptr, d.B, d.N, d.R, d.D, stream));
     if (!m->plain_norm && io->dcond &&
@@ -932,7 +1068,7 @@ extern "C" int vbx_model_backward_embed(const vbx_model* m, const vbx_io* io, vo
       vbx_set_error("vbx_model_backward_embed: copy of d(cond) failed");
       return VBX_EINVAL;
     }
-    return 0;
+    return guard.done(wgo_sync(guard.sd, st, wgrad_overlap::PT_EMBED_END, -1, d.L));
   }
   CK(vbx_convpos_bwd(a.e, P + G[VBX_P_CONVW], P + G[VBX_P_CONVB], io->attn_mask, a.dx, a.dpre, a.de, a.deb, a.wpart,
                      d.R ? Gd + G[VBX_P_REG] : nullptr, d.B, d.N, d.R, d.D, d.ks, stream));
@@ -965,7 +1101,7 @@ extern "C" int vbx_model_backward_embed(const vbx_model* m, const vbx_io* io, vo
   CK(vbx_colsum_f32(a.de, (int)d.M0, d.D, d.D, Gd + G[VBX_P_EMBB], a.cs_scratch, stream));
   CK(vbx_time_embed_bwd(io->times, P + G[VBX_P_SINW], P + G[VBX_P_T1W], a.four, a.pre, a.dtemb, Gd + G[VBX_P_SINW],
                         Gd + G[VBX_P_T1W], Gd + G[VBX_P_T1B], a.tscratch, d.B, d.D, d.Th, stream));
-  return 0;
+  return guard.done(wgo_sync(guard.sd, st, wgrad_overlap::PT_EMBED_END, -1, d.L));
 }
 
 // Segment table of the fused Adam + repack step (vbx_adam_step_packed): every parameter that vbx_model_pack_weights
@@ -1041,6 +1177,19 @@ extern "C" int vbx_model_adaln_factors(const vbx_model* m, const float** dada, c
   return d.L;
 }
 
+extern "C" int vbx_wgrad_overlap(int on) {
+  VBX_REQUIRE(on == 0 || on == 1, "vbx_wgrad_overlap: 0 in line, 1 on the side stream");
+  g_wgo_on = on;
+  return 0;
+}
+extern "C" int vbx_wgrad_overlap_forks(void) { return g_wgo_forks; }
+extern "C" int vbx_wgrad_overlap_delay(float side_us, float main_us) {
+  VBX_REQUIRE(side_us >= 0.f && side_us <= 2000.f && main_us >= 0.f && main_us <= 2000.f, "vbx_wgrad_overlap_delay: 0 .. 2000 us each");
+  g_wgo_delay[0] = side_us;
+  g_wgo_delay[1] = main_us;
+  return 0;
+}
+
 extern "C" int vbx_prof_enable(int on) {
   for (auto& r : g_prof.recs) { (void)hipEventDestroy(r.e0); (void)hipEventDestroy(r.e1); }
   g_prof.recs.clear();
@@ -1086,8 +1235,11 @@ extern "C" void* vbx_model_debug_ptr(const vbx_model* m, const char* name, int l
     if (n == "krn") return y.krn; if (n == "hn2") return y.hn2; if (n == "h1") return y.h1; if (n == "g") return y.g;
   }
   if (n == "xs" && layer >= 0 && layer < (int)a.xs.size()) return a.xs[layer];
-  if (n == "dx") return a.dx; if (n == "dxb") return a.dxb; if (n == "dq") return a.dq; if (n == "dk") return a.dk;
-  if (n == "dqkv") return a.dqkv; if (n == "dO") return a.dO; if (n == "delta") return a.delta; if (n == "dhn") return a.dhn;
+  const bool last = g_last_copy.act == m->act;  // the copy the most recent backward stage wrote (Acts::copy)
+  if (n == "dxb") return a.copy[wgrad_overlap::BUF_DXB][last ? g_last_copy.dxb : 0];
+  if (n == "dqkv") return a.copy[wgrad_overlap::BUF_DQKV][last ? g_last_copy.dqkv : 0];
+  if (n == "dx") return a.dx; if (n == "dq") return a.dq; if (n == "dk") return a.dk;
+  if (n == "dO") return a.dO; if (n == "delta") return a.delta; if (n == "dhn") return a.dhn;
   if (n == "e") return a.e; if (n == "temb") return a.temb; if (n == "ada") return a.ada; if (n == "pred") return a.pred;
   if (n == "dada") return a.dada; if (n == "dtemb") return a.dtemb;
   return nullptr;
