@@ -337,6 +337,36 @@ int vbx_rvq_encode(const float* x, const float* codebooks, const float* norms, l
                    int K, int Q, int codes_qn, void* stream);
 int vbx_rvq_decode(const long* codes, const float* codebooks, float* out, int B, int N, int D, int K, int Q, int codes_qn,
                    int channel_first, void* stream);
+/* SEANet encoder (voicebox_pytorch_amd.SEANetEncoder; csrc/seanet.hip): EnCodec's encoder -- reflect-padded convolutions with ELU,
+ * strided downsampling, an LSTM with a skip, a final convolution -- inference only.  PRECISION CONTRACT: activations between layers
+ * are fp16, channel-last [B, L, C], rounded ONCE and stored before the activation (the Resnet shortcut reads them un-activated);
+ * weights are fp16 (weight norm folded in fp32 first); every sum is fp32 on the matrix cores (v_mfma_f32_16x16x32_f16); ELU is
+ * x > 0 ? x : expm1f(x) in fp32, applied when an operand is staged and rounded to fp16 there; the first convolution reads the fp32
+ * wave with fp32 weights (an fmaf chain on the bias, in tap order); LSTM gates, cell state and the skip add are fp32 with libm's
+ * expf / tanhf, h is rounded to fp16 only as the next step's matrix operand; the final convolution writes fp32.  No atomics: reruns
+ * are bit-identical, and a batch row's result does not depend on its neighbours.
+ * SConv1d (non-causal): k_eff = (k - 1) dilation + 1, padding_total = k_eff - stride, extra = ceil(L / stride) stride - L,
+ * pad_right = padding_total / 2, pad_left = padding_total - pad_right; reflect padding by (pad_left, pad_right + extra) with pad1d's
+ * short-input rule (L <= max pad: append max - L + 1 zeros, reflect, cut them off again); Lout = ceil(L / stride).
+ * vbx_seanet_conv: y [B, Lout, Co] (fp16, or fp32 when out_f32) = conv(elu1 ? ELU(x1) : x1) + bias with w fp16 [Co, k * C1 + C2],
+ *   column tap * C1 + c; a second input x2 [B, L, C2] (needs k = 1, stride = 1; never activated) is K-concatenated as columns
+ *   k * C1 .. : the Resnet block's tail and its shortcut in one product.  C1, C2 multiples of 8 up to 1024, k <= 16, stride <= 8,
+ *   dilation <= 4.  A workgroup owns up to vbx_seanet_conv_tile(...) output positions of one row: the largest of 128 .. 32 whose
+ *   span fits 80 KiB of LDS, else 16 within 160 KiB (negative: not even that fits); fewer on a row shorter than the tile.
+ * vbx_seanet_conv0: wave fp32 [B, T] -> y fp16 [B, T, nf], w fp32 [nf, k], k odd, nf a multiple of 8 up to 64.
+ * vbx_lstm_step: step s of T + layers - 1: layer 0 at time s and layer 1 at time s - 1 in ONE plain launch (each reads only what
+ *   earlier launches wrote).  xproj fp32 [B * T, 4H] = x W_ih0^T + b_ih0 + b_hh0 (a vbx_gemm); w_hh0 fp16 [4H, H]; w_cat1 fp16
+ *   [4H, 2H] = [W_ih1 | W_hh1]; bias1 = b_ih1 + b_hh1; gate order i, f, g, o; h0 / h1 fp16 [B, T, H] and c fp32 [layers, B, H] are
+ *   work buffers (zero initial state, nothing to clear); y16 (and y32 unless NULL) [B, T, H] = h_last + x.  H a multiple of 32 up to
+ *   1024.  vbx_lstm: all the steps in order. */
+int vbx_seanet_conv_tile(int C1, int C2, int k, int stride, int dilation);
+int vbx_seanet_conv(const void* x1_f16, const void* x2_f16, const void* w_f16, const float* bias, void* y, int B, int L, int C1, int C2,
+                    int Co, int k, int stride, int dilation, int elu1, int out_f32, void* stream);
+int vbx_seanet_conv0(const float* wave, const float* w, const float* bias, void* y_f16, int B, int T, int nf, int k, void* stream);
+int vbx_lstm_step(const float* xproj, const void* w_hh0, const void* w_cat1, const float* bias1, void* h0, void* h1, float* c,
+                  const void* x, void* y16, float* y32, int B, int T, int H, int layers, int s, void* stream);
+int vbx_lstm(const float* xproj, const void* w_hh0, const void* w_cat1, const float* bias1, void* h0, void* h1, float* c, const void* x,
+             void* y16, float* y32, int B, int T, int H, int layers, void* stream);
 /* Sample-rate conversion (voicebox_pytorch_amd.resample; csrc/resample.hip): the polyphase windowed-sinc FIR of
  * torchaudio.functional.resample for the REDUCED rate pair orig : nw,
  *   y[r][q * nw + p] = sum_k h[p][k] * x[r][q * orig + k - width],  x = 0 outside [0, L),  p < nw, k < K = 2 * width + orig,

@@ -80,6 +80,11 @@ _PROTOS = {
     "vbx_rvq_norms": [P, P, I, I, I, P],
     "vbx_rvq_encode": [P, P, P, P, P, I, I, I, I, I, I, P],
     "vbx_rvq_decode": [P, P, P, I, I, I, I, I, I, I, P],
+    "vbx_seanet_conv_tile": [I, I, I, I, I],
+    "vbx_seanet_conv": [P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, P],
+    "vbx_seanet_conv0": [P, P, P, P, I, I, I, I, P],
+    "vbx_lstm_step": [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, P],
+    "vbx_lstm": [P, P, P, P, P, P, P, P, P, P, I, I, I, I, P],
     "vbx_resample_max_taps": [],
     "vbx_resample": [P, P, P, P, P, I, L, L, I, I, I, I, I, P],
     "vbx_pack_phoneme_input": [P, P, I, P, I, P, P, P, P, I, I, I, P],

@@ -14,8 +14,8 @@ torchaudio's InverseMelScale.  resample / Resample (csrc/resample.hip), the samp
 too: the published arithmetic of torchaudio.functional.resample, restated in fp64 in tests/resample_ref.py.
 
 ResidualVQ / EncodecVocoCodec (csrc/rvq.hip) are the reference's EncodecVoco (:551-592) around a residual vector quantizer on the device:
-codes in and out, latents from codes, features for a VocosDecoder.  EnCodec's SEANet encoder is not built (encoder= is the user's module)
-and parity with encodec / vocos / vector_quantize_pytorch is UNPINNED likewise (tests/rvq_ref.py restates the arithmetic).
+codes in and out, latents from codes, features for a VocosDecoder.  EnCodec's SEANet encoder is seanet.py's SEANetEncoder, passed as
+encoder= (from_encodec_checkpoint builds both from one local file); parity with encodec / vocos / vector_quantize_pytorch is UNPINNED likewise (tests/rvq_ref.py restates the arithmetic).
 """
 import functools
 import math
@@ -516,8 +516,9 @@ class EncodecVocoCodec(AudioEncoderDecoder):
       decode(latents)          -> wave = vocoder(codes_to_features(decode_to_codes(latents))), batched
       encode(audio)            -> codes_to_latents(decode_to_codes(encoder(audio)))
 
-    EnCodec's SEANet encoder (strided convolutions and an LSTM) is NOT built: `encoder` is the user's module, audio [B, T] ->
-    unquantized latents [B, frames, dim]; without one, encode raises.  Neither weights nor the `encodec` / `vocos` libraries are
+    `encoder` is a module audio [B, T] -> unquantized latents [B, frames, dim]: SEANetEncoder (seanet.py), EnCodec's encoder on the
+    device, or the user's own; without one, encode raises.  from_encodec_checkpoint builds encoder and quantizer from a local
+    EnCodec state dict.  Neither weights nor the `encodec` / `vocos` libraries are
     part of this package; PARITY with them is UNPINNED (tests/rvq_ref.py restates the arithmetic)."""
 
     def __init__(self, *, rvq, vocoder, encoder=None, feature_rvq=None, sampling_rate=24000, downsample_factor=320):
@@ -564,6 +565,31 @@ class EncodecVocoCodec(AudioEncoderDecoder):
         rvq.load_state_dict({"codebook_weights": flat})
         vocoder = VocosDecoder.from_state_dict(sd, hop_length=hop_length, bandwidth_id=bandwidth_id)
         return cls(rvq=rvq, vocoder=vocoder, encoder=encoder, sampling_rate=sampling_rate, downsample_factor=vocoder.hop_length).eval()
+
+    @classmethod
+    def from_encodec_checkpoint(cls, path, *, vocoder, bandwidth_id=2, feature_rvq=None, sampling_rate=24000):
+        """A LOCAL EnCodec state dict (torch.save of the dict, or {'state_dict': ...}): `encoder.*` becomes a SEANetEncoder (its
+        limits apply), `quantizer.vq.layers.{q}._codebook.embed` [codebook_size, dim] the codebooks, of which bandwidth ids 0 .. 3
+        use the first 2, 4, 8, 16 (capped by what the file holds); downsample_factor is the product of the encoder's ratios.  The
+        decoder half of the file is not read: `vocoder` is the caller's (a VocosDecoder)."""
+        from .seanet import SEANetEncoder
+        from .vocos import read_checkpoint
+
+        sd = read_checkpoint(path)
+        if not 0 <= bandwidth_id < len(RVQ_BANDWIDTH_QUANTIZERS):
+            raise ValueError(f"bandwidth_id must be in 0 .. {len(RVQ_BANDWIDTH_QUANTIZERS) - 1} (got {bandwidth_id})")
+        books, q = [], 0
+        while f"quantizer.vq.layers.{q}._codebook.embed" in sd:
+            books.append(sd[f"quantizer.vq.layers.{q}._codebook.embed"])
+            q += 1
+        if not books:
+            raise KeyError("from_encodec_checkpoint: the state dict has no quantizer.vq.layers.0._codebook.embed (not an EnCodec model)")
+        books = books[:RVQ_BANDWIDTH_QUANTIZERS[bandwidth_id]]
+        encoder = SEANetEncoder.from_state_dict({k: v for k, v in sd.items() if k.startswith("encoder.")})
+        rvq = ResidualVQ(dim=books[0].shape[1], codebook_size=books[0].shape[0], num_quantizers=len(books))
+        rvq.load_state_dict({"codebook_weights": torch.cat([b.float() for b in books], dim=0)})
+        return cls(rvq=rvq, vocoder=vocoder, encoder=encoder, feature_rvq=feature_rvq, sampling_rate=sampling_rate,
+                   downsample_factor=encoder.hop_length).eval()
 
     def decode_to_codes(self, latents):
         return self.rvq._search(latents, codes_qn=True, quantized=False, who="EncodecVocoCodec.decode_to_codes")[1]

@@ -1,0 +1,351 @@
+"""SEANetEncoder: the encoder half of EnCodec (Defossez et al. 2022, "High fidelity neural audio compression") on the device -- the
+network behind `EncodecVoco.encode` of the reference (voicebox_pytorch.py:574-576): a 7-tap convolution, four stages of
+(Resnet block, ELU, strided convolution), a 2-layer LSTM with a skip, ELU, a final 7-tap convolution.  Every convolution is
+EnCodec's non-causal SConv1d: reflect padding by (pad_left, pad_right + extra) with pad1d's short-input rule, weight norm.  The
+parameters carry the names and shapes of the published model (`model.{i}.conv.conv.weight_g` ...), so the `encoder.*` part of an
+EnCodec state dict loads as is; neither the `encodec` library nor any weights are part of this package, and nothing here reaches a
+hub: from_checkpoint reads a local file.
+
+PARITY UNPINNED: the `encodec` library is not a dependency and no fixture of it exists.  This follows its published arithmetic
+(encodec/modules/seanet.py, conv.py, lstm.py at the 24 kHz model's settings), restated in fp64 with F.pad / F.conv1d / F.elu and an
+explicit LSTM loop in tests/seanet_ref.py; the kernels are tested against that restatement (tests/test_seanet_gpu.py,
+profiles/seanet_parity.txt).
+
+Device path (csrc/seanet.hip, csrc/gemm.hip): a fixed launch sequence without host synchronisation.  Activations between layers
+are fp16, channel-last, rounded once; weights are fp16 (weight norm folded in fp32 before the rounding); sums, ELU, the LSTM's
+gates and cell state are fp32 (the precision contract in include/vbx.h).  Inference only.
+"""
+import math
+import os
+
+import torch
+from torch import nn
+
+from . import _lib
+
+_PARAM = "parametrizations.weight.original"
+
+
+class _Conv(nn.Module):
+    """the innermost `conv` of SConv1d -> NormConv1d -> nn.Conv1d: weight_g / weight_v / bias under weight norm, weight / bias
+    without; initialised as nn.Conv1d initialises itself"""
+
+    def __init__(self, cin, cout, k, norm):
+        super().__init__()
+        ref = nn.Conv1d(cin, cout, k)
+        if norm == "weight_norm":
+            self.weight_g = nn.Parameter(ref.weight.detach().flatten(1).norm(dim=1).reshape(cout, 1, 1))
+            self.weight_v = nn.Parameter(ref.weight.detach().clone())
+        else:
+            self.weight = nn.Parameter(ref.weight.detach().clone())
+        self.bias = nn.Parameter(ref.bias.detach().clone())
+
+    def folded(self):
+        """fp32 [Co, Ci, k]: w = g * v / |v|, the norm over (Ci, k) per output channel"""
+        if hasattr(self, "weight"):
+            return self.weight.detach().float()
+        v = self.weight_v.detach().float()
+        return self.weight_g.detach().float() * v / v.flatten(1).norm(dim=1).reshape(-1, 1, 1)
+
+
+class _NormConv(nn.Module):
+    def __init__(self, *a):
+        super().__init__()
+        self.conv = _Conv(*a)
+
+
+class _SConv(nn.Module):
+    def __init__(self, cin, cout, k, norm, stride=1, dilation=1):
+        super().__init__()
+        self.conv = _NormConv(cin, cout, k, norm)
+        self.cin, self.cout, self.k, self.stride, self.dilation = cin, cout, k, stride, dilation
+
+    @property
+    def inner(self):
+        return self.conv.conv
+
+
+class _Resnet(nn.Module):
+    def __init__(self, dim, compress, k, dilation, norm):
+        super().__init__()
+        hidden = dim // compress
+        self.block = nn.ModuleList([nn.ELU(), _SConv(dim, hidden, k, norm, dilation=dilation), nn.ELU(), _SConv(hidden, dim, 1, norm)])
+        self.shortcut = _SConv(dim, dim, 1, norm)
+
+
+class _LSTMParams(nn.Module):
+    """the parameters of nn.LSTM(dim, dim, layers) under its names (weight_ih_l{n} ..., gate order i, f, g, o), initialised as
+    nn.LSTM initialises itself; a plain container, so moving it to the device touches no RNN library"""
+
+    def __init__(self, dim, layers):
+        super().__init__()
+        for name, p in nn.LSTM(dim, dim, layers).named_parameters():
+            self.register_parameter(name, nn.Parameter(p.detach().clone()))
+
+
+class _SLSTM(nn.Module):
+    def __init__(self, dim, layers):
+        super().__init__()
+        self.lstm = _LSTMParams(dim, layers)
+
+
+class SEANetEncoder(nn.Module):
+    """audio [B, T] or [B, 1, T] (any float dtype, on the GPU) -> unquantized latents fp32 [B, frames, dimension], frames =
+    ceil(... ceil(T / r_last) ... / r_first) over reversed(ratios).  FRAMES-MAJOR, what EncodecVocoCodec.encode expects of
+    `encoder=`; EnCodec's own SEANetEncoder returns channel-first [B, dimension, frames] -- transpose when comparing.
+
+    Runs without gradients, in eval semantics.  The folded fp16 weights are packed once and re-packed when a parameter's version
+    counter or storage changes; after a write through `p.data` call mark_weights_dirty().
+
+    Raises NotImplementedError for what is not built: causal=True, pad_mode other than "reflect", norm other than "weight_norm" /
+    "none", an activation other than ELU(alpha=1), channels != 1, true_skip=True, compress != 2, n_filters not a multiple of 16 or
+    above 64, other than 1 .. 4 ratios or a ratio outside 2 .. 8, n_residual_layers outside 1 .. 3, dilation_base != 2, lstm
+    outside 0 .. 2, dimension not a multiple of 8 or above 512, kernel_size / last_kernel_size even or above 7,
+    residual_kernel_size != 3, and any convolution of which 16 output positions do not fit the LDS (none inside these ranges: the
+    widest, 512 -> 1024 with kernel 16 and stride 8, takes 138 of 160 KiB).  GPU tensors only; like its siblings, a forward on a
+    device other than the parameters' MOVES THE MODULE there (`self.to(device)`) -- keep one instance per device."""
+
+    def __init__(self, channels=1, dimension=128, n_filters=32, n_residual_layers=1, ratios=(8, 5, 4, 2), activation="ELU",
+                 activation_params=None, norm="weight_norm", kernel_size=7, last_kernel_size=7, residual_kernel_size=3,
+                 dilation_base=2, causal=False, pad_mode="reflect", true_skip=False, compress=2, lstm=2):
+        super().__init__()
+        no = lambda what: NotImplementedError(f"SEANetEncoder: {what} is not built")
+        ratios = tuple(int(r) for r in ratios)
+        if causal:
+            raise no("causal=True")
+        if pad_mode != "reflect":
+            raise no(f'pad_mode="{pad_mode}" (only "reflect")')
+        if norm not in ("weight_norm", "none"):
+            raise no(f'norm="{norm}" (only "weight_norm" and "none")')
+        if activation != "ELU" or float((activation_params or {"alpha": 1.0}).get("alpha", 1.0)) != 1.0:
+            raise no("an activation other than ELU(alpha=1)")
+        if channels != 1:
+            raise no(f"channels={channels} (only 1)")
+        if true_skip:
+            raise no("true_skip=True")
+        if compress != 2:
+            raise no(f"compress={compress} (only 2)")
+        if n_filters <= 0 or n_filters % 16 or n_filters > 64:
+            raise no(f"n_filters={n_filters} (a multiple of 16, at most 64)")
+        if not 1 <= len(ratios) <= 4 or any(not 2 <= r <= 8 for r in ratios):
+            raise no(f"ratios={ratios} (1 to 4 ratios, each in 2 .. 8)")
+        if not 1 <= n_residual_layers <= 3:
+            raise no(f"n_residual_layers={n_residual_layers} (1 .. 3)")
+        if dilation_base != 2:
+            raise no(f"dilation_base={dilation_base} (only 2)")
+        if not 0 <= lstm <= 2:
+            raise no(f"lstm={lstm} (0 .. 2)")
+        if dimension <= 0 or dimension % 8 or dimension > 512:
+            raise no(f"dimension={dimension} (a multiple of 8, at most 512)")
+        for name, k in (("kernel_size", kernel_size), ("last_kernel_size", last_kernel_size)):
+            if k < 1 or k % 2 == 0 or k > 7:
+                raise no(f"{name}={k} (odd, at most 7)")
+        if residual_kernel_size != 3:
+            raise no(f"residual_kernel_size={residual_kernel_size} (only 3)")
+        self.channels, self.dimension, self.n_filters, self.n_residual_layers, self.ratios = channels, dimension, n_filters, n_residual_layers, ratios
+        self.norm, self.kernel_size, self.last_kernel_size, self.residual_kernel_size = norm, kernel_size, last_kernel_size, residual_kernel_size
+        self.dilation_base, self.compress, self.lstm = dilation_base, compress, lstm
+        self.hop_length = math.prod(ratios)
+        model, d = [_SConv(channels, n_filters, kernel_size, norm)], n_filters
+        for r in reversed(ratios):
+            for j in range(n_residual_layers):
+                model.append(_Resnet(d, compress, residual_kernel_size, dilation_base ** j, norm))
+            model += [nn.ELU(), _SConv(d, 2 * d, 2 * r, norm, stride=r)]
+            d *= 2
+        if lstm:
+            model.append(_SLSTM(d, lstm))
+        model += [nn.ELU(), _SConv(d, dimension, last_kernel_size, norm)]
+        self.model = nn.ModuleList(model)
+        self.hidden = d
+        # whatever the convolution kernel cannot tile is refused here, not at the first forward; a Resnet block's 1 x 1 tail is
+        # launched with the shortcut's input K-concatenated, and is asked about as launched
+        tails = {id(m.block[3]): m.shortcut.cin for m in self.modules() if isinstance(m, _Resnet)}
+        shortcuts = {id(m.shortcut) for m in self.modules() if isinstance(m, _Resnet)}
+        for m in self.modules():
+            if isinstance(m, _SConv) and m.cin > 1 and id(m) not in shortcuts:
+                try:
+                    _lib.call_value("vbx_seanet_conv_tile", m.cin, tails.get(id(m), 0), m.k, m.stride, m.dilation)
+                except _lib.VbxError as e:
+                    if not os.path.exists(_lib.LIB_PATH):
+                        raise
+                    raise no(f"a convolution {m.cin} -> {m.cout}, kernel {m.k}, stride {m.stride} ({e})") from None
+        self._packed, self._packed_key = None, None
+
+    def frames(self, T):
+        for r in reversed(self.ratios):
+            T = -(-T // r)
+        return T
+
+    # -- state
+    @staticmethod
+    def _canonical(state_dict):
+        """the two other layouts this accepts: a whole EnCodec dict (`encoder.` stripped, `decoder.*` / `quantizer.*` skipped) and
+        newer torch's parametrizations.weight.original0 / original1 (= weight_g / weight_v)"""
+        if any(k.startswith("encoder.") for k in state_dict):
+            state_dict = {k[len("encoder."):]: v for k, v in state_dict.items() if k.startswith("encoder.")}
+        out = {}
+        for k, v in state_dict.items():
+            if k.startswith(("decoder.", "quantizer.")):
+                continue
+            if k.endswith(_PARAM + "0"):
+                k = k[:-len(_PARAM) - 1] + "weight_g"
+            elif k.endswith(_PARAM + "1"):
+                k = k[:-len(_PARAM) - 1] + "weight_v"
+            out[k] = v
+        return out
+
+    def load_state_dict(self, state_dict, strict=True, **kw):
+        return super().load_state_dict(self._canonical(state_dict), strict=strict, **kw)
+
+    @classmethod
+    def from_checkpoint(cls, path):
+        """A LOCAL file written by torch.save: an EnCodec (or encoder-only) state dict or {'state_dict': ...}; see from_state_dict."""
+        from .vocos import read_checkpoint
+
+        return cls.from_state_dict(read_checkpoint(path))
+
+    @classmethod
+    def from_state_dict(cls, sd):
+        """A state dict already in memory, in any of the three layouts.  The widths are read off the shapes; the ratios off the
+        strided kernels (k = 2 r); what the shapes do not tell (non-causal, reflect padding, ELU) is taken as the 24 kHz model's."""
+        sd = cls._canonical(sd)
+        idx = sorted({int(k.split(".")[1]) for k in sd if k.startswith("model.")})
+        norm = "weight_norm" if "model.0.conv.conv.weight_g" in sd else "none"
+        wkey = "weight_v" if norm == "weight_norm" else "weight"
+        shape = lambda name: tuple(sd[f"{name}.conv.conv.{wkey}"].shape)
+        n_filters, channels, kernel_size = shape("model.0")
+        res = [i for i in idx if f"model.{i}.shortcut.conv.conv.bias" in sd]
+        lstm_i = [i for i in idx if f"model.{i}.lstm.weight_ih_l0" in sd]
+        convs = [i for i in idx if f"model.{i}.conv.conv.bias" in sd]
+        strided = convs[1:-1]
+        if not strided or not res or len(res) % len(strided):
+            raise RuntimeError("SEANetEncoder.from_state_dict: not a SEANet encoder layout (Resnet blocks and strided convolutions)")
+        ratios = tuple(reversed([shape(f"model.{i}")[2] // 2 for i in strided]))
+        lstm = 0 if not lstm_i else 1 + max(int(k[-1]) for k in sd if k.startswith(f"model.{lstm_i[0]}.lstm.weight_ih_l"))
+        first = res[0]
+        hidden = shape(f"model.{first}.block.1")[0]
+        dimension, _, last_k = shape(f"model.{convs[-1]}")
+        self = cls(channels=channels, dimension=dimension, n_filters=n_filters, n_residual_layers=len(res) // len(strided), ratios=ratios,
+                   norm=norm, kernel_size=kernel_size, last_kernel_size=last_k, residual_kernel_size=shape(f"model.{first}.block.1")[2],
+                   compress=n_filters // hidden, lstm=lstm)
+        self.load_state_dict(sd)
+        return self.eval()
+
+    # -- operand copies
+    def _weights_key(self):
+        ver = lambda t: 0 if t.is_inference() else t._version  # an inference tensor has no counter and cannot be written in place
+        return tuple((t.data_ptr(), ver(t)) for t in self.parameters())
+
+    def mark_weights_dirty(self):
+        self._packed_key = None
+
+    @staticmethod
+    def _gemm_weight(w):
+        """folded fp32 [Co, Ci, k] -> fp32 [Co, k * Ci], column tap * Ci + c (the channel-last operand order)"""
+        return w.permute(0, 2, 1).reshape(w.shape[0], -1)
+
+    def folded_weights(self):
+        """the folded fp32 weights by module path, e.g. 'model.3.conv' -> [Co, Ci, k]: what the three state-dict layouts agree on"""
+        return {name: m.inner.folded() for name, m in self.named_modules() if isinstance(m, _SConv)}
+
+    def packed_ops(self):
+        """the launch list: fp16 GEMM operands and fp32 biases as the kernels read them; rebuilt when a parameter's storage or
+        version counter changed (in-place updates, load_state_dict, .to()).  A write through `p.data` changes neither: call
+        mark_weights_dirty() after one."""
+        key = self._weights_key()
+        if key == self._packed_key:
+            return self._packed
+        f = lambda t: t.detach().float().contiguous()
+        h = lambda t: t.half().contiguous()
+        conv = lambda m, elu, out_f32=False: dict(op="conv", w=h(self._gemm_weight(m.inner.folded())), b=f(m.inner.bias), C1=m.cin, C2=0, Co=m.cout,
+                                                   k=m.k, stride=m.stride, dil=m.dilation, elu=elu, out_f32=out_f32)
+        first = self.model[0]
+        ops = [dict(op="conv0", w=f(first.inner.folded()[:, 0, :]), b=f(first.inner.bias), nf=first.cout, k=first.k)]
+        elu = False  # an nn.ELU in the list activates the input of the convolution behind it
+        for m in list(self.model)[1:]:
+            if isinstance(m, nn.ELU):
+                elu = True
+            elif isinstance(m, _Resnet):
+                c3, c1, sc = m.block[1], m.block[3], m.shortcut
+                ops.append(dict(conv(c3, True), keep=True))  # reads x, which the tail reads again
+                tail = torch.cat([self._gemm_weight(c1.inner.folded()), self._gemm_weight(sc.inner.folded())], dim=1)
+                ops.append(dict(op="tail", w=h(tail), b=(f(c1.inner.bias) + f(sc.inner.bias)).contiguous(), C1=c1.cin, C2=sc.cin, Co=c1.cout, k=1,
+                                stride=1, dil=1, elu=True, out_f32=False))
+                elu = False
+            elif isinstance(m, _SLSTM):
+                l, H = m.lstm, self.hidden
+                op = dict(op="lstm", H=H, layers=self.lstm, wih0=h(l.weight_ih_l0.detach().float()), whh0=h(l.weight_hh_l0.detach().float()),
+                          b0=(f(l.bias_ih_l0) + f(l.bias_hh_l0)).contiguous(), wcat1=None, b1=None)
+                if self.lstm == 2:
+                    op["wcat1"] = h(torch.cat([l.weight_ih_l1.detach().float(), l.weight_hh_l1.detach().float()], dim=1))
+                    op["b1"] = (f(l.bias_ih_l1) + f(l.bias_hh_l1)).contiguous()
+                ops.append(op)
+                elu = False
+            else:
+                ops.append(conv(m, elu, out_f32=m is self.model[-1]))
+                elu = False
+        self._packed, self._packed_key = ops, key
+        return ops
+
+    @staticmethod
+    def _conv(op, x1, x2, y, B, L, st):
+        _lib.call("vbx_seanet_conv", x1, x2, op["w"], op["b"], y, B, L, op["C1"], op["C2"], op["Co"], op["k"], op["stride"], op["dil"],
+                  int(op["elu"]), int(op["out_f32"]), st)
+
+    @staticmethod
+    def lstm_forward(op, x, B, T, st, y32=None):
+        """The SLSTM alone: x fp16 [B, T, H] on the device -> y fp16 [B, T, H] = LSTM(x) + x; one GEMM for layer 0's input projection,
+        then T + layers - 1 steps.  op: dict(H, layers, wih0 / whh0 fp16 [4H, H], b0 fp32 [4H] = b_ih0 + b_hh0, and for two layers
+        wcat1 fp16 [4H, 2H] = [W_ih1 | W_hh1], b1 fp32 [4H]; else None).  y32, when given, receives the sum before its rounding."""
+        H, dev = op["H"], x.device
+        xproj = torch.empty(B * T, 4 * H, dtype=torch.float32, device=dev)
+        d = _lib.GemmDesc()
+        d.mode, d.epilogue, d.M, d.N, d.K, d.lda, d.ldb, d.ldc, d.f16 = _lib.VBX_GEMM_NT, _lib.VBX_EPI_F32, B * T, 4 * H, H, H, H, 4 * H, 1
+        d.A, d.B, d.C, d.bias, d.resid = x.data_ptr(), op["wih0"].data_ptr(), xproj.data_ptr(), op["b0"].data_ptr(), None
+        rc = _lib.lib().vbx_gemm(d, st)
+        if rc != 0:
+            raise _lib.VbxError(f"vbx_gemm failed (rc={rc}): {_lib.lib().vbx_last_error().decode()}")
+        h0 = torch.empty(B, T, H, dtype=torch.float16, device=dev)
+        h1 = torch.empty(B, T, H, dtype=torch.float16, device=dev) if op["layers"] == 2 else None
+        c = torch.empty(op["layers"], B, H, dtype=torch.float32, device=dev)
+        y = torch.empty(B, T, H, dtype=torch.float16, device=dev)
+        _lib.call("vbx_lstm", xproj, op["whh0"], op["wcat1"], op["b1"], h0, h1, c, x, y, y32, B, T, H, op["layers"], st)
+        return y
+
+    def forward(self, audio):
+        if audio.ndim == 3 and audio.shape[1] == 1:
+            audio = audio[:, 0]
+        if audio.ndim != 2 or not audio.is_floating_point():
+            raise ValueError(f"SEANetEncoder takes float audio (batch, samples) or (batch, 1, samples), got {tuple(audio.shape)} {audio.dtype}")
+        if audio.shape[0] < 1 or audio.shape[1] < 1:
+            raise ValueError("SEANetEncoder: empty audio")
+        dev = audio.device
+        if dev.type != "cuda":
+            raise _lib.VbxError(f"SEANetEncoder runs only on an MI355X (gfx950) through libvbx_hip.so; the audio is on '{dev}'")
+        if self.model[0].inner.bias.device != dev:
+            self.to(dev)
+        with torch.inference_mode():
+            return self._encode(audio)
+
+    def _encode(self, audio):
+        B, L = audio.shape
+        dev, st = audio.device, _lib.current_stream()
+        ops = self.packed_ops()
+        wave = audio.detach().to(torch.float32).contiguous()
+        x = torch.empty(B, L, ops[0]["nf"], dtype=torch.float16, device=dev)
+        _lib.call("vbx_seanet_conv0", wave, ops[0]["w"], ops[0]["b"], x, B, L, ops[0]["nf"], ops[0]["k"], st)
+        kept = None
+        for op in ops[1:]:
+            if op["op"] == "lstm":
+                x = self.lstm_forward(op, x, B, L, st)
+                continue
+            Lout = -(-L // op["stride"])
+            y = torch.empty(B, Lout, op["Co"], dtype=torch.float32 if op["out_f32"] else torch.float16, device=dev)
+            if op["op"] == "tail":
+                self._conv(op, x, kept, y, B, L, st)
+            else:
+                self._conv(op, x, None, y, B, L, st)
+                if op.get("keep"):
+                    kept = x
+            x, L = y, Lout
+        return x
