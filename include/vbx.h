@@ -367,6 +367,30 @@ int vbx_lstm_step(const float* xproj, const void* w_hh0, const void* w_cat1, con
                   const void* x, void* y16, float* y32, int B, int T, int H, int layers, int s, void* stream);
 int vbx_lstm(const float* xproj, const void* w_hh0, const void* w_cat1, const float* bias1, void* h0, void* h1, float* c, const void* x,
              void* y16, float* y32, int B, int T, int H, int layers, void* stream);
+/* SEANet decoder (voicebox_pytorch_amd.SEANetDecoder; csrc/seanet.hip): EnCodec's decoder -- a first convolution, an LSTM with a
+ * skip, per ratio (ELU, strided transposed convolution, Resnet blocks), ELU, a last convolution to one channel -- inference only, under
+ * the encoder's PRECISION CONTRACT above: fp16 channel-last activations rounded once and stored before the ELU, fp16 weights folded
+ * in fp32, fp32 sums on v_mfma_f32_16x16x32_f16, no atomics, reruns bit-identical, a batch row independent of its neighbours.  The
+ * first convolution, the Resnet blocks and the LSTM are vbx_seanet_conv / vbx_gemm / vbx_lstm unchanged.
+ * vbx_seanet_pack_latents: z fp32 [B, D, T] channel-first -> y fp16 [B, T, D], rounded once.
+ * vbx_seanet_convtr: the non-causal SConvTranspose1d with k = 2 stride, and only that form.  x fp16 [B, L, C] (ELU applied in fp32 as it
+ *   is staged, rounded to fp16 as the operand) -> y fp16 [B, L stride, Co], Co = C / 2.  padding_total = k - stride = r is trimmed:
+ *   right = r / 2, left = r - right.  Untrimmed position j r + p (0 <= p < r) = b[o] + sum_c a[j, c] W[c, o, p] + a[j - 1, c] W[c, o, p + r]
+ *   with a[-1] = a[L] = 0: one product over rows j = 0 .. L with the operand row [a_j | a_{j-1}] (K = 2C) and the packed weight
+ *   w fp16 [r Co, 2C], row p Co + o = [W[:, o, p] | W[:, o, p + r]]; the r Co results of row j are the contiguous run from trimmed
+ *   position j r - left on (row 0 drops its phases p < left, row L keeps only those).  bias fp32 [Co] is added in the epilogue.  C a
+ *   multiple of 16 up to 1024, stride in 2 .. 8.  vbx_seanet_convtr_tile(C, stride) is an UPPER bound on the rows j of one batch row
+ *   that a workgroup owns: the largest of 128 .. 32 whose tile + 1 staged positions fit 80 KiB of LDS, else 16 within 160 KiB
+ *   (negative: not served); it depends on C alone (stride is only range-checked), and a launch with fewer than tile / 2 + 1 product
+ *   rows (L + 1) halves it, down to 16.
+ * vbx_seanet_conv_out: the last convolution, the mirror of vbx_seanet_conv0: x fp16 [B, T, nf] -> y fp32 [B, T] = bias[0] +
+ *   sum_tap sum_c w[tap, c] ELU(x[pad(t + tap), c]); w fp32 [k, nf], k odd and at most 7, nf a multiple of 8 up to 64; SConv1d's reflect
+ *   padding with pad1d's short-input rule; ELU in fp32 on the stored fp16 value, NOT rounded again; one fp32 fmaf chain on the bias,
+ *   tap-major then channel. */
+int vbx_seanet_pack_latents(const float* z, void* y_f16, int B, int D, int T, void* stream);
+int vbx_seanet_convtr_tile(int C, int stride);
+int vbx_seanet_convtr(const void* x_f16, const void* w_f16, const float* bias, void* y_f16, int B, int L, int C, int stride, void* stream);
+int vbx_seanet_conv_out(const void* x_f16, const float* w, const float* bias, float* y, int B, int T, int nf, int k, void* stream);
 /* Sample-rate conversion (voicebox_pytorch_amd.resample; csrc/resample.hip): the polyphase windowed-sinc FIR of
  * torchaudio.functional.resample for the REDUCED rate pair orig : nw,
  *   y[r][q * nw + p] = sum_k h[p][k] * x[r][q * orig + k - width],  x = 0 outside [0, L),  p < nw, k < K = 2 * width + orig,

@@ -85,6 +85,10 @@ _PROTOS = {
     "vbx_seanet_conv0": [P, P, P, P, I, I, I, I, P],
     "vbx_lstm_step": [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, P],
     "vbx_lstm": [P, P, P, P, P, P, P, P, P, P, I, I, I, I, P],
+    "vbx_seanet_pack_latents": [P, P, I, I, I, P],
+    "vbx_seanet_convtr_tile": [I, I],
+    "vbx_seanet_convtr": [P, P, P, P, I, I, I, I, P],
+    "vbx_seanet_conv_out": [P, P, P, P, I, I, I, I, P],
     "vbx_resample_max_taps": [],
     "vbx_resample": [P, P, P, P, P, I, L, L, I, I, I, I, I, P],
     "vbx_pack_phoneme_input": [P, P, I, P, I, P, P, P, P, I, I, I, P],

@@ -17,6 +17,15 @@
 // rule (append zeros, reflect, cut) are resolved when a workgroup stages its input span: it reads its own batch row only, inside
 // [0, L).  Plain launches, no atomics, no workgroup waits for another: the same bits on every run, and a batch row's result does
 // not depend on its neighbours.
+//
+// SEANetDecoder (the same file's `decoder.*`), under the same contract; the launch sequence of one decode:
+//
+//   vbx_seanet_pack_latents  z fp32 [B, D, frames] channel-first -> fp16 [B, frames, D], rounded once
+//   vbx_seanet_conv          k 7, D -> 16 nf;  vbx_gemm + vbx_lstm as above
+//   per stage (ratio r):
+//     vbx_seanet_convtr      ELU, transposed convolution k 2r, stride r, d -> d / 2: ONE product over rows [a_j | a_{j-1}], j = 0 .. L
+//     vbx_seanet_conv x 2    the Resnet block as in the encoder
+//   vbx_seanet_conv_out      ELU (fp32, not rounded again), k 7, nf -> 1, fp32 weights, plain VALU: the wave fp32 [B, frames * hop]
 #include <atomic>
 
 #include "common.hpp"
@@ -258,6 +267,157 @@ __global__ __launch_bounds__(256) void seanet_lstm_step_kernel(SnLstm p) {
   }
 }
 
+// ---------------------------------------------------------------------------------------------------- SEANetDecoder
+// EnCodec's decoder (voicebox-pytorch_amd/seanet.py: SEANetDecoder) runs vbx_seanet_pack_latents, vbx_seanet_conv (first convolution
+// and the Resnet blocks, as in the encoder), vbx_gemm + vbx_lstm, per stage vbx_seanet_convtr, and vbx_seanet_conv_out.
+
+struct SnConvTr {
+  const u16* x;       // [B, L, C], activated with ELU as it is staged
+  const u16* w;       // [r * Co, 2C]: row p * Co + o = [W[:, o, p] | W[:, o, p + r]]
+  const float* bias;  // [Co]
+  u16* y;             // [B, L * r, Co]
+  int L, C, Co, r, left, TT, N;
+};
+
+// The non-causal SConvTranspose1d with k = 2 r as ONE product over rows j = 0 .. L: the operand row is [a_j | a_{j-1}] (a = ELU(x),
+// a_{-1} = a_L = 0), its N = r * Co results are the contiguous run of r output positions from trimmed position j * r - left on.  A
+// workgroup owns TT consecutive rows j of one batch row: positions j0 - 1 .. j0 + TT - 1 sit in the LDS (LDS row m holds position
+// j0 - 1 + m), and row m of the A operand reads LDS row m + 1 for its first C columns and LDS row m for the other C, in place.
+// Work items as in seanet_conv_kernel; every output element is written by exactly one lane of one workgroup.
+template <int MG>
+__global__ __launch_bounds__(256) void seanet_convtr_kernel(SnConvTr p) {
+  extern __shared__ __attribute__((aligned(16))) u16 sn_lds[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int b = blockIdx.y, j0 = blockIdx.x * p.TT;
+  const int ld = p.C + SN_PADH;
+  const uint4 zero = make_uint4(0u, 0u, 0u, 0u);
+  {
+    const int c8 = p.C >> 3;
+    const u16* xb = p.x + (long)b * p.L * p.C;
+    for (int e = tid; e < (p.TT + 1) * c8; e += 256) {
+      const int pos = e / c8, c = (e - pos * c8) * 8;
+      const int i = j0 - 1 + pos;
+      uint4 v = zero;
+      if (i >= 0 && i < p.L) v = sn_elu8(*reinterpret_cast<const uint4*>(xb + (long)i * p.C + c));
+      *reinterpret_cast<uint4*>(sn_lds + pos * ld + c) = v;
+    }
+  }
+  __syncthreads();
+
+  const int NT = (p.N + 15) >> 4, MT = p.TT >> 4, items = NT * (MT / MG);
+  const int fr = lane & 15, g = lane >> 4;
+  const int K = 2 * p.C, ksteps = K >> 5;  // C is a multiple of 16
+  const long Lout = (long)p.L * p.r;
+  for (int it = wave; it < items; it += 4) {
+    const int nt = it % NT, mg = it / NT;
+    const int n = nt * 16 + fr;
+    const u16* wrow = p.w + (long)(n < p.N ? n : p.N - 1) * K;  // a column past N is computed and not stored
+    f32x4 acc[MG];
+#pragma unroll
+    for (int i = 0; i < MG; i++) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int ks = 0; ks < ksteps; ks++) {
+      const int kk = ks * 32 + g * 8;  // the eight columns lie in one of the two halves
+      const f16x8 bf = *reinterpret_cast<const f16x8*>(wrow + kk);
+      const u16* base = kk < p.C ? sn_lds + ld + kk : sn_lds + (kk - p.C);
+      f16x8 af[MG];
+#pragma unroll
+      for (int i = 0; i < MG; i++) af[i] = *reinterpret_cast<const f16x8*>(base + ((mg * MG + i) * 16 + fr) * ld);
+#pragma unroll
+      for (int i = 0; i < MG; i++) acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[i], bf, acc[i], 0, 0, 0);
+    }
+    if (n < p.N) {
+      const int ph = n / p.Co;
+      const float bv = p.bias[n - ph * p.Co];
+#pragma unroll
+      for (int i = 0; i < MG; i++) {
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+          const int j = j0 + (mg * MG + i) * 16 + g * 4 + q;
+          if (j > p.L) continue;
+          const long t = (long)j * p.r + ph - p.left;  // row 0 drops its phases below `left`, row L keeps only those
+          if (t < 0 || t >= Lout) continue;
+          p.y[((long)b * Lout + t) * p.Co + (n - ph * p.Co)] = f32_to_f16(acc[i][q] + bv);
+        }
+      }
+    }
+  }
+}
+
+// the last convolution, nf -> 1: one thread per output sample, the k * nf products as ONE fmaf chain on the bias, tap-major then
+// channel; ELU in fp32 on the stored fp16 value, not rounded again
+__global__ __launch_bounds__(256) void seanet_conv_out_kernel(const u16* __restrict__ x, const float* __restrict__ w,
+                                                              const float* __restrict__ bias, float* __restrict__ y, int T, int nf, int k,
+                                                              int pad_left, int Lz) {
+  __shared__ float sw[7 * 64];
+  const int tid = threadIdx.x, b = blockIdx.y;
+  for (int e = tid; e < k * nf; e += 256) sw[e] = w[e];
+  __syncthreads();
+  const long pos = (long)blockIdx.x * 256 + tid;
+  if (pos >= T) return;
+  const u16* xb = x + (long)b * T * nf;
+  float acc = bias[0];
+  for (int tap = 0; tap < k; tap++) {
+    const int i = sn_src((int)pos + tap, pad_left, T, Lz);
+    if (i < 0) continue;  // one of pad1d's appended zeros: ELU(0) = 0 adds nothing
+    for (int c = 0; c < nf; c += 8) {
+      const uint4 v = *reinterpret_cast<const uint4*>(xb + (long)i * nf + c);
+      const unsigned u[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+      for (int h = 0; h < 4; h++) {
+        acc = fmaf(sw[tap * nf + c + 2 * h], sn_elu(f16_to_f32((u16)(u[h] & 0xFFFFu))), acc);
+        acc = fmaf(sw[tap * nf + c + 2 * h + 1], sn_elu(f16_to_f32((u16)(u[h] >> 16))), acc);
+      }
+    }
+  }
+  y[(long)b * T + pos] = acc;
+}
+
+// latents fp32 [B, D, T] channel-first -> fp16 [B, T, D] channel-last, rounded once: a 32 x 32 tile through the LDS
+__global__ __launch_bounds__(256) void seanet_pack_latents_kernel(const float* __restrict__ z, u16* __restrict__ y, int D, int T) {
+  __shared__ float tile[32][33];
+  const int b = blockIdx.z, t0 = blockIdx.x * 32, d0 = blockIdx.y * 32;
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+  for (int r = ty; r < 32; r += 8) {
+    const int d = d0 + r, t = t0 + tx;
+    tile[r][tx] = (d < D && t < T) ? z[((long)b * D + d) * T + t] : 0.f;
+  }
+  __syncthreads();
+  for (int r = ty; r < 32; r += 8) {
+    const int t = t0 + r, d = d0 + tx;
+    if (t < T && d < D) y[((long)b * T + t) * D + d] = f32_to_f16(tile[tx][r]);
+  }
+}
+
+int sn_convtr_check(int C, int stride) {
+  VBX_REQUIRE(C >= 16 && C % 16 == 0 && C <= SN_MAX_C, "vbx_seanet_convtr: C must be a multiple of 16 in 16 .. %d (got %d)", SN_MAX_C, C);
+  VBX_REQUIRE(stride >= 2 && stride <= SN_MAX_STRIDE, "vbx_seanet_convtr: stride must be in 2 .. %d (got %d)", SN_MAX_STRIDE, stride);
+  return 0;
+}
+
+size_t sn_convtr_lds(int TT, int C) { return (size_t)(TT + 1) * (C + SN_PADH) * sizeof(u16); }
+
+int sn_convtr_tile(int C) {
+  for (int TT = 128; TT >= 16; TT >>= 1)
+    if (sn_convtr_lds(TT, C) <= (size_t)(TT > 16 ? SN_LDS_PREF : SN_LDS_MAX)) return TT;
+  return 0;
+}
+
+template <int MG>
+int sn_convtr_launch(const SnConvTr& p, int B, size_t bytes, hipStream_t st) {
+  static std::atomic<unsigned long long> allowed{0};  // as sn_conv_launch: more than 64 KiB of dynamic LDS, once per device
+  int dev = 0;
+  VBX_REQUIRE(hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64, "vbx_seanet_convtr: no current device");
+  if (!(allowed.load(std::memory_order_acquire) >> dev & 1)) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(seanet_convtr_kernel<MG>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       SN_LDS_MAX);
+    VBX_REQUIRE(e == hipSuccess, "vbx_seanet_convtr: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
+    allowed.fetch_or(1ull << dev, std::memory_order_release);
+  }
+  hipLaunchKernelGGL(seanet_convtr_kernel<MG>, dim3(cdiv(p.L + 1, p.TT), B), dim3(256), bytes, st, p);
+  VBX_LAUNCH_CHECK();
+  return 0;
+}
+
 int sn_conv_check(int C1, int C2, int k, int stride, int dil) {
   VBX_REQUIRE(C1 >= 8 && C1 % 8 == 0 && C1 <= SN_MAX_C, "vbx_seanet_conv: C1 must be a multiple of 8 in 8 .. %d (got %d)", SN_MAX_C, C1);
   VBX_REQUIRE(C2 >= 0 && C2 % 8 == 0 && C2 <= SN_MAX_C, "vbx_seanet_conv: C2 must be 0 or a multiple of 8 up to %d (got %d)", SN_MAX_C, C2);
@@ -382,6 +542,56 @@ extern "C" int vbx_lstm(const float* xproj, const void* w_hh0, const void* w_cat
     p.s = s;
     hipLaunchKernelGGL(seanet_lstm_step_kernel, dim3(H / 16, layers, cdiv(B, 16)), dim3(256), 0, (hipStream_t)stream, p);
   }
+  VBX_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int vbx_seanet_convtr_tile(int C, int stride) {
+  if (int rc = sn_convtr_check(C, stride)) return rc;
+  const int TT = sn_convtr_tile(C);
+  if (!TT) {
+    vbx_set_error("vbx_seanet_convtr: 16 rows of this transposed convolution do not fit the LDS");
+    return VBX_EINVAL;
+  }
+  return TT;
+}
+
+extern "C" int vbx_seanet_convtr(const void* x_f16, const void* w_f16, const float* bias, void* y_f16, int B, int L, int C, int stride,
+                                 void* stream) {
+  VBX_REQUIRE(x_f16 && w_f16 && bias && y_f16, "vbx_seanet_convtr: null operand");
+  VBX_REQUIRE(B >= 1 && B <= 65535 && L >= 1, "vbx_seanet_convtr: need B in 1 .. 65535, L >= 1");
+  if (int rc = sn_convtr_check(C, stride)) return rc;
+  VBX_REQUIRE((long)L * stride < (1L << 30), "vbx_seanet_convtr: row too long");
+  int TT = sn_convtr_tile(C);
+  VBX_REQUIRE(TT > 0, "vbx_seanet_convtr: 16 rows of this transposed convolution do not fit the LDS");
+  while (TT > 16 && TT / 2 >= L + 1) TT >>= 1;  // a short row: L + 1 product rows
+  SnConvTr p;
+  p.x = (const u16*)x_f16, p.w = (const u16*)w_f16, p.bias = bias, p.y = (u16*)y_f16;
+  p.L = L, p.C = C, p.Co = C / 2, p.r = stride, p.left = stride - stride / 2, p.TT = TT, p.N = stride * (C / 2);
+  const size_t bytes = sn_convtr_lds(TT, C);
+  const int NT = (p.N + 15) / 16, MT = TT / 16;
+  const int MG = (MT % 4 == 0 && NT * MT / 4 >= 4) ? 4 : ((MT % 2 == 0 && NT * MT / 2 >= 4) ? 2 : 1);
+  if (MG == 4) return sn_convtr_launch<4>(p, B, bytes, (hipStream_t)stream);
+  if (MG == 2) return sn_convtr_launch<2>(p, B, bytes, (hipStream_t)stream);
+  return sn_convtr_launch<1>(p, B, bytes, (hipStream_t)stream);
+}
+
+extern "C" int vbx_seanet_conv_out(const void* x_f16, const float* w, const float* bias, float* y, int B, int T, int nf, int k,
+                                   void* stream) {
+  VBX_REQUIRE(x_f16 && w && bias && y && B >= 1 && B <= 65535 && T >= 1, "vbx_seanet_conv_out: bad args");
+  VBX_REQUIRE(nf >= 8 && nf % 8 == 0 && nf <= 64, "vbx_seanet_conv_out: n_filters must be a multiple of 8 up to 64 (got %d)", nf);
+  VBX_REQUIRE(k >= 1 && k <= 7 && (k & 1), "vbx_seanet_conv_out: last_kernel_size must be odd, at most 7 (got %d)", k);
+  VBX_REQUIRE(T < (1 << 30), "vbx_seanet_conv_out: row too long");
+  const int right = (k - 1) / 2, left = k - 1 - right, maxpad = left > right ? left : right;
+  hipLaunchKernelGGL(seanet_conv_out_kernel, dim3(cdiv(T, 256), B), dim3(256), 0, (hipStream_t)stream, (const u16*)x_f16, w, bias, y, T, nf,
+                     k, left, T > maxpad ? T : maxpad + 1);
+  VBX_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int vbx_seanet_pack_latents(const float* z, void* y_f16, int B, int D, int T, void* stream) {
+  VBX_REQUIRE(z && y_f16 && B >= 1 && B <= 65535 && D >= 1 && D <= 65535 * 32 && T >= 1, "vbx_seanet_pack_latents: bad args");
+  hipLaunchKernelGGL(seanet_pack_latents_kernel, dim3(cdiv(T, 32), cdiv(D, 32), B), dim3(256), 0, (hipStream_t)stream, z, (u16*)y_f16, D, T);
   VBX_LAUNCH_CHECK();
   return 0;
 }
