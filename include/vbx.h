@@ -391,6 +391,30 @@ int vbx_seanet_pack_latents(const float* z, void* y_f16, int B, int D, int T, vo
 int vbx_seanet_convtr_tile(int C, int stride);
 int vbx_seanet_convtr(const void* x_f16, const void* w_f16, const float* bias, void* y_f16, int B, int L, int C, int stride, void* stream);
 int vbx_seanet_conv_out(const void* x_f16, const float* w, const float* bias, float* y, int B, int T, int nf, int k, void* stream);
+/* Aligner primitives (voicebox_pytorch_amd.maximum_path / forward_sum_loss; csrc/align.hip): monotonic alignment search and the
+ * forward-sum (CTC) loss over an attention map fp32 [B, T, K], T query frames by K keys.  K in 1 .. 1024, any T >= 1, B * T < 2^31;
+ * everything else returns VBX_EINVAL.  query_lens / key_lens: int32 [B] on the device, NULL = T / K; a length is clamped into
+ * [0, T] / [0, K].  A row with key_len == 0 or query_len < key_len has no monotonic path: a defined all-zero result, no error.
+ * One workgroup per batch row, no atomics, no host synchronisation: the same bits on every run and for a row
+ * alone or inside a batch.
+ * vbx_maximum_path: Q[y][x] = max(Q[y-1][x], Q[y-1][x-1]) + value[y][x] over the band max(0, k + y - q) <= x <= min(k - 1, y)
+ *   (a predecessor outside it is excluded), then from idx = k - 1 at y = q - 1 downwards: path[y][idx] = 1 and idx -= 1 iff
+ *   idx != 0 and (idx == y or Q[y-1][idx] < Q[y-1][idx-1]) -- a tie STAYS on the key.  path fp32 [B, T, K] is written whole
+ *   (zeros at t >= q and keys >= k), durations int64 [B, K] = path summed over t.  The returned path is exactly optimal for the
+ *   table as rounded in fp32 (one addition per cell).  bits: scratch, B * T * ceil(K / 64) 64-bit words, contents undefined.
+ * vbx_forward_sum_fwd: per frame t < q the log-softmax over {blank_logprob, value[t][0 .. k)}, then CTC with blank 0 and target
+ *   1 .. k:  nll fp32 [B] = -log Z, 0 for a row without a path or with a non-finite Z (zero_infinity); NOT divided by key_len.
+ *   Scratch kept for the backward: lse fp64 [B, T], alpha fp64 [B, T, K] (the label states; NULL when no backward follows),
+ *   logz fp64 [B].  Inputs, exponentials and logarithms are fp32; the running log-probabilities, whose magnitude grows with T, are
+ *   summed in fp64.  Two launches: the normalisers on every CU, then the recursion.
+ * vbx_forward_sum_bwd: grad fp32 [B, T, K] = grad_nll[b] * d nll[b] / d value, through the pad + mask + log-softmax; written whole,
+ *   exactly 0 at t >= q, at keys >= k and on rows whose nll is 0 by the rule above. */
+int vbx_maximum_path(const float* value, const int* query_lens, const int* key_lens, float* path, long* durations,
+                     unsigned long long* bits, int B, int T, int K, void* stream);
+int vbx_forward_sum_fwd(const float* value, const int* key_lens, const int* query_lens, float blank_logprob, double* lse, double* alpha,
+                        float* nll, double* logz, int B, int T, int K, void* stream);
+int vbx_forward_sum_bwd(const float* value, const int* key_lens, const int* query_lens, float blank_logprob, const double* lse,
+                        const double* alpha, const double* logz, const float* grad_nll, float* grad, int B, int T, int K, void* stream);
 /* Sample-rate conversion (voicebox_pytorch_amd.resample; csrc/resample.hip): the polyphase windowed-sinc FIR of
  * torchaudio.functional.resample for the REDUCED rate pair orig : nw,
  *   y[r][q * nw + p] = sum_k h[p][k] * x[r][q * orig + k - width],  x = 0 outside [0, L),  p < nw, k < K = 2 * width + orig,

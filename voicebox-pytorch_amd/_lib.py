@@ -89,6 +89,9 @@ _PROTOS = {
     "vbx_seanet_convtr_tile": [I, I],
     "vbx_seanet_convtr": [P, P, P, P, I, I, I, I, P],
     "vbx_seanet_conv_out": [P, P, P, P, I, I, I, I, P],
+    "vbx_maximum_path": [P, P, P, P, P, P, I, I, I, P],
+    "vbx_forward_sum_fwd": [P, P, P, F, P, P, P, P, I, I, I, P],
+    "vbx_forward_sum_bwd": [P, P, P, F, P, P, P, P, P, I, I, I, P],
     "vbx_resample_max_taps": [],
     "vbx_resample": [P, P, P, P, P, I, L, L, I, I, I, I, I, P],
     "vbx_pack_phoneme_input": [P, P, I, P, I, P, P, P, P, I, I, I, P],
