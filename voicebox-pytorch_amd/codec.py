@@ -24,6 +24,7 @@ import torch
 from torch import nn
 
 from . import _lib
+from ._packing import PackedWeights, read_checkpoint, tensors_key
 from .masks import take_draw
 
 
@@ -379,7 +380,7 @@ def _check_rvq_args(dim, codebook_size, num_quantizers):
         raise NotImplementedError(f"ResidualVQ: num_quantizers must be in 1 .. 32 (got {num_quantizers})")
 
 
-class ResidualVQ(nn.Module):
+class ResidualVQ(PackedWeights, nn.Module):
     """The residual vector quantizer of an EnCodec-style codec on the device (csrc/rvq.hip): one fp32 buffer `codebooks`
     [num_quantizers, codebook_size, dim], Euclidean codebooks, inference only.  Per frame, r_0 = x and for each quantizer q
     code_q = argmin_k |r_q - c_qk|^2 (the lowest index on an exact tie), r_{q+1} = r_q - c_q[code_q]; the quantized frame is
@@ -401,7 +402,6 @@ class ResidualVQ(nn.Module):
         _check_rvq_args(dim, codebook_size, num_quantizers)
         self.dim, self.codebook_size, self.num_quantizers = dim, codebook_size, num_quantizers
         self.register_buffer("codebooks", torch.randn(num_quantizers, codebook_size, dim))
-        self._norms, self._norms_key = None, None
 
     # -- state
     def _stacked(self, state_dict, prefix=""):
@@ -433,8 +433,13 @@ class ResidualVQ(nn.Module):
         return super()._load_from_state_dict(state_dict, prefix, *args, **kw)
 
     def _weights_key(self):
-        t = self.codebooks
-        return (t.data_ptr(), 0 if t.is_inference() else t._version)
+        return tensors_key((self.codebooks,))
+
+    def _build_norms(self):
+        Q, K, D = self.codebooks.shape
+        norms = torch.empty(Q, K, dtype=torch.float32, device=self.codebooks.device)
+        _lib.call("vbx_rvq_norms", self.codebooks, norms, Q, K, D, _lib.current_stream())
+        return norms
 
     def _tables(self, device, who):
         """(codebooks, |c|^2 table) on `device`; the table is rebuilt when the buffer's storage or version counter changed
@@ -445,16 +450,7 @@ class ResidualVQ(nn.Module):
             raise _lib.VbxError(f"{who} runs only on an MI355X (gfx950) through libvbx_hip.so; the input is on '{device}'")
         if self.codebooks.device != device:
             self.to(device)
-        key = self._weights_key()
-        if key != self._norms_key:
-            Q, K, D = self.codebooks.shape
-            norms = torch.empty(Q, K, dtype=torch.float32, device=device)
-            _lib.call("vbx_rvq_norms", self.codebooks, norms, Q, K, D, _lib.current_stream())
-            self._norms, self._norms_key = norms, key
-        return self.codebooks, self._norms
-
-    def mark_weights_dirty(self):
-        self._norms_key = None
+        return self.codebooks, self._cached(self._build_norms)
 
     # -- device path
     def _search(self, latents, *, codes_qn, quantized, who):
@@ -549,7 +545,7 @@ class EncodecVocoCodec(AudioEncoderDecoder):
         the table holds); the vocoder is built as VocosDecoder.from_checkpoint(path, bandwidth_id=bandwidth_id) builds it, and its
         limits apply: the one published Vocos-EnCodec model (n_fft 1280, padding="same") is outside them and raises
         NotImplementedError, so this loader has only been exercised on synthetic files of that layout."""
-        from .vocos import VocosDecoder, read_checkpoint
+        from .vocos import VocosDecoder
 
         sd = read_checkpoint(path)
         if "feature_extractor.codebook_weights" not in sd:
@@ -575,7 +571,6 @@ class EncodecVocoCodec(AudioEncoderDecoder):
         has no decoder half): the one file is then a complete codec.  A `vocoder` that is passed (a VocosDecoder) is used instead,
         and the decoder half of the file is not read."""
         from .seanet import SEANetDecoder, SEANetEncoder
-        from .vocos import read_checkpoint
 
         sd = read_checkpoint(path)
         if not 0 <= bandwidth_id < len(RVQ_BANDWIDTH_QUANTIZERS):

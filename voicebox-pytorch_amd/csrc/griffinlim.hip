@@ -13,43 +13,18 @@
 // formula (subtract, then divide).  All spectra are frame-major ([B, frames, bins], interleaved re / im) so a workgroup reads and
 // writes whole rows.
 //
-// As in mel.hip a workgroup serves GL_FRAMES = 4 consecutive frames: two complex transforms of n_fft points side by side, 128
-// threads each, each carrying TWO real frames.  Forward: frame 2c is the real part and frame 2c + 1 the imaginary part, separated
-// afterwards by the symmetry of a real signal's spectrum.  Inverse: Z[k] = X0[k] + i X1[k] with both spectra extended by their
-// Hermitian symmetry, so Re z = x0 and Im z = x1; the imaginary parts of the DC and Nyquist bins are DROPPED first (a
-// complex-to-real transform ignores them; a random initial phase makes them non-zero).  Radix-2 decimation in time on bit-reversed
-// input, in place; the inverse uses the conjugate twiddles of the same fp64-built table and the exact factor 1 / n_fft at the end.
-// LDS index i lives at i + (i >> 6) (64 banks of 4 bytes): the same skew and the same reasoning as mel.hip.  The LDS is sized per
-// launch (n_fft and hop dependent), so the default codec takes 21 KiB a workgroup instead of the 2048-point worst case.
-#include "common.hpp"
+// A workgroup serves GL_FRAMES = 4 consecutive frames with the two transforms of fft_lds.hpp (protocol and LDS layout there), each
+// carrying two real frames.  Before an inverse transform the imaginary parts of the DC and Nyquist bins are DROPPED (a
+// complex-to-real transform ignores them; a random initial phase makes them non-zero); its exact factor 1 / n_fft is applied with
+// the window.  The LDS is sized per launch (n_fft and hop dependent), so the default codec takes 21 KiB a workgroup instead of the
+// 2048-point worst case.
+#include "fft_lds.hpp"
 
 namespace {
 
 constexpr int GL_FRAMES = 4;
-constexpr int GL_MAX_FFT = 2048;
 constexpr int GL_MAX_LDS = 64 * 1024;
 constexpr int MM_FRAMES = 8;
-VBX_DEV int skew(int i) { return i + (i >> 6); }
-static inline int fft_ld(int n_fft) { return n_fft + (n_fft >> 6); }
-
-// in-place radix-2 DIT over bit-reversed input; sgn = +1 forward (twiddle e^{-i..}), -1 inverse (conjugate).  All 256 threads call it.
-VBX_DEV void fft_lds(float* re, float* im, const float* __restrict__ tw_re, const float* __restrict__ tw_im, float sgn, int log2n,
-                     int half_n, int t) {
-  for (int s = 0; s < log2n; s++) {
-    const int half = 1 << s, tstep = half_n >> s;
-    for (int q = t; q < half_n; q += 128) {
-      const int pos = q & (half - 1);
-      const int i0 = skew(((q >> s) << (s + 1)) + pos), i1 = skew(((q >> s) << (s + 1)) + pos + half);
-      const float wr = tw_re[pos * tstep], wi = sgn * tw_im[pos * tstep];
-      const float xr = re[i1], xi = im[i1];
-      const float br = xr * wr - xi * wi, bi = xr * wi + xi * wr;
-      const float ar = re[i0], ai = im[i0];
-      re[i0] = ar + br; im[i0] = ai + bi;
-      re[i1] = ar - br; im[i1] = ai - bi;
-    }
-    __syncthreads();
-  }
-}
 
 // wave sample t (0 <= t < (frames - 1) * hop) of batch row `fb`: the frames g with 0 <= n - g * hop < win cover it, n counted from
 // the first sample under the window of frame 0
@@ -73,7 +48,7 @@ __global__ __launch_bounds__(256) void gl_synth_kernel(const float2* __restrict_
   extern __shared__ float smem[];
   const int tid = threadIdx.x, c = tid >> 7, t = tid & 127;
   const int f0 = blockIdx.x * GL_FRAMES, b = blockIdx.y;
-  const int half_n = n_fft >> 1, nb = half_n + 1, ld = n_fft + (n_fft >> 6);
+  const int half_n = n_fft >> 1, nb = half_n + 1, ld = fft_ld(n_fft);
   float* re = smem + c * ld;
   float* im = smem + (2 + c) * ld;
 
@@ -100,21 +75,21 @@ __global__ __launch_bounds__(256) void gl_synth_kernel(const float2* __restrict_
       }
     }
     if (k == 0 || k == half_n) x[0][1] = x[1][1] = 0.f;
-    const int r = skew((int)(__brev((unsigned)k) >> (32 - log2n)));
+    const int r = fft_brev(k, log2n);
     re[r] = x[0][0] - x[1][1];
     im[r] = x[0][1] + x[1][0];
     if (k > 0 && k < half_n) {  // Z[N - k] = conj(X0[k]) + i conj(X1[k])
-      const int r2 = skew((int)(__brev((unsigned)(n_fft - k)) >> (32 - log2n)));
+      const int r2 = fft_brev(n_fft - k, log2n);
       re[r2] = x[0][0] + x[1][1];
       im[r2] = x[1][0] - x[0][1];
     }
   }
   __syncthreads();
-  fft_lds(re, im, tw_re, tw_im, -1.f, log2n, half_n, t);
+  fft_lds<true>(re, im, tw_re, tw_im, log2n, half_n, t);
   const float inv_n = 1.0f / (float)n_fft;
   for (int j = t; j < win; j += 128) {
     const float w = window[left + j] * inv_n;  // 1 / n_fft is a power of two: exact
-    const int i = skew(left + j);
+    const int i = fft_skew(left + j);
     const int f = f0 + 2 * c;
     if (f < frames) fb[((long)b * frames + f) * win + j] = re[i] * w;
     if (f + 1 < frames) fb[((long)b * frames + f + 1) * win + j] = im[i] * w;
@@ -128,7 +103,7 @@ __global__ __launch_bounds__(256) void gl_analysis_kernel(const float* __restric
   extern __shared__ float smem[];
   const int tid = threadIdx.x, c = tid >> 7, t = tid & 127;
   const int f0 = blockIdx.x * GL_FRAMES, b = blockIdx.y;
-  const int half_n = n_fft >> 1, nb = half_n + 1, ld = n_fft + (n_fft >> 6);
+  const int half_n = n_fft >> 1, nb = half_n + 1, ld = fft_ld(n_fft);
   float* re = smem + c * ld;
   float* im = smem + (2 + c) * ld;
   float* seg = smem + 4 * ld;  // the wave under the windows of this workgroup's frames, reflect padding resolved
@@ -154,19 +129,17 @@ __global__ __launch_bounds__(256) void gl_analysis_kernel(const float* __restric
         if (fl < nvalid) v[h] = seg[fl * hop + j - left] * w;
       }
     }
-    const int r = skew((int)(__brev((unsigned)j) >> (32 - log2n)));
+    const int r = fft_brev(j, log2n);
     re[r] = v[0];
     im[r] = v[1];
   }
   __syncthreads();
-  fft_lds(re, im, tw_re, tw_im, 1.f, log2n, half_n, t);
-  // separate the two real frames: A[k] = (Z[k] + conj(Z[N-k])) / 2,  B[k] = (Z[k] - conj(Z[N-k])) / (2i)
+  fft_lds<false>(re, im, tw_re, tw_im, log2n, half_n, t);
   for (int k = t; k <= half_n; k += 128) {
-    const int i0 = skew(k), i1 = skew((n_fft - k) & (n_fft - 1));
-    const float zr = re[i0], zi = im[i0], nr = re[i1], ni = im[i1];
+    const FftPair z = fft_split(re, im, k, n_fft);
     const int f = f0 + 2 * c;
-    if (f < frames) R[((long)b * frames + f) * nb + k] = make_float2(0.5f * (zr + nr), 0.5f * (zi - ni));
-    if (f + 1 < frames) R[((long)b * frames + f + 1) * nb + k] = make_float2(0.5f * (zi + ni), -0.5f * (zr - nr));
+    if (f < frames) R[((long)b * frames + f) * nb + k] = make_float2(z.ar, z.ai);
+    if (f + 1 < frames) R[((long)b * frames + f + 1) * nb + k] = make_float2(z.br, z.bi);
   }
 }
 
@@ -232,14 +205,13 @@ extern "C" int vbx_griffinlim(const float* mag, float* spec_a, float* spec_b, fl
                               int n_iter, float m, void* stream) {
   VBX_REQUIRE(mag && spec_a && spec_b && fb && wave && window && tw_re && tw_im && renv && B > 0 && B <= 65535 && n_iter >= 0,
               "vbx_griffinlim: bad args");
-  VBX_REQUIRE(n_fft >= 256 && n_fft <= GL_MAX_FFT && (n_fft & (n_fft - 1)) == 0, "vbx_griffinlim: n_fft must be a power of two in 256 .. 2048");
+  if (int rc = fft_check_size("vbx_griffinlim", n_fft)) return rc;
   VBX_REQUIRE(win > 0 && win <= n_fft && hop > 0 && hop <= win, "vbx_griffinlim: need 0 < hop <= win_length <= n_fft");
   VBX_REQUIRE(frames > 1 && (long)(frames - 1) * hop > n_fft / 2 && (long)(frames - 1) * hop + n_fft < 2147483647L,
               "vbx_griffinlim: (frames - 1) * hop must exceed n_fft / 2 (reflect padding of the analysis step)");
   const int lds = vbx_griffinlim_lds_bytes(n_fft, win, hop);
   VBX_REQUIRE(lds <= GL_MAX_LDS, "vbx_griffinlim: 3 * hop + win_length does not fit the LDS beside a %d-point transform", n_fft);
-  int log2n = 0;
-  while ((1 << log2n) < n_fft) log2n++;
+  const int log2n = fft_log2(n_fft);
   const int left = (n_fft - win) / 2, half_n = n_fft / 2;
   const long L = (long)(frames - 1) * hop;
   hipStream_t st = (hipStream_t)stream;
@@ -266,11 +238,10 @@ extern "C" int vbx_griffinlim(const float* mag, float* spec_a, float* spec_b, fl
 extern "C" int vbx_istft(const float* mag, const float* spec, float* fb, float* wave, const float* window, const float* tw_re,
                          const float* tw_im, const float* renv, int B, int frames, int n_fft, int win, int hop, void* stream) {
   VBX_REQUIRE(mag && spec && fb && wave && window && tw_re && tw_im && renv && B > 0 && B <= 65535, "vbx_istft: bad args");
-  VBX_REQUIRE(n_fft >= 256 && n_fft <= GL_MAX_FFT && (n_fft & (n_fft - 1)) == 0, "vbx_istft: n_fft must be a power of two in 256 .. 2048");
+  if (int rc = fft_check_size("vbx_istft", n_fft)) return rc;
   VBX_REQUIRE(win > 0 && win <= n_fft && hop > 0 && hop <= win, "vbx_istft: need 0 < hop <= win_length <= n_fft");
   VBX_REQUIRE(frames > 1 && (long)(frames - 1) * hop + n_fft < 2147483647L, "vbx_istft: need at least two frames");
-  int log2n = 0;
-  while ((1 << log2n) < n_fft) log2n++;
+  const int log2n = fft_log2(n_fft);
   const int left = (n_fft - win) / 2;
   const long L = (long)(frames - 1) * hop;
   hipStream_t st = (hipStream_t)stream;

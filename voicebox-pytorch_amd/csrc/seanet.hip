@@ -65,14 +65,58 @@ VBX_DEV int sn_src(int q, int pad_left, int L, int Lz) {
   return i < L ? i : -1;
 }
 
-// A workgroup owns TT consecutive output positions of one batch row and all Co channels.  The input span ((TT - 1) * stride + k_eff
-// positions, channel-last) sits in the LDS; row m of the A operand is the k runs of C1 channels at positions m * stride + tap * dil,
-// read in place (no im2col copy anywhere).  Work items are (16 output channels) x (MG blocks of 16 positions), dealt to the four
-// waves; the weight fragments come straight from memory (every workgroup reads the same matrix: L2 traffic).
+// The product both tiled kernels run once their span is staged in the LDS: out[m][n] = sum_kk A[m][kk] w[n][kk] over the tile's MT * 16
+// rows m and N columns n, every sum fp32 on v_mfma_f32_16x16x32_f16 in ascending kk.  Work items are (16 columns) x (MG blocks of 16
+// rows), dealt to the four waves; the weight fragments come straight from memory (every workgroup reads the same matrix: L2
+// traffic).  TAIL: Ktot need not be a multiple of 32, past it a step takes zeros.  rows(kk, base, ld) says where the eight A columns
+// from kk on live: row m's at base + m * ld, read in place (no im2col copy anywhere).  store(n)(m, v) is handed every out[m][n], n < N.
+template <int MG, bool TAIL, class ARows, class Store>
+VBX_DEV void sn_tile_product(const u16* __restrict__ w, int N, int Ktot, int MT, const ARows& rows, const Store& store) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int NT = (N + 15) >> 4, items = NT * (MT / MG);
+  const int fr = lane & 15, g = lane >> 4;
+  const int ksteps = (Ktot + 31) >> 5;
+  const f16x8 hz = {0, 0, 0, 0, 0, 0, 0, 0};
+  for (int it = wave; it < items; it += 4) {
+    const int nt = it % NT, mg = it / NT;
+    const int n = nt * 16 + fr;
+    const u16* wrow = w + (long)(n < N ? n : N - 1) * Ktot;  // a column past N multiplies the last row again and is not stored
+    f32x4 acc[MG];
+#pragma unroll
+    for (int i = 0; i < MG; i++) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int ks = 0; ks < ksteps; ks++) {
+      const int kk = ks * 32 + g * 8;
+      f16x8 bf = hz, af[MG];
+#pragma unroll
+      for (int i = 0; i < MG; i++) af[i] = hz;
+      if (!TAIL || kk < Ktot) {  // the weight fragment is asked for first: rows' address arithmetic runs under its latency
+        bf = *reinterpret_cast<const f16x8*>(wrow + kk);
+        const u16* base;
+        int ld;
+        rows(kk, base, ld);
+#pragma unroll
+        for (int i = 0; i < MG; i++) af[i] = *reinterpret_cast<const f16x8*>(base + ((mg * MG + i) * 16 + fr) * ld);
+      }
+#pragma unroll
+      for (int i = 0; i < MG; i++) acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[i], bf, acc[i], 0, 0, 0);
+    }
+    if (n < N) {
+      const auto put = store(n);
+#pragma unroll
+      for (int i = 0; i < MG; i++) {
+#pragma unroll
+        for (int r = 0; r < 4; r++) put((mg * MG + i) * 16 + g * 4 + r, acc[i][r]);
+      }
+    }
+  }
+}
+
+// A workgroup owns TT consecutive output positions of one batch row and all Co channels: it stages the input span ((TT - 1) * stride
+// + k_eff positions, channel-last, padding resolved, ELU applied) and the second input's TT positions, then runs the product.
 template <int MG>
 __global__ __launch_bounds__(256) void seanet_conv_kernel(SnConv p) {
   extern __shared__ __attribute__((aligned(16))) u16 sn_lds[];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const int b = blockIdx.y, t0 = blockIdx.x * p.TT;
   const int ld1 = p.C1 + SN_PADH, ld2 = p.C2 + SN_PADH;
   const int keff = (p.k - 1) * p.dil + 1;
@@ -108,56 +152,27 @@ __global__ __launch_bounds__(256) void seanet_conv_kernel(SnConv p) {
     }
   }
   __syncthreads();
-
-  const int NT = (p.Co + 15) >> 4, MT = p.TT >> 4, items = NT * (MT / MG);
-  const int fr = lane & 15, g = lane >> 4;
-  const int K1 = p.k * p.C1, ksteps = (p.Ktot + 31) >> 5;
-  const f16x8 hz = {0, 0, 0, 0, 0, 0, 0, 0};
-  for (int it = wave; it < items; it += 4) {
-    const int nt = it % NT, mg = it / NT;
-    const int n = nt * 16 + fr;
-    // a column past Co multiplies the last row again: column n of the weight only reaches output column n, which is not stored
-    const u16* wrow = p.w + (long)(n < p.Co ? n : p.Co - 1) * p.Ktot;
-    f32x4 acc[MG];
-#pragma unroll
-    for (int i = 0; i < MG; i++) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-    for (int ks = 0; ks < ksteps; ks++) {
-      const int kk = ks * 32 + g * 8;  // C1, C2 are multiples of 8: the eight columns lie in one tap of one input
-      f16x8 bf = hz, af[MG];
-#pragma unroll
-      for (int i = 0; i < MG; i++) af[i] = hz;
-      if (kk < p.Ktot) {
-        bf = *reinterpret_cast<const f16x8*>(wrow + kk);
-        if (kk < K1) {
-          const int tap = kk / p.C1, c = kk - tap * p.C1;
-          const u16* base = s1 + tap * p.dil * ld1 + c;
-#pragma unroll
-          for (int i = 0; i < MG; i++) af[i] = *reinterpret_cast<const f16x8*>(base + ((mg * MG + i) * 16 + fr) * p.stride * ld1);
-        } else {
-          const u16* base = s2 + (kk - K1);
-#pragma unroll
-          for (int i = 0; i < MG; i++) af[i] = *reinterpret_cast<const f16x8*>(base + ((mg * MG + i) * 16 + fr) * ld2);
-        }
-      }
-#pragma unroll
-      for (int i = 0; i < MG; i++) acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[i], bf, acc[i], 0, 0, 0);
+  // row m of the A operand: the k runs of C1 channels at positions m * stride + tap * dil of the span, then x2's C2 channels at
+  // position m.  C1, C2 are multiples of 8: the eight columns lie in one tap of one input.
+  const int K1 = p.k * p.C1;
+  auto rows = [&](int kk, const u16*& base, int& ld) __attribute__((always_inline)) {
+    if (kk < K1) {
+      const int tap = kk / p.C1, c = kk - tap * p.C1;
+      base = s1 + tap * p.dil * ld1 + c, ld = p.stride * ld1;
+    } else {
+      base = s2 + (kk - K1), ld = ld2;
     }
-    if (n < p.Co) {
-      const float bv = p.bias[n];
-#pragma unroll
-      for (int i = 0; i < MG; i++) {
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-          const int t = t0 + (mg * MG + i) * 16 + g * 4 + r;
-          if (t >= p.Lout) continue;
-          const long o = ((long)b * p.Lout + t) * p.Co + n;
-          const float v = acc[i][r] + bv;
-          if (p.out_f32) reinterpret_cast<float*>(p.y)[o] = v;
-          else reinterpret_cast<u16*>(p.y)[o] = f32_to_f16(v);
-        }
-      }
-    }
-  }
+  };
+  auto store = [&](int n) __attribute__((always_inline)) {
+    return [&, n, bv = p.bias[n]](int m, float v) __attribute__((always_inline)) {
+      const int t = t0 + m;
+      if (t >= p.Lout) return;
+      const long o = ((long)b * p.Lout + t) * p.Co + n;
+      if (p.out_f32) reinterpret_cast<float*>(p.y)[o] = v + bv;
+      else reinterpret_cast<u16*>(p.y)[o] = f32_to_f16(v + bv);
+    };
+  };
+  sn_tile_product<MG, true>(p.w, p.Co, p.Ktot, p.TT >> 4, rows, store);
 }
 
 // the first convolution: one thread per (position, eight output channels), the k taps as an fmaf chain on the bias in tap order
@@ -276,18 +291,20 @@ struct SnConvTr {
   const u16* w;       // [r * Co, 2C]: row p * Co + o = [W[:, o, p] | W[:, o, p + r]]
   const float* bias;  // [Co]
   u16* y;             // [B, L * r, Co]
-  int L, C, Co, r, left, TT, N;
+  int L, C, Co, r, left, TT, N, Ktot;
 };
 
 // The non-causal SConvTranspose1d with k = 2 r as ONE product over rows j = 0 .. L: the operand row is [a_j | a_{j-1}] (a = ELU(x),
 // a_{-1} = a_L = 0), its N = r * Co results are the contiguous run of r output positions from trimmed position j * r - left on.  A
 // workgroup owns TT consecutive rows j of one batch row: positions j0 - 1 .. j0 + TT - 1 sit in the LDS (LDS row m holds position
-// j0 - 1 + m), and row m of the A operand reads LDS row m + 1 for its first C columns and LDS row m for the other C, in place.
-// Work items as in seanet_conv_kernel; every output element is written by exactly one lane of one workgroup.
+// j0 - 1 + m), and row m of the A operand reads LDS row m + 1 for its first C columns and LDS row m for the other C, in place (C is
+// a multiple of 16: the eight columns lie in one of the two halves).  Column n is phase n / Co of channel
+// n % Co; row 0 drops its phases below `left`, row L keeps only those: every output element is written by exactly one lane of one
+// workgroup.
 template <int MG>
 __global__ __launch_bounds__(256) void seanet_convtr_kernel(SnConvTr p) {
   extern __shared__ __attribute__((aligned(16))) u16 sn_lds[];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const int b = blockIdx.y, j0 = blockIdx.x * p.TT;
   const int ld = p.C + SN_PADH;
   const uint4 zero = make_uint4(0u, 0u, 0u, 0u);
@@ -303,44 +320,19 @@ __global__ __launch_bounds__(256) void seanet_convtr_kernel(SnConvTr p) {
     }
   }
   __syncthreads();
-
-  const int NT = (p.N + 15) >> 4, MT = p.TT >> 4, items = NT * (MT / MG);
-  const int fr = lane & 15, g = lane >> 4;
-  const int K = 2 * p.C, ksteps = K >> 5;  // C is a multiple of 16
+  auto rows = [&](int kk, const u16*& base, int& ldr) __attribute__((always_inline)) {
+    base = kk < p.C ? sn_lds + ld + kk : sn_lds + (kk - p.C), ldr = ld;
+  };
   const long Lout = (long)p.L * p.r;
-  for (int it = wave; it < items; it += 4) {
-    const int nt = it % NT, mg = it / NT;
-    const int n = nt * 16 + fr;
-    const u16* wrow = p.w + (long)(n < p.N ? n : p.N - 1) * K;  // a column past N is computed and not stored
-    f32x4 acc[MG];
-#pragma unroll
-    for (int i = 0; i < MG; i++) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-    for (int ks = 0; ks < ksteps; ks++) {
-      const int kk = ks * 32 + g * 8;  // the eight columns lie in one of the two halves
-      const f16x8 bf = *reinterpret_cast<const f16x8*>(wrow + kk);
-      const u16* base = kk < p.C ? sn_lds + ld + kk : sn_lds + (kk - p.C);
-      f16x8 af[MG];
-#pragma unroll
-      for (int i = 0; i < MG; i++) af[i] = *reinterpret_cast<const f16x8*>(base + ((mg * MG + i) * 16 + fr) * ld);
-#pragma unroll
-      for (int i = 0; i < MG; i++) acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[i], bf, acc[i], 0, 0, 0);
-    }
-    if (n < p.N) {
-      const int ph = n / p.Co;
-      const float bv = p.bias[n - ph * p.Co];
-#pragma unroll
-      for (int i = 0; i < MG; i++) {
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-          const int j = j0 + (mg * MG + i) * 16 + g * 4 + q;
-          if (j > p.L) continue;
-          const long t = (long)j * p.r + ph - p.left;  // row 0 drops its phases below `left`, row L keeps only those
-          if (t < 0 || t >= Lout) continue;
-          p.y[((long)b * Lout + t) * p.Co + (n - ph * p.Co)] = f32_to_f16(acc[i][q] + bv);
-        }
-      }
-    }
-  }
+  auto store = [&](int n) __attribute__((always_inline)) {
+    const int ph = n / p.Co, o = n - ph * p.Co;
+    return [&, ph, o, bv = p.bias[o]](int m, float v) __attribute__((always_inline)) {
+      const int j = j0 + m;
+      const long t = (long)j * p.r + (ph - p.left);
+      if (j <= p.L && t >= 0 && t < Lout) p.y[((long)b * Lout + t) * p.Co + o] = f32_to_f16(v + bv);
+    };
+  };
+  sn_tile_product<MG, false>(p.w, p.N, p.Ktot, p.TT >> 4, rows, store);
 }
 
 // the last convolution, nf -> 1: one thread per output sample, the k * nf products as ONE fmaf chain on the bias, tap-major then
@@ -394,30 +386,6 @@ int sn_convtr_check(int C, int stride) {
   return 0;
 }
 
-size_t sn_convtr_lds(int TT, int C) { return (size_t)(TT + 1) * (C + SN_PADH) * sizeof(u16); }
-
-int sn_convtr_tile(int C) {
-  for (int TT = 128; TT >= 16; TT >>= 1)
-    if (sn_convtr_lds(TT, C) <= (size_t)(TT > 16 ? SN_LDS_PREF : SN_LDS_MAX)) return TT;
-  return 0;
-}
-
-template <int MG>
-int sn_convtr_launch(const SnConvTr& p, int B, size_t bytes, hipStream_t st) {
-  static std::atomic<unsigned long long> allowed{0};  // as sn_conv_launch: more than 64 KiB of dynamic LDS, once per device
-  int dev = 0;
-  VBX_REQUIRE(hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64, "vbx_seanet_convtr: no current device");
-  if (!(allowed.load(std::memory_order_acquire) >> dev & 1)) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(seanet_convtr_kernel<MG>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       SN_LDS_MAX);
-    VBX_REQUIRE(e == hipSuccess, "vbx_seanet_convtr: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-    allowed.fetch_or(1ull << dev, std::memory_order_release);
-  }
-  hipLaunchKernelGGL(seanet_convtr_kernel<MG>, dim3(cdiv(p.L + 1, p.TT), B), dim3(256), bytes, st, p);
-  VBX_LAUNCH_CHECK();
-  return 0;
-}
-
 int sn_conv_check(int C1, int C2, int k, int stride, int dil) {
   VBX_REQUIRE(C1 >= 8 && C1 % 8 == 0 && C1 <= SN_MAX_C, "vbx_seanet_conv: C1 must be a multiple of 8 in 8 .. %d (got %d)", SN_MAX_C, C1);
   VBX_REQUIRE(C2 >= 0 && C2 % 8 == 0 && C2 <= SN_MAX_C, "vbx_seanet_conv: C2 must be 0 or a multiple of 8 up to %d (got %d)", SN_MAX_C, C2);
@@ -428,32 +396,56 @@ int sn_conv_check(int C1, int C2, int k, int stride, int dil) {
   return 0;
 }
 
+size_t sn_convtr_lds(int TT, int C) { return (size_t)(TT + 1) * (C + SN_PADH) * sizeof(u16); }
+
 size_t sn_conv_lds(int TT, int C1, int C2, int k, int stride, int dil) {
   const size_t span = (size_t)(TT - 1) * stride + (k - 1) * dil + 1;
   return (span * (C1 + SN_PADH) + (C2 ? (size_t)TT * (C2 + SN_PADH) : 0)) * sizeof(u16);
 }
 
-int sn_conv_tile(int C1, int C2, int k, int stride, int dil) {
+// the largest tile of 128 .. 32 rows that leaves room for a second workgroup on the CU, else 16 rows in the whole LDS; 0: none fits
+template <class F>
+int sn_pick_tile(F bytes_for_tile) {
   for (int TT = 128; TT >= 16; TT >>= 1)
-    if (sn_conv_lds(TT, C1, C2, k, stride, dil) <= (size_t)(TT > 16 ? SN_LDS_PREF : SN_LDS_MAX)) return TT;
+    if (bytes_for_tile(TT) <= (size_t)(TT > 16 ? SN_LDS_PREF : SN_LDS_MAX)) return TT;
   return 0;
 }
 
-template <int MG>
-int sn_conv_launch(const SnConv& p, int B, size_t bytes, hipStream_t st) {
-  // more than 64 KiB of dynamic LDS has to be allowed once per device; a repeated call from a second thread is harmless
+int sn_conv_tile(int C1, int C2, int k, int stride, int dil) {
+  return sn_pick_tile([=](int TT) { return sn_conv_lds(TT, C1, C2, k, stride, dil); });
+}
+
+int sn_convtr_tile(int C) {
+  return sn_pick_tile([=](int TT) { return sn_convtr_lds(TT, C); });
+}
+
+// row blocks per work item (NT column blocks, MT row blocks in the tile): as many as divide the tile while every wave still gets an item
+int sn_blocks_per_item(int NT, int MT) { return (MT % 4 == 0 && NT * MT / 4 >= 4) ? 4 : ((MT % 2 == 0 && NT * MT / 2 >= 4) ? 2 : 1); }
+
+// one launch of a tiled kernel.  More than 64 KiB of dynamic LDS has to be allowed once per kernel and device; a repeated call from
+// a second thread is harmless.
+template <auto Kernel, class P>
+int sn_launch(const char* who, const P& p, int blocks, int B, size_t bytes, hipStream_t st) {
   static std::atomic<unsigned long long> allowed{0};
   int dev = 0;
-  VBX_REQUIRE(hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64, "vbx_seanet_conv: no current device");
+  VBX_REQUIRE(hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64, "%s: no current device", who);
   if (!(allowed.load(std::memory_order_acquire) >> dev & 1)) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(seanet_conv_kernel<MG>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       SN_LDS_MAX);
-    VBX_REQUIRE(e == hipSuccess, "vbx_seanet_conv: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, SN_LDS_MAX);
+    VBX_REQUIRE(e == hipSuccess, "%s: hipFuncSetAttribute failed: %s", who, hipGetErrorString(e));
     allowed.fetch_or(1ull << dev, std::memory_order_release);
   }
-  hipLaunchKernelGGL(seanet_conv_kernel<MG>, dim3(cdiv(p.Lout, p.TT), B), dim3(256), bytes, st, p);
+  hipLaunchKernelGGL(Kernel, dim3(blocks, B), dim3(256), bytes, st, p);
   VBX_LAUNCH_CHECK();
   return 0;
+}
+
+// SConv1d's padding: (k_eff - stride) split with the larger half on the left, `extra` on the right so that the last window is whole;
+// Lz is the length pad1d reflects about (sn_src)
+struct SnPads { int left, Lz; };
+SnPads sn_pads(int k, int stride, int dil, int L, int Lout) {
+  const int total = (k - 1) * dil + 1 - stride, extra = Lout * stride - L;
+  const int right = total / 2, left = total - right, maxpad = left > right + extra ? left : right + extra;
+  return SnPads{left, L > maxpad ? L : maxpad + 1};
 }
 
 int sn_lstm_check(const SnLstm& p) {
@@ -488,18 +480,15 @@ extern "C" int vbx_seanet_conv(const void* x1_f16, const void* x2_f16, const voi
   SnConv p;
   p.x1 = (const u16*)x1_f16, p.x2 = C2 ? (const u16*)x2_f16 : nullptr, p.w = (const u16*)w_f16, p.bias = bias, p.y = y;
   p.L = L, p.Lout = cdiv(L, stride), p.C1 = C1, p.C2 = C2, p.Co = Co, p.k = k, p.stride = stride, p.dil = dilation;
-  const int keff = (k - 1) * dilation + 1, total = keff - stride, extra = p.Lout * stride - L;
-  const int right = total / 2, left = total - right, maxpad = left > right + extra ? left : right + extra;
-  p.pad_left = left, p.Lz = L > maxpad ? L : maxpad + 1;
+  const SnPads pads = sn_pads(k, stride, dilation, L, p.Lout);
+  p.pad_left = pads.left, p.Lz = pads.Lz;
   p.elu1 = elu1 ? 1 : 0, p.out_f32 = out_f32 ? 1 : 0, p.TT = TT, p.Ktot = k * C1 + C2;
   VBX_REQUIRE((long)L * stride < (1L << 30), "vbx_seanet_conv: row too long");
   const size_t bytes = sn_conv_lds(TT, C1, C2, k, stride, dilation);
-  const int NT = (Co + 15) / 16, MT = TT / 16;
-  // position blocks per work item: as many as divide the tile while every wave still gets an item
-  const int MG = (MT % 4 == 0 && NT * MT / 4 >= 4) ? 4 : ((MT % 2 == 0 && NT * MT / 2 >= 4) ? 2 : 1);
-  if (MG == 4) return sn_conv_launch<4>(p, B, bytes, (hipStream_t)stream);
-  if (MG == 2) return sn_conv_launch<2>(p, B, bytes, (hipStream_t)stream);
-  return sn_conv_launch<1>(p, B, bytes, (hipStream_t)stream);
+  const int MG = sn_blocks_per_item((Co + 15) / 16, TT / 16), blocks = cdiv(p.Lout, TT);
+  if (MG == 4) return sn_launch<seanet_conv_kernel<4>>("vbx_seanet_conv", p, blocks, B, bytes, (hipStream_t)stream);
+  if (MG == 2) return sn_launch<seanet_conv_kernel<2>>("vbx_seanet_conv", p, blocks, B, bytes, (hipStream_t)stream);
+  return sn_launch<seanet_conv_kernel<1>>("vbx_seanet_conv", p, blocks, B, bytes, (hipStream_t)stream);
 }
 
 extern "C" int vbx_seanet_conv0(const float* wave, const float* w, const float* bias, void* y_f16, int B, int T, int nf, int k,
@@ -508,9 +497,9 @@ extern "C" int vbx_seanet_conv0(const float* wave, const float* w, const float* 
   VBX_REQUIRE(nf >= 8 && nf % 8 == 0 && nf <= 64, "vbx_seanet_conv0: n_filters must be a multiple of 8 up to 64 (got %d)", nf);
   VBX_REQUIRE(k >= 1 && k <= SN_MAX_K && (k & 1), "vbx_seanet_conv0: kernel_size must be odd, at most %d (got %d)", SN_MAX_K - 1, k);
   VBX_REQUIRE((long)T * (nf / 8) < (1L << 31) * 256, "vbx_seanet_conv0: row too long");
-  const int right = (k - 1) / 2, left = k - 1 - right, maxpad = left > right ? left : right;
+  const SnPads pads = sn_pads(k, 1, 1, T, T);
   hipLaunchKernelGGL(seanet_conv0_kernel, dim3(cdiv((long)T * (nf / 8), 256), B), dim3(256), 0, (hipStream_t)stream, wave, w, bias,
-                     (u16*)y_f16, T, nf, k, left, T > maxpad ? T : maxpad + 1);
+                     (u16*)y_f16, T, nf, k, pads.left, pads.Lz);
   VBX_LAUNCH_CHECK();
   return 0;
 }
@@ -567,13 +556,12 @@ extern "C" int vbx_seanet_convtr(const void* x_f16, const void* w_f16, const flo
   while (TT > 16 && TT / 2 >= L + 1) TT >>= 1;  // a short row: L + 1 product rows
   SnConvTr p;
   p.x = (const u16*)x_f16, p.w = (const u16*)w_f16, p.bias = bias, p.y = (u16*)y_f16;
-  p.L = L, p.C = C, p.Co = C / 2, p.r = stride, p.left = stride - stride / 2, p.TT = TT, p.N = stride * (C / 2);
+  p.L = L, p.C = C, p.Co = C / 2, p.r = stride, p.left = stride - stride / 2, p.TT = TT, p.N = stride * (C / 2), p.Ktot = 2 * C;
   const size_t bytes = sn_convtr_lds(TT, C);
-  const int NT = (p.N + 15) / 16, MT = TT / 16;
-  const int MG = (MT % 4 == 0 && NT * MT / 4 >= 4) ? 4 : ((MT % 2 == 0 && NT * MT / 2 >= 4) ? 2 : 1);
-  if (MG == 4) return sn_convtr_launch<4>(p, B, bytes, (hipStream_t)stream);
-  if (MG == 2) return sn_convtr_launch<2>(p, B, bytes, (hipStream_t)stream);
-  return sn_convtr_launch<1>(p, B, bytes, (hipStream_t)stream);
+  const int MG = sn_blocks_per_item((p.N + 15) / 16, TT / 16), blocks = cdiv(L + 1, TT);
+  if (MG == 4) return sn_launch<seanet_convtr_kernel<4>>("vbx_seanet_convtr", p, blocks, B, bytes, (hipStream_t)stream);
+  if (MG == 2) return sn_launch<seanet_convtr_kernel<2>>("vbx_seanet_convtr", p, blocks, B, bytes, (hipStream_t)stream);
+  return sn_launch<seanet_convtr_kernel<1>>("vbx_seanet_convtr", p, blocks, B, bytes, (hipStream_t)stream);
 }
 
 extern "C" int vbx_seanet_conv_out(const void* x_f16, const float* w, const float* bias, float* y, int B, int T, int nf, int k,
@@ -582,9 +570,9 @@ extern "C" int vbx_seanet_conv_out(const void* x_f16, const float* w, const floa
   VBX_REQUIRE(nf >= 8 && nf % 8 == 0 && nf <= 64, "vbx_seanet_conv_out: n_filters must be a multiple of 8 up to 64 (got %d)", nf);
   VBX_REQUIRE(k >= 1 && k <= 7 && (k & 1), "vbx_seanet_conv_out: last_kernel_size must be odd, at most 7 (got %d)", k);
   VBX_REQUIRE(T < (1 << 30), "vbx_seanet_conv_out: row too long");
-  const int right = (k - 1) / 2, left = k - 1 - right, maxpad = left > right ? left : right;
+  const SnPads pads = sn_pads(k, 1, 1, T, T);
   hipLaunchKernelGGL(seanet_conv_out_kernel, dim3(cdiv(T, 256), B), dim3(256), 0, (hipStream_t)stream, (const u16*)x_f16, w, bias, y, T, nf,
-                     k, left, T > maxpad ? T : maxpad + 1);
+                     k, pads.left, pads.Lz);
   VBX_LAUNCH_CHECK();
   return 0;
 }

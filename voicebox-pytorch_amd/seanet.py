@@ -29,6 +29,7 @@ import torch
 from torch import nn
 
 from . import _lib
+from ._packing import PackedWeights, read_checkpoint
 
 _PARAM = "parametrizations.weight.original"
 
@@ -173,7 +174,7 @@ def _check_keywords(who, channels, dimension, n_filters, n_residual_layers, rati
     return no
 
 
-class _SEANet(nn.Module):
+class _SEANet(PackedWeights, nn.Module):
     """what SEANetEncoder and SEANetDecoder share: the state-dict layouts, the once-per-version operand packing, the launches of the
     convolution kernel and of the LSTM"""
 
@@ -222,17 +223,14 @@ class _SEANet(nn.Module):
     @classmethod
     def from_checkpoint(cls, path):
         """A LOCAL file written by torch.save: an EnCodec (or one half's) state dict or {'state_dict': ...}; see from_state_dict."""
-        from .vocos import read_checkpoint
-
         return cls.from_state_dict(read_checkpoint(path))
 
     # -- operand copies
-    def _weights_key(self):
-        ver = lambda t: 0 if t.is_inference() else t._version  # an inference tensor has no counter and cannot be written in place
-        return tuple((t.data_ptr(), ver(t)) for t in self.parameters())
-
-    def mark_weights_dirty(self):
-        self._packed_key = None
+    def packed_ops(self):
+        """the launch list: fp16 GEMM operands and fp32 biases as the kernels read them; rebuilt when a parameter's storage or
+        version counter changed (in-place updates, load_state_dict, .to()).  A write through `p.data` changes neither: call
+        mark_weights_dirty() after one."""
+        return self._cached(self._build_ops)
 
     @staticmethod
     def _gemm_weight(w):
@@ -337,7 +335,6 @@ class SEANetEncoder(_SEANet):
         self.model = nn.ModuleList(model)
         self.hidden = d
         self._check_tiles(no)
-        self._packed, self._packed_key = None, None
 
     def frames(self, T):
         for r in reversed(self.ratios):
@@ -371,13 +368,7 @@ class SEANetEncoder(_SEANet):
         self.load_state_dict(sd)
         return self.eval()
 
-    def packed_ops(self):
-        """the launch list: fp16 GEMM operands and fp32 biases as the kernels read them; rebuilt when a parameter's storage or
-        version counter changed (in-place updates, load_state_dict, .to()).  A write through `p.data` changes neither: call
-        mark_weights_dirty() after one."""
-        key = self._weights_key()
-        if key == self._packed_key:
-            return self._packed
+    def _build_ops(self):
         f = lambda t: t.detach().float().contiguous()
         first = self.model[0]
         ops = [dict(op="conv0", w=f(first.inner.folded()[:, 0, :]), b=f(first.inner.bias), nf=first.cout, k=first.k)]
@@ -394,7 +385,6 @@ class SEANetEncoder(_SEANet):
             else:
                 ops.append(self._conv_op(m, elu, out_f32=m is self.model[-1]))
                 elu = False
-        self._packed, self._packed_key = ops, key
         return ops
 
     def forward(self, audio):
@@ -489,7 +479,6 @@ class SEANetDecoder(_SEANet):
         model += [nn.ELU(), _SConv(d, channels, last_kernel_size, norm)]
         self.model = nn.ModuleList(model)
         self._check_tiles(no)
-        self._packed, self._packed_key = None, None
 
     @classmethod
     def from_state_dict(cls, sd):
@@ -523,11 +512,7 @@ class SEANetDecoder(_SEANet):
         t = w.permute(2, 1, 0)  # [2r, Co, C]
         return torch.cat([t[:r].reshape(-1, w.shape[0]), t[r:].reshape(-1, w.shape[0])], dim=1)
 
-    def packed_ops(self):
-        """the launch list, as SEANetEncoder.packed_ops: rebuilt when a parameter's storage or version counter changed"""
-        key = self._weights_key()
-        if key == self._packed_key:
-            return self._packed
+    def _build_ops(self):
         f = lambda t: t.detach().float().contiguous()
         ops, last = [self._conv_op(self.model[0], False)], self.model[-1]
         for m in list(self.model)[1:-1]:
@@ -539,7 +524,6 @@ class SEANetDecoder(_SEANet):
             elif isinstance(m, _Resnet):
                 ops += self._resnet_ops(m)
         ops.append(dict(op="conv_out", w=f(last.inner.folded()[0].t()), b=f(last.inner.bias), nf=last.cin, k=last.k))  # fp32 [k, nf]
-        self._packed, self._packed_key = ops, key
         return ops
 
     def forward(self, z):

@@ -18,15 +18,10 @@ import torch
 from torch import nn
 
 from . import _lib
+from ._packing import PackedWeights, read_checkpoint, tensors_key  # read_checkpoint: importable from here as before
 from .codec import _check_stft_args, _stft_tables, ola_reciprocal_envelope
 
 LN_EPS = 1e-6
-
-
-def read_checkpoint(path):
-    """the state dict of a LOCAL torch.save file: the dict itself or its 'state_dict' entry"""
-    sd = torch.load(path, map_location="cpu", weights_only=True)
-    return sd["state_dict"] if isinstance(sd, dict) and "state_dict" in sd else sd
 
 
 class _ConvNeXtBlock(nn.Module):
@@ -61,7 +56,7 @@ class _Head(nn.Module):
         self.istft = _ISTFT(n_fft)
 
 
-class VocosDecoder(nn.Module):
+class VocosDecoder(PackedWeights, nn.Module):
     """features [B, input_channels, frames] -> wave fp32 [B, (frames - 1) * hop_length].  forward = decode = Vocos.decode: the
     features are taken as given unless input_log, which applies log(clamp(x, min=1e-7)) first -- what Vocos's own mel feature
     extractor feeds its backbone (the published vocos-mel-24khz weights expect it, at hop_length 256).
@@ -96,7 +91,6 @@ class VocosDecoder(nn.Module):
             if isinstance(m, (nn.Conv1d, nn.Linear)):
                 nn.init.trunc_normal_(m.weight, std=0.02)
                 nn.init.zeros_(m.bias)
-        self._packed, self._packed_key = None, None
         self._tables, self._tables_key = None, None
 
     # -- state
@@ -142,17 +136,8 @@ class VocosDecoder(nn.Module):
         return self.eval()
 
     # -- operand copies
-    def _weights_key(self):
-        ver = lambda t: 0 if t.is_inference() else t._version  # an inference tensor has no counter and cannot be written in place
-        return tuple((t.data_ptr(), ver(t)) for t in self.parameters())
-
     def _pack(self):
-        """fp16 GEMM operands and fp32 vectors as the launch sequence reads them; rebuilt when a parameter's storage or version
-        counter changed (in-place updates, load_state_dict, .to()).  A write through `p.data` changes neither: call
-        mark_weights_dirty() after one."""
-        key = self._weights_key()
-        if key == self._packed_key:
-            return self._packed
+        """fp16 GEMM operands and fp32 vectors as the launch sequence reads them; kept per parameter version (PackedWeights)"""
         bb, C, D = self.backbone, self.input_channels, self.dim
         f = lambda t: t.detach().float().contiguous()
         Kp = _lib.lib().vbx_vocos_kp(C)
@@ -172,19 +157,14 @@ class VocosDecoder(nn.Module):
                 cb=f(blk.dwconv.bias), lnw=f(blk.norm.weight), lnb=f(blk.norm.bias),
                 w1=blk.pwconv1.weight.detach().float().half().contiguous(), b1=f(blk.pwconv1.bias),
                 w2=(g[:, None] * blk.pwconv2.weight.detach().float()).half().contiguous(), b2=(g * blk.pwconv2.bias.detach().float()).contiguous()))
-        self._packed = dict(Kp=Kp, nhp=nhp, emb=emb.half(), emb_b=f(bb.embed.bias), n0w=f(bb.norm.weight), n0b=f(bb.norm.bias), layers=layers,
-                            flw=f(bb.final_layer_norm.weight), flb=f(bb.final_layer_norm.bias), hw=hw.half(), hb=hb)
-        self._packed_key = key
-        return self._packed
-
-    def mark_weights_dirty(self):
-        self._packed_key = None
+        return dict(Kp=Kp, nhp=nhp, emb=emb.half(), emb_b=f(bb.embed.bias), n0w=f(bb.norm.weight), n0b=f(bb.norm.bias), layers=layers,
+                    flw=f(bb.final_layer_norm.weight), flb=f(bb.final_layer_norm.bias), hw=hw.half(), hb=hb)
 
     def _istft_tables(self, frames, device):
         """window, twiddles and the reciprocal window-square envelope of the kept range, from the `head.istft.window` buffer
         (ValueError where it and hop_length violate NOLA, as torch.istft)"""
         win = self.head.istft.window
-        key = (frames, str(device), win.data_ptr(), 0 if win.is_inference() else win._version)
+        key = (frames, str(device), tensors_key((win,)))
         if key != self._tables_key:
             win = win.detach().double().cpu()
             renv = ola_reciprocal_envelope(self.n_fft, self.n_fft, self.hop_length, frames, window=win)
@@ -224,7 +204,7 @@ class VocosDecoder(nn.Module):
         B, C, frames = features.shape
         n_fft, hop, D, I, dev = self.n_fft, self.hop_length, self.dim, self.intermediate_dim, features.device
         window, tw_re, tw_im, renv = tables
-        w = self._pack()
+        w = self._cached(self._pack)
         st = _lib.current_stream()
         M, Kp, nhp, nb = B * frames, w["Kp"], w["nhp"], n_fft // 2 + 1
         x = features.detach().to(torch.float32).contiguous()
