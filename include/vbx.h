@@ -301,6 +301,20 @@ int vbx_griffinlim(const float* mag, float* spec_a, float* spec_b, float* fb, fl
  *   as vbx_griffinlim.  Two launches, the same bits on every run. */
 int vbx_istft(const float* mag, const float* spec, float* fb, float* wave, const float* window, const float* tw_re, const float* tw_im,
               const float* renv, int B, int frames, int n_fft, int win, int hop, void* stream);
+/* vbx_istft_trim: the same two launches with any trim (Vocos's ISTFT at padding = "same"; the center trim gives vbx_istft's bits).
+ *   The frames' windowed inverse transforms add up to (frames - 1) * hop + n_fft samples, frame g starting at g * hop; wave
+ *   [B, out_len] is samples [trim, trim + out_len) of that sum, each times renv [out_len], summed over the covering frames in
+ *   ascending frame order (no atomics, the same bits on every run).  "same": trim = (win - hop) / 2, out_len = (frames - 1) * hop +
+ *   win - 2 trim;  "center": trim = n_fft / 2, out_len = (frames - 1) * hop.  frames >= 1, trim >= 0, out_len >= 1, trim + out_len
+ *   within the sum.
+ * Sizes of the two inverse-only entries: n_fft a power of two in 256 .. 2048, OR 5 * 2^m = 320, 640, 1280 (a mixed-radix transform,
+ *   csrc/fft_lds.hpp: radix-2 stages, one radix-5 pass).  The tables are the SAME at every size: tw_re / tw_im [n_fft / 2] =
+ *   cos / -sin(2 pi k / n_fft); the radix-5 pass reaches the upper half of the circle through W^(j + n_fft / 2) = -W^j, no full
+ *   table is passed.  1 / n_fft is applied in fp32 with the window (exact at a power of two, two roundings more otherwise).
+ *   vbx_logmel and vbx_griffinlim (forward transforms) refuse 320 / 640 / 1280. */
+int vbx_istft_trim(const float* mag, const float* spec, float* fb, float* wave, const float* window, const float* tw_re,
+                   const float* tw_im, const float* renv, int B, int frames, int n_fft, int win, int hop, int trim, long out_len,
+                   void* stream);
 /* Vocos decoder (voicebox_pytorch_amd.VocosDecoder; csrc/vocos.hip): the kernels around the GEMMs of a ConvNeXt backbone + ISTFT head.
  * vbx_vocos_kp: Kp = 7 * C rounded up to a multiple of 32, the K of the embedding GEMM.
  * vbx_vocos_pack_input: features x fp32 [B, C, frames] -> the im2col operand of the 7-tap input convolution, fp16 [B * frames, Kp]:

@@ -4,7 +4,8 @@ Public API mirrors the reference package (voicebox_pytorch/__init__.py:1-15) for
 VoiceBox, ConditionalFlowMatcherWrapper, Transformer, Attend, DurationPredictor (inference), VoiceBoxTrainer (latents or waves),
 AudioEncoderDecoder / LogMelCodec (the codec interface, the log-mel encoder and its vocoder-free decode), griffin_lim (Griffin-Lim
 phase recovery on the device), resample / Resample (sample-rate conversion on the device, in front of a codec), VocosDecoder (the
-Vocos neural vocoder's decoder on the device; weights are the user's, from a local checkpoint), ResidualVQ / EncodecVocoCodec
+Vocos neural vocoder's decoder on the device; weights are the user's, from a local checkpoint), VocosEncodecDecoder (its
+EnCodec-conditioned variant as published: AdaLayerNorm tables, n_fft 1280, padding="same"), ResidualVQ / EncodecVocoCodec
 (EnCodec's residual vector quantizer on the device and the reference's EncodecVoco around it: codes in and out), SEANetEncoder
 (EnCodec's encoder on the device: waves into that codec; weights are the user's, from a local checkpoint), SEANetDecoder (EnCodec's
 decoder on the device: that codec's latents back into waves, from the same local checkpoint), maximum_path / forward_sum_loss /
@@ -19,14 +20,14 @@ try:  # model classes need torch; keep `_lib` importable on its own
     from .trainer import VoiceBoxTrainer  # noqa: F401
     from .duration import DurationPredictor  # noqa: F401
     from .codec import AudioEncoderDecoder, LogMelCodec, griffin_lim, resample, Resample, ResidualVQ, EncodecVocoCodec  # noqa: F401
-    from .vocos import VocosDecoder  # noqa: F401
+    from .vocos import VocosDecoder, VocosEncodecDecoder  # noqa: F401
     from .seanet import SEANetDecoder, SEANetEncoder  # noqa: F401
     from .align import maximum_path, forward_sum_loss, ForwardSumLoss  # noqa: F401
     from .engine import precise_mode, set_precise, precise_enabled  # noqa: F401
 
     __all__ += ["VoiceBox", "ConditionalFlowMatcherWrapper", "Transformer", "Attend", "VoiceBoxTrainer", "DurationPredictor", "mask_from_frac_lengths",
                 "mask_from_start_end_indices", "prob_mask_like", "reduce_masks_with_and", "precise_mode", "set_precise", "precise_enabled",
-                "AudioEncoderDecoder", "LogMelCodec", "griffin_lim", "resample", "Resample", "VocosDecoder", "ResidualVQ", "EncodecVocoCodec", "SEANetEncoder", "SEANetDecoder",
+                "AudioEncoderDecoder", "LogMelCodec", "griffin_lim", "resample", "Resample", "VocosDecoder", "VocosEncodecDecoder", "ResidualVQ", "EncodecVocoCodec", "SEANetEncoder", "SEANetDecoder",
                 "maximum_path", "forward_sum_loss", "ForwardSumLoss"]
 except ModuleNotFoundError as _e:  # pragma: no cover - only while the package is being bootstrapped
     if "masks" not in str(_e) and "model" not in str(_e):

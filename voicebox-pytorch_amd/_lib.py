@@ -73,6 +73,7 @@ _PROTOS = {
     "vbx_griffinlim_lds_bytes": [I, I, I],
     "vbx_griffinlim": [P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, F, P],
     "vbx_istft": [P, P, P, P, P, P, P, P, I, I, I, I, I, P],
+    "vbx_istft_trim": [P, P, P, P, P, P, P, P, I, I, I, I, I, I, L, P],
     "vbx_vocos_kp": [I],
     "vbx_vocos_pack_input": [P, P, I, I, I, I, P],
     "vbx_vocos_dwconv_ln": [P, P, P, P, P, P, I, I, I, F, P],

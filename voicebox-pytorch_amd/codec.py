@@ -78,6 +78,14 @@ def _check_stft_args(n_fft, win_length, hop_length):
         raise ValueError("need 0 < win_length <= n_fft, hop_length > 0")
 
 
+def _check_istft_args(n_fft, win_length, hop_length):
+    """what the inverse-only entries (vbx_istft, vbx_istft_trim) serve: the sizes above and 5 * 2^m = 320, 640, 1280"""
+    if n_fft not in (320, 640, 1280) and (n_fft & (n_fft - 1) or not 256 <= n_fft <= 2048):
+        raise NotImplementedError(f"n_fft must be a power of two in 256 .. 2048 or one of 320, 640, 1280 (got {n_fft})")
+    if not 0 < win_length <= n_fft or hop_length <= 0:
+        raise ValueError("need 0 < win_length <= n_fft, hop_length > 0")
+
+
 def _stft_tables(n_fft, win_length):
     """fp64: the periodic Hann window of win_length samples centred in n_fft (torch.stft's placement), cos / -sin(2 pi k / n_fft)"""
     win = torch.zeros(n_fft, dtype=torch.float64)
@@ -99,6 +107,23 @@ def ola_reciprocal_envelope(n_fft, win_length, hop_length, frames, window=None):
     if env.numel() == 0 or float(env.min()) <= 1e-11:
         raise ValueError(f"window overlap-add envelope is zero somewhere (NOLA): win_length {win_length}, hop_length {hop_length}, "
                          f"n_fft {n_fft}, {frames} frames")
+    return 1.0 / env
+
+
+def ola_reciprocal_envelope_trim(n_fft, hop_length, frames, window, trim, out_len):
+    """1 / (window-square envelope) on [trim, trim + out_len) of the (frames - 1) * hop + n_fft overlap-added samples, fp64: Vocos's
+    ISTFT at padding="same" keeps trim = (win_length - hop) // 2 from each end.  `window` [n_fft].  Raises ValueError where Vocos
+    asserts: an envelope <= 1e-11 on the kept range (NOLA)."""
+    w2 = window.double() ** 2
+    env = torch.zeros(n_fft + (frames - 1) * hop_length, dtype=torch.float64)
+    for f in range(frames):
+        env[f * hop_length:f * hop_length + n_fft] += w2
+    if trim < 0 or out_len < 1 or trim + out_len > env.numel():
+        raise ValueError(f"the kept range [{trim}, {trim + out_len}) is not inside the {env.numel()} overlap-added samples")
+    env = env[trim:trim + out_len]
+    if float(env.min()) <= 1e-11:
+        raise ValueError(f"window overlap-add envelope is zero somewhere on the kept range (NOLA): hop_length {hop_length}, n_fft {n_fft}, "
+                         f"{frames} frames, {trim} samples trimmed")
     return 1.0 / env
 
 
@@ -504,7 +529,7 @@ class ResidualVQ(PackedWeights, nn.Module):
 
 class EncodecVocoCodec(AudioEncoderDecoder):
     """The reference's EncodecVoco (voicebox_pytorch.py:551-592) on the device: EnCodec's residual vector quantizer (ResidualVQ) and
-    a Vocos decoder (VocosDecoder) conditioned on EnCodec features.  Latents are the summed codewords [B, frames, rvq.dim].
+    a Vocos decoder (VocosDecoder, or VocosEncodecDecoder: the published head) conditioned on EnCodec features.  Latents are the summed codewords [B, frames, rvq.dim].
 
       decode_to_codes(latents) -> codes int64 [B, Q, frames]        the RVQ search
       codes_to_latents(codes)  -> latents [B, frames, dim]          EncodecWrapper's get_emb_from_indices
@@ -539,13 +564,19 @@ class EncodecVocoCodec(AudioEncoderDecoder):
         return self._sampling_rate
 
     @classmethod
-    def from_vocos_checkpoint(cls, path, *, bandwidth_id=2, encoder=None, codebook_size=1024, hop_length=None, sampling_rate=24000):
+    def from_vocos_checkpoint(cls, path, *, bandwidth_id=2, encoder=None, codebook_size=1024, hop_length=None, sampling_rate=24000,
+                              padding="center"):
         """A LOCAL Vocos-EnCodec state dict (torch.save of the dict, or {'state_dict': ...}): `feature_extractor.codebook_weights`
         [Q' * codebook_size, dim] becomes the codebooks, of which bandwidth ids 0 .. 3 use the first 2, 4, 8, 16 (capped by what
-        the table holds); the vocoder is built as VocosDecoder.from_checkpoint(path, bandwidth_id=bandwidth_id) builds it, and its
-        limits apply: the one published Vocos-EnCodec model (n_fft 1280, padding="same") is outside them and raises
-        NotImplementedError, so this loader has only been exercised on synthetic files of that layout."""
-        from .vocos import VocosDecoder
+        the table holds).  padding="center" (the default): the vocoder is built as VocosDecoder.from_checkpoint(path,
+        bandwidth_id=bandwidth_id) builds it, folded to that one id, (frames - 1) * hop samples.  padding="same": a
+        VocosEncodecDecoder with the file's AdaLayerNorm tables kept and bandwidth_id as its default id -- for the published
+        `vocos-encodec-24khz` file (n_fft 1280, hop 320) that is the reference's EncodecVoco, and decode returns [B, frames * 320].
+        No such file is part of this package: the loader is exercised on synthetic files of that layout."""
+        from .vocos import VocosDecoder, VocosEncodecDecoder
+
+        if padding not in ("center", "same"):
+            raise ValueError(f'padding must be "center" or "same" (got "{padding}")')
 
         sd = read_checkpoint(path)
         if "feature_extractor.codebook_weights" not in sd:
@@ -559,7 +590,10 @@ class EncodecVocoCodec(AudioEncoderDecoder):
         rvq = ResidualVQ(dim=flat.shape[1], codebook_size=codebook_size,
                          num_quantizers=min(RVQ_BANDWIDTH_QUANTIZERS[bandwidth_id], flat.shape[0] // codebook_size))
         rvq.load_state_dict({"codebook_weights": flat})
-        vocoder = VocosDecoder.from_state_dict(sd, hop_length=hop_length, bandwidth_id=bandwidth_id)
+        if padding == "same":
+            vocoder = VocosEncodecDecoder.from_state_dict(sd, hop_length=hop_length, bandwidth_id=bandwidth_id)
+        else:
+            vocoder = VocosDecoder.from_state_dict(sd, hop_length=hop_length, bandwidth_id=bandwidth_id)
         return cls(rvq=rvq, vocoder=vocoder, encoder=encoder, sampling_rate=sampling_rate, downsample_factor=vocoder.hop_length).eval()
 
     @classmethod

@@ -18,6 +18,10 @@
 // complex-to-real transform ignores them; a random initial phase makes them non-zero); its exact factor 1 / n_fft is applied with
 // the window.  The LDS is sized per launch (n_fft and hop dependent), so the default codec takes 21 KiB a workgroup instead of the
 // 2048-point worst case.
+//
+// gl_synth_kernel<true> is the same synthesis at n_fft = 5 * 2^m (320, 640, 1280: fft_lds.hpp's mixed-radix inverse), a separate
+// instantiation that only vbx_istft / vbx_istft_trim launch; the analysis step, and with it vbx_griffinlim, stays at powers of two.
+// vbx_istft_trim is the overlap-add with any trim (Vocos's padding="same" keeps frames * hop samples).
 #include "fft_lds.hpp"
 
 namespace {
@@ -40,6 +44,8 @@ VBX_DEV float ola_sample(const float* __restrict__ fb, const float* __restrict__
   return s * renv[t];
 }
 
+// R5: n_fft = 5 * 2^log2n (log2n is then m of fft_lds.hpp), else n_fft = 2^log2n
+template <bool R5>
 __global__ __launch_bounds__(256) void gl_synth_kernel(const float2* __restrict__ P, const float2* __restrict__ Q,
                                                        const float* __restrict__ mag, float* __restrict__ fb,
                                                        const float* __restrict__ window, const float* __restrict__ tw_re,
@@ -75,20 +81,21 @@ __global__ __launch_bounds__(256) void gl_synth_kernel(const float2* __restrict_
       }
     }
     if (k == 0 || k == half_n) x[0][1] = x[1][1] = 0.f;
-    const int r = fft_brev(k, log2n);
+    const int r = R5 ? fft_map5(k, log2n) : fft_brev(k, log2n);
     re[r] = x[0][0] - x[1][1];
     im[r] = x[0][1] + x[1][0];
     if (k > 0 && k < half_n) {  // Z[N - k] = conj(X0[k]) + i conj(X1[k])
-      const int r2 = fft_brev(n_fft - k, log2n);
+      const int r2 = R5 ? fft_map5(n_fft - k, log2n) : fft_brev(n_fft - k, log2n);
       re[r2] = x[0][0] + x[1][1];
       im[r2] = x[1][0] - x[0][1];
     }
   }
   __syncthreads();
-  fft_lds<true>(re, im, tw_re, tw_im, log2n, half_n, t);
+  if constexpr (R5) fft_lds5_inverse(re, im, tw_re, tw_im, log2n, n_fft, t);
+  else fft_lds<true>(re, im, tw_re, tw_im, log2n, half_n, t);
   const float inv_n = 1.0f / (float)n_fft;
   for (int j = t; j < win; j += 128) {
-    const float w = window[left + j] * inv_n;  // 1 / n_fft is a power of two: exact
+    const float w = window[left + j] * inv_n;  // 1 / n_fft is a power of two: exact (R5: two more roundings, inv_n's and the product's)
     const int i = fft_skew(left + j);
     const int f = f0 + 2 * c;
     if (f < frames) fb[((long)b * frames + f) * win + j] = re[i] * w;
@@ -150,6 +157,17 @@ __global__ __launch_bounds__(256) void gl_ola_kernel(const float* __restrict__ f
   const long t = (long)blockIdx.x * 256 + threadIdx.x;
   const int b = blockIdx.y;
   if (t < L) wave[(long)b * L + t] = ola_sample(fb + (long)b * frames * win, renv, t, frames, hop, win, left, half_n);
+}
+
+// samples [trim, trim + out_len) of the overlap-add, counted from the first sample of frame 0's n_fft-point transform; a sample before
+// the first window (win < n_fft, trim < left) is zero
+__global__ __launch_bounds__(256) void gl_ola_trim_kernel(const float* __restrict__ fb, float* __restrict__ wave,
+                                                          const float* __restrict__ renv, int frames, int win, int left, int hop,
+                                                          int trim, long out_len) {
+  const long t = (long)blockIdx.x * 256 + threadIdx.x;
+  const int b = blockIdx.y;
+  if (t < out_len)
+    wave[(long)b * out_len + t] = t + trim < left ? 0.f : ola_sample(fb + (long)b * frames * win, renv, t, frames, hop, win, left, trim);
 }
 
 // MM_FRAMES frames of one batch row: dB -> power (in fp64: 10^(x / 10) amplifies the rounding of x / 10 by x ln 10 / 10), the frames'
@@ -221,7 +239,7 @@ extern "C" int vbx_griffinlim(const float* mag, float* spec_a, float* spec_b, fl
   float2* q = (float2*)spec_b;  // T_k = R_{k-1}
   for (int k = 0; k <= n_iter; k++) {
     // k = 0: A_0 as given;  k = 1: T_0 = 0 (whatever finite values q holds are multiplied by m = 0);  k >= 2: the momentum term is live
-    hipLaunchKernelGGL(gl_synth_kernel, grid, block, lds_synth, st, (const float2*)p, (const float2*)q, mag, fb, window, tw_re, tw_im,
+    hipLaunchKernelGGL(gl_synth_kernel<false>, grid, block, lds_synth, st, (const float2*)p, (const float2*)q, mag, fb, window, tw_re, tw_im,
                        k >= 2 ? m : 0.f, k == 0 ? 1 : 0, frames, n_fft, log2n, win, left);
     if (k == n_iter) break;
     hipLaunchKernelGGL(gl_analysis_kernel, grid, block, (size_t)lds, st, (const float*)fb, q, window, tw_re, tw_im, renv, frames, n_fft,
@@ -233,23 +251,55 @@ extern "C" int vbx_griffinlim(const float* mag, float* spec_a, float* spec_b, fl
   return 0;
 }
 
+// the synthesis launch of one inverse STFT: the power-of-two or the mixed-radix instantiation by n_fft (checked by the caller)
+static void istft_synth(const float* mag, const float* spec, float* fb, const float* window, const float* tw_re, const float* tw_im,
+                        int B, int frames, int n_fft, int win, hipStream_t st) {
+  const dim3 grid(cdiv(frames, GL_FRAMES), B), block(256);
+  const size_t lds = sizeof(float) * 4 * fft_ld(n_fft);
+  const int left = (n_fft - win) / 2;
+  if (fft_is_radix5(n_fft))
+    hipLaunchKernelGGL(gl_synth_kernel<true>, grid, block, lds, st, (const float2*)spec, (const float2*)spec, mag, fb, window, tw_re,
+                       tw_im, 0.f, 1, frames, n_fft, fft_log2(n_fft / 5), win, left);
+  else
+    hipLaunchKernelGGL(gl_synth_kernel<false>, grid, block, lds, st, (const float2*)spec, (const float2*)spec, mag, fb, window, tw_re,
+                       tw_im, 0.f, 1, frames, n_fft, fft_log2(n_fft), win, left);
+}
+
 // One inverse STFT (torch.istft, center = True, length = None) of mag * phasor: the synthesis and overlap-add launches above alone,
 // so nothing of the analysis step's reflect padding is demanded -- two frames are enough (csrc/vocos.hip's last step).
 extern "C" int vbx_istft(const float* mag, const float* spec, float* fb, float* wave, const float* window, const float* tw_re,
                          const float* tw_im, const float* renv, int B, int frames, int n_fft, int win, int hop, void* stream) {
   VBX_REQUIRE(mag && spec && fb && wave && window && tw_re && tw_im && renv && B > 0 && B <= 65535, "vbx_istft: bad args");
-  if (int rc = fft_check_size("vbx_istft", n_fft)) return rc;
+  if (int rc = fft_check_size_inverse("vbx_istft", n_fft)) return rc;
   VBX_REQUIRE(win > 0 && win <= n_fft && hop > 0 && hop <= win, "vbx_istft: need 0 < hop <= win_length <= n_fft");
   VBX_REQUIRE(frames > 1 && (long)(frames - 1) * hop + n_fft < 2147483647L, "vbx_istft: need at least two frames");
-  const int log2n = fft_log2(n_fft);
   const int left = (n_fft - win) / 2;
   const long L = (long)(frames - 1) * hop;
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(gl_synth_kernel, dim3(cdiv(frames, GL_FRAMES), B), dim3(256), sizeof(float) * 4 * fft_ld(n_fft), st,
-                     (const float2*)spec, (const float2*)spec, mag, fb, window, tw_re, tw_im, 0.f, 1, frames, n_fft, log2n, win, left);
+  istft_synth(mag, spec, fb, window, tw_re, tw_im, B, frames, n_fft, win, st);
   VBX_LAUNCH_CHECK();
   hipLaunchKernelGGL(gl_ola_kernel, dim3(cdiv(L, 256), B), dim3(256), 0, st, (const float*)fb, wave, renv, frames, win, left, hop,
                      n_fft / 2);
+  VBX_LAUNCH_CHECK();
+  return 0;
+}
+
+// vbx_istft with any trim: wave [B, out_len] = samples [trim, trim + out_len) of the (frames - 1) * hop + n_fft samples the frames'
+// windowed inverse transforms add up to, times renv [out_len].  One frame is enough.  Same summation order as vbx_istft.
+extern "C" int vbx_istft_trim(const float* mag, const float* spec, float* fb, float* wave, const float* window, const float* tw_re,
+                              const float* tw_im, const float* renv, int B, int frames, int n_fft, int win, int hop, int trim,
+                              long out_len, void* stream) {
+  VBX_REQUIRE(mag && spec && fb && wave && window && tw_re && tw_im && renv && B > 0 && B <= 65535, "vbx_istft_trim: bad args");
+  if (int rc = fft_check_size_inverse("vbx_istft_trim", n_fft)) return rc;
+  VBX_REQUIRE(win > 0 && win <= n_fft && hop > 0 && hop <= win, "vbx_istft_trim: need 0 < hop <= win_length <= n_fft");
+  VBX_REQUIRE(frames > 0 && (long)(frames - 1) * hop + n_fft < 2147483647L, "vbx_istft_trim: need at least one frame");
+  VBX_REQUIRE(trim >= 0 && out_len > 0 && trim + out_len <= (long)(frames - 1) * hop + n_fft,
+              "vbx_istft_trim: [trim, trim + out_len) must lie inside the (frames - 1) * hop + n_fft samples");
+  hipStream_t st = (hipStream_t)stream;
+  istft_synth(mag, spec, fb, window, tw_re, tw_im, B, frames, n_fft, win, st);
+  VBX_LAUNCH_CHECK();
+  hipLaunchKernelGGL(gl_ola_trim_kernel, dim3((unsigned)cdiv(out_len, 256), B), dim3(256), 0, st, (const float*)fb, wave, renv, frames,
+                     win, (n_fft - win) / 2, hop, trim, out_len);
   VBX_LAUNCH_CHECK();
   return 0;
 }

@@ -13,33 +13,59 @@ Device path (csrc/vocos.hip, csrc/gemm.hip, csrc/griffinlim.hip): a fixed launch
 operands are fp16 (weights packed once per parameter version, the layer scale gamma folded into pwconv2 in fp32 before the rounding:
 gamma * (W g + b) = (gamma * W) g + gamma * b); the residual stream, LayerNorm, the head's exp / sin / cos and the inverse STFT are
 fp32.  Inference only.
+
+VocosEncodecDecoder is the EnCodec-conditioned variant as the published `vocos-encodec-24khz` file holds it: AdaLayerNorm tables kept
+whole (the bandwidth id is chosen per call), n_fft 1280 (a mixed-radix inverse transform, csrc/fft_lds.hpp) and Vocos's
+padding="same" inverse STFT (vbx_istft_trim), frames * hop_length samples.  PARITY UNPINNED likewise; tests/vocos_same_ref.py
+restates it, tests/test_vocos_encodec_gpu.py and profiles/vocos_encodec_parity.txt hold the kernels against that.
 """
 import torch
 from torch import nn
 
 from . import _lib
 from ._packing import PackedWeights, read_checkpoint, tensors_key  # read_checkpoint: importable from here as before
-from .codec import _check_stft_args, _stft_tables, ola_reciprocal_envelope
+from .codec import _check_istft_args, _stft_tables, ola_reciprocal_envelope, ola_reciprocal_envelope_trim
 
 LN_EPS = 1e-6
 
 
+class _AdaLayerNorm(nn.Module):
+    """Vocos's AdaLayerNorm: layer_norm(x) * scale[id] + shift[id], two embedding tables [num_embeddings, dim] (ones / zeros)"""
+
+    def __init__(self, num_embeddings, dim):
+        super().__init__()
+        self.scale = nn.Embedding(num_embeddings, dim)
+        self.shift = nn.Embedding(num_embeddings, dim)
+        nn.init.ones_(self.scale.weight)
+        nn.init.zeros_(self.shift.weight)
+
+
+def _norm(dim, adanorm):
+    return nn.LayerNorm(dim, eps=LN_EPS) if adanorm is None else _AdaLayerNorm(adanorm, dim)
+
+
+def _norm_tables(norm):
+    """fp32 (weight, bias) [dim] of a LayerNorm, or the (scale, shift) tables [num_embeddings, dim] of an _AdaLayerNorm"""
+    w, b = (norm.scale.weight, norm.shift.weight) if isinstance(norm, _AdaLayerNorm) else (norm.weight, norm.bias)
+    return w.detach().float().contiguous(), b.detach().float().contiguous()
+
+
 class _ConvNeXtBlock(nn.Module):
-    def __init__(self, dim, intermediate_dim, gamma0):
+    def __init__(self, dim, intermediate_dim, gamma0, adanorm=None):
         super().__init__()
         self.dwconv = nn.Conv1d(dim, dim, kernel_size=7, padding=3, groups=dim)
-        self.norm = nn.LayerNorm(dim, eps=LN_EPS)
+        self.norm = _norm(dim, adanorm)
         self.pwconv1 = nn.Linear(dim, intermediate_dim)
         self.pwconv2 = nn.Linear(intermediate_dim, dim)
         self.gamma = nn.Parameter(gamma0 * torch.ones(dim))
 
 
 class _Backbone(nn.Module):
-    def __init__(self, input_channels, dim, intermediate_dim, num_layers, gamma0):
+    def __init__(self, input_channels, dim, intermediate_dim, num_layers, gamma0, adanorm=None):
         super().__init__()
         self.embed = nn.Conv1d(input_channels, dim, kernel_size=7, padding=3)
-        self.norm = nn.LayerNorm(dim, eps=LN_EPS)
-        self.convnext = nn.ModuleList([_ConvNeXtBlock(dim, intermediate_dim, gamma0) for _ in range(num_layers)])
+        self.norm = _norm(dim, adanorm)
+        self.convnext = nn.ModuleList([_ConvNeXtBlock(dim, intermediate_dim, gamma0, adanorm) for _ in range(num_layers)])
         self.final_layer_norm = nn.LayerNorm(dim, eps=LN_EPS)
 
 
@@ -61,9 +87,9 @@ class VocosDecoder(PackedWeights, nn.Module):
     features are taken as given unless input_log, which applies log(clamp(x, min=1e-7)) first -- what Vocos's own mel feature
     extractor feeds its backbone (the published vocos-mel-24khz weights expect it, at hop_length 256).
 
-    Raises NotImplementedError for what is not built: padding="same", adanorm_num_embeddings (the EnCodec-conditioned variant as a
-    module; from_checkpoint(bandwidth_id=...) loads such a checkpoint for ONE fixed id),
-    n_fft outside the powers of two 256 .. 2048, dim not a multiple of 64 or above 2048, intermediate_dim not a multiple of 8,
+    Raises NotImplementedError for what this class does not serve: padding="same" and adanorm_num_embeddings (the EnCodec-conditioned
+    variant as a module: both are VocosEncodecDecoder's; from_checkpoint(bandwidth_id=...) here loads such a checkpoint folded to
+    ONE fixed id), n_fft outside the powers of two 256 .. 2048 and 320 / 640 / 1280, dim not a multiple of 64 or above 2048, intermediate_dim not a multiple of 8,
     input_channels above 512, fewer than two frames, a hop / n_fft pair beyond the LDS of the inverse transform; ValueError, as
     ola_reciprocal_envelope, where window and hop violate NOLA.  GPU tensors only."""
 
@@ -71,10 +97,16 @@ class VocosDecoder(PackedWeights, nn.Module):
                  layer_scale_init_value=None, input_log=False, adanorm_num_embeddings=None):
         super().__init__()
         if padding != "center":
-            raise NotImplementedError(f'VocosDecoder: padding="{padding}" is not built (only "center", torch.istft with center=True)')
+            raise NotImplementedError(f'VocosDecoder: padding="{padding}" is not built here (only "center", torch.istft with center=True); '
+                                      'VocosEncodecDecoder serves padding="same"')
         if adanorm_num_embeddings is not None:
-            raise NotImplementedError("VocosDecoder: adanorm_num_embeddings (the EnCodec-conditioned AdaLayerNorm variant) is not built")
-        _check_stft_args(n_fft, n_fft, hop_length)
+            raise NotImplementedError("VocosDecoder: adanorm_num_embeddings (the EnCodec-conditioned AdaLayerNorm variant) is not built "
+                                      "here; VocosEncodecDecoder keeps the tables")
+        self._setup(input_channels, dim, intermediate_dim, num_layers, n_fft, hop_length, padding, layer_scale_init_value, input_log, None)
+
+    def _setup(self, input_channels, dim, intermediate_dim, num_layers, n_fft, hop_length, padding, layer_scale_init_value, input_log,
+               adanorm_num_embeddings):
+        _check_istft_args(n_fft, n_fft, hop_length)
         if dim <= 0 or dim % 64 or dim > 2048:
             raise NotImplementedError(f"VocosDecoder: dim must be a multiple of 64, at most 2048 (got {dim})")
         if intermediate_dim <= 0 or intermediate_dim % 8:
@@ -85,7 +117,9 @@ class VocosDecoder(PackedWeights, nn.Module):
             raise ValueError("need num_layers >= 1")
         self.input_channels, self.dim, self.intermediate_dim, self.num_layers = input_channels, dim, intermediate_dim, num_layers
         self.n_fft, self.hop_length, self.padding, self.input_log = n_fft, hop_length, padding, bool(input_log)
-        self.backbone = _Backbone(input_channels, dim, intermediate_dim, num_layers, layer_scale_init_value or 1.0 / num_layers)
+        self.adanorm_num_embeddings = adanorm_num_embeddings
+        self.backbone = _Backbone(input_channels, dim, intermediate_dim, num_layers, layer_scale_init_value or 1.0 / num_layers,
+                                  adanorm_num_embeddings)
         self.head = _Head(dim, n_fft)
         for m in self.modules():
             if isinstance(m, (nn.Conv1d, nn.Linear)):
@@ -125,7 +159,8 @@ class VocosDecoder(PackedWeights, nn.Module):
         become the LayerNorm weights.  Without it such a dict raises NotImplementedError."""
         if any(k.startswith("backbone.norm.scale") or k.startswith("backbone.norm.shift") for k in sd):
             if bandwidth_id is None:
-                raise NotImplementedError("VocosDecoder: adanorm_num_embeddings (the EnCodec-conditioned AdaLayerNorm variant) is not built")
+                raise NotImplementedError("VocosDecoder: adanorm_num_embeddings (the EnCodec-conditioned AdaLayerNorm variant) is not built "
+                                          "here: pass bandwidth_id= for one fixed id, or load the file into a VocosEncodecDecoder")
             sd = cls._fold_adanorm(sd, int(bandwidth_id))
         dim, channels, _ = sd["backbone.embed.weight"].shape
         layers = 1 + max(int(k.split(".")[2]) for k in sd if k.startswith("backbone.convnext."))
@@ -152,12 +187,14 @@ class VocosDecoder(PackedWeights, nn.Module):
         layers = []
         for blk in bb.convnext:
             g = blk.gamma.detach().float()
+            lnw, lnb = _norm_tables(blk.norm)
             layers.append(dict(
                 taps=blk.dwconv.weight.detach().float()[:, 0, :].t().contiguous(),  # [7, D]
-                cb=f(blk.dwconv.bias), lnw=f(blk.norm.weight), lnb=f(blk.norm.bias),
+                cb=f(blk.dwconv.bias), lnw=lnw, lnb=lnb,
                 w1=blk.pwconv1.weight.detach().float().half().contiguous(), b1=f(blk.pwconv1.bias),
                 w2=(g[:, None] * blk.pwconv2.weight.detach().float()).half().contiguous(), b2=(g * blk.pwconv2.bias.detach().float()).contiguous()))
-        return dict(Kp=Kp, nhp=nhp, emb=emb.half(), emb_b=f(bb.embed.bias), n0w=f(bb.norm.weight), n0b=f(bb.norm.bias), layers=layers,
+        n0w, n0b = _norm_tables(bb.norm)
+        return dict(Kp=Kp, nhp=nhp, emb=emb.half(), emb_b=f(bb.embed.bias), n0w=n0w, n0b=n0b, layers=layers,
                     flw=f(bb.final_layer_norm.weight), flb=f(bb.final_layer_norm.bias), hw=hw.half(), hb=hb)
 
     def _istft_tables(self, frames, device):
@@ -167,11 +204,14 @@ class VocosDecoder(PackedWeights, nn.Module):
         key = (frames, str(device), tensors_key((win,)))
         if key != self._tables_key:
             win = win.detach().double().cpu()
-            renv = ola_reciprocal_envelope(self.n_fft, self.n_fft, self.hop_length, frames, window=win)
+            renv = self._reciprocal_envelope(frames, win)
             _, tw_re, tw_im = _stft_tables(self.n_fft, self.n_fft)
             self._tables = tuple(t.float().to(device) for t in (win, tw_re, tw_im, renv))
             self._tables_key = key
         return self._tables
+
+    def _reciprocal_envelope(self, frames, win):
+        return ola_reciprocal_envelope(self.n_fft, self.n_fft, self.hop_length, frames, window=win)
 
     @staticmethod
     def _gemm(epi, M, N, K, A, B, C, ldc, bias, resid=None):
@@ -200,11 +240,12 @@ class VocosDecoder(PackedWeights, nn.Module):
         with torch.inference_mode():
             return self._decode(features, tables)
 
-    def _decode(self, features, tables):
+    def _decode(self, features, tables, norm_id=None):
+        """norm_id: the row of the AdaLayerNorm tables the LayerNorm kernels read as weight / bias (None: plain LayerNorms)"""
         B, C, frames = features.shape
         n_fft, hop, D, I, dev = self.n_fft, self.hop_length, self.dim, self.intermediate_dim, features.device
-        window, tw_re, tw_im, renv = tables
         w = self._cached(self._pack)
+        row = (lambda t: t) if norm_id is None else (lambda t: t[norm_id])
         st = _lib.current_stream()
         M, Kp, nhp, nb = B * frames, w["Kp"], w["nhp"], n_fft // 2 + 1
         x = features.detach().to(torch.float32).contiguous()
@@ -214,10 +255,10 @@ class VocosDecoder(PackedWeights, nn.Module):
         _lib.call("vbx_vocos_pack_input", x, a16, B, C, frames, int(self.input_log), st)
         xa, xb = f32(M, D), f32(M, D)  # the residual stream ping-pongs: pwconv2 reads one as `resid` and writes the other
         self._gemm(_lib.VBX_EPI_F32, M, D, Kp, a16, w["emb"], xb, D, w["emb_b"])
-        _lib.call("vbx_layernorm_fwd", xb, w["n0w"], w["n0b"], None, xa, M, D, LN_EPS, st)
+        _lib.call("vbx_layernorm_fwd", xb, row(w["n0w"]), row(w["n0b"]), None, xa, M, D, LN_EPS, st)
         h16, g16 = f16(M, D), f16(M, I)
         for l in w["layers"]:
-            _lib.call("vbx_vocos_dwconv_ln", xa, l["taps"], l["cb"], l["lnw"], l["lnb"], h16, B, frames, D, LN_EPS, st)
+            _lib.call("vbx_vocos_dwconv_ln", xa, l["taps"], l["cb"], row(l["lnw"]), row(l["lnb"]), h16, B, frames, D, LN_EPS, st)
             self._gemm(_lib.VBX_EPI_GELU, M, I, D, h16, l["w1"], g16, I, l["b1"])
             self._gemm(_lib.VBX_EPI_F32, M, D, I, g16, l["w2"], xb, D, l["b2"], resid=xa)
             xa, xb = xb, xa
@@ -226,8 +267,118 @@ class VocosDecoder(PackedWeights, nn.Module):
         self._gemm(_lib.VBX_EPI_F32, M, nhp, D, h16, w["hw"], ho, nhp, w["hb"])
         mag, ph = f32(B, frames, nb), f32(B, frames, nb, 2)
         _lib.call("vbx_vocos_head", ho, mag, ph, M, nb, nhp, st)
-        fb, wave = f32(B, frames, n_fft), f32(B, (frames - 1) * hop)
+        return self._istft(mag, ph, f32(B, frames, n_fft), tables, st)
+
+    def _istft(self, mag, ph, fb, tables, st):
+        B, frames, n_fft, hop = fb.shape[0], fb.shape[1], self.n_fft, self.hop_length
+        window, tw_re, tw_im, renv = tables
+        wave = torch.empty(B, (frames - 1) * hop, dtype=torch.float32, device=fb.device)
         _lib.call("vbx_istft", mag, ph, fb, wave, window, tw_re, tw_im, renv, B, frames, n_fft, n_fft, hop, st)
+        return wave
+
+    decode = forward
+
+
+class VocosEncodecDecoder(VocosDecoder):
+    """The EnCodec-conditioned Vocos decoder with its AdaLayerNorm tables kept and Vocos's padding="same" inverse STFT; the defaults
+    are the published `vocos-encodec-24khz` configuration, whose state dict loads as is (`backbone.norm.scale.weight` /
+    `.shift.weight` [adanorm_num_embeddings, dim], the same per block, a plain `backbone.final_layer_norm`; `feature_extractor.*` is
+    skipped).
+
+    forward(features [B, input_channels, frames], bandwidth_id=None) -> wave fp32 [B, frames * hop_length] at "same" (in general
+    (frames - 1) * hop + n_fft - 2 * ((n_fft - hop) // 2); one frame is enough), [B, (frames - 1) * hop_length] at "center".  Every
+    AdaLayerNorm is layer_norm(x) * scale[id] + shift[id]: the LayerNorm kernels of VocosDecoder reading row `id` of the packed fp32
+    tables, so a decoder folded to that id (VocosDecoder.from_state_dict(bandwidth_id=id)) gives the same bits.  bandwidth_id is a
+    Python int (None: the constructor's); it is never read from a device tensor.  adanorm_num_embeddings=None builds plain
+    LayerNorms: a "same"-padded Vocos.
+
+    "same" is Vocos's ISTFT: irfft per frame (imaginary DC / Nyquist ignored), times the window, overlap-add, (n_fft - hop) // 2
+    samples trimmed from each end, divided by the window-square envelope of the kept range (ValueError "NOLA" where it is <= 1e-11).
+    The other limits are VocosDecoder's."""
+
+    def __init__(self, input_channels=128, dim=384, intermediate_dim=1152, num_layers=8, n_fft=1280, hop_length=320, padding="same",
+                 adanorm_num_embeddings=4, bandwidth_id=2, layer_scale_init_value=None, input_log=False):
+        nn.Module.__init__(self)
+        if padding not in ("same", "center"):
+            raise ValueError(f'VocosEncodecDecoder: padding must be "same" or "center" (got "{padding}")')
+        if adanorm_num_embeddings is not None:
+            if adanorm_num_embeddings < 1:
+                raise ValueError("need adanorm_num_embeddings >= 1, or None for plain LayerNorms")
+            self._check_id(bandwidth_id, adanorm_num_embeddings)
+        self._setup(input_channels, dim, intermediate_dim, num_layers, n_fft, hop_length, padding, layer_scale_init_value, input_log,
+                    adanorm_num_embeddings)
+        self.bandwidth_id = bandwidth_id if adanorm_num_embeddings is not None else None
+
+    @staticmethod
+    def _check_id(bandwidth_id, rows):
+        if isinstance(bandwidth_id, torch.Tensor) or not isinstance(bandwidth_id, int):
+            raise TypeError(f"VocosEncodecDecoder: bandwidth_id is a Python int (got {type(bandwidth_id).__name__}); it is never read "
+                            "from a tensor")
+        if not 0 <= bandwidth_id < rows:
+            raise ValueError(f"VocosEncodecDecoder: bandwidth_id {bandwidth_id} is outside the {rows} rows of the AdaLayerNorm tables")
+
+    @classmethod
+    def from_checkpoint(cls, path, *, hop_length=None, input_log=False, padding="same", bandwidth_id=2):
+        """A LOCAL file written by torch.save: a Vocos state dict or {'state_dict': ...}; see from_state_dict."""
+        return cls.from_state_dict(read_checkpoint(path), hop_length=hop_length, input_log=input_log, padding=padding,
+                                   bandwidth_id=bandwidth_id)
+
+    @classmethod
+    def from_state_dict(cls, sd, *, hop_length=None, input_log=False, padding="same", bandwidth_id=2):
+        """A Vocos state dict already in memory, loaded as is.  The widths and the number of AdaLayerNorm rows are read off the
+        shapes (a dict without `backbone.norm.scale.weight` gives plain LayerNorms, and bandwidth_id is ignored); hop_length is not
+        in a state dict (default n_fft / 4).  bandwidth_id is the default id of forward."""
+        dim, channels, _ = sd["backbone.embed.weight"].shape
+        layers = 1 + max(int(k.split(".")[2]) for k in sd if k.startswith("backbone.convnext."))
+        n_fft = sd["head.out.weight"].shape[0] - 2
+        rows = sd["backbone.norm.scale.weight"].shape[0] if "backbone.norm.scale.weight" in sd else None
+        self = cls(input_channels=channels, dim=dim, intermediate_dim=sd["backbone.convnext.0.pwconv1.weight"].shape[0],
+                   num_layers=layers, n_fft=n_fft, hop_length=hop_length or n_fft // 4, padding=padding, adanorm_num_embeddings=rows,
+                   bandwidth_id=bandwidth_id, input_log=input_log)
+        self.load_state_dict(sd)
+        return self.eval()
+
+    def _trim(self, frames):
+        """(trim, out_len) of the overlap-add's (frames - 1) * hop + n_fft samples"""
+        if self.padding == "center":
+            return self.n_fft // 2, (frames - 1) * self.hop_length
+        trim = (self.n_fft - self.hop_length) // 2
+        return trim, (frames - 1) * self.hop_length + self.n_fft - 2 * trim
+
+    def _reciprocal_envelope(self, frames, win):
+        trim, out_len = self._trim(frames)
+        return ola_reciprocal_envelope_trim(self.n_fft, self.hop_length, frames, win, trim, out_len)
+
+    def forward(self, features, bandwidth_id=None):
+        if features.ndim != 3 or features.shape[1] != self.input_channels:
+            raise ValueError(f"VocosEncodecDecoder takes features (batch, input_channels = {self.input_channels}, frames), got "
+                             f"{tuple(features.shape)}")
+        if self.adanorm_num_embeddings is None:
+            if bandwidth_id is not None:
+                raise ValueError("VocosEncodecDecoder: built with plain LayerNorms (adanorm_num_embeddings=None), there is no bandwidth_id")
+        else:
+            bandwidth_id = self.bandwidth_id if bandwidth_id is None else bandwidth_id
+            self._check_id(bandwidth_id, self.adanorm_num_embeddings)
+        frames, dev = features.shape[2], features.device
+        if frames < 1 or self._trim(frames)[1] < 1:
+            raise NotImplementedError(f'VocosEncodecDecoder: padding="{self.padding}" keeps no sample of {frames} frame(s)')
+        if _lib.lib().vbx_griffinlim_lds_bytes(self.n_fft, self.n_fft, self.hop_length) > 65536:
+            raise NotImplementedError(f"VocosEncodecDecoder: 3 * hop_length + n_fft = {3 * self.hop_length + self.n_fft} samples do not "
+                                      f"fit the LDS beside a {self.n_fft}-point transform")
+        if dev.type == "cuda" and self.head.out.weight.device != dev:
+            self.to(dev)
+        tables = self._istft_tables(frames, dev)  # ValueError: NOLA
+        if dev.type != "cuda":
+            raise _lib.VbxError(f"VocosEncodecDecoder runs only on an MI355X (gfx950) through libvbx_hip.so; the features are on '{dev}'")
+        with torch.inference_mode():
+            return self._decode(features, tables, bandwidth_id)
+
+    def _istft(self, mag, ph, fb, tables, st):
+        B, frames, n_fft, hop = fb.shape[0], fb.shape[1], self.n_fft, self.hop_length
+        window, tw_re, tw_im, renv = tables
+        trim, out_len = self._trim(frames)
+        wave = torch.empty(B, out_len, dtype=torch.float32, device=fb.device)
+        _lib.call("vbx_istft_trim", mag, ph, fb, wave, window, tw_re, tw_im, renv, B, frames, n_fft, n_fft, hop, trim, out_len, st)
         return wave
 
     decode = forward
