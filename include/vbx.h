@@ -429,6 +429,49 @@ int vbx_forward_sum_fwd(const float* value, const int* key_lens, const int* quer
                         float* nll, double* logz, int B, int T, int K, void* stream);
 int vbx_forward_sum_bwd(const float* value, const int* key_lens, const int* query_lens, float blank_logprob, const double* lse,
                         const double* alpha, const double* logz, const float* grad_nll, float* grad, int B, int T, int K, void* stream);
+/* The Aligner network (voicebox_pytorch_amd.Aligner / aligner_attention; csrc/aligner.hip): the distance attention of "One TTS
+ * Alignment To Rule Them All" / RAD-TTS over encodings q fp32 [B, T, A] and k fp32 [B, K, A], 1 <= A <= vbx_aligner_attn_max_channels()
+ * (128: a 64-key chunk of that width fills the LDS tile), 1 <= B <= 65535, B * T < 2^31, any K >= 1; everything else VBX_EINVAL.
+ * mask uint8 [B, K], non-zero = a real key, NULL = all real.  fp32 throughout, no atomics, no host synchronisation; the same bits on
+ * every run and for a row alone or inside a batch.  u = 2^-24 below.
+ * vbx_aligner_attn_fwd, one launch: logprob[b][t][j] = -temperature * sum_c (q[b][t][c] - k[b][j][c])^2, NOT masked, the sum an fp32
+ *   fmaf chain over c = 0 .. A - 1 of the rounded differences (never |q|^2 + |k|^2 - 2 q.k, never a 16-bit copy of the encodings):
+ *     |logprob - ref| <= (A + 4) u |ref|,  ref the fp64 value from the same fp32 q, k and temperature.
+ *   attn[b][t][.] = softmax_j(mask ? logprob : -FLT_MAX) with libm's expf (1 ulp): a masked key gets exactly 0, a row with every key
+ *   masked exactly 1 / K.  Against the fp64 softmax p of the kernel's OWN logprob x (m = its row maximum over the kept keys):
+ *     |attn - p| <= (|x - m| + sum_j p_j |x_j - m| + ceil(K / 64) + 16) u p + 2^-126
+ *   (the subtraction x - m rounds once, which exp turns into |x - m| u; expf and its rounding 4 u per term, in the numerator and,
+ *   weighted by p, in the sum; the sum of K positive terms, one serial chain per lane and a 6-step tree, ceil(K / 64) + 6 u; the
+ *   division 1 u; 2^-126 where expf underflows).
+ * vbx_aligner_attn_bwd: with G = g_logprob + mask * attn * (g_attn - sum_j attn * g_attn) (the masked softmax's backward: no gradient
+ *   reaches a filled key, not even on a fully masked row),
+ *     dq[b][t][c] = -2 temperature sum_j G[t][j] (q[t][c] - k[j][c]),   dk[b][j][c] = +2 temperature sum_t G[t][j] (q[t][c] - k[j][c]),
+ *   each ONE thread's fmaf chain over j = 0 .. K - 1 (t = 0 .. T - 1) in index order, inside the workgroup that owns 16 rows of dq
+ *   (dk).  g_logprob or g_attn may be NULL (not both); attn and gmap (scratch, fp32 [B, T, K]) are needed only with g_attn; dq or dk
+ *   may be NULL and is then not computed.  With gh = |g_logprob| + attn (|g_attn| + sum_j attn |g_attn|) (what |G| is bounded by)
+ *     |dq - ref| <= (K + 32) u 2 temperature sum_j gh[t][j] |q[t][c] - k[j][c]|,   |dk - ref| <= (T + 32) u 2 temperature sum_t (same),
+ *   ref in fp64 from the same fp32 operands (n terms of a chain: n + 1; the difference and the final scale: 2; G's own rounding, a
+ *   ceil(K / 64) + 6 dot product, the subtraction, the product and the sum: ceil(K / 64) + 10, K <= 1024 assumed for the constant 32;
+ *   beyond that it is K + ceil(K / 64) + 16).
+ * The convolution stacks are vbx_gemm launches around three small kernels:
+ * vbx_aligner_pack: x fp32 [B, T, C] (channel_first: [B, C, T]) -> out 16-bit [B * T, C * taps] (fmt 2: three times as wide), taps
+ *   1 or 3, out[b * T + t][c * taps + tap] = act(x[b][t + tap - taps / 2][c]), 0 outside 0 <= t' < T (nn.Conv1d's zero padding of
+ *   the padded batch), act = max(., 0) with relu.  fmt 0: fp16 (saturating); 1: bfloat16; 2: the three-piece fp16 row
+ *   [hi | hi 2^-8 | lo 2^8] of the precise mode (vbx_split3_f16), to be multiplied with [W_hi | W_lo 2^8 | W_hi 2^-8]: products to
+ *   fp32 accuracy on the same GEMM tiles.  Column c * taps + tap is the Conv1d weight's own [Cout, Cin * taps] view: the forward
+ *   is NT against it, the dgrad NN, the wgrad TN lands in the weight's layout.
+ * vbx_aligner_relu_bwd: g fp32 [n] *= (pre > 0) in place (pre NULL: unchanged) and g_bf16 = bfloat16(g).
+ * vbx_aligner_fold: d fp32 [B * T, 3 C] (the dgrad in the packed layout) -> dx[b][t][c] = d[t + 1][3 c] + d[t][3 c + 1] + d[t - 1][3 c + 2]
+ *   within a batch row, fp32 [B, T, C] or, channel_first, [B, C, T]. */
+int vbx_aligner_attn_max_channels(void);
+int vbx_aligner_attn_fwd(const float* q, const float* k, const uint8_t* mask, float temperature, float* attn, float* logprob, int B, int T,
+                         int K, int A, void* stream);
+int vbx_aligner_attn_bwd(const float* q, const float* k, const uint8_t* mask, const float* attn, const float* g_logprob,
+                         const float* g_attn, float temperature, float* gmap, float* dq, float* dk, int B, int T, int K, int A,
+                         void* stream);
+int vbx_aligner_pack(const float* x, void* out, int B, int T, int C, int taps, int relu, int channel_first, int fmt, void* stream);
+int vbx_aligner_relu_bwd(float* g, const float* pre, void* g_bf16, long n, void* stream);
+int vbx_aligner_fold(const float* d, float* dx, int B, int T, int C, int channel_first, void* stream);
 /* Sample-rate conversion (voicebox_pytorch_amd.resample; csrc/resample.hip): the polyphase windowed-sinc FIR of
  * torchaudio.functional.resample for the REDUCED rate pair orig : nw,
  *   y[r][q * nw + p] = sum_k h[p][k] * x[r][q * orig + k - width],  x = 0 outside [0, L),  p < nw, k < K = 2 * width + orig,

@@ -93,6 +93,12 @@ _PROTOS = {
     "vbx_maximum_path": [P, P, P, P, P, P, I, I, I, P],
     "vbx_forward_sum_fwd": [P, P, P, F, P, P, P, P, I, I, I, P],
     "vbx_forward_sum_bwd": [P, P, P, F, P, P, P, P, P, I, I, I, P],
+    "vbx_aligner_attn_max_channels": [],
+    "vbx_aligner_attn_fwd": [P, P, P, F, P, P, I, I, I, I, P],
+    "vbx_aligner_attn_bwd": [P, P, P, P, P, P, F, P, P, P, I, I, I, I, P],
+    "vbx_aligner_pack": [P, P, I, I, I, I, I, I, I, P],
+    "vbx_aligner_relu_bwd": [P, P, P, L, P],
+    "vbx_aligner_fold": [P, P, I, I, I, I, P],
     "vbx_resample_max_taps": [],
     "vbx_resample": [P, P, P, P, P, I, L, L, I, I, I, I, I, P],
     "vbx_pack_phoneme_input": [P, P, I, P, I, P, P, P, P, I, I, I, P],

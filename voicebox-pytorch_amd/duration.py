@@ -7,10 +7,16 @@ Compute: vbx_pack_phoneme_input (embedding gather + condition masking / dropping
 (to_embed) -> vbx_convpos_fwd (+ residual) -> the native Transformer stack (plain RMSNorm, no registers) -> vbx_rowdot (to_pred).
 
 Not built, and raising instead of silently differing:
-  * training: the reference's training branch (:841-876) needs naturalspeech2_pytorch's `Aligner`, `ForwardSumLoss` and
-    `maximum_path` (third-party, absent) and computes its L1 loss on the hidden state rather than the predicted durations;
+  * training: the reference's training branch (:841-876) computes its L1 loss on the hidden state rather than the predicted
+    durations and needs a Transformer backward of its own; `.train()(...)` raises;
   * `tokenizer` / `texts` (espeak phonemizer, third-party) and `audio_enc_dec` (codecs are out of scope): pass `phoneme_ids`.
-`aligner.*` entries of a reference checkpoint are skipped on load (there is no aligner module here).
+
+The aligner (align.py: `Aligner`, `maximum_path`, `ForwardSumLoss`) is optional.  By default `self.aligner` is None, `aligner.*`
+entries of a reference checkpoint are skipped on load and `state_dict()` has no such keys.  `attach_aligner()` builds
+`Aligner(dim_hidden=dim_phoneme_emb, **aligner_kwargs)` (or takes a given one); from then on `aligner.*` keys are loaded and saved,
+`forward_aligner` (:730-754) returns the reference's four alignment tensors, and `align_phoneme_ids(mel, phoneme_ids)` gives the
+frame-aligned phoneme ids that a text-conditioned VoiceBox takes as `cond_token_ids`.  The aligner is trained with
+ForwardSumLoss(aligner(...)[1], ...): its parameters are ordinary parameters of this module once attached.
 """
 from random import random
 
@@ -18,6 +24,7 @@ import torch
 from torch import nn
 
 from . import _lib
+from .align import Aligner, maximum_path
 from .masks import mask_from_frac_lengths, prob_mask_like, take_draw
 from .model import ConvPositionEmbed, Transformer, exists
 
@@ -63,7 +70,8 @@ class DurationPredictor(nn.Module):
                                        use_gateloop_layers=use_gateloop_layers)
         self.to_pred = nn.Sequential(nn.Linear(dim, 1), nn.Identity())  # [1]: Rearrange('... 1 -> ...'), done by vbx_rowdot
         self.dim, self.dim_phoneme_emb, self.ksize = dim, dim_phoneme_emb, conv_pos_embed_kernel_size
-        self.aligner = None  # naturalspeech2_pytorch.Aligner(dim_hidden=dim_phoneme_emb, **aligner_kwargs): training only
+        self.aligner_kwargs = dict(aligner_kwargs)
+        self.aligner = None  # attach_aligner(): Aligner(dim_hidden=dim_phoneme_emb, **aligner_kwargs)
         self.align_loss = None
 
     @property
@@ -71,8 +79,53 @@ class DurationPredictor(nn.Module):
         return next(self.parameters()).device
 
     def load_state_dict(self, state_dict, strict=True, **kw):
+        if self.aligner is not None:
+            return super().load_state_dict(state_dict, strict=strict, **kw)
         kept = {k: v for k, v in state_dict.items() if not k.startswith("aligner.")}
         return super().load_state_dict(kept, strict=strict, **kw)
+
+    def attach_aligner(self, aligner=None):
+        """Gives this module its aligner: the given one, or Aligner(dim_hidden=dim_phoneme_emb, **aligner_kwargs) on the device of
+        the parameters.  From then on `aligner.*` keys are part of state_dict() and are loaded.  Returns the aligner."""
+        if aligner is None:
+            aligner = Aligner(dim_hidden=self.dim_phoneme_emb, **self.aligner_kwargs).to(self.device)
+        elif not isinstance(aligner, Aligner):
+            raise TypeError(f"attach_aligner takes a voicebox_pytorch_amd.Aligner (got {type(aligner).__name__})")
+        elif aligner.dim_hidden != self.dim_phoneme_emb:
+            raise ValueError(f"attach_aligner: the aligner's dim_hidden ({aligner.dim_hidden}) must be dim_phoneme_emb "
+                             f"({self.dim_phoneme_emb})")
+        self.aligner = aligner
+        return aligner
+
+    def _need_aligner(self, who):
+        if self.aligner is None:
+            raise RuntimeError(f"DurationPredictor.{who} needs an aligner: call attach_aligner() first")
+
+    def forward_aligner(self, x, x_mask, y, y_mask):  # voicebox_pytorch.py:730-754
+        """x [B, Tx, dim_phoneme_emb] phoneme embeddings, x_mask [B, 1, Tx], y [B, Ty, dim_in] mel, y_mask [B, 1, Ty] ->
+        (alignment_hard fp32 [B, Tx], alignment_soft [B, Tx, Ty], alignment_logprob [B, 1, Ty, Tx], alignment_mas [B, Tx, Ty]).
+        alignment_soft and alignment_mas are transposed views of the aligner's map and of maximum_path's path.  The masks must be
+        PREFIX masks (real entries first): the search takes the lengths, the masks' sums, which stay on the device.  The soft map
+        and the log-probabilities are differentiable; the hard alignment is not."""
+        self._need_aligner("forward_aligner")
+        soft, logprob = self.aligner(y.transpose(1, 2), x, x_mask)
+        key_lens = (x_mask.reshape(x_mask.shape[0], -1) != 0).sum(-1)
+        query_lens = (y_mask.reshape(y_mask.shape[0], -1) != 0).sum(-1)
+        path, durations = maximum_path(soft, query_lens, key_lens)
+        return durations.float(), soft[:, 0].transpose(1, 2), logprob, path[:, 0].transpose(1, 2)
+
+    def align_phoneme_ids(self, mel, phoneme_ids, phoneme_len=None, mel_len=None):
+        """mel [B, dim_in, T] and phoneme_ids [B, K] (-1 = padding) -> the phoneme id of every mel frame, int64 [B, frames]:
+        embedding -> aligner.align -> align_phoneme_ids_with_durations.  phoneme_len / mel_len int [B] on the device (None: the
+        count of ids != -1 / T).  This is what VoiceBox(condition_on_text=True) takes as cond_token_ids."""
+        self._need_aligner("align_phoneme_ids")
+        with torch.no_grad():
+            ids = phoneme_ids.to(self.device, torch.long)
+            if phoneme_len is None:
+                phoneme_len = (ids != -1).sum(-1)
+            emb = self.to_phoneme_emb(ids.clamp(min=0))
+            durations, _ = self.aligner.align(mel, emb, key_lens=phoneme_len, query_lens=mel_len)
+            return self.align_phoneme_ids_with_durations(ids.clamp(min=0), durations)
 
     def align_phoneme_ids_with_durations(self, phoneme_ids, durations):  # voicebox_pytorch.py:689-692
         repeat_mask = generate_mask_from_repeats(durations.clamp(min=1))
