@@ -41,7 +41,15 @@ int vbx_check_device(int dev);
  *   NN: A[M,K] (k contiguous), B[K,N] (n contiguous)  -> C[M,N] = A . B      dgrad  (dX = dY . W)
  *   TN: A[K,M] (m contiguous), B[K,N] (n contiguous)  -> C[M,N] = A^T . B    wgrad  (dW = dY^T . X)
  * Replaces every nn.Linear / F.linear on the path (voicebox_pytorch.py:314-315,320,333,345,348,
- * 938,966,1078,1092) and their autograd backward. */
+ * 938,966,1078,1092) and their autograd backward.
+ * Argument contract (anything else is VBX_EINVAL, from vbx_gemm and vbx_gemm_route alike, before anything is launched):
+ *  - lda, ldb, ldc and N are multiples of 8 (16-byte rows) and cover their rows: lda >= K (NT / NN) or M (TN), ldb >= K (NT) or N
+ *    (NN / TN), ldc >= N for VBX_EPI_BF16 / F32 / GELU (VBX_EPI_GEGLU's ldc is the row of its [M, N/2] result; QKV has none);
+ *  - K is a multiple of 8 in NT and in NN: the k-contiguous operands are staged in 16-byte pieces, so a ragged K would make the
+ *    kernels read a row's padding A[row, K .. lda) and multiply it by zeros -- a NaN or Inf there (torch.empty) would poison the
+ *    output row.  TN takes any K (both operands are k-strided) and needs M to be a multiple of 8;
+ *  - within these rules the kernels read nothing outside A[.., :K] / B's logical extent and write nothing outside C[:M, :N]:
+ *    row padding, the rows behind the last and the columns N .. ldc of an output are never touched (tests/test_gemm_edges_gpu.py). */
 enum { VBX_GEMM_NT = 0, VBX_GEMM_NN = 1, VBX_GEMM_TN = 2 };
 
 enum {

@@ -836,15 +836,20 @@ static int gemm_validate(const vbx_gemm_desc* d) {
   VBX_REQUIRE(d->M > 0 && d->N > 0 && d->K > 0, "vbx_gemm: bad dims M=%d N=%d K=%d", d->M, d->N, d->K);
   VBX_REQUIRE(d->lda % 8 == 0 && d->ldb % 8 == 0, "vbx_gemm: leading dims must be multiples of 8 (16-byte rows)");
   VBX_REQUIRE(d->N % 8 == 0, "vbx_gemm: N must be a multiple of 8");
-  if (d->mode == VBX_GEMM_NT) VBX_REQUIRE(d->K % 8 == 0, "vbx_gemm NT: K must be a multiple of 8");
-  if (d->mode == VBX_GEMM_TN) VBX_REQUIRE(d->M % 8 == 0, "vbx_gemm TN: M must be a multiple of 8");
   const bool ntnn = d->mode == VBX_GEMM_NT || d->mode == VBX_GEMM_NN;
+  // K-contiguous operands (A of NT / NN, B of NT) are staged in 16-byte pieces: with K % 8 != 0 the last piece of a row would read the
+  // caller's row padding A[row, K .. roundup8(K)) and multiply it by zeros -- a NaN or Inf there turns the whole output row into NaN
+  if (ntnn) VBX_REQUIRE(d->K % 8 == 0, "vbx_gemm NT / NN: K must be a multiple of 8");
+  if (d->mode == VBX_GEMM_TN) VBX_REQUIRE(d->M % 8 == 0, "vbx_gemm TN: M must be a multiple of 8");
+  // every row lies inside its leading dimension: A is [M,K] (NT / NN) or [K,M] (TN), B is [N,K] (NT) or [K,N] (NN / TN)
+  VBX_REQUIRE(d->lda >= (d->mode == VBX_GEMM_TN ? d->M : d->K), "vbx_gemm: lda = %d is shorter than a row of A", d->lda);
+  VBX_REQUIRE(d->ldb >= (d->mode == VBX_GEMM_NT ? d->K : d->N), "vbx_gemm: ldb = %d is shorter than a row of B", d->ldb);
   bool known = false;
   switch (d->epilogue) {
     case VBX_EPI_BF16:
     case VBX_EPI_F32:
       known = ntnn;
-      if (known) VBX_REQUIRE(d->C && d->ldc % 8 == 0, "vbx_gemm BF16 / F32: bad C/ldc");
+      if (known) VBX_REQUIRE(d->C && d->ldc % 8 == 0 && d->ldc >= d->N, "vbx_gemm BF16 / F32: bad C/ldc (ldc >= N, a multiple of 8)");
       break;
     case VBX_EPI_QKV:
       VBX_REQUIRE(d->mode == VBX_GEMM_NT, "vbx_gemm QKV: NT only");
