@@ -191,6 +191,18 @@ int vbx_attn_bwd(const void* q16, const void* k16, const void* qb, const void* k
 /* backward of MultiheadRMSNorm + rotary (voicebox_pytorch.py:286-287,199): consumes dq/dk fp32
  * [B,H,Np,64] and the saved q16/k16 + rnorm, writes d(raw q|k) bf16 into dqkv[(b*Np+n)*ld + which*H*64
  * + h*64 + d] and partial gamma grads gpart[2][vbx_qknorm_rope_bwd_gpart_rows(B)][H][64]. */
+/* delta[b,h,n] = sum_j P[n,j] dP[n,j] from the attention backward's own operands (P = exp2(q16 . k16 - lse), masked keys 0;
+ * dP = dO . V^T over the bf16 v), for a following vbx_attn_bwd* call with out = NULL ("delta is already written").  The default pass
+ * inside those calls, rowsum(dO * O), reads the forward's fp16 output, which was summed from the fp16 copy of v: the same number
+ * mathematically, but dS = P (dP - delta) is then a small difference of two terms whose roundings of v differ by 2^-9, multiplied by
+ * scale |q| |k| on the way to q and k.  Under a dense loss over many rows that averages out; under a loss on a handful of rows of a
+ * short sequence it is most of d(q), d(k) and the qk-norm gammas (one token: P = 1, the exact dS is 0, everything that arrives is that
+ * rounding difference).  Cost is quadratic in Np (fp32 VALU, one workgroup per 64 queries of a head); the stage runtime uses it for the
+ * stand-alone stack at Np <= VBX_ATTN_DELTA_CONSISTENT_MAX_NP without attention dropout.  q16, k16 fp16 and v bf16 [B,H,Np,64], dout
+ * bf16 [B*Np, H*64], lse / delta fp32 [B,H,Np], mask [B,Np] or NULL.  No atomics, reruns bit-identical.  B * H <= 65535. */
+#define VBX_ATTN_DELTA_CONSISTENT_MAX_NP 256
+int vbx_attn_delta_consistent(const void* q16, const void* k16, const void* v, const uint8_t* mask, const void* dout, const float* lse,
+                              float* delta, int B, int H, int Np, void* stream);
 /* vbx_attn_bwd with the backward of rotary + MultiheadRMSNorm (vbx_qknorm_rope_bwd) folded into the epilogues of its two kernels:
  * no fp32 dq / dk round trip; writes d(qkv) bf16 [B*Np, ld] (q | k | v blocks of H*64 columns) directly.  gpart: partial gamma
  * gradients [2][B * vbx_attn_bwd_fused_tiles(Np)][H][64] (q then k), to be summed over the rows (qk_scale > 0 only). */
@@ -502,6 +514,35 @@ int vbx_cond_emb_bwd(const void* demb_bf16, int ld, const long* ids, int T, cons
  * cond_mask [B,S] (may be NULL), drop_mask [B] (may be NULL).  Feeds vbx_gemm (to_embed, f16 operands). */
 int vbx_pack_phoneme_input(const long* ids, const float* table, int E, const float* cond, int S, const uint8_t* cond_mask,
                            const uint8_t* drop_mask, const float* null_cond, void* out_f16, int B, int N, int D, void* stream);
+/* The training forward's variant: the same fp16 rows (bit for bit) and, in the same launch, out_bf16 [B*N, E+D], the operand of the
+ * to_embed weight gradient, and emb_f32 [B*N, E], the gathered embedding rows unrounded (the aligner's keys).  Either may be NULL. */
+int vbx_pack_phoneme_input_train(const long* ids, const float* table, int E, const float* cond, int S, const uint8_t* cond_mask,
+                                 const uint8_t* drop_mask, const float* null_cond, void* out_f16, void* out_bf16, float* emb_f32, int B,
+                                 int N, int D, void* stream);
+/* ------------------------------------------------------------------ DurationPredictor training (csrc/duration.hip)
+ * The loss of voicebox_pytorch.py:858-866 taken on the PREDICTED durations (the reference writes it on the hidden state, which only
+ * broadcasts at degenerate shapes).  All of it fp32, no atomics; every sum runs in an order fixed by the shapes alone, so reruns are
+ * bit-identical and a batch row gives the same durations / num / den alone as inside a batch.
+ *
+ * vbx_duration_head_fwd (two launches): durations[r] = hid[r,:] . w + bias[0] with vbx_rowdot's arithmetic (the same bits);
+ *   num[b] = sum_n m |d - t|, den[b] = sum_n m over loss_mask m [B, n] (uint8), loss[0] = (1/B) sum_b num[b] / max(den[b], 1e-5).
+ *   Bounds: |d - d64| <= (D + 2) 2^-24 (sum |x w| + |b|); the loss on the kernel's own d within (n + B + 4) 2^-24 of its fp64 value.
+ * vbx_duration_head_bwd (two launches): g_r = gscale[0] m sign(d - t) / (B max(den[b], 1e-5)), sign(0) = 0 as torch's l1_loss;
+ *   gscale is a device scalar (NULL = 1).  dhid[r,:] = g_r w (fp32 only: the stack's backward takes fp32), two roundings;
+ *   dw[D] = sum_r g_r hid[r,:] and db[1] = sum_r g_r through one partial per 32 rows (rows ascending) and one ascending sum over the
+ *   partials: within (B n + 2) 2^-24 sum |terms|.  scratch: vbx_duration_head_bwd_scratch_floats(B, n, D) floats.
+ * vbx_phoneme_emb_bwd (one launch, one workgroup per table row): gtable[v,:] = sum over the rows r with max(ids[r], 0) == v, in
+ *   ascending r, of g_packed[r, 0:E] (row stride ld_packed) + g_emb[r, 0:E] (dense) -- the two consumers of the embedding, either may
+ *   be NULL.  Rows of unused ids are exactly 0; every row of gtable [V, E] is written.  Padding positions (-1, clamped to 0)
+ *   contribute whatever gradient reaches them, as in the reference.  E <= 2048.  Within (count_v + 2) 2^-24 sum |terms|. */
+int vbx_duration_head_fwd(const float* hid, const float* w, const float* bias, const float* target, const uint8_t* loss_mask,
+                          float* durations, float* num, float* den, float* loss, int B, int n, int D, void* stream);
+long vbx_duration_head_bwd_scratch_floats(int B, int n, int D);
+int vbx_duration_head_bwd(const float* hid, const float* w, const float* durations, const float* target, const uint8_t* loss_mask,
+                          const float* den, const float* gscale, float* dhid, float* dw, float* db, float* scratch, int B, int n, int D,
+                          void* stream);
+int vbx_phoneme_emb_bwd(const long* ids, const float* g_packed, int ld_packed, const float* g_emb, float* gtable, long rows, int V,
+                        int E, void* stream);
 /* to_pred = Linear(dim, 1) + squeeze (voicebox_pytorch.py:672-675): out[r] = x[r,:] . w + bias[0]  (bias may be NULL). */
 int vbx_rowdot(const float* x, const float* w, const float* bias, float* out, long rows, int D, void* stream);
 /* standalone Transformer.forward (voicebox_pytorch.py:417-431, :476-477): residual stream [B,N+R,D] = register tokens (rows

@@ -102,7 +102,12 @@ _PROTOS = {
     "vbx_resample_max_taps": [],
     "vbx_resample": [P, P, P, P, P, I, L, L, I, I, I, I, I, P],
     "vbx_pack_phoneme_input": [P, P, I, P, I, P, P, P, P, I, I, I, P],
+    "vbx_pack_phoneme_input_train": [P, P, I, P, I, P, P, P, P, P, P, I, I, I, P],
     "vbx_rowdot": [P, P, P, P, L, I, P],
+    "vbx_attn_delta_consistent": [P, P, P, P, P, P, P, I, I, I, P],
+    "vbx_duration_head_fwd": [P, P, P, P, P, P, P, P, P, I, I, I, P],
+    "vbx_duration_head_bwd": [P, P, P, P, P, P, P, P, P, P, P, I, I, I, P],
+    "vbx_phoneme_emb_bwd": [P, P, I, P, P, L, I, I, P],
     "vbx_stack_input": [P, P, P, I, I, I, I, P],
     "vbx_stack_input_bwd": [P, P, P, I, I, I, I, P],
     "vbx_unet_cat": [P, P, F, P, P, L, I, P],
@@ -208,6 +213,8 @@ def lib():
     l.vbx_attn_q_prescale.restype = F
     l.vbx_adaln_dtemb_all_scratch_floats.argtypes = [I, I, I, I]
     l.vbx_adaln_dtemb_all_scratch_floats.restype = C.c_long
+    l.vbx_duration_head_bwd_scratch_floats.argtypes = [I, I, I]
+    l.vbx_duration_head_bwd_scratch_floats.restype = C.c_long
     l.vbx_ode_norm_slab_doubles.argtypes = [L]
     l.vbx_ode_norm_slab_doubles.restype = C.c_long
     _lib = l
@@ -216,7 +223,8 @@ def lib():
 
 def exported_symbols():
     return sorted(_PROTOS) + ["vbx_last_error", "vbx_attn_bwd_scratch_bytes", "vbx_dropout_keep_scale", "vbx_attn_q_prescale",
-                              "vbx_adaln_dtemb_all_scratch_floats", "vbx_ode_norm_slab_doubles"]  # + the stage-level entries bound in engine.py
+                              "vbx_adaln_dtemb_all_scratch_floats", "vbx_ode_norm_slab_doubles",
+                              "vbx_duration_head_bwd_scratch_floats"]  # + the stage-level entries bound in engine.py
 
 
 def ptr(t):

@@ -488,6 +488,67 @@ __global__ void attn_delta_kernel(const u16* __restrict__ o, const u16* __restri
   }
 }
 
+// delta from the backward's OWN operands: delta[b,h,n] = sum_j P[n,j] * dP[n,j] with P = exp2(q16 . k16 - L) (masked keys 0) and
+// dP = dO . V^T over the bf16 copy of v -- the two factors of dS = P * (dP - delta) as the backward kernels form them.  The streaming
+// pass above reads the forward's fp16 output instead, which was summed from the fp16 copy of v: mathematically the same number, but the
+// two roundings of v differ by 2^-9, and dP - delta is a small difference that the qk-norm scale multiplies by 10 |q| |k|.  With many
+// rows under a dense loss that noise averages out; with a handful of loss rows of a short sequence it is the gradient of q and k
+// (at one token, where P = 1 and dS is exactly 0, ALL of it).  Quadratic in Np, fp32 VALU: for short sequences (the caller decides).
+// One workgroup per (b, h, 64 queries); thread = query (lane) x key class (wave), so a key's row is an LDS broadcast; a thread adds
+// its keys in ascending order, the four classes are added in order: no atomics, the same bits on every run.
+__global__ __launch_bounds__(256) void attn_delta_consistent_kernel(const u16* __restrict__ q16, const u16* __restrict__ k16,
+                                                                    const u16* __restrict__ v, const uint8_t* __restrict__ mask,
+                                                                    const u16* __restrict__ dout, const float* __restrict__ lse,
+                                                                    float* __restrict__ delta, int H, int Np) {
+  __shared__ __attribute__((aligned(16))) float ksm[64][64];
+  __shared__ __attribute__((aligned(16))) float vsm[64][64];
+  __shared__ float red[4][64];
+  const int tid = threadIdx.x, qi = tid & 63, w = tid >> 6;
+  const long bh = blockIdx.y;
+  const int b = (int)(bh / H), h = (int)(bh % H);
+  const int n = blockIdx.x * 64 + qi, nn = min(n, Np - 1);
+  float q[64], g[64];
+  {
+    const u16* qp = q16 + (bh * Np + nn) * 64;
+    const u16* gp = dout + ((long)b * Np + nn) * ((long)H * 64) + h * 64;
+#pragma unroll
+    for (int d = 0; d < 64; d++) {
+      q[d] = f16_to_f32(qp[d]);
+      g[d] = bf16_to_f32(gp[d]);
+    }
+  }
+  const float L = lse[bh * Np + nn];
+  float acc = 0.f;
+  for (int k0 = 0; k0 < Np; k0 += 64) {
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < 16; i++) {
+      const int idx = tid + 256 * i, key = idx >> 6, d = idx & 63, kg = k0 + key;
+      const bool in = kg < Np;
+      ksm[key][d] = in ? f16_to_f32(k16[(bh * Np + kg) * 64 + d]) : 0.f;
+      vsm[key][d] = in ? bf16_to_f32(v[(bh * Np + kg) * 64 + d]) : 0.f;
+    }
+    __syncthreads();
+    for (int kk = 0; kk < 16; kk++) {
+      const int key = w * 16 + kk, kg = k0 + key;
+      bool ok = kg < Np;
+      if (ok && mask) ok = mask[(long)b * Np + kg] != 0;
+      if (!ok) continue;  // wave-uniform
+      float s = 0.f, dp = 0.f;
+#pragma unroll
+      for (int d = 0; d < 64; d += 4) {
+        const float4 kf = *reinterpret_cast<const float4*>(&ksm[key][d]), vf = *reinterpret_cast<const float4*>(&vsm[key][d]);
+        s = fmaf(q[d], kf.x, s); s = fmaf(q[d + 1], kf.y, s); s = fmaf(q[d + 2], kf.z, s); s = fmaf(q[d + 3], kf.w, s);
+        dp = fmaf(g[d], vf.x, dp); dp = fmaf(g[d + 1], vf.y, dp); dp = fmaf(g[d + 2], vf.z, dp); dp = fmaf(g[d + 3], vf.w, dp);
+      }
+      acc = fmaf(__builtin_amdgcn_exp2f(s - L), dp, acc);
+    }
+  }
+  red[w][qi] = acc;
+  __syncthreads();
+  if (w == 0 && n < Np) delta[bh * Np + n] = ((red[0][qi] + red[1][qi]) + red[2][qi]) + red[3][qi];
+}
+
 // (Round 1's register-staged backward kernels, attn_bwd_dq_kernel / attn_bwd_dkdv_kernel, were removed in round 6: docs/history.md.)
 
 // ---- Round-2 experiment, removed after measurement: "v2" backward kernels with 8 waves = two groups of four that work on
@@ -1217,6 +1278,16 @@ static int attn_bwd_impl(const void* q16, const void* k16, const void* qb, const
   VBX_LAUNCH_CHECK();
   // a fully masked batch: dv of the uniform softmax (its dq / dk, and the fused path's d(q, k) and gamma partials, are already 0)
   return mask ? attn_empty_batch_fixup(2, dout, mask, B, H, Np, drop.cm, drop.p, nullptr, nullptr, dv, dv_ld, nullptr, stream) : 0;
+}
+
+extern "C" int vbx_attn_delta_consistent(const void* q16, const void* k16, const void* v, const uint8_t* mask, const void* dout,
+                                         const float* lse, float* delta, int B, int H, int Np, void* stream) {
+  VBX_REQUIRE(q16 && k16 && v && dout && lse && delta, "vbx_attn_delta_consistent: null pointer");
+  VBX_REQUIRE(B > 0 && H > 0 && Np > 0 && (long)B * H <= 65535, "vbx_attn_delta_consistent: bad dims (B * H <= 65535)");
+  hipLaunchKernelGGL(attn_delta_consistent_kernel, dim3(cdiv(Np, 64), B * H), dim3(256), 0, (hipStream_t)stream, (const u16*)q16,
+                     (const u16*)k16, (const u16*)v, mask, (const u16*)dout, lse, delta, H, Np);
+  VBX_LAUNCH_CHECK();
+  return 0;
 }
 
 extern "C" int vbx_attn_bwd(const void* q16, const void* k16, const void* qb, const void* kb, const void* v,

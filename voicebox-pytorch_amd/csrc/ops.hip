@@ -116,7 +116,7 @@ __global__ void pack_embed_text_kernel(const float* __restrict__ x, const float*
 __global__ void pack_phoneme_kernel(const long* __restrict__ ids, const float* __restrict__ table, int E,
                                     const float* __restrict__ cond, int S, const uint8_t* __restrict__ cmask,
                                     const uint8_t* __restrict__ drop, const float* __restrict__ null_cond,
-                                    u16* __restrict__ out, int B, int N, int D) {
+                                    u16* __restrict__ out, u16* __restrict__ outb, float* __restrict__ emb32, int B, int N, int D) {
   const int ce = E / 8, cpr = ce + D / 8;
   const long total = (long)B * N * cpr;
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
@@ -130,6 +130,10 @@ __global__ void pack_phoneme_kernel(const long* __restrict__ ids, const float* _
       const float* src = table + id * E + c * 8;
 #pragma unroll
       for (int k = 0; k < 8; k++) v[k] = src[k];
+      if (emb32) {  // training: the embedding rows themselves, unrounded (the aligner's keys)
+        *reinterpret_cast<float4*>(emb32 + row * E + c * 8) = make_float4(v[0], v[1], v[2], v[3]);
+        *reinterpret_cast<float4*>(emb32 + row * E + c * 8 + 4) = make_float4(v[4], v[5], v[6], v[7]);
+      }
     } else {
       const int d = (c - ce) * 8;
       const long crow = (long)b * S + n;
@@ -143,6 +147,7 @@ __global__ void pack_phoneme_kernel(const long* __restrict__ ids, const float* _
       }
     }
     *reinterpret_cast<uint4*>(out + row * (long)(E + D) + (long)c * 8) = pack8_h(v);
+    if (outb) *reinterpret_cast<uint4*>(outb + row * (long)(E + D) + (long)c * 8) = pack8(v);  // training: the wgrad's operand
   }
 }
 // to_pred = Linear(dim, 1) + Rearrange('... 1 -> ...') (:672-675): one wave per row.
@@ -1619,7 +1624,21 @@ extern "C" int vbx_pack_phoneme_input(const long* ids, const float* table, int E
   VBX_REQUIRE(!drop_mask || null_cond, "vbx_pack_phoneme_input: a drop mask needs null_cond");
   const long chunks = (long)B * N * (D + E) / 8;
   hipLaunchKernelGGL(pack_phoneme_kernel, dim3(grid_for(chunks)), dim3(256), 0, ST, ids, table, E, cond, S, cond_mask, drop_mask,
-                     null_cond, (u16*)out_f16, B, N, D);
+                     null_cond, (u16*)out_f16, (u16*)nullptr, (float*)nullptr, B, N, D);
+  VBX_LAUNCH_CHECK();
+  return 0;
+}
+// the training forward's variant: the same fp16 rows and, in the same launch, their bf16 copy (operand of the to_embed weight gradient)
+// and / or the gathered embedding rows in fp32 [B*N, E]
+extern "C" int vbx_pack_phoneme_input_train(const long* ids, const float* table, int E, const float* cond, int S,
+                                            const uint8_t* cond_mask, const uint8_t* drop_mask, const float* null_cond,
+                                            void* out_f16, void* out_bf16, float* emb_f32, int B, int N, int D, void* stream) {
+  VBX_REQUIRE(ids && table && cond && out_f16 && B > 0 && N > 0 && S > 0 && D % 8 == 0 && E > 0 && E % 8 == 0,
+              "vbx_pack_phoneme_input_train: bad args");
+  VBX_REQUIRE(!drop_mask || null_cond, "vbx_pack_phoneme_input_train: a drop mask needs null_cond");
+  const long chunks = (long)B * N * (D + E) / 8;
+  hipLaunchKernelGGL(pack_phoneme_kernel, dim3(grid_for(chunks)), dim3(256), 0, ST, ids, table, E, cond, S, cond_mask, drop_mask,
+                     null_cond, (u16*)out_f16, (u16*)out_bf16, emb_f32, B, N, D);
   VBX_LAUNCH_CHECK();
   return 0;
 }

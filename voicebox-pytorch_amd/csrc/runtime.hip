@@ -982,8 +982,15 @@ extern "C" int vbx_model_backward_layer(const vbx_model* m, const vbx_io* io, in
   // point runs its own pass over O and dO.)
   { ProfScope ps("dgrad to_out", st); CK(gemm_nn_bf16(dxb_attn, d.D, wl.out, d.I, M, d.I, d.D, a.dO, d.I, st)); }
   CK(wgrad(dxb_attn, d.D, y.o, d.I, d.D, d.I, d.M, slabs + 2 * sfl, Gd + o[VBX_L_OUTW], d.D, d.I, 0, 0, st, &wj, wgp, gs, sq_at(2)));
+  // The stand-alone stack on a short sequence (phonemes under a masked, per-row loss: DurationPredictor training) takes delta from the
+  // backward's own operands, vbx_attn_delta_consistent: include/vbx.h says what that buys.  Attention dropout keeps the streaming pass.
+  const bool own_delta = m->stack_only && d.Np <= VBX_ATTN_DELTA_CONSISTENT_MAX_NP && !(drop_on && m->attn_dropout > 0.f);
+  if (own_delta) {
+    ProfScope ps("bwd attention delta", st);
+    CK(vbx_attn_delta_consistent(y.q16, y.k16, y.v, attn_mask_p, a.dO, y.lse, a.delta, d.B, d.H, d.Np, stream));
+  }
   { ProfScope ps("bwd attention", st);
-    CK(vbx_attn_bwd_fused_dropout(y.q16, y.k16, y.qb, y.kb, y.v, attn_mask_p, y.oh, 1, a.dO, y.lse, a.delta, y.qrn, y.krn, q_gamma, k_gamma,
+    CK(vbx_attn_bwd_fused_dropout(y.q16, y.k16, y.qb, y.kb, y.v, attn_mask_p, own_delta ? nullptr : y.oh, 1, a.dO, y.lse, a.delta, y.qrn, y.krn, q_gamma, k_gamma,
                                   m->rot_cos, m->rot_sin, m->qk_norm ? 8.0f : 0.0f, dqkv, 3 * d.I, gpart, d.B, d.H, d.Np, m->attn_scale,
                                   a.attn_scratch, drop_on ? y.dbr : nullptr, y.dbc, m->attn_dropout, stream)); }
   { ProfScope ps("dgrad to_qkv", st); CK(gemm_nn_bf16(dqkv, 3 * d.I, wl.qkv, d.D, M, d.D, 3 * d.I, a.dhn, d.D, st)); }

@@ -1,22 +1,44 @@
-"""DurationPredictor inference on the native kernels.
+"""DurationPredictor on the native kernels, inference and training.
 
-Mirrors voicebox_pytorch.py:596-839 -- same constructor keywords, module tree and state-dict keys (`to_phoneme_emb`,
-`to_embed`, `null_cond`, `conv_embed.dw_conv1d.0`, `transformer.*`, `to_pred.0`) -- for the path the sampler uses
-(:1231-1241): `forward` in eval mode, `forward_with_cond_scale` (:694-727) and `align_phoneme_ids_with_durations` (:689-692).
-Compute: vbx_pack_phoneme_input (embedding gather + condition masking / dropping / curtail_or_pad, fp16) -> vbx_gemm
-(to_embed) -> vbx_convpos_fwd (+ residual) -> the native Transformer stack (plain RMSNorm, no registers) -> vbx_rowdot (to_pred).
+Mirrors voicebox_pytorch.py:596-876 -- same constructor keywords, module tree and state-dict keys (`to_phoneme_emb`, `to_embed`,
+`null_cond`, `conv_embed.dw_conv1d.0`, `transformer.*`, `to_pred.0`).
 
-Not built, and raising instead of silently differing:
-  * training: the reference's training branch (:841-876) computes its L1 loss on the hidden state rather than the predicted
-    durations and needs a Transformer backward of its own; `.train()(...)` raises;
-  * `tokenizer` / `texts` (espeak phonemizer, third-party) and `audio_enc_dec` (codecs are out of scope): pass `phoneme_ids`.
+eval(): `forward` (:757-839), `forward_with_cond_scale` (:694-727) and `align_phoneme_ids_with_durations` (:689-692), the path the
+sampler uses (:1231-1241).  Compute: vbx_pack_phoneme_input (embedding gather + condition masking / dropping / curtail_or_pad, fp16)
+-> vbx_gemm (to_embed) -> vbx_convpos_fwd (+ residual) -> the native Transformer stack (plain RMSNorm, no registers) -> vbx_rowdot.
+
+train(): `forward` returns the loss of :841-876, a 0-dim fp32 tensor on the device, and `loss.backward()` fills `.grad` of
+`to_pred.0`, every `transformer.*` parameter, `conv_embed.dw_conv1d.0`, `to_embed`, `to_phoneme_emb.weight` (and `aligner.*`, see
+below).  Two branches:
+  * aligner branch -- all of `mel [B, T, dim_in], phoneme_len, mel_len, phoneme_mask, mel_mask` given (needs attach_aligner()):
+    target = forward_aligner(phoneme_emb, phoneme_mask, mel, mel_mask)[0]; the phoneme embedding the aligner reads is the same
+    differentiable tensor that feeds to_embed; a passed `target=` is ignored, as in the reference;
+  * given durations -- none of the five given, `target=` [B, n] (any float or int dtype); no aligner needed.
+  loss_mask = cond_mask & self_attn_mask; loss = mean_b( sum_n m |d - t| / max(sum_n m, 1e-5) ).
+Two decisions:
+  1. The L1 is taken on the PREDICTED durations d = to_pred(x).  The reference writes F.l1_loss(x, target) with x the hidden state
+     [b, n, dim] against [b, n], which only broadcasts at degenerate shapes; this branch is therefore unpinned against the reference
+     by construction, and its yardstick is the fp64 restatement tests/duration_train_ref.py.
+  2. As in the reference, ForwardSumLoss(alignment_logprob, phoneme_len, mel_len) is added only with
+     return_aligned_phoneme_ids=True.  With the default False the aligner receives NO gradient (alignment_hard is not
+     differentiable) and its `.grad` stays None.
+What raises instead of silently differing: some but not all of the five inputs (AssertionError, the reference's message); none of
+them and no `target=` (NotImplementedError); the aligner branch without attach_aligner() (RuntimeError); `cond.shape[1] !=
+phoneme_ids.shape[-1]` in training (ValueError: cond_mask & self_attn_mask cannot broadcast); `cond.requires_grad`
+(NotImplementedError: the condition gets no gradient; null_cond has requires_grad=False and gets none either); CPU tensors (VbxError).
+The path is three autograd nodes, each testable alone: _FrontEndFn (pack -> to_embed -> conv_embed + residual), the Transformer's
+_StackFn, _HeadFn (to_pred + loss: csrc/duration.hip).  No host synchronisation in forward or backward; no atomics: the same seed
+gives the same bits, the table gradient included.  ff_dropout / attn_dropout are live in train().  The activation arena of the
+stand-alone Transformer holds ONE training forward per (B, n): run backward before the next training forward of the same shape.
+
+Not built: `tokenizer` / `texts` (espeak phonemizer, third-party) and `audio_enc_dec` (codecs are out of scope): pass `phoneme_ids`.
 
 The aligner (align.py: `Aligner`, `maximum_path`, `ForwardSumLoss`) is optional.  By default `self.aligner` is None, `aligner.*`
 entries of a reference checkpoint are skipped on load and `state_dict()` has no such keys.  `attach_aligner()` builds
 `Aligner(dim_hidden=dim_phoneme_emb, **aligner_kwargs)` (or takes a given one); from then on `aligner.*` keys are loaded and saved,
 `forward_aligner` (:730-754) returns the reference's four alignment tensors, and `align_phoneme_ids(mel, phoneme_ids)` gives the
-frame-aligned phoneme ids that a text-conditioned VoiceBox takes as `cond_token_ids`.  The aligner is trained with
-ForwardSumLoss(aligner(...)[1], ...): its parameters are ordinary parameters of this module once attached.
+frame-aligned phoneme ids that a text-conditioned VoiceBox takes as `cond_token_ids`.  Its parameters are ordinary parameters of
+this module once attached.
 """
 from random import random
 
@@ -24,7 +46,7 @@ import torch
 from torch import nn
 
 from . import _lib
-from .align import Aligner, maximum_path
+from .align import Aligner, forward_sum_loss, maximum_path
 from .masks import mask_from_frac_lengths, prob_mask_like, take_draw
 from .model import ConvPositionEmbed, Transformer, exists
 
@@ -54,8 +76,8 @@ class DurationPredictor(nn.Module):
             raise NotImplementedError("the espeak phoneme Tokenizer is third-party: pass num_phoneme_tokens and call with phoneme_ids")
         if dim_phoneme_emb % 8 != 0:
             raise NotImplementedError("dim_phoneme_emb must be a multiple of 8 (vectorised embedding gather)")
-        # ff_dropout / attn_dropout go to the Transformer as in the reference (:631-642); this module only runs in eval mode (forward
-        # raises while .training), where nn.Dropout is the identity, so they never change a result here
+        # ff_dropout / attn_dropout go to the Transformer as in the reference (:631-642): the identity in eval mode, live in train()
+        # (the stack's own dropout, seeded from torch's generator)
         self.audio_enc_dec = None
         self.proj_in = nn.Identity()
         self.tokenizer = None
@@ -146,45 +168,54 @@ class DurationPredictor(nn.Module):
             return durations
         return durations, self.align_phoneme_ids_with_durations(phoneme_ids.to(durations.device), durations)
 
+    def _resolve(self, cond, phoneme_ids, cond_mask, cond_drop_prob, self_attn_mask):
+        """The shared host part of :774-809 on the device of the parameters: (cond fp32, ids, cond_mask bool, its uint8 copy, the
+        classifier-free-guidance drop uint8 or None, self_attn_mask bool, its uint8 copy).  No host synchronisation."""
+        dev = self.device
+        cond = cond.detach().to(dev, torch.float32).contiguous()
+        batch, seq_len, cond_dim = cond.shape
+        assert cond_dim == self.dim
+        ids = phoneme_ids.to(dev, torch.long).contiguous()
+        assert ids.ndim == 2 and ids.shape[0] == batch
+        if not exists(cond_mask):  # :786-791
+            coin = take_draw("coin")
+            if (random() < 0.5) if coin is None else bool(coin):
+                frac = take_draw("frac_lengths")
+                if frac is None:
+                    frac = torch.zeros((batch,), device=dev).float().uniform_(*self.frac_lengths_mask)
+                cond_mask = mask_from_frac_lengths(seq_len, frac.to(dev))
+            else:
+                cond_mask = prob_mask_like((batch, seq_len), self.p_drop_prob, dev)
+        cond_mask = cond_mask.to(dev)
+        cmask = cond_mask.to(torch.uint8).contiguous()
+        drop = None
+        if cond_drop_prob > 0.:  # :797-804
+            drop = take_draw("cond_drop")
+            drop = prob_mask_like((batch,), cond_drop_prob, dev) if drop is None else drop.to(dev)
+            drop = drop.to(torch.uint8).contiguous()
+        if not exists(self_attn_mask):
+            self_attn_mask = ids != -1  # :808-809 (phoneme id -1 is padding)
+        amask = self_attn_mask.to(dev).to(torch.bool)
+        return cond, ids, cond_mask, cmask, drop, amask, amask.to(torch.uint8).contiguous()
+
     def forward(self, *, cond, texts=None, phoneme_ids=None, cond_drop_prob=0., target=None, cond_mask=None, mel=None,
                 phoneme_len=None, mel_len=None, phoneme_mask=None, mel_mask=None, self_attn_mask=None,
-                return_aligned_phoneme_ids=False):  # voicebox_pytorch.py:757-839
-        if self.training:
-            raise NotImplementedError(
-                "DurationPredictor training needs naturalspeech2_pytorch's Aligner / maximum_path (third-party, absent); "
-                "call .eval() -- the inference path is what ConditionalFlowMatcherWrapper.sample uses")
+                return_aligned_phoneme_ids=False):  # voicebox_pytorch.py:757-876
+        """eval mode: the durations fp32 [B, n] (and the frame-aligned ids with return_aligned_phoneme_ids).  train mode: the loss,
+        a 0-dim fp32 tensor on the device (see the module docstring for the two branches and what raises)."""
         if exists(texts) or not exists(phoneme_ids):
             raise NotImplementedError("texts need the espeak Tokenizer (third-party): pass phoneme_ids")
+        if self.training:
+            return self._forward_train(cond, phoneme_ids, cond_drop_prob, target, cond_mask, mel, phoneme_len, mel_len, phoneme_mask,
+                                       mel_mask, self_attn_mask, return_aligned_phoneme_ids)
         dev = self.device
         if dev.type != "cuda":
             raise _lib.VbxError("DurationPredictor compute runs only on an MI355X (gfx950) through libvbx_hip.so; "
                                 f"parameters are on '{dev}' and there is no CPU fallback")
         with torch.no_grad():
-            cond = cond.to(dev, torch.float32).contiguous()
-            batch, seq_len, cond_dim = cond.shape
-            assert cond_dim == self.dim
-            ids = phoneme_ids.to(dev, torch.long).contiguous()
-            assert ids.ndim == 2 and ids.shape[0] == batch
+            cond, ids, _, cmask, drop, amask, am8 = self._resolve(cond, phoneme_ids, cond_mask, cond_drop_prob, self_attn_mask)
+            batch, seq_len, _ = cond.shape
             n = ids.shape[-1]
-            if not exists(cond_mask):  # :786-791
-                coin = take_draw("coin")
-                if (random() < 0.5) if coin is None else bool(coin):
-                    frac = take_draw("frac_lengths")
-                    if frac is None:
-                        frac = torch.zeros((batch,), device=dev).float().uniform_(*self.frac_lengths_mask)
-                    cond_mask = mask_from_frac_lengths(seq_len, frac.to(dev))
-                else:
-                    cond_mask = prob_mask_like((batch, seq_len), self.p_drop_prob, dev)
-            cmask = cond_mask.to(dev).to(torch.uint8).contiguous()
-            drop = None
-            if cond_drop_prob > 0.:  # :797-804
-                drop = take_draw("cond_drop")
-                drop = prob_mask_like((batch,), cond_drop_prob, dev) if drop is None else drop.to(dev)
-                drop = drop.to(torch.uint8).contiguous()
-            if not exists(self_attn_mask):
-                self_attn_mask = ids != -1  # :808-809 (phoneme id -1 is padding)
-            amask = self_attn_mask.to(dev).to(torch.bool)
-            am8 = amask.to(torch.uint8).contiguous()
             E, D = self.dim_phoneme_emb, self.dim
             st = _lib.current_stream()
             packed = torch.empty(batch * n, E + D, dtype=torch.float16, device=dev)
@@ -193,13 +224,7 @@ class DurationPredictor(nn.Module):
             w16 = self.to_embed.weight.detach().to(torch.float16).contiguous()
             bias = self.to_embed.bias.detach().float().contiguous()
             e = torch.empty(batch * n, D, dtype=torch.float32, device=dev)
-            d = _lib.GemmDesc()
-            d.mode, d.epilogue, d.M, d.N, d.K = _lib.VBX_GEMM_NT, _lib.VBX_EPI_F32, batch * n, D, E + D
-            d.lda, d.ldb, d.ldc, d.f16 = E + D, E + D, D, 1
-            d.A, d.B, d.C, d.bias = packed.data_ptr(), w16.data_ptr(), e.data_ptr(), bias.data_ptr()
-            rc = _lib.lib().vbx_gemm(d, st)  # to_embed (:823-824)
-            if rc != 0:
-                raise _lib.VbxError(f"vbx_gemm failed (rc={rc}): {_lib.lib().vbx_last_error().decode()}")
+            _gemm(_lib.VBX_GEMM_NT, _lib.VBX_EPI_F32, batch * n, D, E + D, packed, E + D, w16, E + D, e, D, bias=bias, f16=1)  # :823-824
             conv = self.conv_embed.dw_conv1d[0]
             x = torch.empty(batch, n, D, dtype=torch.float32, device=dev)
             _lib.call("vbx_convpos_fwd", e, conv.weight.detach().float().contiguous(), conv.bias.detach().float().contiguous(), am8,
@@ -212,3 +237,146 @@ class DurationPredictor(nn.Module):
         if not return_aligned_phoneme_ids:
             return durations
         return durations, self.align_phoneme_ids_with_durations(ids.clamp(min=0), durations)  # ids clamped as :811 does before :839
+
+    def _forward_train(self, cond, phoneme_ids, cond_drop_prob, target, cond_mask, mel, phoneme_len, mel_len, phoneme_mask, mel_mask,
+                       self_attn_mask, return_aligned_phoneme_ids):  # voicebox_pytorch.py:841-876
+        five = (mel, phoneme_len, mel_len, phoneme_mask, mel_mask)
+        given = sum(exists(el) for el in five)
+        assert given in (0, 5), \
+            'need to pass phoneme_len, mel_len, phoneme_mask, mel_mask, to train duration predictor module'
+        use_aligner = given == 5
+        if not use_aligner and not exists(target):
+            raise NotImplementedError("DurationPredictor training needs its targets: pass target= (durations [B, n]), or attach an "
+                                      "aligner (attach_aligner()) and pass mel, phoneme_len, mel_len, phoneme_mask and mel_mask")
+        if use_aligner:
+            self._need_aligner("forward (training on the aligner's durations)")
+        if cond.ndim != 3 or phoneme_ids.ndim != 2 or cond.shape[1] != phoneme_ids.shape[-1]:
+            raise ValueError("DurationPredictor training: cond [B, n, dim] must have the length of phoneme_ids [B, n] (got "
+                             f"{tuple(cond.shape)} and {tuple(phoneme_ids.shape)}): the loss mask is cond_mask & self_attn_mask")
+        if cond.requires_grad:
+            raise NotImplementedError("DurationPredictor training passes no gradient to cond: detach it")
+        dev = self.device
+        if dev.type != "cuda":
+            raise _lib.VbxError("DurationPredictor compute runs only on an MI355X (gfx950) through libvbx_hip.so; "
+                                f"parameters are on '{dev}' and there is no CPU fallback")
+        cond, ids, cond_mask, cmask, drop, amask, am8 = self._resolve(cond, phoneme_ids, cond_mask, cond_drop_prob, self_attn_mask)
+        batch, n = ids.shape
+        conv, pred = self.conv_embed.dw_conv1d[0], self.to_pred[0]
+        x, emb = _FrontEndFn.apply(self, ids, cond, cmask, drop, am8, use_aligner, self.to_phoneme_emb.weight, self.to_embed.weight,
+                                   self.to_embed.bias, conv.weight, conv.bias)
+        hid = self.transformer(x, mask=amask)  # :828-831 (_StackFn)
+        align_loss = None
+        if use_aligner:  # :847-848; a passed target= is overwritten there and never read
+            target, _, logprob, _ = self.forward_aligner(emb, phoneme_mask.to(dev), mel.to(dev), mel_mask.to(dev))
+            if return_aligned_phoneme_ids:  # :868-874: only then does the aligner receive a gradient
+                align_loss = forward_sum_loss(logprob, phoneme_len.to(dev), mel_len.to(dev))
+        else:
+            target = target.detach().to(dev)
+            if target.shape != (batch, n):
+                raise ValueError(f"DurationPredictor training: target must be [B, n] = {(batch, n)} (got {tuple(target.shape)})")
+        loss_mask = (cond_mask.to(torch.bool) & amask).to(torch.uint8).contiguous()  # :851
+        loss = _HeadFn.apply(hid, pred.weight, pred.bias, target.to(torch.float32).contiguous(), loss_mask)
+        return loss if align_loss is None else loss + align_loss
+
+
+def _gemm(mode, epi, M, N, K, A, lda, B, ldb, C, ldc, bias=None, f16=0, splits=0):
+    d = _lib.GemmDesc()
+    d.mode, d.epilogue, d.M, d.N, d.K, d.lda, d.ldb, d.ldc, d.f16, d.splits = mode, epi, M, N, K, lda, ldb, ldc, f16, splits
+    d.A, d.B, d.C, d.bias = A.data_ptr(), B.data_ptr(), C.data_ptr(), None if bias is None else bias.data_ptr()
+    rc = _lib.lib().vbx_gemm(d, _lib.current_stream())
+    if rc != 0:
+        raise _lib.VbxError(f"vbx_gemm failed (rc={rc}): {_lib.lib().vbx_last_error().decode()}")
+
+
+class _FrontEndFn(torch.autograd.Function):
+    """pack -> to_embed -> conv_embed + residual (:811-826) as one node.  Outputs x [B, n, D] and, when asked, the phoneme embedding
+    [B, n, E] that the aligner reads: the same rows that sit in columns 0:E of the packed operand, so the table gradient is one
+    deterministic sum over both consumers (vbx_phoneme_emb_bwd).  cond and null_cond receive no gradient."""
+
+    @staticmethod
+    def forward(ctx, mod, ids, cond, cmask, drop, am8, want_emb, table, we, be, cw, cb):
+        dev, st = ids.device, _lib.current_stream()
+        B, n = ids.shape
+        E, D, M = mod.dim_phoneme_emb, mod.dim, B * n
+        table32 = table.detach().float().contiguous()
+        packed = torch.empty(M, E + D, dtype=torch.float16, device=dev)
+        packed_b = torch.empty(M, E + D, dtype=torch.bfloat16, device=dev)
+        emb = torch.empty(B, n, E, dtype=torch.float32, device=dev) if want_emb else None
+        _lib.call("vbx_pack_phoneme_input_train", ids, table32, E, cond, cond.shape[1], cmask, drop,
+                  mod.null_cond.detach().float().contiguous(), packed, packed_b, emb, B, n, D, st)
+        e = torch.empty(M, D, dtype=torch.float32, device=dev)
+        _gemm(_lib.VBX_GEMM_NT, _lib.VBX_EPI_F32, M, D, E + D, packed, E + D, we.detach().to(torch.float16).contiguous(), E + D, e, D,
+              bias=be.detach().float().contiguous(), f16=1)
+        cw32, cb32 = cw.detach().float().contiguous(), cb.detach().float().contiguous()
+        x = torch.empty(B, n, D, dtype=torch.float32, device=dev)
+        _lib.call("vbx_convpos_fwd", e, cw32, cb32, am8, None, x, B, n, 0, D, mod.ksize, st)
+        ctx.save_for_backward(ids, am8, packed_b, e, cw32, cb32, we)
+        ctx.dims = (B, n, E, D, mod.ksize, table.shape[0])
+        ctx.set_materialize_grads(False)
+        return x, emb
+
+    @staticmethod
+    def backward(ctx, gx, gemb):
+        ids, am8, packed_b, e, cw32, cb32, we = ctx.saved_tensors
+        B, n, E, D, ks, V = ctx.dims
+        M, dev, st = B * n, ids.device, _lib.current_stream()
+        if gx is None and gemb is None:
+            return (None,) * 12
+        dwe = dbe = dcw = dcb = dpk = None
+        if gx is not None:
+            chunks = _lib.lib().vbx_convpos_bwd_chunks(B, n)
+            dpre = torch.empty(M, D, dtype=torch.float32, device=dev)
+            de = torch.empty(M, D, dtype=torch.float32, device=dev)
+            deb = torch.empty(M, D, dtype=torch.bfloat16, device=dev)
+            wpart = torch.zeros(chunks, D, 64, dtype=torch.float32, device=dev)
+            _lib.call("vbx_convpos_bwd", e, cw32, cb32, am8, gx.to(torch.float32).contiguous(), dpre, de, deb, wpart, None, B, n, 0, D,
+                      ks, st)
+            dcw = torch.empty(cw32.shape, dtype=torch.float32, device=dev)
+            dcb = torch.empty(D, dtype=torch.float32, device=dev)
+            _lib.call("vbx_conv_wgrad_finalize", wpart, chunks, D, ks, dcw, dcb, st)
+            dbe = torch.empty(D, dtype=torch.float32, device=dev)
+            scratch = torch.empty(_lib.lib().vbx_colsum_scratch_floats(M, D), dtype=torch.float32, device=dev)
+            _lib.call("vbx_colsum_f32", de, M, D, D, dbe, scratch, st)
+            splits = max(1, min(8, M // 256))  # every split keeps rows, as the aligner's weight gradients
+            slabs = torch.empty(splits, D, E + D, dtype=torch.float32, device=dev)
+            _gemm(_lib.VBX_GEMM_TN, _lib.VBX_EPI_SPLITK, D, E + D, M, deb, D, packed_b, E + D, slabs, E + D, splits=splits)
+            dwe = torch.empty(D, E + D, dtype=torch.float32, device=dev)
+            _lib.call("vbx_splitk_reduce", slabs, splits, D, E + D, dwe, D, E + D, E + D, 0, 0, 0, st)
+            if ctx.needs_input_grad[7]:  # d(packed)[:, 0:E] only: the condition columns need no gradient
+                dpk = torch.empty(M, E, dtype=torch.float32, device=dev)
+                _gemm(_lib.VBX_GEMM_NN, _lib.VBX_EPI_F32, M, E, D, deb, D, we.detach().to(torch.bfloat16).contiguous(), E + D, dpk, E)
+        gtable = None
+        if ctx.needs_input_grad[7] and (dpk is not None or gemb is not None):
+            gtable = torch.empty(V, E, dtype=torch.float32, device=dev)
+            ge = None if gemb is None else gemb.to(torch.float32).contiguous()
+            _lib.call("vbx_phoneme_emb_bwd", ids, dpk, E, ge, gtable, M, V, E, st)
+        return None, None, None, None, None, None, None, gtable, dwe, dbe, dcw, dcb
+
+
+class _HeadFn(torch.autograd.Function):
+    """to_pred + the masked L1 of :858-866 on the predicted durations: vbx_duration_head_fwd / _bwd."""
+
+    @staticmethod
+    def forward(ctx, hid, w, b, target, m8):
+        B, n, D = hid.shape
+        dev, st = hid.device, _lib.current_stream()
+        hid = hid.detach().to(torch.float32).contiguous()
+        w32, b32 = w.detach().float().contiguous(), b.detach().float().contiguous()
+        durations = torch.empty(B, n, dtype=torch.float32, device=dev)
+        num, den = torch.empty(B, dtype=torch.float32, device=dev), torch.empty(B, dtype=torch.float32, device=dev)
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        _lib.call("vbx_duration_head_fwd", hid, w32, b32, target, m8, durations, num, den, loss, B, n, D, st)
+        ctx.save_for_backward(hid, w32, durations, target, m8, den)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        hid, w32, durations, target, m8, den = ctx.saved_tensors
+        B, n, D = hid.shape
+        dev = hid.device
+        dhid = torch.empty_like(hid)
+        dw, db = torch.empty(1, D, dtype=torch.float32, device=dev), torch.empty(1, dtype=torch.float32, device=dev)
+        scratch = torch.empty(_lib.lib().vbx_duration_head_bwd_scratch_floats(B, n, D), dtype=torch.float32, device=dev)
+        _lib.call("vbx_duration_head_bwd", hid, w32, durations, target, m8, den, g.detach().to(torch.float32).reshape(1).contiguous(),
+                  dhid, dw, db, scratch, B, n, D, _lib.current_stream())
+        return dhid, dw, db, None, None
