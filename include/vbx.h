@@ -96,7 +96,7 @@ typedef struct {
 
 int vbx_gemm(const vbx_gemm_desc* d, void* stream);
 /* Tuning knob (results are identical up to fp32 summation order): which tile serves vbx_gemm / the grouped launch.
- * 0 automatic per shape (default; environment VBX_GEMM_PATH=<n> presets it), 1 the 128-wide kernels only, 2 the 256 x 256
+ * 0 automatic per shape (default; the environment preset VBX_GEMM_PATH was last in commit bb5b90c), 1 the 128-wide kernels only, 2 the 256 x 256
  * 8-wave kernel (gemm3.hip) wherever it can serve, 3 the 128 x 256 two-workgroups-per-CU kernel (gemm4.hip) wherever it can,
  * 4 = 0 with the weight-stationary kernel (gemm5.hip) on even when VBX_GEMM5=0.  Not thread safe; call before launching work. */
 int vbx_gemm_select(int path);
@@ -173,7 +173,8 @@ int vbx_attn_fwd(const void* q16, const void* k16, const void* v16 /* fp16 */, c
  * dq,dk fp32 [B,H,Np,64]; dv is written bf16 token-major at dv[(b*Np+n)*dv_ld + h*64 + d].
  * One kernel family serves it: the TWO-BODY kernel -- dq and dk/dv bodies in one launch, S / dP evaluated in both, no inter-workgroup
  * waits, deterministic.  By default its softmax statistics are folded into the MFMA accumulator (csrc/attn_bwd_fold.inc: P = exp2(-(L - q.k))
- * with L added inside the matrix pipe); vbx_attn_bwd_select(3) / VBX_ATTN_BWD_FOLD=0 runs the same bodies without the fold (round 3's
+ * with L added inside the matrix pipe); vbx_attn_bwd_select(3) runs the same bodies without the fold (the environment
+ * switch VBX_ATTN_BWD_FOLD=0 that did the same was last in commit bb5b90c) (round 3's
  * arithmetic -- what attention dropout always uses); the two differ by fp32 rounding of the exponent only.  Tail tiles of <= 16 rows
  * (Np % 128 <= 16: the register tokens) run a 16 x 16 MFMA role with their ring rows split over the waves (csrc/attn_bwd_ragged.inc).
  * Round 3's ONE-PASS chain kernel (select 2: S / dP once, dq summed by an ordered chain of workgroups through device memory) was correct

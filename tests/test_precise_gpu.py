@@ -284,7 +284,7 @@ def test_precise_cfg4_reference_init_all_seeds(golden):
     print("PRECISE cfg4 reference-init total-gradient-norm relative differences (bf16-operand backward)", {k: round(v, 3) for k, v in gtot.items()})
     # A chaotic statistic (reference init: the forward here is exact to ~1e-6, the bf16-operand backward is the fast path's): measured
     # 1.5 - 9.8 % in round 5 and 7.2 - 15.2 % in round 6 on the same six seeds after the row-norm kernels changed their fp32 summation
-    # ORDER (outputs equal to 1e-7, tools A/B with VBX_RMS_LEAN=0) -- two draws of the same distribution (the fast path: 5 - 17 %).  The
+    # ORDER (outputs equal to 1e-7, A/B against the generic kernels with VBX_RMS_LEAN=0, a switch last in commit bb5b90c) -- two draws of the same distribution (the fast path: 5 - 17 %).  The
     # backward itself is pinned tightly where the problem is well posed (test_model_gpu.py: *_wc goldens, every gradient norm 0.3 %).
     assert max(gtot.values()) < 0.25, gtot
     mean_abs = sum(abs(v) for v in diffs.values()) / len(diffs)

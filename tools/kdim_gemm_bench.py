@@ -1,7 +1,8 @@
 """Stand-alone timing of the two K = dim forward GEMMs with their real fused epilogues at the benchmark shape (dim 512, 16 heads,
 B = 8 x 1040 rows): to_qkv (+ MultiheadRMSNorm + rotary + head split) and FeedForward-in (+ GEGLU), each as the training step
 launches it (fp16 + bf16 outputs, saved pre-activation) and as the sampler does (fp16 outputs only).  Descriptors mirror
-csrc/runtime.hip.  Usage: python tools/kdim_gemm_bench.py [iters]   (VBX_GEMM_PATH / VBX_GEMM_ABL apply)."""
+csrc/runtime.hip.  Usage: python tools/kdim_gemm_bench.py [iters]   (vbx_gemm_select picks the kernel family; VBX_GEMM5=0 the tiled
+kernels)."""
 import math, os, sys, torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

@@ -184,9 +184,8 @@ int main(int argc, char** argv) {
     }
     return 0;
   }
-  if (argc > 1 && !strcmp(argv[1], "time")) {  // back-to-back launch times of all three tiles (VBX_GEMM_STAGGER A/B: one process per value)
+  if (argc > 1 && !strcmp(argv[1], "time")) {  // back-to-back launch times of all three tiles
     struct { const char* n; vbx_gemm_desc* d; } L[5] = {{"plain bf16 N=3072", &plain}, {"to_qkv eval", &qkv}, {"to_qkv train", &qkvt}, {"ff_in eval", &ff}, {"ff_in train", &fft}};
-    printf("stagger %s us:", getenv("VBX_GEMM_STAGGER") ? getenv("VBX_GEMM_STAGGER") : "0");
     for (auto& l : L) {
       printf("  %s", l.n);
       for (int path = 1; path <= 3; path++) {

@@ -11,7 +11,6 @@
 // and the P^T accumulator registers are already the B operand of the next MFMA (slot s of half hi <->
 // key (s&3) + 8*(s>>2) + 4*hi inside each 16-key group; the V^T fragment uses the same key order).
 #include "common.hpp"
-#include <stdlib.h>
 #include <type_traits>
 
 namespace {
@@ -219,7 +218,9 @@ struct AttnCoord { int tile, h, b; bool ok; };
 // overlap with full workgroups; dispatched last they were a 30 us drain phase with the chip empty (tools/attn_timeline.py).  The short
 // <= 16-row tails of round 6 go LAST instead (attn_xmap_for).
 // xmap bit 0: consecutive ids rotate over the 8 XCDs, all tiles of a (b, h) on one XCD sharing its L2 copy of K / V;
-// bit 1: tails last.
+// bit 1: tails last; bit 2: a <= 16-row tail runs the full-tile role instead of the ragged one.  attn_xmap_for() returns 1 or 3 only:
+// bit 0 clear and bit 2 were reachable through an environment override that was removed (docs/history.md); the arms stay in the
+// device code so that it is instruction for instruction what was measured.
 VBX_DEV int attn_tail_ids(int Np, int BH, int xmap) { return (Np & 127) ? ((xmap & 1) ? ((BH + 7) >> 3) * 8 : BH) : 0; }
 VBX_DEV AttnCoord attn_coord_id(int id, int H, int Np, int BH, int xmap) {
   const int nfull = Np >> 7;
@@ -270,26 +271,6 @@ __device__ unsigned long long* g_attn_trace = nullptr;
 #define ATTN_TRACE_BEGIN()
 #define ATTN_TRACE_LOOP_END()
 #define ATTN_TRACE_END(TAG)
-#endif
-
-// Diagnostic build only (-DVBX_ATTN_STEPTRACE, tools/attn_fwd_steptrace.sh): eight s_memtime stamps (100 MHz) per key tile and wave of the
-// forward kernel -- 0 step entry, 1 behind the barrier and the DMA issue, 2 first K fragments arrived, 3 / 4 first / second S chain issued, 5 softmax done,
-// 6 / 7 first / second P.V block issued; the time between consecutive stamps is summed over the key loop in scalar registers
-// and written once per wave: [workgroup][wave][8 segment sums (segment 0 = stamp 7 -> next stamp 0), first stamp, last stamp].
-#ifdef VBX_ATTN_STEPTRACE
-__device__ unsigned long long* g_attn_steptrace = nullptr;
-#define ATTN_ST_DECL() unsigned long long st_acc_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, st_prev_ = __builtin_amdgcn_s_memtime(), st_first_ = st_prev_
-#define ATTN_ST(i) do { __builtin_amdgcn_sched_barrier(0); const unsigned long long t_ = __builtin_amdgcn_s_memtime(); st_acc_[i] += t_ - st_prev_; st_prev_ = t_; __builtin_amdgcn_sched_barrier(0); } while (0)
-#define ATTN_ST_FLUSH()                                                                                        \
-  if (g_attn_steptrace && (threadIdx.x & 63) == 0) {                                                           \
-    unsigned long long* r_ = g_attn_steptrace + ((size_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 10;            \
-    _Pragma("unroll") for (int i_ = 0; i_ < 8; i_++) r_[i_] = st_acc_[i_];                                     \
-    r_[8] = st_first_; r_[9] = st_prev_;                                                                       \
-  }
-#else
-#define ATTN_ST_DECL()
-#define ATTN_ST(i)
-#define ATTN_ST_FLUSH()
 #endif
 
 // (Rounds 1-2's forward kernels -- the register-staged double buffer and the 3-slot / 3-per-CU LDS-DMA form "v2" -- were removed in
@@ -375,64 +356,6 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_kernel_v3_drop(const u16* __r
 #include "attn_fwd_v3_body.inc"
 }
 #undef VBX_FWD_DROP
-
-#ifdef VBX_ATTN_DIAG  // tools/attn_ablation.sh: timing ablations of the forward step, separate instantiations of the same body
-#define VBX_ABL_KERNEL(N)                                                                                                        \
-  __global__ __launch_bounds__(256, 4) void attn_fwd_kernel_v3_abl##N(const u16* __restrict__ q16, const u16* __restrict__ k16,  \
-                                                                      const u16* __restrict__ vv, const uint8_t* __restrict__ mask, \
-                                                                      u16* __restrict__ out, u16* __restrict__ outb,           \
-                                                                      float* __restrict__ lse, int H, int Np, float scale2, int BH, int xmap)
-#define VBX_FWD_ABL 1
-VBX_ABL_KERNEL(1) { extern __shared__ __attribute__((aligned(16))) char smem[];
-#include "attn_fwd_v3_body.inc"
-}
-#undef VBX_FWD_ABL
-#define VBX_FWD_ABL 6
-VBX_ABL_KERNEL(6) { extern __shared__ __attribute__((aligned(16))) char smem[];
-#include "attn_fwd_v3_body.inc"
-}
-#undef VBX_FWD_ABL
-#define VBX_FWD_ABL 8
-VBX_ABL_KERNEL(8) { extern __shared__ __attribute__((aligned(16))) char smem[];
-#include "attn_fwd_v3_body.inc"
-}
-#undef VBX_FWD_ABL
-#define VBX_FWD_ABL 14
-VBX_ABL_KERNEL(14) { extern __shared__ __attribute__((aligned(16))) char smem[];
-#include "attn_fwd_v3_body.inc"
-}
-#undef VBX_FWD_ABL
-#define VBX_FWD_ABL 16
-VBX_ABL_KERNEL(16) { extern __shared__ __attribute__((aligned(16))) char smem[];
-#include "attn_fwd_v3_body.inc"
-}
-#undef VBX_FWD_ABL
-#define VBX_FWD_ABL 49
-VBX_ABL_KERNEL(49) { extern __shared__ __attribute__((aligned(16))) char smem[];
-#include "attn_fwd_v3_body.inc"
-}
-#undef VBX_FWD_ABL
-#define VBX_FWD_ABL 64
-VBX_ABL_KERNEL(64) { extern __shared__ __attribute__((aligned(16))) char smem[];
-#include "attn_fwd_v3_body.inc"
-}
-#undef VBX_FWD_ABL
-#define VBX_FWD_ABL 384
-VBX_ABL_KERNEL(384) { extern __shared__ __attribute__((aligned(16))) char smem[];
-#include "attn_fwd_v3_body.inc"
-}
-#undef VBX_FWD_ABL
-#define VBX_FWD_ABL 63
-VBX_ABL_KERNEL(63) { extern __shared__ __attribute__((aligned(16))) char smem[];
-#include "attn_fwd_v3_body.inc"
-}
-#undef VBX_FWD_ABL
-#define VBX_FWD_ABL 447
-VBX_ABL_KERNEL(447) { extern __shared__ __attribute__((aligned(16))) char smem[];
-#include "attn_fwd_v3_body.inc"
-}
-#undef VBX_FWD_ABL
-#endif
 
 // ---- Round-4 experiments on the forward, measured at the benchmark grid (8 x 16 heads x 1040 rows, stand-alone, same box) and removed:
 //  * "v4": 256-row workgroups, a wave owning TWO 32-query blocks whose chains are interleaved in one instruction stream (S of block B
@@ -704,34 +627,22 @@ __device__ __forceinline__ void attn_bwd_dkdv_dma_body(char* smem, int wg_id, co
     }
     {
       f32x4 l4[4];
-#if defined(VBX_ATTN_ABL_DKDV) && (VBX_ATTN_ABL_DKDV & 1)  // timing ablation (diagnostic builds only): no statistics reads
-      for (int g4 = 0; g4 < 4; g4++) l4[g4] = f32x4{scale, scale, scale, scale};
-#else
       D3_READ128(l4[0], sa, SO + QB * 128); D3_READ128(l4[1], sa, SO + QB * 128 + 32);
       D3_READ128(l4[2], sa, SO + QB * 128 + 64); D3_READ128(l4[3], sa, SO + QB * 128 + 96);
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#endif
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int g4 = 0; g4 < 4; g4++)
 #pragma unroll
         for (int j = 0; j < 4; j++)
-#if defined(VBX_ATTN_ABL_DKDV) && (VBX_ATTN_ABL_DKDV & 2)  // timing ablation: no exponentials
-          s[4 * g4 + j] = fmaf(s[4 * g4 + j], scale2, -l4[g4][j]);
-#else
           s[4 * g4 + j] = fast_exp2(fmaf(s[4 * g4 + j], scale2, -l4[g4][j]));
-#endif
       __builtin_amdgcn_sched_barrier(0);
     }
     {
       f32x4 d4[4];
-#if defined(VBX_ATTN_ABL_DKDV) && (VBX_ATTN_ABL_DKDV & 1)
-      for (int g4 = 0; g4 < 4; g4++) d4[g4] = f32x4{scale2, scale2, scale2, scale2};
-#else
       D3_READ128(d4[0], sa, SO + QB * 128 + 256); D3_READ128(d4[1], sa, SO + QB * 128 + 288);
       D3_READ128(d4[2], sa, SO + QB * 128 + 320); D3_READ128(d4[3], sa, SO + QB * 128 + 352);
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#endif
       __builtin_amdgcn_sched_barrier(0);
       if constexpr (DROP) {
         const unsigned wk = (QB ? wkeep.y : wkeep.x) >> (4 * hi);  // register 4 * g4 + j <-> query 8 * g4 + 4 * hi + j of the block
@@ -1041,7 +952,7 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_kernel_dma(const AttnBwdArgs 
     role = a.role == 1;
   } else {  // launch order: tails of both roles, dk/dv full tiles (the longer ones), dq full tiles
     const int T = attn_tail_ids(a.Np, a.BH, a.xmap), F = a.grid_one - T;
-    if (a.xmap & 2) {  // A/B: tails last
+    if (a.xmap & 2) {  // tails last
       if (id < 2 * F) { role = id >= F; id -= role * F; }
       else { id -= 2 * F; role = id >= T; id += F - role * T; }
     } else if (id < 2 * T) {
@@ -1144,10 +1055,8 @@ static const float LOG2E = 1.4426950408889634f;
 // <= 16 rows runs the short 16 x 16-shaped role (round 6): dispatched first it holds 128 of the 1024 slots while the last full tiles wait;
 // dispatched last it fills the drain of the launch -- same call, tails first -> last: train step 8.86 -> 8.73 ms, 64-interval sample
 // 283.6 -> 279.6 ms (profiles/r06_ab_attn_tails_last.txt).  Longer tails (one to four waves walking the whole key loop at the pace of a
-// full tile) still go first, where they overlap with full workgroups.  VBX_ATTN_XMAP=<bits> overrides.
+// full tile) still go first, where they overlap with full workgroups.
 static int attn_xmap_for(int Np) {
-  static const int forced = getenv("VBX_ATTN_XMAP") ? atoi(getenv("VBX_ATTN_XMAP")) : -1;
-  if (forced >= 0) return forced;
   const int tail = Np & 127;
   return (tail != 0 && tail <= 16) ? 3 : 1;
 }
@@ -1162,7 +1071,7 @@ static int attn_fwd_impl(const void* q16, const void* k16, const void* v, const 
                          float* lse, int B, int H, int Np, float scale, const void* drop_bits_rm, float drop_p, void* stream) {
   VBX_REQUIRE(q16 && k16 && v && out && lse, "vbx_attn_fwd: null pointer");
   VBX_REQUIRE(B > 0 && H > 0 && Np > 0 && scale > 0.f, "vbx_attn_fwd: bad dims");
-  const int xmap = attn_xmap_for(Np);  // VBX_ATTN_XMAP=0: A/B against the plain tile order
+  const int xmap = attn_xmap_for(Np);
   const int BH = B * H;
   dim3 grid(cdiv(Np, 128) * ((xmap & 1) ? cdiv(BH, 8) * 8 : BH));
   if (drop_bits_rm) {  // training-time attention dropout (attend.py:131): the 4-per-CU body with the keep-bit selects
@@ -1173,34 +1082,11 @@ static int attn_fwd_impl(const void* q16, const void* k16, const void* v, const 
     VBX_LAUNCH_CHECK();
     return mask ? attn_empty_batch_fixup(1, v, mask, B, H, Np, drop_bits_rm, drop_p, nullptr, out, out_bf16, (long)H * 64, lse, stream) : 0;
   }
-#ifdef VBX_ATTN_DIAG
-  if (getenv("VBX_FWD_ABL3") && atoi(getenv("VBX_FWD_ABL3")) != 0) {
-    const int a3 = atoi(getenv("VBX_FWD_ABL3"));
-#define VBX_ABL_LAUNCH(N)                                                                                                  \
-  case N:                                                                                                                  \
-    hipLaunchKernelGGL(attn_fwd_kernel_v3_abl##N, grid, dim3(256), A3ST * ASTAGE, (hipStream_t)stream, (const u16*)q16,     \
-                       (const u16*)k16, (const u16*)v, mask, (u16*)out, (u16*)out_bf16, lse, H, Np, QK_UNIT, BH, xmap);     \
-    break;
-    switch (a3) {
-      VBX_ABL_LAUNCH(1) VBX_ABL_LAUNCH(6) VBX_ABL_LAUNCH(8) VBX_ABL_LAUNCH(14) VBX_ABL_LAUNCH(16) VBX_ABL_LAUNCH(49) VBX_ABL_LAUNCH(64)
-      VBX_ABL_LAUNCH(384) VBX_ABL_LAUNCH(63) VBX_ABL_LAUNCH(447)
-      default: VBX_REQUIRE(false, "VBX_FWD_ABL3: no such ablation build");
-    }
-#undef VBX_ABL_LAUNCH
-    VBX_LAUNCH_CHECK();
-    return 0;
-  }
-#endif
   hipLaunchKernelGGL(attn_fwd_kernel_v3, grid, dim3(256), A3ST * ASTAGE, (hipStream_t)stream, (const u16*)q16, (const u16*)k16,
                      (const u16*)v, mask, (u16*)out, (u16*)out_bf16, lse, H, Np, QK_UNIT, BH, xmap);
   VBX_LAUNCH_CHECK();
   return mask ? attn_empty_batch_fixup(1, v, mask, B, H, Np, nullptr, 0.f, nullptr, out, out_bf16, (long)H * 64, lse, stream) : 0;
 }
-#ifdef VBX_ATTN_STEPTRACE
-extern "C" int vbx_debug_attn_steptrace(void* buf) {
-  return hipMemcpyToSymbol(HIP_SYMBOL(g_attn_steptrace), &buf, sizeof(buf)) == hipSuccess ? 0 : -1;
-}
-#endif
 extern "C" float vbx_attn_q_prescale(float scale) { return scale * LOG2E; }
 extern "C" int vbx_attn_fwd(const void* q16, const void* k16, const void* v, const uint8_t* mask, void* out, void* out_bf16,
                             float* lse, int B, int H, int Np, float scale, void* stream) {
@@ -1269,9 +1155,8 @@ static int attn_bwd_impl(const void* q16, const void* k16, const void* qb, const
   a.dout = (const u16*)dout; a.mask = mask; a.lse = lse; a.delta = delta; a.dq = dq; a.dk = dk; a.dv = (u16*)dv; a.dv_ld = dv_ld;
   a.H = H; a.Np = Np; a.BH = BH; a.xmap = xmap; a.grid_one = (int)grid.x; a.scale2 = QK_UNIT; a.scale = scale; a.fq = fq; a.fk = fk;
   a.role = 0;  // both bodies in ONE launch
-  // VBX_ATTN_BWD_FOLD=0: A/B against round 3's bodies (statistics subtracted by VALU instead of folded into the MFMA accumulator)
-  static const bool fold_env = !(getenv("VBX_ATTN_BWD_FOLD") && atoi(getenv("VBX_ATTN_BWD_FOLD")) == 0);
-  const bool fold = fold_env && g_attn_bwd_variant != 3;
+  // vbx_attn_bwd_select(3): round 3's bodies (statistics subtracted by VALU instead of folded into the MFMA accumulator)
+  const bool fold = g_attn_bwd_variant != 3;
   if (dropout) hipLaunchKernelGGL(attn_bwd_kernel_dma<true>, dim3(2 * grid.x), dim3(256), BWD_DMA_LDS, st, a);
   else if (fold) hipLaunchKernelGGL(attn_bwd_kernel_fold, dim3(2 * grid.x), dim3(256), BWD_DMA_LDS, st, a);
   else hipLaunchKernelGGL(attn_bwd_kernel_dma<false>, dim3(2 * grid.x), dim3(256), BWD_DMA_LDS, st, a);

@@ -21,10 +21,8 @@
 // The 16 exponentials of a block depend only on the S chain, so they are issued BETWEEN the four dependent MFMAs of the dP chain
 // (sched_group_barrier: 1 MFMA, 4 TRANS), where the wave would otherwise wait for the matrix pipe.
 
-#ifndef VBX_BWD_ABL
-#define VBX_BWD_ABL 0  // timing ablations of the dk/dv body (diagnostic build, tools/attn_bwd_ablation.sh): wrong results by construction
-#endif
-#define BABL(n) (((VBX_BWD_ABL) & (n)) != 0)
+// (The timing ablations of the dk/dv body -- no exponentials, one MFMA per chain, no fragment / statistics reads, no DMA, no barrier --
+//  were compile-time arms of this file; they were removed, their figures are in profiles/r06_attn_bwd_ablation.txt and docs/history.md.)
 VBX_DEV f32x16 cat16(const f32x4& a, const f32x4& b, const f32x4& c, const f32x4& d) {
   typedef __attribute__((ext_vector_type(8))) float f32x8;
   const f32x8 lo = __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
@@ -159,53 +157,29 @@ VBX_DEV void attn_bwd_dkdv_fold_body(char* smem, int wg_id, const u16* __restric
     {
       f16x8 qfr[4];
       f32x4 l4[4];
-      if (BABL(8)) {
-        asm volatile("" : "=v"(qfr[0]), "=v"(qfr[1]), "=v"(qfr[2]), "=v"(qfr[3]));
-      } else {
-        D3_READ128(qfr[0], ra[0], O); D3_READ128(qfr[1], ra[1], O); D3_READ128(qfr[2], ra[2], O); D3_READ128(qfr[3], ra[3], O);
-      }
-      if (BABL(8) || BABL(32)) {
-        asm volatile("" : "=v"(l4[0]), "=v"(l4[1]), "=v"(l4[2]), "=v"(l4[3]));
-      } else {
-        D3_READ128(l4[0], sa, SO + QB * 128); D3_READ128(l4[1], sa, SO + QB * 128 + 32);
-        D3_READ128(l4[2], sa, SO + QB * 128 + 64); D3_READ128(l4[3], sa, SO + QB * 128 + 96);
-      }
+      D3_READ128(qfr[0], ra[0], O); D3_READ128(qfr[1], ra[1], O); D3_READ128(qfr[2], ra[2], O); D3_READ128(qfr[3], ra[3], O);
+      D3_READ128(l4[0], sa, SO + QB * 128); D3_READ128(l4[1], sa, SO + QB * 128 + 32);
+      D3_READ128(l4[2], sa, SO + QB * 128 + 64); D3_READ128(l4[3], sa, SO + QB * 128 + 96);
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_sched_barrier(0);
       s = cat16(l4[0], l4[1], l4[2], l4[3]);
       __builtin_amdgcn_s_setprio(1);
 #pragma unroll
-      for (int t = 0; t < (BABL(2) ? 1 : 4); t++) s = __builtin_amdgcn_mfma_f32_32x32x16_f16(qfr[t], kf[t], s, 0, 0, 0);  // L - Q . K^T
+      for (int t = 0; t < 4; t++) s = __builtin_amdgcn_mfma_f32_32x32x16_f16(qfr[t], kf[t], s, 0, 0, 0);  // L - Q . K^T
       __builtin_amdgcn_s_setprio(0);
       __builtin_amdgcn_sched_barrier(0);
     }
     {
       bf16x8 dofr[4];
       f32x4 d4[4];
-      if (BABL(8)) {
-        asm volatile("" : "=v"(dofr[0]), "=v"(dofr[1]), "=v"(dofr[2]), "=v"(dofr[3]));
-      } else {
-        D3_READ128(dofr[0], ra[0], O + 2 * TILE16); D3_READ128(dofr[1], ra[1], O + 2 * TILE16);
-        D3_READ128(dofr[2], ra[2], O + 2 * TILE16); D3_READ128(dofr[3], ra[3], O + 2 * TILE16);
-      }
-      if (BABL(8) || BABL(32)) {
-        asm volatile("" : "=v"(d4[0]), "=v"(d4[1]), "=v"(d4[2]), "=v"(d4[3]));
-      } else {
-        D3_READ128(d4[0], sa, SO + QB * 128 + 256); D3_READ128(d4[1], sa, SO + QB * 128 + 288);
-        D3_READ128(d4[2], sa, SO + QB * 128 + 320); D3_READ128(d4[3], sa, SO + QB * 128 + 352);
-      }
+      D3_READ128(dofr[0], ra[0], O + 2 * TILE16); D3_READ128(dofr[1], ra[1], O + 2 * TILE16);
+      D3_READ128(dofr[2], ra[2], O + 2 * TILE16); D3_READ128(dofr[3], ra[3], O + 2 * TILE16);
+      D3_READ128(d4[0], sa, SO + QB * 128 + 256); D3_READ128(d4[1], sa, SO + QB * 128 + 288);
+      D3_READ128(d4[2], sa, SO + QB * 128 + 320); D3_READ128(d4[3], sa, SO + QB * 128 + 352);
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_sched_barrier(0);
       dp = cat16(d4[0], d4[1], d4[2], d4[3]);
       // delta - dO . V^T, with the block's 16 exponentials (they need only s) in the gaps of the dependent chain
-      if (BABL(1) || BABL(2)) {
-#pragma unroll
-        for (int t = 0; t < (BABL(2) ? 1 : 4); t++) dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dofr[t], vf[t], dp, 0, 0, 0);
-        if (!BABL(1)) {
-#pragma unroll
-          for (int j = 0; j < 16; j++) s[j] = exp2_neg(s[j]);
-        }
-      } else {
 #pragma unroll
       for (int t = 0; t < 4; t++) {
         dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dofr[t], vf[t], dp, 0, 0, 0);
@@ -213,7 +187,6 @@ VBX_DEV void attn_bwd_dkdv_fold_body(char* smem, int wg_id, const u16* __restric
         for (int j = 0; j < 4; j++) s[4 * t + j] = exp2_neg(s[4 * t + j]);
       }
       FOLD_SGB_MFMA_EXP(); FOLD_SGB_MFMA_EXP(); FOLD_SGB_MFMA_EXP(); FOLD_SGB_MFMA_EXP();
-      }
       __builtin_amdgcn_sched_barrier(0);
     }
     // -dS = P * dp'.  One v_mul_f32 per element, by hand: left to the SLP vectoriser the 16 products become 12 v_pk_mul_f32 on
@@ -232,15 +205,10 @@ VBX_DEV void attn_bwd_dkdv_fold_body(char* smem, int wg_id, const u16* __restric
     }
     __builtin_amdgcn_sched_barrier(0);
     s16x4 tl[4], th[4];  // transposed dO / Qb fragments of rows +0..15 (t2 = 0)
-    if (BABL(8)) {
-#pragma unroll
-      for (int j = 0; j < 4; j++) asm volatile("" : "=v"(tl[j]), "=v"(th[j]));
-    } else {
     D3_READTR(tl[0], ta[0], O + 2 * TILE16); D3_READTR(th[0], ta8[0], O + 2 * TILE16);
     D3_READTR(tl[1], ta[1], O + 2 * TILE16); D3_READTR(th[1], ta8[1], O + 2 * TILE16);
     D3_READTR(tl[2], ta[0], O + TILE16); D3_READTR(th[2], ta8[0], O + TILE16);
     D3_READTR(tl[3], ta[1], O + TILE16); D3_READTR(th[3], ta8[1], O + TILE16);
-    }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
     bf16x8 fr[4];
@@ -256,15 +224,10 @@ VBX_DEV void attn_bwd_dkdv_fold_body(char* smem, int wg_id, const u16* __restric
     adk[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fr[3], dsf[0], adk[1], 0, 0, 0);
     __builtin_amdgcn_s_setprio(0);
     __builtin_amdgcn_sched_barrier(0);
-    if (BABL(8)) {
-#pragma unroll
-      for (int j = 0; j < 4; j++) asm volatile("" : "=v"(tl[j]), "=v"(th[j]));
-    } else {
     D3_READTR(tl[0], ta[0], O + 2 * TILE16 + 2048); D3_READTR(th[0], ta8[0], O + 2 * TILE16 + 2048);
     D3_READTR(tl[1], ta[1], O + 2 * TILE16 + 2048); D3_READTR(th[1], ta8[1], O + 2 * TILE16 + 2048);
     D3_READTR(tl[2], ta[0], O + TILE16 + 2048); D3_READTR(th[2], ta8[0], O + TILE16 + 2048);
     D3_READTR(tl[3], ta[1], O + TILE16 + 2048); D3_READTR(th[3], ta8[1], O + TILE16 + 2048);
-    }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -273,22 +236,18 @@ VBX_DEV void attn_bwd_dkdv_fold_body(char* smem, int wg_id, const u16* __restric
       fr[j] = __builtin_bit_cast(bf16x8, v8);
     }
     __builtin_amdgcn_s_setprio(1);
-    if (!BABL(2)) {
     adv[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fr[0], pf[1], adv[0], 0, 0, 0);
     adk[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fr[2], dsf[1], adk[0], 0, 0, 0);
     adv[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fr[1], pf[1], adv[1], 0, 0, 0);
     adk[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fr[3], dsf[1], adk[1], 0, 0, 0);
-    } else {
-      asm volatile("" ::"v"(fr[0]), "v"(fr[1]), "v"(fr[2]), "v"(fr[3]), "v"(pf[1]), "v"(dsf[1]));
-    }
     __builtin_amdgcn_s_setprio(0);
     __builtin_amdgcn_sched_barrier(0);
   };
   auto step = [&](auto so_c, int qt) {
-    if (!BABL(128)) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (!BABL(256)) __builtin_amdgcn_s_barrier();
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
-    if (!BABL(128) && qt + 1 < ntiles) issue(qt + 1);
+    if (qt + 1 < ntiles) issue(qt + 1);
     if (!active) return;
     block(so_c, std::integral_constant<int, 0>{});
     if (qt * 64 + 32 < Np) block(so_c, std::integral_constant<int, 1>{});
@@ -547,4 +506,3 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_kernel_fold(const AttnBwdArgs
     attn_bwd_dkdv_fold_body(smem, id, a.q16, a.qb16, a.k16, a.vv, a.mask, a.dout, a.lse, a.delta, a.dk, a.dv, a.dv_ld, a.H, a.Np,
                             a.scale, a.BH, a.xmap, a.fk);
 }
-#undef BABL

@@ -2,10 +2,6 @@
 // outb, lse, H, Np, scale2, BH, xmap and `smem`.  With VBX_FWD_DROP defined (training-time attention dropout, attend.py:131) also
 // dbits (row-major keep bits R[bh][q][W2], ops.hip), W2 and rkeep: the softmax statistics (row maximum, row sum, LSE) are those
 // of the UNdropped probabilities, dropped entries are zeroed in the P fragment only, and 1 / keep rides in the final 1 / l.
-#ifndef VBX_FWD_ABL
-#define VBX_FWD_ABL 0  // timing ablations (diagnostic build, -DVBX_ATTN_DIAG): wrong results by construction
-#endif
-#define ABL(n) (((VBX_FWD_ABL) & (n)) != 0)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, hi = lane >> 5;
   const AttnCoord co = attn_coord(H, Np, BH, xmap);
   if (!co.ok) return;
@@ -51,7 +47,7 @@
   // walk the key loop with one active wave of 32-query blocks: 26 us of life for 1/8 of a wave's work.  Here its four waves split
   // every 64-key tile into 16-key blocks and run 16 x 16 MFMA shapes on the 16 queries -- S^T[16 keys][16 q] = 2 x 16x16x32,
   // O^T[64 d][16 q] += V^T . P^T = 4 x 16x16x16 per wave and tile -- then merge their (m, l, O) through LDS.  (attend.py:119-137)
-  if (co.tile == (Np >> 7) && (Np & 127) <= 16 && !(xmap & 4)) {  // xmap bit 2 (VBX_ATTN_XMAP=5): A/B without the ragged role
+  if (co.tile == (Np >> 7) && (Np & 127) <= 16 && !(xmap & 4)) {  // xmap bit 2: without the ragged role (no caller sets it, attn_coord_id)
 #include "attn_fwd_ragged.inc"
     ATTN_TRACE_END(0);
     return;
@@ -84,12 +80,6 @@
 #pragma unroll
   for (int i = 0; i < 16; i++) { o[0][i] = 0.f; o[1][i] = 0.f; }
   float m_run = NEG_INF, l_run = 0.f;
-#ifdef VBX_FWD_STAGGER  // experiment: the co-resident workgroups of a CU start their key loops a fraction of a step apart
-  {
-    const int slot = ((int)blockIdx.x >> 8) & 3;
-    for (int i = 0; i < slot; i++) __builtin_amdgcn_s_sleep(VBX_FWD_STAGGER);
-  }
-#endif
 #ifdef VBX_FWD_DROP
   const unsigned* brow = dbits + (bh * Np + qc) * W2;
   uint2 wkeep = *reinterpret_cast<const uint2*>(brow);  // keep bits of key tile 0; tile kt + 1 is requested during step kt
@@ -100,79 +90,47 @@
   //  forward 70.5 / 71.7 us -> 71.1 / 69.8 us: nothing measurable -- and the extra instantiations pushed the kernel to 14 spilled
   //  registers, two of them the V^T fragments of an inline-asm ds_read spilled BEFORE their s_waitcnt (wrong results whenever the
   //  half tile sat in ring slot 1).  Removed.)
-  ATTN_ST_DECL();
   auto step = [&](auto stg_c, int kt) {
     constexpr int STG = decltype(stg_c)::value;
     constexpr int SO = STG * ASTAGE;
-    ATTN_ST(0);
-    if (!ABL(128)) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this thread's pieces of tile kt have landed
-    if (!ABL(256)) __builtin_amdgcn_s_barrier();                     // tile kt visible to all; everyone is done with tile kt-1
-#ifndef VBX_FWD_DMAPOS
-#define VBX_FWD_DMAPOS 0  // where the next tile's four LDS-DMA pieces are issued: 0 behind the barrier, 1 / 2 behind the first / second S chain, 3 behind the
-                          // softmax, 4 / 5 behind the ISSUE of the first / of both K fragment read groups (before their wait)
-#endif
-    if (VBX_FWD_DMAPOS == 0 || !active) { if (!ABL(128) && kt + 1 < ntiles) dma_kv((unsigned)((STG ^ 1) * ASTAGE), kt + 1); }
-    ATTN_ST(1);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this thread's pieces of tile kt have landed
+    __builtin_amdgcn_s_barrier();                     // tile kt visible to all; everyone is done with tile kt-1
+    // The next tile's four LDS-DMA pieces are issued here, behind the barrier.  Five later placements were measured (behind the first /
+    // second S chain, behind the softmax, behind the issue of the first / of both K fragment read groups): 63.1-64.4 us for every one
+    // in the unstamped kernel.  Their arms, the per-step stamps and the timing ablations of this step were removed; the figures are in
+    // profiles/r06_attn_fwd_steptrace.txt, profiles/r06_attn_fwd_ablation.txt and docs/history.md.
+    if (kt + 1 < ntiles) dma_kv((unsigned)((STG ^ 1) * ASTAGE), kt + 1);
     if (!active) return;
     const int k0 = kt * 64;
     f32x16 s[2];
 #pragma unroll
     for (int i = 0; i < 16; i++) { s[0][i] = 0.f; s[1][i] = 0.f; }
     {
-      f16x8 kf[4], kf2[4];
-      if (ABL(8)) {
-        asm volatile("" : "=v"(kf[0]), "=v"(kf[1]), "=v"(kf[2]), "=v"(kf[3]));
-      } else {
-        kf[0] = asm_read_b128<SO>(ka[0]); kf[1] = asm_read_b128<SO>(ka[1]);
-        kf[2] = asm_read_b128<SO>(ka[2]); kf[3] = asm_read_b128<SO>(ka[3]);
-        if (VBX_FWD_DMAPOS == 5) {
-          kf2[0] = asm_read_b128<SO + 4096>(ka[0]); kf2[1] = asm_read_b128<SO + 4096>(ka[1]);
-          kf2[2] = asm_read_b128<SO + 4096>(ka[2]); kf2[3] = asm_read_b128<SO + 4096>(ka[3]);
-        }
-      }
-      if (VBX_FWD_DMAPOS == 4 || VBX_FWD_DMAPOS == 5) {  // the fragment reads are in the LDS queue ahead of the DMA traffic
-        __builtin_amdgcn_sched_barrier(0);
-        if (!ABL(128) && kt + 1 < ntiles) dma_kv((unsigned)((STG ^ 1) * ASTAGE), kt + 1);
-      }
+      f16x8 kf[4];
+      kf[0] = asm_read_b128<SO>(ka[0]); kf[1] = asm_read_b128<SO>(ka[1]);
+      kf[2] = asm_read_b128<SO>(ka[2]); kf[3] = asm_read_b128<SO>(ka[3]);
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_sched_barrier(0);
-      ATTN_ST(2);
-      if (!ABL(64)) __builtin_amdgcn_s_setprio(1);
+      __builtin_amdgcn_s_setprio(1);
 #pragma unroll
-      for (int t = 0; t < (ABL(4) ? 1 : 4); t++) s[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf[t], qf[t], s[0], 0, 0, 0);
-      if (!ABL(64)) __builtin_amdgcn_s_setprio(0);
+      for (int t = 0; t < 4; t++) s[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf[t], qf[t], s[0], 0, 0, 0);
+      __builtin_amdgcn_s_setprio(0);
       __builtin_amdgcn_sched_barrier(0);
-      if (VBX_FWD_DMAPOS == 1) { if (!ABL(128) && kt + 1 < ntiles) dma_kv((unsigned)((STG ^ 1) * ASTAGE), kt + 1); }
-      ATTN_ST(3);
-      if (VBX_FWD_DMAPOS == 5) {
-#pragma unroll
-        for (int t = 0; t < 4; t++) kf[t] = kf2[t];
-      } else if (ABL(8)) {
-        asm volatile("" : "=v"(kf[0]), "=v"(kf[1]), "=v"(kf[2]), "=v"(kf[3]));
-      } else {
-        kf[0] = asm_read_b128<SO + 4096>(ka[0]); kf[1] = asm_read_b128<SO + 4096>(ka[1]);
-        kf[2] = asm_read_b128<SO + 4096>(ka[2]); kf[3] = asm_read_b128<SO + 4096>(ka[3]);
-      }
+      kf[0] = asm_read_b128<SO + 4096>(ka[0]); kf[1] = asm_read_b128<SO + 4096>(ka[1]);
+      kf[2] = asm_read_b128<SO + 4096>(ka[2]); kf[3] = asm_read_b128<SO + 4096>(ka[3]);
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_sched_barrier(0);
-      if (!ABL(64)) __builtin_amdgcn_s_setprio(1);
+      __builtin_amdgcn_s_setprio(1);
 #pragma unroll
-      for (int t = 0; t < (ABL(4) ? 1 : 4); t++) s[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf[t], qf[t], s[1], 0, 0, 0);
-      if (!ABL(64)) __builtin_amdgcn_s_setprio(0);
-      if (VBX_FWD_DMAPOS == 2) { __builtin_amdgcn_sched_barrier(0); if (!ABL(128) && kt + 1 < ntiles) dma_kv((unsigned)((STG ^ 1) * ASTAGE), kt + 1); __builtin_amdgcn_sched_barrier(0); }
-      ATTN_ST(4);
+      for (int t = 0; t < 4; t++) s[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf[t], qf[t], s[1], 0, 0, 0);
+      __builtin_amdgcn_s_setprio(0);
     }
     // V^T fragments of the first 32-key block: requested now, consumed after the softmax
     s16x4 vl[4], vh[4];
-    if (ABL(8)) {
-#pragma unroll
-      for (int j = 0; j < 4; j++) asm volatile("" : "=v"(vl[j]), "=v"(vh[j]));
-    } else {
-      asm_read_tr<SO>(vl[0], vh[0], va[0], va8[0]);
-      asm_read_tr<SO>(vl[1], vh[1], va[1], va8[1]);
-      asm_read_tr<SO + 2048>(vl[2], vh[2], va[0], va8[0]);
-      asm_read_tr<SO + 2048>(vl[3], vh[3], va[1], va8[1]);
-    }
+    asm_read_tr<SO>(vl[0], vh[0], va[0], va8[0]);
+    asm_read_tr<SO>(vl[1], vh[1], va[1], va8[1]);
+    asm_read_tr<SO + 2048>(vl[2], vh[2], va[0], va8[0]);
+    asm_read_tr<SO + 2048>(vl[3], vh[3], va[1], va8[1]);
     const bool need_mask = (mask != nullptr) || (k0 + 64 > Np);
     if (need_mask) {
 #pragma unroll
@@ -189,7 +147,7 @@
 #pragma unroll
     for (int kb = 0; kb < 2; kb++)
 #pragma unroll
-      for (int r = 0; r < (ABL(32) ? 1 : 16); r++) mx = fmaxf(mx, s[kb][r]);
+      for (int r = 0; r < 16; r++) mx = fmaxf(mx, s[kb][r]);
     mx = xhalf_max(mx);  // v_permlane32_swap: no LDS round trip on the softmax's critical path
     const float m_new = fmaxf(m_run, mx * scale2);
     const float m_use = (m_new == NEG_INF) ? 0.f : m_new;
@@ -203,7 +161,7 @@
       for (int r = 0; r < 16; r += 2) {
         const f2 sv = {s[kb][r], s[kb][r + 1]};
         const f2 e = __builtin_elementwise_fma(sv, sc2, mneg);
-        const f2 p = ABL(1) ? e : (f2){fast_exp2(e.x), fast_exp2(e.y)};
+        const f2 p = {fast_exp2(e.x), fast_exp2(e.y)};
         s[kb][r] = p.x;
         s[kb][r + 1] = p.y;
         ps2 += p;
@@ -221,7 +179,7 @@
       if (kt + 1 < ntiles) wkeep = *reinterpret_cast<const uint2*>(brow + 2 * (kt + 1));
     }
 #endif
-    if (!ABL(16)) {
+    {
       const f2 a2 = {alpha, alpha};
 #pragma unroll
       for (int i = 0; i < 16; i += 2) {
@@ -242,40 +200,26 @@
         const s16x8 t = {vl[j][0], vl[j][1], vl[j][2], vl[j][3], vh[j][0], vh[j][1], vh[j][2], vh[j][3]};       \
         vf[j] = __builtin_bit_cast(f16x8, t);                                                                   \
       }                                                                                                         \
-      if (!ABL(64)) __builtin_amdgcn_s_setprio(1);                                                              \
+      __builtin_amdgcn_s_setprio(1);                                                                            \
       o[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf[0], p0, o[0], 0, 0, 0);                                  \
       o[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf[1], p0, o[1], 0, 0, 0);                                  \
-      if (!ABL(2)) {                                                                                            \
-        o[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf[2], p1, o[0], 0, 0, 0);                                \
-        o[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf[3], p1, o[1], 0, 0, 0);                                \
-      } else {                                                                                                  \
-        asm volatile("" ::"v"(vf[2]), "v"(vf[3]), "v"(p1));                                                     \
-      }                                                                                                         \
-      if (!ABL(64)) __builtin_amdgcn_s_setprio(0);                                                              \
+      o[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf[2], p1, o[0], 0, 0, 0);                                  \
+      o[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf[3], p1, o[1], 0, 0, 0);                                  \
+      __builtin_amdgcn_s_setprio(0);                                                                            \
       __builtin_amdgcn_sched_barrier(0);                                                                        \
     }
-    if (VBX_FWD_DMAPOS == 3) { __builtin_amdgcn_sched_barrier(0); if (!ABL(128) && kt + 1 < ntiles) dma_kv((unsigned)((STG ^ 1) * ASTAGE), kt + 1); __builtin_amdgcn_sched_barrier(0); }
-    ATTN_ST(5);
     VBX_PV3(0)
-    ATTN_ST(6);
-    if (ABL(8)) {
-#pragma unroll
-      for (int j = 0; j < 4; j++) asm volatile("" : "=v"(vl[j]), "=v"(vh[j]));
-    } else {
-      asm_read_tr<SO + 4096>(vl[0], vh[0], va[0], va8[0]);
-      asm_read_tr<SO + 4096>(vl[1], vh[1], va[1], va8[1]);
-      asm_read_tr<SO + 4096 + 2048>(vl[2], vh[2], va[0], va8[0]);
-      asm_read_tr<SO + 4096 + 2048>(vl[3], vh[3], va[1], va8[1]);
-    }
+    asm_read_tr<SO + 4096>(vl[0], vh[0], va[0], va8[0]);
+    asm_read_tr<SO + 4096>(vl[1], vh[1], va[1], va8[1]);
+    asm_read_tr<SO + 4096 + 2048>(vl[2], vh[2], va[0], va8[0]);
+    asm_read_tr<SO + 4096 + 2048>(vl[3], vh[3], va[1], va8[1]);
     VBX_PV3(1)
-    ATTN_ST(7);
 #undef VBX_PV3
   };
   for (int kt = 0; kt < ntiles; kt += 2) {
     step(std::integral_constant<int, 0>{}, kt);
     if (kt + 1 < ntiles) step(std::integral_constant<int, 1>{}, kt + 1);
   }
-  ATTN_ST_FLUSH();
   __syncthreads();  // every wave is done with the ring before it becomes epilogue staging space
   ATTN_TRACE_LOOP_END();
 
@@ -316,4 +260,3 @@
     }
   }
   ATTN_TRACE_END(0);
-#undef ABL

@@ -77,18 +77,6 @@ VBX_DEV void interp_src(int n, int N, int T, int& i0, int& i1, float& lam) {
   lam = src - (float)i0;
 }
 
-// Start-phase stagger (experiment, VBX_GEMM_STAGGER=<us>): workgroups that become co-resident on a CU at launch run their
-// k-loops and their epilogues in lockstep -- the matrix pipes idle while every CU stores and the memory system idles while every
-// CU multiplies (tools/native/gemm_trace.cpp).  Delaying the workgroups of launch slot s (blockIdx / #CUs) by s * ticks (100 MHz
-// s_memrealtime units) puts the co-residents out of phase; later workgroups inherit the phase of the slot they take over.
-VBX_DEV void stagger_wait(int slot, int ticks) {
-  if (slot > 0 && ticks > 0) {
-    const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-    const unsigned long long d = (unsigned long long)slot * (unsigned)ticks;
-    while (__builtin_amdgcn_s_memrealtime() - t0 < d) __builtin_amdgcn_s_sleep(16);
-  }
-}
-
 // ---- dropout: Philox4x32-10 (Salmon et al., SC'11), the counter-based generator torch / JAX dropout use --------------------------
 // One call = 128 random bits = EIGHT 16-bit lots: element e of a call is kept iff lot_e < thr16, thr16 = round(keep * 65536)
 // (<= 65535), so the kept fraction is thr16 / 65536 and the survivors are scaled by 65536 / thr16 -- exactly unbiased.
@@ -175,10 +163,9 @@ int vbx_gemm3_tn_splitk_grouped(const vbx_gemm_desc* descs, int n, hipStream_t s
 int vbx_gemm4(const vbx_gemm_desc* d, hipStream_t st);
 int vbx_gemm5(const vbx_gemm_desc* d, hipStream_t st);
 int vbx_gemm5_cus();  // CUs a gemm5 launch may use on the current device (vbx_gemm5_cu_limit applied); < 0: an error code
-// vbx_gemm_select / VBX_GEMM_PATH: 0 automatic choice per shape (default), 1 gemm.hip kernels only, 2 gemm3 wherever it can serve,
+// vbx_gemm_select: 0 automatic choice per shape (default), 1 gemm.hip kernels only, 2 gemm3 wherever it can serve,
 // 3 gemm4 wherever it can serve, 4 = 0 with gemm5 on whatever VBX_GEMM5 says
 int vbx_gemm_path();
-int vbx_gemm_stagger();  // VBX_GEMM_STAGGER (diagnostic): start-phase stagger of co-resident workgroups, in percent of a k-step
 
 // precise.hip: the exact-operand forward (vbx_model.precise).  runtime.hip hands over the tensors of its own arenas that the
 // precise forward fills for the loss and for the (unchanged) backward; null pointers = not kept (inference).

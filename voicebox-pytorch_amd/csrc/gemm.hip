@@ -47,9 +47,6 @@ struct GemmParams {
   long lda, ldb;
   int kchunk;  // K range handled by one blockIdx.y (multiple of BK); == K when not split
   int tiles_m;
-  int abl;     // timing ablations (tools only; results are wrong when != 0): 1 no DMA, 2 no LDS reads, 4 no barrier,
-               // 8/16 linear A/B sources, 32 no epilogue functor, 64 no epilogue at all
-  int stagger; // start-phase stagger of co-resident workgroups in 10 ns ticks (common.hpp::stagger_wait); 0 = off
 };
 
 // 16x16x32 MFMA on raw 16-bit fragments: bf16 (default) or fp16 (the q/k projection: 11-bit mantissa)
@@ -161,13 +158,13 @@ struct FragPlan {
 
 // BM_ = 128: 2x2 waves of 64x64.  BM_ = 64 (MA == 0 only): 1x4 waves of 64x32 -- twice the workgroups for the
 // N = dim dgrads that would otherwise fill half the chip.
-// Timing ablations on 8192^3 (VBX_GEMM_ABL, tools only): full 690 TF; no LDS reads 691; no barrier 706; no DMA 1350;
-// neither DMA nor LDS reads 2080 (83 % of peak) -> the L2->LDS operand stream of 128x128 tiles (64 FLOP/B) is the limiter.
+// Timing ablations on 8192^3: full 690 TF; no LDS reads 691; no barrier 706; no DMA 1350; neither DMA nor LDS reads 2080 (83 % of
+// peak) -> the L2->LDS operand stream of 128x128 tiles (64 FLOP/B) is the limiter.  (The arms that produced these figures were a
+// run-time word of GemmParams read in the k-loop; they were removed, docs/history.md.)
 template <int MA, int MB, class Epi, bool F16, int BM_>
 __global__ __launch_bounds__(256, 3) void gemm_kernel_v2(GemmParams p, Epi epi) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   GEMM2_TRACE_DECL();
-  if (p.stagger && gridDim.y == 1 && blockIdx.x < 768) stagger_wait(blockIdx.x >> 8, p.stagger);  // 3 workgroups per CU
 #define VBX_BX_ blockIdx.x
 #define VBX_T_ gridDim.x
 #define VBX_SPLIT_ blockIdx.y
@@ -189,9 +186,8 @@ __global__ __launch_bounds__(256, 3) void gemm_kernel_v2(GemmParams p, Epi epi) 
 // (24 KiB: 3 DMA instructions x 512 threads, rows >= 160 from the zero page) + B [128][64] or two K-strided [32][128] images
 // (16 KiB), 3 stages = 120 KiB, one barrier per 64 k (half as many as before).  Back to back (tools/native/gemm3_check time): to_out
 // 21.9 -> 18.9 us, FeedForward-out 26.3 -> 22.4, dgrad to_qkv 45.0 -> 36.4 (720 TFLOP/s), dgrad FeedForward-in 42.4 -> 34.0.
-#ifndef VBX_V9_ABL
-#define VBX_V9_ABL 0  // diagnostic builds (tools/native/v9_abl.sh): 1 no DMA behind the prologue, 2 no fragment reads, 4 no barrier, 8 no MFMAs, 64 no epilogue
-#endif
+// (The timing ablations of this kernel -- no DMA behind the prologue, no fragment reads, no barrier, no MFMAs, no epilogue -- were
+//  compile-time arms of its k-loop; they were removed, their figures are in profiles/r06_ndim_tile_ablation.txt.)
 constexpr int V9_A_BYTES = 192 * 128;
 constexpr int V9_B_BYTES = 16384;
 constexpr int V9_STAGE = V9_A_BYTES + V9_B_BYTES;  // 40 KiB
@@ -325,27 +321,16 @@ __global__ __launch_bounds__(512, 1) void gemm_kernel_bm160k64(GemmParams p, Epi
     constexpr int STG = decltype(stg_c)::value;
     if (t + 1 < nt) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");  // k-tile t has landed, t+1 may stay in flight
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (!(VBX_V9_ABL & 4)) __builtin_amdgcn_s_barrier();  // k-tile t visible to all; every wave is done reading k-tile t-1
+    __builtin_amdgcn_s_barrier();  // k-tile t visible to all; every wave is done reading k-tile t-1
     Frags9 f;
-    if ((VBX_V9_ABL & 2) && t > 0) {
-#pragma unroll
-      for (int kk = 0; kk < 2; kk++) {
-#pragma unroll
-        for (int i = 0; i < 5; i++) asm volatile("" : "=v"(f.af[kk][i]));
-#pragma unroll
-        for (int j = 0; j < 2; j++) asm volatile("" : "=v"(f.bfr[kk][j]), "=v"(f.blo[kk][j]), "=v"(f.bhi[kk][j]));
-      }
-    } else {
-      read_frags(stg_c, f);
-    }
+    read_frags(stg_c, f);
     // the DMAs of k-tile t+2 are issued BEHIND the fragment reads: the LDS round trip runs under their issue time (dgrad to_qkv
     // 39.1 -> 36.4 us back to back against issuing them first).  Prefetching the fragments of k-tile t+1 before the MFMAs of
     // k-tile t (two register sets) measured 1 us SLOWER than this order.
-    if (t + 2 < nt && !(VBX_V9_ABL & 1)) stage((STG + 2) % 3, t + 2);
+    if (t + 2 < nt) stage((STG + 2) % 3, t + 2);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
-    if (!(VBX_V9_ABL & 8)) mfmas(f);
-    else asm volatile("" ::"v"(f.af[0][0]), "v"(f.af[1][4]), "v"(f.bfr[0][0]), "v"(f.bfr[1][1]));
+    mfmas(f);
   };
   for (int t = 0; t < nt; t += 3) {
     step(std::integral_constant<int, 0>{}, t);
@@ -354,15 +339,6 @@ __global__ __launch_bounds__(512, 1) void gemm_kernel_bm160k64(GemmParams p, Epi
   }
   // ---- epilogue: as gemm_kernel_bm160x8
   float* Cs = reinterpret_cast<float*>(smem);
-  if (VBX_V9_ABL & 64) {
-    float tsum = 0.f;
-#pragma unroll
-    for (int i = 0; i < 5; i++)
-#pragma unroll
-      for (int j = 0; j < 2; j++) tsum += acc[i][j][0] + acc[i][j][1] + acc[i][j][2] + acc[i][j][3];
-    if (tsum == 123.456f) Cs[tid] = tsum;
-    return;
-  }
   const int half = tid >> 8, tq = tid & 255;
   // 16-bit outputs: the whole 160 x 128 fp32 tile is staged at once in the idle ring (84.5 of 120 KiB), two barriers instead of six: the N = dim
   // dgrads 36.1 -> 35.6, 34.4 -> 33.6 us.  The fp32 + residual functor keeps the three 64-row chunks: staged at once its stores come in one
@@ -610,9 +586,6 @@ struct EpiGEGLU {
   }
 };
 
-#ifndef VBX_EPIQKV_ABL
-#define VBX_EPIQKV_ABL 0  // diagnostic builds only (tools/kdim_gemm_ablation.sh): 1 no stores, 2 no 1/|x|, 4 no rotary / gamma loads
-#endif
 // to_qkv + MultiheadRMSNorm + rotary, written head-major (voicebox_pytorch.py:320-328).
 struct EpiQKV {
   int Np, H;
@@ -641,7 +614,6 @@ struct EpiQKV {
         float t[8];
         load8(Cs, row, cc, t);
         const long o = (((long)b * H + hbase + (cc >> 3)) * Np + n) * 64 + (cc & 7) * 8;
-        if ((VBX_EPIQKV_ABL & 1) && t[0] != 123.456f) continue;
         if (v) *reinterpret_cast<uint4*>(v + o) = pack8_bf16(t);
         if (v16) *reinterpret_cast<uint4*>(v16 + o) = pack8_f16_sat(t);
       }
@@ -653,7 +625,8 @@ struct EpiQKV {
     // Round 6: everything a pass reads from global memory is requested BEFORE the first pass computes -- the head's gamma chunk
     // (the same for every pass) and the rotary rows of all passes of this call.  Written pass by pass, every pass was
     // gamma loads -> s_waitcnt vmcnt(0) -> rotary loads -> s_waitcnt vmcnt(0) -> stores, and on gfx950 vmcnt also counts the previous
-    // pass's STORES: two exposed round trips behind a store drain per pass, 22 of the 64 us of this GEMM (VBX_GEMM_ABL=32).
+    // pass's STORES: two exposed round trips behind a store drain per pass, 22 of the 64 us of this GEMM (measured by a
+    // build without the epilogue functor; that arm was removed, docs/history.md).
     const int hj = tid & 7;
     const int hl = hj >> 2, j = hj & 3;  // head inside the 128-column tile, chunk pair
     const int head = hbase + hl;
@@ -678,8 +651,8 @@ struct EpiQKV {
       const int gr = m0 + (it0 + it) * 32 + (tid >> 3);
       pv[it] = it < npass && gr < M;
       split_row(pv[it] ? gr : mb, pb[it], pn[it]);
-      gload8(rc + (long)pn[it] * 32 + d0, it < npass && !(VBX_EPIQKV_ABL & 4), cs[it]);
-      gload8(rs + (long)pn[it] * 32 + d0, it < npass && !(VBX_EPIQKV_ABL & 4), sn[it]);
+      gload8(rc + (long)pn[it] * 32 + d0, it < npass, cs[it]);
+      gload8(rs + (long)pn[it] * 32 + d0, it < npass, sn[it]);
     }
     retire8(glo);
     retire8(ghi);
@@ -704,7 +677,7 @@ struct EpiQKV {
       // the raw v_rsq moved the chaotic random-init depth-12 loss from 1.0e-3 to 3.9e-3 off the reference
       // (tests/test_model_gpu.py::test_cfg4_depth12_parity); with one Newton step the test passes again, and neither variant is
       // measurably faster (16-interval sample 80.6 vs 80.6 ms in the same run).  The IEEE sequence stays.
-      const float rinv = (VBX_EPIQKV_ABL & 2) ? ss : 1.0f / fmaxf(sqrtf(ss), 1e-12f);
+      const float rinv = 1.0f / fmaxf(sqrtf(ss), 1e-12f);
       if (qk_scale > 0.f) {
         const float rs_ = rinv * qk_scale;
 #pragma unroll
@@ -720,7 +693,7 @@ struct EpiQKV {
         olo[i] = lo[i] * cs[it][i] - hi[i] * sn[it][i];
         ohi[i] = hi[i] * cs[it][i] + lo[i] * sn[it][i];
       }
-      if ((VBX_EPIQKV_ABL & 1) ? (pv[it] && olo[0] == 123.456f) : pv[it]) {
+      if (pv[it]) {
         const long o = (((long)pb[it] * H + head) * Np + pn[it]) * 64 + d0;
         if (bcopy) {
           *reinterpret_cast<uint4*>(bcopy + o) = pack8_bf16(olo);
@@ -811,19 +784,8 @@ __global__ __launch_bounds__(256) void splitk_reduce_multi_kernel(vbx_skr_jobs j
 
 }  // namespace
 
-int vbx_gemm_stagger() {
-  static const int stagger = getenv("VBX_GEMM_STAGGER") ? (int)(atof(getenv("VBX_GEMM_STAGGER")) * 100.0) : 0;
-  return stagger;
-}
-static int g_gemm_path = -1;
-int vbx_gemm_path() {
-  if (g_gemm_path < 0) {
-    const char* e = getenv("VBX_GEMM_PATH");
-    g_gemm_path = e ? atoi(e) : 0;
-    if (g_gemm_path < 0 || g_gemm_path > 4) g_gemm_path = 0;
-  }
-  return g_gemm_path;
-}
+static int g_gemm_path = 0;  // vbx_gemm_select
+int vbx_gemm_path() { return g_gemm_path; }
 extern "C" int vbx_gemm_select(int path) {
   VBX_REQUIRE(path >= 0 && path <= 4, "vbx_gemm_select: 0 automatic, 1 128-wide kernels only, 2 256x256 tile wherever it serves, 3 128x256 tile wherever it serves, 4 = 0 with the weight-stationary kernel forced on");
   g_gemm_path = path;
@@ -909,9 +871,6 @@ extern "C" int vbx_gemm(const vbx_gemm_desc* d, void* stream) {
   p.A = (const u16*)d->A; p.B = (const u16*)d->B;
   p.M = d->M; p.N = d->N; p.K = d->K; p.lda = d->lda; p.ldb = d->ldb;
   p.kchunk = d->K; p.tiles_m = cdiv(d->M, BM);
-  static const int abl = getenv("VBX_GEMM_ABL") ? atoi(getenv("VBX_GEMM_ABL")) : 0;
-  p.abl = abl;
-  p.stagger = vbx_gemm_stagger();
   const bool nt = d->mode == VBX_GEMM_NT;
   switch (d->epilogue) {
     case VBX_EPI_BF16: {

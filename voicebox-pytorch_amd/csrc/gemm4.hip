@@ -13,7 +13,6 @@
 #include "common.hpp"
 #include "gemm4_layout.hpp"
 #include "gemm_epi3.hpp"
-#include <stdlib.h>
 #include <type_traits>
 
 namespace {
@@ -26,8 +25,6 @@ struct G4Params {
   const u16* B;
   int M, N, K;
   long lda, ldb;
-  int stagger;  // start-phase stagger of the second workgroup per CU in 10 ns ticks (common.hpp::stagger_wait); 0 = off
-  int late_dma; // a k-tile's DMAs issued behind the fragment reads (default; VBX_GEMM_LATE_DMA=0: in front of them, A/B)
 };
 
 __device__ uint4 g4_zero_page[4];
@@ -117,7 +114,6 @@ template <int MA, int MB, class Epi, bool F16>
 __global__ __launch_bounds__(256, 2) void gemm4_kernel(G4Params p, Epi epi) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   GEMM_TRACE_DECL();
-  if (p.stagger && blockIdx.x >= 256 && blockIdx.x < 512) stagger_wait(1, p.stagger);  // 2 workgroups per CU
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wr = wave >> 1, wc = wave & 1;
@@ -168,12 +164,11 @@ __global__ __launch_bounds__(256, 2) void gemm4_kernel(G4Params p, Epi epi) {
     if (t + 1 < nt) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();  // k-tile t visible to all waves; everyone is done reading k-tile t-1
-    if (!p.late_dma && t + 2 < nt) stage(t + 2);  // into the slot k-tile t-1 used
     RawFrag4 af[4], bf[8];
     fa.template read<SO, 0>(af[0]); fa.template read<SO, 1>(af[1]); fa.template read<SO, 2>(af[2]); fa.template read<SO, 3>(af[3]);
     fb.template read<SO, 0>(bf[0]); fb.template read<SO, 1>(bf[1]); fb.template read<SO, 2>(bf[2]); fb.template read<SO, 3>(bf[3]);
     fb.template read<SO, 4>(bf[4]); fb.template read<SO, 5>(bf[5]); fb.template read<SO, 6>(bf[6]); fb.template read<SO, 7>(bf[7]);
-    if (p.late_dma && t + 2 < nt) stage(t + 2);
+    if (t + 2 < nt) stage(t + 2);  // into the slot k-tile t-1 used, behind the fragment reads (as gemm_v2_body.inc)
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_setprio(1);
@@ -218,8 +213,7 @@ int launch4(const G4Params& p, const Epi& epi, hipStream_t st) {
 
 // A validated NT / NN descriptor that gemm_route.hpp sent here (wide_tile_serves)
 int vbx_gemm4(const vbx_gemm_desc* d, hipStream_t st) {
-  static const int late = getenv("VBX_GEMM_LATE_DMA") ? atoi(getenv("VBX_GEMM_LATE_DMA")) : 1;
-  G4Params p{(const u16*)d->A, (const u16*)d->B, d->M, d->N, d->K, d->lda, d->ldb, vbx_gemm_stagger(), late};
+  G4Params p{(const u16*)d->A, (const u16*)d->B, d->M, d->N, d->K, d->lda, d->ldb};
   const bool nt = d->mode == VBX_GEMM_NT;
   switch (d->epilogue) {
     case VBX_EPI_BF16: {

@@ -25,15 +25,13 @@
 //   activation block in LDS: row t (32 rows of 1 KiB), 16-byte chunk c at chunk position c ^ (t & 15): the 16 lanes of a
 //                  ds_read_b128 group (tokens {0-3,12-15,20-27} / {4-11,16-19,28-31}) hit 16 distinct bank groups.
 #include "common.hpp"
-#include <stdlib.h>
 #include <type_traits>
 #include <utility>
 
 namespace {
 
-#ifndef VBX_G5_ABL
-#define VBX_G5_ABL 0  // diagnostic builds (tools/native/g5_abl.sh): 1 no epilogue, 2 no DMA, 8 no MFMAs -- wrong results by construction
-#endif
+// (The timing ablations of the phase -- no epilogue, no DMA, no MFMAs -- were compile-time arms of this file; they were removed, their
+//  figures are in profiles/r06_gemm5_ablation.txt and docs/history.md.)
 // (Measured and removed: the four waves taking turns at the texture path -- wave w issuing its pieces in slots 1 + w, 5 + w, ... --
 //  is 1-3 us SLOWER than all four issuing in the same slots.  Block 0's activation rows requested before the weight rounds (weight
 //  regions moved behind slot 0, 160 KiB of LDS): 39.6 / 34.4 / 38.6 / 33.1 us against 39.1 / 34.4 / 38.4 / 32.7 us in the same call --
@@ -625,7 +623,6 @@ __global__ __launch_bounds__(256, 1) void gemm5_kernel(G5Params p, Epi epi) {
       return b;
     };
     auto issue_piece = [&](int q, const Blk& b) {  // piece q of a block of this workgroup -> its X slot / rotary slot
-      if constexpr (VBX_G5_ABL & 2) return;
       if (q < 8) {
         g5_buf_lds(p.A, b.xbytes, b.xdst + q * G5_ROWB, (int)voff[q], b.soff);
       } else {
@@ -655,7 +652,7 @@ __global__ __launch_bounds__(256, 1) void gemm5_kernel(G5Params p, Epi epi) {
     // (all inline asm) and the counted waits:  R(b0) | s0: R(b1) W(b0) | s8: R(b2) W(b1) E0 | s16: R(b3) W(b2) | s17: W(E0) |
     // s24: R(b4) W(b3) | s32: R(b5) W(b4) | s33: E1 | s40: R(b6) W(b5) | s41: W(E1) | s48: R(b7) W(b6) | s56: W(b7).
     auto phase = [&](auto mf_c, auto ep_c, int j) {
-      constexpr bool MF = decltype(mf_c)::value && !(VBX_G5_ABL & 8), EP = decltype(ep_c)::value && !(VBX_G5_ABL & 1);
+      constexpr bool MF = decltype(mf_c)::value, EP = decltype(ep_c)::value;
       constexpr int EE = EP ? E : 0, X4 = MF ? 4 : 0;
       const unsigned so = (unsigned)((j % G5_NSLOT) * G5_SLOT);
       const unsigned ra = rot_a + (unsigned)(((j - 1) & 3) * G5_ROTSLOT);
@@ -774,16 +771,14 @@ int launch5(const vbx_gemm_desc* d, const Epi& epi, int nslab, bool train, hipSt
   if (p.wpp > p.nrb) p.wpp = p.nrb;
   int grid = p.npan * p.wpp;
   p.px = 0; p.xs = 0;
-  static const bool xcd_map = !(getenv("VBX_GEMM5_XCD") && atoi(getenv("VBX_GEMM5_XCD")) == 0);
-  if (xcd_map && cus == ncu && ncu % 8 == 0 && p.nrb >= 8 * 8) {
+  if (cus == ncu && ncu % 8 == 0 && p.nrb >= 8 * 8) {
     // the XCD map with the lowest cost = max over panels of (row blocks per workgroup x the panel's relative block time, Epi::panel_cost:
     // a v head of to_qkv has a light epilogue), if that is no worse than the plain map; ties go to fewer panel groups (= fewer L2s
-    // fetching an activation row).  VBX_GEMM5_PX=<1|2|4> forces one (A/B).
-    static const int px_force = getenv("VBX_GEMM5_PX") ? atoi(getenv("VBX_GEMM5_PX")) : 0;
+    // fetching an activation row).  (The three maps forced one by one: profiles/r06_gemm5_fetch_by_work_map.txt.)
     const int xs = ncu / 8;
     float best = (float)cdiv(p.nrb, p.wpp);
     for (int px = 1; px <= 4; px *= 2) {
-      if (p.npan % px || (px_force && px != px_force)) continue;
+      if (p.npan % px) continue;
       const int ppg = p.npan / px, nrg = 8 / px;
       if (ppg > xs) continue;
       const int base = xs / ppg, extra = xs - base * ppg, rows_max = cdiv(p.nrb, nrg);  // (slices differ by at most one row block)
@@ -793,7 +788,7 @@ int launch5(const vbx_gemm_desc* d, const Epi& epi, int nslab, bool train, hipSt
           const float c = (float)cdiv(rows_max, pl < extra ? base + 1 : base) * Epi::panel_cost(pl * px + pg, p.npan);
           cost = c > cost ? c : cost;
         }
-      if (cost < best - 1e-3f || (px_force && !p.px) || (!p.px && cost <= best + 1e-3f)) { best = cost < best ? cost : best; p.px = px; p.xs = xs; grid = ncu; }
+      if (cost < best - 1e-3f || (!p.px && cost <= best + 1e-3f)) { best = cost < best ? cost : best; p.px = px; p.xs = xs; grid = ncu; }
     }
   }
   if (d->f16) return train ? launch5k<Epi, true, true>(p, epi, grid, st) : launch5k<Epi, true, false>(p, epi, grid, st);

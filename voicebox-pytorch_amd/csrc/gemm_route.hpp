@@ -8,7 +8,7 @@
 namespace gemm_route {
 
 struct Facts {
-  int path;    // vbx_gemm_select / VBX_GEMM_PATH: 0 automatic, 1 the 128-wide kernels only, 2 / 3 gemm3 / gemm4 wherever they serve,
+  int path;    // vbx_gemm_select: 0 automatic, 1 the 128-wide kernels only, 2 / 3 gemm3 / gemm4 wherever they serve,
                // 4 = 0 with the weight-stationary kernel on whatever VBX_GEMM5 says
   bool gemm5;  // VBX_GEMM5 preset (on unless VBX_GEMM5=0)
   int cus;     // CUs a gemm5 launch may use on the current device (vbx_gemm5_cu_limit applied)
@@ -84,8 +84,8 @@ inline int tile128_family(const vbx_gemm_desc* d) {
 //  * the other NT / NN GEMMs stay on the 128-wide kernels except the cases below: at K = dim = 512 a tile's k-loop (12-14 us for
 //    256 x 256) is followed by a VALU-bound epilogue of the same order (qk-norm + rotary 10-13 us, GEGLU 5.5 us:
 //    tools/native/gemm_trace.cpp) during which the matrix pipes idle; three independent 128 x 128 workgroups per CU overlap the two
-//    phases better than one 256 x 256 or two lock-stepped 128 x 256 workgroups (a start-phase stagger of the co-resident workgroups,
-//    VBX_GEMM_STAGGER, did not help either); the N = dim GEMMs have too few wide tiles.
+//    phases better than one 256 x 256 or two lock-stepped 128 x 256 workgroups (a start-phase stagger of the co-resident workgroups
+//    did not help either; its busy-wait was removed, docs/history.md); the N = dim GEMMs have too few wide tiles.
 // Paths 2 / 3 force the wide tiles for measurements (tools/native/gemm3_check).
 inline int route(const vbx_gemm_desc* d, const Facts& f) {
   if (f.path == 1) return tile128_family(d);

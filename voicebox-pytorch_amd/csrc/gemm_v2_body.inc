@@ -21,25 +21,6 @@
   DmaPlan<MB, 128> db;
   da.init(p.A, p.lda, m0, p.M, tid);
   db.init(p.B, p.ldb, n0, p.N, tid);
-  if (p.abl & 24) {  // ablation: operand tiles stored as contiguous 8 KiB k-tile images (what a tiled layout would stream)
-    const int nkt = (p.K + BK2 - 1) / BK2;
-    if (p.abl & 8) {
-#pragma unroll
-      for (int i = 0; i < DmaPlan<MA, BM_>::N; i++) {
-        da.base[i] = p.A + ((long)tm * nkt * (BM_ * 32)) + (i * 256 + tid) * 8;
-        da.kstride = BM_;  // k0 * kstride = (k0/32) * BM_*32
-        da.ok[i] = true; da.kq[i] = 0;
-      }
-    }
-    if (p.abl & 16) {
-#pragma unroll
-      for (int i = 0; i < 2; i++) {
-        db.base[i] = p.B + ((long)tn * nkt * 4096) + (i * 256 + tid) * 8;
-        db.kstride = 128;
-        db.ok[i] = true; db.kq[i] = 0;
-      }
-    }
-  }
   FragPlan<MA> fa;
   FragPlan<MB> fb;
   fa.init(smem, wm * 64, lane);
@@ -70,22 +51,9 @@
     } else {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
-    if (!(p.abl & 4)) __builtin_amdgcn_s_barrier();  // tile t visible to all waves; everyone is done reading tile t-1
-    if (t + NST - 1 < nt && (p.abl & 128) && !(p.abl & 1)) {  // A/B (VBX_GEMM_ABL=128): the DMAs in FRONT of the fragment reads
-      da.issue(smem + NXT * STAGE_BYTES, kbeg + (t + NST - 1) * BK2, kend, tid);
-      db.issue(smem + NXT * STAGE_BYTES + OP_BYTES, kbeg + (t + NST - 1) * BK2, kend, tid);
-    }
+    __builtin_amdgcn_s_barrier();  // tile t visible to all waves; everyone is done reading tile t-1
     bf16x8 af[4], bfr[4];
     s16x4 alo[4], ahi[4], blo[4], bhi[4];
-    if ((p.abl & 2) && t > 0) {  // ablation: skip the LDS fragment reads (registers keep whatever they hold)
-#pragma unroll
-      for (int s = 0; s < 4; s++) { asm volatile("" : "=v"(af[s])); asm volatile("" : "=v"(bfr[s])); }
-#pragma unroll
-      for (int i = 0; i < 4; i++)
-#pragma unroll
-        for (int j = 0; j < NT_; j++) acc[i][j] = mfma16<F16>(af[i], bfr[j], acc[i][j]);
-      return;
-    }
     fa.template read<STG * STAGE_BYTES, 0>(af[0], alo[0], ahi[0]);
     fa.template read<STG * STAGE_BYTES, 1>(af[1], alo[1], ahi[1]);
     fa.template read<STG * STAGE_BYTES, 2>(af[2], alo[2], ahi[2]);
@@ -97,8 +65,9 @@
       fb.template read<STG * STAGE_BYTES + OP_BYTES, 3>(bfr[3], blo[3], bhi[3]);
     }
     // the DMAs of tile t+NST-1 (into the slot tile t-1 used) go out BEHIND the fragment reads: the LDS round trip then runs under
-    // their issue time (back to back 1-3 % faster on the model's shapes, neutral in the train step)
-    if (t + NST - 1 < nt && !(p.abl & (1 | 128))) {
+    // their issue time (back to back 1-3 % faster on the model's shapes than in front of them, neutral in the train step; the arm
+    // that issued them in front was removed, docs/history.md)
+    if (t + NST - 1 < nt) {
       da.issue(smem + NXT * STAGE_BYTES, kbeg + (t + NST - 1) * BK2, kend, tid);
       db.issue(smem + NXT * STAGE_BYTES + OP_BYTES, kbeg + (t + NST - 1) * BK2, kend, tid);
     }
@@ -134,15 +103,6 @@
   GEMM2_TRACE_MARK();
 #endif
   float* Cs = reinterpret_cast<float*>(smem);
-  if (p.abl & 64) {  // ablation: no epilogue at all (keep the accumulators alive)
-    float t = 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; i++)
-#pragma unroll
-      for (int j = 0; j < NT_; j++) t += acc[i][j][0] + acc[i][j][1] + acc[i][j][2] + acc[i][j][3];
-    if (t == 123.456f) Cs[tid] = t;
-    return;
-  }
 #pragma unroll
   for (int h = 0; h < WM; h++) {
     __syncthreads();  // ring (h = 0) / previous half (h = 1) no longer read
@@ -159,5 +119,5 @@
           }
     }
     __syncthreads();
-    if (!(p.abl & 32)) epi(Cs, m0 + h * 64, n0, tid, split, p.M, p.N, 64);
+    epi(Cs, m0 + h * 64, n0, tid, split, p.M, p.N, 64);
   }

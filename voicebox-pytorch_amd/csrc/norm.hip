@@ -1,7 +1,6 @@
 // RMSNorm / AdaptiveRMSNorm forward+backward and the backward of MultiheadRMSNorm+rotary.
 // Memory-bound row kernels: one wave64 per row, float4 (16 B/lane) loads, wave-shuffle reductions.
 #include "common.hpp"
-#include <stdlib.h>
 
 namespace {
 
@@ -509,10 +508,6 @@ __global__ __launch_bounds__(256) void qknorm_rope_bwd_kernel(const float* __res
 
 }  // namespace
 
-static bool rms_lean() {  // VBX_RMS_LEAN=0: the generic kernels also at the widths the lean ones serve (tests, A/B)
-  static const bool lean = !(getenv("VBX_RMS_LEAN") && atoi(getenv("VBX_RMS_LEAN")) == 0);
-  return lean;
-}
 static int rmsnorm_fwd_launch(const float* x, const float* gamma, const float* beta, long gb_stride, void* y_bf16, void* y_f16,
                               float* y_f32, int B, int Np, int n0, int rows_per_batch, int D, void* stream) {
   VBX_REQUIRE(x && gamma && (y_bf16 || y_f16 || y_f32), "vbx_rmsnorm_fwd: null pointer");
@@ -524,7 +519,7 @@ static int rmsnorm_fwd_launch(const float* x, const float* gamma, const float* b
 #define VBX_RF_LAUNCH1(NC_)                                                                                                      \
   hipLaunchKernelGGL((rmsnorm_fwd_kernel<1, NC_>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, gamma, beta, gb_stride, \
                      (u16*)y_bf16, (u16*)y_f16, B, Np, n0, rows_per_batch, D, y_f32)
-  if (rms_lean() && (D == 512 || D == 1024 || D == 2048)) {
+  if (D == 512 || D == 1024 || D == 2048) {  // the lean kernels; every other width: the generic ones below
     const dim3 lgrid(cdiv(rows_per_batch, 4), B);
 #define VBX_RF_LAUNCHL(NC_)                                                                                                          \
   hipLaunchKernelGGL((rmsnorm_fwd_lean_kernel<NC_>), lgrid, dim3(256), 0, (hipStream_t)stream, x, gamma, beta, gb_stride, (u16*)y_bf16, \
@@ -568,7 +563,7 @@ extern "C" int vbx_rmsnorm_bwd(const float* x, const float* gamma, long gb_strid
   VBX_REQUIRE(!colpart || dx_in, "vbx_rmsnorm_bwd: column sums need dx_in");
   const bool eight = (size_t)8 * 3 * D * sizeof(float) <= 160 * 1024;
   const size_t lds = (size_t)(eight ? 8 : 4) * 3 * D * sizeof(float);
-  if (rms_lean() && (D == 512 || D == 1024)) {  // (D = 2048: the [8][3][D] reduction buffer exceeds the LDS, generic path)
+  if (D == 512 || D == 1024) {  // (D = 2048: the [8][3][D] reduction buffer exceeds the LDS, generic path)
 #define VBX_RB_LAUNCHL(NC_)                                                                                                          \
   do {                                                                                                                               \
     static bool attr_ = false;                                                                                                       \

@@ -398,10 +398,8 @@ WgoSide* wgo_side(bool create) {
   if (sides[dev] || !create) return sides[dev];
   WgoSide* s = new WgoSide;
   int least = 0, greatest = 0;  // "least" is the numerically largest value: the lowest priority
-  const char* pe = getenv("VBX_WGRAD_OVERLAP_PRIORITY");  // measurement only: "default" = same priority as the caller's stream
-  const bool low = !(pe && !strcmp(pe, "default"));
   bool ok = hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess &&
-            hipStreamCreateWithPriority(&s->st, hipStreamNonBlocking, low ? least : 0) == hipSuccess;
+            hipStreamCreateWithPriority(&s->st, hipStreamNonBlocking, least) == hipSuccess;
   for (int i = 0; ok && i < wgrad_overlap::EV_N; i++) ok = hipEventCreateWithFlags(&s->ev[i], hipEventDisableTiming) == hipSuccess;
   if (!ok) {
     for (auto e : s->ev) if (e) (void)hipEventDestroy(e);
