@@ -234,6 +234,14 @@ int vbx_dropout_rows(void* x_f16, void* x_bf16, long rows, int cols, int ld, uns
                      void* stream);
 /* the same mask (same seed / stream_id / element index) on an fp32 matrix: precise mode's unrounded GEGLU output */
 int vbx_dropout_rows_f32(float* x, long rows, int cols, int ld, unsigned long long seed, unsigned stream_id, float p, void* stream);
+/* vbx_attn_fwd for prefix lengths (inference; the sampler's lens=): key_lens int32 [B] on the device, key_lens[b] >= 1; keys at or
+ * past key_lens[b] are masked whatever `mask` (the equivalent prefix mask, or NULL) says.  A workgroup of batch row b walks
+ * ceil(key_lens[b] / 64) key tiles instead of ceil(Np / 64) (the DMA ring prefetches against the same bound); a 128-row query tile
+ * wholly at or past key_lens[b] writes zeros and lse 1e30 and leaves.  Every output row and lse of a query < key_lens[b] is bit-equal
+ * to vbx_attn_fwd with the prefix mask: a skipped tile would add +0 to l and O, and max(m, -inf) = m.  Rows >= key_lens[b] are
+ * padding.  The benchmark's kernel is a separate instantiation and is not changed by this one. */
+int vbx_attn_fwd_lens(const void* q16, const void* k16, const void* v16, const uint8_t* mask, const int* key_lens, void* out16,
+                      void* out_bf16, float* lse, int B, int H, int Np, float scale, void* stream);
 int vbx_attn_fwd_dropout(const void* q16, const void* k16, const void* v16, const uint8_t* mask, void* out16, void* out_bf16,
                          float* lse, int B, int H, int Np, float scale, const void* bits_rm, float p, void* stream);
 int vbx_attn_bwd_dropout(const void* q16, const void* k16, const void* qb, const void* kb, const void* v, const uint8_t* mask,
@@ -542,6 +550,11 @@ long vbx_duration_head_bwd_scratch_floats(int B, int n, int D);
 int vbx_duration_head_bwd(const float* hid, const float* w, const float* durations, const float* target, const uint8_t* loss_mask,
                           const float* den, const float* gscale, float* dhid, float* dw, float* db, float* scratch, int B, int n, int D,
                           void* stream);
+/* Length regulator (sample(lens="durations")): ids int64 [B][K] (-1 = padding phoneme), durations fp32 [B][K] -> lens int32 [B],
+ * lens[b] = sum over ids != -1 of int(max(durations, 1)) (truncation; padding phonemes own no frames), and, unless aligned is NULL,
+ * aligned int64 [B][Nmax]: phoneme i's id over its run of frames, 0 from lens[b] on; frames >= Nmax are not written.  One workgroup
+ * per row: a prefix sum over K, each thread writes the runs of its phonemes.  Call once with aligned NULL, read lens, allocate. */
+int vbx_length_regulate(const long* ids, const float* durations, long* aligned, int* lens, int B, int K, int Nmax, void* stream);
 int vbx_phoneme_emb_bwd(const long* ids, const float* g_packed, int ld_packed, const float* g_emb, float* gtable, long rows, int V,
                         int E, void* stream);
 /* to_pred = Linear(dim, 1) + squeeze (voicebox_pytorch.py:672-675): out[r] = x[r,:] . w + bias[0]  (bias may be NULL). */
@@ -675,6 +688,14 @@ enum { VBX_ODE_CTRL_STEP = 0, VBX_ODE_CTRL_INIT0 = 1, VBX_ODE_CTRL_INIT1 = 2 };
 long vbx_ode_norm_slab_doubles(long n);
 int vbx_ode_norm(double* state, double* slab, int mode, const float* y0, const float* y1, const float* const* k, const float* c, int S,
                  long n, int nfe_per_eval, void* stream);
+/* vbx_ode_norm over the real frames of a padded batch (sample(lens=)): the state is [B][N][row_elems], N = n / (B row_elems),
+ * row_elems a multiple of 4; every element of a frame >= lens[b] (int32 [B], device) leaves both the sums of squares and the count
+ * (n becomes row_elems sum_b lens[b]) and is not read.  Same two launches, same grid and summation order: with lens == NULL or every
+ * lens[b] == N the state gets the bits vbx_ode_norm writes. */
+int vbx_ode_norm_lens(double* state, double* slab, int mode, const float* y0, const float* y1, const float* const* k, const float* c,
+                      int S, long n, int nfe_per_eval, const int* lens, int B, int row_elems, void* stream);
+/* x[b][n][:] = 0 for n >= lens[b]; x fp32 [B][N][D], lens int32 [B] on the device */
+int vbx_zero_tail_rows(float* x, const int* lens, int B, int N, int D, void* stream);
 /* after an attempt: if LAST && !DONE, y <- y1 and k1 <- k7 (first-same-as-last); the last accepted step stays for vbx_ode_dense */
 int vbx_ode_commit(float* y, float* k1, const float* y1, const float* k7, const double* state, long n, void* stream);
 /* dense output at TEND inside the last accepted step [T0, T1] (torchdiffeq _interp_fit / _interp_evaluate): y_mid = y0 + sum_j
@@ -896,6 +917,9 @@ typedef struct {
   const int* ada_counter;       /* the forward then skips the time embedding and the projection GEMV and takes time point         */
   int ada_slot;                 /* ada_stride * ada_counter[0] + ada_slot of the table (`times` is not read)                     */
   int ada_stride;               /* time points per interval of ada_table, >= 1 (midpoint 2, euler 1, rk4 4); 0 <= ada_slot < ada_stride */
+  const int* key_lens;          /* inference only, or NULL: [B] int32 on the device, key_lens[b] = R + len_b >= 1 where attn_mask_p is the
+                                   prefix mask n < key_lens[b] (the sampler's lens=).  The fast-path forward then runs vbx_attn_fwd_lens:
+                                   key tiles past the length are not walked.  Requires attn_mask_p; precise mode ignores it (mask only). */
 } vbx_io;
 
 size_t vbx_model_wpack_bytes(const vbx_model* m);

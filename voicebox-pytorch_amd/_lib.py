@@ -45,6 +45,7 @@ _PROTOS = {
     "vbx_rmsnorm_bwd_chunks": [I],
     "vbx_rmsnorm_bwd": [P, P, L, P, P, P, P, P, P, I, I, I, I, I, P],
     "vbx_attn_fwd": [P, P, P, P, P, P, P, I, I, I, F, P],
+    "vbx_attn_fwd_lens": [P, P, P, P, P, P, P, P, I, I, I, F, P],
     "vbx_attn_bwd": [P, P, P, P, P, P, P, I, P, P, P, P, P, P, I, I, I, I, F, P, P],
     "vbx_attn_bwd_fused": [P, P, P, P, P, P, P, I, P, P, P, P, P, P, P, P, P, F, P, I, P, I, I, I, F, P, P],
     "vbx_attn_bwd_select": [I],
@@ -108,6 +109,7 @@ _PROTOS = {
     "vbx_duration_head_fwd": [P, P, P, P, P, P, P, P, P, I, I, I, P],
     "vbx_duration_head_bwd": [P, P, P, P, P, P, P, P, P, P, P, I, I, I, P],
     "vbx_phoneme_emb_bwd": [P, P, I, P, P, L, I, I, P],
+    "vbx_length_regulate": [P, P, P, P, I, I, I, P],
     "vbx_stack_input": [P, P, P, I, I, I, I, P],
     "vbx_stack_input_bwd": [P, P, P, I, I, I, I, P],
     "vbx_unet_cat": [P, P, F, P, P, L, I, P],
@@ -154,6 +156,8 @@ _PROTOS = {
     "vbx_ode_stage_time": [P, I, P, P, I, I, P],
     "vbx_ode_stage_time_dp": [P, I, P, F, I, P],
     "vbx_ode_norm": [P, P, I, P, P, P, P, I, L, I, P],
+    "vbx_ode_norm_lens": [P, P, I, P, P, P, P, I, L, I, P, I, I, P],
+    "vbx_zero_tail_rows": [P, P, I, I, I, P],
     "vbx_ode_commit": [P, P, P, P, P, L, P],
     "vbx_ode_dense": [P, P, P, P, P, P, L, P],
     "vbx_stream_delay": [F, P],

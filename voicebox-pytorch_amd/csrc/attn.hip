@@ -356,6 +356,17 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_kernel_v3_drop(const u16* __r
 #include "attn_fwd_v3_body.inc"
 }
 #undef VBX_FWD_DROP
+// the same body with per-batch-row key lengths (inference, the sampler's lens=): the key loop stops at the last live tile of its row
+#define VBX_FWD_LENS
+__global__ __launch_bounds__(256, 4) void attn_fwd_kernel_v3_lens(const u16* __restrict__ q16, const u16* __restrict__ k16,
+                                                                  const u16* __restrict__ vv, const uint8_t* __restrict__ mask,
+                                                                  u16* __restrict__ out, u16* __restrict__ outb,
+                                                                  float* __restrict__ lse, int H, int Np, float scale2, int BH, int xmap,
+                                                                  const int* __restrict__ key_lens) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+#include "attn_fwd_v3_body.inc"
+}
+#undef VBX_FWD_LENS
 
 // ---- Round-4 experiments on the forward, measured at the benchmark grid (8 x 16 heads x 1040 rows, stand-alone, same box) and removed:
 //  * "v4": 256-row workgroups, a wave owning TWO 32-query blocks whose chains are interleaved in one instruction stream (S of block B
@@ -1091,6 +1102,21 @@ extern "C" float vbx_attn_q_prescale(float scale) { return scale * LOG2E; }
 extern "C" int vbx_attn_fwd(const void* q16, const void* k16, const void* v, const uint8_t* mask, void* out, void* out_bf16,
                             float* lse, int B, int H, int Np, float scale, void* stream) {
   return attn_fwd_impl(q16, k16, v, mask, out, out_bf16, lse, B, H, Np, scale, nullptr, 0.f, stream);
+}
+// Prefix lengths: keys (and whole query tiles) at or past key_lens[b] are dead.  Every output row and lse of a query < key_lens[b] is
+// bit-equal to vbx_attn_fwd with the equivalent prefix mask; rows past it are padding (zeros / lse 1e30 where their whole 128-row tile
+// is dead, vbx_attn_fwd's values otherwise).  key_lens[b] >= 1: there is no empty-batch pass here.
+extern "C" int vbx_attn_fwd_lens(const void* q16, const void* k16, const void* v, const uint8_t* mask, const int* key_lens, void* out,
+                                 void* out_bf16, float* lse, int B, int H, int Np, float scale, void* stream) {
+  VBX_REQUIRE(q16 && k16 && v && out && lse && key_lens, "vbx_attn_fwd_lens: null pointer");
+  VBX_REQUIRE(B > 0 && H > 0 && Np > 0 && scale > 0.f, "vbx_attn_fwd_lens: bad dims");
+  const int xmap = attn_xmap_for(Np);
+  const int BH = B * H;
+  dim3 grid(cdiv(Np, 128) * ((xmap & 1) ? cdiv(BH, 8) * 8 : BH));
+  hipLaunchKernelGGL(attn_fwd_kernel_v3_lens, grid, dim3(256), A3ST * ASTAGE, (hipStream_t)stream, (const u16*)q16, (const u16*)k16,
+                     (const u16*)v, mask, (u16*)out, (u16*)out_bf16, lse, H, Np, QK_UNIT, BH, xmap, key_lens);
+  VBX_LAUNCH_CHECK();
+  return 0;
 }
 extern "C" int vbx_attn_fwd_dropout(const void* q16, const void* k16, const void* v, const uint8_t* mask, void* out, void* out_bf16,
                                     float* lse, int B, int H, int Np, float scale, const void* bits_rm, float p, void* stream) {

@@ -47,11 +47,17 @@
     s4 = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf0, qf2[0], s4, 0, 0, 0);
     s4 = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf1, qf2[1], s4, 0, 0, 0);
     const int kg0 = kt * 64 + wave * 16 + 4 * g;
-    if (mask != nullptr || kt * 64 + 64 > Np) {
+#ifdef VBX_FWD_LENS
+#define VBX_KLIM kend  // vbx_attn_fwd_lens: keys stop at key_lens[b]
+#else
+#define VBX_KLIM Np
+#endif
+    if (mask != nullptr || kt * 64 + 64 > VBX_KLIM) {
 #pragma unroll
       for (int i = 0; i < 4; i++) {
         const int kg = kg0 + i;
-        bool ok = kg < Np;
+        bool ok = kg < VBX_KLIM;
+#undef VBX_KLIM
         if (ok && mask) ok = mask[(long)b * Np + kg] != 0;
         if (!ok) s4[i] = NEG_INF;
       }

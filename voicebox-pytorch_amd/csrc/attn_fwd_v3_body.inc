@@ -2,6 +2,10 @@
 // outb, lse, H, Np, scale2, BH, xmap and `smem`.  With VBX_FWD_DROP defined (training-time attention dropout, attend.py:131) also
 // dbits (row-major keep bits R[bh][q][W2], ops.hip), W2 and rkeep: the softmax statistics (row maximum, row sum, LSE) are those
 // of the UNdropped probabilities, dropped entries are zeroed in the P fragment only, and 1 / keep rides in the final 1 / l.
+// With VBX_FWD_LENS defined (the sampler's prefix lengths, vbx_attn_fwd_lens) also key_lens [B]: keys at or past key_lens[b] are
+// masked whatever `mask` says, so the key loop and the DMA ring stop at tile ceil(key_lens[b] / 64) -- a tile past it has maximum -inf
+// and probabilities 0, it would add +0 to l and O and leave m alone -- and a query tile wholly at or past key_lens[b] (padding
+// queries only) writes zeros and lse 1e30 without touching K or V.  Without the macro the text below is what it was.
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, hi = lane >> 5;
   const AttnCoord co = attn_coord(H, Np, BH, xmap);
   if (!co.ok) return;
@@ -14,7 +18,25 @@
   const bool active = q0 < Np;
   const int q = q0 + (lane & 31);
   const int qc = min(q, Np - 1);
+#ifdef VBX_FWD_LENS
+  const int kend = min(max(key_lens[b], 0), Np);  // uniform over the workgroup
+  const int ntiles = (kend + 63) / 64;
+  if (co.tile * 128 >= kend) {
+    for (int i = tid; i < 128 * 8; i += 256) {
+      const int qq = co.tile * 128 + (i >> 3);
+      if (qq < Np) {
+        const long go = ((long)b * Np + qq) * (H * 64) + h * 64 + (i & 7) * 8;
+        *reinterpret_cast<uint4*>(out + go) = make_uint4(0u, 0u, 0u, 0u);
+        if (outb) *reinterpret_cast<uint4*>(outb + go) = make_uint4(0u, 0u, 0u, 0u);
+        if ((i & 7) == 0) lse[bh * Np + qq] = 1e30f;
+      }
+    }
+    ATTN_TRACE_END(0);
+    return;
+  }
+#else
   const int ntiles = (Np + 63) / 64;
+#endif
 
   // K|V tile DMA (round 6): the per-lane part of the source address is a 32-bit offset inside a 64-row tile, computed ONCE; the
   // tile's base pointer and the LDS destination are scalars, so a tile costs 4 LDS-DMA instructions and no vector ALU work (the
@@ -131,14 +153,22 @@
     asm_read_tr<SO>(vl[1], vh[1], va[1], va8[1]);
     asm_read_tr<SO + 2048>(vl[2], vh[2], va[0], va8[0]);
     asm_read_tr<SO + 2048>(vl[3], vh[3], va[1], va8[1]);
+#ifdef VBX_FWD_LENS
+    const bool need_mask = (mask != nullptr) || (k0 + 64 > kend);
+#else
     const bool need_mask = (mask != nullptr) || (k0 + 64 > Np);
+#endif
     if (need_mask) {
 #pragma unroll
       for (int kb = 0; kb < 2; kb++)
 #pragma unroll
         for (int r = 0; r < 16; r++) {
           const int kg = k0 + kb * 32 + acc_row(r, hi);
+#ifdef VBX_FWD_LENS
+          bool ok = kg < kend;
+#else
           bool ok = kg < Np;
+#endif
           if (ok && mask) ok = mask[(long)b * Np + kg] != 0;
           if (!ok) s[kb][r] = NEG_INF;
         }

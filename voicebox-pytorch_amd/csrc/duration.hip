@@ -169,6 +169,45 @@ __global__ __launch_bounds__(256) void phoneme_emb_bwd_kernel(const long* __rest
   }
 }
 
+// Length regulator of sample(lens="durations"): one workgroup per batch row.  Phoneme i with ids[i] != -1 owns rep_i =
+// int(max(durations[i], 1)) frames (torch's clamp(min=1).int(): truncation; a NaN counts 1), a -1 padding phoneme owns none.  Thread t
+// takes the contiguous phonemes [t c, t c + c), c = ceil(K / 256): its own sum, an exclusive scan of the 256 sums through LDS, then it
+// writes its phonemes' runs; lens[b] = the row total, frames [lens[b], Nmax) get id 0.  aligned == NULL: lens only.  Frames at or past
+// Nmax are never written.
+constexpr int LR_THREADS = 256;
+VBX_DEV long lr_reps(long id, float d) { return id == -1 ? 0L : (long)fminf(fmaxf(d, 1.0f), 1073741824.0f); }
+__global__ __launch_bounds__(LR_THREADS) void length_regulate_kernel(const long* __restrict__ ids, const float* __restrict__ dur,
+                                                                     long* __restrict__ aligned, int* __restrict__ lens, int K,
+                                                                     int Nmax) {
+  __shared__ long scan[LR_THREADS];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int c = (K + LR_THREADS - 1) / LR_THREADS;
+  const int i0 = min(tid * c, K), i1 = min(i0 + c, K);
+  const long* idr = ids + (long)b * K;
+  const float* dr = dur + (long)b * K;
+  long mine = 0;
+  for (int i = i0; i < i1; i++) mine += lr_reps(idr[i], dr[i]);
+  scan[tid] = mine;
+  __syncthreads();
+  for (int off = 1; off < LR_THREADS; off <<= 1) {  // inclusive scan
+    const long add = tid >= off ? scan[tid - off] : 0L;
+    __syncthreads();
+    scan[tid] += add;
+    __syncthreads();
+  }
+  const long total = scan[LR_THREADS - 1];
+  if (tid == 0) lens[b] = (int)(total < 2147483647L ? total : 2147483647L);
+  if (!aligned) return;
+  long* out = aligned + (long)b * Nmax;
+  long pos = scan[tid] - mine;
+  for (int i = i0; i < i1 && pos < Nmax; i++) {
+    const long id = idr[i], end = pos + lr_reps(id, dr[i]);
+    for (long j = pos; j < end && j < Nmax; j++) out[j] = id;
+    pos = end;
+  }
+  for (long j = total + tid; j < Nmax; j += LR_THREADS) out[j] = 0;
+}
+
 }  // namespace
 
 #define ST ((hipStream_t)stream)
@@ -208,6 +247,15 @@ extern "C" int vbx_phoneme_emb_bwd(const long* ids, const float* g_packed, int l
   VBX_REQUIRE(rows > 0 && V > 0 && E > 0 && E <= 2048 && (!g_packed || ld_packed >= E), "vbx_phoneme_emb_bwd: bad dims rows=%ld V=%d E=%d ld=%d",
               rows, V, E, ld_packed);
   hipLaunchKernelGGL(phoneme_emb_bwd_kernel, dim3(V), dim3(256), 0, ST, ids, g_packed, ld_packed, g_emb, gtable, rows, E);
+  VBX_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int vbx_length_regulate(const long* ids, const float* durations, long* aligned, int* lens, int B, int K, int Nmax,
+                                   void* stream) {
+  VBX_REQUIRE(ids && durations && lens, "vbx_length_regulate: null pointer");
+  VBX_REQUIRE(B > 0 && K > 0 && (!aligned || Nmax > 0), "vbx_length_regulate: bad dims B=%d K=%d Nmax=%d", B, K, Nmax);
+  hipLaunchKernelGGL(length_regulate_kernel, dim3(B), dim3(LR_THREADS), 0, ST, ids, durations, aligned, lens, K, aligned ? Nmax : 0);
   VBX_LAUNCH_CHECK();
   return 0;
 }

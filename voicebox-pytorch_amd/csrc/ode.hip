@@ -111,15 +111,22 @@ VBX_DEV void block_sum2(double& a, double& b, double* sa, double* sb) {
 //   ERROR: (err / tol)^2, err = sum_j (c_j fp32(dt)) k_j (k1 .. k7, never stored), tol = atol + rtol max(|y0|, |y1|)   (lane 0)
 //   INIT0: (y0 / scale)^2 (lane 0) and (f0 / scale)^2 (lane 1), scale = atol + |y0| rtol, f0 = k[0]
 //   INIT1: ((f1 - f0) / scale)^2 (lane 0), f0 = k[0], f1 = k[1]
+// LENS (vbx_ode_norm_lens): the state is [B][N][D] with frame4 = D / 4 float4 per frame and batch4 = N * D / 4 per batch row; a frame
+// at or past lens[b] is padding and is not read -- same grid, same order, so at full lengths the sums are those of the plain kernel.
+template <bool LENS>
 __global__ __launch_bounds__(kNormThreads) void ode_norm_partials_kernel(double* __restrict__ slab, int mode, const float* y0,
                                                                          const float* y1, OdeTerms t, int S, const double* state,
-                                                                         long n4) {
+                                                                         long n4, const int* __restrict__ lens, long batch4, int frame4) {
   __shared__ double sa[kNormThreads], sb[kNormThreads];
   const float atol = (float)state[VBX_DP_ATOL], rtol = (float)state[VBX_DP_RTOL];
   float c[kMaxStages];
   if (mode == VBX_ODE_NORM_ERROR) load_coefs(c, t, S, nullptr, 0, nullptr, 0, 0, state, VBX_DP_DT);
   double a = 0.0, b = 0.0;
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+    if (LENS) {
+      const long row = i / batch4;
+      if ((i - row * batch4) / frame4 >= lens[row]) continue;
+    }
     const float4 u = ld4(y0, i);
     if (mode == VBX_ODE_NORM_ERROR) {
       const float4 v = ld4(y1, i), e = stage_sum(t, c, S, i);
@@ -151,9 +158,16 @@ __global__ __launch_bounds__(kNormThreads) void ode_norm_partials_kernel(double*
 }
 
 // Launch 2: one workgroup sums the slab in a fixed order (thread i: entries i, i + 256, ...; then the tree) and runs the controller.
+// lens != NULL: the mean is over the kept elements, n = row_elems * sum_b lens[b].
 __global__ __launch_bounds__(kNormThreads) void ode_control_kernel(double* __restrict__ state, const double* __restrict__ slab,
-                                                                   int nblocks, long n, int mode, int nfe_per_eval) {
+                                                                   int nblocks, long n, int mode, int nfe_per_eval,
+                                                                   const int* __restrict__ lens, int B, int row_elems) {
   __shared__ double sa[kNormThreads], sb[kNormThreads];
+  if (lens) {
+    long frames = 0;
+    for (int i = 0; i < B; i++) frames += lens[i];
+    n = frames * row_elems;
+  }
   double a = 0.0, b = 0.0;
   for (int i = threadIdx.x; i < nblocks; i += kNormThreads) {
     a += slab[2 * i];
@@ -241,6 +255,14 @@ __global__ void ode_dense_kernel(float* __restrict__ out, const float* __restric
   }
 }
 
+// x[b][n][:] = 0 for n >= lens[b]
+__global__ void zero_tail_rows_kernel(float* __restrict__ x, const int* __restrict__ lens, long total, long ND, int D) {
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const long b = i / ND;
+    if ((i - b * ND) / D >= lens[b]) x[i] = 0.f;
+  }
+}
+
 bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 bool load_terms(OdeTerms& t, const float* const* k, const float* c, int S) {
@@ -303,8 +325,9 @@ extern "C" int vbx_ode_stage_time_dp(float* times, int B, const double* state, f
 
 extern "C" long vbx_ode_norm_slab_doubles(long n) { return 2L * norm_blocks(n / 4); }
 
-extern "C" int vbx_ode_norm(double* state, double* slab, int mode, const float* y0, const float* y1, const float* const* k,
-                            const float* c, int S, long n, int nfe_per_eval, void* stream) {
+// lens == NULL: the whole state (vbx_ode_norm); else the state is [B][n / (B row_elems)][row_elems] and frames >= lens[b] are left out
+static int ode_norm_impl(double* state, double* slab, int mode, const float* y0, const float* y1, const float* const* k, const float* c,
+                         int S, long n, int nfe_per_eval, const int* lens, int B, int row_elems, void* stream) {
   OdeTerms t;
   const bool err = mode == VBX_ODE_NORM_ERROR;
   const int need = err ? S : (mode == VBX_ODE_NORM_INIT0 ? 1 : 2);
@@ -312,11 +335,36 @@ extern "C" int vbx_ode_norm(double* state, double* slab, int mode, const float* 
                   S <= kMaxStages && (!err || (y1 && c && aligned16(y1))) && n > 0 && n % 4 == 0 && aligned16(y0) &&
                   load_terms(t, k, c, S) && nfe_per_eval >= 1,
               "vbx_ode_norm: bad args");
+  VBX_REQUIRE(!lens || (B > 0 && row_elems > 0 && row_elems % 4 == 0 && n % ((long)B * row_elems) == 0),
+              "vbx_ode_norm_lens: the state must be [B][N][row_elems] with row_elems a multiple of 4");
   const int nb = norm_blocks(n / 4);
-  hipLaunchKernelGGL(ode_norm_partials_kernel, dim3(nb), dim3(kNormThreads), 0, ST, slab, mode, y0, y1, t, S, state, n / 4);
+  if (lens)
+    hipLaunchKernelGGL(ode_norm_partials_kernel<true>, dim3(nb), dim3(kNormThreads), 0, ST, slab, mode, y0, y1, t, S, state, n / 4, lens,
+                       n / B / 4, row_elems / 4);
+  else
+    hipLaunchKernelGGL(ode_norm_partials_kernel<false>, dim3(nb), dim3(kNormThreads), 0, ST, slab, mode, y0, y1, t, S, state, n / 4,
+                       nullptr, 0L, 0);
   VBX_LAUNCH_CHECK();
   const int ctrl = err ? VBX_ODE_CTRL_STEP : (mode == VBX_ODE_NORM_INIT0 ? VBX_ODE_CTRL_INIT0 : VBX_ODE_CTRL_INIT1);
-  hipLaunchKernelGGL(ode_control_kernel, dim3(1), dim3(kNormThreads), 0, ST, state, slab, nb, n, ctrl, nfe_per_eval);
+  hipLaunchKernelGGL(ode_control_kernel, dim3(1), dim3(kNormThreads), 0, ST, state, slab, nb, n, ctrl, nfe_per_eval, lens, B, row_elems);
+  VBX_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int vbx_ode_norm(double* state, double* slab, int mode, const float* y0, const float* y1, const float* const* k,
+                            const float* c, int S, long n, int nfe_per_eval, void* stream) {
+  return ode_norm_impl(state, slab, mode, y0, y1, k, c, S, n, nfe_per_eval, nullptr, 0, 0, stream);
+}
+
+extern "C" int vbx_ode_norm_lens(double* state, double* slab, int mode, const float* y0, const float* y1, const float* const* k,
+                                 const float* c, int S, long n, int nfe_per_eval, const int* lens, int B, int row_elems, void* stream) {
+  return ode_norm_impl(state, slab, mode, y0, y1, k, c, S, n, nfe_per_eval, lens, B, row_elems, stream);
+}
+
+extern "C" int vbx_zero_tail_rows(float* x, const int* lens, int B, int N, int D, void* stream) {
+  VBX_REQUIRE(x && lens && B > 0 && N > 0 && D > 0, "vbx_zero_tail_rows: bad args");
+  const long total = (long)B * N * D;
+  hipLaunchKernelGGL(zero_tail_rows_kernel, dim3(ode_grid(total)), dim3(256), 0, ST, x, lens, total, (long)N * D, D);
   VBX_LAUNCH_CHECK();
   return 0;
 }

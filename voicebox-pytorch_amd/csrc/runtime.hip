@@ -583,6 +583,7 @@ extern "C" int vbx_model_forward(const vbx_model* m, const vbx_io* io, void* str
               "vbx_model_forward: null io field");
   VBX_REQUIRE(!io->target || (io->loss_mask && io->loss), "vbx_model_forward: target needs loss_mask and loss");
   VBX_REQUIRE((io->attn_mask == nullptr) == (io->attn_mask_p == nullptr), "vbx_model_forward: attn_mask and attn_mask_p go together");
+  VBX_REQUIRE(!io->key_lens || io->attn_mask_p, "vbx_model_forward: key_lens restates a prefix attn_mask_p, which must be given too");
   hipStream_t st = (hipStream_t)stream;
   const Dims d = dims_of(m);
   WPack w;
@@ -686,7 +687,10 @@ extern "C" int vbx_model_forward(const vbx_model* m, const vbx_io* io, void* str
                               m->attn_dropout, stream));
     } else {
       ProfScope ps("fwd attention", st);
-      CK(vbx_attn_fwd(y.q16, y.k16, y.vh, io->attn_mask_p, y.oh, y.o, y.lse, d.B, d.H, d.Np, m->attn_scale, stream));
+      if (io->key_lens && !m->training)  // the sampler's prefix lengths: dead key tiles are not walked (bit-equal on live queries)
+        CK(vbx_attn_fwd_lens(y.q16, y.k16, y.vh, io->attn_mask_p, io->key_lens, y.oh, y.o, y.lse, d.B, d.H, d.Np, m->attn_scale, stream));
+      else
+        CK(vbx_attn_fwd(y.q16, y.k16, y.vh, io->attn_mask_p, y.oh, y.o, y.lse, d.B, d.H, d.Np, m->attn_scale, stream));
     }
     { ProfScope ps("fwd to_out", st);
       CK(gemm_nt(y.oh, d.I, w.layer[l].outh, d.I, (int)d.M, d.D, d.I, VBX_EPI_F32, x_mid, d.D, nullptr, x_in, nullptr, nullptr, st)); }

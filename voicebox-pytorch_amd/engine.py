@@ -28,7 +28,7 @@ class VbxIO(C.Structure):
     _fields_ = [("x", P), ("cond", P), ("cond_mask", P), ("attn_mask", P), ("attn_mask_p", P), ("loss_mask", P),
                 ("times", P), ("target", P), ("pred", P), ("loss", P), ("cond_ids", P), ("T", I), ("null_id", C.c_long),
                 ("drop_mask", P), ("null_cond", P), ("dx", P), ("dcond", P), ("dropout", I), ("drop_seed", C.c_ulonglong),
-                ("ada_table", P), ("ada_counter", P), ("ada_slot", I), ("ada_stride", I)]
+                ("ada_table", P), ("ada_counter", P), ("ada_slot", I), ("ada_stride", I), ("key_lens", P)]
 
 
 class VbxAdamSeg(C.Structure):
@@ -430,12 +430,15 @@ class Engine:
         self.packed_version = self.fp.weights_key()  # this engine's operand copies were refreshed in the same pass
 
     # -- forward
-    def forward(self, x, cond, cond_mask, times, attn_mask=None, target=None, loss_mask=None, pred_out=None, text=None, ada=None):
+    def forward(self, x, cond, cond_mask, times, attn_mask=None, target=None, loss_mask=None, pred_out=None, text=None, ada=None,
+                attn_mask_p=None, key_lens=None):
         """All tensors on self.device, fp32 contiguous / bool.  Returns the loss tensor (1,) if target is given,
         else the prediction (B,N,D).  text (text-conditioned models): (ids int64 (B,T), null_id, drop_mask bool (B,) or None,
         null_cond fp32 (D,)).  ada (inference, the sampler): (table fp32 [stride * intervals, L, 4 * D], counter int32 [1], slot, stride) --
         the adaLN projections of every time point of the ODE grid, precomputed (stride >= 1 time points per interval, this forward at
-        row stride * counter + slot); `times` is then not read."""
+        row stride * counter + slot); `times` is then not read.  attn_mask_p (the sampler, with attn_mask): the caller's own uint8
+        [B, N + R] copy of attn_mask behind R ones -- a static buffer whose address a captured graph may keep -- instead of the copy
+        built here per call; key_lens int32 [B] = R + len_b where attn_mask is the prefix mask n < len_b (vbx_io.key_lens)."""
         self.bind_params()
         B, N, D = self.B, self.N, self.Din
         assert x.shape == (B, N, D) and cond.shape == (B, N, D), (tuple(x.shape), tuple(cond.shape), (B, N, D))
@@ -445,11 +448,17 @@ class Engine:
         if attn_mask is not None:
             am = _u8(attn_mask)
             R = self.cfg["R"]
-            amp = torch.cat((torch.ones(B, R, dtype=torch.uint8, device=am.device), am), dim=1).contiguous() if R else am
+            if attn_mask_p is not None:
+                assert attn_mask_p.shape == (B, N + R) and attn_mask_p.dtype == torch.uint8 and attn_mask_p.is_contiguous()
+                amp = attn_mask_p
+            else:
+                amp = torch.cat((torch.ones(B, R, dtype=torch.uint8, device=am.device), am), dim=1).contiguous() if R else am
+        assert key_lens is None or (am is not None and target is None and key_lens.dtype == torch.int32 and key_lens.shape == (B,))
         io = self.io
         io.x, io.cond, io.cond_mask = x.data_ptr(), cond.data_ptr(), cm.data_ptr()
         io.attn_mask = am.data_ptr() if am is not None else None
         io.attn_mask_p = amp.data_ptr() if amp is not None else None
+        io.key_lens = key_lens.data_ptr() if key_lens is not None else None
         io.times = times.data_ptr()
         if ada is not None:
             assert target is None and not self.training
@@ -477,7 +486,7 @@ class Engine:
             io.drop_mask = drop8.data_ptr() if drop8 is not None else None
             io.null_cond = null_cond.data_ptr()
             text = (ids, drop8, null_cond)
-        self._keep = (x, cond, cm, am, amp, lm, times, target, pred, text, ada)  # keep inputs alive until backward
+        self._keep = (x, cond, cm, am, amp, lm, times, target, pred, text, ada, key_lens)  # keep inputs alive until backward
         self.generation += 1
         self._draw_dropout_seed()
         _check(_rt().vbx_model_forward(C.byref(self.m), C.byref(io), _lib.current_stream()), "vbx_model_forward")
@@ -538,6 +547,7 @@ class Engine:
         io.cond_mask = io.times = io.target = io.loss_mask = io.loss = io.dx = io.dcond = None
         io.attn_mask = am.data_ptr() if am is not None else None
         io.attn_mask_p = amp.data_ptr() if amp is not None else None
+        io.key_lens = None
         io.pred = out.data_ptr()
         self._keep = (x, cond, am, amp, out)
         self.generation += 1

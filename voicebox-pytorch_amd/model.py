@@ -638,6 +638,7 @@ class ConditionalFlowMatcherWrapper(nn.Module):
         self.odeint_kwargs = dict(atol=ode_atol, rtol=ode_rtol, method=torchdiffeq_ode_method)  # atol/rtol: read by dopri5 only
         self._samplers = {}
         self.last_sample_stats = None  # {"method", "nfe", "accepted", "rejected"} of the last sample() call
+        self.last_sample_lens = None   # int64 CPU [B] after sample(lens=): frames per row (latents, codes) or samples per row (waves)
 
     @property
     def device(self):
@@ -653,12 +654,26 @@ class ConditionalFlowMatcherWrapper(nn.Module):
     @torch.inference_mode()
     def sample(self, *, cond=None, texts=None, text_token_ids=None, semantic_token_ids=None, phoneme_ids=None,
                cond_mask=None, steps=3, cond_scale=1., decode_to_audio=True, decode_to_codes=False,
-               max_semantic_token_ids=2048, spec_decode=False, spec_decode_gamma=5, use_graph=True):
+               max_semantic_token_ids=2048, spec_decode=False, spec_decode_gamma=5, use_graph=True, lens=None, length_bucket=None):
         """voicebox_pytorch.py:1175-1330 with torchdiffeq.odeint replaced by the built-in device solvers (solver.py), per
         torchdiffeq_ode_method: 'midpoint' (the default), 'euler' and 'rk4' on the fixed grid linspace(0, 1, steps) -- 2, 1 and 4
         function evaluations per interval -- or the adaptive 'dopri5' with ode_atol / ode_rtol (steps does not change its result).
-        Counts of the call: self.last_sample_stats."""
+        Counts of the call: self.last_sample_stats.
+
+        lens (not a reference keyword): a list or an int tensor [B], 1 <= len_b <= N -- row b of the padded batch has len_b real
+        frames and is integrated as if alone: frames past it are masked in every forward (self_attn_mask[b, n] = n < len_b), whatever
+        cond / cond_mask / the y0 draw hold there is ignored, and they come back as 0.0 in latents, -1 in codes, 0 in waves (row b
+        of a wave is codec.decode(latents[b:b+1, :len_b]), zero-filled to the longest).  self.last_sample_lens: the per-row output
+        lengths.  lens="durations" (phoneme_ids + duration_predictor): len_b is the sum of the predicted durations of row b's
+        phonemes, and -1 padding phonemes get no frames.  length_bucket (with lens): the sampler runs at N rounded up to a multiple
+        of it, the extra frames masked like any padding, so that calls whose N share a bucket share one sampler and one graph."""
         from .solver import make_sampler
+        from .sample_lens import bucketed, decode_rows, durations_lens, mask_codes, pad_frames, validate_lens
+
+        if exists(length_bucket) and not exists(lens):
+            raise ValueError("length_bucket needs lens: without lengths the frames added up to the bucket could not be masked")
+        if isinstance(lens, str) and (lens != "durations" or not exists(phoneme_ids) or not exists(self.duration_predictor)):
+            raise ValueError(f"lens={lens!r}: the only named source of lengths is 'durations', on the phoneme_ids + duration_predictor path")
 
         codec = self.voicebox.audio_enc_dec
         if is_probably_audio_from_shape(cond):  # :1192-1201
@@ -681,8 +696,12 @@ class ConditionalFlowMatcherWrapper(nn.Module):
                     raise NotImplementedError("phoneme_ids need a DurationPredictor (pass duration_predictor=) to be aligned to frames")
                 assert exists(cond), "the duration predictor is conditioned on cond (B, frames, dim)"
                 self.duration_predictor.eval()
-                _, cond_token_ids = self.duration_predictor.forward_with_cond_scale(
-                    cond=cond, phoneme_ids=phoneme_ids, return_aligned_phoneme_ids=True)
+                if isinstance(lens, str):  # the length regulator kernel: padding phonemes own no frames
+                    durations = self.duration_predictor.forward_with_cond_scale(cond=cond, phoneme_ids=phoneme_ids)
+                    cond_token_ids, lens = durations_lens(phoneme_ids.to(durations.device), durations)
+                else:
+                    _, cond_token_ids = self.duration_predictor.forward_with_cond_scale(
+                        cond=cond, phoneme_ids=phoneme_ids, return_aligned_phoneme_ids=True)
             target_len = cond_token_ids.shape[-1]
             if exists(cond):  # curtail_or_pad(cond, cond_target_length) (:109-119, :1253)
                 n = cond.shape[-2]
@@ -702,10 +721,18 @@ class ConditionalFlowMatcherWrapper(nn.Module):
         y0 = take_draw("y0")
         y0 = torch.randn_like(cond) if y0 is None else y0.to(dev, torch.float32)
         B, N, _ = cond.shape
+        masked, n_out = exists(lens), N
+        self.last_sample_lens = None
+        if masked:
+            lens = validate_lens(lens, B, N)  # the one host read of lens: int32 CPU [B]
+            assert not exists(cond_token_ids) or cond_token_ids.shape[-1] == N, "under lens there is one token id per frame"
+            N = bucketed(N, length_bucket)
+            if N != n_out:  # the frames up to the bucket are padding of every row; y0 was drawn at n_out, so a draw does not depend on them
+                cond, y0, cond_mask, cond_token_ids = pad_frames(N, cond, y0, cond_mask, cond_token_ids)
         T = cond_token_ids.shape[-1] if exists(cond_token_ids) else 0
         method, guided = self.odeint_kwargs["method"], float(cond_scale) != 1.
         atol, rtol = float(self.odeint_kwargs["atol"]), float(self.odeint_kwargs["rtol"])
-        key = (B, N, steps, bool(use_graph), T, guided, precise_enabled(), method) + ((atol, rtol) if method == "dopri5" else ())
+        key = (B, N, steps, bool(use_graph), T, guided, precise_enabled(), method, masked) + ((atol, rtol) if method == "dopri5" else ())
         fp = self.voicebox.flat_params()
         # a re-flatten (.to(), dtype change) frees the buffer whose addresses the cached hipGraphs captured: drop them
         self._samplers = {k: s for k, s in self._samplers.items() if s.flat_gen == fp.flat_gen and s.eng.fp is fp}
@@ -714,7 +741,17 @@ class ConditionalFlowMatcherWrapper(nn.Module):
             if len(self._samplers) >= 2:
                 self._samplers.pop(next(iter(self._samplers)))
             smp = self._samplers[key] = make_sampler(method, self.voicebox, B, N, steps, use_graph=use_graph, tokens=T, guided=guided,
-                                                     atol=atol, rtol=rtol)
+                                                     atol=atol, rtol=rtol, masked=masked)
+        if masked:
+            out = smp.run(y0, cond, cond_mask, cond_token_ids=cond_token_ids, cond_scale=float(cond_scale), lens=lens)[:, :n_out]
+            self.last_sample_stats = smp.stats()
+            self.last_sample_lens = lens.to(torch.int64)
+            if decode_to_codes and exists(codec):
+                return mask_codes(codec.decode_to_codes(out.contiguous()), lens)
+            if not decode_to_audio or not exists(codec):
+                return out.contiguous()
+            wave, self.last_sample_lens = decode_rows(codec, out, lens)
+            return wave
         out = smp.run(y0, cond, cond_mask, cond_token_ids=cond_token_ids, cond_scale=float(cond_scale))
         self.last_sample_stats = smp.stats()
         if decode_to_codes and exists(codec):  # :1324-1330

@@ -27,6 +27,14 @@ before the end, and the second stream starts SPLIT_OFFSET_US late, so that diffe
 joined branches of one graph 82.5, two free-running graphs 81.7, with the offset 80.1 (tools/sample_concurrent.py,
 tools/sample_offset.py); results bit-identical to the single-stream run.  VBX_SAMPLE_SPLIT=1 restores the single stream (A/B).
 Without a graph (use_graph=False) the halves run as fork / join branches per interval.
+
+Unequal lengths (masked=True, run(lens=)).  Row b of the padded batch has len_b real frames.  A masked sampler owns three more static
+buffers -- amask [B, N] bool (n < len_b), amask_p [B, R + N] uint8 (the same behind R ones: the copy Engine.forward would otherwise
+allocate per call, whose address a captured graph must keep) and key_lens [B] int32 = R + len_b -- sliced into the parts like the
+rest and refreshed by _load_inputs, which also writes "masked" / 0 into cond_mask / cond past the lengths and zeroes y0 there.  Every
+forward of _eval gets the mask (convolutional position embedding, attention) and the key lengths (vbx_attn_fwd_lens: dead key tiles
+are not walked); dopri5's error norm leaves the padding out (vbx_ode_norm_lens); the returned state is zeroed past the lengths.  The
+rows of padding frames still go through the GEMMs and norms.  An unmasked sampler passes none of this and launches what it always did.
 """
 import contextlib
 import ctypes as _C
@@ -37,6 +45,8 @@ import torch
 from . import _lib
 from .engine import precise_enabled
 
+
+ATTN_KEY_LENS = True  # read when a masked sampler is built.  False: the mask alone, every key tile walked (tools/sample_lens_times.py arm B)
 
 SPLIT_OFFSET_US = float(os.environ.get("VBX_SAMPLE_OFFSET_US", "60"))  # start delay of the second (third, ...) half-batch stream; 30 .. 250 us measured equal
 
@@ -62,8 +72,8 @@ class _Sampler:
     knows its time points up front: self.t_table, and the adaLN projections of all of them are tabulated (self.ada_tab, row
     ada_stride * counter + slot).  grid = None: every forward evaluates its own projections from p.times."""
 
-    def __init__(self, voicebox, B, N, use_graph=True, tokens=0, guided=False, split=None, grid=None):
-        self.vb, self.B, self.N = voicebox, B, N
+    def __init__(self, voicebox, B, N, use_graph=True, tokens=0, guided=False, split=None, grid=None, masked=False):
+        self.vb, self.B, self.N, self.masked = voicebox, B, N, bool(masked)
         if split is None:
             # Default: two concurrent half batches -- EXCEPT where the weight-stationary kernel serves to_qkv / FeedForward-in (dim 512,
             # csrc/gemm5.hip): it owns whole CUs, the half batches' launches cannot interleave with it, and ONE stream is then both
@@ -94,6 +104,13 @@ class _Sampler:
         self.cond = torch.zeros(B, N, D, device=dev)
         self.cmask = torch.ones(B, N, dtype=torch.bool, device=dev)
         self.times = torch.zeros(B, device=dev)
+        if self.masked:
+            R = voicebox._cfg["R"]
+            self.amask = torch.ones(B, N, dtype=torch.bool, device=dev)
+            self.amask_p = torch.ones(B, R + N, dtype=torch.uint8, device=dev)
+            self.lens = torch.full((B,), N, dtype=torch.int32, device=dev)
+            self.key_lens = torch.full((B,), R + N, dtype=torch.int32, device=dev) if ATTN_KEY_LENS else None
+            self.frames = torch.arange(N, device=dev)[None]
         self.counters = torch.zeros(split, dtype=torch.int32, device=dev)  # one per part (each branch advances its own)
         # text-conditioned models: static token ids; classifier-free guidance (forward_with_cond_scale, :972-985) runs a
         # second, fully dropped evaluation (cond -> null_cond, ids -> null_cond_id) and mixes null + (logits - null) * scale
@@ -113,6 +130,9 @@ class _Sampler:
             p.sl = sl = slice(i * Bp, (i + 1) * Bp)
             p.y, p.ymid, p.f, p.cond, p.cmask, p.times = self.y[sl], self.ymid[sl], self.f[sl], self.cond[sl], self.cmask[sl], self.times[sl]
             p.counter = self.counters[i:i + 1]
+            if self.masked:
+                p.mask_kw = dict(attn_mask=self.amask[sl], attn_mask_p=self.amask_p[sl],
+                                 key_lens=self.key_lens[sl] if self.key_lens is not None else None)
             if self.tokens:
                 p.ids, p.drop_all = self.ids[sl], self.drop_all[sl]
             if self.guided:
@@ -127,14 +147,28 @@ class _Sampler:
         self.graph = None
         self.use_graph = use_graph
 
-    def _load_inputs(self, cond, cond_mask, cond_token_ids, cond_scale):
+    def _zero_tail(self, x):
+        """x [B, N, D] fp32: frames at or past the lengths <- 0"""
+        _lib.call("vbx_zero_tail_rows", x, self.lens, self.B, self.N, x.shape[-1], _lib.current_stream())
+
+    def _load_inputs(self, cond, cond_mask, cond_token_ids, cond_scale, lens=None):
         # eval semantics of the reference: cond_mask None -> everything masked -> cond is zeroed (:1028-1035)
+        assert (lens is not None) == self.masked, "a masked sampler runs with lens, an unmasked one without"
         if cond is not None:
             self.cond.copy_(cond)
         if cond_mask is not None:
             self.cmask.copy_(cond_mask.to(self.cmask.device))
         else:
             self.cmask.fill_(True)
+        if self.masked:  # lens: host int32 [B], validated by the caller
+            R = self.vb._cfg["R"]
+            self.lens.copy_(lens, non_blocking=True)
+            torch.lt(self.frames, self.lens[:, None], out=self.amask)
+            self.amask_p[:, R:] = self.amask
+            if self.key_lens is not None:
+                torch.add(self.lens, R, out=self.key_lens)
+            self.cmask.logical_or_(~self.amask)  # past the length: "masked", and 0 in cond, whatever the caller left there
+            self._zero_tail(self.cond)
         if self.tokens:
             self.ids.copy_(cond_token_ids.to(self.ids.device))
         if self.guided:
@@ -156,15 +190,16 @@ class _Sampler:
         time is row ada_stride * counter + slot of the adaLN table, or without one whatever the caller left in p.times."""
         p.eng.dropout_active = False  # sampling is eval (:1268) whatever mode a later forward of the same shape left on the engine
         ada = (self.ada_tab, p.counter, slot, self.ada_stride) if self.ada_tab is not None else None
+        mk = p.mask_kw if self.masked else {}
         if not self.tokens:
-            p.eng.forward(x, p.cond, p.cmask, p.times, pred_out=out, ada=ada)
+            p.eng.forward(x, p.cond, p.cmask, p.times, pred_out=out, ada=ada, **mk)
             return
         vb = self.vb
-        p.eng.forward(x, p.cond, p.cmask, p.times, pred_out=out, text=(p.ids, vb.null_cond_id, None, vb.null_cond), ada=ada)
+        p.eng.forward(x, p.cond, p.cmask, p.times, pred_out=out, text=(p.ids, vb.null_cond_id, None, vb.null_cond), ada=ada, **mk)
         if self.guided:
             st, n = _lib.current_stream, out.numel()
             p.eng.forward(x, p.cond, p.cmask, p.times, pred_out=p.f_null,
-                          text=(p.ids, vb.null_cond_id, p.drop_all, vb.null_cond), ada=ada)
+                          text=(p.ids, vb.null_cond_id, p.drop_all, vb.null_cond), ada=ada, **mk)
             _lib.call("vbx_axpy_dev", out, p.f_null, self.g_table, 0, p.f_diff, n, st())   # logits - null
             _lib.call("vbx_axpy_dev", p.f_null, p.f_diff, self.g_table, 1, out, n, st())   # null + scale * diff
 
@@ -174,9 +209,10 @@ class _FixedGridSampler(_Sampler):
     coefficients [intervals * S, ...]), host fp32; the subclass's _interval_part(p) launches one interval of one part, reading row
     S * p.counter + slot of them, and advances the counter."""
 
-    def __init__(self, voicebox, B, N, steps, method, tables, use_graph=True, tokens=0, guided=False, split=None):
+    def __init__(self, voicebox, B, N, steps, method, tables, use_graph=True, tokens=0, guided=False, split=None, masked=False):
         S = tables[0].numel() // (steps - 1)
-        super().__init__(voicebox, B, N, use_graph=use_graph, tokens=tokens, guided=guided, split=split, grid=(tables[0], S))
+        super().__init__(voicebox, B, N, use_graph=use_graph, tokens=tokens, guided=guided, split=split, grid=(tables[0], S),
+                         masked=masked)
         self.method, self.steps, self.S = method, steps, S
         dev = self.y.device
         self.c_table = tables[1].to(dev)
@@ -255,11 +291,13 @@ class _FixedGridSampler(_Sampler):
         for s in self.part_streams:
             cur.wait_stream(s)
 
-    def run(self, y0, cond=None, cond_mask=None, cond_token_ids=None, cond_scale=1.0):
-        self._load_inputs(cond, cond_mask, cond_token_ids, cond_scale)
+    def run(self, y0, cond=None, cond_mask=None, cond_token_ids=None, cond_scale=1.0, lens=None):
+        self._load_inputs(cond, cond_mask, cond_token_ids, cond_scale, lens)
         if self.use_graph and self.graph is None:
             self._capture()
         self.y.copy_(y0)
+        if self.masked:
+            self._zero_tail(self.y)
         self.counters.zero_()
         if self.use_graph and self.split > 1:
             self._replay_parts()
@@ -270,7 +308,10 @@ class _FixedGridSampler(_Sampler):
                 else:
                     with self._cu_share():
                         self._interval()
-        return self.y.clone()
+        out = self.y.clone()
+        if self.masked:
+            self._zero_tail(out)
+        return out
 
     def stats(self):
         return {"method": self.method, "nfe": self.nfe, "accepted": self.steps - 1, "rejected": 0}
@@ -290,9 +331,9 @@ def midpoint_tables(steps):
 class MidpointSampler(_FixedGridSampler):
     """torchdiffeq's fixed-grid midpoint.  Its own step on vbx_axpy_ctr (fused y + f * a), not a tableau: see the module docstring."""
 
-    def __init__(self, voicebox, B, N, steps, use_graph=True, tokens=0, guided=False, split=None):
+    def __init__(self, voicebox, B, N, steps, use_graph=True, tokens=0, guided=False, split=None, masked=False):
         super().__init__(voicebox, B, N, steps, "midpoint", midpoint_tables(steps), use_graph=use_graph, tokens=tokens, guided=guided,
-                         split=split)
+                         split=split, masked=masked)
 
     def _interval_part(self, p):
         st = _lib.current_stream
@@ -346,11 +387,11 @@ class RKSampler(_FixedGridSampler):
     dt * a_ij, dt * b_j are formed on the host in fp32 torch arithmetic (fixed_grid_tables) and live in device tables
     [intervals * S] / [intervals * S][S] indexed by the part's device counter; the adaLN table holds every STAGE time."""
 
-    def __init__(self, voicebox, B, N, steps, method, use_graph=True, tokens=0, guided=False, split=None):
+    def __init__(self, voicebox, B, N, steps, method, use_graph=True, tokens=0, guided=False, split=None, masked=False):
         if method not in FIXED_TABLEAUS:
             raise ValueError(f"RKSampler: no fixed-grid tableau {method!r} (have {sorted(FIXED_TABLEAUS)})")
         super().__init__(voicebox, B, N, steps, method, fixed_grid_tables(method, steps), use_graph=use_graph, tokens=tokens,
-                         guided=guided, split=split)
+                         guided=guided, split=split, masked=masked)
         self.ks = [self.f] + [torch.zeros_like(self.y) for _ in range(self.S - 1)]  # stage derivatives; the stage inputs go to ymid
         for p in self.parts:
             p.k = [k[p.sl] for k in self.ks]
@@ -404,8 +445,9 @@ class Dopri5Sampler(_Sampler):
     `steps` does not change the result (only the final time point is returned) and is not kept; with no grid, t_table and
     ada_stride are None and _eval passes ada=None."""
 
-    def __init__(self, voicebox, B, N, steps, use_graph=True, tokens=0, guided=False, atol=1e-5, rtol=1e-5, max_attempts=10000):
-        super().__init__(voicebox, B, N, use_graph=use_graph, tokens=tokens, guided=guided, split=1, grid=None)
+    def __init__(self, voicebox, B, N, steps, use_graph=True, tokens=0, guided=False, atol=1e-5, rtol=1e-5, max_attempts=10000,
+                 masked=False):
+        super().__init__(voicebox, B, N, use_graph=use_graph, tokens=tokens, guided=guided, split=1, grid=None, masked=masked)
         self.atol, self.rtol, self.max_attempts = float(atol), float(rtol), int(max_attempts)
         dev = self.y.device
         self.ks = [self.f] + [torch.zeros_like(self.y) for _ in range(6)]  # k1 .. k7
@@ -416,6 +458,15 @@ class Dopri5Sampler(_Sampler):
         self.mult = 2 if self.guided else 1
         self.last_stats = self.nfe = None  # counted on the device: known after a run
 
+    def _norm(self, mode, y1, ks, c, S):
+        """the RMS norm + controller over the whole state, or under lens over the real frames only"""
+        n, st = self.y.numel(), _lib.current_stream()
+        if self.masked:
+            _lib.call("vbx_ode_norm_lens", self.state, self.slab, mode, self.y, y1, _ptrs(ks), c, S, n, self.mult, self.lens, self.B,
+                      self.y.shape[-1], st)
+        else:
+            _lib.call("vbx_ode_norm", self.state, self.slab, mode, self.y, y1, _ptrs(ks), c, S, n, self.mult, st)
+
     def _attempt(self):
         p, st, n = self.parts[0], _lib.current_stream, self.y.numel()
         for i in range(6):
@@ -424,8 +475,7 @@ class Dopri5Sampler(_Sampler):
             mode = TIME_END if DP_ALPHA[i] == 1.0 else TIME_STAGE
             _lib.call("vbx_ode_stage_time_dp", p.times, self.B, self.state, DP_ALPHA[i], mode, st())
             self._eval(p, x, self.ks[i + 1])
-        _lib.call("vbx_ode_norm", self.state, self.slab, NORM_ERROR, self.y, self.y1, _ptrs(self.ks), _floats(DP_C_ERROR), 7, n,
-                  self.mult, st())
+        self._norm(NORM_ERROR, self.y1, self.ks, _floats(DP_C_ERROR), 7)
         _lib.call("vbx_ode_commit", self.y, self.ks[0], self.y1, self.ks[6], self.state, n, st())
 
     def _initial(self):
@@ -436,11 +486,11 @@ class Dopri5Sampler(_Sampler):
         self.state.copy_(init)
         p.times.fill_(0.0)
         self._eval(p, self.y, self.ks[0])
-        _lib.call("vbx_ode_norm", self.state, self.slab, NORM_INIT0, self.y, None, _ptrs(self.ks[:1]), None, 1, n, self.mult, st())
+        self._norm(NORM_INIT0, None, self.ks[:1], None, 1)
         _lib.call("vbx_ode_combine_dp", self.ymid, self.y, _ptrs(self.ks[:1]), _floats([1.0]), 1, self.state, DP_H0, n, st())
         _lib.call("vbx_ode_stage_time_dp", p.times, self.B, self.state, 0.0, TIME_PROBE, st())
         self._eval(p, self.ymid, self.ks[1])
-        _lib.call("vbx_ode_norm", self.state, self.slab, NORM_INIT1, self.y, None, _ptrs(self.ks[:2]), None, 2, n, self.mult, st())
+        self._norm(NORM_INIT1, None, self.ks[:2], None, 2)
 
     def _capture(self):
         g = torch.cuda.CUDAGraph()
@@ -448,9 +498,11 @@ class Dopri5Sampler(_Sampler):
             self._attempt()
         self.graph = g
 
-    def run(self, y0, cond=None, cond_mask=None, cond_token_ids=None, cond_scale=1.0):
-        self._load_inputs(cond, cond_mask, cond_token_ids, cond_scale)
+    def run(self, y0, cond=None, cond_mask=None, cond_token_ids=None, cond_scale=1.0, lens=None):
+        self._load_inputs(cond, cond_mask, cond_token_ids, cond_scale, lens)
         self.y.copy_(y0)
+        if self.masked:
+            self._zero_tail(self.y)
         self._initial()
         attempts = 0
         while True:
@@ -475,15 +527,18 @@ class Dopri5Sampler(_Sampler):
                   _lib.current_stream())
         self.last_stats = {"method": "dopri5", "nfe": int(s[DP_NFE]), "accepted": int(s[DP_ACCEPTED]), "rejected": int(s[DP_REJECTED])}
         self.nfe = self.last_stats["nfe"]
-        return self.out.clone()
+        out = self.out.clone()
+        if self.masked:
+            self._zero_tail(out)
+        return out
 
     def stats(self):
         return dict(self.last_stats)
 
 
-def make_sampler(method, voicebox, B, N, steps, *, use_graph=True, tokens=0, guided=False, atol=1e-5, rtol=1e-5):
-    """The sampler of a torchdiffeq method name (atol / rtol: read by dopri5 only)."""
-    kw = dict(use_graph=use_graph, tokens=tokens, guided=guided)
+def make_sampler(method, voicebox, B, N, steps, *, use_graph=True, tokens=0, guided=False, atol=1e-5, rtol=1e-5, masked=False):
+    """The sampler of a torchdiffeq method name (atol / rtol: read by dopri5 only; masked: it runs with lens)."""
+    kw = dict(use_graph=use_graph, tokens=tokens, guided=guided, masked=masked)
     if method == "midpoint":
         return MidpointSampler(voicebox, B, N, steps, **kw)
     if method == "dopri5":
