@@ -528,6 +528,24 @@ int vbx_pack_phoneme_input(const long* ids, const float* table, int E, const flo
 int vbx_pack_phoneme_input_train(const long* ids, const float* table, int E, const float* cond, int S, const uint8_t* cond_mask,
                                  const uint8_t* drop_mask, const float* null_cond, void* out_f16, void* out_bf16, float* emb_f32, int B,
                                  int N, int D, void* stream);
+/* The same operand for a DurationPredictor over codec latents (attach_codec(); csrc/duration.hip): latent fp32 [B, S, L] goes
+ * through proj_in inside the launch,
+ *   cond''[b, r] = r >= S ? 0 : drop[b] ? null_cond : cond_mask[b, r] ? 0 : latent[b, r] . W^T + bias      (voicebox_pytorch.py:776-819)
+ * -- proj_in at length S, then the mask (a masked row is 0, not the bias), then the drop, then curtail_or_pad to N.  Columns 0:E are
+ * the bits vbx_pack_phoneme_input writes.  The product has vbx_proj_in_embed's arithmetic: latents and W rounded once to fp16
+ * (saturating), w_f16 = W packed [D, Kp], Kp = vbx_proj_in_kp(L), zero past column L (vbx_pack_weight); fp32 sums in ascending k on
+ * v_mfma_f32_16x16x32_f16, bias (fp32 [D]) added in fp32, one rounding to fp16 on store: per element within
+ * (L + 2) 2^-24 (sum |w x| + |b|) + 2^-11 |y| of the exact value on the rounded operands.  L in 8 .. 1024, D a multiple of 64, E of 8.
+ * _train writes in the same launch out_bf16 [B*N, E+D] and emb_f32 [B*N, E] (may be NULL) as vbx_pack_phoneme_input_train does, and
+ * lc_bf16 [B*N, Kp], the operand of proj_in's weight gradient: the latent row with column L = 1, ALL zero on the rows that pass no
+ * gradient to proj_in (r >= S, cond_mask set, dropped sample), zero past column L: (d cond'')^T . lc = [ d weight | d bias ], which
+ * vbx_proj_in_wgrad_reduce splits.  One launch, no atomics: reruns are bit-identical, and a batch row gives the same bits alone. */
+int vbx_pack_phoneme_latent(const long* ids, const float* table, int E, const float* latent, int S, int L, const void* w_f16,
+                            const float* bias, const uint8_t* cond_mask, const uint8_t* drop_mask, const float* null_cond, void* out_f16,
+                            int B, int N, int D, void* stream);
+int vbx_pack_phoneme_latent_train(const long* ids, const float* table, int E, const float* latent, int S, int L, const void* w_f16,
+                                  const float* bias, const uint8_t* cond_mask, const uint8_t* drop_mask, const float* null_cond,
+                                  void* out_f16, void* out_bf16, float* emb_f32, void* lc_bf16, int B, int N, int D, void* stream);
 /* ------------------------------------------------------------------ DurationPredictor training (csrc/duration.hip)
  * The loss of voicebox_pytorch.py:858-866 taken on the PREDICTED durations (the reference writes it on the hidden state, which only
  * broadcasts at degenerate shapes).  All of it fp32, no atomics; every sum runs in an order fixed by the shapes alone, so reruns are

@@ -104,6 +104,8 @@ _PROTOS = {
     "vbx_resample": [P, P, P, P, P, I, L, L, I, I, I, I, I, P],
     "vbx_pack_phoneme_input": [P, P, I, P, I, P, P, P, P, I, I, I, P],
     "vbx_pack_phoneme_input_train": [P, P, I, P, I, P, P, P, P, P, P, I, I, I, P],
+    "vbx_pack_phoneme_latent": [P, P, I, P, I, I, P, P, P, P, P, P, I, I, I, P],
+    "vbx_pack_phoneme_latent_train": [P, P, I, P, I, I, P, P, P, P, P, P, P, P, P, I, I, I, P],
     "vbx_rowdot": [P, P, P, P, L, I, P],
     "vbx_attn_delta_consistent": [P, P, P, P, P, P, P, I, I, I, P],
     "vbx_duration_head_fwd": [P, P, P, P, P, P, P, P, P, I, I, I, P],

@@ -208,6 +208,117 @@ __global__ __launch_bounds__(LR_THREADS) void length_regulate_kernel(const long*
   for (long j = total + tid; j < Nmax; j += LR_THREADS) out[j] = 0;
 }
 
+// ---- DurationPredictor front end over codec latents (attach_codec(), voicebox_pytorch.py:776, :793-823): one launch writes the
+// to_embed operand [B n, E + D] = [ to_phoneme_emb(max(ids, 0)) | cond'' ],
+//   cond''[b, r] = r >= S ? 0 : drop[b] ? null_cond : cmask[b, r] ? 0 : latent[b, r] . W^T + bias
+// -- proj_in at length S, then the mask (a masked row is 0, not the bias), then the drop, then curtail_or_pad to n.  The product has
+// the arithmetic of proj_in_embed_kernel (codec.hip): operands rounded once to fp16 (saturating), W pre-packed [D, Kp], fp32 sums
+// on v_mfma_f32_16x16x32_f16 in ascending k, computed transposed (C^T[d][row] = sum_k W[d][k] X[row][k]) so that a lane holds four
+// consecutive output columns of one row; bias added in fp32; one rounding on store.  A workgroup owns 32 rows x 64 columns (16 per
+// wave); the workgroups of column block 0 also gather the embedding columns and write lcb.
+// lcb (training) bf16 [B n, Kp]: the operand of the weight gradient -- the latent row with column L = 1 on the rows that pass a
+// gradient to proj_in, all zero on the others (r >= S, cond_mask set, dropped sample), so d cond''^T . lcb = [ d weight | d bias ].
+constexpr int PL_TM = 32;           // rows per workgroup
+constexpr int PL_TN = 64;           // output columns per workgroup
+constexpr int PL_KC = 128;          // K chunk staged in the LDS
+constexpr int PL_LD = PL_KC + 8;    // row stride 272 bytes: consecutive rows start 4 banks apart
+
+VBX_DEV uint4 pl_pack8_h(const float v[8]) {
+  return make_uint4(pack_f16x2_sat(v[0], v[1]), pack_f16x2_sat(v[2], v[3]), pack_f16x2_sat(v[4], v[5]), pack_f16x2_sat(v[6], v[7]));
+}
+VBX_DEV uint4 pl_pack8_b(const float v[8]) {
+  return make_uint4(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]), pack_bf16x2(v[6], v[7]));
+}
+
+__global__ __launch_bounds__(256) void pack_phoneme_latent_kernel(const long* __restrict__ ids, const float* __restrict__ table, int E,
+                                                                  const float* __restrict__ latent, int S, int L, int Kp,
+                                                                  const u16* __restrict__ wh, const float* __restrict__ bias,
+                                                                  const uint8_t* __restrict__ cmask, const uint8_t* __restrict__ drop,
+                                                                  const float* __restrict__ null_cond, u16* __restrict__ out,
+                                                                  u16* __restrict__ outb, float* __restrict__ emb32,
+                                                                  u16* __restrict__ lcb, long M, int N, int D) {
+  __shared__ __attribute__((aligned(16))) u16 sA[PL_TM * PL_LD];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const long m0 = (long)blockIdx.x * PL_TM;
+  const int n0 = blockIdx.y * PL_TN + wave * 16;
+  const int ld = E + D;
+
+  if (blockIdx.y == 0) {  // columns 0:E, pack_phoneme_kernel's gather (ops.hip): the same bits
+    const int ce = E / 8;
+    for (int i = tid; i < PL_TM * ce; i += 256) {
+      const int r = i / ce, c = i - r * ce;
+      const long row = m0 + r;
+      if (row >= M) continue;
+      long id = ids[row];
+      id = id < 0 ? 0 : id;  // -1 = padding, clamped (:811)
+      const float* src = table + id * E + c * 8;
+      float v[8];
+#pragma unroll
+      for (int k = 0; k < 8; k++) v[k] = src[k];
+      *reinterpret_cast<uint4*>(out + row * ld + c * 8) = pl_pack8_h(v);
+      if (outb) *reinterpret_cast<uint4*>(outb + row * ld + c * 8) = pl_pack8_b(v);
+      if (emb32) {
+        *reinterpret_cast<float4*>(emb32 + row * E + c * 8) = make_float4(v[0], v[1], v[2], v[3]);
+        *reinterpret_cast<float4*>(emb32 + row * E + c * 8 + 4) = make_float4(v[4], v[5], v[6], v[7]);
+      }
+    }
+  }
+
+  f32x4 acc[2];
+  acc[0] = f32x4{0.f, 0.f, 0.f, 0.f};
+  acc[1] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int k0 = 0; k0 < Kp; k0 += PL_KC) {
+    const int kc = (Kp - k0) < PL_KC ? (Kp - k0) : PL_KC;  // multiple of 32
+    if (k0) __syncthreads();
+    for (int i = tid; i < PL_TM * PL_KC; i += 256) {
+      const int r = i / PL_KC, c = i - r * PL_KC;
+      if (c >= kc) continue;
+      const long row = m0 + r;
+      const int k = k0 + c;
+      const int b = (int)(row / N), pos = (int)(row - (long)b * N);
+      const bool in = row < M && pos < S;  // curtail_or_pad: rows past S hold no latent
+      const long crow = (long)b * S + pos;
+      float v = 0.f;
+      if (in && k < L) v = latent[crow * L + k];
+      sA[r * PL_LD + c] = f32_to_f16_sat(v);
+      if (lcb && blockIdx.y == 0 && row < M) {
+        const bool keep = in && !(drop && drop[b]) && !(cmask && cmask[crow]);
+        lcb[row * Kp + k] = f32_to_bf16(keep ? (k == L ? 1.0f : v) : 0.f);
+      }
+    }
+    __syncthreads();
+    for (int kk = 0; kk < kc; kk += 32) {
+      const f16x8 a = *reinterpret_cast<const f16x8*>(wh + (long)(n0 + (lane & 15)) * Kp + k0 + kk + (lane >> 4) * 8);
+#pragma unroll
+      for (int t = 0; t < 2; t++) {
+        const f16x8 bfr = *reinterpret_cast<const f16x8*>(sA + (t * 16 + (lane & 15)) * PL_LD + kk + (lane >> 4) * 8);
+        acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, bfr, acc[t], 0, 0, 0);
+      }
+    }
+  }
+  // epilogue: lane holds columns n0 + (lane >> 4) * 4 + 0..3 of row t * 16 + (lane & 15)
+  const int nc = n0 + (lane >> 4) * 4;
+  const float4 bv = *reinterpret_cast<const float4*>(bias + nc);
+#pragma unroll
+  for (int t = 0; t < 2; t++) {
+    const long row = m0 + t * 16 + (lane & 15);
+    if (row >= M) continue;
+    const int b = (int)(row / N), pos = (int)(row - (long)b * N);
+    float v0 = acc[t][0] + bv.x, v1 = acc[t][1] + bv.y, v2 = acc[t][2] + bv.z, v3 = acc[t][3] + bv.w;
+    if (pos >= S) {
+      v0 = v1 = v2 = v3 = 0.f;
+    } else if (drop && drop[b]) {
+      const float4 nv = *reinterpret_cast<const float4*>(null_cond + nc);
+      v0 = nv.x; v1 = nv.y; v2 = nv.z; v3 = nv.w;
+    } else if (cmask && cmask[(long)b * S + pos]) {
+      v0 = v1 = v2 = v3 = 0.f;
+    }
+    const long oo = row * ld + E + nc;
+    *reinterpret_cast<uint2*>(out + oo) = make_uint2(pack_f16x2_sat(v0, v1), pack_f16x2_sat(v2, v3));
+    if (outb) *reinterpret_cast<uint2*>(outb + oo) = make_uint2(pack_bf16x2(v0, v1), pack_bf16x2(v2, v3));
+  }
+}
+
 }  // namespace
 
 #define ST ((hipStream_t)stream)
@@ -258,4 +369,38 @@ extern "C" int vbx_length_regulate(const long* ids, const float* durations, long
   hipLaunchKernelGGL(length_regulate_kernel, dim3(B), dim3(LR_THREADS), 0, ST, ids, durations, aligned, lens, K, aligned ? Nmax : 0);
   VBX_LAUNCH_CHECK();
   return 0;
+}
+
+static int pack_phoneme_latent(const char* who, const long* ids, const float* table, int E, const float* latent, int S, int L,
+                               const void* w_f16, const float* bias, const uint8_t* cond_mask, const uint8_t* drop_mask,
+                               const float* null_cond, void* out_f16, void* out_bf16, float* emb_f32, void* lc_bf16, int B, int N, int D,
+                               void* stream) {
+  VBX_REQUIRE(ids && table && latent && w_f16 && bias && out_f16 && B > 0 && N > 0 && S > 0 && (long)B * N < (1L << 31) &&
+                  (long)B * S < (1L << 31),
+              "%s: bad args", who);
+  VBX_REQUIRE(L >= 8 && L <= 1024 && D > 0 && D % PL_TN == 0 && E > 0 && E % 8 == 0,
+              "%s: latent_dim must be in 8 .. 1024, dim a multiple of 64, dim_phoneme_emb a multiple of 8 (got %d, %d, %d)", who, L, D, E);
+  VBX_REQUIRE(!drop_mask || null_cond, "%s: a drop mask needs null_cond", who);
+  const long M = (long)B * N;
+  hipLaunchKernelGGL(pack_phoneme_latent_kernel, dim3((unsigned)cdiv(M, PL_TM), D / PL_TN), dim3(256), 0, ST, ids, table, E, latent, S, L,
+                     vbx_proj_in_kp(L), (const u16*)w_f16, bias, cond_mask, drop_mask, null_cond, (u16*)out_f16, (u16*)out_bf16, emb_f32,
+                     (u16*)lc_bf16, M, N, D);
+  VBX_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int vbx_pack_phoneme_latent(const long* ids, const float* table, int E, const float* latent, int S, int L, const void* w_f16,
+                                       const float* bias, const uint8_t* cond_mask, const uint8_t* drop_mask, const float* null_cond,
+                                       void* out_f16, int B, int N, int D, void* stream) {
+  return pack_phoneme_latent("vbx_pack_phoneme_latent", ids, table, E, latent, S, L, w_f16, bias, cond_mask, drop_mask, null_cond, out_f16,
+                             nullptr, nullptr, nullptr, B, N, D, stream);
+}
+
+extern "C" int vbx_pack_phoneme_latent_train(const long* ids, const float* table, int E, const float* latent, int S, int L,
+                                             const void* w_f16, const float* bias, const uint8_t* cond_mask, const uint8_t* drop_mask,
+                                             const float* null_cond, void* out_f16, void* out_bf16, float* emb_f32, void* lc_bf16, int B,
+                                             int N, int D, void* stream) {
+  VBX_REQUIRE(out_bf16 && lc_bf16, "vbx_pack_phoneme_latent_train: null pointer");
+  return pack_phoneme_latent("vbx_pack_phoneme_latent_train", ids, table, E, latent, S, L, w_f16, bias, cond_mask, drop_mask, null_cond,
+                             out_f16, out_bf16, emb_f32, lc_bf16, B, N, D, stream);
 }

@@ -31,7 +31,21 @@ _StackFn, _HeadFn (to_pred + loss: csrc/duration.hip).  No host synchronisation 
 gives the same bits, the table gradient included.  ff_dropout / attn_dropout are live in train().  The activation arena of the
 stand-alone Transformer holds ONE training forward per (B, n): run backward before the next training forward of the same shape.
 
-Not built: `tokenizer` / `texts` (espeak phonemizer, third-party) and `audio_enc_dec` (codecs are out of scope): pass `phoneme_ids`.
+Not built: `tokenizer` / `texts` (espeak phonemizer, third-party): pass `phoneme_ids`.
+
+Codec latents (the reference's DurationPredictor(audio_enc_dec=codec), :627-630, :776).  The constructor keyword `audio_enc_dec` still
+raises NotImplementedError -- two tests from before this path existed pin that -- and `attach_codec(codec)` serves it instead, as
+attach_aligner() serves the aligner.  It checks the codec's members as VoiceBox does, sets `self.audio_enc_dec` (a submodule, as in
+VoiceBox) and, when codec.latent_dim != dim, replaces `proj_in` by a trainable nn.Linear(latent_dim, dim) (state-dict keys
+`proj_in.weight [dim, latent_dim]`, `proj_in.bias [dim]`, the reference's).  From then on `cond` is fp32 [B, S, latent_dim] -- latents;
+as in the reference, forward never encodes audio, the wrapper does.  proj_in is applied FIRST (:776): the mask follows it, so a masked
+row is 0 and not the bias; then the guidance drop; then curtail_or_pad, so rows past S are 0 even for a dropped sample.  One kernel
+does all of it and the embedding gather: vbx_pack_phoneme_latent (csrc/duration.hip; fp16 operands, fp32 MFMA sums, the arithmetic of
+vbx_proj_in_embed), fed by an fp16 pack of proj_in.weight that is cached per parameter version.  In train() the same launch writes the
+bf16 operand `lcb` of the weight gradient (the latent row with a 1 in column latent_dim, zero on rows that pass no gradient), and
+_FrontEndFn's backward adds three launches: d cond'' = de . W_embed[:, E:] (bf16), the split-K product d cond''^T . lcb, and
+vbx_proj_in_wgrad_reduce, which splits it into d proj_in.weight and d proj_in.bias.  With latent_dim == dim proj_in stays nn.Identity()
+and every path is the one without a codec, bit for bit.  No gradient reaches `cond`.
 
 The aligner (align.py: `Aligner`, `maximum_path`, `ForwardSumLoss`) is optional.  By default `self.aligner` is None, `aligner.*`
 entries of a reference checkpoint are skipped on load and `state_dict()` has no such keys.  `attach_aligner()` builds
@@ -46,6 +60,7 @@ import torch
 from torch import nn
 
 from . import _lib
+from ._packing import tensors_key
 from .align import Aligner, forward_sum_loss, maximum_path
 from .masks import mask_from_frac_lengths, prob_mask_like, take_draw
 from .model import ConvPositionEmbed, Transformer, exists
@@ -69,7 +84,8 @@ class DurationPredictor(nn.Module):
                  frac_lengths_mask=(0.1, 1.), aligner_kwargs: dict = dict(dim_in=80, attn_channels=80)):
         super().__init__()
         if exists(audio_enc_dec):
-            raise NotImplementedError("audio codecs are out of the hot path's scope: feed latents")
+            raise NotImplementedError("DurationPredictor(audio_enc_dec=...) is not served by the constructor: build the predictor "
+                                      "without it and call attach_codec(codec), then feed latents [B, S, codec.latent_dim]")
         assert not (exists(tokenizer) and exists(num_phoneme_tokens)), \
             'if a phoneme tokenizer was passed into duration module, number of phoneme tokens does not need to be specified'
         if exists(tokenizer) or not exists(num_phoneme_tokens):
@@ -95,6 +111,7 @@ class DurationPredictor(nn.Module):
         self.aligner_kwargs = dict(aligner_kwargs)
         self.aligner = None  # attach_aligner(): Aligner(dim_hidden=dim_phoneme_emb, **aligner_kwargs)
         self.align_loss = None
+        self._proj_pack = (None, None)  # (key of proj_in.weight, its fp16 pack [dim, Kp])
 
     @property
     def device(self):
@@ -118,6 +135,44 @@ class DurationPredictor(nn.Module):
                              f"({self.dim_phoneme_emb})")
         self.aligner = aligner
         return aligner
+
+    def attach_codec(self, codec):
+        """Gives this module its audio codec (the reference's constructor keyword audio_enc_dec, :627-630): any nn.Module with
+        encode / decode / latent_dim / sampling_rate / downsample_factor, the check VoiceBox makes.  With codec.latent_dim != dim,
+        proj_in becomes a trainable nn.Linear(latent_dim, dim) (torch's default initialisation, on the device of the parameters) and
+        `cond` is from then on fp32 [B, S, latent_dim]; with latent_dim == dim nothing else changes.  Returns self."""
+        missing = [n for n in ("encode", "decode", "latent_dim", "sampling_rate", "downsample_factor") if not hasattr(codec, n)]
+        if not isinstance(codec, nn.Module) or missing:
+            raise TypeError(f"attach_codec takes an nn.Module with encode / decode / latent_dim / sampling_rate / downsample_factor "
+                            f"(missing: {missing})")
+        latent_dim = int(codec.latent_dim)
+        if latent_dim != self.dim and not 8 <= latent_dim <= 1024:
+            raise NotImplementedError(f"attach_codec: codec.latent_dim must be dim ({self.dim}) or in 8 .. 1024 (got {latent_dim})")
+        if exists(self.audio_enc_dec) and latent_dim != self.latent_dim:
+            raise ValueError(f"attach_codec: a codec of latent width {self.latent_dim} is attached already; one of width {latent_dim} "
+                             "would change proj_in's shape")
+        if latent_dim != self.dim and not isinstance(self.proj_in, nn.Linear):
+            self.proj_in = nn.Linear(latent_dim, self.dim).to(self.device)
+        self.audio_enc_dec = codec
+        return self
+
+    @property
+    def latent_dim(self):
+        """width of `cond`: the attached codec's latent_dim, or dim"""
+        return self.proj_in.in_features if isinstance(self.proj_in, nn.Linear) else self.dim
+
+    def _proj_operands(self):
+        """(fp16 pack of proj_in.weight [dim, Kp], zero past column latent_dim; bias fp32 [dim]) -- the pack is rebuilt when the
+        weight's storage or version counter moved (optimizer step, load_state_dict, .to())"""
+        w = self.proj_in.weight
+        key = tensors_key((w,))
+        if key != self._proj_pack[0]:
+            L, D = self.latent_dim, self.dim
+            Kp = _lib.lib().vbx_proj_in_kp(L)
+            pack = torch.empty(D, Kp, dtype=torch.float16, device=w.device)
+            _lib.call("vbx_pack_weight", w.detach().float().contiguous(), D, L, None, pack, D, Kp, 0, 0, _lib.current_stream())
+            self._proj_pack = (key, pack)
+        return self._proj_pack[1], self.proj_in.bias.detach().float().contiguous()
 
     def _need_aligner(self, who):
         if self.aligner is None:
@@ -174,7 +229,10 @@ class DurationPredictor(nn.Module):
         dev = self.device
         cond = cond.detach().to(dev, torch.float32).contiguous()
         batch, seq_len, cond_dim = cond.shape
-        assert cond_dim == self.dim
+        assert cond_dim == self.latent_dim, \
+            (f"cond has width {cond_dim}, this DurationPredictor takes {self.latent_dim}" +
+             (" (the attached codec's latent_dim)" if exists(self.audio_enc_dec) else
+              f" (dim): for codec latents of another width call attach_codec(codec) first"))
         ids = phoneme_ids.to(dev, torch.long).contiguous()
         assert ids.ndim == 2 and ids.shape[0] == batch
         if not exists(cond_mask):  # :786-791
@@ -219,8 +277,13 @@ class DurationPredictor(nn.Module):
             E, D = self.dim_phoneme_emb, self.dim
             st = _lib.current_stream()
             packed = torch.empty(batch * n, E + D, dtype=torch.float16, device=dev)
-            _lib.call("vbx_pack_phoneme_input", ids, self.to_phoneme_emb.weight.detach().float().contiguous(), E, cond, seq_len,
-                      cmask, drop, self.null_cond.detach().float().contiguous(), packed, batch, n, D, st)
+            table, null = self.to_phoneme_emb.weight.detach().float().contiguous(), self.null_cond.detach().float().contiguous()
+            if isinstance(self.proj_in, nn.Linear):  # :776 + :793-823 in one launch
+                pw16, pb = self._proj_operands()
+                _lib.call("vbx_pack_phoneme_latent", ids, table, E, cond, seq_len, self.latent_dim, pw16, pb, cmask, drop, null, packed,
+                          batch, n, D, st)
+            else:
+                _lib.call("vbx_pack_phoneme_input", ids, table, E, cond, seq_len, cmask, drop, null, packed, batch, n, D, st)
             w16 = self.to_embed.weight.detach().to(torch.float16).contiguous()
             bias = self.to_embed.bias.detach().float().contiguous()
             e = torch.empty(batch * n, D, dtype=torch.float32, device=dev)
@@ -251,7 +314,7 @@ class DurationPredictor(nn.Module):
         if use_aligner:
             self._need_aligner("forward (training on the aligner's durations)")
         if cond.ndim != 3 or phoneme_ids.ndim != 2 or cond.shape[1] != phoneme_ids.shape[-1]:
-            raise ValueError("DurationPredictor training: cond [B, n, dim] must have the length of phoneme_ids [B, n] (got "
+            raise ValueError("DurationPredictor training: cond [B, n, dim or latent_dim] must have the length of phoneme_ids [B, n] (got "
                              f"{tuple(cond.shape)} and {tuple(phoneme_ids.shape)}): the loss mask is cond_mask & self_attn_mask")
         if cond.requires_grad:
             raise NotImplementedError("DurationPredictor training passes no gradient to cond: detach it")
@@ -262,8 +325,9 @@ class DurationPredictor(nn.Module):
         cond, ids, cond_mask, cmask, drop, amask, am8 = self._resolve(cond, phoneme_ids, cond_mask, cond_drop_prob, self_attn_mask)
         batch, n = ids.shape
         conv, pred = self.conv_embed.dw_conv1d[0], self.to_pred[0]
+        proj = (self.proj_in.weight, self.proj_in.bias) if isinstance(self.proj_in, nn.Linear) else ()
         x, emb = _FrontEndFn.apply(self, ids, cond, cmask, drop, am8, use_aligner, self.to_phoneme_emb.weight, self.to_embed.weight,
-                                   self.to_embed.bias, conv.weight, conv.bias)
+                                   self.to_embed.bias, conv.weight, conv.bias, *proj)
         hid = self.transformer(x, mask=amask)  # :828-831 (_StackFn)
         align_loss = None
         if use_aligner:  # :847-848; a passed target= is overwritten there and never read
@@ -291,10 +355,12 @@ def _gemm(mode, epi, M, N, K, A, lda, B, ldb, C, ldc, bias=None, f16=0, splits=0
 class _FrontEndFn(torch.autograd.Function):
     """pack -> to_embed -> conv_embed + residual (:811-826) as one node.  Outputs x [B, n, D] and, when asked, the phoneme embedding
     [B, n, E] that the aligner reads: the same rows that sit in columns 0:E of the packed operand, so the table gradient is one
-    deterministic sum over both consumers (vbx_phoneme_emb_bwd).  cond and null_cond receive no gradient."""
+    deterministic sum over both consumers (vbx_phoneme_emb_bwd).  cond and null_cond receive no gradient.  With proj_in a Linear
+    (attach_codec) its weight and bias are two more inputs: the pack is vbx_pack_phoneme_latent_train, and the backward also forms
+    d cond'' and, from it and the pack's lcb operand, d proj_in.weight / d proj_in.bias."""
 
     @staticmethod
-    def forward(ctx, mod, ids, cond, cmask, drop, am8, want_emb, table, we, be, cw, cb):
+    def forward(ctx, mod, ids, cond, cmask, drop, am8, want_emb, table, we, be, cw, cb, pw=None, pb=None):
         dev, st = ids.device, _lib.current_stream()
         B, n = ids.shape
         E, D, M = mod.dim_phoneme_emb, mod.dim, B * n
@@ -302,27 +368,37 @@ class _FrontEndFn(torch.autograd.Function):
         packed = torch.empty(M, E + D, dtype=torch.float16, device=dev)
         packed_b = torch.empty(M, E + D, dtype=torch.bfloat16, device=dev)
         emb = torch.empty(B, n, E, dtype=torch.float32, device=dev) if want_emb else None
-        _lib.call("vbx_pack_phoneme_input_train", ids, table32, E, cond, cond.shape[1], cmask, drop,
-                  mod.null_cond.detach().float().contiguous(), packed, packed_b, emb, B, n, D, st)
+        null, lcb, L = mod.null_cond.detach().float().contiguous(), None, 0
+        if pw is not None:
+            L = pw.shape[1]
+            pw16, pb32 = mod._proj_operands()
+            lcb = torch.empty(M, pw16.shape[1], dtype=torch.bfloat16, device=dev)
+            _lib.call("vbx_pack_phoneme_latent_train", ids, table32, E, cond, cond.shape[1], L, pw16, pb32, cmask, drop, null, packed,
+                      packed_b, emb, lcb, B, n, D, st)
+        else:
+            _lib.call("vbx_pack_phoneme_input_train", ids, table32, E, cond, cond.shape[1], cmask, drop, null, packed, packed_b, emb,
+                      B, n, D, st)
         e = torch.empty(M, D, dtype=torch.float32, device=dev)
         _gemm(_lib.VBX_GEMM_NT, _lib.VBX_EPI_F32, M, D, E + D, packed, E + D, we.detach().to(torch.float16).contiguous(), E + D, e, D,
               bias=be.detach().float().contiguous(), f16=1)
         cw32, cb32 = cw.detach().float().contiguous(), cb.detach().float().contiguous()
         x = torch.empty(B, n, D, dtype=torch.float32, device=dev)
         _lib.call("vbx_convpos_fwd", e, cw32, cb32, am8, None, x, B, n, 0, D, mod.ksize, st)
-        ctx.save_for_backward(ids, am8, packed_b, e, cw32, cb32, we)
+        ctx.save_for_backward(ids, am8, packed_b, e, cw32, cb32, we, lcb)
         ctx.dims = (B, n, E, D, mod.ksize, table.shape[0])
+        ctx.latent = L  # 0: proj_in is the identity, and forward took 12 inputs
         ctx.set_materialize_grads(False)
         return x, emb
 
     @staticmethod
     def backward(ctx, gx, gemb):
-        ids, am8, packed_b, e, cw32, cb32, we = ctx.saved_tensors
+        ids, am8, packed_b, e, cw32, cb32, we, lcb = ctx.saved_tensors
         B, n, E, D, ks, V = ctx.dims
         M, dev, st = B * n, ids.device, _lib.current_stream()
+        L = ctx.latent
         if gx is None and gemb is None:
-            return (None,) * 12
-        dwe = dbe = dcw = dcb = dpk = None
+            return (None,) * (14 if L else 12)
+        dwe = dbe = dcw = dcb = dpk = dpw = dpb = None
         if gx is not None:
             chunks = _lib.lib().vbx_convpos_bwd_chunks(B, n)
             dpre = torch.empty(M, D, dtype=torch.float32, device=dev)
@@ -342,15 +418,26 @@ class _FrontEndFn(torch.autograd.Function):
             _gemm(_lib.VBX_GEMM_TN, _lib.VBX_EPI_SPLITK, D, E + D, M, deb, D, packed_b, E + D, slabs, E + D, splits=splits)
             dwe = torch.empty(D, E + D, dtype=torch.float32, device=dev)
             _lib.call("vbx_splitk_reduce", slabs, splits, D, E + D, dwe, D, E + D, E + D, 0, 0, 0, st)
-            if ctx.needs_input_grad[7]:  # d(packed)[:, 0:E] only: the condition columns need no gradient
+            web = we.detach().to(torch.bfloat16).contiguous() if (ctx.needs_input_grad[7] or L) else None
+            if ctx.needs_input_grad[7]:  # d(packed)[:, 0:E]: the table's columns
                 dpk = torch.empty(M, E, dtype=torch.float32, device=dev)
-                _gemm(_lib.VBX_GEMM_NN, _lib.VBX_EPI_F32, M, E, D, deb, D, we.detach().to(torch.bfloat16).contiguous(), E + D, dpk, E)
+                _gemm(_lib.VBX_GEMM_NN, _lib.VBX_EPI_F32, M, E, D, deb, D, web, E + D, dpk, E)
+            if L:  # d cond'' = de . W_embed[:, E:E+D] (bf16), then [ d proj_in.weight | d proj_in.bias ] = d cond''^T . lcb
+                Kp = lcb.shape[1]
+                dcond = torch.empty(M, D, dtype=torch.bfloat16, device=dev)
+                _gemm(_lib.VBX_GEMM_NN, _lib.VBX_EPI_BF16, M, D, D, deb, D, web[:, E:], E + D, dcond, D)
+                pslabs = torch.empty(splits, D, Kp, dtype=torch.float32, device=dev)
+                _gemm(_lib.VBX_GEMM_TN, _lib.VBX_EPI_SPLITK, D, Kp, M, dcond, D, lcb, Kp, pslabs, Kp, splits=splits)
+                dpw = torch.empty(D, L, dtype=torch.float32, device=dev)
+                dpb = torch.empty(D, dtype=torch.float32, device=dev)
+                _lib.call("vbx_proj_in_wgrad_reduce", pslabs, splits, D, L, dpw, dpb, st)
         gtable = None
         if ctx.needs_input_grad[7] and (dpk is not None or gemb is not None):
             gtable = torch.empty(V, E, dtype=torch.float32, device=dev)
             ge = None if gemb is None else gemb.to(torch.float32).contiguous()
             _lib.call("vbx_phoneme_emb_bwd", ids, dpk, E, ge, gtable, M, V, E, st)
-        return None, None, None, None, None, None, None, gtable, dwe, dbe, dcw, dcb
+        out = (None, None, None, None, None, None, None, gtable, dwe, dbe, dcw, dcb)
+        return out + (dpw, dpb) if L else out
 
 
 class _HeadFn(torch.autograd.Function):
