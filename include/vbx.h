@@ -391,6 +391,14 @@ int vbx_rvq_decode(const long* codes, const float* codebooks, float* out, int B,
  * SConv1d (non-causal): k_eff = (k - 1) dilation + 1, padding_total = k_eff - stride, extra = ceil(L / stride) stride - L,
  * pad_right = padding_total / 2, pad_left = padding_total - pad_right; reflect padding by (pad_left, pad_right + extra) with pad1d's
  * short-input rule (L <= max pad: append max - L + 1 zeros, reflect, cut them off again); Lout = ceil(L / stride).
+ * SConv1d (causal, what the published 24 kHz model is built with): the same k_eff, padding_total, extra and Lout; reflect padding
+ * by (padding_total, extra) -- all of padding_total on the left, only extra on the right -- with the same short-input rule, now at
+ * max pad = max(padding_total, extra).  Either form resolves a padded position with ONE reflection per side: pad1d reflects about a
+ * row of Lz = max(L, max pad + 1) samples (the appended zeros included), and each padding is at most Lz - 1.  The largest
+ * padding_total the SEANet classes ask for is 8 (k = 16 at stride 8; k = 3 at dilation 4).
+ * vbx_seanet_conv_c / vbx_seanet_conv0_c / vbx_seanet_conv_out_c: vbx_seanet_conv / _conv0 / _conv_out with `causal` (0: the
+ *   non-causal padding, nonzero: the causal one); the entry points without the suffix are these at causal = 0, bit for bit.  The
+ *   products, their order, the tiles and the stores do not depend on `causal`: only which sample a padded position reads.
  * vbx_seanet_conv: y [B, Lout, Co] (fp16, or fp32 when out_f32) = conv(elu1 ? ELU(x1) : x1) + bias with w fp16 [Co, k * C1 + C2],
  *   column tap * C1 + c; a second input x2 [B, L, C2] (needs k = 1, stride = 1; never activated) is K-concatenated as columns
  *   k * C1 .. : the Resnet block's tail and its shortcut in one product.  C1, C2 multiples of 8 up to 1024, k <= 16, stride <= 8,
@@ -406,6 +414,10 @@ int vbx_seanet_conv_tile(int C1, int C2, int k, int stride, int dilation);
 int vbx_seanet_conv(const void* x1_f16, const void* x2_f16, const void* w_f16, const float* bias, void* y, int B, int L, int C1, int C2,
                     int Co, int k, int stride, int dilation, int elu1, int out_f32, void* stream);
 int vbx_seanet_conv0(const float* wave, const float* w, const float* bias, void* y_f16, int B, int T, int nf, int k, void* stream);
+int vbx_seanet_conv_c(const void* x1_f16, const void* x2_f16, const void* w_f16, const float* bias, void* y, int B, int L, int C1, int C2,
+                      int Co, int k, int stride, int dilation, int elu1, int out_f32, int causal, void* stream);
+int vbx_seanet_conv0_c(const float* wave, const float* w, const float* bias, void* y_f16, int B, int T, int nf, int k, int causal,
+                       void* stream);
 int vbx_lstm_step(const float* xproj, const void* w_hh0, const void* w_cat1, const float* bias1, void* h0, void* h1, float* c,
                   const void* x, void* y16, float* y32, int B, int T, int H, int layers, int s, void* stream);
 int vbx_lstm(const float* xproj, const void* w_hh0, const void* w_cat1, const float* bias1, void* h0, void* h1, float* c, const void* x,
@@ -426,6 +438,11 @@ int vbx_lstm(const float* xproj, const void* w_hh0, const void* w_cat1, const fl
  *   that a workgroup owns: the largest of 128 .. 32 whose tile + 1 staged positions fit 80 KiB of LDS, else 16 within 160 KiB
  *   (negative: not served); it depends on C alone (stride is only range-checked), and a launch with fewer than tile / 2 + 1 product
  *   rows (L + 1) halves it, down to 16.
+ * vbx_seanet_convtr_t: the same product with the trim given: trim_left samples are cut in front and padding_total - trim_left
+ *   behind, 0 <= trim_left <= stride (anything else: VBX_EINVAL).  The causal SConvTranspose1d trims padding_right =
+ *   ceil(padding_total trim_right_ratio) behind and trim_left = padding_total - padding_right in front: 0 at the published ratio 1.0,
+ *   where the first L stride untrimmed samples are the output.  vbx_seanet_convtr is this at trim_left = stride - stride / 2, bit
+ *   for bit.  At trim_left = 0 row j = L stores nothing and is not launched: L product rows, and the halving rule counts those.
  * vbx_seanet_conv_out: the last convolution, the mirror of vbx_seanet_conv0: x fp16 [B, T, nf] -> y fp32 [B, T] = bias[0] +
  *   sum_tap sum_c w[tap, c] ELU(x[pad(t + tap), c]); w fp32 [k, nf], k odd and at most 7, nf a multiple of 8 up to 64; SConv1d's reflect
  *   padding with pad1d's short-input rule; ELU in fp32 on the stored fp16 value, NOT rounded again; one fp32 fmaf chain on the bias,
@@ -434,6 +451,10 @@ int vbx_seanet_pack_latents(const float* z, void* y_f16, int B, int D, int T, vo
 int vbx_seanet_convtr_tile(int C, int stride);
 int vbx_seanet_convtr(const void* x_f16, const void* w_f16, const float* bias, void* y_f16, int B, int L, int C, int stride, void* stream);
 int vbx_seanet_conv_out(const void* x_f16, const float* w, const float* bias, float* y, int B, int T, int nf, int k, void* stream);
+int vbx_seanet_convtr_t(const void* x_f16, const void* w_f16, const float* bias, void* y_f16, int B, int L, int C, int stride, int trim_left,
+                        void* stream);
+int vbx_seanet_conv_out_c(const void* x_f16, const float* w, const float* bias, float* y, int B, int T, int nf, int k, int causal,
+                          void* stream);
 /* Aligner primitives (voicebox_pytorch_amd.maximum_path / forward_sum_loss; csrc/align.hip): monotonic alignment search and the
  * forward-sum (CTC) loss over an attention map fp32 [B, T, K], T query frames by K keys.  K in 1 .. 1024, any T >= 1, B * T < 2^31;
  * everything else returns VBX_EINVAL.  query_lens / key_lens: int32 [B] on the device, NULL = T / K; a length is clamped into

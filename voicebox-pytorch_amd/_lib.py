@@ -91,6 +91,10 @@ _PROTOS = {
     "vbx_seanet_convtr_tile": [I, I],
     "vbx_seanet_convtr": [P, P, P, P, I, I, I, I, P],
     "vbx_seanet_conv_out": [P, P, P, P, I, I, I, I, P],
+    "vbx_seanet_conv_c": [P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, P],
+    "vbx_seanet_conv0_c": [P, P, P, P, I, I, I, I, I, P],
+    "vbx_seanet_convtr_t": [P, P, P, P, I, I, I, I, I, P],
+    "vbx_seanet_conv_out_c": [P, P, P, P, I, I, I, I, I, P],
     "vbx_maximum_path": [P, P, P, P, P, P, I, I, I, P],
     "vbx_forward_sum_fwd": [P, P, P, F, P, P, P, P, I, I, I, P],
     "vbx_forward_sum_bwd": [P, P, P, F, P, P, P, P, P, I, I, I, P],

@@ -539,7 +539,9 @@ class EncodecVocoCodec(AudioEncoderDecoder):
 
     `encoder` is a module audio [B, T] -> unquantized latents [B, frames, dim]: SEANetEncoder (seanet.py), EnCodec's encoder on the
     device, or the user's own; without one, encode raises.  from_encodec_checkpoint builds encoder, quantizer and -- when no
-    vocoder is passed -- EnCodec's own decoder (SEANetDecoder, a vocoder by its call shape) from one local EnCodec state dict.  Neither weights nor the `encodec` / `vocos` libraries are
+    vocoder is passed -- EnCodec's own decoder (SEANetDecoder, a vocoder by its call shape) from one local EnCodec state dict; the
+    PUBLISHED encodec_24khz file is EnCodec's causal form and needs from_encodec_checkpoint(path, causal=True), which builds
+    CausalSEANetEncoder / CausalSEANetDecoder (a state dict cannot say which form it is).  Neither weights nor the `encodec` / `vocos` libraries are
     part of this package; PARITY with them is UNPINNED (tests/rvq_ref.py restates the arithmetic)."""
 
     def __init__(self, *, rvq, vocoder, encoder=None, feature_rvq=None, sampling_rate=24000, downsample_factor=320):
@@ -597,14 +599,25 @@ class EncodecVocoCodec(AudioEncoderDecoder):
         return cls(rvq=rvq, vocoder=vocoder, encoder=encoder, sampling_rate=sampling_rate, downsample_factor=vocoder.hop_length).eval()
 
     @classmethod
-    def from_encodec_checkpoint(cls, path, *, vocoder=None, bandwidth_id=2, feature_rvq=None, sampling_rate=24000):
+    def from_encodec_checkpoint(cls, path, *, causal=False, trim_right_ratio=1.0, vocoder=None, bandwidth_id=2, feature_rvq=None,
+                                sampling_rate=24000):
         """A LOCAL EnCodec state dict (torch.save of the dict, or {'state_dict': ...}): `encoder.*` becomes a SEANetEncoder (its
         limits apply), `quantizer.vq.layers.{q}._codebook.embed` [codebook_size, dim] the codebooks, of which bandwidth ids 0 .. 3
         use the first 2, 4, 8, 16 (capped by what the file holds); downsample_factor is the product of the encoder's ratios.
         Without `vocoder`, the file's `decoder.*` becomes a SEANetDecoder (EnCodec's own way back to a wave; KeyError when the file
         has no decoder half): the one file is then a complete codec.  A `vocoder` that is passed (a VocosDecoder) is used instead,
-        and the decoder half of the file is not read."""
-        from .seanet import SEANetDecoder, SEANetEncoder
+        and the decoder half of the file is not read.
+
+        causal: the file cannot say whether its network is EnCodec's causal form (keys and shapes are the same), so the caller
+        does.  The PUBLISHED `encodec_24khz` file is causal and needs causal=True, which builds CausalSEANetEncoder and (without
+        `vocoder`) CausalSEANetDecoder with `trim_right_ratio`; with the default it loads without complaint and runs as a different
+        network.  The default stays False only because existing callers depend on it: it builds exactly what it always built."""
+        from .seanet import CausalSEANetDecoder, CausalSEANetEncoder, SEANetDecoder, SEANetEncoder
+
+        if not causal and float(trim_right_ratio) != 1.0:
+            raise ValueError("from_encodec_checkpoint: trim_right_ratio matters for causal=True alone")
+        enc_cls, dec_cls, dec_kw = (CausalSEANetEncoder, CausalSEANetDecoder, dict(trim_right_ratio=trim_right_ratio)) if causal else \
+            (SEANetEncoder, SEANetDecoder, {})
 
         sd = read_checkpoint(path)
         if not 0 <= bandwidth_id < len(RVQ_BANDWIDTH_QUANTIZERS):
@@ -616,12 +629,12 @@ class EncodecVocoCodec(AudioEncoderDecoder):
         if not books:
             raise KeyError("from_encodec_checkpoint: the state dict has no quantizer.vq.layers.0._codebook.embed (not an EnCodec model)")
         books = books[:RVQ_BANDWIDTH_QUANTIZERS[bandwidth_id]]
-        encoder = SEANetEncoder.from_state_dict({k: v for k, v in sd.items() if k.startswith("encoder.")})
+        encoder = enc_cls.from_state_dict({k: v for k, v in sd.items() if k.startswith("encoder.")})
         if vocoder is None:
             half = {k: v for k, v in sd.items() if k.startswith("decoder.")}
             if not any(k.startswith("decoder.model.") for k in half):
                 raise KeyError("from_encodec_checkpoint: the state dict has no decoder.model.* (no decoder half); pass vocoder=")
-            vocoder = SEANetDecoder.from_state_dict(half)
+            vocoder = dec_cls.from_state_dict(half, **dec_kw)
         rvq = ResidualVQ(dim=books[0].shape[1], codebook_size=books[0].shape[0], num_quantizers=len(books))
         rvq.load_state_dict({"codebook_weights": torch.cat([b.float() for b in books], dim=0)})
         return cls(rvq=rvq, vocoder=vocoder, encoder=encoder, feature_rvq=feature_rvq, sampling_rate=sampling_rate,

@@ -26,6 +26,10 @@
 //     vbx_seanet_convtr      ELU, transposed convolution k 2r, stride r, d -> d / 2: ONE product over rows [a_j | a_{j-1}], j = 0 .. L
 //     vbx_seanet_conv x 2    the Resnet block as in the encoder
 //   vbx_seanet_conv_out      ELU (fp32, not rounded again), k 7, nf -> 1, fp32 weights, plain VALU: the wave fp32 [B, frames * hop]
+//
+// Causal mode (CausalSEANetEncoder / CausalSEANetDecoder: the published 24 kHz model) runs the same launches through the entry points
+// that carry the side: vbx_seanet_conv_c / _conv0_c / _conv_out_c (causal: all of padding_total on the left) and vbx_seanet_convtr_t
+// (trim_left: how much of padding_total is cut in front).  Only sn_pads and SnConvTr::left differ; the products do not.
 #include <atomic>
 
 #include "common.hpp"
@@ -57,7 +61,9 @@ VBX_DEV uint4 sn_elu8(uint4 v) {
 }
 
 // padded position q (0 = the first sample of the left padding) -> index into the row, or -1 for one of pad1d's appended zeros.
-// Lz = max(L, max(pad_left, pad_right + extra) + 1) is the length pad1d reflects about; one reflection per side suffices.
+// Lz = max(L, max(pad_left, pad_right + extra) + 1) is the length pad1d reflects about; one reflection per side suffices:
+// both paddings are at most Lz - 1, so the left one mirrors into [1, Lz - 1] and the right one into [0, Lz - 2] -- in the causal
+// form (pad_left = padding_total, pad_right = 0) as in the non-causal one.
 VBX_DEV int sn_src(int q, int pad_left, int L, int Lz) {
   int i = q - pad_left;
   if (i < 0) i = -i;
@@ -294,13 +300,14 @@ struct SnConvTr {
   int L, C, Co, r, left, TT, N, Ktot;
 };
 
-// The non-causal SConvTranspose1d with k = 2 r as ONE product over rows j = 0 .. L: the operand row is [a_j | a_{j-1}] (a = ELU(x),
+// SConvTranspose1d with k = 2 r (`left` samples trimmed in front: r - r / 2 non-causal, r - ceil(r * trim_right_ratio) causal) as
+// ONE product over rows j = 0 .. L: the operand row is [a_j | a_{j-1}] (a = ELU(x),
 // a_{-1} = a_L = 0), its N = r * Co results are the contiguous run of r output positions from trimmed position j * r - left on.  A
 // workgroup owns TT consecutive rows j of one batch row: positions j0 - 1 .. j0 + TT - 1 sit in the LDS (LDS row m holds position
 // j0 - 1 + m), and row m of the A operand reads LDS row m + 1 for its first C columns and LDS row m for the other C, in place (C is
 // a multiple of 16: the eight columns lie in one of the two halves).  Column n is phase n / Co of channel
-// n % Co; row 0 drops its phases below `left`, row L keeps only those: every output element is written by exactly one lane of one
-// workgroup.
+// n % Co; row 0 drops its phases below `left`, row L keeps only those (none at left = 0: the host then launches rows 0 .. L - 1):
+// every output element is written by exactly one lane of one workgroup.
 template <int MG>
 __global__ __launch_bounds__(256) void seanet_convtr_kernel(SnConvTr p) {
   extern __shared__ __attribute__((aligned(16))) u16 sn_lds[];
@@ -439,12 +446,12 @@ int sn_launch(const char* who, const P& p, int blocks, int B, size_t bytes, hipS
   return 0;
 }
 
-// SConv1d's padding: (k_eff - stride) split with the larger half on the left, `extra` on the right so that the last window is whole;
-// Lz is the length pad1d reflects about (sn_src)
+// SConv1d's padding: (k_eff - stride) split with the larger half on the left -- causal: all of it on the left --, `extra` on the
+// right so that the last window is whole; Lz is the length pad1d reflects about (sn_src)
 struct SnPads { int left, Lz; };
-SnPads sn_pads(int k, int stride, int dil, int L, int Lout) {
+SnPads sn_pads(int k, int stride, int dil, int L, int Lout, int causal) {
   const int total = (k - 1) * dil + 1 - stride, extra = Lout * stride - L;
-  const int right = total / 2, left = total - right, maxpad = left > right + extra ? left : right + extra;
+  const int right = causal ? 0 : total / 2, left = total - right, maxpad = left > right + extra ? left : right + extra;
   return SnPads{left, L > maxpad ? L : maxpad + 1};
 }
 
@@ -469,8 +476,8 @@ extern "C" int vbx_seanet_conv_tile(int C1, int C2, int k, int stride, int dilat
   return TT;
 }
 
-extern "C" int vbx_seanet_conv(const void* x1_f16, const void* x2_f16, const void* w_f16, const float* bias, void* y, int B, int L, int C1,
-                               int C2, int Co, int k, int stride, int dilation, int elu1, int out_f32, void* stream) {
+extern "C" int vbx_seanet_conv_c(const void* x1_f16, const void* x2_f16, const void* w_f16, const float* bias, void* y, int B, int L, int C1,
+                                 int C2, int Co, int k, int stride, int dilation, int elu1, int out_f32, int causal, void* stream) {
   VBX_REQUIRE(x1_f16 && w_f16 && bias && y && (x2_f16 || !C2), "vbx_seanet_conv: null operand");
   VBX_REQUIRE(B >= 1 && B <= 65535 && L >= 1 && Co >= 1 && Co <= 4096, "vbx_seanet_conv: need B in 1 .. 65535, L >= 1, Co in 1 .. 4096");
   if (int rc = sn_conv_check(C1, C2, k, stride, dilation)) return rc;
@@ -480,7 +487,7 @@ extern "C" int vbx_seanet_conv(const void* x1_f16, const void* x2_f16, const voi
   SnConv p;
   p.x1 = (const u16*)x1_f16, p.x2 = C2 ? (const u16*)x2_f16 : nullptr, p.w = (const u16*)w_f16, p.bias = bias, p.y = y;
   p.L = L, p.Lout = cdiv(L, stride), p.C1 = C1, p.C2 = C2, p.Co = Co, p.k = k, p.stride = stride, p.dil = dilation;
-  const SnPads pads = sn_pads(k, stride, dilation, L, p.Lout);
+  const SnPads pads = sn_pads(k, stride, dilation, L, p.Lout, causal);
   p.pad_left = pads.left, p.Lz = pads.Lz;
   p.elu1 = elu1 ? 1 : 0, p.out_f32 = out_f32 ? 1 : 0, p.TT = TT, p.Ktot = k * C1 + C2;
   VBX_REQUIRE((long)L * stride < (1L << 30), "vbx_seanet_conv: row too long");
@@ -491,17 +498,27 @@ extern "C" int vbx_seanet_conv(const void* x1_f16, const void* x2_f16, const voi
   return sn_launch<seanet_conv_kernel<1>>("vbx_seanet_conv", p, blocks, B, bytes, (hipStream_t)stream);
 }
 
-extern "C" int vbx_seanet_conv0(const float* wave, const float* w, const float* bias, void* y_f16, int B, int T, int nf, int k,
-                                void* stream) {
+extern "C" int vbx_seanet_conv(const void* x1_f16, const void* x2_f16, const void* w_f16, const float* bias, void* y, int B, int L, int C1,
+                               int C2, int Co, int k, int stride, int dilation, int elu1, int out_f32, void* stream) {
+  return vbx_seanet_conv_c(x1_f16, x2_f16, w_f16, bias, y, B, L, C1, C2, Co, k, stride, dilation, elu1, out_f32, 0, stream);
+}
+
+extern "C" int vbx_seanet_conv0_c(const float* wave, const float* w, const float* bias, void* y_f16, int B, int T, int nf, int k,
+                                  int causal, void* stream) {
   VBX_REQUIRE(wave && w && bias && y_f16 && B >= 1 && B <= 65535 && T >= 1, "vbx_seanet_conv0: bad args");
   VBX_REQUIRE(nf >= 8 && nf % 8 == 0 && nf <= 64, "vbx_seanet_conv0: n_filters must be a multiple of 8 up to 64 (got %d)", nf);
   VBX_REQUIRE(k >= 1 && k <= SN_MAX_K && (k & 1), "vbx_seanet_conv0: kernel_size must be odd, at most %d (got %d)", SN_MAX_K - 1, k);
   VBX_REQUIRE((long)T * (nf / 8) < (1L << 31) * 256, "vbx_seanet_conv0: row too long");
-  const SnPads pads = sn_pads(k, 1, 1, T, T);
+  const SnPads pads = sn_pads(k, 1, 1, T, T, causal);
   hipLaunchKernelGGL(seanet_conv0_kernel, dim3(cdiv((long)T * (nf / 8), 256), B), dim3(256), 0, (hipStream_t)stream, wave, w, bias,
                      (u16*)y_f16, T, nf, k, pads.left, pads.Lz);
   VBX_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int vbx_seanet_conv0(const float* wave, const float* w, const float* bias, void* y_f16, int B, int T, int nf, int k,
+                                void* stream) {
+  return vbx_seanet_conv0_c(wave, w, bias, y_f16, B, T, nf, k, 0, stream);
 }
 
 static SnLstm sn_lstm_desc(const float* xproj, const void* w_hh0, const void* w_cat1, const float* bias1, void* h0, void* h1, float* c,
@@ -545,36 +562,49 @@ extern "C" int vbx_seanet_convtr_tile(int C, int stride) {
   return TT;
 }
 
-extern "C" int vbx_seanet_convtr(const void* x_f16, const void* w_f16, const float* bias, void* y_f16, int B, int L, int C, int stride,
-                                 void* stream) {
+extern "C" int vbx_seanet_convtr_t(const void* x_f16, const void* w_f16, const float* bias, void* y_f16, int B, int L, int C, int stride,
+                                   int trim_left, void* stream) {
   VBX_REQUIRE(x_f16 && w_f16 && bias && y_f16, "vbx_seanet_convtr: null operand");
   VBX_REQUIRE(B >= 1 && B <= 65535 && L >= 1, "vbx_seanet_convtr: need B in 1 .. 65535, L >= 1");
   if (int rc = sn_convtr_check(C, stride)) return rc;
+  VBX_REQUIRE(trim_left >= 0 && trim_left <= stride, "vbx_seanet_convtr_t: trim_left must be in 0 .. stride (got %d, stride %d)", trim_left,
+              stride);
   VBX_REQUIRE((long)L * stride < (1L << 30), "vbx_seanet_convtr: row too long");
   int TT = sn_convtr_tile(C);
   VBX_REQUIRE(TT > 0, "vbx_seanet_convtr: 16 rows of this transposed convolution do not fit the LDS");
-  while (TT > 16 && TT / 2 >= L + 1) TT >>= 1;  // a short row: L + 1 product rows
+  const int rows = trim_left ? L + 1 : L;  // nothing trimmed in front: row L lies wholly behind the output
+  while (TT > 16 && TT / 2 >= rows) TT >>= 1;  // a short row: no tile of rows that store nothing
   SnConvTr p;
   p.x = (const u16*)x_f16, p.w = (const u16*)w_f16, p.bias = bias, p.y = (u16*)y_f16;
-  p.L = L, p.C = C, p.Co = C / 2, p.r = stride, p.left = stride - stride / 2, p.TT = TT, p.N = stride * (C / 2), p.Ktot = 2 * C;
+  p.L = L, p.C = C, p.Co = C / 2, p.r = stride, p.left = trim_left, p.TT = TT, p.N = stride * (C / 2), p.Ktot = 2 * C;
   const size_t bytes = sn_convtr_lds(TT, C);
-  const int MG = sn_blocks_per_item((p.N + 15) / 16, TT / 16), blocks = cdiv(L + 1, TT);
+  const int MG = sn_blocks_per_item((p.N + 15) / 16, TT / 16), blocks = cdiv(rows, TT);
   if (MG == 4) return sn_launch<seanet_convtr_kernel<4>>("vbx_seanet_convtr", p, blocks, B, bytes, (hipStream_t)stream);
   if (MG == 2) return sn_launch<seanet_convtr_kernel<2>>("vbx_seanet_convtr", p, blocks, B, bytes, (hipStream_t)stream);
   return sn_launch<seanet_convtr_kernel<1>>("vbx_seanet_convtr", p, blocks, B, bytes, (hipStream_t)stream);
 }
 
-extern "C" int vbx_seanet_conv_out(const void* x_f16, const float* w, const float* bias, float* y, int B, int T, int nf, int k,
-                                   void* stream) {
+extern "C" int vbx_seanet_convtr(const void* x_f16, const void* w_f16, const float* bias, void* y_f16, int B, int L, int C, int stride,
+                                 void* stream) {
+  return vbx_seanet_convtr_t(x_f16, w_f16, bias, y_f16, B, L, C, stride, stride - stride / 2, stream);
+}
+
+extern "C" int vbx_seanet_conv_out_c(const void* x_f16, const float* w, const float* bias, float* y, int B, int T, int nf, int k,
+                                     int causal, void* stream) {
   VBX_REQUIRE(x_f16 && w && bias && y && B >= 1 && B <= 65535 && T >= 1, "vbx_seanet_conv_out: bad args");
   VBX_REQUIRE(nf >= 8 && nf % 8 == 0 && nf <= 64, "vbx_seanet_conv_out: n_filters must be a multiple of 8 up to 64 (got %d)", nf);
   VBX_REQUIRE(k >= 1 && k <= 7 && (k & 1), "vbx_seanet_conv_out: last_kernel_size must be odd, at most 7 (got %d)", k);
   VBX_REQUIRE(T < (1 << 30), "vbx_seanet_conv_out: row too long");
-  const SnPads pads = sn_pads(k, 1, 1, T, T);
+  const SnPads pads = sn_pads(k, 1, 1, T, T, causal);
   hipLaunchKernelGGL(seanet_conv_out_kernel, dim3(cdiv(T, 256), B), dim3(256), 0, (hipStream_t)stream, (const u16*)x_f16, w, bias, y, T, nf,
                      k, pads.left, pads.Lz);
   VBX_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int vbx_seanet_conv_out(const void* x_f16, const float* w, const float* bias, float* y, int B, int T, int nf, int k,
+                                   void* stream) {
+  return vbx_seanet_conv_out_c(x_f16, w, bias, y, B, T, nf, k, 0, stream);
 }
 
 extern "C" int vbx_seanet_pack_latents(const float* z, void* y_f16, int B, int D, int T, void* stream) {

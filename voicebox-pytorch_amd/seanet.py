@@ -9,7 +9,7 @@ EnCodec state dict loads as is; neither the `encodec` library nor any weights ar
 hub: from_checkpoint reads a local file.
 
 PARITY UNPINNED: the `encodec` library is not a dependency and no fixture of it exists.  This follows its published arithmetic
-(encodec/modules/seanet.py, conv.py, lstm.py at the 24 kHz model's settings), restated in fp64 with F.pad / F.conv1d / F.elu and an
+(encodec/modules/seanet.py, conv.py, lstm.py at the 24 kHz model's widths, causal=False), restated in fp64 with F.pad / F.conv1d / F.elu and an
 explicit LSTM loop in tests/seanet_ref.py; the kernels are tested against that restatement (tests/test_seanet_gpu.py,
 profiles/seanet_parity.txt).
 
@@ -21,6 +21,14 @@ SEANetDecoder is the other half of the same file: EnCodec's decoder (`decoder.*`
 the LSTM, per ratio ELU + a strided transposed convolution (k = 2 r, as one product over the two input frames under every output
 sample) + Resnet blocks, ELU and a last convolution to one channel; the same contract, the same state-dict layouts, restated in
 tests/seanet_dec_ref.py.  EncodecVocoCodec.from_encodec_checkpoint(path) makes one local EnCodec state dict a complete codec.
+
+CAUSAL OR NOT.  EnCodec's PUBLISHED 24 kHz model (`encodec_24khz`) is built with causal=True: every SConv1d pads all of
+padding_total on the left, every SConvTranspose1d trims at the right end only (trim_right_ratio = 1.0).  SEANetEncoder and
+SEANetDecoder are the NON-causal form; CausalSEANetEncoder and CausalSEANetDecoder at the end of this file are the causal one
+(the same kernels, the padding side and the trim handed to them; restated in tests/seanet_causal_ref.py).  A state dict cannot
+say which form it is -- keys and shapes are identical -- so the published file needs the Causal classes, or
+from_encodec_checkpoint(path, causal=True); loaded into the non-causal classes it runs without complaint as a different
+network.  The defaults stay non-causal only because existing callers depend on them.
 """
 import math
 import os
@@ -137,11 +145,14 @@ class _SConvTr(nn.Module):
 
 
 def _check_keywords(who, channels, dimension, n_filters, n_residual_layers, ratios, activation, activation_params, norm, kernel_size,
-                    last_kernel_size, residual_kernel_size, dilation_base, causal, pad_mode, true_skip, compress, lstm):
-    """what neither half of the network is built for; returns the exception factory for the caller's own refusals"""
+                    last_kernel_size, residual_kernel_size, dilation_base, causal, pad_mode, true_skip, compress, lstm, causal_class=None):
+    """what neither half of the network is built for; returns the exception factory for the caller's own refusals.  causal_class:
+    the name of the Causal subclass that is being constructed (it alone admits causal=True, and nothing else), or None"""
     no = lambda what: NotImplementedError(f"{who}: {what} is not built")
-    if causal:
-        raise no("causal=True")
+    if causal_class and not causal:
+        raise ValueError(f"{causal_class} is the causal network: causal=False is {who}")
+    if causal and not causal_class:
+        raise no(f"causal=True (use Causal{who})")
     if pad_mode != "reflect":
         raise no(f'pad_mode="{pad_mode}" (only "reflect")')
     if norm not in ("weight_norm", "none"):
@@ -179,6 +190,8 @@ class _SEANet(PackedWeights, nn.Module):
     convolution kernel and of the LSTM"""
 
     _HALF = ""  # "encoder" / "decoder": the prefix of this half in a whole EnCodec state dict
+    _CAUSAL = None  # the name of a Causal subclass; None in the non-causal classes
+    causal = False
 
     def _check_tiles(self, no):
         """whatever the convolution kernels cannot tile is refused at construction, not at the first forward; a Resnet block's 1 x 1
@@ -221,9 +234,9 @@ class _SEANet(PackedWeights, nn.Module):
         return super().load_state_dict(self._canonical(state_dict), strict=strict, **kw)
 
     @classmethod
-    def from_checkpoint(cls, path):
+    def from_checkpoint(cls, path, **kw):
         """A LOCAL file written by torch.save: an EnCodec (or one half's) state dict or {'state_dict': ...}; see from_state_dict."""
-        return cls.from_state_dict(read_checkpoint(path))
+        return cls.from_state_dict(read_checkpoint(path), **kw)
 
     # -- operand copies
     def packed_ops(self):
@@ -268,10 +281,9 @@ class _SEANet(PackedWeights, nn.Module):
             op["b1"] = (f(l.bias_ih_l1) + f(l.bias_hh_l1)).contiguous()
         return op
 
-    @staticmethod
-    def _conv(op, x1, x2, y, B, L, st):
-        _lib.call("vbx_seanet_conv", x1, x2, op["w"], op["b"], y, B, L, op["C1"], op["C2"], op["Co"], op["k"], op["stride"], op["dil"],
-                  int(op["elu"]), int(op["out_f32"]), st)
+    def _conv(self, op, x1, x2, y, B, L, st):
+        _lib.call("vbx_seanet_conv_c", x1, x2, op["w"], op["b"], y, B, L, op["C1"], op["C2"], op["Co"], op["k"], op["stride"], op["dil"],
+                  int(op["elu"]), int(op["out_f32"]), int(self.causal), st)
 
     @staticmethod
     def lstm_forward(op, x, B, T, st, y32=None):
@@ -302,7 +314,7 @@ class SEANetEncoder(_SEANet):
     Runs without gradients, in eval semantics.  The folded fp16 weights are packed once and re-packed when a parameter's version
     counter or storage changes; after a write through `p.data` call mark_weights_dirty().
 
-    Raises NotImplementedError for what is not built: causal=True, pad_mode other than "reflect", norm other than "weight_norm" /
+    Raises NotImplementedError for what is not built: causal=True (served by CausalSEANetEncoder, not here), pad_mode other than "reflect", norm other than "weight_norm" /
     "none", an activation other than ELU(alpha=1), channels != 1, true_skip=True, compress != 2, n_filters not a multiple of 16 or
     above 64, other than 1 .. 4 ratios or a ratio outside 2 .. 8, n_residual_layers outside 1 .. 3, dilation_base != 2, lstm
     outside 0 .. 2, dimension not a multiple of 8 or above 512, kernel_size / last_kernel_size even or above 7,
@@ -318,7 +330,9 @@ class SEANetEncoder(_SEANet):
         super().__init__()
         ratios = tuple(int(r) for r in ratios)
         no = _check_keywords("SEANetEncoder", channels, dimension, n_filters, n_residual_layers, ratios, activation, activation_params, norm,
-                             kernel_size, last_kernel_size, residual_kernel_size, dilation_base, causal, pad_mode, true_skip, compress, lstm)
+                             kernel_size, last_kernel_size, residual_kernel_size, dilation_base, causal, pad_mode, true_skip, compress, lstm,
+                             causal_class=self._CAUSAL)
+        self.causal = bool(causal)
         self.channels, self.dimension, self.n_filters, self.n_residual_layers, self.ratios = channels, dimension, n_filters, n_residual_layers, ratios
         self.norm, self.kernel_size, self.last_kernel_size, self.residual_kernel_size = norm, kernel_size, last_kernel_size, residual_kernel_size
         self.dilation_base, self.compress, self.lstm = dilation_base, compress, lstm
@@ -342,9 +356,11 @@ class SEANetEncoder(_SEANet):
         return T
 
     @classmethod
-    def from_state_dict(cls, sd):
+    def from_state_dict(cls, sd, **kw):
         """A state dict already in memory, in any of the three layouts.  The widths are read off the shapes; the ratios off the
-        strided kernels (k = 2 r); what the shapes do not tell (non-causal, reflect padding, ELU) is taken as the 24 kHz model's."""
+        strided kernels (k = 2 r); reflect padding and ELU are taken as given.  A state dict CANNOT say whether its network is
+        causal -- the keys and shapes are the same -- so the class says it: SEANetEncoder.from_state_dict builds the non-causal
+        network, CausalSEANetEncoder.from_state_dict the causal one (what the published `encodec_24khz` file needs)."""
         sd = cls._canonical(sd)
         idx = sorted({int(k.split(".")[1]) for k in sd if k.startswith("model.")})
         norm = "weight_norm" if "model.0.conv.conv.weight_g" in sd else "none"
@@ -364,7 +380,7 @@ class SEANetEncoder(_SEANet):
         dimension, _, last_k = shape(f"model.{convs[-1]}")
         self = cls(channels=channels, dimension=dimension, n_filters=n_filters, n_residual_layers=len(res) // len(strided), ratios=ratios,
                    norm=norm, kernel_size=kernel_size, last_kernel_size=last_k, residual_kernel_size=shape(f"model.{first}.block.1")[2],
-                   compress=n_filters // hidden, lstm=lstm)
+                   compress=n_filters // hidden, lstm=lstm, **kw)
         self.load_state_dict(sd)
         return self.eval()
 
@@ -408,7 +424,7 @@ class SEANetEncoder(_SEANet):
         ops = self.packed_ops()
         wave = audio.detach().to(torch.float32).contiguous()
         x = torch.empty(B, L, ops[0]["nf"], dtype=torch.float16, device=dev)
-        _lib.call("vbx_seanet_conv0", wave, ops[0]["w"], ops[0]["b"], x, B, L, ops[0]["nf"], ops[0]["k"], st)
+        _lib.call("vbx_seanet_conv0_c", wave, ops[0]["w"], ops[0]["b"], x, B, L, ops[0]["nf"], ops[0]["k"], int(self.causal), st)
         kept = None
         for op in ops[1:]:
             if op["op"] == "lstm":
@@ -445,7 +461,7 @@ class SEANetDecoder(_SEANet):
     weights are folded in fp32 and packed once per parameter version (mark_weights_dirty() after a write through `p.data`).
 
     Raises NotImplementedError for what SEANetEncoder refuses (same keywords, same ranges), for final_activation other than None
-    and trim_right_ratio != 1.0, and for any layer without a tile in its kernel (none inside these ranges).  GPU tensors only; a
+    and trim_right_ratio != 1.0 (causal=True and trim_right_ratio are served by CausalSEANetDecoder, not here), and for any layer without a tile in its kernel (none inside these ranges).  GPU tensors only; a
     forward on a device other than the parameters' MOVES THE MODULE there -- keep one instance per device."""
 
     _HALF = "decoder"
@@ -457,11 +473,16 @@ class SEANetDecoder(_SEANet):
         super().__init__()
         ratios = tuple(int(r) for r in ratios)
         no = _check_keywords("SEANetDecoder", channels, dimension, n_filters, n_residual_layers, ratios, activation, activation_params, norm,
-                             kernel_size, last_kernel_size, residual_kernel_size, dilation_base, causal, pad_mode, true_skip, compress, lstm)
+                             kernel_size, last_kernel_size, residual_kernel_size, dilation_base, causal, pad_mode, true_skip, compress, lstm,
+                             causal_class=self._CAUSAL)
         if final_activation is not None:
             raise no(f"final_activation={final_activation!r} (only None)")
-        if float(trim_right_ratio) != 1.0:
-            raise no(f"trim_right_ratio={trim_right_ratio} (only 1.0; it matters for causal=True alone)")
+        if self._CAUSAL:
+            if not 0.0 <= float(trim_right_ratio) <= 1.0:
+                raise ValueError(f"{self._CAUSAL}: trim_right_ratio must be in [0, 1] (got {trim_right_ratio})")
+        elif float(trim_right_ratio) != 1.0:
+            raise no(f"trim_right_ratio={trim_right_ratio} (only 1.0; it matters for causal=True alone: use CausalSEANetDecoder)")
+        self.causal, self.trim_right_ratio = bool(causal), float(trim_right_ratio)
         self.channels, self.dimension, self.n_filters, self.n_residual_layers, self.ratios = channels, dimension, n_filters, n_residual_layers, ratios
         self.norm, self.kernel_size, self.last_kernel_size, self.residual_kernel_size = norm, kernel_size, last_kernel_size, residual_kernel_size
         self.dilation_base, self.compress, self.lstm = dilation_base, compress, lstm
@@ -481,9 +502,11 @@ class SEANetDecoder(_SEANet):
         self._check_tiles(no)
 
     @classmethod
-    def from_state_dict(cls, sd):
+    def from_state_dict(cls, sd, **kw):
         """A state dict already in memory, in any of the three layouts.  The widths are read off the shapes; the ratios off the
-        transposed kernels (k = 2 r); what the shapes do not tell (non-causal, reflect padding, ELU) is taken as the 24 kHz model's."""
+        transposed kernels (k = 2 r); reflect padding and ELU are taken as given.  A state dict CANNOT say whether its network is
+        causal: SEANetDecoder.from_state_dict builds the non-causal network, CausalSEANetDecoder.from_state_dict the causal one
+        (what the published `encodec_24khz` file needs).  **kw: constructor keywords the shapes do not tell (trim_right_ratio)."""
         sd = cls._canonical(sd)
         idx = sorted({int(k.split(".")[1]) for k in sd if k.startswith("model.")})
         norm = "weight_norm" if "model.0.conv.conv.weight_g" in sd else "none"
@@ -501,7 +524,8 @@ class SEANetDecoder(_SEANet):
         lstm = 0 if not lstm_i else 1 + max(int(k[-1]) for k in sd if k.startswith(f"model.{lstm_i[0]}.lstm.weight_ih_l"))
         hidden, dim, res_k = shape(f"model.{res[0]}.block.1")
         self = cls(channels=channels, dimension=dimension, n_filters=n_filters, n_residual_layers=len(res) // len(trs), ratios=ratios,
-                   norm=norm, kernel_size=kernel_size, last_kernel_size=last_k, residual_kernel_size=res_k, compress=dim // hidden, lstm=lstm)
+                   norm=norm, kernel_size=kernel_size, last_kernel_size=last_k, residual_kernel_size=res_k, compress=dim // hidden, lstm=lstm,
+                   **kw)
         self.load_state_dict(sd)
         return self.eval()
 
@@ -511,6 +535,13 @@ class SEANetDecoder(_SEANet):
         phase p of an output run"""
         t = w.permute(2, 1, 0)  # [2r, Co, C]
         return torch.cat([t[:r].reshape(-1, w.shape[0]), t[r:].reshape(-1, w.shape[0])], dim=1)
+
+    def trim_left(self, stride):
+        """what a transposed convolution of this stride cuts in FRONT of its padding_total = stride surplus samples: the larger half
+        in the non-causal network; padding_total - ceil(padding_total * trim_right_ratio) in the causal one (0 at the ratio 1.0)"""
+        if not self.causal:
+            return stride - stride // 2
+        return stride - math.ceil(stride * self.trim_right_ratio)
 
     def _build_ops(self):
         f = lambda t: t.detach().float().contiguous()
@@ -553,11 +584,11 @@ class SEANetDecoder(_SEANet):
                 x = self.lstm_forward(op, x, B, L, st)
             elif op["op"] == "convtr":
                 y = f16(B, L * op["stride"], op["Co"])
-                _lib.call("vbx_seanet_convtr", x, op["w"], op["b"], y, B, L, op["C"], op["stride"], st)
+                _lib.call("vbx_seanet_convtr_t", x, op["w"], op["b"], y, B, L, op["C"], op["stride"], self.trim_left(op["stride"]), st)
                 x, L = y, L * op["stride"]
             elif op["op"] == "conv_out":
                 y = torch.empty(B, L, dtype=torch.float32, device=dev)
-                _lib.call("vbx_seanet_conv_out", x, op["w"], op["b"], y, B, L, op["nf"], op["k"], st)
+                _lib.call("vbx_seanet_conv_out_c", x, op["w"], op["b"], y, B, L, op["nf"], op["k"], int(self.causal), st)
                 x = y
             else:
                 y = f16(B, L, op["Co"])
@@ -566,3 +597,44 @@ class SEANetDecoder(_SEANet):
                     kept = x
                 x = y
         return x
+
+
+class CausalSEANetEncoder(SEANetEncoder):
+    """SEANetEncoder in EnCodec's causal form -- what the PUBLISHED 24 kHz model (`encodec_24khz`) is built with.  Every SConv1d pads
+    all of padding_total = k_eff - stride on the left and only `extra` on the right (reflect, pad1d's short-input rule at max pad =
+    max(padding_total, extra)); the LSTM is unidirectional in either form; layers, state-dict keys, the three layouts, the limits
+    and the precision contract are SEANetEncoder's.  The state dict of a causal and of a non-causal model cannot be told apart,
+    so the caller chooses the class; a causal model loaded into SEANetEncoder runs, silently, as a different network.
+
+    `causal` defaults to True; causal=False raises ValueError (that network is SEANetEncoder).  Causal in EnCodec's sense: frame f
+    reads no sample behind its own hop, except that the FIRST frames also read the reflection of the samples just after the
+    start.  Same kernels, through vbx_seanet_conv0_c / vbx_seanet_conv_c (include/vbx.h).  PARITY with the `encodec` library is
+    UNPINNED here as well; the yardstick is tests/seanet_causal_ref.py."""
+
+    _CAUSAL = "CausalSEANetEncoder"
+
+    def __init__(self, channels=1, dimension=128, n_filters=32, n_residual_layers=1, ratios=(8, 5, 4, 2), activation="ELU",
+                 activation_params=None, norm="weight_norm", kernel_size=7, last_kernel_size=7, residual_kernel_size=3,
+                 dilation_base=2, causal=True, pad_mode="reflect", true_skip=False, compress=2, lstm=2):
+        super().__init__(channels, dimension, n_filters, n_residual_layers, ratios, activation, activation_params, norm, kernel_size,
+                         last_kernel_size, residual_kernel_size, dilation_base, causal, pad_mode, true_skip, compress, lstm)
+
+
+class CausalSEANetDecoder(SEANetDecoder):
+    """SEANetDecoder in EnCodec's causal form -- what the PUBLISHED 24 kHz model is built with.  Its convolutions pad as
+    CausalSEANetEncoder's; each SConvTranspose1d trims padding_right = ceil(padding_total * trim_right_ratio) samples behind and
+    padding_total - padding_right in front (padding_total = stride): at the published ratio 1.0 nothing in front, the first
+    L * stride untrimmed samples are the output.  trim_right_ratio may be anything in [0, 1] (ValueError outside).  `causal`
+    defaults to True; causal=False raises ValueError (that network is SEANetDecoder).  Everything else -- layers, keys, layouts,
+    limits, the precision contract -- is SEANetDecoder's; the same kernels through vbx_seanet_conv_c / vbx_seanet_convtr_t /
+    vbx_seanet_conv_out_c.  PARITY with the `encodec` library is UNPINNED; the yardstick is tests/seanet_causal_ref.py."""
+
+    _CAUSAL = "CausalSEANetDecoder"
+
+    def __init__(self, channels=1, dimension=128, n_filters=32, n_residual_layers=1, ratios=(8, 5, 4, 2), activation="ELU",
+                 activation_params=None, final_activation=None, final_activation_params=None, norm="weight_norm", kernel_size=7,
+                 last_kernel_size=7, residual_kernel_size=3, dilation_base=2, causal=True, pad_mode="reflect", true_skip=False,
+                 compress=2, lstm=2, trim_right_ratio=1.0):
+        super().__init__(channels, dimension, n_filters, n_residual_layers, ratios, activation, activation_params, final_activation,
+                         final_activation_params, norm, kernel_size, last_kernel_size, residual_kernel_size, dilation_base, causal,
+                         pad_mode, true_skip, compress, lstm, trim_right_ratio)
