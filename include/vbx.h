@@ -242,6 +242,29 @@ int vbx_dropout_rows_f32(float* x, long rows, int cols, int ld, unsigned long lo
  * padding.  The benchmark's kernel is a separate instantiation and is not changed by this one. */
 int vbx_attn_fwd_lens(const void* q16, const void* k16, const void* v16, const uint8_t* mask, const int* key_lens, void* out16,
                       void* out_bf16, float* lse, int B, int H, int Np, float scale, void* stream);
+/* ------------------------------------------------------------------ packed rows (inference; the sampler's lens= with pack=True)
+ * A ragged batch of B rows with len_b frames each runs as ONE batch row of Mp rows.
+ *  - A segment is one batch row: R register rows, then len_b frame rows, then dead rows up to the next multiple of
+ *    VBX_PACK_ALIGN = 128, the attention query tile.  A query tile and a 64-row conv_embed chunk belong to exactly one segment.
+ *  - Segments follow each other in batch order.  Mp = sum of the segment sizes, optionally rounded up (the sampler's pack_bucket, a
+ *    multiple of 128); rows past the last segment are dead.
+ *  - Device tables, int32, S segments: seg_start[S] (a multiple of 128), seg_klen[S] = R + len_b >= 1 (the live rows = the keys of
+ *    the segment), tile_seg[Mp / 128] = the segment of the tile, or -1 past the last segment; and the rotary tables rot_cos /
+ *    rot_sin [Mp, 32] gathered by each row's index inside its own segment (registers at position -10000, frame n at n), dead rows
+ *    taking row 0.  The kernels index by these tables without checking them: the caller validates them on the host (starts aligned
+ *    and ascending, 1 <= klen, seg_start + align(klen) <= Mp, tile_seg agreeing with the starts) before they reach the device.
+ *  - Dead rows are finite but otherwise unspecified after the first layer.  No live row depends on them (the attention kernel
+ *    never loads a row outside the live keys of the query's segment, the convolution reads 0 outside 0 <= n < len_b, every other
+ *    kernel is row-wise), and the caller never reads them back.
+ * vbx_attn_fwd_segs: q16 / k16 / v16 [1, H, Mp, 64], out [Mp, H * 64], lse [H, Mp].  The workgroup of query tile t reads
+ * s = tile_seg[t] and walks ceil(seg_klen[s] / 64) key tiles from row seg_start[s]; only the last, partial tile compares key < klen
+ * (no mask bytes), and its DMA re-reads row seg_start[s] + seg_klen[s] - 1 instead of anything past it.  Every live query row and
+ * lse is bit-equal to vbx_attn_fwd_lens on the segment alone (B = 1, Np = its aligned size, key_lens = klen, mask NULL); a dead
+ * query row, and every row of a tile with s < 0, gets zeros and lse 1e30 whatever q / k / v hold there.  Grid fixed by (Mp / 128, H),
+ * the XCD-aware order of vbx_attn_fwd.  A fourth instantiation of the forward body: the other three are not changed by it. */
+#define VBX_PACK_ALIGN 128
+int vbx_attn_fwd_segs(const void* q16, const void* k16, const void* v16, const int* seg_start, const int* seg_klen,
+                      const int* tile_seg, void* out16, void* out_bf16, float* lse, int H, int Mp, float scale, void* stream);
 int vbx_attn_fwd_dropout(const void* q16, const void* k16, const void* v16, const uint8_t* mask, void* out16, void* out_bf16,
                          float* lse, int B, int H, int Np, float scale, const void* bits_rm, float p, void* stream);
 int vbx_attn_bwd_dropout(const void* q16, const void* k16, const void* qb, const void* kb, const void* v, const uint8_t* mask,
@@ -613,6 +636,12 @@ int vbx_convpos_fwd(const float* e, const float* w, const float* bias, const uin
 /* vbx_convpos_fwd with libm's erff in the GELU instead of the fast path's Abramowitz-Stegun form (precise mode) */
 int vbx_convpos_fwd_libm(const float* e, const float* w, const float* bias, const uint8_t* mask, const float* reg,
                          float* xs, int B, int N, int R, int D, int ksize, void* stream);
+/* conv_embed over packed rows (see "packed rows"): e [Mp, D] = to_embed over every packed row (its register and dead rows are
+ * computed and not read), xs [Mp, D]: register rows = reg [R, D], frame row n of a segment = e + GELU(conv) with taps outside
+ * 0 <= n < len_b reading 0 (tap order and GELU of vbx_convpos_fwd: a frame is bit-equal to vbx_convpos_fwd on the row alone), dead
+ * rows exactly 0.  seg_klen[s] = R + len_b. */
+int vbx_convpos_fwd_segs(const float* e, const float* w, const float* bias, const float* reg, const int* seg_start,
+                         const int* seg_klen, const int* tile_seg, float* xs, int Mp, int R, int D, int ksize, void* stream);
 /* ksize: any odd kernel size <= 31 (the reference default is 31, voicebox_pytorch.py:893; one unrolled instantiation per size).
  * backward: de = dxs[:,R:] + conv-transpose(...) ; dw/db partials [chunks][D][ksize+1]; dreg [R,D]. */
 int vbx_convpos_bwd(const float* e, const float* w, const float* bias, const uint8_t* mask, const float* dxs,
@@ -930,6 +959,13 @@ typedef struct {
                              vbx_proj_in_embed, to_embed is Linear(2*D + E, D), to_pred Linear(D, Lc), null_cond is D wide.  Din must be
                              0 or D.  Operand copies are zero-padded inside the arenas (proj_in K to vbx_proj_in_kp(Lc), to_pred N to a
                              multiple of 8).  Not served by precise mode. */
+  int packed;             /* 1: packed rows (see "packed rows"; inference only): B must be 1 and N = Mp, a multiple of VBX_PACK_ALIGN.  The
+                             layout has no register rows of its own -- Np = N = Mp, M0 = M, rot_cos / rot_sin are [Mp, 32] in the packed
+                             order, x / cond / cond_mask / pred are [1, Mp, .] -- and R and the register parameter go to
+                             vbx_convpos_fwd_segs only.  vbx_model_forward runs vbx_convpos_fwd_segs and vbx_attn_fwd_segs with the
+                             tables of vbx_io in place of vbx_convpos_fwd and vbx_attn_fwd*, the final norm and to_pred over all Mp
+                             rows, every other launch as usual with M = Mp.  Exact where all rows share the time point (the sampler).
+                             Not served: training, precise, gateloop, stack_only, an attn_mask, key_lens (VBX_EINVAL).  0 = none. */
 } vbx_model;
 
 typedef struct {
@@ -959,6 +995,9 @@ typedef struct {
   const int* key_lens;          /* inference only, or NULL: [B] int32 on the device, key_lens[b] = R + len_b >= 1 where attn_mask_p is the
                                    prefix mask n < key_lens[b] (the sampler's lens=).  The fast-path forward then runs vbx_attn_fwd_lens:
                                    key tiles past the length are not walked.  Requires attn_mask_p; precise mode ignores it (mask only). */
+  const int* seg_start;         /* vbx_model.packed only (NULL otherwise): the device tables of "packed rows", validated by the caller: */
+  const int* seg_klen;          /* seg_start / seg_klen int32 [segments], tile_seg int32 [Mp / 128]                                    */
+  const int* tile_seg;
 } vbx_io;
 
 size_t vbx_model_wpack_bytes(const vbx_model* m);

@@ -46,6 +46,7 @@ _PROTOS = {
     "vbx_rmsnorm_bwd": [P, P, L, P, P, P, P, P, P, I, I, I, I, I, P],
     "vbx_attn_fwd": [P, P, P, P, P, P, P, I, I, I, F, P],
     "vbx_attn_fwd_lens": [P, P, P, P, P, P, P, P, I, I, I, F, P],
+    "vbx_attn_fwd_segs": [P, P, P, P, P, P, P, P, P, I, I, F, P],
     "vbx_attn_bwd": [P, P, P, P, P, P, P, I, P, P, P, P, P, P, I, I, I, I, F, P, P],
     "vbx_attn_bwd_fused": [P, P, P, P, P, P, P, I, P, P, P, P, P, P, P, P, P, F, P, I, P, I, I, I, F, P, P],
     "vbx_attn_bwd_select": [I],
@@ -124,6 +125,7 @@ _PROTOS = {
     "vbx_rmsnorm_fwd_f32": [P, P, P, L, P, I, I, I, I, I, P],
     "vbx_convpos_fwd": [P, P, P, P, P, P, I, I, I, I, I, P],
     "vbx_convpos_fwd_libm": [P, P, P, P, P, P, I, I, I, I, I, P],
+    "vbx_convpos_fwd_segs": [P, P, P, P, P, P, P, P, I, I, I, I, P],
     "vbx_convpos_bwd": [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, P],
     "vbx_convpos_bwd_chunks": [I, I],
     "vbx_conv_wgrad_finalize": [P, I, I, I, P, P, P],

@@ -367,6 +367,18 @@ __global__ __launch_bounds__(256, 4) void attn_fwd_kernel_v3_lens(const u16* __r
 #include "attn_fwd_v3_body.inc"
 }
 #undef VBX_FWD_LENS
+// the same body over the segments of a packed row stream (inference, the sampler's pack=True; include/vbx.h "packed rows"): one batch
+// row of Np = Mp rows, every 128-row query tile inside one segment, keys from that segment's live rows only, no mask
+#define VBX_FWD_SEGS
+__global__ __launch_bounds__(256, 4) void attn_fwd_kernel_v3_segs(const u16* __restrict__ q16, const u16* __restrict__ k16,
+                                                                  const u16* __restrict__ vv, u16* __restrict__ out,
+                                                                  u16* __restrict__ outb, float* __restrict__ lse, int H, int Np,
+                                                                  float scale2, int BH, int xmap, const int* __restrict__ seg_start,
+                                                                  const int* __restrict__ seg_klen, const int* __restrict__ tile_seg) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+#include "attn_fwd_v3_body.inc"
+}
+#undef VBX_FWD_SEGS
 
 // ---- Round-4 experiments on the forward, measured at the benchmark grid (8 x 16 heads x 1040 rows, stand-alone, same box) and removed:
 //  * "v4": 256-row workgroups, a wave owning TWO 32-query blocks whose chains are interleaved in one instruction stream (S of block B
@@ -1115,6 +1127,21 @@ extern "C" int vbx_attn_fwd_lens(const void* q16, const void* k16, const void* v
   dim3 grid(cdiv(Np, 128) * ((xmap & 1) ? cdiv(BH, 8) * 8 : BH));
   hipLaunchKernelGGL(attn_fwd_kernel_v3_lens, grid, dim3(256), A3ST * ASTAGE, (hipStream_t)stream, (const u16*)q16, (const u16*)k16,
                      (const u16*)v, mask, (u16*)out, (u16*)out_bf16, lse, H, Np, QK_UNIT, BH, xmap, key_lens);
+  VBX_LAUNCH_CHECK();
+  return 0;
+}
+// Packed rows (include/vbx.h "packed rows"): one batch row of Mp rows, the workgroup of query tile t serves segment tile_seg[t].  The
+// three tables are device memory the kernel indexes by, so the CALLER validates them on the host before they get there
+// (sample_pack.check_tables); here only what the host sees.  Grid (Mp / 128) x H tiles in the XCD-aware order, fixed by (Mp, H).
+extern "C" int vbx_attn_fwd_segs(const void* q16, const void* k16, const void* v, const int* seg_start, const int* seg_klen,
+                                 const int* tile_seg, void* out, void* out_bf16, float* lse, int H, int Mp, float scale, void* stream) {
+  VBX_REQUIRE(q16 && k16 && v && out && lse && seg_start && seg_klen && tile_seg, "vbx_attn_fwd_segs: null pointer");
+  VBX_REQUIRE(H > 0 && Mp > 0 && Mp % VBX_PACK_ALIGN == 0 && scale > 0.f, "vbx_attn_fwd_segs: Mp must be a positive multiple of %d (got %d)",
+              VBX_PACK_ALIGN, Mp);
+  const int xmap = 1;  // XCD-local heads; Mp has no tail tile
+  dim3 grid((Mp / 128) * cdiv(H, 8) * 8);
+  hipLaunchKernelGGL(attn_fwd_kernel_v3_segs, grid, dim3(256), A3ST * ASTAGE, (hipStream_t)stream, (const u16*)q16, (const u16*)k16,
+                     (const u16*)v, (u16*)out, (u16*)out_bf16, lse, H, Mp, QK_UNIT, H, xmap, seg_start, seg_klen, tile_seg);
   VBX_LAUNCH_CHECK();
   return 0;
 }

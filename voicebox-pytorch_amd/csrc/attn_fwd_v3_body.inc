@@ -6,19 +6,49 @@
 // masked whatever `mask` says, so the key loop and the DMA ring stop at tile ceil(key_lens[b] / 64) -- a tile past it has maximum -inf
 // and probabilities 0, it would add +0 to l and O and leave m alone -- and a query tile wholly at or past key_lens[b] (padding
 // queries only) writes zeros and lse 1e30 without touching K or V.  Without the macro the text below is what it was.
+// With VBX_FWD_SEGS defined (packed rows, vbx_attn_fwd_segs; include/vbx.h "packed rows") there is ONE batch row of Np = Mp rows, a
+// multiple of 128, no `mask` parameter, and seg_start / seg_klen / tile_seg: the workgroup of query tile t serves segment
+// s = tile_seg[t] and walks ceil(seg_klen[s] / 64) key tiles from row seg_start[s]; key indices below are LOCAL to the segment, the
+// DMA never leaves its live rows (the partial tile re-reads row seg_klen[s] - 1), a query row at or past seg_klen[s] writes zeros
+// and lse 1e30, and so does a whole tile with s < 0.  There is no ragged tail role: every tile has 128 rows.
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, hi = lane >> 5;
   const AttnCoord co = attn_coord(H, Np, BH, xmap);
   if (!co.ok) return;
   ATTN_TRACE_BEGIN();
   const int h = co.h, b = co.b;
   const long bh = (long)b * H + h;
+#ifdef VBX_FWD_SEGS
+  const uint8_t* const mask = nullptr;
+  const int seg = tile_seg[co.tile];  // uniform over the workgroup, like everything read through it
+  const int sst = seg < 0 ? 0 : seg_start[seg];
+  const int kend = seg < 0 ? 0 : seg_klen[seg];
+  const u16* kbase = k16 + (bh * Np + sst) * 64;
+  const u16* vbase = vv + (bh * Np + sst) * 64;
+#define VBX_KROWS kend  // rows the K | V tile DMA may read, counted from kbase
+#else
   const u16* kbase = k16 + bh * Np * 64;
   const u16* vbase = vv + bh * Np * 64;
+#define VBX_KROWS Np
+#endif
   const int q0 = co.tile * 128 + wave * 32;
   const bool active = q0 < Np;
   const int q = q0 + (lane & 31);
   const int qc = min(q, Np - 1);
-#ifdef VBX_FWD_LENS
+#ifdef VBX_FWD_SEGS
+  const int ntiles = (kend + 63) / 64;
+  if (seg < 0) {
+    for (int i = tid; i < 128 * 8; i += 256) {
+      const int qq = co.tile * 128 + (i >> 3);
+      const long go = (long)qq * (H * 64) + h * 64 + (i & 7) * 8;
+      *reinterpret_cast<uint4*>(out + go) = make_uint4(0u, 0u, 0u, 0u);
+      if (outb) *reinterpret_cast<uint4*>(outb + go) = make_uint4(0u, 0u, 0u, 0u);
+      if ((i & 7) == 0) lse[bh * Np + qq] = 1e30f;
+    }
+    ATTN_TRACE_END(0);
+    return;
+  }
+  const bool qdead = q - sst >= kend;  // a dead row of the segment: zeros and lse 1e30, whatever its q holds
+#elif defined(VBX_FWD_LENS)
   const int kend = min(max(key_lens[b], 0), Np);  // uniform over the workgroup
   const int ntiles = (kend + 63) / 64;
   if (co.tile * 128 >= kend) {
@@ -50,8 +80,8 @@
   const unsigned m0b = __builtin_amdgcn_readfirstlane(lds_addr32(smem) + (unsigned)(tid & ~63) * 16u);
   auto dma_kv = [&](unsigned slot_off, int kt) {
     unsigned o0 = dvo[0], o1 = dvo[1];
-    if ((kt + 1) * 64 > Np) {  // the last, partial tile: rows past the end re-read the last row (masked, never stored)
-      const unsigned lim = (unsigned)(Np - 1 - kt * 64);
+    if ((kt + 1) * 64 > VBX_KROWS) {  // the last, partial tile: rows past the end re-read the last row (masked, never stored)
+      const unsigned lim = (unsigned)(VBX_KROWS - 1 - kt * 64);
       o0 -= ((o0 >> 7) - min(o0 >> 7, lim)) << 7;
       o1 -= ((o1 >> 7) - min(o1 >> 7, lim)) << 7;
     }
@@ -64,7 +94,7 @@
   };
   dma_kv(0u, 0);
 
-#ifndef VBX_FWD_DROP
+#if !defined(VBX_FWD_DROP) && !defined(VBX_FWD_SEGS)
   // ---- ragged tail tile (round 6): <= 16 query rows (the 16 register tokens at the benchmark's Np = 1040).  Such a workgroup used to
   // walk the key loop with one active wave of 32-query blocks: 26 us of life for 1/8 of a wave's work.  Here its four waves split
   // every 64-key tile into 16-key blocks and run 16 x 16 MFMA shapes on the 16 queries -- S^T[16 keys][16 q] = 2 x 16x16x32,
@@ -153,7 +183,7 @@
     asm_read_tr<SO>(vl[1], vh[1], va[1], va8[1]);
     asm_read_tr<SO + 2048>(vl[2], vh[2], va[0], va8[0]);
     asm_read_tr<SO + 2048>(vl[3], vh[3], va[1], va8[1]);
-#ifdef VBX_FWD_LENS
+#if defined(VBX_FWD_LENS) || defined(VBX_FWD_SEGS)
     const bool need_mask = (mask != nullptr) || (k0 + 64 > kend);
 #else
     const bool need_mask = (mask != nullptr) || (k0 + 64 > Np);
@@ -164,7 +194,7 @@
 #pragma unroll
         for (int r = 0; r < 16; r++) {
           const int kg = k0 + kb * 32 + acc_row(r, hi);
-#ifdef VBX_FWD_LENS
+#if defined(VBX_FWD_LENS) || defined(VBX_FWD_SEGS)
           bool ok = kg < kend;
 #else
           bool ok = kg < Np;
@@ -259,7 +289,11 @@
 #else
   const float inv = (l_tot > 0.f) ? 1.0f / l_tot : 0.f;
 #endif
+#ifdef VBX_FWD_SEGS
+  if (hi == 0) lse[bh * Np + q] = (l_tot > 0.f && !qdead) ? (m_run + log2f(l_tot)) : 1e30f;
+#else
   if (active && hi == 0 && q < Np) lse[bh * Np + q] = (l_tot > 0.f) ? (m_run + log2f(l_tot)) : 1e30f;
+#endif
   char* ost = smem + wave * 8192;
   if (active) {
     const int ql = lane & 31;
@@ -268,8 +302,13 @@
 #pragma unroll
       for (int g4 = 0; g4 < 4; g4++) {
         const int d = db * 32 + 8 * g4 + 4 * hi;
+#ifdef VBX_FWD_SEGS
+        const float v0 = qdead ? 0.f : o[db][4 * g4 + 0] * inv, v1 = qdead ? 0.f : o[db][4 * g4 + 1] * inv,
+                    v2 = qdead ? 0.f : o[db][4 * g4 + 2] * inv, v3 = qdead ? 0.f : o[db][4 * g4 + 3] * inv;
+#else
         const float v0 = o[db][4 * g4 + 0] * inv, v1 = o[db][4 * g4 + 1] * inv, v2 = o[db][4 * g4 + 2] * inv,
                     v3 = o[db][4 * g4 + 3] * inv;
+#endif
         const int off = ql * 128 + ((((d >> 3) ^ (ql & 7))) << 4) + (d & 7) * 2;
         *reinterpret_cast<uint2*>(ost + off) = make_uint2(pack_f16x2(v0, v1), pack_f16x2(v2, v3));
         if (outb) *reinterpret_cast<uint2*>(ost + 4096 + off) = make_uint2(pack_bf16x2(v0, v1), pack_bf16x2(v2, v3));
@@ -289,4 +328,5 @@
       }
     }
   }
+#undef VBX_KROWS
   ATTN_TRACE_END(0);

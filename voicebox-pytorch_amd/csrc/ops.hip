@@ -234,6 +234,62 @@ __global__ __launch_bounds__(256) void convpos_fwd_kernel(const float* __restric
   }
 }
 
+// conv_embed over packed rows (include/vbx.h "packed rows"): block (c, dy) owns the 64 packed rows of chunk c -- all inside segment
+// tile_seg[c / 2], segments being 128-aligned -- and 64 channels.  Row l of the segment is a register (l < R: the parameter), frame
+// n = l - R (n < len: e + GELU(conv), taps outside 0 <= n < len read 0) or dead (exactly 0); register and dead rows of e are never
+// read.  Tap order, accumulation and GELU are convpos_fwd_kernel<0, KS>'s, so a frame gets the bits of that kernel on the row alone.
+template <int KS>
+__global__ __launch_bounds__(256) void convpos_fwd_segs_kernel(const float* __restrict__ e, const float* __restrict__ w,
+                                                               const float* __restrict__ bias, const float* __restrict__ reg,
+                                                               const int* __restrict__ seg_start, const int* __restrict__ seg_klen,
+                                                               const int* __restrict__ tile_seg, float* __restrict__ out, int R, int D) {
+  extern __shared__ float tile[];  // [(CT + ks - 1)][64]
+  constexpr int ks = KS;
+  const int half = ks / 2;
+  const int r0 = blockIdx.x * CT, dbase = blockIdx.y * 64;
+  const int dl = threadIdx.x & 63, ng = threadIdx.x >> 6;
+  const int d = dbase + dl;
+  const int seg = tile_seg[blockIdx.x >> 1];
+  if (seg < 0) {  // past the last segment: dead rows
+    if (d < D)
+      for (int i = 0; i < 16; i++) out[(long)(r0 + ng * 16 + i) * D + d] = 0.f;
+    return;
+  }
+  const int sst = seg_start[seg], N = seg_klen[seg] - R;  // N: frames of this segment
+  const long f0 = (long)sst + R;                            // packed row of frame 0
+  const int n0 = r0 - sst - R;                              // frame index of the chunk's first row (negative inside the registers)
+  const int rows = CT + ks - 1;
+  for (int r = ng; r < rows; r += 4) {
+    const int n = n0 + r - half;
+    float v = 0.f;
+    if (n >= 0 && n < N && d < D) v = e[(f0 + n) * D + d];
+    tile[r * 64 + dl] = v;
+  }
+  __syncthreads();
+  if (d >= D) return;
+  float wr[KS];
+#pragma unroll
+  for (int k = 0; k < ks; k++) wr[k] = w[(long)d * ks + k];
+  const float bb = bias[d];
+  for (int i = 0; i < 16; i++) {
+    const int nl = ng * 16 + i, n = n0 + nl;
+    float* dst = out + (long)(r0 + nl) * D + d;
+    if (n < 0) { *dst = reg[(long)(n + R) * D + d]; continue; }
+    if (n >= N) { *dst = 0.f; continue; }
+    // convpos_fwd_kernel's `acc += w * x` compiles to one fused multiply-add per tap, in tap order (default contraction); here the
+    // same chain is spelled out, so that unrolling over the 16 rows cannot pair the multiplies up (v_pk_mul_f32) and round them
+    float acc = bb;
+#pragma unroll
+    for (int k = 0; k < ks; k++) acc = __builtin_fmaf(wr[k], tile[(nl + k) * 64 + dl], acc);
+    const float ev = e[(f0 + n) * D + d], gl = gelu_erf(acc);
+    {
+      // convpos_fwd_kernel adds a select (mask ? gelu : 0), which keeps the GELU's last multiply out of this add: no fma here either
+#pragma clang fp contract(off)
+      *dst = ev + gl;
+    }
+  }
+}
+
 // standalone Transformer.forward (voicebox_pytorch.py:412-431): rows n >= R of the residual stream = the caller's x
 __global__ void stack_rows_kernel(const float* __restrict__ src, float* __restrict__ dst, int B, int N, int R, int D, int to_stack) {
   // to_stack = 1: dst[b, R+n, :] = src[b, n, :] ([B,N,D] -> [B,N+R,D]);  0: dst[b, n, :] = src[b, R+n, :]
@@ -1701,6 +1757,24 @@ extern "C" int vbx_convpos_fwd(const float* e, const float* w, const float* bias
 extern "C" int vbx_convpos_fwd_libm(const float* e, const float* w, const float* bias, const uint8_t* mask, const float* reg,
                                     float* xs, int B, int N, int R, int D, int ksize, void* stream) {
   return convpos_fwd_impl(e, w, bias, mask, reg, xs, B, N, R, D, ksize, true, stream);
+}
+
+// packed rows: the tables are device memory the kernel indexes by; the caller validated them on the host (include/vbx.h)
+extern "C" int vbx_convpos_fwd_segs(const float* e, const float* w, const float* bias, const float* reg, const int* seg_start,
+                                    const int* seg_klen, const int* tile_seg, float* xs, int Mp, int R, int D, int ksize, void* stream) {
+  VBX_REQUIRE(e && w && bias && xs && seg_start && seg_klen && tile_seg, "vbx_convpos_fwd_segs: null pointer");
+  VBX_REQUIRE(conv_ks_ok(ksize), "vbx_convpos_fwd_segs: conv_pos_embed_kernel_size must be odd and <= 31 (got %d)", ksize);
+  VBX_REQUIRE(Mp > 0 && Mp % VBX_PACK_ALIGN == 0 && D > 0 && R >= 0 && R < VBX_PACK_ALIGN && (R == 0 || reg),
+              "vbx_convpos_fwd_segs: Mp must be a positive multiple of %d, 0 <= R < %d with the register tokens given (Mp %d, R %d)",
+              VBX_PACK_ALIGN, VBX_PACK_ALIGN, Mp, R);
+  dim3 grid(Mp / CT, cdiv(D, 64));
+#define VBX_CALL(KS)                                                                                                               \
+  hipLaunchKernelGGL(convpos_fwd_segs_kernel<KS>, grid, dim3(256), (CT + KS - 1) * 64 * sizeof(float), ST, e, w, bias, reg, seg_start, \
+                     seg_klen, tile_seg, xs, R, D)
+  VBX_CONV_KS_SWITCH(ksize, VBX_CALL)
+#undef VBX_CALL
+  VBX_LAUNCH_CHECK();
+  return 0;
 }
 
 extern "C" int vbx_stack_input(const float* x, const float* reg, float* xs, int B, int N, int R, int D, void* stream) {

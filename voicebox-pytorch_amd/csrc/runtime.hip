@@ -45,7 +45,9 @@ struct Dims {
 };
 Dims dims_of(const vbx_model* m) {
   Dims d;
-  d.B = m->B; d.N = m->N; d.R = m->R; d.Np = m->N + m->R; d.D = m->D; d.H = m->H; d.I = m->H * 64;
+  // packed rows (vbx_model.packed): the registers sit inside the segments of the N = Mp rows, so Np = N and M0 = M; R stays the
+  // model's, for vbx_convpos_fwd_segs alone
+  d.B = m->B; d.N = m->N; d.R = m->R; d.Np = m->packed ? m->N : m->N + m->R; d.D = m->D; d.H = m->H; d.I = m->H * 64;
   d.Din = m->Din > 0 ? m->Din : m->D;
   d.E = m->E; d.Ke = 2 * d.Din + m->E;
   d.Lc = m->Lc; d.Kp = d.Lc ? vbx_proj_in_kp(d.Lc) : 0;
@@ -468,6 +470,14 @@ int check_model(const vbx_model* m) {
   VBX_REQUIRE(m->attn_dropout >= 0.f && m->attn_dropout < 1.f && m->ff_dropout >= 0.f && m->ff_dropout < 1.f, "vbx_model: dropout must be in [0, 1)");
   VBX_REQUIRE(!m->unet || (m->stack_only && m->L % 2 == 0 && !m->precise),
               "vbx_model: u-net skip connections belong to the standalone stack (even depth); VoiceBox never enables them");
+  if (m->packed) {
+    VBX_REQUIRE(m->B == 1 && m->N % VBX_PACK_ALIGN == 0 && m->R < VBX_PACK_ALIGN,
+                "vbx_model: packed rows run as one batch row of N = Mp rows, a multiple of %d (got B %d, N %d)", VBX_PACK_ALIGN, m->B, m->N);
+    VBX_REQUIRE(!m->training && !m->precise && !m->gateloop && !m->stack_only,
+                "vbx_model: packed rows serve the fast-path inference forward of VoiceBox only -- not training, precise mode, GateLoop "
+                "layers (the scan has no segment reset) or the standalone stack (training %d, precise %d, gateloop %d, stack_only %d)",
+                m->training, m->precise, m->gateloop, m->stack_only);
+  }
   return 0;
 }
 
@@ -584,6 +594,13 @@ extern "C" int vbx_model_forward(const vbx_model* m, const vbx_io* io, void* str
   VBX_REQUIRE(!io->target || (io->loss_mask && io->loss), "vbx_model_forward: target needs loss_mask and loss");
   VBX_REQUIRE((io->attn_mask == nullptr) == (io->attn_mask_p == nullptr), "vbx_model_forward: attn_mask and attn_mask_p go together");
   VBX_REQUIRE(!io->key_lens || io->attn_mask_p, "vbx_model_forward: key_lens restates a prefix attn_mask_p, which must be given too");
+  if (m->packed) {  // (training / precise / gateloop / stack_only: check_model)
+    VBX_REQUIRE(!io->attn_mask && !io->attn_mask_p && !io->key_lens && !io->target,
+                "vbx_model_forward: packed rows take no attn_mask, key_lens or target -- the segment tables say which rows are live");
+    VBX_REQUIRE(io->seg_start && io->seg_klen && io->tile_seg, "vbx_model_forward: packed rows need seg_start, seg_klen and tile_seg");
+  } else {
+    VBX_REQUIRE(!io->seg_start && !io->seg_klen && !io->tile_seg, "vbx_model_forward: segment tables belong to a packed model (vbx_model.packed)");
+  }
   hipStream_t st = (hipStream_t)stream;
   const Dims d = dims_of(m);
   WPack w;
@@ -640,6 +657,10 @@ extern "C" int vbx_model_forward(const vbx_model* m, const vbx_io* io, void* str
   CK(gemm_nt(a.embed_inh, d.Ke, w.embh, d.Ke, (int)d.M0, d.D, d.Ke, VBX_EPI_F32, a.e, d.D, P + G[VBX_P_EMBB], nullptr,
              nullptr, nullptr, st));
   // conv_embed(x) + x, register tokens in place   (:1080, :422-425)
+  if (m->packed)  // the same over the segments of the packed rows: registers, frames and dead rows in place
+    CK(vbx_convpos_fwd_segs(a.e, P + G[VBX_P_CONVW], P + G[VBX_P_CONVB], d.R ? P + G[VBX_P_REG] : nullptr, io->seg_start, io->seg_klen,
+                            io->tile_seg, a.xs[0], d.N, d.R, d.D, d.ks, stream));
+  else
   CK(vbx_convpos_fwd(a.e, P + G[VBX_P_CONVW], P + G[VBX_P_CONVB], io->attn_mask, d.R ? P + G[VBX_P_REG] : nullptr, a.xs[0],
                      d.B, d.N, d.R, d.D, d.ks, stream));
   }
@@ -687,7 +708,9 @@ extern "C" int vbx_model_forward(const vbx_model* m, const vbx_io* io, void* str
                               m->attn_dropout, stream));
     } else {
       ProfScope ps("fwd attention", st);
-      if (io->key_lens && !m->training)  // the sampler's prefix lengths: dead key tiles are not walked (bit-equal on live queries)
+      if (m->packed)  // packed rows: every query tile against the live keys of its own segment
+        CK(vbx_attn_fwd_segs(y.q16, y.k16, y.vh, io->seg_start, io->seg_klen, io->tile_seg, y.oh, y.o, y.lse, d.H, d.Np, m->attn_scale, stream));
+      else if (io->key_lens && !m->training)  // the sampler's prefix lengths: dead key tiles are not walked (bit-equal on live queries)
         CK(vbx_attn_fwd_lens(y.q16, y.k16, y.vh, io->attn_mask_p, io->key_lens, y.oh, y.o, y.lse, d.B, d.H, d.Np, m->attn_scale, stream));
       else
         CK(vbx_attn_fwd(y.q16, y.k16, y.vh, io->attn_mask_p, y.oh, y.o, y.lse, d.B, d.H, d.Np, m->attn_scale, stream));
@@ -710,7 +733,9 @@ extern "C" int vbx_model_forward(const vbx_model* m, const vbx_io* io, void* str
     return vbx_rmsnorm_fwd_f32(a.xs[(m->gateloop ? 3 : 2) * d.L], P + G[VBX_P_FNG], nullptr, 0, io->pred, d.B, d.Np, d.R, d.N, d.D,
                                stream);
   // strip registers, final RMSNorm, to_pred   (:476-479, :1092)
-  CK(vbx_rmsnorm_fwd(a.xs[(m->gateloop ? 3 : 2) * d.L], P + G[VBX_P_FNG], nullptr, 0, a.hf, a.hfh, d.B, d.Np, d.R, d.N, d.D, stream));
+  // (packed rows: nothing to strip -- all Mp rows go through the norm and to_pred, the caller reads the frame rows)
+  CK(vbx_rmsnorm_fwd(a.xs[(m->gateloop ? 3 : 2) * d.L], P + G[VBX_P_FNG], nullptr, 0, a.hf, a.hfh, d.B, d.Np, m->packed ? 0 : d.R, d.N, d.D,
+                     stream));
   if (d.Dop != d.Do) {  // a latent width that is not a multiple of 8: the product lands in padded rows of the arena
     CK(gemm_nt(a.hfh, d.D, w.predh, d.D, (int)d.M0, d.Dop, d.D, VBX_EPI_F32, a.pred, d.Dop, nullptr, nullptr, nullptr, nullptr, st));
     if (io->pred) CK(vbx_copy_cols_f32(a.pred, d.Dop, io->pred, d.M0, d.Do, stream));

@@ -21,14 +21,16 @@ class VbxModel(C.Structure):
                 ("qk_norm", I), ("attn_scale", F), ("training", I), ("params", P), ("grads", P), ("off", P),
                 ("wpack", P), ("act", P), ("rot_cos", P), ("rot_sin", P), ("gateloop", I),
                 ("stack_only", I), ("E", I), ("V1", I), ("plain_norm", I), ("attn_dropout", F), ("ff_dropout", F), ("Din", I),
-                ("precise", I), ("wpack3", P), ("pscratch", P), ("unet", I), ("skip_scale", F), ("adaln_factors", I), ("defer_reduce", I), ("sq_partials", P), ("Lc", I)]
+                ("precise", I), ("wpack3", P), ("pscratch", P), ("unet", I), ("skip_scale", F), ("adaln_factors", I), ("defer_reduce", I), ("sq_partials", P), ("Lc", I),
+                ("packed", I)]
 
 
 class VbxIO(C.Structure):
     _fields_ = [("x", P), ("cond", P), ("cond_mask", P), ("attn_mask", P), ("attn_mask_p", P), ("loss_mask", P),
                 ("times", P), ("target", P), ("pred", P), ("loss", P), ("cond_ids", P), ("T", I), ("null_id", C.c_long),
                 ("drop_mask", P), ("null_cond", P), ("dx", P), ("dcond", P), ("dropout", I), ("drop_seed", C.c_ulonglong),
-                ("ada_table", P), ("ada_counter", P), ("ada_slot", I), ("ada_stride", I), ("key_lens", P)]
+                ("ada_table", P), ("ada_counter", P), ("ada_slot", I), ("ada_stride", I), ("key_lens", P),
+                ("seg_start", P), ("seg_klen", P), ("tile_seg", P)]
 
 
 class VbxAdamSeg(C.Structure):
@@ -230,12 +232,19 @@ class Engine:
     """One (batch, frames, training) configuration of a VoiceBox on one GPU: owns the packed-weight and
     activation arenas and issues the native stage calls on the current HIP stream."""
 
-    def __init__(self, cfg, flat: FlatParams, B, N, training, device, wpack_from=None, precise=False):
+    def __init__(self, cfg, flat: FlatParams, B, N, training, device, wpack_from=None, precise=False, packed=False):
         """wpack_from: another Engine of the same model whose packed-weight arena this one shares (the arena depends on the
         architecture only): the concurrent half-batch engines of the sampler keep ONE copy of the operand weights.
-        precise: the exact-operand forward (csrc/precise.hip): two more arenas (split weights, fp32 intermediates)."""
+        precise: the exact-operand forward (csrc/precise.hip): two more arenas (split weights, fp32 intermediates).
+        packed: packed rows (include/vbx.h "packed rows"; inference): B = 1, N = Mp; rot_cos / rot_sin are static [Mp, 32] buffers in
+        the packed order, refreshed by load_packed_rotary, and forward() takes the segment tables (segs=)."""
         self.cfg, self.fp, self.B, self.N, self.training, self.device = cfg, flat, B, N, bool(training), device
         self.precise = bool(precise)
+        self.packed = bool(packed)
+        if self.packed:
+            assert B == 1 and N % 128 == 0 and not training and not precise, (B, N, training, precise)
+            if cfg.get("gateloop") or cfg.get("stack_only"):
+                raise NotImplementedError("packed rows do not serve GateLoop layers (the scan has no segment reset) or the standalone stack")
         self.wpack_owner = wpack_from
         _lib.call("vbx_check_device", device.index if device.index is not None else torch.cuda.current_device())
         l = _rt()
@@ -260,7 +269,12 @@ class Engine:
         self.dropout_active = False  # nn.Dropout semantics: the owning module sets this to its .training flag before a forward
         self.off_table = flat.offset_table()
         m.off = C.cast(self.off_table, P)
-        self.rot_cos, self.rot_sin = rotary_tables(N, cfg["R"], 64, cfg["theta"], device)
+        if self.packed:
+            m.packed = 1
+            self.rot_cos, self.rot_sin = (torch.zeros(N, 32, dtype=torch.float32, device=device) for _ in range(2))
+            self._rot_base = None  # (frames, cos, sin) of the unpacked [R + frames, 32] tables the packed ones are gathered from
+        else:
+            self.rot_cos, self.rot_sin = rotary_tables(N, cfg["R"], 64, cfg["theta"], device)
         m.rot_cos, m.rot_sin = self.rot_cos.data_ptr(), self.rot_sin.data_ptr()
         self.m = m
         if wpack_from is not None:
@@ -430,8 +444,18 @@ class Engine:
         self.packed_version = self.fp.weights_key()  # this engine's operand copies were refreshed in the same pass
 
     # -- forward
+    def load_packed_rotary(self, local_row, frames):
+        """Packed engines: refresh the static rot_cos / rot_sin [Mp, 32] by copy -- row r takes row local_row[r] of the unpacked tables
+        rotary_tables(frames, R, ...), the row's own position inside its segment (registers -10000, frame n at n; dead rows row 0)."""
+        assert self.packed and local_row.shape == (self.N,)
+        if self._rot_base is None or self._rot_base[0] < frames:
+            self._rot_base = (frames,) + rotary_tables(frames, self.cfg["R"], 64, self.cfg["theta"], self.device)
+        idx = local_row.to(self.device)
+        torch.index_select(self._rot_base[1], 0, idx, out=self.rot_cos)
+        torch.index_select(self._rot_base[2], 0, idx, out=self.rot_sin)
+
     def forward(self, x, cond, cond_mask, times, attn_mask=None, target=None, loss_mask=None, pred_out=None, text=None, ada=None,
-                attn_mask_p=None, key_lens=None):
+                attn_mask_p=None, key_lens=None, segs=None):
         """All tensors on self.device, fp32 contiguous / bool.  Returns the loss tensor (1,) if target is given,
         else the prediction (B,N,D).  text (text-conditioned models): (ids int64 (B,T), null_id, drop_mask bool (B,) or None,
         null_cond fp32 (D,)).  ada (inference, the sampler): (table fp32 [stride * intervals, L, 4 * D], counter int32 [1], slot, stride) --
@@ -459,6 +483,12 @@ class Engine:
         io.attn_mask = am.data_ptr() if am is not None else None
         io.attn_mask_p = amp.data_ptr() if amp is not None else None
         io.key_lens = key_lens.data_ptr() if key_lens is not None else None
+        # packed rows: (seg_start, seg_klen, tile_seg) int32 device tables, validated on the host by their owner (sample_pack.check_tables)
+        assert (segs is not None) == self.packed, "a packed engine runs with its segment tables, any other without"
+        if segs is not None:
+            assert am is None and key_lens is None and target is None and segs[2].shape == (N // 128,)
+            assert all(t.dtype == torch.int32 and t.is_contiguous() and t.device == x.device for t in segs)
+            io.seg_start, io.seg_klen, io.tile_seg = (t.data_ptr() for t in segs)
         io.times = times.data_ptr()
         if ada is not None:
             assert target is None and not self.training

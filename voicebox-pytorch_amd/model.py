@@ -478,9 +478,9 @@ class VoiceBox(nn.Module):
             self._engines.clear()
         return self._flat
 
-    def engine(self, B, N, training, slot=0, wpack_from=None):
+    def engine(self, B, N, training, slot=0, wpack_from=None, packed=False):
         """slot > 0: a further engine (own activation arena) for the same shape -- the sampler integrates the halves of a
-        batch concurrently on two streams."""
+        batch concurrently on two streams.  packed: the engine of a packed row stream (sample(pack=True); B = 1, N = Mp rows)."""
         fp = self.flat_params()
         dev = fp.flat.device
         if dev.type != "cuda":
@@ -493,6 +493,12 @@ class VoiceBox(nn.Module):
         # key[2] carries the mode: 0/1 = inference/training on the fast path, 2/3 = the same in precise mode (own arenas)
         tkey = int(bool(training)) + (2 if precise else 0)
         key = (B, N, tkey) if slot == 0 else (B, N, tkey, slot)
+        if packed:
+            if precise:
+                raise NotImplementedError("precise mode does not serve packed rows (sample(pack=True)) -- leave precise mode, or call "
+                                          "sample(lens=) without pack")
+            assert B == 1 and slot == 0 and wpack_from is None and not training
+            key = ("packed", N, tkey)  # an owner key (length 3) of its own: never the engine of an unpacked (1, N) call
         eng = self._engines.get(key)
         if eng is not None and eng.wpack_owner is not wpack_from:
             eng = None
@@ -506,7 +512,7 @@ class VoiceBox(nn.Module):
                 victim = next(k for k in owners if self._engines[k] is not wpack_from)
                 for k in [k for k in self._engines if k[:3] == victim]:
                     self._engines.pop(k)
-            eng = Engine(self._cfg, fp, B, N, training, dev, wpack_from=wpack_from, precise=precise)
+            eng = Engine(self._cfg, fp, B, N, training, dev, wpack_from=wpack_from, precise=precise, packed=packed)
             self._engines[key] = eng
         eng.dropout_active = self.training  # nn.Dropout semantics (attend.py:131, voicebox_pytorch.py:346): the module's mode
         return eng
@@ -654,7 +660,8 @@ class ConditionalFlowMatcherWrapper(nn.Module):
     @torch.inference_mode()
     def sample(self, *, cond=None, texts=None, text_token_ids=None, semantic_token_ids=None, phoneme_ids=None,
                cond_mask=None, steps=3, cond_scale=1., decode_to_audio=True, decode_to_codes=False,
-               max_semantic_token_ids=2048, spec_decode=False, spec_decode_gamma=5, use_graph=True, lens=None, length_bucket=None):
+               max_semantic_token_ids=2048, spec_decode=False, spec_decode_gamma=5, use_graph=True, lens=None, length_bucket=None,
+               pack=False, pack_bucket=None):
         """voicebox_pytorch.py:1175-1330 with torchdiffeq.odeint replaced by the built-in device solvers (solver.py), per
         torchdiffeq_ode_method: 'midpoint' (the default), 'euler' and 'rk4' on the fixed grid linspace(0, 1, steps) -- 2, 1 and 4
         function evaluations per interval -- or the adaptive 'dopri5' with ode_atol / ode_rtol (steps does not change its result).
@@ -666,12 +673,39 @@ class ConditionalFlowMatcherWrapper(nn.Module):
         of a wave is codec.decode(latents[b:b+1, :len_b]), zero-filled to the longest).  self.last_sample_lens: the per-row output
         lengths.  lens="durations" (phoneme_ids + duration_predictor): len_b is the sum of the predicted durations of row b's
         phonemes, and -1 padding phonemes get no frames.  length_bucket (with lens): the sampler runs at N rounded up to a multiple
-        of it, the extra frames masked like any padding, so that calls whose N share a bucket share one sampler and one graph."""
+        of it, the extra frames masked like any padding, so that calls whose N share a bucket share one sampler and one graph.
+
+        pack=True (with lens; opt-in): the same call and the same result contract, but the batch runs as ONE packed row stream of
+        Mp = sum_b align(R + len_b, 128) rows (sample_pack.py, include/vbx.h "packed rows") -- padding frames go through no GEMM, norm
+        or attention tile, and attention walks each row's own keys without a mask.  euler / midpoint / rk4, eager or captured, one
+        stream; guidance, one-id-per-frame text and codec-latent models are served; dopri5, GateLoop layers and precise mode are not
+        (NotImplementedError).  pack_bucket (a multiple of 128): Mp is rounded up to a multiple of it and the sampler is keyed by that
+        Mp alone, so calls of different B, N and lengths that land in one bucket share one sampler and one captured graph.
+        self.last_sample_stats gains packed_rows, live_rows and padded_rows."""
         from .solver import make_sampler
         from .sample_lens import bucketed, decode_rows, durations_lens, mask_codes, pad_frames, validate_lens
+        from .sample_pack import check_pack_bucket
 
         if exists(length_bucket) and not exists(lens):
             raise ValueError("length_bucket needs lens: without lengths the frames added up to the bucket could not be masked")
+        if pack and not exists(lens):
+            raise ValueError("pack=True needs lens: the packed layout is built from the per-row lengths -- pass lens=, or drop pack")
+        if exists(pack_bucket) and not pack:
+            raise ValueError("pack_bucket only applies to pack=True -- pass pack=True, or use length_bucket with lens= alone")
+        if pack:
+            check_pack_bucket(pack_bucket)
+            if exists(length_bucket):
+                raise ValueError("length_bucket pads frames that pack=True would drop again -- with pack=True bucket the packed rows "
+                                 "with pack_bucket instead")
+            method = self.odeint_kwargs["method"]
+            if method == "dopri5":
+                raise NotImplementedError("dopri5 does not serve pack=True: its error norm would have to leave the dead rows out and "
+                                          "vbx_ode_norm_lens is laid out for [B, N] -- use euler, midpoint or rk4, or lens= without pack")
+            if self.voicebox._cfg.get("gateloop"):
+                raise NotImplementedError("GateLoop layers do not serve pack=True: the scan has no segment reset -- call sample(lens=) "
+                                          "without pack")
+            if precise_enabled():
+                raise NotImplementedError("precise mode does not serve pack=True -- leave precise mode, or call sample(lens=) without pack")
         if isinstance(lens, str) and (lens != "durations" or not exists(phoneme_ids) or not exists(self.duration_predictor)):
             raise ValueError(f"lens={lens!r}: the only named source of lengths is 'durations', on the phoneme_ids + duration_predictor path")
 
@@ -726,6 +760,10 @@ class ConditionalFlowMatcherWrapper(nn.Module):
         if masked:
             lens = validate_lens(lens, B, N)  # the one host read of lens: int32 CPU [B]
             assert not exists(cond_token_ids) or cond_token_ids.shape[-1] == N, "under lens there is one token id per frame"
+        if pack:
+            return self._sample_packed(cond, y0, cond_mask, cond_token_ids, lens, steps, cond_scale, use_graph, pack_bucket, codec,
+                                       decode_to_audio, decode_to_codes)
+        if masked:
             N = bucketed(N, length_bucket)
             if N != n_out:  # the frames up to the bucket are padding of every row; y0 was drawn at n_out, so a draw does not depend on them
                 cond, y0, cond_mask, cond_token_ids = pad_frames(N, cond, y0, cond_mask, cond_token_ids)
@@ -759,6 +797,42 @@ class ConditionalFlowMatcherWrapper(nn.Module):
         if not decode_to_audio or not exists(codec):
             return out
         return codec.decode(out)
+
+    def _sample_packed(self, cond, y0, cond_mask, cond_token_ids, lens, steps, cond_scale, use_graph, pack_bucket, codec, decode_to_audio,
+                       decode_to_codes):
+        """sample(lens=, pack=True) from the validated inputs on: cond / y0 [B, N, .] (y0 drawn at [B, N], so a seed gives the masked
+        and the packed path the same noise), lens int32 CPU [B].  pack_rows / unpack_rows run once before and once after the ODE loop,
+        outside the captured interval; the sampler is keyed by the packed row count, not by (B, N)."""
+        from .solver import make_sampler
+        from .sample_lens import decode_rows, mask_codes
+        from .sample_pack import pack_plan, pack_rows, unpack_rows
+
+        B, N, _ = cond.shape
+        plan = pack_plan(lens, self.voicebox._cfg["R"], pack_bucket, N=N)
+        tokens, method, guided = exists(cond_token_ids), self.odeint_kwargs["method"], float(cond_scale) != 1.
+        Mp = plan.Mp
+        key = ("packed", Mp, steps, bool(use_graph), bool(tokens), guided, method)
+        fp = self.voicebox.flat_params()
+        self._samplers = {k: s for k, s in self._samplers.items() if s.flat_gen == fp.flat_gen and s.eng.fp is fp}
+        smp = self._samplers.get(key)
+        if smp is None:
+            if len(self._samplers) >= 2:
+                self._samplers.pop(next(iter(self._samplers)))
+            smp = self._samplers[key] = make_sampler(method, self.voicebox, 1, Mp, steps, use_graph=use_graph, tokens=Mp if tokens else 0,
+                                                     guided=guided, packed=True)
+        dev = cond.device
+        out = smp.run(pack_rows(y0, plan), pack_rows(cond, plan),
+                      pack_rows(cond_mask.to(dev, torch.bool), plan, fill=True) if exists(cond_mask) else None,
+                      cond_token_ids=pack_rows(cond_token_ids, plan) if tokens else None, cond_scale=float(cond_scale), plan=plan)
+        out = unpack_rows(out, plan)  # [B, N, .], exactly 0.0 past len_b
+        self.last_sample_stats = dict(smp.stats(), packed_rows=plan.Mp, live_rows=plan.live_rows, padded_rows=plan.padded_rows)
+        self.last_sample_lens = lens.to(torch.int64)
+        if decode_to_codes and exists(codec):
+            return mask_codes(codec.decode_to_codes(out.contiguous()), lens)
+        if not decode_to_audio or not exists(codec):
+            return out.contiguous()
+        wave, self.last_sample_lens = decode_rows(codec, out, lens)
+        return wave
 
     def encode_raw_audio(self, x1, cond=None, input_sampling_rate=None):
         """voicebox_pytorch.py:1349-1371: a 2-D tensor, or a 3-D one with a middle dimension of 1, is a wave -- encoded by the codec

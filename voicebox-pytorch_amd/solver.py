@@ -35,6 +35,13 @@ rest and refreshed by _load_inputs, which also writes "masked" / 0 into cond_mas
 forward of _eval gets the mask (convolutional position embedding, attention) and the key lengths (vbx_attn_fwd_lens: dead key tiles
 are not walked); dopri5's error norm leaves the padding out (vbx_ode_norm_lens); the returned state is zeroed past the lengths.  The
 rows of padding frames still go through the GEMMs and norms.  An unmasked sampler passes none of this and launches what it always did.
+
+Packed rows (packed=True, run(plan=); sample(lens=, pack=True)).  The ragged batch is ONE batch row of N = Mp rows (sample_pack.py,
+include/vbx.h "packed rows"): B = 1, one stream, a packed engine, not masked.  The caller packs y0 / cond / cond_mask / ids before
+run() and unpacks the result after it, outside the captured interval; the sampler owns the static tables seg_start / seg_klen /
+tile_seg (capacity Mp / 128 segments), which _load_inputs validates on the host (sample_pack.check_tables) and refreshes by copy
+together with the engine's packed rotary tables, and every forward of _eval gets them (vbx_convpos_fwd_segs, vbx_attn_fwd_segs).
+All rows share the time point, so B = 1 in the adaLN table is exact.  Fixed-grid methods only.
 """
 import contextlib
 import ctypes as _C
@@ -72,8 +79,11 @@ class _Sampler:
     knows its time points up front: self.t_table, and the adaLN projections of all of them are tabulated (self.ada_tab, row
     ada_stride * counter + slot).  grid = None: every forward evaluates its own projections from p.times."""
 
-    def __init__(self, voicebox, B, N, use_graph=True, tokens=0, guided=False, split=None, grid=None, masked=False):
-        self.vb, self.B, self.N, self.masked = voicebox, B, N, bool(masked)
+    def __init__(self, voicebox, B, N, use_graph=True, tokens=0, guided=False, split=None, grid=None, masked=False, packed=False):
+        self.vb, self.B, self.N, self.masked, self.packed = voicebox, B, N, bool(masked), bool(packed)
+        if self.packed:  # one batch row of N = Mp packed rows on one stream; the segment tables say which rows are live
+            assert B == 1 and N % 128 == 0 and not masked, (B, N, masked)
+            split = 1
         if split is None:
             # Default: two concurrent half batches -- EXCEPT where the weight-stationary kernel serves to_qkv / FeedForward-in (dim 512,
             # csrc/gemm5.hip): it owns whole CUs, the half batches' launches cannot interleave with it, and ONE stream is then both
@@ -91,7 +101,7 @@ class _Sampler:
             split = 1
         self.split = split
         Bp = B // split
-        engines = [voicebox.engine(Bp, N, training=False)]
+        engines = [voicebox.engine(Bp, N, training=False, packed=self.packed)]
         for i in range(1, split):
             engines.append(voicebox.engine(Bp, N, training=False, slot=i, wpack_from=engines[0]))
         self.eng = engines[0]
@@ -111,6 +121,10 @@ class _Sampler:
             self.lens = torch.full((B,), N, dtype=torch.int32, device=dev)
             self.key_lens = torch.full((B,), R + N, dtype=torch.int32, device=dev) if ATTN_KEY_LENS else None
             self.frames = torch.arange(N, device=dev)[None]
+        if self.packed:  # static device tables of include/vbx.h "packed rows", refreshed per call; capacity N / 128 segments
+            self.seg_start = torch.zeros(N // 128, dtype=torch.int32, device=dev)
+            self.seg_klen = torch.ones(N // 128, dtype=torch.int32, device=dev)
+            self.tile_seg = torch.full((N // 128,), -1, dtype=torch.int32, device=dev)
         self.counters = torch.zeros(split, dtype=torch.int32, device=dev)  # one per part (each branch advances its own)
         # text-conditioned models: static token ids; classifier-free guidance (forward_with_cond_scale, :972-985) runs a
         # second, fully dropped evaluation (cond -> null_cond, ids -> null_cond_id) and mixes null + (logits - null) * scale
@@ -133,6 +147,8 @@ class _Sampler:
             if self.masked:
                 p.mask_kw = dict(attn_mask=self.amask[sl], attn_mask_p=self.amask_p[sl],
                                  key_lens=self.key_lens[sl] if self.key_lens is not None else None)
+            if self.packed:
+                p.mask_kw = dict(segs=(self.seg_start, self.seg_klen, self.tile_seg))
             if self.tokens:
                 p.ids, p.drop_all = self.ids[sl], self.drop_all[sl]
             if self.guided:
@@ -151,9 +167,23 @@ class _Sampler:
         """x [B, N, D] fp32: frames at or past the lengths <- 0"""
         _lib.call("vbx_zero_tail_rows", x, self.lens, self.B, self.N, x.shape[-1], _lib.current_stream())
 
-    def _load_inputs(self, cond, cond_mask, cond_token_ids, cond_scale, lens=None):
+    def _load_inputs(self, cond, cond_mask, cond_token_ids, cond_scale, lens=None, plan=None):
         # eval semantics of the reference: cond_mask None -> everything masked -> cond is zeroed (:1028-1035)
         assert (lens is not None) == self.masked, "a masked sampler runs with lens, an unmasked one without"
+        assert (plan is not None) == self.packed, "a packed sampler runs with its plan (sample_pack.pack_plan), any other without"
+        if self.packed:
+            # the inputs arrive packed (sample_pack.pack_rows: cond 0, cond_mask "masked", id 0 on register and dead rows); the
+            # kernels index by the tables, so they are checked here, on the host, before they reach the device
+            from .sample_pack import check_tables
+
+            S = len(plan.lens)
+            if plan.Mp != self.N or S > self.seg_start.numel():
+                raise ValueError(f"packed sampler of {self.N} rows got a plan of {plan.Mp} rows / {S} segments")
+            check_tables(plan.seg_start, plan.seg_klen, plan.tile_seg, self.N, S)
+            self.seg_start[:S].copy_(plan.seg_start)
+            self.seg_klen[:S].copy_(plan.seg_klen)
+            self.tile_seg.copy_(plan.tile_seg)
+            self.eng.load_packed_rotary(plan.local_row, plan.N)
         if cond is not None:
             self.cond.copy_(cond)
         if cond_mask is not None:
@@ -190,7 +220,7 @@ class _Sampler:
         time is row ada_stride * counter + slot of the adaLN table, or without one whatever the caller left in p.times."""
         p.eng.dropout_active = False  # sampling is eval (:1268) whatever mode a later forward of the same shape left on the engine
         ada = (self.ada_tab, p.counter, slot, self.ada_stride) if self.ada_tab is not None else None
-        mk = p.mask_kw if self.masked else {}
+        mk = p.mask_kw if (self.masked or self.packed) else {}
         if not self.tokens:
             p.eng.forward(x, p.cond, p.cmask, p.times, pred_out=out, ada=ada, **mk)
             return
@@ -209,10 +239,11 @@ class _FixedGridSampler(_Sampler):
     coefficients [intervals * S, ...]), host fp32; the subclass's _interval_part(p) launches one interval of one part, reading row
     S * p.counter + slot of them, and advances the counter."""
 
-    def __init__(self, voicebox, B, N, steps, method, tables, use_graph=True, tokens=0, guided=False, split=None, masked=False):
+    def __init__(self, voicebox, B, N, steps, method, tables, use_graph=True, tokens=0, guided=False, split=None, masked=False,
+                 packed=False):
         S = tables[0].numel() // (steps - 1)
         super().__init__(voicebox, B, N, use_graph=use_graph, tokens=tokens, guided=guided, split=split, grid=(tables[0], S),
-                         masked=masked)
+                         masked=masked, packed=packed)
         self.method, self.steps, self.S = method, steps, S
         dev = self.y.device
         self.c_table = tables[1].to(dev)
@@ -291,8 +322,8 @@ class _FixedGridSampler(_Sampler):
         for s in self.part_streams:
             cur.wait_stream(s)
 
-    def run(self, y0, cond=None, cond_mask=None, cond_token_ids=None, cond_scale=1.0, lens=None):
-        self._load_inputs(cond, cond_mask, cond_token_ids, cond_scale, lens)
+    def run(self, y0, cond=None, cond_mask=None, cond_token_ids=None, cond_scale=1.0, lens=None, plan=None):
+        self._load_inputs(cond, cond_mask, cond_token_ids, cond_scale, lens, plan)
         if self.use_graph and self.graph is None:
             self._capture()
         self.y.copy_(y0)
@@ -331,9 +362,9 @@ def midpoint_tables(steps):
 class MidpointSampler(_FixedGridSampler):
     """torchdiffeq's fixed-grid midpoint.  Its own step on vbx_axpy_ctr (fused y + f * a), not a tableau: see the module docstring."""
 
-    def __init__(self, voicebox, B, N, steps, use_graph=True, tokens=0, guided=False, split=None, masked=False):
+    def __init__(self, voicebox, B, N, steps, use_graph=True, tokens=0, guided=False, split=None, masked=False, packed=False):
         super().__init__(voicebox, B, N, steps, "midpoint", midpoint_tables(steps), use_graph=use_graph, tokens=tokens, guided=guided,
-                         split=split, masked=masked)
+                         split=split, masked=masked, packed=packed)
 
     def _interval_part(self, p):
         st = _lib.current_stream
@@ -387,11 +418,11 @@ class RKSampler(_FixedGridSampler):
     dt * a_ij, dt * b_j are formed on the host in fp32 torch arithmetic (fixed_grid_tables) and live in device tables
     [intervals * S] / [intervals * S][S] indexed by the part's device counter; the adaLN table holds every STAGE time."""
 
-    def __init__(self, voicebox, B, N, steps, method, use_graph=True, tokens=0, guided=False, split=None, masked=False):
+    def __init__(self, voicebox, B, N, steps, method, use_graph=True, tokens=0, guided=False, split=None, masked=False, packed=False):
         if method not in FIXED_TABLEAUS:
             raise ValueError(f"RKSampler: no fixed-grid tableau {method!r} (have {sorted(FIXED_TABLEAUS)})")
         super().__init__(voicebox, B, N, steps, method, fixed_grid_tables(method, steps), use_graph=use_graph, tokens=tokens,
-                         guided=guided, split=split, masked=masked)
+                         guided=guided, split=split, masked=masked, packed=packed)
         self.ks = [self.f] + [torch.zeros_like(self.y) for _ in range(self.S - 1)]  # stage derivatives; the stage inputs go to ymid
         for p in self.parts:
             p.k = [k[p.sl] for k in self.ks]
@@ -536,9 +567,16 @@ class Dopri5Sampler(_Sampler):
         return dict(self.last_stats)
 
 
-def make_sampler(method, voicebox, B, N, steps, *, use_graph=True, tokens=0, guided=False, atol=1e-5, rtol=1e-5, masked=False):
-    """The sampler of a torchdiffeq method name (atol / rtol: read by dopri5 only; masked: it runs with lens)."""
+def make_sampler(method, voicebox, B, N, steps, *, use_graph=True, tokens=0, guided=False, atol=1e-5, rtol=1e-5, masked=False,
+                 packed=False):
+    """The sampler of a torchdiffeq method name (atol / rtol: read by dopri5 only; masked: it runs with lens; packed: it runs one
+    batch row of N = Mp packed rows with a plan, fixed-grid methods only)."""
     kw = dict(use_graph=use_graph, tokens=tokens, guided=guided, masked=masked)
+    if packed:
+        if method == "dopri5":
+            raise NotImplementedError("dopri5 does not serve pack=True: its error norm would have to leave the dead rows out and "
+                                      "vbx_ode_norm_lens is laid out for [B, N] -- use euler, midpoint or rk4, or lens= without pack")
+        kw["packed"] = True
     if method == "midpoint":
         return MidpointSampler(voicebox, B, N, steps, **kw)
     if method == "dopri5":
