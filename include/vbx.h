@@ -242,6 +242,35 @@ int vbx_dropout_rows_f32(float* x, long rows, int cols, int ld, unsigned long lo
  * padding.  The benchmark's kernel is a separate instantiation and is not changed by this one. */
 int vbx_attn_fwd_lens(const void* q16, const void* k16, const void* v16, const uint8_t* mask, const int* key_lens, void* out16,
                       void* out_bf16, float* lse, int B, int H, int Np, float scale, void* stream);
+/* ------------------------------------------------------------------ attention backward with prefix lengths (training, lens=)
+ * vbx_attn_bwd_lens / vbx_attn_bwd_fused_lens: the arguments of vbx_attn_bwd / vbx_attn_bwd_fused plus key_lens, int32 [B] on the
+ * device, 1 <= key_lens[b] <= Np (the kernel clamps into that range: no value can become an out-of-range bound).  Keys at or past
+ * key_lens[b] are dead whatever `mask` (the equivalent prefix mask, or NULL) says.  The length-aware kernel does not read `mask` at
+ * all -- the lengths say the same, and the per-block mask byte loads are what a masked backward costs over a plain one; only the
+ * fallbacks below read it.
+ *  - PRECONDITION: query rows at or past key_lens[b] are padding and dout is ZERO there.  The train step guarantees it: their loss is
+ *    masked and every layer between the loss and the attention output is row-wise or (GateLoop) causal towards the front.
+ *  - Under it dq, dk, dv (resp. dqkv and gpart) equal what vbx_attn_bwd / vbx_attn_bwd_fused give with the prefix mask: bit for bit
+ *    on rows < key_lens[b], zero on the rows at or past it.  Every row < Np of every output is written (the caller does not pre-zero).
+ *  - dq role (128 query rows per workgroup): walks ceil(key_lens[b] / 64) key tiles instead of ceil(Np / 64), the DMA ring prefetches
+ *    against the same bound, the last walked tile clamps its rows and compares its keys against key_lens[b].  dk/dv role (128 keys
+ *    per workgroup): walks ceil(key_lens[b] / 64) query tiles.  A skipped tile would have contributed P = 0 (dead keys) or
+ *    dO = delta = 0 (dead queries), i.e. +-0, to every sum.  A 128-row tile of either role wholly at or past key_lens[b] issues no
+ *    DMA, writes zero rows (fused form: zero dqkv columns and a zero gpart record) and leaves.
+ *  - Launch order, XCD map and the <= 16-row ragged tail role (Np % 128 in 1..16) are those of vbx_attn_bwd.  delta comes from the
+ *    same streaming pass.  No atomics; reruns are bit-identical.  No empty-batch pass: key_lens >= 1.
+ *  - The kernel is a further instantiation of the folded two-body backward; the existing kernels are not changed by it.  There is no
+ *    length-aware form of attention dropout, of vbx_attn_bwd_select(3) or of precise mode: callers run the masked entry points with
+ *    the prefix mask bytes there (the same values).  Under vbx_attn_bwd_select(3) these two entry points do that themselves and
+ *    then require `mask`. */
+int vbx_attn_bwd_lens(const void* q16, const void* k16, const void* qb, const void* kb, const void* v, const uint8_t* mask,
+                      const int* key_lens, const void* out, int out_is_f16, const void* dout, const float* lse, float* delta,
+                      float* dq, float* dk, void* dv, int dv_ld, int B, int H, int Np, float scale, void* scratch, void* stream);
+int vbx_attn_bwd_fused_lens(const void* q16, const void* k16, const void* qb, const void* kb, const void* v, const uint8_t* mask,
+                            const int* key_lens, const void* out, int out_is_f16, const void* dout, const float* lse, float* delta,
+                            const float* q_rnorm, const float* k_rnorm, const float* q_gamma, const float* k_gamma,
+                            const float* rot_cos, const float* rot_sin, float qk_scale, void* dqkv, int ld, float* gpart, int B,
+                            int H, int Np, float scale, void* scratch, void* stream);
 /* ------------------------------------------------------------------ packed rows (inference; the sampler's lens= with pack=True)
  * A ragged batch of B rows with len_b frames each runs as ONE batch row of Mp rows.
  *  - A segment is one batch row: R register rows, then len_b frame rows, then dead rows up to the next multiple of
@@ -992,9 +1021,12 @@ typedef struct {
   const int* ada_counter;       /* the forward then skips the time embedding and the projection GEMV and takes time point         */
   int ada_slot;                 /* ada_stride * ada_counter[0] + ada_slot of the table (`times` is not read)                     */
   int ada_stride;               /* time points per interval of ada_table, >= 1 (midpoint 2, euler 1, rk4 4); 0 <= ada_slot < ada_stride */
-  const int* key_lens;          /* inference only, or NULL: [B] int32 on the device, key_lens[b] = R + len_b >= 1 where attn_mask_p is the
-                                   prefix mask n < key_lens[b] (the sampler's lens=).  The fast-path forward then runs vbx_attn_fwd_lens:
-                                   key tiles past the length are not walked.  Requires attn_mask_p; precise mode ignores it (mask only). */
+  const int* key_lens;          /* NULL, or [B] int32 on the device, key_lens[b] = R + len_b >= 1 where attn_mask_p is the prefix mask
+                                   n < key_lens[b] (lens= of the sampler and of the train step).  The fast-path forward then runs
+                                   vbx_attn_fwd_lens and the backward vbx_attn_bwd_fused_lens: tiles past the length are not walked.
+                                   Must stay alive (and unchanged) until the backward of this forward has run.  Requires attn_mask_p,
+                                   which the convolution, the loss and the fallbacks keep reading: attention dropout and precise
+                                   mode ignore key_lens (mask only). */
   const int* seg_start;         /* vbx_model.packed only (NULL otherwise): the device tables of "packed rows", validated by the caller: */
   const int* seg_klen;          /* seg_start / seg_klen int32 [segments], tile_seg int32 [Mp / 128]                                    */
   const int* tile_seg;

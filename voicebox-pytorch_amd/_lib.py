@@ -49,6 +49,8 @@ _PROTOS = {
     "vbx_attn_fwd_segs": [P, P, P, P, P, P, P, P, P, I, I, F, P],
     "vbx_attn_bwd": [P, P, P, P, P, P, P, I, P, P, P, P, P, P, I, I, I, I, F, P, P],
     "vbx_attn_bwd_fused": [P, P, P, P, P, P, P, I, P, P, P, P, P, P, P, P, P, F, P, I, P, I, I, I, F, P, P],
+    "vbx_attn_bwd_lens": [P, P, P, P, P, P, P, P, I, P, P, P, P, P, P, I, I, I, I, F, P, P],
+    "vbx_attn_bwd_fused_lens": [P, P, P, P, P, P, P, P, I, P, P, P, P, P, P, P, P, P, F, P, I, P, I, I, I, F, P, P],
     "vbx_attn_bwd_select": [I],
     "vbx_attn_bwd_variant": [],
     "vbx_dropout_bits_words": [I],

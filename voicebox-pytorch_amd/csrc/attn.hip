@@ -1177,7 +1177,7 @@ struct AttnDrop {  // training-time attention dropout: keep bits in both orienta
 static int attn_bwd_impl(const void* q16, const void* k16, const void* qb, const void* kb, const void* v, const uint8_t* mask,
                          const void* out, int out_is_f16, const void* dout, const float* lse, float* delta, float* dq, float* dk,
                          void* dv, int dv_ld, int B, int H, int Np, float scale, const QKBwd& fq, const QKBwd& fk, void* scratch,
-                         const AttnDrop& drop, void* stream) {
+                         const AttnDrop& drop, void* stream, const int* key_lens = nullptr) {
   hipStream_t st = (hipStream_t)stream;
   static bool attr = false;
   const bool dropout = drop.rm != nullptr;
@@ -1187,6 +1187,7 @@ static int attn_bwd_impl(const void* q16, const void* k16, const void* qb, const
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_kernel_dma<false>), hipFuncAttributeMaxDynamicSharedMemorySize, BWD_DMA_LDS);
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_kernel_dma<true>), hipFuncAttributeMaxDynamicSharedMemorySize, BWD_DMA_LDS);
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_kernel_fold), hipFuncAttributeMaxDynamicSharedMemorySize, BWD_DMA_LDS);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_kernel_fold_lens), hipFuncAttributeMaxDynamicSharedMemorySize, BWD_DMA_LDS);
     attr = true;
   }
   const long chunks = (long)B * Np * H * 8;
@@ -1210,6 +1211,16 @@ static int attn_bwd_impl(const void* q16, const void* k16, const void* qb, const
   a.role = 0;  // both bodies in ONE launch
   // vbx_attn_bwd_select(3): round 3's bodies (statistics subtracted by VALU instead of folded into the MFMA accumulator)
   const bool fold = g_attn_bwd_variant != 3;
+  // Prefix lengths: the folded bodies stop at key_lens[b].  Attention dropout and the unfolded bodies have no length-aware form: they
+  // run on the mask bytes, which say the same (vbx_attn_bwd_lens requires them then); key_lens >= 1, so no batch is empty.
+  if (key_lens && fold && !dropout) {
+    // The lengths say all the mask bytes could: the kernel gets no mask pointer, so only the last walked tile of a row compares keys
+    // (the per-block byte loads are what the masked kernels cost over the plain ones, profiles/train_lens_times.json).
+    a.mask = nullptr;
+    hipLaunchKernelGGL(attn_bwd_kernel_fold_lens, dim3(2 * grid.x), dim3(256), BWD_DMA_LDS, st, a, key_lens);
+    VBX_LAUNCH_CHECK();
+    return 0;
+  }
   if (dropout) hipLaunchKernelGGL(attn_bwd_kernel_dma<true>, dim3(2 * grid.x), dim3(256), BWD_DMA_LDS, st, a);
   else if (fold) hipLaunchKernelGGL(attn_bwd_kernel_fold, dim3(2 * grid.x), dim3(256), BWD_DMA_LDS, st, a);
   else hipLaunchKernelGGL(attn_bwd_kernel_dma<false>, dim3(2 * grid.x), dim3(256), BWD_DMA_LDS, st, a);
@@ -1274,4 +1285,34 @@ extern "C" int vbx_attn_bwd_fused_dropout(const void* q16, const void* k16, cons
            gpart ? gpart + (size_t)B * tiles * H * 64 : nullptr, 1.0f};
   return attn_bwd_impl(q16, k16, qb, kb, v, mask, out, out_is_f16, dout, lse, delta, nullptr, nullptr, (u16*)dqkv + 2 * I, ld, B, H, Np,
                        scale, fq, fk, scratch, AttnDrop{(const unsigned*)bits_rm, (const unsigned*)bits_cm, p}, stream);
+}
+
+// Prefix lengths (include/vbx.h "attention backward with prefix lengths"): the arguments of vbx_attn_bwd / vbx_attn_bwd_fused_dropout
+// plus key_lens.  Under vbx_attn_bwd_select(3) or with keep bits the masked kernels run instead and need the equivalent mask bytes.
+extern "C" int vbx_attn_bwd_lens(const void* q16, const void* k16, const void* qb, const void* kb, const void* v,
+                                 const uint8_t* mask, const int* key_lens, const void* out, int out_is_f16, const void* dout,
+                                 const float* lse, float* delta, float* dq, float* dk, void* dv, int dv_ld, int B, int H, int Np,
+                                 float scale, void* scratch, void* stream) {
+  VBX_REQUIRE(q16 && k16 && qb && kb && v && dout && lse && delta && dq && dk && dv && key_lens, "vbx_attn_bwd_lens: null pointer");
+  VBX_REQUIRE(B > 0 && H > 0 && Np > 0 && scale > 0.f && dv_ld % 8 == 0, "vbx_attn_bwd_lens: bad dims (dv_ld must be a multiple of 8)");
+  VBX_REQUIRE(mask || g_attn_bwd_variant != 3, "vbx_attn_bwd_lens: the unfolded bodies (vbx_attn_bwd_select(3)) need the prefix mask bytes");
+  const QKBwd none{};
+  return attn_bwd_impl(q16, k16, qb, kb, v, mask, out, out_is_f16, dout, lse, delta, dq, dk, dv, dv_ld, B, H, Np, scale, none, none,
+                       scratch, AttnDrop{}, stream, key_lens);
+}
+extern "C" int vbx_attn_bwd_fused_lens(const void* q16, const void* k16, const void* qb, const void* kb, const void* v,
+                                       const uint8_t* mask, const int* key_lens, const void* out, int out_is_f16, const void* dout,
+                                       const float* lse, float* delta, const float* q_rnorm, const float* k_rnorm, const float* q_gamma,
+                                       const float* k_gamma, const float* rot_cos, const float* rot_sin, float qk_scale, void* dqkv,
+                                       int ld, float* gpart, int B, int H, int Np, float scale, void* scratch, void* stream) {
+  VBX_REQUIRE(q16 && k16 && qb && kb && v && dout && lse && delta && dqkv && rot_cos && rot_sin && key_lens, "vbx_attn_bwd_fused_lens: null pointer");
+  VBX_REQUIRE(B > 0 && H > 0 && Np > 0 && scale > 0.f && ld % 8 == 0 && ld >= 3 * H * 64, "vbx_attn_bwd_fused_lens: bad dims");
+  VBX_REQUIRE(qk_scale <= 0.f || (q_rnorm && k_rnorm && q_gamma && k_gamma && gpart), "vbx_attn_bwd_fused_lens: qk-norm needs norms, gammas, gpart");
+  VBX_REQUIRE(mask || g_attn_bwd_variant != 3, "vbx_attn_bwd_fused_lens: the unfolded bodies (vbx_attn_bwd_select(3)) need the prefix mask bytes");
+  const int I = H * 64, tiles = cdiv(Np, 128);
+  QKBwd fq{(const u16*)q16, q_rnorm, q_gamma, rot_cos, rot_sin, qk_scale, (u16*)dqkv, ld, 0, gpart, 1.0f / (scale * LOG2E)};
+  QKBwd fk{(const u16*)k16, k_rnorm, k_gamma, rot_cos, rot_sin, qk_scale, (u16*)dqkv, ld, I,
+           gpart ? gpart + (size_t)B * tiles * H * 64 : nullptr, 1.0f};
+  return attn_bwd_impl(q16, k16, qb, kb, v, mask, out, out_is_f16, dout, lse, delta, nullptr, nullptr, (u16*)dqkv + 2 * I, ld, B, H, Np,
+                       scale, fq, fk, scratch, AttnDrop{}, stream, key_lens);
 }

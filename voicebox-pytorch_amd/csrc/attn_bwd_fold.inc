@@ -48,11 +48,46 @@ VBX_DEV float exp2_neg(float x) { return __builtin_amdgcn_exp2f(-x); }  // v_exp
   __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);      \
   __builtin_amdgcn_sched_group_barrier(0x400, 4, 0)
 
+// Length-aware instantiations (LENS; vbx_attn_bwd_lens / vbx_attn_bwd_fused_lens, include/vbx.h): keys at or past kend = key_lens[b] are
+// dead whatever `mask` says, and query rows at or past it carry dO = 0 (the caller's precondition).  Both bodies then walk
+// ceil(kend / 64) ring tiles instead of ceil(Np / 64) -- a skipped tile would have had P = 0 (dead keys) or dO = delta = 0 (dead
+// queries), i.e. +-0 added to every sum -- and a 128-row tile wholly at or past kend writes zeros and leaves before any DMA.  With
+// LENS = false `kend` IS Np and the bodies compile to the instructions they had (profiles/train_lens_attn.txt).
+//
+// The zero rows of a wholly dead tile: fp32 rows of x32 [B,H,Np,64] (unfused dq / dk), bf16 rows of the fused epilogue's dqkv block
+// with its zero gamma-partial record, and (dk/dv role) the bf16 dv rows.
+VBX_DEV void attn_bwd_zero_tile(float* __restrict__ x32, const QKBwd& f, u16* __restrict__ dv, int dv_ld, int b, int h, int H, int tile,
+                                int Np) {
+  const int tid = threadIdx.x;
+  const long bh = (long)b * H + h;
+  const int row0 = tile * 128;
+  const uint4 z = make_uint4(0u, 0u, 0u, 0u);
+  if (f.dqkv) {
+    for (int i = tid; i < 128 * 8; i += 256) {
+      const int n = row0 + (i >> 3);
+      if (n < Np) *reinterpret_cast<uint4*>(f.dqkv + ((long)b * Np + n) * f.ld + f.col0 + h * 64 + (i & 7) * 8) = z;
+    }
+    if (f.qk_scale > 0.f && f.gpart && tid < 64) f.gpart[(((long)b * ((Np + 127) >> 7) + tile) * H + h) * 64 + tid] = 0.f;
+  } else {
+    for (int i = tid; i < 128 * 16; i += 256) {
+      const int n = row0 + (i >> 4);
+      if (n < Np) *reinterpret_cast<uint4*>(x32 + (bh * Np + n) * 64 + (i & 15) * 4) = z;
+    }
+  }
+  if (dv) {
+    for (int i = tid; i < 128 * 8; i += 256) {
+      const int n = row0 + (i >> 3);
+      if (n < Np) *reinterpret_cast<uint4*>(dv + ((long)b * Np + n) * dv_ld + h * 64 + (i & 7) * 8) = z;
+    }
+  }
+}
+
+template <bool LENS>
 VBX_DEV void attn_bwd_dkdv_fold_body(char* smem, int wg_id, const u16* __restrict__ q16, const u16* __restrict__ qb16,
                                      const u16* __restrict__ k16, const u16* __restrict__ vv, const uint8_t* __restrict__ mask,
                                      const u16* __restrict__ dout, const float* __restrict__ lse, const float* __restrict__ delta,
                                      float* __restrict__ dk, u16* __restrict__ dv, int dv_ld, int H, int Np, float scale, int BH,
-                                     int xmap, const QKBwd& fk) {
+                                     int xmap, const QKBwd& fk, const int* __restrict__ key_lens) {
   const int tid = threadIdx.x, lane = tid & 63, hi = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const AttnCoord co = attn_coord_id(wg_id, H, Np, BH, xmap);
@@ -60,6 +95,15 @@ VBX_DEV void attn_bwd_dkdv_fold_body(char* smem, int wg_id, const u16* __restric
   ATTN_TRACE_BEGIN();
   const int h = co.h, b = co.b;
   const long bh = (long)b * H + h;
+  int kend = Np;  // uniform over the workgroup
+  if constexpr (LENS) {
+    kend = min(max(key_lens[b], 1), Np);
+    if (co.tile * 128 >= kend) {  // dead keys only: zero dk / dv rows (and gamma partials), no DMA
+      attn_bwd_zero_tile(dk, fk, dv, dv_ld, b, h, H, co.tile, Np);
+      ATTN_TRACE_END(2);
+      return;
+    }
+  }
   const u16* qbase = q16 + bh * Np * 64;
   const u16* qbbase = qb16 + bh * Np * 64;
   const u16* dobase = dout + (long)b * Np * (H * 64) + h * 64;
@@ -67,9 +111,9 @@ VBX_DEV void attn_bwd_dkdv_fold_body(char* smem, int wg_id, const u16* __restric
   const bool active = key0 < Np;
   const int key = key0 + (lane & 31);
   const int keyc = min(key, Np - 1);
-  bool kvalid = key < Np;
+  bool kvalid = key < kend;
   if (kvalid && mask) kvalid = mask[(long)b * Np + key] != 0;
-  const int ntiles = (Np + 63) / 64;
+  const int ntiles = (kend + 63) / 64;  // query tiles: rows at or past kend carry dO = 0
 
   f16x8 kf[4];   // -K
   bf16x8 vf[4];  // -V
@@ -250,7 +294,7 @@ VBX_DEV void attn_bwd_dkdv_fold_body(char* smem, int wg_id, const u16* __restric
     if (qt + 1 < ntiles) issue(qt + 1);
     if (!active) return;
     block(so_c, std::integral_constant<int, 0>{});
-    if (qt * 64 + 32 < Np) block(so_c, std::integral_constant<int, 1>{});
+    if (qt * 64 + 32 < kend) block(so_c, std::integral_constant<int, 1>{});
   };
   for (int qt = 0; qt < ntiles; qt += 2) {
     step(std::integral_constant<int, 0>{}, qt);
@@ -293,10 +337,12 @@ VBX_DEV void attn_bwd_dkdv_fold_body(char* smem, int wg_id, const u16* __restric
 }
 
 // ---------------------------------------------------------------------------- dq with the folded statistics
+template <bool LENS>
 VBX_DEV void attn_bwd_dq_fold_body(char* smem, int wg_id, const u16* __restrict__ q16, const u16* __restrict__ k16,
                                    const u16* __restrict__ kb16, const u16* __restrict__ vv, const uint8_t* __restrict__ mask,
                                    const u16* __restrict__ dout, const float* __restrict__ lse, const float* __restrict__ delta,
-                                   float* __restrict__ dq, int H, int Np, float scale, int BH, int xmap, const QKBwd& fq) {
+                                   float* __restrict__ dq, int H, int Np, float scale, int BH, int xmap, const QKBwd& fq,
+                                   const int* __restrict__ key_lens) {
   const int tid = threadIdx.x, lane = tid & 63, hi = lane >> 5;
   const AttnCoord co = attn_coord_id(wg_id, H, Np, BH, xmap);
   if (!co.ok) return;
@@ -304,6 +350,15 @@ VBX_DEV void attn_bwd_dq_fold_body(char* smem, int wg_id, const u16* __restrict_
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int h = co.h, b = co.b;
   const long bh = (long)b * H + h;
+  int kend = Np;  // uniform over the workgroup
+  if constexpr (LENS) {
+    kend = min(max(key_lens[b], 1), Np);
+    if (co.tile * 128 >= kend) {  // padding queries only (dO = 0): zero dq rows (and gamma partials), no DMA
+      attn_bwd_zero_tile(dq, fq, nullptr, 0, b, h, H, co.tile, Np);
+      ATTN_TRACE_END(1);
+      return;
+    }
+  }
   const u16* kbase = k16 + bh * Np * 64;
   const u16* kbbase = kb16 + bh * Np * 64;
   const u16* vbase = vv + bh * Np * 64;
@@ -311,7 +366,7 @@ VBX_DEV void attn_bwd_dq_fold_body(char* smem, int wg_id, const u16* __restrict_
   const bool active = q0 < Np;
   const int q = q0 + (lane & 31);
   const int qc = min(q, Np - 1);
-  const int ntiles = (Np + 63) / 64;
+  const int ntiles = (kend + 63) / 64;  // key tiles
 
   f16x8 qf[4];    // -Q (pre-scaled)
   bf16x8 dof[4];  // -dO
@@ -344,8 +399,8 @@ VBX_DEV void attn_bwd_dq_fold_body(char* smem, int wg_id, const u16* __restrict_
   auto issue = [&](int kt) {
     const unsigned so = (unsigned)((kt & 1) * Q3_SLOT);
     unsigned o0 = dvo[0], o1 = dvo[1];
-    if ((kt + 1) * 64 > Np) {
-      const unsigned lim = (unsigned)(Np - 1 - kt * 64);
+    if ((kt + 1) * 64 > kend) {
+      const unsigned lim = (unsigned)(kend - 1 - kt * 64);
       o0 -= ((o0 >> 7) - min(o0 >> 7, lim)) << 7;
       o1 -= ((o1 >> 7) - min(o1 >> 7, lim)) << 7;
     }
@@ -427,7 +482,7 @@ VBX_DEV void attn_bwd_dq_fold_body(char* smem, int wg_id, const u16* __restrict_
 #pragma unroll
       for (int r = 0; r < 16; r++) {
         const int kg = k0 + KB * 32 + acc_row(r, hi);
-        bool ok = kg < Np;
+        bool ok = kg < kend;
         if (ok && mask) ok = mask[(long)b * Np + kg] != 0;
         if (!ok) s[r] = 0.f;
       }
@@ -458,9 +513,9 @@ VBX_DEV void attn_bwd_dq_fold_body(char* smem, int wg_id, const u16* __restrict_
     if (kt + 1 < ntiles) issue(kt + 1);
     if (!active) return;
     const int k0 = kt * 64;
-    const bool need_mask = (mask != nullptr) || (k0 + 64 > Np);
+    const bool need_mask = (mask != nullptr) || (k0 + 64 > kend);
     block(so_c, std::integral_constant<int, 0>{}, k0, need_mask);
-    if (k0 + 32 < Np) block(so_c, std::integral_constant<int, 1>{}, k0, need_mask);
+    if (k0 + 32 < kend) block(so_c, std::integral_constant<int, 1>{}, k0, need_mask);
   };
   for (int kt = 0; kt < ntiles; kt += 2) {
     step(std::integral_constant<int, 0>{}, kt);
@@ -480,12 +535,14 @@ VBX_DEV void attn_bwd_dq_fold_body(char* smem, int wg_id, const u16* __restrict_
   ATTN_TRACE_END(1);
 }
 
-__global__ __launch_bounds__(256, 3) void attn_bwd_kernel_fold(const AttnBwdArgs a) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
+// blockIdx -> (role, workgroup id of that role's grid).  Launch order: tails of both roles, dk/dv full tiles (the longer ones), dq full
+// tiles (as attn_bwd_kernel_dma).
+template <bool LENS>
+VBX_DEV void attn_bwd_fold_roles(char* smem, const AttnBwdArgs& a, const int* __restrict__ key_lens) {
   int id = blockIdx.x, role;
   if (a.role) {
     role = a.role == 1;
-  } else {  // launch order: tails of both roles, dk/dv full tiles (the longer ones), dq full tiles (as attn_bwd_kernel_dma)
+  } else {
     const int T = attn_tail_ids(a.Np, a.BH, a.xmap), F = a.grid_one - T;
     if (a.xmap & 2) {
       if (id < 2 * F) { role = id >= F; id -= role * F; }
@@ -500,9 +557,19 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_kernel_fold(const AttnBwdArgs
     }
   }
   if (role)
-    attn_bwd_dq_fold_body(smem, id, a.q16, a.k16, a.kb16, a.vv, a.mask, a.dout, a.lse, a.delta, a.dq, a.H, a.Np, a.scale, a.BH,
-                          a.xmap, a.fq);
+    attn_bwd_dq_fold_body<LENS>(smem, id, a.q16, a.k16, a.kb16, a.vv, a.mask, a.dout, a.lse, a.delta, a.dq, a.H, a.Np, a.scale, a.BH,
+                                a.xmap, a.fq, key_lens);
   else
-    attn_bwd_dkdv_fold_body(smem, id, a.q16, a.qb16, a.k16, a.vv, a.mask, a.dout, a.lse, a.delta, a.dk, a.dv, a.dv_ld, a.H, a.Np,
-                            a.scale, a.BH, a.xmap, a.fk);
+    attn_bwd_dkdv_fold_body<LENS>(smem, id, a.q16, a.qb16, a.k16, a.vv, a.mask, a.dout, a.lse, a.delta, a.dk, a.dv, a.dv_ld, a.H, a.Np,
+                                  a.scale, a.BH, a.xmap, a.fk, key_lens);
+}
+__global__ __launch_bounds__(256, 3) void attn_bwd_kernel_fold(const AttnBwdArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  attn_bwd_fold_roles<false>(smem, a, nullptr);
+}
+// the same two bodies with per-batch-row prefix lengths (training on ragged batches, lens=): same launch order, XCD map and tail roles.
+// key_lens is a parameter of its own, behind AttnBwdArgs: no other kernel's argument block changes.
+__global__ __launch_bounds__(256, 3) void attn_bwd_kernel_fold_lens(const AttnBwdArgs a, const int* __restrict__ key_lens) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  attn_bwd_fold_roles<true>(smem, a, key_lens);
 }

@@ -10,7 +10,8 @@
 // A lane owns the stationary row (lane & 15) and four ring rows 4 (lane >> 4) .. + 3, so the S / dP values it holds ARE the B
 // fragments of the second products.  No statistics fold here (plain VALU subtracts): these workgroups are latency-bound.  The four
 // waves' partial blocks are summed through LDS in the staging layout of store_rows_qknorm / store_rows_f32, whose row passes then
-// run unchanged.  Reference: autograd of attend.py:121-135.
+// run unchanged.  Reference: autograd of attend.py:121-135.  `kend` is the bodies' live-key bound (Np, or key_lens[b] in their
+// length-aware instantiations, whose `ntiles` and `issue` stop there too).
 #ifdef VBX_BWD_RAGGED_DQ
   if (co.tile == (Np >> 7) && (Np & 127) <= 16 && !(xmap & 4)) {
     const int qi = lane & 15, g = lane >> 4;
@@ -61,7 +62,7 @@
 #pragma unroll
       for (int i = 0; i < 4; i++) {
         const int kg = kg0 + i;
-        bool ok = kg < Np;
+        bool ok = kg < kend;
         if (ok && mask) ok = mask[(long)b * Np + kg] != 0;
         const float p = ok ? __builtin_amdgcn_exp2f(s4[i] - Lq) : 0.f;
         ds[i] = p * (dp4[i] - dlq);
@@ -117,7 +118,7 @@
     const int kb0 = co.tile * 128;
     const int R = Np - kb0;
     const int krow = min(kb0 + ki, Np - 1);
-    bool kval = kb0 + ki < Np;
+    bool kval = kb0 + ki < kend;
     if (kval && mask) kval = mask[(long)b * Np + kb0 + ki] != 0;
     f16x8 kf2[2];
     bf16x8 vf2[2];

@@ -710,8 +710,12 @@ extern "C" int vbx_model_forward(const vbx_model* m, const vbx_io* io, void* str
       ProfScope ps("fwd attention", st);
       if (m->packed)  // packed rows: every query tile against the live keys of its own segment
         CK(vbx_attn_fwd_segs(y.q16, y.k16, y.vh, io->seg_start, io->seg_klen, io->tile_seg, y.oh, y.o, y.lse, d.H, d.Np, m->attn_scale, stream));
-      else if (io->key_lens && !m->training)  // the sampler's prefix lengths: dead key tiles are not walked (bit-equal on live queries)
-        CK(vbx_attn_fwd_lens(y.q16, y.k16, y.vh, io->attn_mask_p, io->key_lens, y.oh, y.o, y.lse, d.B, d.H, d.Np, m->attn_scale, stream));
+      else if (io->key_lens)  // prefix lengths (the sampler's and the train step's lens=): dead key tiles are not walked; lse and output
+                              // of the live queries are vbx_attn_fwd's bits, which is all the backward reads of them under dO = 0.
+                              // Training passes no mask bytes beside the lengths (they say the same; only the last walked tile of a
+                              // row then compares keys); the sampler's launch is what it was.
+        CK(vbx_attn_fwd_lens(y.q16, y.k16, y.vh, m->training ? nullptr : io->attn_mask_p, io->key_lens, y.oh, y.o, y.lse, d.B, d.H, d.Np,
+                             m->attn_scale, stream));
       else
         CK(vbx_attn_fwd(y.q16, y.k16, y.vh, io->attn_mask_p, y.oh, y.o, y.lse, d.B, d.H, d.Np, m->attn_scale, stream));
     }
@@ -1016,7 +1020,15 @@ extern "C" int vbx_model_backward_layer(const vbx_model* m, const vbx_io* io, in
     ProfScope ps("bwd attention delta", st);
     CK(vbx_attn_delta_consistent(y.q16, y.k16, y.v, attn_mask_p, a.dO, y.lse, a.delta, d.B, d.H, d.Np, stream));
   }
-  { ProfScope ps("bwd attention", st);
+  // Prefix lengths (the forward's io->key_lens): the length-aware folded bodies.  Attention dropout and precise mode have none and run
+  // the masked kernels on the mask bytes beside the lengths (the same values); so does vbx_attn_bwd_select(3), inside the entry point.
+  if (io && io->key_lens && !m->precise && !(drop_on && m->attn_dropout > 0.f)) {
+    ProfScope ps("bwd attention", st);
+    CK(vbx_attn_bwd_fused_lens(y.q16, y.k16, y.qb, y.kb, y.v, attn_mask_p, io->key_lens, own_delta ? nullptr : y.oh, 1, a.dO, y.lse, a.delta, y.qrn, y.krn,
+                               q_gamma, k_gamma, m->rot_cos, m->rot_sin, m->qk_norm ? 8.0f : 0.0f, dqkv, 3 * d.I, gpart, d.B, d.H, d.Np,
+                               m->attn_scale, a.attn_scratch, stream));
+  } else {
+    ProfScope ps("bwd attention", st);
     CK(vbx_attn_bwd_fused_dropout(y.q16, y.k16, y.qb, y.kb, y.v, attn_mask_p, own_delta ? nullptr : y.oh, 1, a.dO, y.lse, a.delta, y.qrn, y.krn, q_gamma, k_gamma,
                                   m->rot_cos, m->rot_sin, m->qk_norm ? 8.0f : 0.0f, dqkv, 3 * d.I, gpart, d.B, d.H, d.Np, m->attn_scale,
                                   a.attn_scratch, drop_on ? y.dbr : nullptr, y.dbc, m->attn_dropout, stream)); }

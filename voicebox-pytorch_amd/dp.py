@@ -321,13 +321,14 @@ class TrainStep:
 
     # -- gradient accumulation with a deferred exchange (VoiceBoxTrainer.train_step, trainer.py:258-272: every micro-batch but
     #    the last runs under accelerator.no_sync, the loss is divided by grad_accum_every)
-    def accumulate(self, x1, weight, mask=None, cond_token_ids=None, input_sampling_rate=None):
-        """forward + backward of one micro-batch; gradients * weight are added to the accumulation buffer (no exchange)."""
+    def accumulate(self, x1, weight, mask=None, cond_token_ids=None, input_sampling_rate=None, lens=None):
+        """forward + backward of one micro-batch; gradients * weight are added to the accumulation buffer (no exchange).
+        lens: see step."""
         if getattr(self, "gacc", None) is None:
             self.gacc = torch.zeros_like(self.gflat)
             self.acc_coef = torch.zeros(1, device=self.gflat.device)
             self.acc_pending = False
-        loss = self._forward_backward(x1, mask, cond_token_ids, on_stage=None, input_sampling_rate=input_sampling_rate)
+        loss = self._forward_backward(x1, mask, cond_token_ids, on_stage=None, input_sampling_rate=input_sampling_rate, lens=lens)
         self.acc_coef.fill_(float(weight))
         n = self.gflat.numel()
         _lib.call("vbx_axpy_dev", self.gacc, self.gflat, self.acc_coef, 0, self.gacc, n, _lib.current_stream())
@@ -384,7 +385,7 @@ class TrainStep:
                                              dada_all.shape[1], Th, J4, 0, st), "vbx_adaln_expand_dw")
         self._keep_factors = (dada_all, temb_all)  # alive until the launches have run
 
-    def accumulate_last_and_apply(self, x1, weight, mask=None, cond_token_ids=None, lr=None, input_sampling_rate=None):
+    def accumulate_last_and_apply(self, x1, weight, mask=None, cond_token_ids=None, lr=None, input_sampling_rate=None, lens=None):
         """The LAST micro-batch of an accumulation window, with the exchange overlapped with its backward (DDP leaves `no_sync`
         for exactly this micro-batch, trainer.py:258-272): as each backward stage completes, its slice of the accumulator is
         folded in (g = acc + weight * g) and the bucketed all-reduce of that slice starts while earlier layers are still running --
@@ -400,7 +401,7 @@ class TrainStep:
             if self.exchange:
                 red.stage_done(i, rng)
 
-        loss = self._forward_backward(x1, mask, cond_token_ids, on_stage=on_stage, input_sampling_rate=input_sampling_rate)
+        loss = self._forward_backward(x1, mask, cond_token_ids, on_stage=on_stage, input_sampling_rate=input_sampling_rate, lens=lens)
         red.finish()
         self._stage_buf = red.stage_buf
         self.gacc.zero_()
@@ -423,10 +424,21 @@ class TrainStep:
             self._stage_buf = red.stage_buf
         self._clip_adam(self._last_eng, lr)
 
-    def _forward_backward(self, x1, mask, cond_token_ids, on_stage, adaln_factors=False, sq_fold=False, input_sampling_rate=None):
+    def _forward_backward(self, x1, mask, cond_token_ids, on_stage, adaln_factors=False, sq_fold=False, input_sampling_rate=None,
+                          lens=None):
         vb, w = self.vb, self.wrapper
         dev = self.fp.flat.device
         st = _lib.current_stream
+        key_lens = None
+        if lens is not None:  # a ragged batch by lengths (train_lens.py): refusals and host validation before anything is launched
+            from . import train_lens
+
+            train_lens.refuse_with_mask(lens, mask, "TrainStep")
+            train_lens.refuse_raw_audio(lens, x1, "TrainStep")
+            lens = train_lens.frame_lens(lens, x1.shape[0], x1.shape[1], dev)
+            mask = train_lens.prefix_mask(lens, x1.shape[1])
+            # the frames added up to length_bucket below lie past every length: key_lens is unchanged by that padding
+            key_lens = train_lens.key_lens(lens, vb._cfg["R"])
         # a wave batch of a codec model (voicebox_pytorch.py:1349-1371), resampled first when the wrapper says so; latents pass through
         x1, _ = w.encode_raw_audio(x1, None, input_sampling_rate)
         x1 = x1.to(dev, torch.float32).contiguous()
@@ -471,7 +483,7 @@ class TrainStep:
             cond_mask, loss_mask = padm(cond_mask), padm(loss_mask)
             N = Nb
         eng = vb.engine(B, N, training=True)
-        loss = eng.forward(wt, flow, cond_mask, times, attn_mask=mask, target=flow, loss_mask=loss_mask, text=text)
+        loss = eng.forward(wt, flow, cond_mask, times, attn_mask=mask, target=flow, loss_mask=loss_mask, text=text, key_lens=key_lens)
         sq = None
         if sq_fold and adaln_factors and on_stage is None and eng.sq_partials_info()[0] > 0:
             need = eng.sumsq_scratch_floats(True)
@@ -552,10 +564,13 @@ class TrainStep:
             _lib.call("vbx_adam_step", self.fp.flat, self.gflat, self.m, self.v, n, float(lr if lr is not None else self.lr),
                       float(self.betas[0]), float(self.betas[1]), float(self.eps), self.steps, self.coef, st())
 
-    def step(self, x1, mask=None, lr=None, cond_token_ids=None, input_sampling_rate=None):
+    def step(self, x1, mask=None, lr=None, cond_token_ids=None, input_sampling_rate=None, lens=None):
         """x1: (B_local, frames, dim) on this rank's GPU, or a wave batch (B_local, samples) for a model built with audio_enc_dec
         (cond_token_ids (B_local, tokens) for a text-conditioned model); input_sampling_rate: the rate of such waves, for a wrapper built
         with resample_input=True.
+        lens: a list, a CPU int tensor or a device int tensor [B_local] of frame counts instead of mask -- the same step as
+        mask = arange(frames) < lens[:, None], bit for bit, with the attention forward and backward stopping at each row's length
+        (ConditionalFlowMatcherWrapper.forward).  With text conditioning it counts frames, not tokens.
         Returns the (un-synchronised) local loss tensor."""
         # --- backward with overlapped gradient exchange
         factors = self.adaln_factors_apply(batch=int(x1.shape[0])) and os.environ.get("VBX_FUSED_ADAM", "1") != "0"
@@ -564,7 +579,7 @@ class TrainStep:
         # weight gradients for the clip norm); VBX_SUMSQ_FOLD=0: A/B
         fold = factors and not self.exchange and os.environ.get("VBX_SUMSQ_FOLD", "1") != "0"
         loss = self._forward_backward(x1, mask, cond_token_ids, on_stage=red.stage_done if self.exchange else None, adaln_factors=factors,
-                                      sq_fold=fold, input_sampling_rate=input_sampling_rate)
+                                      sq_fold=fold, input_sampling_rate=input_sampling_rate, lens=lens)
         if factors and self.exchange:  # the factors travel (one small all-gather) while the last buckets are still in flight
             self._exchange_adaln_factors(self._last_eng)
         red.finish()

@@ -462,7 +462,8 @@ class Engine:
         the adaLN projections of every time point of the ODE grid, precomputed (stride >= 1 time points per interval, this forward at
         row stride * counter + slot); `times` is then not read.  attn_mask_p (the sampler, with attn_mask): the caller's own uint8
         [B, N + R] copy of attn_mask behind R ones -- a static buffer whose address a captured graph may keep -- instead of the copy
-        built here per call; key_lens int32 [B] = R + len_b where attn_mask is the prefix mask n < len_b (vbx_io.key_lens)."""
+        built here per call; key_lens int32 [B] = R + len_b where attn_mask is the prefix mask n < len_b (vbx_io.key_lens), in training
+        too: it is kept alive with the other inputs until the backward, which reads it again."""
         self.bind_params()
         B, N, D = self.B, self.N, self.Din
         assert x.shape == (B, N, D) and cond.shape == (B, N, D), (tuple(x.shape), tuple(cond.shape), (B, N, D))
@@ -477,7 +478,7 @@ class Engine:
                 amp = attn_mask_p
             else:
                 amp = torch.cat((torch.ones(B, R, dtype=torch.uint8, device=am.device), am), dim=1).contiguous() if R else am
-        assert key_lens is None or (am is not None and target is None and key_lens.dtype == torch.int32 and key_lens.shape == (B,))
+        assert key_lens is None or (am is not None and key_lens.dtype == torch.int32 and key_lens.shape == (B,))
         io = self.io
         io.x, io.cond, io.cond_mask = x.data_ptr(), cond.data_ptr(), cm.data_ptr()
         io.attn_mask = am.data_ptr() if am is not None else None

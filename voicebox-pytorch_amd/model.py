@@ -361,8 +361,9 @@ class _VoiceBoxLossFn(torch.autograd.Function):
     vbx_model_backward_{head,layer,embed} into a fresh flat gradient buffer whose views are returned per parameter."""
 
     @staticmethod
-    def forward(ctx, vb, eng, x, cond, cond_mask, times, attn_mask, target, loss_mask, text, *params):
-        loss = eng.forward(x, cond, cond_mask, times, attn_mask=attn_mask, target=target, loss_mask=loss_mask, text=text)
+    def forward(ctx, vb, eng, x, cond, cond_mask, times, attn_mask, target, loss_mask, text, key_lens, *params):
+        loss = eng.forward(x, cond, cond_mask, times, attn_mask=attn_mask, target=target, loss_mask=loss_mask, text=text,
+                           key_lens=key_lens)  # kept alive by the engine until its backward
         ctx.vb, ctx.eng, ctx.gen = vb, eng, eng.generation
         ctx.wkey = (eng.wpack_owner or eng).packed_version  # the operand copies this forward ran on (shared by the slot engines)
         ctx.token = _InFlight()           # dies with the autograd graph: the arena is free again when nobody can call backward
@@ -384,7 +385,7 @@ class _VoiceBoxLossFn(torch.autograd.Function):
         gscale = gloss.detach().to(torch.float32).reshape(1).contiguous()
         eng.backward(gflat, gscale=gscale)
         eng._in_flight = None
-        return (None,) * 10 + tuple(vb._flat.grad_views(gflat))
+        return (None,) * 11 + tuple(vb._flat.grad_views(gflat))
 
 
 class VoiceBox(nn.Module):
@@ -537,12 +538,23 @@ class VoiceBox(nn.Module):
         return null_logits + (logits - null_logits) * cond_scale
 
     def forward(self, x, *, times, cond_token_ids, self_attn_mask=None, cond_drop_prob=0.1, target=None, cond=None,
-                cond_mask=None):  # voicebox_pytorch.py:987-1115
+                cond_mask=None, self_attn_lens=None):  # voicebox_pytorch.py:987-1115
+        """self_attn_lens (not a reference keyword): a list, a CPU int tensor or a device int tensor [B] of frame counts -- exactly
+        self_attn_mask = arange(N)[None] < self_attn_lens[:, None], and the attention forward and backward do not walk the tiles past
+        a row's length (train_lens.py).  Not together with self_attn_mask."""
+        from . import train_lens
+
+        train_lens.refuse_with_mask(self_attn_lens, self_attn_mask, "VoiceBox.forward", "self_attn_lens", "self_attn_mask")
         cond = default(cond, target)  # :1003
         assert exists(cond), "either cond or target must be given"
         batch, seq_len, cond_dim = cond.shape
         assert cond_dim == x.shape[-1]
         dev = self.device
+        key_lens = None
+        if exists(self_attn_lens):  # validated on the host (list, CPU tensor) or clamped on the device, before anything is launched
+            self_attn_lens = train_lens.frame_lens(self_attn_lens, batch, seq_len, dev)
+            self_attn_mask = train_lens.prefix_mask(self_attn_lens, seq_len)
+            key_lens = train_lens.key_lens(self_attn_lens, self._cfg["R"])
         x, cond = x.to(dev, torch.float32), cond.to(dev, torch.float32)
         times = torch.as_tensor(times, device=dev).to(torch.float32)
         if times.ndim == 0:  # :1015-1019 (odeint hands a 0-dim time)
@@ -580,7 +592,7 @@ class VoiceBox(nn.Module):
             text = (ids, self.null_cond_id, drop, self.null_cond)
         if not exists(target):
             eng = self.engine(batch, seq_len, training=False)
-            return eng.forward(x, cond, cond_mask, times, attn_mask=self_attn_mask, text=text)
+            return eng.forward(x, cond, cond_mask, times, attn_mask=self_attn_mask, text=text, key_lens=key_lens)
         target = target.to(dev, torch.float32)
         loss_mask = reduce_masks_with_and(cond_mask, self_attn_mask)  # :1099
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
@@ -598,10 +610,10 @@ class VoiceBox(nn.Module):
             eng._flight_seq = self._flight_counter
             fp = self._flat
             params = [fp.slots[s] for s in fp.order]
-            return _VoiceBoxLossFn.apply(self, eng, x, cond, cond_mask, times, self_attn_mask, target, loss_mask, text, *params)
+            return _VoiceBoxLossFn.apply(self, eng, x, cond, cond_mask, times, self_attn_mask, target, loss_mask, text, key_lens, *params)
         eng = self.engine(batch, seq_len, training=False)
         return eng.forward(x, cond, cond_mask, times, attn_mask=self_attn_mask, target=target, loss_mask=loss_mask,
-                           text=text).clone().reshape(())
+                           text=text, key_lens=key_lens).clone().reshape(())
 
 
 # --------------------------------------------------------------------------------------- CFM wrapper
@@ -863,8 +875,20 @@ class ConditionalFlowMatcherWrapper(nn.Module):
                 cond = codec.encode(cond)
         return x1, cond
 
-    def forward(self, x1, *, mask=None, semantic_token_ids=None, phoneme_ids=None, cond=None, cond_mask=None,
+    def forward(self, x1, *, mask=None, lens=None, semantic_token_ids=None, phoneme_ids=None, cond=None, cond_mask=None,
                 input_sampling_rate=None):  # voicebox_pytorch.py:1332-1427
+        """lens (not a reference keyword): a list, a CPU int tensor or a device int tensor [B] of frame counts, 1 <= len_b <= N -- the
+        batch is ragged, row b has len_b real frames.  It means exactly mask = arange(N)[None] < lens[:, None] (same loss, same
+        gradients, bit for bit), and the attention forward and backward stop at each row's length instead of masking the padding
+        after the products.  Not with mask, not with raw audio (encode first, or pass mask).  A list or CPU tensor is validated on the
+        host; a device tensor is clamped into 1 .. N on the device without a host synchronisation."""
+        if exists(lens):
+            from . import train_lens
+
+            who = "ConditionalFlowMatcherWrapper.forward"
+            train_lens.refuse_with_mask(lens, mask, who)
+            train_lens.refuse_raw_audio(lens, x1, who)
+            lens = train_lens.frame_lens(lens, x1.shape[0], x1.shape[1], self.device)
         x1, cond = self.encode_raw_audio(x1, cond, input_sampling_rate)
         assert self.condition_on_text or not (exists(semantic_token_ids) or exists(phoneme_ids)), \
             'semantic or phoneme ids should not be passed in if not conditioning on text'
@@ -888,5 +912,5 @@ class ConditionalFlowMatcherWrapper(nn.Module):
                 assert exists(phoneme_ids)
                 cond_token_ids = phoneme_ids
         self.voicebox.train()  # :1414
-        return self.voicebox(w, cond=cond, cond_mask=cond_mask, times=times, target=flow, self_attn_mask=mask,
+        return self.voicebox(w, cond=cond, cond_mask=cond_mask, times=times, target=flow, self_attn_mask=mask, self_attn_lens=lens,
                              cond_token_ids=cond_token_ids, cond_drop_prob=self.cond_drop_prob)

@@ -42,7 +42,9 @@ def checkpoint_num_steps(checkpoint_path):  # trainer.py:44-57
     return int(results[-1]) if len(results) else 0
 
 
-def _collate(pad_to_longest):  # data.py:69-101 (tensors only)
+def _collate(pad_to_longest, with_lens=False):  # data.py:69-101 (tensors only)
+    """with_lens (VoiceBoxTrainer(mask_padding=True)): the batch tuple gets one more entry behind the padded columns -- the length of
+    each item of the FIRST column before pad_sequence (int64 [B]; the cropped length without pad_to_longest)."""
     def one(data):
         if pad_to_longest:
             return pad_sequence(list(data), batch_first=True)
@@ -54,11 +56,16 @@ def _collate(pad_to_longest):  # data.py:69-101 (tensors only)
             return (one(batch),)
         return tuple(one(col) for col in zip(*batch))
 
-    return inner
+    def inner_lens(batch):
+        out = inner(batch)
+        first = batch if not isinstance(batch[0], tuple) else [item[0] for item in batch]
+        return out + (torch.tensor([min(d.shape[0], out[0].shape[1]) for d in first], dtype=torch.int64),)
+
+    return inner_lens if with_lens else inner
 
 
-def get_dataloader(ds, pad_to_longest=True, **kwargs):  # data.py:103-105
-    return DataLoader(ds, collate_fn=_collate(pad_to_longest), **kwargs)
+def get_dataloader(ds, pad_to_longest=True, with_lens=False, **kwargs):  # data.py:103-105
+    return DataLoader(ds, collate_fn=_collate(pad_to_longest, with_lens), **kwargs)
 
 
 class VoiceBoxTrainer(nn.Module):
@@ -66,12 +73,17 @@ class VoiceBoxTrainer(nn.Module):
                  num_warmup_steps=None, num_epochs=None, lr=3e-4, initial_lr=1e-5, grad_accum_every=1, wd=0., max_grad_norm=0.5,
                  valid_frac=0.05, random_split_seed=42, log_every=10, save_results_every=100, save_model_every=1000,
                  results_folder='./results', force_clear_prev_results=None, split_batches=False, drop_last=False,
-                 accelerate_kwargs: dict = dict(), length_bucket=64, input_sampling_rate=None):
+                 accelerate_kwargs: dict = dict(), length_bucket=64, input_sampling_rate=None, mask_padding=False):
         # length_bucket (not a reference keyword): batches of a varying-length dataset are padded with masked frames to the next
         # multiple of it, so that training runs on a handful of activation arenas (dp.TrainStep); 0 = exact lengths
         # input_sampling_rate (not a reference keyword: its trainer never passes one): the rate of a dataset of waves, handed to
         # every train and validation step; a wrapper built with resample_input=True resamples them to the codec's rate
+        # mask_padding (not a reference keyword; opt-in, because the reference trains on the frames pad_sequence adds): the collate
+        # function also returns each item's length, and every train and validation step passes lens= -- padding frames are masked in the
+        # convolution, the attention and the loss, and the attention kernels stop at each row's length.  Latent datasets only: with a
+        # dataset of waves the first batch raises ValueError (the frame count is the codec's business).
         super().__init__()
+        self.mask_padding = bool(mask_padding)
         self.input_sampling_rate = input_sampling_rate
         assert isinstance(cfm_wrapper, ConditionalFlowMatcherWrapper)
         self.wd = float(wd)  # > 0: AdamW with decay on the ndim >= 2 parameters (get_optimizer, optimizer.py:10-35)
@@ -110,8 +122,9 @@ class VoiceBoxTrainer(nn.Module):
         sampler = None
         if self.world > 1:  # what accelerator.prepare(dl) does: each rank sees its own shard
             sampler = torch.utils.data.distributed.DistributedSampler(self.ds, num_replicas=self.world, rank=self.rank, shuffle=True)
-        self.dl = get_dataloader(self.ds, batch_size=self.rank_batch_size, shuffle=sampler is None, sampler=sampler, drop_last=drop_last)
-        self.valid_dl = get_dataloader(self.valid_ds, batch_size=batch_size, shuffle=True, drop_last=drop_last)
+        self.dl = get_dataloader(self.ds, batch_size=self.rank_batch_size, shuffle=sampler is None, sampler=sampler, drop_last=drop_last,
+                                 with_lens=self.mask_padding)
+        self.valid_dl = get_dataloader(self.valid_ds, batch_size=batch_size, shuffle=True, drop_last=drop_last, with_lens=self.mask_padding)
         self.dl_iter, self.valid_dl_iter = cycle(self.dl, sampler), cycle(self.valid_dl)
         self.log_every, self.save_model_every, self.save_results_every = log_every, save_model_every, save_results_every
         self.results_folder = Path(results_folder)
@@ -239,6 +252,13 @@ class VoiceBoxTrainer(nn.Module):
         """(latents or waves,) or (latents or waves, cond_token_ids): the second column feeds a text-conditioned model as semantic ids."""
         x = batch[0]
         kw = dict(input_sampling_rate=self.input_sampling_rate) if exists(self.input_sampling_rate) else {}
+        if getattr(self, "mask_padding", False):  # the collate function's last entry: the items' lengths before padding
+            batch, lens = batch[:-1], batch[-1]
+            if x.ndim == 2 or (x.ndim == 3 and x.shape[1] == 1):
+                raise ValueError("VoiceBoxTrainer(mask_padding=True) needs a dataset of latents (frames, dim): the lengths of waves are "
+                                 "in samples, and the frame count is the codec's business -- encode the dataset first, or leave "
+                                 "mask_padding off")
+            kw['lens'] = lens
         if len(batch) > 1 and self.cfm_wrapper.condition_on_text:
             kw['cond_token_ids'] = batch[1]
         return x, kw
@@ -272,6 +292,7 @@ class VoiceBoxTrainer(nn.Module):
                 self.cfm_wrapper.eval()
                 ids = kw.get('cond_token_ids')
                 valid_loss = self.cfm_wrapper(x.to(self.device), input_sampling_rate=self.input_sampling_rate,
+                                              **({'lens': kw['lens']} if 'lens' in kw else {}),
                                               **({'semantic_token_ids': ids.to(self.device)} if ids is not None else {}))
             self.print(f'{steps}: valid loss {float(valid_loss):0.3f}')
             logs['valid_loss'] = float(valid_loss)
