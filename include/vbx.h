@@ -917,6 +917,36 @@ int vbx_adam_adaln_factors(float* p, float* m, float* v, const long* w_off /* ho
  * coef[1] = norm.  (accelerator.clip_grad_norm_, trainer.py:274-275) */
 int vbx_clip_coef(const float* sumsq, float max_norm, float inv_world, float* coef /* [2] */, void* stream);
 
+/* ---- LoRA adapters on the fp32 master weights (csrc/lora.hip; voicebox_pytorch_amd/lora.py, dp.TrainStep).  An adapted matrix
+ * W [N, K] (an nn.Linear weight's own [out, in] layout, in its slot of the flat parameter buffer) holds W0 + scale . B . A with
+ * A [r, K], B [N, r], 1 <= r <= 64, scale = alpha / r.  W0 lives in a separate store; A and B in a small flat buffer `lflat` whose
+ * layout the gradient buffer `glflat` shares.  One descriptor per adapted matrix; a table covers all targets of all layers and every
+ * entry point below is ONE grouped launch over it (vbx_lora_grad: two).  vbx_lora_plan checks a HOST table against the buffer sizes
+ * (every range inside its buffer) and fills the launch fields; the caller keeps a DEVICE copy of the filled table.
+ *   vbx_lora_apply  per element: acc = 0; for j ascending: acc = fmaf(B[n, j], A[j, k], acc); W[n, k] = fmaf(scale, acc, W0[n, k]).
+ *                   |W - exact| <= (r + 2) 2^-24 (|W0| + |scale| sum_j |B A|) per element; acc == 0 (B = 0) stores the bits of W0;
+ *                   reruns are bit-identical.
+ *   vbx_lora_grad   reads dW [N, K] at w_off of `gflat` (the materialised weight gradient the backward wrote there) ONCE and writes
+ *                   dB[n, j] = scale . sum_k dW[n, k] A[j, k] and dA[j, k] = scale . sum_n B[n, j] dW[n, k] into glflat at b_off / a_off.
+ *                   fp32 fmaf chains in a fixed order (tiles of 128 rows x 256 columns, ascending inside a tile, tile partials added
+ *                   in ascending order), no atomics: reruns are bit-identical and an entry's result does not depend on the rest of
+ *                   the table.  Per element |dB - exact| <= (K + 2) 2^-24 |scale| sum_k |dW A| and
+ *                   |dA - exact| <= (N + 2) 2^-24 |scale| sum_n |B dW|.  scratch: scratch_floats of vbx_lora_plan. */
+typedef struct {
+  long w_off;        /* W in the flat parameter buffer, dW in the flat gradient buffer (floats) */
+  long w0_off;       /* W0 in the W0 store */
+  long a_off, b_off; /* A [r, K] and B [N, r] in lflat; dA and dB in glflat */
+  int N, K, r;
+  float scale;
+  long blk0, tile0, red0, pa_off, pb_off; /* filled by vbx_lora_plan: grid prefixes and the partials' places in scratch */
+} vbx_lora_desc;
+int vbx_lora_plan(vbx_lora_desc* descs_host, int n, long flat_floats, long w0_floats, long lflat_floats, long* apply_blocks,
+                  long* grad_tiles, long* reduce_blocks, long* scratch_floats, int* max_rank, int* max_k);
+int vbx_lora_apply(float* flat, const float* w0, const float* lflat, const vbx_lora_desc* descs_dev, int n, long apply_blocks, int max_k,
+                   void* stream);
+int vbx_lora_grad(const float* gflat, const float* lflat, float* glflat, const vbx_lora_desc* descs_dev, int n, long grad_tiles,
+                  long reduce_blocks, int max_rank, float* scratch, void* stream);
+
 /* ------------------------------------------------------------------ stage-level runtime
  * The whole VoiceBox forward / backward as native sequences of launches (no host sync, no allocation:
  * hipGraph-capturable).  Replaces VoiceBox.forward (voicebox_pytorch.py:987-1115) incl.

@@ -183,6 +183,9 @@ _PROTOS = {
     "vbx_attn_fwd_f32_dropout": [P, P, P, P, P, P, P, P, I, I, I, F, P, F, P],
     "vbx_geglu_f32": [P, P, P, P, P, L, I, P],
     "vbx_adaln_proj_f32": [P, P, P, P, I, I, I, I, P],
+    "vbx_lora_plan": [P, I, L, L, L, P, P, P, P, P, P],
+    "vbx_lora_apply": [P, P, P, P, I, L, I, P],
+    "vbx_lora_grad": [P, P, P, P, I, L, L, I, P, P],
     "vbx_probe_tr16": [P, P, P, P],
     "vbx_probe_mfma": [I, P, P, P, P],
 }

@@ -255,6 +255,86 @@ class WarmupCosineLR:
         return self.cur
 
 
+def trainable_ranges(fp, flags, exclude=()):
+    """Flat ranges [lo, hi) of the slots of `fp.order` whose flag is set, minus the `exclude` ranges: hi rounded up to 4 floats (the
+    padding behind a slot is never written: zeros in every gradient buffer), neighbours merged across that padding.  What the clip
+    norm of a partly frozen model is taken over (vbx_sumsq_ranges reads 16-byte groups)."""
+    out = []
+    excl = sorted(exclude)
+    for s, on in zip(fp.order, flags):
+        if not on:
+            continue
+        lo = fp.offsets[s]
+        hi = lo + (fp.slots[s].numel() + 3) // 4 * 4
+        if any(a <= lo and hi <= b for a, b in excl):
+            continue
+        nxt = (hi + 63) // 64 * 64
+        if out and out[-1][2] == lo:
+            out[-1][1], out[-1][2] = hi, nxt
+        else:
+            out.append([lo, hi, nxt])
+    return [(lo, hi) for lo, hi, _ in out]
+
+
+def range_chunks(ranges, limit=64):
+    """vbx_sumsq_ranges takes at most 64 ranges per launch: the list in launches of `limit`."""
+    return [ranges[i:i + limit] for i in range(0, len(ranges), limit)]
+
+
+def filter_adam_segments(segs, frozen):
+    """The vbx_adam_seg table of a partly frozen model.  segs: dicts with the fields of vbx_adam_seg (off, count, dst_bf16, dst_f16,
+    dst_f32, cols, dst_ld, rowmap, F) tiling the flat buffer; frozen: [lo, hi) slot ranges that must not be touched.  A segment
+    inside a frozen range is dropped (the table supports gaps: that is how the factor-form adaLN blocks are left out), one that
+    straddles is split.  A packed segment ([rows, cols] written to its operand copy) is cut at whole rows only -- the adaLN weight
+    block (four tensors of D rows each) and the one-row adaLN bias block are the packed segments that hold more than one tensor --
+    and the pieces' destinations move with them.  block0 is renumbered; returns (segments, total_blocks)."""
+    out = []
+    frozen = sorted(frozen)
+    for sg in segs:
+        lo, hi = sg["off"], sg["off"] + sg["count"]
+        keep, cur = [], lo
+        for a, b in frozen:
+            if b <= cur or a >= hi:
+                continue
+            if a > cur:
+                keep.append((cur, a))
+            cur = max(cur, b)
+        if cur < hi:
+            keep.append((cur, hi))
+        packed = bool(sg["dst_bf16"] or sg["dst_f16"] or sg["dst_f32"])
+        for a, b in keep:
+            if (a, b) == (lo, hi):
+                out.append(dict(sg))
+                continue
+            piece = dict(sg, off=a, count=b - a)
+            if packed:
+                cols, rows = sg["cols"], sg["count"] // sg["cols"]
+                if rows == 1:  # one row (the adaLN bias block): any cut, the piece is a shorter row further right
+                    shift, piece["cols"] = a - lo, b - a
+                else:
+                    assert sg["rowmap"] == 0 and (a - lo) % cols == 0 and (b - lo) % cols == 0, "a packed segment splits at whole rows only"
+                    shift = (a - lo) // cols * sg["dst_ld"]
+                for k, width in (("dst_bf16", 2), ("dst_f16", 2), ("dst_f32", 4)):
+                    if sg[k]:
+                        piece[k] = sg[k] + shift * width
+            out.append(piece)
+    blocks = 0
+    for sg in out:
+        sg["block0"] = blocks
+        blocks += 0 if sg["rowmap"] == 2 else (sg["count"] + 2047) // 2048
+    return out, blocks
+
+
+def adaln_rule(flags_by_slot, depth):
+    """What a partly frozen model does with the adaLN weight gradients: "all" (every G1W / B1W / G2W / B2W trainable: the factor path
+    as it is), "none" (all frozen: no factor Adam and no Gram terms; the backward may still leave the blocks unwritten) or "mixed"
+    (fall back to the materialised gradient)."""
+    fl = [flags_by_slot[f"L{l}.{n}"] for l in range(depth) for n in ("G1W", "B1W", "G2W", "B2W") if f"L{l}.{n}" in flags_by_slot]
+    if not fl or all(fl):
+        return "all"
+    return "none" if not any(fl) else "mixed"
+
+
 class TrainStep:
     def __init__(self, wrapper, lr=3e-4, betas=(0.9, 0.99), eps=1e-8, max_grad_norm=0.5, group=None,
                  bucket_bytes=64 << 20, broadcast_params=True, lr_schedule=None, grad_comm_dtype=None, wd=0., length_bucket=0,
@@ -272,7 +352,17 @@ class TrainStep:
         grad_mode: "allreduce" (DDP's exchange: every rank holds the summed gradient and runs the whole optimizer) or "shard"
         (reduce-scatter the buckets, each rank clips / Adams its 1 / world of the flat buffers, all-gather the updated fp32
         parameters, repack the operand copies in one pass): same results up to the summation order of the gradient norm, the
-        optimizer's 3.3 GB of HBM traffic per step divided by the world size."""
+        optimizer's 3.3 GB of HBM traffic per step divided by the world size.
+
+        Frozen parameters and LoRA adapters (one GPU).  The trainable set is the VoiceBox parameters with requires_grad=True, read
+        here and re-derived whenever the tuple of flags differs from the cached one (a host comparison).  A frozen tensor keeps its
+        bits, its m and v stay zero, it takes no part in the clip norm and gets no weight decay: the fused Adam runs over a filtered
+        segment table and the norm over the trainable ranges only.  adaLN weights: all trainable -> the factor path as it is; all
+        frozen -> no factor Adam, no Gram terms; mixed -> the step falls back to "materialize".  With adapters attached
+        (VoiceBox.add_lora) the step runs vbx_lora_grad after the backward, takes the norm over the trainable ranges plus the adapter
+        gradients, runs Adam on the adapters with the same coefficient and re-applies them (vbx_lora_apply).  With nothing frozen
+        and no adapters every launch and table is what it was.  Anything frozen or adapted together with a gradient exchange
+        (world > 1, VBX_FORCE_DIST) or grad_mode="shard" raises NotImplementedError, here or at the step that finds it."""
         assert grad_mode in ("allreduce", "shard"), grad_mode
         assert adaln_grads in ("auto", "factors", "materialize"), adaln_grads
         self.grad_mode = grad_mode
@@ -310,6 +400,53 @@ class TrainStep:
         # keys and the loss are all masked: voicebox_pytorch.py:220-233, attend.py:118-125, :1099-1115); 0 = exact lengths.
         self.length_bucket = int(length_bucket)
         self._stage_buf = None  # wire-dtype staging of the gradient exchange, allocated once (grad_comm_dtype only)
+        self._flags = None   # (requires_grad per slot of fp.order, id of the attached LoRA state) the filter below was built from
+        self._filter = None  # None: everything trainable, no adapters -- the step as it always was
+        self._refresh_trainable()
+
+    # -- frozen parameters and LoRA adapters
+    def _refresh_trainable(self):
+        """Re-derives the trainable set when the requires_grad flags (or the attached adapters) changed: host comparison, no sync."""
+        fp = self.fp
+        st = getattr(self.vb, "_lora", None)
+        flags = (tuple(bool(fp.slots[s].requires_grad) for s in fp.order), id(st) if st is not None else None)
+        if flags == self._flags:
+            return
+        on = flags[0]
+        if all(on) and st is None:
+            self._flags, self._filter, self._lora_rt = flags, None, None
+            self._wd_params = [p for p in self.vb.parameters() if p.requires_grad and p.ndim >= 2] if self.wd > 0 else []
+            return
+        what = "LoRA adapters" if st is not None else "frozen parameters (requires_grad=False)"
+        if self.exchange:
+            raise NotImplementedError(f"TrainStep: {what} together with a gradient exchange (world size > 1 or VBX_FORCE_DIST) are not "
+                                      "served: multi-rank fine-tuning is a follow-up -- fine-tune on one GPU")
+        if self.grad_mode == "shard":
+            raise NotImplementedError(f"TrainStep: {what} are not served by grad_mode='shard' -- use grad_mode='allreduce' on one GPU")
+        by_slot = dict(zip(fp.order, on))
+        rule = adaln_rule(by_slot, fp.depth)
+        adaln_blocks = self.adaln_weight_ranges() if any(s.endswith(".G1W") for s in fp.order) else []
+        ranges = trainable_ranges(fp, on)
+        ranges_fa = trainable_ranges(fp, on, exclude=adaln_blocks)  # what is read from gflat when the adaLN blocks are in factor form
+        if rule == "all" and not ranges_fa and st is None:
+            rule = "mixed"  # nothing but adaLN weights is trainable: the norm launch needs a range, so take the materialised gradient
+        # (with the padding up to the next slot, so that what is left of a plain segment starts on a slot boundary: 16-byte accesses)
+        frozen = [(fp.offsets[s], (fp.offsets[s] + fp.slots[s].numel() + 63) // 64 * 64) for s, f in zip(fp.order, on) if not f]
+        self._filter = dict(key=flags, ranges=ranges, ranges_factor=ranges_fa, adaln=rule, frozen=frozen, any_base=any(on))
+        self._wd_params = [p for p in self.vb.parameters() if p.requires_grad and p.ndim >= 2] if self.wd > 0 else []
+        self._lora_rt = None
+        if st is not None:
+            dev = fp.flat.device
+            lflat = st.ensure(dev)
+            tab = st.table()
+            old = getattr(self, "_lora_keep", None)  # the moments survive a refresh that keeps the same adapters
+            if old is not None and old["state"] is st and old["m"].numel() == lflat.numel() and old["m"].device == dev:
+                self._lora_rt = old
+            else:
+                self._lora_rt = dict(state=st, g=torch.zeros_like(lflat), m=torch.zeros_like(lflat), v=torch.zeros_like(lflat),
+                                     scratch=torch.zeros(max(1, tab.scratch_floats), device=dev))
+            self._lora_keep = self._lora_rt
+        self._flags = flags
 
     def _dirty(self, keep=None):
         """The flat parameter buffer was written behind PyTorch's version counters (native Adam, broadcast): bump the weights
@@ -324,6 +461,7 @@ class TrainStep:
     def accumulate(self, x1, weight, mask=None, cond_token_ids=None, input_sampling_rate=None, lens=None):
         """forward + backward of one micro-batch; gradients * weight are added to the accumulation buffer (no exchange).
         lens: see step."""
+        self._refresh_trainable()
         if getattr(self, "gacc", None) is None:
             self.gacc = torch.zeros_like(self.gflat)
             self.acc_coef = torch.zeros(1, device=self.gflat.device)
@@ -343,6 +481,8 @@ class TrainStep:
         batch falls back to the materialised gradient in "auto" mode (it used to raise after the backward)."""
         if self.adaln_grads == "materialize" or self.grad_mode == "shard":
             return False
+        if self._filter is not None and self._filter["adaln"] == "mixed":
+            return False  # some adaLN weights frozen, some not: the factor kernels serve whole blocks, so the gradient is materialised
         if self.adaln_grads == "auto" and os.environ.get("VBX_ADALN_FACTORS", "1") == "0":
             return False
         c = self.vb._cfg
@@ -390,6 +530,7 @@ class TrainStep:
         for exactly this micro-batch, trainer.py:258-272): as each backward stage completes, its slice of the accumulator is
         folded in (g = acc + weight * g) and the bucketed all-reduce of that slice starts while earlier layers are still running --
         instead of exchanging all 410 MB after the backward with nothing to overlap (apply_accumulated).  Then clip + Adam."""
+        self._refresh_trainable()
         if getattr(self, "gacc", None) is None or not getattr(self, "acc_pending", False):
             self.gacc = torch.zeros_like(self.gflat) if getattr(self, "gacc", None) is None else self.gacc
         red = self._reducer(self.grad_comm_dtype)
@@ -413,6 +554,7 @@ class TrainStep:
         """all-reduce (sum) of the accumulated gradients, clip, Adam; clears the accumulator.  (No backward is left to overlap the
         exchange with: prefer accumulate_last_and_apply for the window's last micro-batch.)"""
         assert getattr(self, "acc_pending", False), "nothing accumulated"
+        self._refresh_trainable()
         self.gflat.copy_(self.gacc)
         self.gacc.zero_()
         self.acc_pending = False
@@ -540,6 +682,8 @@ class TrainStep:
         red = getattr(self, "_red", None)
         if self.grad_mode == "shard" and red is not None and red.shard and red.active:
             return self._clip_adam_sharded(eng, lr, red)
+        if self._filter is not None:
+            return self._clip_adam_filtered(eng, lr, adaln_factors)
         if adaln_factors:
             folded = getattr(self, "_sq_folded", False)
             if not folded and self.scratch.numel() < eng.sumsq_scratch_floats(False):  # (folded: sized before the backward wrote into it)
@@ -564,6 +708,59 @@ class TrainStep:
             _lib.call("vbx_adam_step", self.fp.flat, self.gflat, self.m, self.v, n, float(lr if lr is not None else self.lr),
                       float(self.betas[0]), float(self.betas[1]), float(self.eps), self.steps, self.coef, st())
 
+    def _sumsq_filtered(self, eng, factor_terms):
+        """self.sumsq[0] = sum of squares over the trainable ranges of gflat (+ the adaLN Gram terms when those blocks are trainable and
+        in factor form, + the adapter gradient buffer): vbx_sumsq_ranges in launches of at most 64 ranges, every launch but the last
+        leaving its sum behind the Gram terms in the scratch, where the last one picks them up as extra values."""
+        import ctypes as C
+        from .engine import _rt, _check
+        f, lo = self._filter, self._lora_rt
+        st = _lib.current_stream()
+        nterms = eng.cfg["L"] * eng.B * eng.B if factor_terms else 0
+        launches = [(self.gflat, ch) for ch in range_chunks(f["ranges_factor"] if factor_terms else f["ranges"])]
+        if lo is not None:
+            launches.append((lo["g"], [(0, lo["g"].numel())]))
+        assert launches, "nothing is trainable"
+        need = 1024 + nterms + len(launches)
+        if self.scratch.numel() < need:
+            self.scratch = torch.zeros(need, device=self.scratch.device)
+        if factor_terms:
+            dada, temb, _, _, J4, Th = eng.adaln_factor_info()
+            _check(_rt().vbx_sumsq_adaln_factors(dada, temb, eng.cfg["L"], eng.B, J4, Th, self.scratch.data_ptr() + 4 * 1024, st),
+                   "vbx_sumsq_adaln_factors")
+        for i, (buf, ch) in enumerate(launches):
+            last = i + 1 == len(launches)
+            arr = (C.c_long * (2 * len(ch)))(*[x for r in ch for x in r])
+            out = self.sumsq.data_ptr() if last else self.scratch.data_ptr() + 4 * (1024 + nterms + i)
+            _check(_rt().vbx_sumsq_ranges(buf.data_ptr(), arr, len(ch), (nterms + i) if last else 0, out, self.scratch.data_ptr(), st),
+                   "vbx_sumsq_ranges")
+
+    def _clip_adam_filtered(self, eng, lr, adaln_factors):
+        """clip + Adam of a partly frozen and / or adapted model (one GPU): vbx_lora_grad, the norm over what is trainable,
+        vbx_clip_coef, the filtered fused Adam on the base, vbx_adam_step on the adapters with the same coefficient, vbx_lora_apply."""
+        f, lo = self._filter, self._lora_rt
+        st = _lib.current_stream
+        rate = float(lr if lr is not None else self.lr)
+        factor_terms = bool(adaln_factors) and f["adaln"] == "all"
+        if lo is not None:
+            state = lo["state"]
+            lflat = state.ensure(self.fp.flat.device)
+            state.table().grad(self.gflat, lflat, lo["g"], lo["scratch"])
+        self._sumsq_filtered(eng, factor_terms)
+        _lib.call("vbx_clip_coef", self.sumsq, float(self.max_grad_norm or 0.0), 1.0 / self.world, self.coef, st())
+        if self._wd_params:
+            with torch.no_grad():
+                torch._foreach_mul_(self._wd_params, 1.0 - rate * self.wd)
+            eng.packed_version = self.fp.weights_key()  # (as in _clip_adam; with adapters the apply below makes every engine repack)
+        if f["any_base"]:
+            eng.adam_step_packed(self.gflat, self.m, self.v, rate, self.betas[0], self.betas[1], self.eps, self.steps, self.coef,
+                                 adaln_factors=adaln_factors, trainable=f, factor_adam=factor_terms)
+        if lo is not None:
+            _lib.call("vbx_adam_step", lflat, lo["g"], lo["m"], lo["v"], lflat.numel(), rate, float(self.betas[0]), float(self.betas[1]),
+                      float(self.eps), self.steps, self.coef, st())
+            state.needs_apply = True
+            state.apply()  # W_eff = W0 + s . B . A into the master slots; bumps the weights epoch: every engine and sampler repacks
+
     def step(self, x1, mask=None, lr=None, cond_token_ids=None, input_sampling_rate=None, lens=None):
         """x1: (B_local, frames, dim) on this rank's GPU, or a wave batch (B_local, samples) for a model built with audio_enc_dec
         (cond_token_ids (B_local, tokens) for a text-conditioned model); input_sampling_rate: the rate of such waves, for a wrapper built
@@ -573,11 +770,13 @@ class TrainStep:
         (ConditionalFlowMatcherWrapper.forward).  With text conditioning it counts frames, not tokens.
         Returns the (un-synchronised) local loss tensor."""
         # --- backward with overlapped gradient exchange
+        self._refresh_trainable()
         factors = self.adaln_factors_apply(batch=int(x1.shape[0])) and os.environ.get("VBX_FUSED_ADAM", "1") != "0"
         red = self._reducer(self.grad_comm_dtype, skip_adaln=factors and self.exchange)
         # one GPU, factor form: the slab reduce also leaves the sums of squares of what it stores (no second pass over the big
         # weight gradients for the clip norm); VBX_SUMSQ_FOLD=0: A/B
-        fold = factors and not self.exchange and os.environ.get("VBX_SUMSQ_FOLD", "1") != "0"
+        # (a partly frozen or adapted model takes the plain path: the fold's partials cover all four big matrices of every layer)
+        fold = factors and not self.exchange and os.environ.get("VBX_SUMSQ_FOLD", "1") != "0" and self._filter is None
         loss = self._forward_backward(x1, mask, cond_token_ids, on_stage=red.stage_done if self.exchange else None, adaln_factors=factors,
                                       sq_fold=fold, input_sampling_rate=input_sampling_rate, lens=lens)
         if factors and self.exchange:  # the factors travel (one small all-gather) while the last buckets are still in flight

@@ -408,34 +408,58 @@ class Engine:
         arr, nr = cache[bool(nsq)]
         _check(l.vbx_sumsq_ranges(gflat.data_ptr(), arr, nr, nterms + nsq, out.data_ptr(), scratch.data_ptr(), st), "vbx_sumsq_ranges")
 
+    def _adam_segments_host(self, adaln_factors):
+        """(host table of vbx_adam_seg, total blocks) of vbx_model_adam_segments for this arena"""
+        l = _rt()
+        self.m.adaln_factors = int(bool(adaln_factors))
+        try:
+            nblocks = C.c_long(0)
+            n = l.vbx_model_adam_segments(C.byref(self.m), self.fp.flat.numel(), None, 0, C.byref(nblocks))
+            if n <= 0:
+                _check(n if n < 0 else -1, "vbx_model_adam_segments")
+            tab = (VbxAdamSeg * n)()
+            assert l.vbx_model_adam_segments(C.byref(self.m), self.fp.flat.numel(), tab, n, C.byref(nblocks)) == n
+        finally:
+            self.m.adaln_factors = 0
+        return tab, nblocks.value
+
     # -- optimizer: Adam over the flat buffers that also refreshes this engine's packed operand copies
-    def adam_step_packed(self, gflat, m, v, lr, beta1, beta2, eps, step, gscale, adaln_factors=False):
+    def adam_step_packed(self, gflat, m, v, lr, beta1, beta2, eps, step, gscale, adaln_factors=False, trainable=None, factor_adam=None):
         """adaln_factors=True: the adaLN weight blocks are updated from their factor-form gradients (the last backward ran with
-        adaln_factors) by a second launch; the fused launch leaves them out."""
+        adaln_factors) by a second launch; the fused launch leaves them out.
+        trainable (dp.TrainStep of a partly frozen model): dict with `key` (hashable) and `frozen` ([lo, hi) slot ranges) -- the
+        segment table is filtered (dp.filter_adam_segments) so that the launch never touches a frozen range; factor_adam=False
+        then also skips the factor-form launch (all adaLN weights frozen)."""
         l = _rt()
         flat = self.fp.flat
         self.bind_params()  # the packed arena must be current before it is updated incrementally
         cache = self.__dict__.setdefault("_adam_segs_by_mode", {})
-        if bool(adaln_factors) not in cache:
-            self.m.adaln_factors = int(bool(adaln_factors))
-            try:
-                nblocks = C.c_long(0)
-                n = l.vbx_model_adam_segments(C.byref(self.m), flat.numel(), None, 0, C.byref(nblocks))
-                if n <= 0:
-                    _check(n if n < 0 else -1, "vbx_model_adam_segments")
-                tab = (VbxAdamSeg * n)()
-                n2 = l.vbx_model_adam_segments(C.byref(self.m), flat.numel(), tab, n, C.byref(nblocks))
-                assert n2 == n
-            finally:
-                self.m.adaln_factors = 0
-            raw = torch.frombuffer(bytearray(bytes(tab)), dtype=torch.uint8).to(self.device)
-            cache[bool(adaln_factors)] = (raw, n, nblocks.value)
-        raw, n, nblocks = cache[bool(adaln_factors)]
+        if factor_adam is None:
+            factor_adam = bool(adaln_factors)
+        ckey = bool(adaln_factors) if trainable is None else (bool(adaln_factors), trainable["key"])
+        if ckey not in cache:
+            tab, nblocks = self._adam_segments_host(adaln_factors)
+            n = len(tab)
+            if trainable is not None:
+                from .dp import filter_adam_segments
+
+                for k in [k for k in cache if isinstance(k, tuple)]:
+                    cache.pop(k)  # one filtered table at a time
+                names = [f for f, _ in VbxAdamSeg._fields_]
+                rows, nblocks = filter_adam_segments([{f: (getattr(sg, f) or 0) for f in names} for sg in tab], trainable["frozen"])
+                n = len(rows)
+                tab = (VbxAdamSeg * max(1, n))()
+                for dst, row in zip(tab, rows):
+                    for f in names:
+                        setattr(dst, f, (row[f] or None) if f in ("dst_bf16", "dst_f16", "dst_f32") else row[f])
+            cache[ckey] = (torch.frombuffer(bytearray(bytes(tab)), dtype=torch.uint8).to(self.device), n, nblocks)
+        raw, n, nblocks = cache[ckey]
         gs = gscale.data_ptr() if gscale is not None else None
-        _check(l.vbx_adam_step_packed(flat.data_ptr(), gflat.data_ptr(), m.data_ptr(), v.data_ptr(), raw.data_ptr(), n, nblocks,
-                                      float(lr), float(beta1), float(beta2), float(eps), int(step), gs, _lib.current_stream()),
-               "vbx_adam_step_packed")
-        if adaln_factors:
+        if n > 0 and nblocks > 0:  # (a filtered table may be empty: nothing but adaLN weights in factor form is trainable)
+            _check(l.vbx_adam_step_packed(flat.data_ptr(), gflat.data_ptr(), m.data_ptr(), v.data_ptr(), raw.data_ptr(), n, nblocks,
+                                          float(lr), float(beta1), float(beta2), float(eps), int(step), gs, _lib.current_stream()),
+                   "vbx_adam_step_packed")
+        if adaln_factors and factor_adam:
             dada, temb, woff, dst, J4, Th = self.adaln_factor_info()
             _check(l.vbx_adam_adaln_factors(flat.data_ptr(), m.data_ptr(), v.data_ptr(), woff, dst, dada, temb, self.cfg["L"], self.B, J4,
                                             Th, float(lr), float(beta1), float(beta2), float(eps), int(step), gs, _lib.current_stream()),

@@ -295,6 +295,9 @@ class Transformer(nn.Module):
             s[p + "FF1W"], s[p + "FF1B"], s[p + "FF2W"], s[p + "FF2B"] = ff[0].weight, ff[0].bias, ff[3].weight, ff[3].bias
         return s
 
+    def add_lora(self, *args, **kwargs):
+        raise NotImplementedError("LoRA adapters are served on a VoiceBox (VoiceBox.add_lora), not on the stand-alone Transformer")
+
     def _slots(self):
         s = {"FNG": self.final_norm.gamma}
         if self.has_register_tokens:
@@ -453,6 +456,38 @@ class VoiceBox(nn.Module):
                          Lc=int(latent_dim) if codec_proj else 0)
         self._flat = None
         self._engines = {}
+        self._lora = None  # lora.LoraState while adapters are attached (add_lora)
+
+    # ---- LoRA adapters on the master weights (lora.py)
+    def add_lora(self, rank=16, alpha=16., targets=("to_qkv", "to_out", "ff_in", "ff_out"), layers=None, train_base=False):
+        """Attaches LoRA adapters W0 + (alpha / rank) . B . A to the targets (the four big matrices of a layer) of `layers` (None: all):
+        nn.Parameters lora_A [rank, in] (initialised as nn.Linear initialises a weight) and lora_B [out, rank] (zero) on the adapted
+        nn.Linear modules.  Every other parameter is frozen unless train_base=True (individual tensors may be re-enabled:
+        dp.TrainStep honours requires_grad); the adapted matrices themselves are always frozen.  While attached, state_dict() holds
+        W0 under the reference's keys plus the adapter keys, and the adapters train through dp.TrainStep / VoiceBoxTrainer only."""
+        from . import lora
+
+        return lora.add_lora(self, rank, alpha, targets, layers, train_base)
+
+    def lora_state_dict(self):
+        from . import lora
+
+        return lora.lora_state_dict(self)
+
+    def load_lora_state_dict(self, sd):
+        from . import lora
+
+        return lora.load_lora_state_dict(self, sd)
+
+    def merge_lora(self):
+        from . import lora
+
+        return lora.merge_lora(self)
+
+    def detach_lora(self):
+        from . import lora
+
+        return lora.detach_lora(self)
 
     # ---- native plumbing
     def _slots(self):
@@ -488,6 +523,10 @@ class VoiceBox(nn.Module):
             raise _lib.VbxError("VoiceBox compute runs only on an MI355X (gfx950) through libvbx_hip.so; "
                                 f"parameters are on '{dev}' and there is no CPU fallback")
         precise = precise_enabled()
+        if self._lora is not None:
+            if precise:
+                raise NotImplementedError("precise mode does not serve LoRA adapters -- leave precise mode, or merge_lora() first")
+            self._lora.sync()  # host check: a pending merge (loaded on the CPU) or an adapter written through its parameter
         if precise and self._cfg["Lc"]:
             raise NotImplementedError("precise mode does not serve codec-latent models (audio_enc_dec with latent_dim != dim: the "
                                       "proj_in product runs on the fast path only) -- leave precise mode to call them")
@@ -524,6 +563,9 @@ class VoiceBox(nn.Module):
         them -- that their fp16 / bf16 packed operand copies are stale.  Writes through the parameters themselves (optimizer steps,
         load_state_dict, p.copy_()) and this package's own training step are detected automatically."""
         self.flat_params().bump()
+        if self._lora is not None:  # an adapter may have been the tensor written: W_eff = W0 + s . B . A again
+            self._lora.needs_apply = True
+            self._lora.apply()
 
     @property
     def device(self):
@@ -596,6 +638,10 @@ class VoiceBox(nn.Module):
         target = target.to(dev, torch.float32)
         loss_mask = reduce_masks_with_and(cond_mask, self_attn_mask)  # :1099
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            if self._lora is not None:
+                from .lora import refuse_autograd
+
+                refuse_autograd(self)
             # The reference's autograd keeps any number of graphs alive (voicebox_pytorch.py:1416-1425); an activation arena holds ONE
             # training forward.  Two arenas per shape form a ring: a second forward before the first one's backward (two micro-batch
             # losses summed before .backward(), a regulariser evaluated on a second input) takes the other arena, which shares the
@@ -882,6 +928,10 @@ class ConditionalFlowMatcherWrapper(nn.Module):
         gradients, bit for bit), and the attention forward and backward stop at each row's length instead of masking the padding
         after the products.  Not with mask, not with raw audio (encode first, or pass mask).  A list or CPU tensor is validated on the
         host; a device tensor is clamped into 1 .. N on the device without a host synchronisation."""
+        if self.voicebox._lora is not None and torch.is_grad_enabled() and any(p.requires_grad for p in self.voicebox.parameters()):
+            from .lora import refuse_autograd
+
+            refuse_autograd(self.voicebox)  # before anything is launched
         if exists(lens):
             from . import train_lens
 

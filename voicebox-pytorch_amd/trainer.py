@@ -68,6 +68,20 @@ def get_dataloader(ds, pad_to_longest=True, with_lens=False, **kwargs):  # data.
     return DataLoader(ds, collate_fn=_collate(pad_to_longest, with_lens), **kwargs)
 
 
+def _adapter_moments(ts):
+    """{id(adapter parameter): (exp_avg view, exp_avg_sq view)} of the LoRA adapters a TrainStep trains (empty without adapters)."""
+    if not hasattr(ts, "_refresh_trainable"):
+        return {}
+    ts._refresh_trainable()
+    lo = getattr(ts, "_lora_rt", None)
+    out = {}
+    if lo is not None:
+        for e in lo["state"].entries:
+            for p, off in ((e["module"].lora_A, e["a_off"]), (e["module"].lora_B, e["b_off"])):
+                out[id(p)] = (lo["m"][off:off + p.numel()].view(p.shape), lo["v"][off:off + p.numel()].view(p.shape))
+    return out
+
+
 class VoiceBoxTrainer(nn.Module):
     def __init__(self, cfm_wrapper: ConditionalFlowMatcherWrapper, *, batch_size, dataset: Dataset, num_train_steps=None,
                  num_warmup_steps=None, num_epochs=None, lr=3e-4, initial_lr=1e-5, grad_accum_every=1, wd=0., max_grad_norm=0.5,
@@ -162,8 +176,13 @@ class VoiceBoxTrainer(nn.Module):
         by_param = {id(fp.slots[s]): s for s in fp.order}
         state = {}
         params, n_wd = self._optim_param_order()
+        adapters = _adapter_moments(self.train_step_fn)
         for i, p in enumerate(params):
             s = by_param.get(id(p))
+            if s is None and id(p) in adapters and ts.steps > 0:  # a LoRA adapter: its moments live beside the adapter buffer
+                state[i] = {'step': torch.tensor(float(ts.steps)), 'exp_avg': adapters[id(p)][0].clone(),
+                            'exp_avg_sq': adapters[id(p)][1].clone()}
+                continue
             if s is None or ts.steps == 0:
                 continue  # parameters that never received a gradient (null_cond) have no Adam state, as in torch
             o, n = fp.offsets[s], p.numel()
@@ -195,9 +214,15 @@ class VoiceBoxTrainer(nn.Module):
             st = sd['state'].get(i)
             if st is not None and (tuple(st['exp_avg'].shape) != tuple(p.shape) or tuple(st['exp_avg_sq'].shape) != tuple(p.shape)):
                 raise ValueError(f"optimizer state {i} has shape {tuple(st['exp_avg'].shape)}, parameter has {tuple(p.shape)}")
+        adapters = _adapter_moments(self.train_step_fn)
         for i, p in enumerate(params):
             st = sd['state'].get(i)
             s = by_param.get(id(p))
+            if st is not None and s is None and id(p) in adapters:
+                adapters[id(p)][0].copy_(st['exp_avg'])
+                adapters[id(p)][1].copy_(st['exp_avg_sq'])
+                steps = max(steps, int(float(st['step'])))
+                continue
             if st is None or s is None:
                 continue
             o, n = fp.offsets[s], p.numel()
