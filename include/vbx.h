@@ -912,6 +912,30 @@ int vbx_sumsq_ranges(const float* x, const long* ranges /* host [2 n] */, int n,
 int vbx_adam_adaln_factors(float* p, float* m, float* v, const long* w_off /* host [L] */, void* const* dst_f16 /* host [L] or NULL */,
                            const float* dada, const float* temb, int L, int B, int J4, int Th, float lr, float beta1, float beta2,
                            float eps, int step, const float* gscale, void* stream);
+/* ---- EMA of the weights inside the Adam launches (dp.TrainStep(ema_decay=)).  The three _ema entry points are the Adam entry points
+ * above with two more arguments behind v: `ema`, an fp32 buffer with the layout of p, and the decay d = ema_decay.  The thread that
+ * stores the updated fp32 weight p' (and its fp16 / bf16 copies) also reads and writes the element of `ema` at the same index:
+ *     e' = fmaf(d, e - p', p')                                   (fp32; one subtraction, one fused multiply-add)
+ * Rules that take no tolerance: d == 0 stores the bits of p'; e == p' stores the bits of p' (p' = -0 excepted: the sum is +0); an
+ * element the launch does not touch -- a frozen range or a gap the segment table leaves out, padding, anything behind n -- keeps its
+ * bits; reruns are bit-identical (no atomics).  Per element, given the device's own p' and the previous e,
+ *     |e' - exact| <= u (d |e - p'| + |exact|),   exact = p' + d (e - p'),   u = 2^-24
+ * (two roundings: the subtraction's, scaled by d, and the fused multiply-add's).  p, m, v and every operand copy get the bits the entry point without _ema gives them; those
+ * entry points and the kernels they launch are unchanged (the EMA = false instantiation of the same template).
+ * Refused (VBX_EINVAL, nothing launched): ema == NULL, ema == p, an `ema` whose address differs from p's modulo 16 bytes (the 16-byte
+ * accesses of the vector arms are taken at the same element index in both), ema_decay outside [0, 1), and whatever the entry point
+ * without _ema refuses. */
+int vbx_adam_step_ema(float* p, const float* g, float* m, float* v, float* ema, float ema_decay, long n, float lr, float beta1,
+                      float beta2, float eps, int step, const float* gscale, void* stream);
+int vbx_adam_step_packed_ema(float* p, const float* g, float* m, float* v, float* ema, float ema_decay, const vbx_adam_seg* segs_dev,
+                             int nsegs, long total_blocks, float lr, float beta1, float beta2, float eps, int step, const float* gscale,
+                             void* stream);
+int vbx_adam_adaln_factors_ema(float* p, float* m, float* v, float* ema, float ema_decay, const long* w_off /* host [L] */,
+                               void* const* dst_f16 /* host [L] or NULL */, const float* dada, const float* temb, int L, int B, int J4,
+                               int Th, float lr, float beta1, float beta2, float eps, int step, const float* gscale, void* stream);
+/* a[i] <-> b[i] for i < n, in place: 16-byte accesses when both pointers are 16-byte aligned (scalar ones otherwise) and a scalar
+ * tail of n % 4 elements.  The buffers must not overlap; n > 0.  (TrainStep.ema_weights() serves the average without a temporary.) */
+int vbx_swap_f32(float* a, float* b, long n, void* stream);
 /* gradient-clip coefficient for a buffer holding the SUM over `world` ranks (inv_world = 1/world):
  * norm = sqrt(sumsq)*inv_world; coef[0] = min(1, max_norm/(norm+1e-6)) * inv_world (max_norm <= 0: no clipping);
  * coef[1] = norm.  (accelerator.clip_grad_norm_, trainer.py:274-275) */

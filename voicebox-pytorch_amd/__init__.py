@@ -26,13 +26,14 @@ try:  # model classes need torch; keep `_lib` importable on its own
     from .seanet import CausalSEANetDecoder, CausalSEANetEncoder, SEANetDecoder, SEANetEncoder  # noqa: F401
     from .align import maximum_path, forward_sum_loss, ForwardSumLoss, Aligner, aligner_attention  # noqa: F401
     from .engine import precise_mode, set_precise, precise_enabled  # noqa: F401
+    from .dp import ema_decay_at  # noqa: F401  (the decay schedule of dp.TrainStep(ema_decay=))
     from . import lora  # noqa: F401  (VoiceBox.add_lora / lora_state_dict / load_lora_state_dict / merge_lora / detach_lora)
 
     __all__ += ["VoiceBox", "ConditionalFlowMatcherWrapper", "Transformer", "Attend", "VoiceBoxTrainer", "DurationPredictor", "mask_from_frac_lengths",
                 "mask_from_start_end_indices", "prob_mask_like", "reduce_masks_with_and", "precise_mode", "set_precise", "precise_enabled",
                 "AudioEncoderDecoder", "LogMelCodec", "griffin_lim", "resample", "Resample", "VocosDecoder", "VocosEncodecDecoder", "ResidualVQ", "EncodecVocoCodec", "SEANetEncoder", "SEANetDecoder",
                 "CausalSEANetEncoder", "CausalSEANetDecoder",
-                "maximum_path", "forward_sum_loss", "ForwardSumLoss", "Aligner", "aligner_attention", "lora"]
+                "maximum_path", "forward_sum_loss", "ForwardSumLoss", "Aligner", "aligner_attention", "lora", "ema_decay_at"]
 except ModuleNotFoundError as _e:  # pragma: no cover - only while the package is being bootstrapped
     if "masks" not in str(_e) and "model" not in str(_e):
         raise

@@ -174,6 +174,8 @@ _PROTOS = {
     "vbx_pack_weight": [P, I, I, P, P, I, I, I, I, P],
     "vbx_pack_bias": [P, I, P, I, I, I, P],
     "vbx_adam_step": [P, P, P, P, L, F, F, F, F, I, P, P],
+    "vbx_adam_step_ema": [P, P, P, P, P, F, L, F, F, F, F, I, P, P],
+    "vbx_swap_f32": [P, P, L, P],
     "vbx_sumsq": [P, L, P, P, P],
     "vbx_clip_coef": [P, F, F, P, P],
     "vbx_split3_f16": [P, L, I, L, P, I, P],

@@ -1263,10 +1263,17 @@ VBX_DEV float adam_one(float pv, float gv, float& mv, float& vv, const AdamCoef&
   // torch.optim.Adam: p -= lr/bc1 * m / (sqrt(v)/sqrt(bc2) + eps)
   return pv - k.lr_bc1 * mv / (sqrtf(vv) / k.bc2_sqrt + k.eps);
 }
+// EMA of the weights (include/vbx.h "EMA"): e' = fmaf(d, e - p', p') with the p' this thread has just stored
+VBX_DEV float ema_one(float e, float pn, float d) { return fmaf(d, e - pn, pn); }
+VBX_DEV float4 ema_four(float4 e, float4 pn, float d) {
+  return make_float4(ema_one(e.x, pn.x, d), ema_one(e.y, pn.y, d), ema_one(e.z, pn.z, d), ema_one(e.w, pn.w, d));
+}
+// EMA = true (vbx_adam_step_packed_ema): the same launch also reads and writes `ema` where it writes p; EMA = false never looks at it
+template <bool EMA>
 __global__ __launch_bounds__(256) void adam_packed_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                           float* __restrict__ v, const vbx_adam_seg* __restrict__ segs, int nsegs,
                                                           float lr_bc1, float b1, float b2, float eps, float bc2_sqrt,
-                                                          const float* __restrict__ gscale) {
+                                                          const float* __restrict__ gscale, float* __restrict__ ema, float ed) {
   // segment of this block: last s with segs[s].block0 <= blockIdx.x
   int lo = 0, hi = nsegs - 1;
   while (lo < hi) {
@@ -1291,6 +1298,8 @@ __global__ __launch_bounds__(256) void adam_packed_kernel(float* __restrict__ p,
       const float4 gv = *reinterpret_cast<const float4*>(g + i);
       float4 mv = *reinterpret_cast<const float4*>(m + i), vv = *reinterpret_cast<const float4*>(v + i);
       float4 pv = *reinterpret_cast<const float4*>(p + i);
+      float4 ev;
+      if constexpr (EMA) ev = *reinterpret_cast<const float4*>(ema + i);
       pv.x = adam_one(pv.x, gv.x, mv.x, vv.x, k);
       pv.y = adam_one(pv.y, gv.y, mv.y, vv.y, k);
       pv.z = adam_one(pv.z, gv.z, mv.z, vv.z, k);
@@ -1298,6 +1307,7 @@ __global__ __launch_bounds__(256) void adam_packed_kernel(float* __restrict__ p,
       *reinterpret_cast<float4*>(m + i) = mv;
       *reinterpret_cast<float4*>(v + i) = vv;
       *reinterpret_cast<float4*>(p + i) = pv;
+      if constexpr (EMA) *reinterpret_cast<float4*>(ema + i) = ema_four(ev, pv, ed);
       if (packed) {
         const int r = (int)(j / sg.cols), c = (int)(j - (long)r * sg.cols);
         int dr = r;
@@ -1325,6 +1335,17 @@ __global__ __launch_bounds__(256) void adam_packed_kernel(float* __restrict__ p,
           if (sg.dst_f32) sg.dst_f32[o] = pn;
         }
       }
+      if constexpr (EMA) {
+        // (a pass of its own.  It reads back the weights this thread has just stored -- a volatile load, a cache hit on an
+        // arm that only tails and odd segments take: with the values handed over in registers, the fmaf call made the vectoriser
+        // look at the Adam arithmetic behind its operand and pair b1 * m with (1 - b1) * g into one packed multiply)
+        if (ema) {
+          for (int e = 0; e < 4 && j + e < sg.count; e++) {
+            const float pn = *reinterpret_cast<const volatile float*>(p + i + e);
+            ema[i + e] = ema_one(ema[i + e], pn, ed);
+          }
+        }
+      }
     }
   }
 }
@@ -1346,9 +1367,13 @@ struct AdaFactorArgs {
   const float* temb;  // [B][Th]
   int L, B, J4, Th;
 };
+// EMA = true (vbx_adam_adaln_factors_ema): two more float4[G] groups, the average of the rows in flight and of the next group
+// (profiles/ema_kernel_resources.txt: no scratch in either instantiation)
+template <bool EMA>
 __global__ __launch_bounds__(256) void adam_adaln_factor_kernel(float* __restrict__ p, float* __restrict__ m, float* __restrict__ v,
                                                                 const AdaFactorArgs a, float lr_bc1, float b1, float b2, float eps,
-                                                                float bc2_sqrt, const float* __restrict__ gscale) {
+                                                                float bc2_sqrt, const float* __restrict__ gscale,
+                                                                float* __restrict__ ema, float ed) {
   const int l = blockIdx.z, r0 = blockIdx.y * ADAF_ROWS;
   const int c_raw = (blockIdx.x * 256 + threadIdx.x) * 4;
   const bool cv = c_raw < a.Th;       // threads past the row stay in the block (barriers below) with a clamped column and no stores
@@ -1359,11 +1384,12 @@ __global__ __launch_bounds__(256) void adam_adaln_factor_kernel(float* __restric
   const int nrows = min(ADAF_ROWS, a.J4 - r0);
   // the optimizer state of the block's first rows is requested BEFORE the gradient is expanded (their latency hides under the FMAs)
   constexpr int G = 4;  // rows whose p / m / v are in flight together
-  float4 pv[G], mv[G], vv[G];
+  float4 pv[G], mv[G], vv[G], ev[G];
 #pragma unroll
   for (int r = 0; r < G; r++) {
     const long i = base + (long)min(r, nrows - 1) * a.Th;
     pv[r] = *reinterpret_cast<const float4*>(p + i); mv[r] = *reinterpret_cast<const float4*>(m + i); vv[r] = *reinterpret_cast<const float4*>(v + i);
+    if constexpr (EMA) ev[r] = *reinterpret_cast<const float4*>(ema + i);
   }
   float4 acc[ADAF_ROWS];
 #pragma unroll
@@ -1392,12 +1418,13 @@ __global__ __launch_bounds__(256) void adam_adaln_factor_kernel(float* __restric
   u16* dh = a.dst_f16[l];
 #pragma unroll
   for (int g0 = 0; g0 < ADAF_ROWS; g0 += G) {
-    float4 pn[G], mn[G], vn[G];
+    float4 pn[G], mn[G], vn[G], en[G];
     if (g0 + G < ADAF_ROWS) {  // next group's state: requested before this group is computed and stored
 #pragma unroll
       for (int r = 0; r < G; r++) {
         const long i = base + (long)min(g0 + G + r, nrows - 1) * a.Th;
         pn[r] = *reinterpret_cast<const float4*>(p + i); mn[r] = *reinterpret_cast<const float4*>(m + i); vn[r] = *reinterpret_cast<const float4*>(v + i);
+        if constexpr (EMA) en[r] = *reinterpret_cast<const float4*>(ema + i);
       }
     }
 #pragma unroll
@@ -1412,12 +1439,16 @@ __global__ __launch_bounds__(256) void adam_adaln_factor_kernel(float* __restric
         *reinterpret_cast<float4*>(m + i) = mv[r];
         *reinterpret_cast<float4*>(v + i) = vv[r];
         *reinterpret_cast<float4*>(p + i) = pv[r];
+        if constexpr (EMA) *reinterpret_cast<float4*>(ema + i) = ema_four(ev[r], pv[r], ed);
         if (dh) *reinterpret_cast<uint2*>(dh + (long)(r0 + g0 + r) * a.Th + c) = make_uint2(pack_f16x2(pv[r].x, pv[r].y), pack_f16x2(pv[r].z, pv[r].w));
       }
     }
     if (g0 + G < ADAF_ROWS) {
 #pragma unroll
-      for (int r = 0; r < G; r++) { pv[r] = pn[r]; mv[r] = mn[r]; vv[r] = vn[r]; }
+      for (int r = 0; r < G; r++) {
+        pv[r] = pn[r]; mv[r] = mn[r]; vv[r] = vn[r];
+        if constexpr (EMA) ev[r] = en[r];
+      }
     }
   }
 }
@@ -1517,9 +1548,10 @@ __global__ __launch_bounds__(256) void sumsq_ranges_stage1(const float* __restri
   __syncthreads();
   if (threadIdx.x == 0) scratch[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
 }
+template <bool EMA>
 __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                             long n, float lr, float b1, float b2, float eps, float bc1, float bc2_sqrt,
-                            const float* __restrict__ gscale) {
+                            const float* __restrict__ gscale, float* __restrict__ ema, float ed) {
   const float gs = gscale ? gscale[0] : 1.0f;
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
     const float gr = g[i] * gs;
@@ -1529,7 +1561,25 @@ __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, 
     v[i] = vv;
     // torch.optim.Adam: p -= lr/bc1 * m / (sqrt(v)/sqrt(bc2) + eps)
     const float denom = sqrtf(vv) / bc2_sqrt + eps;
-    p[i] -= (lr / bc1) * mm / denom;
+    const float pn = p[i] - (lr / bc1) * mm / denom;
+    p[i] = pn;
+    if constexpr (EMA) ema[i] = ema_one(ema[i], pn, ed);
+  }
+}
+// a <-> b element by element, in place (TrainStep.ema_weights: the averaged weights are served without a second copy of the model):
+// 16-byte accesses over the first n4 groups (0 when a pointer is not 16-byte aligned), scalar accesses over the rest
+__global__ __launch_bounds__(256) void swap_f32_kernel(float* __restrict__ a, float* __restrict__ b, long n, long n4) {
+  float4* a4 = reinterpret_cast<float4*>(a);
+  float4* b4 = reinterpret_cast<float4*>(b);
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+    const float4 x = a4[i], y = b4[i];
+    a4[i] = y;
+    b4[i] = x;
+  }
+  for (long i = n4 * 4 + blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    const float x = a[i], y = b[i];
+    a[i] = y;
+    b[i] = x;
   }
 }
 __global__ __launch_bounds__(256) void sumsq_stage1(const float* __restrict__ x, long n, float* __restrict__ scratch) {
@@ -2131,8 +2181,22 @@ extern "C" int vbx_adam_step_packed(float* p, const float* g, float* m, float* v
   VBX_REQUIRE(p && g && m && v && segs_dev && nsegs > 0 && total_blocks > 0 && step >= 1, "vbx_adam_step_packed: bad args");
   const float bc1 = 1.0f - powf(beta1, (float)step);
   const float bc2 = 1.0f - powf(beta2, (float)step);
-  hipLaunchKernelGGL(adam_packed_kernel, dim3((unsigned)total_blocks), dim3(256), 0, ST, p, g, m, v, segs_dev, nsegs, lr / bc1, beta1,
-                     beta2, eps, sqrtf(bc2), gscale);
+  hipLaunchKernelGGL(adam_packed_kernel<false>, dim3((unsigned)total_blocks), dim3(256), 0, ST, p, g, m, v, segs_dev, nsegs, lr / bc1,
+                     beta1, beta2, eps, sqrtf(bc2), gscale, (float*)nullptr, 0.0f);
+  VBX_LAUNCH_CHECK();
+  return 0;
+}
+// the _ema entry points: `ema` follows p (same layout, same alignment), 0 <= ema_decay < 1
+static bool ema_args_ok(const float* p, const float* ema, float d) { return ema && ema != p && (((size_t)ema ^ (size_t)p) & 15) == 0 && d >= 0.0f && d < 1.0f; }
+extern "C" int vbx_adam_step_packed_ema(float* p, const float* g, float* m, float* v, float* ema, float ema_decay,
+                                        const vbx_adam_seg* segs_dev, int nsegs, long total_blocks, float lr, float beta1, float beta2,
+                                        float eps, int step, const float* gscale, void* stream) {
+  VBX_REQUIRE(p && g && m && v && segs_dev && nsegs > 0 && total_blocks > 0 && step >= 1, "vbx_adam_step_packed_ema: bad args");
+  VBX_REQUIRE(ema_args_ok(p, ema, ema_decay), "vbx_adam_step_packed_ema: ema must be a buffer aligned like p, ema_decay in [0, 1)");
+  const float bc1 = 1.0f - powf(beta1, (float)step);
+  const float bc2 = 1.0f - powf(beta2, (float)step);
+  hipLaunchKernelGGL(adam_packed_kernel<true>, dim3((unsigned)total_blocks), dim3(256), 0, ST, p, g, m, v, segs_dev, nsegs, lr / bc1,
+                     beta1, beta2, eps, sqrtf(bc2), gscale, ema, ema_decay);
   VBX_LAUNCH_CHECK();
   return 0;
 }
@@ -2142,8 +2206,26 @@ extern "C" int vbx_adam_step(float* p, const float* g, float* m, float* v, long 
   VBX_REQUIRE(p && g && m && v && n > 0 && step >= 1, "vbx_adam_step: bad args");
   const float bc1 = 1.0f - powf(beta1, (float)step);
   const float bc2 = 1.0f - powf(beta2, (float)step);
-  hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n, 8192)), dim3(256), 0, ST, p, g, m, v, n, lr, beta1, beta2, eps, bc1,
-                     sqrtf(bc2), gscale);
+  hipLaunchKernelGGL(adam_kernel<false>, dim3(grid_for(n, 8192)), dim3(256), 0, ST, p, g, m, v, n, lr, beta1, beta2, eps, bc1,
+                     sqrtf(bc2), gscale, (float*)nullptr, 0.0f);
+  VBX_LAUNCH_CHECK();
+  return 0;
+}
+extern "C" int vbx_adam_step_ema(float* p, const float* g, float* m, float* v, float* ema, float ema_decay, long n, float lr,
+                                 float beta1, float beta2, float eps, int step, const float* gscale, void* stream) {
+  VBX_REQUIRE(p && g && m && v && n > 0 && step >= 1, "vbx_adam_step_ema: bad args");
+  VBX_REQUIRE(ema_args_ok(p, ema, ema_decay), "vbx_adam_step_ema: ema must be a buffer aligned like p, ema_decay in [0, 1)");
+  const float bc1 = 1.0f - powf(beta1, (float)step);
+  const float bc2 = 1.0f - powf(beta2, (float)step);
+  hipLaunchKernelGGL(adam_kernel<true>, dim3(grid_for(n, 8192)), dim3(256), 0, ST, p, g, m, v, n, lr, beta1, beta2, eps, bc1,
+                     sqrtf(bc2), gscale, ema, ema_decay);
+  VBX_LAUNCH_CHECK();
+  return 0;
+}
+extern "C" int vbx_swap_f32(float* a, float* b, long n, void* stream) {
+  VBX_REQUIRE(a && b && n > 0 && (a + n <= b || b + n <= a), "vbx_swap_f32: two buffers of n > 0 floats that do not overlap");
+  const long n4 = ((((size_t)a | (size_t)b) & 15) == 0) ? n / 4 : 0;
+  hipLaunchKernelGGL(swap_f32_kernel, dim3(grid_for(n4 > 0 ? n4 : n, 8192)), dim3(256), 0, ST, a, b, n, n4);
   VBX_LAUNCH_CHECK();
   return 0;
 }
@@ -2180,23 +2262,38 @@ extern "C" int vbx_sumsq_ranges(const float* x, const long* ranges /* host [2 n]
   return 0;
 }
 // factor-form adaLN weight gradients (see adam_adaln_factor_kernel): Adam on the L weight blocks, and their sums of squares
-extern "C" int vbx_adam_adaln_factors(float* p, float* m, float* v, const long* w_off /* host [L] */, void* const* dst_f16 /* host [L] */,
-                                      const float* dada, const float* temb, int L, int B, int J4, int Th, float lr, float beta1,
-                                      float beta2, float eps, int step, const float* gscale, void* stream) {
+template <bool EMA>
+static int adam_adaln_factors_launch(const char* who, float* p, float* m, float* v, float* ema, float ema_decay, const long* w_off,
+                                     void* const* dst_f16, const float* dada, const float* temb, int L, int B, int J4, int Th, float lr,
+                                     float beta1, float beta2, float eps, int step, const float* gscale, void* stream) {
   VBX_REQUIRE(p && m && v && w_off && dada && temb && L > 0 && L <= 32 && B > 0 && J4 > 0 && Th > 0 && Th % 4 == 0 && step >= 1,
-              "vbx_adam_adaln_factors: bad args");
+              "%s: bad args", who);
+  if (EMA) VBX_REQUIRE(ema_args_ok(p, ema, ema_decay), "%s: ema must be a buffer aligned like p, ema_decay in [0, 1)", who);
   AdaFactorArgs a{};
   for (int l = 0; l < L; l++) {
-    VBX_REQUIRE(w_off[l] % 4 == 0, "vbx_adam_adaln_factors: weight offsets must be 16-byte aligned");
+    VBX_REQUIRE(w_off[l] % 4 == 0, "%s: weight offsets must be 16-byte aligned", who);
     a.w_off[l] = w_off[l];
     a.dst_f16[l] = dst_f16 ? (u16*)dst_f16[l] : nullptr;
   }
   a.dada = dada; a.temb = temb; a.L = L; a.B = B; a.J4 = J4; a.Th = Th;
   const float bc1 = 1.0f - powf(beta1, (float)step), bc2 = 1.0f - powf(beta2, (float)step);
-  hipLaunchKernelGGL(adam_adaln_factor_kernel, dim3(cdiv(Th, 1024), cdiv(J4, ADAF_ROWS), L), dim3(256), 0, ST, p, m, v, a, lr / bc1,
-                     beta1, beta2, eps, sqrtf(bc2), gscale);
+  hipLaunchKernelGGL(adam_adaln_factor_kernel<EMA>, dim3(cdiv(Th, 1024), cdiv(J4, ADAF_ROWS), L), dim3(256), 0, ST, p, m, v, a, lr / bc1,
+                     beta1, beta2, eps, sqrtf(bc2), gscale, ema, ema_decay);
   VBX_LAUNCH_CHECK();
   return 0;
+}
+extern "C" int vbx_adam_adaln_factors(float* p, float* m, float* v, const long* w_off /* host [L] */, void* const* dst_f16 /* host [L] */,
+                                      const float* dada, const float* temb, int L, int B, int J4, int Th, float lr, float beta1,
+                                      float beta2, float eps, int step, const float* gscale, void* stream) {
+  return adam_adaln_factors_launch<false>("vbx_adam_adaln_factors", p, m, v, nullptr, 0.0f, w_off, dst_f16, dada, temb, L, B, J4, Th, lr,
+                                          beta1, beta2, eps, step, gscale, stream);
+}
+extern "C" int vbx_adam_adaln_factors_ema(float* p, float* m, float* v, float* ema, float ema_decay, const long* w_off /* host [L] */,
+                                          void* const* dst_f16 /* host [L] */, const float* dada, const float* temb, int L, int B, int J4,
+                                          int Th, float lr, float beta1, float beta2, float eps, int step, const float* gscale,
+                                          void* stream) {
+  return adam_adaln_factors_launch<true>("vbx_adam_adaln_factors_ema", p, m, v, ema, ema_decay, w_off, dst_f16, dada, temb, L, B, J4, Th,
+                                         lr, beta1, beta2, eps, step, gscale, stream);
 }
 extern "C" int vbx_adaln_expand_dw(const float* temb, const float* dada, float* dw, int B, int Th, int J4, int reserved, void* stream) {
   (void)reserved;

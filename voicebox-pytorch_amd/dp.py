@@ -325,6 +325,35 @@ def filter_adam_segments(segs, frozen):
     return out, blocks
 
 
+def ema_decay_at(t, ema_decay, ema_update_after_step=0, ema_inv_gamma=1.0, ema_power=None):
+    """The decay TrainStep(ema_decay=) uses at optimizer step t (1-based: TrainStep.steps after its increment); pure host arithmetic in
+    Python floats (the C ABI receives the value converted to fp32).  t <= ema_update_after_step: 0.0 (the average is a copy of the
+    weights); otherwise, with k = t - ema_update_after_step, `ema_decay` (ema_power=None) or the warm-up
+    min(ema_decay, 1 - (1 + k / ema_inv_gamma) ** -ema_power).  The keywords follow ema-pytorch's; parity with that library is not
+    pinned by any test (it is not a dependency)."""
+    t, after = int(t), int(ema_update_after_step)
+    if t <= after:
+        return 0.0
+    if ema_power is None:
+        return float(ema_decay)
+    k = t - after
+    return min(float(ema_decay), 1.0 - (1.0 + k / float(ema_inv_gamma)) ** -float(ema_power))
+
+
+def check_ema_hyper(ema_decay, ema_update_after_step=0, ema_inv_gamma=1.0, ema_power=None):
+    """ValueError for hyper-parameters outside the contract (before anything is allocated)."""
+    if ema_decay is None:
+        return
+    if not (isinstance(ema_decay, (int, float)) and 0.0 <= float(ema_decay) < 1.0):
+        raise ValueError(f"ema_decay must be in [0, 1) (got {ema_decay!r})")
+    if ema_power is not None and not (isinstance(ema_power, (int, float)) and float(ema_power) > 0.0):
+        raise ValueError(f"ema_power must be > 0 (got {ema_power!r})")
+    if not (isinstance(ema_inv_gamma, (int, float)) and float(ema_inv_gamma) > 0.0):
+        raise ValueError(f"ema_inv_gamma must be > 0 (got {ema_inv_gamma!r})")
+    if not (isinstance(ema_update_after_step, int) and ema_update_after_step >= 0):
+        raise ValueError(f"ema_update_after_step must be an integer >= 0 (got {ema_update_after_step!r})")
+
+
 def adaln_rule(flags_by_slot, depth):
     """What a partly frozen model does with the adaLN weight gradients: "all" (every G1W / B1W / G2W / B2W trainable: the factor path
     as it is), "none" (all frozen: no factor Adam and no Gram terms; the backward may still leave the blocks unwritten) or "mixed"
@@ -338,7 +367,7 @@ def adaln_rule(flags_by_slot, depth):
 class TrainStep:
     def __init__(self, wrapper, lr=3e-4, betas=(0.9, 0.99), eps=1e-8, max_grad_norm=0.5, group=None,
                  bucket_bytes=64 << 20, broadcast_params=True, lr_schedule=None, grad_comm_dtype=None, wd=0., length_bucket=0,
-                 grad_mode="allreduce", adaln_grads="auto"):
+                 grad_mode="allreduce", adaln_grads="auto", ema_decay=None, ema_update_after_step=0, ema_inv_gamma=1.0, ema_power=None):
         """adaln_grads: what step() does with the gradient of the adaLN projection WEIGHTS (voicebox_pytorch.py:256-276; 49 % of the
         parameters at dim 512 / depth 12, each layer's block a rank-B outer product dada_l^T . temb):
           "materialize"  the backward writes it into the flat gradient buffer like every other gradient (the only form in which the
@@ -362,9 +391,29 @@ class TrainStep:
         (VoiceBox.add_lora) the step runs vbx_lora_grad after the backward, takes the norm over the trainable ranges plus the adapter
         gradients, runs Adam on the adapters with the same coefficient and re-applies them (vbx_lora_apply).  With nothing frozen
         and no adapters every launch and table is what it was.  Anything frozen or adapted together with a gradient exchange
-        (world > 1, VBX_FORCE_DIST) or grad_mode="shard" raises NotImplementedError, here or at the step that finds it."""
+        (world > 1, VBX_FORCE_DIST) or grad_mode="shard" raises NotImplementedError, here or at the step that finds it.
+
+        ema_decay (None: off -- nothing is allocated, every launch and table is what it was): an exponential moving average of the
+        weights, kept in `self.ema` (fp32, the layout of the flat parameter buffer: `fp.offsets` index it) and updated INSIDE the Adam
+        launches of every optimizer step, e' = fmaf(d, e - p', p') with d = ema_decay_at(self.steps) (include/vbx.h "EMA"): the fused
+        pass, its filtered table, the factor-form launch, the plain launch of VBX_FUSED_ADAM=0 and the adapter Adam (on a second small
+        buffer beside the adapters) all take their _ema entry point.  ema_update_after_step / ema_inv_gamma / ema_power: the decay
+        schedule (dp.ema_decay_at; ema-pytorch's keywords, parity with that library unpinned).  The average starts as a copy of the
+        weights (after the DP broadcast); ema_reset() copies them again.  A frozen tensor's average is not touched; with adapters the
+        adapted matrices' slots of `self.ema` are frozen by construction and never read (the averaged W_eff is W0 + s . B_ema . A_ema).
+        ema_state_dict() / load_ema_state_dict() / `with step.ema_weights():` see there.  grad_mode="shard" with ema_decay raises
+        NotImplementedError: the owned chunks would need a gather before every use."""
         assert grad_mode in ("allreduce", "shard"), grad_mode
         assert adaln_grads in ("auto", "factors", "materialize"), adaln_grads
+        check_ema_hyper(ema_decay, ema_update_after_step, ema_inv_gamma, ema_power)
+        if ema_decay is not None and grad_mode == "shard":
+            raise NotImplementedError("TrainStep: ema_decay is not served by grad_mode='shard' (each rank updates only the chunks it owns: the "
+                                      "average would need an all-gather before every use) -- use grad_mode='allreduce'")
+        self.ema_hyper = None if ema_decay is None else dict(ema_decay=float(ema_decay), ema_update_after_step=int(ema_update_after_step),
+                                                             ema_inv_gamma=float(ema_inv_gamma),
+                                                             ema_power=None if ema_power is None else float(ema_power))
+        self.ema = None
+        self._ema_swapped = False  # inside `with ema_weights():`
         self.grad_mode = grad_mode
         self.adaln_grads = adaln_grads
         self.wrapper, self.vb = wrapper, wrapper.voicebox
@@ -387,6 +436,9 @@ class TrainStep:
         self.gflat = torch.zeros_like(flat)
         self.m = torch.zeros_like(flat)
         self.v = torch.zeros_like(flat)
+        if self.ema_hyper is not None:
+            self.ema = torch.zeros_like(flat)
+            self.ema.copy_(flat)
         self.sumsq = torch.zeros(1, device=dev)
         self.coef = torch.zeros(2, device=dev)
         self.scratch = torch.zeros(1024 + 32 * 64 * 64, device=dev)  # 1024 block partials + the L * B * B factor terms of the gradient norm
@@ -445,6 +497,8 @@ class TrainStep:
             else:
                 self._lora_rt = dict(state=st, g=torch.zeros_like(lflat), m=torch.zeros_like(lflat), v=torch.zeros_like(lflat),
                                      scratch=torch.zeros(max(1, tab.scratch_floats), device=dev))
+                if self.ema is not None:  # the adapters' average: lflat's layout, starts as a copy, kept like m / v
+                    self._lora_rt["ema"] = lflat.detach().clone()
             self._lora_keep = self._lora_rt
         self._flags = flags
 
@@ -456,11 +510,146 @@ class TrainStep:
         if keep is not None:
             keep.packed_version = self.fp.weights_key()
 
+    # -- EMA of the weights (ema_decay=): kept by the Adam launches themselves, see __init__
+    def ema_decay_at(self, t):
+        """The decay of optimizer step t (1-based) under this step's schedule: dp.ema_decay_at with the constructor's keywords."""
+        self._require_ema("ema_decay_at")
+        return ema_decay_at(t, **self.ema_hyper)
+
+    def _require_ema(self, what):
+        if self.ema is None:
+            raise RuntimeError(f"TrainStep.{what}: this step keeps no average (build it with ema_decay=)")
+
+    def _refuse_inside_ema_weights(self, what):
+        if self._ema_swapped:
+            raise RuntimeError(f"TrainStep.{what} inside `with ema_weights():` -- the flat buffer holds the average there, not the "
+                               "optimizer's iterate; leave the context first")
+
+    def _ema_launch_args(self):
+        """What engine.adam_step_packed takes beside its arguments when the average is on (nothing otherwise)."""
+        if self.ema is None:
+            return {}
+        return dict(ema=self.ema, ema_decay=self.ema_decay_at(self.steps))
+
+    def _lora_ema(self):
+        """(lflat, its average) with adapters attached, else None."""
+        self._refresh_trainable()
+        lo = self._lora_rt
+        if lo is None or self.ema is None:
+            return None
+        return lo["state"].ensure(self.fp.flat.device), lo["ema"]
+
+    def ema_reset(self):
+        """The average becomes a copy of the weights again: after weights were written behind the step (load_state_dict, a
+        broadcast), which the average cannot know about."""
+        self._require_ema("ema_reset")
+        self._refuse_inside_ema_weights("ema_reset")
+        self.ema.copy_(self.fp.flat)
+        la = self._lora_ema()
+        if la is not None:
+            la[1].copy_(la[0])
+
+    def _ema_views(self):
+        """{state-dict key: view of the average with the parameter's shape} for every flat-backed parameter and every adapter."""
+        fp = self.fp
+        by_id = {id(fp.slots[s]): s for s in fp.order}
+        la = self._lora_ema()
+        adapters = {}
+        if la is not None:
+            for e in self._lora_rt["state"].entries:
+                adapters[id(e["module"].lora_A)], adapters[id(e["module"].lora_B)] = e["a_off"], e["b_off"]
+        out = {}
+        for k, p in self.vb.named_parameters(remove_duplicate=False):
+            if id(p) in by_id:
+                o = fp.offsets[by_id[id(p)]]
+                out[k] = self.ema[o:o + p.numel()].view(p.shape)
+            elif id(p) in adapters:
+                o = adapters[id(p)]
+                out[k] = la[1][o:o + p.numel()].view(p.shape)
+        return out
+
+    def ema_state_dict(self):
+        """The averaged model, keyed like vb.state_dict(): clones out of the average for every flat-backed parameter, the live tensors
+        for everything else (null_cond, buffers).  With adapters attached W0 sits under the reference's keys and the averaged
+        lora_A / lora_B are included, exactly as state_dict() does for the live ones.  (Inside `with ema_weights():` the model's own
+        state dict is that already: clones of it.)"""
+        self._require_ema("ema_state_dict")
+        sd = self.vb.state_dict()
+        if self._ema_swapped:
+            return type(sd)((k, v.detach().clone()) for k, v in sd.items())
+        adapted = set()
+        st = getattr(self.vb, "_lora", None)
+        if st is not None:
+            adapted = {e["key"] for e in st.entries}  # W0 stands there (the state-dict hook): not the slot of the average
+        for k, view in self._ema_views().items():
+            if k in sd and k not in adapted:
+                sd[k] = view.detach().clone()
+        return sd
+
+    def load_ema_state_dict(self, sd):
+        """The inverse of ema_state_dict(): every flat-backed parameter's (and adapter's) entry is copied into the average; the other
+        keys are not the average's business.  A missing key or a shape mismatch raises ValueError before anything is copied."""
+        self._require_ema("load_ema_state_dict")
+        self._refuse_inside_ema_weights("load_ema_state_dict")
+        st = getattr(self.vb, "_lora", None)
+        adapted = {e["key"] for e in st.entries} if st is not None else set()
+        views = {k: v for k, v in self._ema_views().items() if k not in adapted}
+        missing = sorted(k for k in views if k not in sd)
+        if missing:
+            raise ValueError(f"load_ema_state_dict: missing keys {missing}")
+        for k, view in views.items():
+            if tuple(sd[k].shape) != tuple(view.shape):
+                raise ValueError(f"load_ema_state_dict: {k} has shape {tuple(sd[k].shape)}, the parameter has {tuple(view.shape)}")
+        with torch.no_grad():
+            for k, view in views.items():
+                view.copy_(sd[k])
+
+    def _ema_swap(self, entering):
+        """flat <-> ema (and the adapters <-> their average) in place, vbx_swap_f32: the addresses stay, so engines and captured graphs
+        stay valid and only repack (fp.bump)."""
+        st = _lib.current_stream()
+        flat = self.fp.flat
+        la = self._lora_ema()
+        _lib.call("vbx_swap_f32", flat, self.ema, flat.numel(), st)
+        if la is not None:
+            _lib.call("vbx_swap_f32", la[0], la[1], la[0].numel(), st)
+            if entering:
+                # the adapted slots hold what the average's (never updated) slots held: W_eff = W0 + s . B_ema . A_ema into them.
+                # On the way out the swap itself brings the live W_eff back bit for bit.
+                state = self._lora_rt["state"]
+                state.needs_apply = True
+                state.apply()
+        self.fp.bump()
+
+    def ema_weights(self):
+        """`with step.ema_weights():` -- the averaged model is served by every path that reads the weights (wrapper(...) in eval,
+        wrapper.sample(...), cached and captured samplers, state_dict()): the flat buffer and the average change places in place.  On
+        exit (also after an exception) they change back: the weights are bit-equal to before.  Nesting, and step() / accumulate*()
+        inside, raise RuntimeError."""
+        import contextlib
+
+        self._require_ema("ema_weights")
+
+        @contextlib.contextmanager
+        def ctx():
+            if self._ema_swapped:
+                raise RuntimeError("TrainStep.ema_weights: already inside `with ema_weights():` (the context does not nest)")
+            self._ema_swap(True)
+            self._ema_swapped = True
+            try:
+                yield self
+            finally:
+                self._ema_swapped = False
+                self._ema_swap(False)
+
+        return ctx()
+
     # -- gradient accumulation with a deferred exchange (VoiceBoxTrainer.train_step, trainer.py:258-272: every micro-batch but
     #    the last runs under accelerator.no_sync, the loss is divided by grad_accum_every)
     def accumulate(self, x1, weight, mask=None, cond_token_ids=None, input_sampling_rate=None, lens=None):
         """forward + backward of one micro-batch; gradients * weight are added to the accumulation buffer (no exchange).
         lens: see step."""
+        self._refuse_inside_ema_weights("accumulate")
         self._refresh_trainable()
         if getattr(self, "gacc", None) is None:
             self.gacc = torch.zeros_like(self.gflat)
@@ -530,6 +719,7 @@ class TrainStep:
         for exactly this micro-batch, trainer.py:258-272): as each backward stage completes, its slice of the accumulator is
         folded in (g = acc + weight * g) and the bucketed all-reduce of that slice starts while earlier layers are still running --
         instead of exchanging all 410 MB after the backward with nothing to overlap (apply_accumulated).  Then clip + Adam."""
+        self._refuse_inside_ema_weights("accumulate_last_and_apply")
         self._refresh_trainable()
         if getattr(self, "gacc", None) is None or not getattr(self, "acc_pending", False):
             self.gacc = torch.zeros_like(self.gflat) if getattr(self, "gacc", None) is None else self.gacc
@@ -553,6 +743,7 @@ class TrainStep:
     def apply_accumulated(self, lr=None):
         """all-reduce (sum) of the accumulated gradients, clip, Adam; clears the accumulator.  (No backward is left to overlap the
         exchange with: prefer accumulate_last_and_apply for the window's last micro-batch.)"""
+        self._refuse_inside_ema_weights("apply_accumulated")
         assert getattr(self, "acc_pending", False), "nothing accumulated"
         self._refresh_trainable()
         self.gflat.copy_(self.gacc)
@@ -701,12 +892,17 @@ class TrainStep:
         # Adam + refresh of the training engine's fp16/bf16 operand copies in one pass (other engines repack lazily)
         if os.environ.get("VBX_FUSED_ADAM", "1") != "0":
             eng.adam_step_packed(self.gflat, self.m, self.v, float(lr if lr is not None else self.lr), self.betas[0], self.betas[1],
-                                 self.eps, self.steps, self.coef, adaln_factors=adaln_factors)  # bumps the weights epoch; `eng` stays current
+                                 self.eps, self.steps, self.coef, adaln_factors=adaln_factors,
+                                 **self._ema_launch_args())  # bumps the weights epoch; `eng` stays current
         else:  # A/B: plain Adam, the next forward repacks every weight
             assert not adaln_factors, "VBX_FUSED_ADAM=0 needs the materialised gradient: set VBX_ADALN_FACTORS=0 too"
             self._dirty()
-            _lib.call("vbx_adam_step", self.fp.flat, self.gflat, self.m, self.v, n, float(lr if lr is not None else self.lr),
-                      float(self.betas[0]), float(self.betas[1]), float(self.eps), self.steps, self.coef, st())
+            hyper = (n, float(lr if lr is not None else self.lr), float(self.betas[0]), float(self.betas[1]), float(self.eps), self.steps,
+                     self.coef, st())
+            if self.ema is None:
+                _lib.call("vbx_adam_step", self.fp.flat, self.gflat, self.m, self.v, *hyper)
+            else:
+                _lib.call("vbx_adam_step_ema", self.fp.flat, self.gflat, self.m, self.v, self.ema, self.ema_decay_at(self.steps), *hyper)
 
     def _sumsq_filtered(self, eng, factor_terms):
         """self.sumsq[0] = sum of squares over the trainable ranges of gflat (+ the adaLN Gram terms when those blocks are trainable and
@@ -754,10 +950,13 @@ class TrainStep:
             eng.packed_version = self.fp.weights_key()  # (as in _clip_adam; with adapters the apply below makes every engine repack)
         if f["any_base"]:
             eng.adam_step_packed(self.gflat, self.m, self.v, rate, self.betas[0], self.betas[1], self.eps, self.steps, self.coef,
-                                 adaln_factors=adaln_factors, trainable=f, factor_adam=factor_terms)
+                                 adaln_factors=adaln_factors, trainable=f, factor_adam=factor_terms, **self._ema_launch_args())
         if lo is not None:
-            _lib.call("vbx_adam_step", lflat, lo["g"], lo["m"], lo["v"], lflat.numel(), rate, float(self.betas[0]), float(self.betas[1]),
-                      float(self.eps), self.steps, self.coef, st())
+            hyper = (lflat.numel(), rate, float(self.betas[0]), float(self.betas[1]), float(self.eps), self.steps, self.coef, st())
+            if self.ema is None:
+                _lib.call("vbx_adam_step", lflat, lo["g"], lo["m"], lo["v"], *hyper)
+            else:
+                _lib.call("vbx_adam_step_ema", lflat, lo["g"], lo["m"], lo["v"], lo["ema"], self.ema_decay_at(self.steps), *hyper)
             state.needs_apply = True
             state.apply()  # W_eff = W0 + s . B . A into the master slots; bumps the weights epoch: every engine and sampler repacks
 
@@ -770,6 +969,7 @@ class TrainStep:
         (ConditionalFlowMatcherWrapper.forward).  With text conditioning it counts frames, not tokens.
         Returns the (un-synchronised) local loss tensor."""
         # --- backward with overlapped gradient exchange
+        self._refuse_inside_ema_weights("step")
         self._refresh_trainable()
         factors = self.adaln_factors_apply(batch=int(x1.shape[0])) and os.environ.get("VBX_FUSED_ADAM", "1") != "0"
         red = self._reducer(self.grad_comm_dtype, skip_adaln=factors and self.exchange)

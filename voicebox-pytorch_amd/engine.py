@@ -100,6 +100,10 @@ def _rt():
         l.vbx_sumsq_ranges.restype = I
         l.vbx_adam_adaln_factors.argtypes = [P, P, P, C.POINTER(C.c_long), C.POINTER(P), P, P, I, I, I, I, F, F, F, F, I, P, P]
         l.vbx_adam_adaln_factors.restype = I
+        l.vbx_adam_step_packed_ema.argtypes = [P, P, P, P, P, F, P, I, C.c_long, F, F, F, F, I, P, P]
+        l.vbx_adam_step_packed_ema.restype = I
+        l.vbx_adam_adaln_factors_ema.argtypes = [P, P, P, P, F, C.POINTER(C.c_long), C.POINTER(P), P, P, I, I, I, I, F, F, F, F, I, P, P]
+        l.vbx_adam_adaln_factors_ema.restype = I
         l.vbx_adaln_expand_dw.argtypes = [P, P, P, I, I, I, I, P]
         l.vbx_adaln_expand_dw.restype = I
         for name, at in (("vbx_model_pack_weights", [MP, P]), ("vbx_model_pack_weights_precise", [MP, P]), ("vbx_model_forward", [MP, IP, P]),
@@ -203,7 +207,8 @@ class FlatParams:
         """Call after writing parameter values behind PyTorch's back (raw-pointer kernels, collectives into `flat`) -- and after
         writes through `p.data` (p.data.copy_(), p.data.mul_(), EMA weight swaps): `.data` has its own version counter, so such a
         write changes neither p._version nor flat._version and the engines (and the hipGraph samplers that hold them) would keep
-        serving the previous fp16 / bf16 packed copies.  Public spelling: VoiceBox.mark_weights_dirty()."""
+        serving the previous fp16 / bf16 packed copies.  Public spelling: VoiceBox.mark_weights_dirty().  (dp.TrainStep(ema_decay=)
+        keeps its own average and bumps by itself when `with step.ema_weights():` swaps it in and out.)"""
         self.epoch += 1
 
     def weights_key(self):
@@ -424,9 +429,12 @@ class Engine:
         return tab, nblocks.value
 
     # -- optimizer: Adam over the flat buffers that also refreshes this engine's packed operand copies
-    def adam_step_packed(self, gflat, m, v, lr, beta1, beta2, eps, step, gscale, adaln_factors=False, trainable=None, factor_adam=None):
+    def adam_step_packed(self, gflat, m, v, lr, beta1, beta2, eps, step, gscale, adaln_factors=False, trainable=None, factor_adam=None,
+                         ema=None, ema_decay=0.0):
         """adaln_factors=True: the adaLN weight blocks are updated from their factor-form gradients (the last backward ran with
         adaln_factors) by a second launch; the fused launch leaves them out.
+        ema (dp.TrainStep(ema_decay=)): an fp32 buffer with the flat buffer's layout; both launches then go through the _ema entry
+        points and update it with the decay `ema_decay` (include/vbx.h "EMA").  None: the launches as they always were.
         trainable (dp.TrainStep of a partly frozen model): dict with `key` (hashable) and `frozen` ([lo, hi) slot ranges) -- the
         segment table is filtered (dp.filter_adam_segments) so that the launch never touches a frozen range; factor_adam=False
         then also skips the factor-form launch (all adaLN weights frozen)."""
@@ -455,15 +463,25 @@ class Engine:
             cache[ckey] = (torch.frombuffer(bytearray(bytes(tab)), dtype=torch.uint8).to(self.device), n, nblocks)
         raw, n, nblocks = cache[ckey]
         gs = gscale.data_ptr() if gscale is not None else None
+        hyper = (float(lr), float(beta1), float(beta2), float(eps), int(step), gs, _lib.current_stream())
+        if ema is not None:  # the same launches through the _ema entry points: the average is updated where p' is stored
+            assert ema.numel() == flat.numel() and ema.dtype == torch.float32 and ema.device == flat.device
+            avg = (ema.data_ptr(), float(ema_decay))
         if n > 0 and nblocks > 0:  # (a filtered table may be empty: nothing but adaLN weights in factor form is trainable)
-            _check(l.vbx_adam_step_packed(flat.data_ptr(), gflat.data_ptr(), m.data_ptr(), v.data_ptr(), raw.data_ptr(), n, nblocks,
-                                          float(lr), float(beta1), float(beta2), float(eps), int(step), gs, _lib.current_stream()),
-                   "vbx_adam_step_packed")
+            if ema is None:
+                _check(l.vbx_adam_step_packed(flat.data_ptr(), gflat.data_ptr(), m.data_ptr(), v.data_ptr(), raw.data_ptr(), n, nblocks,
+                                              *hyper), "vbx_adam_step_packed")
+            else:
+                _check(l.vbx_adam_step_packed_ema(flat.data_ptr(), gflat.data_ptr(), m.data_ptr(), v.data_ptr(), *avg, raw.data_ptr(), n,
+                                                  nblocks, *hyper), "vbx_adam_step_packed_ema")
         if adaln_factors and factor_adam:
             dada, temb, woff, dst, J4, Th = self.adaln_factor_info()
-            _check(l.vbx_adam_adaln_factors(flat.data_ptr(), m.data_ptr(), v.data_ptr(), woff, dst, dada, temb, self.cfg["L"], self.B, J4,
-                                            Th, float(lr), float(beta1), float(beta2), float(eps), int(step), gs, _lib.current_stream()),
-                   "vbx_adam_adaln_factors")
+            shape = (woff, dst, dada, temb, self.cfg["L"], self.B, J4, Th)
+            if ema is None:
+                _check(l.vbx_adam_adaln_factors(flat.data_ptr(), m.data_ptr(), v.data_ptr(), *shape, *hyper), "vbx_adam_adaln_factors")
+            else:
+                _check(l.vbx_adam_adaln_factors_ema(flat.data_ptr(), m.data_ptr(), v.data_ptr(), *avg, *shape, *hyper),
+                       "vbx_adam_adaln_factors_ema")
         self.fp.bump()  # the flat buffer was written through a raw pointer: every other engine must repack
         self.packed_version = self.fp.weights_key()  # this engine's operand copies were refreshed in the same pass
 

@@ -87,7 +87,8 @@ class VoiceBoxTrainer(nn.Module):
                  num_warmup_steps=None, num_epochs=None, lr=3e-4, initial_lr=1e-5, grad_accum_every=1, wd=0., max_grad_norm=0.5,
                  valid_frac=0.05, random_split_seed=42, log_every=10, save_results_every=100, save_model_every=1000,
                  results_folder='./results', force_clear_prev_results=None, split_batches=False, drop_last=False,
-                 accelerate_kwargs: dict = dict(), length_bucket=64, input_sampling_rate=None, mask_padding=False):
+                 accelerate_kwargs: dict = dict(), length_bucket=64, input_sampling_rate=None, mask_padding=False,
+                 ema_decay=None, ema_update_after_step=0, ema_inv_gamma=1.0, ema_power=None):
         # length_bucket (not a reference keyword): batches of a varying-length dataset are padded with masked frames to the next
         # multiple of it, so that training runs on a handful of activation arenas (dp.TrainStep); 0 = exact lengths
         # input_sampling_rate (not a reference keyword: its trainer never passes one): the rate of a dataset of waves, handed to
@@ -96,6 +97,10 @@ class VoiceBoxTrainer(nn.Module):
         # function also returns each item's length, and every train and validation step passes lens= -- padding frames are masked in the
         # convolution, the attention and the loss, and the attention kernels stop at each row's length.  Latent datasets only: with a
         # dataset of waves the first batch raises ValueError (the frame count is the codec's business).
+        # ema_decay / ema_update_after_step / ema_inv_gamma / ema_power (not reference keywords): handed to dp.TrainStep, which keeps an
+        # exponential moving average of the weights inside its Adam launches.  save() then adds 'ema_model' (TrainStep.ema_state_dict())
+        # and 'ema' (the four hyper-parameters) beside the reference's three keys, load() restores the average from them (or resets it
+        # to the loaded weights when the file has none), and the rank-0 validation also logs the loss of the averaged model.
         super().__init__()
         self.mask_padding = bool(mask_padding)
         self.input_sampling_rate = input_sampling_rate
@@ -131,7 +136,8 @@ class VoiceBoxTrainer(nn.Module):
         self.num_warmup_steps = num_warmup_steps if exists(num_warmup_steps) else 0
         self.schedule = WarmupCosineLR(lr, self.num_train_steps, self.num_warmup_steps, initial_lr)
         self.train_step_fn = TrainStep(cfm_wrapper, lr=lr, betas=(0.9, 0.99), eps=1e-8, max_grad_norm=max_grad_norm, wd=self.wd,
-                                       lr_schedule=None, length_bucket=length_bucket)
+                                       lr_schedule=None, length_bucket=length_bucket, ema_decay=ema_decay,
+                                       ema_update_after_step=ema_update_after_step, ema_inv_gamma=ema_inv_gamma, ema_power=ema_power)
 
         sampler = None
         if self.world > 1:  # what accelerator.prepare(dl) does: each rank sees its own shard
@@ -240,6 +246,10 @@ class VoiceBoxTrainer(nn.Module):
         """Reference checkpoint format.  With TrainStep(grad_mode="shard") and world size > 1 call it on EVERY rank (only rank 0 needs
         to pass a real path to keep) unless the optimizer state was gathered collectively beforehand (gathered=True)."""
         pkg = dict(model=self.cfm_wrapper.state_dict(), optim=self._optim_state_dict(gathered), scheduler=self._scheduler_state_dict())
+        ts = self.train_step_fn
+        if ts.ema is not None:  # two more keys; the reference's loader reads 'model' only, so the file still loads there
+            pkg['ema_model'] = ts.ema_state_dict()
+            pkg['ema'] = dict(ts.ema_hyper)
         torch.save(pkg, path)
 
     def load(self, path):
@@ -247,6 +257,11 @@ class VoiceBoxTrainer(nn.Module):
         self.train_step_fn.fp = self.cfm_wrapper.voicebox.flat_params()  # load_state_dict copied into the flat views
         self.train_step_fn._dirty()
         self._load_optim_state_dict(pkg['optim'])
+        ts = self.train_step_fn
+        if ts.ema is not None:  # (a file written with EMA loads into a trainer without it: the extra keys are ignored)
+            ts.ema_reset()  # the loaded weights; then the file's average over it, when it has one
+            if 'ema_model' in pkg:
+                ts.load_ema_state_dict(pkg['ema_model'])
         sc = pkg['scheduler']
         self.schedule.sched_epoch, self.schedule.cur = int(sc['last_epoch']), float(sc['_last_lr'][0])
         # + 1 to start from the next step and avoid overwriting the last checkpoint (trainer.py:206-207)
@@ -313,6 +328,9 @@ class VoiceBoxTrainer(nn.Module):
             dist.barrier()
         if self.is_main and not (steps % self.save_results_every):  # rank-0 validation (:289-301)
             x, kw = self._model_kwargs(next(self.valid_dl_iter))
+            dev = torch.device(self.device)
+            if ts.ema is not None:  # the generator states the validation starts from: the averaged model gets the same draws below
+                rng = (torch.get_rng_state(), torch.cuda.get_rng_state(dev) if dev.type == 'cuda' else None)
             with torch.inference_mode():
                 self.cfm_wrapper.eval()
                 ids = kw.get('cond_token_ids')
@@ -321,6 +339,18 @@ class VoiceBoxTrainer(nn.Module):
                                               **({'semantic_token_ids': ids.to(self.device)} if ids is not None else {}))
             self.print(f'{steps}: valid loss {float(valid_loss):0.3f}')
             logs['valid_loss'] = float(valid_loss)
+            if ts.ema is not None:
+                # the same batch and the same random draws through the averaged weights, inside a forked generator state: the
+                # training that follows draws what a trainer without EMA draws
+                with torch.random.fork_rng(devices=[dev] if dev.type == 'cuda' else []), ts.ema_weights(), torch.inference_mode():
+                    torch.set_rng_state(rng[0])
+                    if rng[1] is not None:
+                        torch.cuda.set_rng_state(rng[1], dev)
+                    valid_loss_ema = self.cfm_wrapper(x.to(self.device), input_sampling_rate=self.input_sampling_rate,
+                                                      **({'lens': kw['lens']} if 'lens' in kw else {}),
+                                                      **({'semantic_token_ids': ids.to(self.device)} if ids is not None else {}))
+                self.print(f'{steps}: valid loss (ema) {float(valid_loss_ema):0.3f}')
+                logs['valid_loss_ema'] = float(valid_loss_ema)
         if not (steps % self.save_model_every):
             # grad_mode="shard": the Adam moments of a chunk live on its owner -- collecting them is a COLLECTIVE, so every rank takes
             # part here, before rank 0 alone writes the file (a rank-0-only gather would hang or pair with the other ranks'
