@@ -507,6 +507,52 @@ int vbx_seanet_convtr_t(const void* x_f16, const void* w_f16, const float* bias,
                         void* stream);
 int vbx_seanet_conv_out_c(const void* x_f16, const float* w, const float* bias, float* y, int B, int T, int nf, int k, int causal,
                           void* stream);
+/* HiFi-GAN generator (voicebox_pytorch_amd.HiFiGANGenerator; csrc/hifigan.hip): conv_pre, per stage (leaky ReLU, transposed
+ * convolution, the mean of up to three residual blocks), leaky ReLU, conv_post, tanh -- inference only, on SEANet's tile core
+ * (csrc/seanet_tile.hpp) and under SEANet's PRECISION CONTRACT: activations fp16 channel-last [B, L, C], rounded ONCE and stored
+ * BEFORE the activation (the residual reads them un-activated); leaky ReLU is x > 0 ? x : x * slope in fp32, applied when an operand
+ * is staged and rounded to fp16 there; weights fp16 (weight norm folded in fp32 first); every sum fp32 on v_mfma_f32_16x16x32_f16 in
+ * ascending column order; all paddings are ZEROS; no atomics, reruns bit-identical, a batch row independent of its neighbours.
+ * Error bounds against fp64 on the same fp16 operands (tests/test_hifigan_gpu.py): a sum of n fp32 terms in any order is within
+ * (n - 1) 2^-24 (1 + o(1)) of sum |terms|, so
+ *   vbx_hifigan_conv    |err| <= (k C + 3) 2^-24 (sum |w a| + |b| + |res|) + 2^-11 |y| + 2^-25: k C products, the bias and the residual
+ *                       are k C + 2 terms, one more for slack; then the fp16 store (half an ulp, 2^-25 below the normal range)
+ *   vbx_hifigan_convtr  |err| <= (2 C + 2) 2^-24 (sum |w a| + |b|) + 2^-11 |y| + 2^-25
+ *   vbx_hifigan_post    |err| <= (k C + 2) 2^-24 (sum |w a| + |b|) + 2^-22: the fp32 fmaf chain (tanh is 1-Lipschitz, so the error of its
+ *                       argument passes at most unchanged), then tanhf within 4 fp32 ulps of |y| <= 1; no fp16 store
+ * The leaky ReLU and the n = 2, 3 mean are single correctly rounded fp32 operations (a product, a sum, a division), so the staged
+ * operand is reproduced exactly on the host and the bounds carry no term for it.
+ * vbx_hifigan_pack: mel fp32 [B, M, T] channel-first -> y fp16 [B, T, Mp], Mp = M rounded up to a multiple of 8, columns M .. Mp - 1
+ *   zero; log != 0: logf(fmaxf(mel, 1e-5f)) first.  M in 1 .. 512.
+ * vbx_hifigan_conv: y fp16 [B, L, Co] = conv(act ? lrelu(x) : x) + bias (+ res), x fp16 [B, L, C], w fp16 [Co, k C], column tap * C + c,
+ *   k odd and at most 11, dilation 1 .. 12, zero padding (k - 1) dilation / 2 on both sides; res fp16 [B, L, Co] or NULL is added in
+ *   fp32 as (sum + bias) + res before the one rounding.  C a multiple of 8 up to 1024.  A workgroup owns up to
+ *   vbx_hifigan_conv_tile(C, k, dilation) positions of one row: the largest of 128 .. 32 whose span of tile + (k - 1) dilation positions
+ *   fits 80 KiB of LDS, else 16 within 160 KiB (negative: not even that fits); fewer on a row shorter than the tile.
+ * vbx_hifigan_respair: y = x + c2(lrelu(c1(lrelu(x)))), c1 with the given dilation, c2 with dilation 1, both k taps and C -> C, in ONE
+ *   launch: the intermediate lives in the LDS, rounded to fp16 exactly where vbx_hifigan_conv would have stored it, and is ZERO at
+ *   positions outside [0, L) (c2's padding).  BIT-EQUAL to vbx_hifigan_conv(x, w1, b1, NULL, h, act = 1) followed by
+ *   vbx_hifigan_conv(h, w2, b2, res = x, y, act = 1).  C a multiple of 8 up to vbx_hifigan_respair_max_channels() = 64.
+ * vbx_hifigan_convtr: ConvTranspose1d(C, C / 2, 2 stride, stride, padding stride / 2) in vbx_seanet_convtr_t's one-product form at
+ *   trim_left = stride / 2: w fp16 [stride Co, 2C], row p Co + o = [W[:, o, p] | W[:, o, p + stride]].  The operand is
+ *   lrelu(mean of `inputs` tensors x0 .. x2 fp16 [B, L, C]): ((x0 + x1) + x2) / inputs in fp32, rounded to fp16 once.  y fp16
+ *   [B, L stride, C / 2].  C a multiple of 16 up to 1024, stride even in 2 .. 8.
+ * vbx_hifigan_post: y fp32 [B, T] = tanhf(bias[0] + sum_tap sum_c w[tap, c] lrelu(mean of the inputs)[t + tap - k / 2, c]), zero
+ *   padded, w fp32 [k, C]; the operand stays fp32 (not rounded again); one fmaf chain on the bias: per chunk of 32 channels tap-major,
+ *   then channel (C <= 32: tap-major, then channel).  C a multiple of 8 up to 512, k odd and at most 11.
+ * vbx_hifigan_conv and vbx_hifigan_convtr halve their tile, down to 16, while a launch has fewer than 256 workgroups (one per CU of an
+ *   MI355X); an element's sum does not depend on the tile, so the bits do not either. */
+int vbx_hifigan_pack(const float* mel, void* y_f16, int B, int M, int T, int log, void* stream);
+int vbx_hifigan_conv_tile(int C, int k, int dilation);
+int vbx_hifigan_conv(const void* x_f16, const void* w_f16, const float* bias, const void* res_f16, void* y_f16, int B, int L, int C, int Co,
+                     int k, int dilation, int act, float slope, void* stream);
+int vbx_hifigan_respair_max_channels(void);
+int vbx_hifigan_respair(const void* x_f16, const void* w1_f16, const float* bias1, const void* w2_f16, const float* bias2, void* y_f16, int B,
+                        int L, int C, int k, int dilation, float slope, void* stream);
+int vbx_hifigan_convtr(const void* x0_f16, const void* x1_f16, const void* x2_f16, int inputs, const void* w_f16, const float* bias,
+                       void* y_f16, int B, int L, int C, int stride, float slope, void* stream);
+int vbx_hifigan_post(const void* x0_f16, const void* x1_f16, const void* x2_f16, int inputs, const float* w, const float* bias, float* y,
+                     int B, int T, int C, int k, float slope, void* stream);
 /* Aligner primitives (voicebox_pytorch_amd.maximum_path / forward_sum_loss; csrc/align.hip): monotonic alignment search and the
  * forward-sum (CTC) loss over an attention map fp32 [B, T, K], T query frames by K keys.  K in 1 .. 1024, any T >= 1, B * T < 2^31;
  * everything else returns VBX_EINVAL.  query_lens / key_lens: int32 [B] on the device, NULL = T / K; a length is clamped into

@@ -98,6 +98,13 @@ _PROTOS = {
     "vbx_seanet_conv0_c": [P, P, P, P, I, I, I, I, I, P],
     "vbx_seanet_convtr_t": [P, P, P, P, I, I, I, I, I, P],
     "vbx_seanet_conv_out_c": [P, P, P, P, I, I, I, I, I, P],
+    "vbx_hifigan_pack": [P, P, I, I, I, I, P],
+    "vbx_hifigan_conv_tile": [I, I, I],
+    "vbx_hifigan_conv": [P, P, P, P, P, I, I, I, I, I, I, I, F, P],
+    "vbx_hifigan_respair_max_channels": [],
+    "vbx_hifigan_respair": [P, P, P, P, P, P, I, I, I, I, I, F, P],
+    "vbx_hifigan_convtr": [P, P, P, I, P, P, P, I, I, I, I, F, P],
+    "vbx_hifigan_post": [P, P, P, I, P, P, P, I, I, I, I, F, P],
     "vbx_maximum_path": [P, P, P, P, P, P, I, I, I, P],
     "vbx_forward_sum_fwd": [P, P, P, F, P, P, P, P, I, I, I, P],
     "vbx_forward_sum_bwd": [P, P, P, F, P, P, P, P, P, I, I, I, P],
