@@ -553,6 +553,55 @@ int vbx_hifigan_convtr(const void* x0_f16, const void* x1_f16, const void* x2_f1
                        void* y_f16, int B, int L, int C, int stride, float slope, void* stream);
 int vbx_hifigan_post(const void* x0_f16, const void* x1_f16, const void* x2_f16, int inputs, const float* w, const float* bias, float* y,
                      int B, int T, int C, int k, float slope, void* stream);
+/* BigVGAN generator (voicebox_pytorch_amd.BigVGANGenerator; csrc/bigvgan.hip on csrc/hifigan_tile.hpp): HiFi-GAN's generator with
+ * every leaky ReLU replaced by Activation1d A (2x up-sampling with a 12-tap filter f_u, the snake function per channel, 12-tap
+ * low-pass f_d and 2x down-sampling) and no activation in front of the transposed convolutions.  The PRECISION CONTRACT is
+ * HiFi-GAN's above: fp16 channel-last activations rounded once where stored, fp32 sums, no atomics, reruns bit-identical, a batch
+ * row independent of its neighbours.  Per channel, x the fp32 mean ((x0 + x1) + x2) / n of the fp16 inputs at one position:
+ *   u[m] = 2 sum_i f_u[m + 5 - 2 i] x[clamp(i, 0, L - 1)]   over the six i with 0 <= m + 5 - 2 i <= 11, m in [0, 2 L)
+ *   s[m] = u[m] + inv_beta sin^2(alpha u[m])
+ *   A(x)[t] = sum_{tau = 0 .. 11} f_d[tau] s[clamp(2 t + tau - 5, 0, 2 L - 1)]
+ * (the replicate paddings of the published modules as clamps: x is clamped to [0, L), s to [0, 2 L)).  ORDER OF OPERATIONS, all
+ * fp32: acc = 0; acc = fmaf(f_u[m + 5 - 2 i], x[clamp(i)], acc) for the six i ASCENDING; u = 2 acc; a = alpha * u (one rounded
+ * product); sn = sinf(a), the accurate library sine, never the fast intrinsic; s = fmaf(inv_beta, sn * sn, u) with sn * sn rounded;
+ * acc = 0; acc = fmaf(f_d[tau], s[clamp(2 t + tau - 5)], acc) for tau = 0 .. 11 ASCENDING; the result is rounded to fp16 once.  Every
+ * kernel below evaluates A by this one sequence, whatever its tiling: the same x give the same bits.  alpha, inv_beta: fp32 [C] on
+ * the device (inv_beta = 1 / (beta + 1e-9), or 1 / (alpha + 1e-9) for snake, computed by the caller); f_u, f_d: fp32 [12] on the device.
+ * Error bound of vbx_bigvgan_act against fp64 on the same inputs and parameters (eps = 2^-24; second-order terms are covered by
+ * the slack of one term in each sum):
+ *   E_u[m] = 7 eps 2 sum_i |f_u x|                                          six fmaf roundings and one of slack; the doubling is exact
+ *   E_s[m] = (1 + alpha inv_beta) E_u + inv_beta (eps |alpha u| + 2^-20 + eps) + eps |s|
+ *            the error of u and the rounding of the argument a pass through |ds/du| = |1 + inv_beta alpha sin(2 a)| <= 1 + alpha
+ *            inv_beta; sinf within 4 ulp of a value of at most 1 is 2^-21, doubled by the square (|d sn^2| <= 2 |sn| |d sn|); the
+ *            rounding of sn * sn; the rounding of the last fmaf
+ *   |err[t]| <= sum_tau |f_d[tau]| E_s[clamp(2 t + tau - 5)] + 13 eps sum_tau |f_d s| + 2^-11 |y| + 2^-25
+ *            twelve fmaf roundings and one of slack, then the fp16 store
+ * The 4 ulp of sinf is the figure of the OpenCL C specification (full profile), which the device library's sine is built to; it is
+ * ASSUMED here, not measured.
+ * vbx_bigvgan_act: y fp16 [B, L, C] = fp16(A(mean of `inputs` tensors x0 .. x2 fp16 [B, L, C])).  C a multiple of 8 up to 1536,
+ *   L in 1 .. 2^29 - 1.  Each s[m] is computed once per run of up to 32 positions that a thread walks with the twelve s of the
+ *   current output in registers.
+ * vbx_bigvgan_conv: y fp16 [B, L, Co] = conv(A(x)) + bias (+ res), A computed while the span is staged into the LDS: BIT-EQUAL to
+ *   vbx_bigvgan_act followed by vbx_hifigan_conv(act = 0) with the same operands.  A span position outside [0, L) is the convolution's
+ *   ZERO padding, not A evaluated past the row.  Limits and tile (vbx_bigvgan_conv_tile) are vbx_hifigan_conv's: the activation's
+ *   window lives in registers and takes no LDS beside the span.
+ * vbx_bigvgan_convtr: vbx_hifigan_convtr without an activation, C a multiple of 16 up to 1536; up to 1024 BIT-EQUAL to
+ *   vbx_hifigan_convtr(slope = 1.0), whose own limit stays 1024; its bound holds with the plain mean as the operand.
+ * vbx_bigvgan_post: y fp32 [B, T] = final(bias[0] + sum w[tap, c] fp16(A(mean of the inputs))[t + tap - k / 2, c]), zero padded, w fp32
+ *   [k, C], bias NULL = 0, the fmaf chain of vbx_hifigan_post; final 0: tanhf, 1: fminf(fmaxf(., -1), 1).  With a bias and final = 0
+ *   BIT-EQUAL to vbx_bigvgan_act followed by vbx_hifigan_post(inputs = 1, slope = 1.0).  Against fp64 on vbx_bigvgan_act's own output:
+ *   vbx_hifigan_post's bound, for final = 1 without the tanhf term: (k C + 2) 2^-24 (sum |w a| + |b|) (a clamp is 1-Lipschitz and
+ *   exact).  C a multiple of 8 up to 512, k odd and at most 11. */
+int vbx_bigvgan_act(const void* x0_f16, const void* x1_f16, const void* x2_f16, int inputs, const float* alpha, const float* inv_beta,
+                    const float* f_u, const float* f_d, void* y_f16, int B, int L, int C, void* stream);
+int vbx_bigvgan_conv_tile(int C, int k, int dilation);
+int vbx_bigvgan_conv(const void* x_f16, const float* alpha, const float* inv_beta, const float* f_u, const float* f_d, const void* w_f16,
+                     const float* bias, const void* res_f16, void* y_f16, int B, int L, int C, int Co, int k, int dilation, void* stream);
+int vbx_bigvgan_convtr(const void* x0_f16, const void* x1_f16, const void* x2_f16, int inputs, const void* w_f16, const float* bias,
+                       void* y_f16, int B, int L, int C, int stride, void* stream);
+int vbx_bigvgan_post(const void* x0_f16, const void* x1_f16, const void* x2_f16, int inputs, const float* alpha, const float* inv_beta,
+                     const float* f_u, const float* f_d, const float* w, const float* bias, float* y, int B, int T, int C, int k, int final,
+                     void* stream);
 /* Aligner primitives (voicebox_pytorch_amd.maximum_path / forward_sum_loss; csrc/align.hip): monotonic alignment search and the
  * forward-sum (CTC) loss over an attention map fp32 [B, T, K], T query frames by K keys.  K in 1 .. 1024, any T >= 1, B * T < 2^31;
  * everything else returns VBX_EINVAL.  query_lens / key_lens: int32 [B] on the device, NULL = T / K; a length is clamped into

@@ -13,7 +13,8 @@ CausalSEANetDecoder (the same two in EnCodec's causal form, which the published 
 ForwardSumLoss (monotonic alignment search and the forward-sum loss on the device: what an aligner is trained with), Aligner /
 aligner_attention (the alignment network itself, forward and backward on the device: phonemes and mels into durations),
 HiFiGANGenerator (HiFi-GAN's generator on the device: mels into waves, a `vocoder=` of LogMelCodec; weights are the user's, from a
-local checkpoint).
+local checkpoint), BigVGANGenerator (BigVGAN's generator on the device, its anti-aliased snake activations in HIP: the same call
+shape; a local checkpoint and its config.json).
 """
 from . import _lib  # noqa: F401
 
@@ -27,6 +28,7 @@ try:  # model classes need torch; keep `_lib` importable on its own
     from .vocos import VocosDecoder, VocosEncodecDecoder  # noqa: F401
     from .seanet import CausalSEANetDecoder, CausalSEANetEncoder, SEANetDecoder, SEANetEncoder  # noqa: F401
     from .hifigan import HiFiGANGenerator  # noqa: F401
+    from .bigvgan import BigVGANGenerator  # noqa: F401
     from .align import maximum_path, forward_sum_loss, ForwardSumLoss, Aligner, aligner_attention  # noqa: F401
     from .engine import precise_mode, set_precise, precise_enabled  # noqa: F401
     from .dp import ema_decay_at  # noqa: F401  (the decay schedule of dp.TrainStep(ema_decay=))
@@ -35,7 +37,7 @@ try:  # model classes need torch; keep `_lib` importable on its own
     __all__ += ["VoiceBox", "ConditionalFlowMatcherWrapper", "Transformer", "Attend", "VoiceBoxTrainer", "DurationPredictor", "mask_from_frac_lengths",
                 "mask_from_start_end_indices", "prob_mask_like", "reduce_masks_with_and", "precise_mode", "set_precise", "precise_enabled",
                 "AudioEncoderDecoder", "LogMelCodec", "griffin_lim", "resample", "Resample", "VocosDecoder", "VocosEncodecDecoder", "ResidualVQ", "EncodecVocoCodec", "SEANetEncoder", "SEANetDecoder",
-                "CausalSEANetEncoder", "CausalSEANetDecoder", "HiFiGANGenerator",
+                "CausalSEANetEncoder", "CausalSEANetDecoder", "HiFiGANGenerator", "BigVGANGenerator",
                 "maximum_path", "forward_sum_loss", "ForwardSumLoss", "Aligner", "aligner_attention", "lora", "ema_decay_at"]
 except ModuleNotFoundError as _e:  # pragma: no cover - only while the package is being bootstrapped
     if "masks" not in str(_e) and "model" not in str(_e):

@@ -105,6 +105,11 @@ _PROTOS = {
     "vbx_hifigan_respair": [P, P, P, P, P, P, I, I, I, I, I, F, P],
     "vbx_hifigan_convtr": [P, P, P, I, P, P, P, I, I, I, I, F, P],
     "vbx_hifigan_post": [P, P, P, I, P, P, P, I, I, I, I, F, P],
+    "vbx_bigvgan_act": [P, P, P, I, P, P, P, P, P, I, I, I, P],
+    "vbx_bigvgan_conv_tile": [I, I, I],
+    "vbx_bigvgan_conv": [P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, P],
+    "vbx_bigvgan_convtr": [P, P, P, I, P, P, P, I, I, I, I, P],
+    "vbx_bigvgan_post": [P, P, P, I, P, P, P, P, P, P, P, I, I, I, I, I, P],
     "vbx_maximum_path": [P, P, P, P, P, P, I, I, I, P],
     "vbx_forward_sum_fwd": [P, P, P, F, P, P, P, P, I, I, I, P],
     "vbx_forward_sum_bwd": [P, P, P, F, P, P, P, P, P, I, I, I, P],
