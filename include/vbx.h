@@ -360,6 +360,19 @@ int vbx_copy_cols_f32(const float* src, int ld_src, float* dst, long rows, int c
 int vbx_logmel(const float* audio, float* out, const float* window, const float* tw_re, const float* tw_im, const int* fb_start,
                const int* fb_len, const int* fb_off, const float* fb_w, int B, long T, int n_fft, int hop, int n_mels, int log_out,
                void* stream);
+/* The vocoders' own mel front end (HiFiGANMelCodec.encode / mel_spectrogram; the arithmetic of HiFi-GAN's and BigVGAN's
+ * meldataset.mel_spectrogram at center = False), the sibling of vbx_logmel on the same transform and the same filter runs:
+ * audio fp32 [B, T] is reflect-padded by `pad` samples on both sides (HiFi-GAN: pad = (n_fft - hop) / 2; 0 <= pad <= n_fft / 2, T > pad,
+ * T + 2 pad >= n_fft: one reflection per side suffices, and one frame may reflect on both), frame f = the n_fft samples from
+ * f * hop - pad, frames = 1 + (T + 2 pad - n_fft) / hop, times window[n_fft], fp32 FFT in the LDS (sizes and tables as vbx_logmel),
+ * mag = sqrtf(re^2 + im^2 + 1e-9f), mel filter runs as vbx_logmel (the caller passes Slaney-scale, area-normalised weights),
+ * out = (ln(max(mel, 1e-5f)) - mean) * inv_std -- the accurate sqrtf, the logarithm taken in fp64 and rounded once to fp32 (the device's
+ * logf is a 2-ulp function: silence would miss ln(1e-5) by 1.7 ulp); mean = 0, inv_std = 1 give the plain logarithm exactly.
+ * channel_first = 0: out [B, frames, n_mels] (a codec's latents); 1: out [B, n_mels, frames] (what the generators take) -- the same
+ * bits, transposed.  One launch, no atomics: reruns are bit-identical and a row does not depend on the rows beside it. */
+int vbx_melspec(const float* audio, float* out, const float* window, const float* tw_re, const float* tw_im, const int* fb_start,
+                const int* fb_len, const int* fb_off, const float* fb_w, int B, long T, int n_fft, int hop, int pad, int n_mels,
+                float mean, float inv_std, int channel_first, void* stream);
 /* Vocoder-free decode (LogMelCodec.mel_to_magnitude / griffin_lim; csrc/griffinlim.hip).
  * vbx_mel_to_mag: mel fp32 [B, frames, n_mels] (dB when log_in, else power) -> mag fp32 [B, frames, n_bins] (frame-major)
  *   = sqrt(max(pinv(fb^T) @ P, 0)), P = 10^(mel / 10) or mel; pinv_t [n_mels, n_bins] is the pseudo-inverse (taken in fp64 on the

@@ -14,7 +14,8 @@ ForwardSumLoss (monotonic alignment search and the forward-sum loss on the devic
 aligner_attention (the alignment network itself, forward and backward on the device: phonemes and mels into durations),
 HiFiGANGenerator (HiFi-GAN's generator on the device: mels into waves, a `vocoder=` of LogMelCodec; weights are the user's, from a
 local checkpoint), BigVGANGenerator (BigVGAN's generator on the device, its anti-aliased snake activations in HIP: the same call
-shape; a local checkpoint and its config.json).
+shape; a local checkpoint and its config.json), HiFiGANMelCodec / mel_spectrogram (the mel front end those two generators were
+trained on -- Slaney filters, magnitude, ln, center=False -- in one kernel: the codec published HiFi-GAN / BigVGAN weights want).
 """
 from . import _lib  # noqa: F401
 
@@ -25,6 +26,7 @@ try:  # model classes need torch; keep `_lib` importable on its own
     from .trainer import VoiceBoxTrainer  # noqa: F401
     from .duration import DurationPredictor  # noqa: F401
     from .codec import AudioEncoderDecoder, LogMelCodec, griffin_lim, resample, Resample, ResidualVQ, EncodecVocoCodec  # noqa: F401
+    from .codec import HiFiGANMelCodec, mel_spectrogram  # noqa: F401
     from .vocos import VocosDecoder, VocosEncodecDecoder  # noqa: F401
     from .seanet import CausalSEANetDecoder, CausalSEANetEncoder, SEANetDecoder, SEANetEncoder  # noqa: F401
     from .hifigan import HiFiGANGenerator  # noqa: F401
@@ -37,7 +39,7 @@ try:  # model classes need torch; keep `_lib` importable on its own
     __all__ += ["VoiceBox", "ConditionalFlowMatcherWrapper", "Transformer", "Attend", "VoiceBoxTrainer", "DurationPredictor", "mask_from_frac_lengths",
                 "mask_from_start_end_indices", "prob_mask_like", "reduce_masks_with_and", "precise_mode", "set_precise", "precise_enabled",
                 "AudioEncoderDecoder", "LogMelCodec", "griffin_lim", "resample", "Resample", "VocosDecoder", "VocosEncodecDecoder", "ResidualVQ", "EncodecVocoCodec", "SEANetEncoder", "SEANetDecoder",
-                "CausalSEANetEncoder", "CausalSEANetDecoder", "HiFiGANGenerator", "BigVGANGenerator",
+                "CausalSEANetEncoder", "CausalSEANetDecoder", "HiFiGANGenerator", "BigVGANGenerator", "HiFiGANMelCodec", "mel_spectrogram",
                 "maximum_path", "forward_sum_loss", "ForwardSumLoss", "Aligner", "aligner_attention", "lora", "ema_decay_at"]
 except ModuleNotFoundError as _e:  # pragma: no cover - only while the package is being bootstrapped
     if "masks" not in str(_e) and "model" not in str(_e):

@@ -73,6 +73,7 @@ _PROTOS = {
     "vbx_masked_mse_bwd_ld": [P, I, P, P, P, P, P, I, I, I, P],
     "vbx_copy_cols_f32": [P, I, P, L, I, P],
     "vbx_logmel": [P, P, P, P, P, P, P, P, P, I, L, I, I, I, I, P],
+    "vbx_melspec": [P, P, P, P, P, P, P, P, P, I, L, I, I, I, I, F, F, I, P],
     "vbx_mel_to_mag": [P, P, P, I, I, I, I, I, P],
     "vbx_griffinlim_lds_bytes": [I, I, I],
     "vbx_griffinlim": [P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, F, P],

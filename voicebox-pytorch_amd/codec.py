@@ -16,6 +16,11 @@ too: the published arithmetic of torchaudio.functional.resample, restated in fp6
 ResidualVQ / EncodecVocoCodec (csrc/rvq.hip) are the reference's EncodecVoco (:551-592) around a residual vector quantizer on the device:
 codes in and out, latents from codes, features for a VocosDecoder.  EnCodec's SEANet encoder is seanet.py's SEANetEncoder, passed as
 encoder= (from_encodec_checkpoint builds both from one local file); parity with encodec / vocos / vector_quantize_pytorch is UNPINNED likewise (tests/rvq_ref.py restates the arithmetic).
+
+HiFiGANMelCodec / mel_spectrogram (csrc/mel.hip, vbx_melspec) are the mel front end HiFi-GAN and BigVGAN were trained on -- Slaney
+filters, magnitude, ln(clamp(., 1e-5)), center=False framing -- and the codec published weights of those generators want (the
+Voicebox paper's own: 80-bin log mels decoded by HiFi-GAN).  Parity with HiFi-GAN / BigVGAN / librosa is UNPINNED likewise
+(tests/hifigan_mel_ref.py restates the arithmetic in fp64).
 """
 import functools
 import math
@@ -48,6 +53,13 @@ def mel_filter_runs(n_fft, n_mels, sampling_rate, f_max, f_min=0.0):
     f_diff = f_pts[1:] - f_pts[:-1]
     slopes = f_pts[None, :] - all_freqs[:, None]
     fb = torch.clamp(torch.minimum(-slopes[:, :-2] / f_diff[:-1], slopes[:, 2:] / f_diff[1:]), min=0.0)  # [n_freqs, n_mels]
+    return _filter_runs(fb)
+
+
+def _filter_runs(fb):
+    """a dense bank fp64 [n_freqs, n_mels] as the runs vbx_logmel / vbx_melspec read: per filter the bins from its first to its last
+    non-zero weight (an all-zero filter is a run of length 0); one zero weight is appended so the table is never empty"""
+    n_mels = fb.shape[1]
     start, length, offset, weights = [], [], [], []
     for m in range(n_mels):
         nz = torch.nonzero(fb[:, m]).flatten()
@@ -391,6 +403,242 @@ class LogMelCodec(AudioEncoderDecoder):
         if self.log:
             mel = torch.pow(10.0, 0.05 * mel)  # DB_to_amplitude(ref=1, power=0.5)
         return self.vocoder(mel)
+
+
+def hz_to_mel_slaney(f):
+    """Slaney's mel scale (the Auditory Toolbox; librosa's default, htk=False): linear below 1 kHz at 200 / 3 Hz per mel,
+    logarithmic above with step ln(6.4) / 27, so 1000 Hz = 15 mel"""
+    return 3.0 * f / 200.0 if f < 1000.0 else 15.0 + math.log(f / 1000.0) * (27.0 / math.log(6.4))
+
+
+def mel_to_hz_slaney(m):
+    return 200.0 * m / 3.0 if m < 15.0 else 1000.0 * math.exp((math.log(6.4) / 27.0) * (m - 15.0))
+
+
+def slaney_mel_filterbank(n_fft, num_mels, sampling_rate, fmin=0.0, fmax=None):
+    """librosa.filters.mel(sr, n_fft, n_mels, fmin, fmax) at its defaults (htk=False, norm='slaney'), restated from the published
+    formulas (PARITY UNPINNED: librosa is not a dependency): fp64 [num_mels, n_fft / 2 + 1].  Triangles between the num_mels + 2
+    points equally spaced on Slaney's mel scale from fmin to fmax (None: sampling_rate / 2), over the bin frequencies
+    linspace(0, sampling_rate / 2, n_fft / 2 + 1) -- the float sampling_rate / 2 --, filter m times 2 / (f[m + 2] - f[m]) (unit area).
+    An all-zero filter warns, as librosa does."""
+    fmax = sampling_rate / 2.0 if fmax is None else float(fmax)
+    freqs = torch.linspace(0, sampling_rate / 2.0, n_fft // 2 + 1, dtype=torch.float64)
+    lo, hi = hz_to_mel_slaney(float(fmin)), hz_to_mel_slaney(fmax)
+    mels = torch.linspace(lo, hi, num_mels + 2, dtype=torch.float64)
+    f_pts = torch.where(mels < 15.0, 200.0 * mels / 3.0, 1000.0 * torch.exp((math.log(6.4) / 27.0) * (mels - 15.0)))
+    f_diff = f_pts[1:] - f_pts[:-1]
+    ramps = f_pts[:, None] - freqs[None, :]
+    fb = torch.clamp(torch.minimum(-ramps[:-2] / f_diff[:-1, None], ramps[2:] / f_diff[1:, None]), min=0.0)
+    fb = fb * (2.0 / (f_pts[2:] - f_pts[:-2]))[:, None]
+    if not bool((fb.max(dim=1).values > 0).all()):
+        import warnings
+
+        warnings.warn("Empty filters detected in mel frequency basis. Some channels will produce empty responses. Try increasing "
+                      "your sampling rate (and fmax) or reducing n_mels.", stacklevel=2)
+    return fb
+
+
+def melspec_pad(n_fft, hop_size):
+    """the reflect pad of HiFi-GAN's mel_spectrogram on each side: int((n_fft - hop_size) / 2)"""
+    return int((n_fft - hop_size) / 2)
+
+
+def melspec_frames(samples, n_fft, hop_size):
+    """frames of `samples` samples at center=False over that pad: samples // hop_size when n_fft - hop_size is even"""
+    return 1 + (samples + 2 * melspec_pad(n_fft, hop_size) - n_fft) // hop_size
+
+
+def _check_melspec_args(n_fft, num_mels, sampling_rate, hop_size, win_size, fmin, fmax, center=False):
+    """what vbx_melspec serves; returns fmax with None resolved to sampling_rate / 2"""
+    if center:
+        raise NotImplementedError("center=True is not built: HiFi-GAN / BigVGAN frame with center=False over a hop-aligned reflect pad "
+                                  "(LogMelCodec is the centred front end)")
+    if int(n_fft) != n_fft or n_fft & (n_fft - 1) or not 256 <= n_fft <= 2048:
+        raise NotImplementedError(f"n_fft must be a power of two in 256 .. 2048 (got {n_fft})")
+    if not 0 < win_size <= n_fft or not 0 < hop_size <= n_fft:
+        raise ValueError(f"need 0 < win_size <= n_fft and 0 < hop_size <= n_fft (got win_size {win_size}, hop_size {hop_size}, n_fft {n_fft})")
+    if not 1 <= num_mels <= 512:
+        raise NotImplementedError(f"num_mels must be in 1 .. 512 (got {num_mels})")
+    if sampling_rate <= 0:
+        raise ValueError(f"need sampling_rate > 0 (got {sampling_rate})")
+    fmax = sampling_rate / 2.0 if fmax is None else fmax
+    if not 0 <= fmin < fmax <= sampling_rate / 2.0:
+        raise ValueError(f"need 0 <= fmin < fmax <= sampling_rate / 2 (got fmin {fmin}, fmax {fmax}, sampling_rate {sampling_rate})")
+    return fmax
+
+
+_melspec_tables_cache = {}  # (n_fft, num_mels, sampling_rate, win_size, fmin, fmax, device) -> device tables, least recently used first
+
+
+def _melspec_tables(n_fft, num_mels, sampling_rate, win_size, fmin, fmax, device):
+    """(window, tw_re, tw_im, fb_start, fb_len, fb_off, fb_w) on `device`: built in fp64, rounded once to fp32"""
+    key = (int(n_fft), int(num_mels), float(sampling_rate), int(win_size), float(fmin), float(fmax), str(device))
+    hit = _melspec_tables_cache.pop(key, None)
+    if hit is None:
+        win, tw_re, tw_im = _stft_tables(n_fft, win_size)
+        start, length, offset, weights = _filter_runs(slaney_mel_filterbank(n_fft, num_mels, sampling_rate, fmin, fmax).T)
+        assert int((start + length).max()) <= n_fft // 2 + 1
+        hit = tuple(t.to(device) for t in (win.float(), tw_re.float(), tw_im.float(), start, length, offset, weights.float()))
+        if len(_melspec_tables_cache) >= 8:
+            _melspec_tables_cache.pop(next(iter(_melspec_tables_cache)))
+    _melspec_tables_cache[key] = hit
+    return hit
+
+
+def _melspec(y, n_fft, num_mels, sampling_rate, hop_size, win_size, fmin, fmax, mean, std, channel_first, who):
+    """one launch of vbx_melspec over waves [B, T] or [B, 1, T]; the arguments are already checked"""
+    if y.ndim == 3 and y.shape[1] == 1:
+        y = y[:, 0]
+    if y.ndim != 2 or not y.is_floating_point():
+        raise ValueError(f"{who} takes float waves (batch, samples), got {tuple(y.shape)} {y.dtype}")
+    B, T = y.shape
+    pad = melspec_pad(n_fft, hop_size)
+    if T <= pad:
+        raise RuntimeError(f"reflect padding of (n_fft - hop_size) / 2 = {pad} samples needs a longer wave (got {T} samples)")
+    if T + 2 * pad < n_fft:
+        raise RuntimeError(f"{T} samples and {pad} of padding on each side do not fill one frame of n_fft = {n_fft}")
+    if y.device.type != "cuda":
+        raise _lib.VbxError(f"{who} runs only on an MI355X (gfx950) through libvbx_hip.so; the wave is on '{y.device}'")
+    tables = _melspec_tables(n_fft, num_mels, sampling_rate, win_size, fmin, fmax, y.device)
+    y = y.detach().to(torch.float32).contiguous()
+    frames = melspec_frames(T, n_fft, hop_size)
+    out = torch.empty((B, num_mels, frames) if channel_first else (B, frames, num_mels), dtype=torch.float32, device=y.device)
+    if B:
+        _lib.call("vbx_melspec", y, out, *tables, B, T, n_fft, hop_size, pad, num_mels, 0.0 if mean is None else float(mean),
+                  1.0 if std is None else 1.0 / float(std), int(channel_first), _lib.current_stream())
+    return out
+
+
+def mel_spectrogram(y, n_fft, num_mels, sampling_rate, hop_size, win_size, fmin, fmax, center=False):
+    """HiFi-GAN's meldataset.mel_spectrogram (BigVGAN ships the same function) on the device, one launch (csrc/mel.hip): waves
+    y [B, T] -> ln(clamp(mel, 1e-5)) fp32 [B, num_mels, frames], frames = 1 + (T + 2 p - n_fft) // hop_size:
+
+        p = int((n_fft - hop_size) / 2) samples of reflect padding on both sides (T > p, else RuntimeError as F.pad raises)
+        frames of n_fft samples every hop_size (center=False), times the periodic Hann window of win_size samples centred in n_fft
+        mag = sqrt(re^2 + im^2 + 1e-9);  mel = slaney_mel_filterbank(...) @ mag;  fmax=None: sampling_rate / 2
+
+    PARITY UNPINNED: neither HiFi-GAN, BigVGAN nor librosa is a dependency and no vector of them is committed; this follows their
+    published arithmetic, restated in fp64 in tests/hifigan_mel_ref.py.  Tables are cached per argument tuple and device.  Raises
+    NotImplementedError for center=True, n_fft not a power of two in 256 .. 2048 and num_mels outside 1 .. 512, ValueError for the
+    other argument ranges.  Runs only on the GPU; no gradient is taken through it."""
+    fmax = _check_melspec_args(n_fft, num_mels, sampling_rate, hop_size, win_size, fmin, fmax, center)
+    return _melspec(y, n_fft, num_mels, sampling_rate, hop_size, win_size, fmin, fmax, None, None, True, "mel_spectrogram")
+
+
+class HiFiGANMelCodec(AudioEncoderDecoder):
+    """The mel front end HiFi-GAN and BigVGAN were trained on (mel_spectrogram above) as a codec: latents are ln(clamp(mel, 1e-5))
+    fp32 [B, frames, num_mels], frames = samples // hop_size (n_fft - hop_size even), optionally (. - mean) / std with two scalars
+    (the Voicebox paper's global normalisation; fit_normalization measures them).  The defaults are HiFi-GAN's V1 configuration.
+    Published HiFi-GAN / BigVGAN weights want THIS codec, not LogMelCodec(vocoder=gen): that one hands HTK-scale, power, centred
+    features no such checkpoint has seen.
+
+    vocoder: a HiFiGANGenerator, a BigVGANGenerator or any module mel [B, num_mels, frames] -> wave, built with input_log=False
+    (the codec already hands log features).  decode undoes the normalisation, transposes and calls it.  "griffin_lim" raises: that
+    decode assumes centred framing.  PARITY with HiFi-GAN / BigVGAN / librosa is UNPINNED (mel_spectrogram's docstring)."""
+
+    def __init__(self, *, num_mels=80, n_fft=1024, hop_size=256, win_size=1024, sampling_rate=22050, fmin=0, fmax=8000, vocoder=None,
+                 mean=None, std=None):
+        super().__init__()
+        self.fmax = _check_melspec_args(n_fft, num_mels, sampling_rate, hop_size, win_size, fmin, fmax)
+        if isinstance(vocoder, str):
+            if vocoder == "griffin_lim":
+                raise NotImplementedError('HiFiGANMelCodec(vocoder="griffin_lim") is not built: griffin_lim assumes centred framing '
+                                          "(LogMelCodec serves it)")
+            raise ValueError(f'vocoder must be None or a module (got "{vocoder}")')
+        self.num_mels, self.n_fft, self.hop_size, self.win_size, self.fmin = int(num_mels), int(n_fft), int(hop_size), int(win_size), fmin
+        self._sampling_rate = sampling_rate
+        self.vocoder = vocoder
+        self.mean = self.std = None
+        self.set_normalization(mean, std)
+
+    def set_normalization(self, mean, std):
+        """both None: plain log mels; else the two scalars of (. - mean) / std, std > 0"""
+        if (mean is None) != (std is None):
+            raise ValueError("mean and std go together: give both or neither")
+        if std is not None and not (float(std) > 0 and math.isfinite(float(std)) and math.isfinite(float(mean))):
+            raise ValueError(f"need finite mean and std > 0 (got mean {mean}, std {std})")
+        self.mean, self.std = (None, None) if mean is None else (float(mean), float(std))
+
+    @classmethod
+    def from_config(cls, config, vocoder=None, **kw):
+        """config: a LOCAL config.json path or a dict with HiFi-GAN's / BigVGAN's keys num_mels, n_fft, hop_size, win_size,
+        sampling_rate, fmin, fmax (null: sampling_rate / 2); every other key (fmax_for_loss, the generator's) is ignored.
+        **kw: mean, std."""
+        from .hifigan import _read_config
+
+        config = _read_config(config)
+        keys = ("num_mels", "n_fft", "hop_size", "win_size", "sampling_rate", "fmin", "fmax")
+        missing = [k for k in keys if k not in config]
+        if missing:
+            raise KeyError(f"HiFiGANMelCodec.from_config: the config has no {missing}")
+        return cls(vocoder=vocoder, **{k: config[k] for k in keys}, **kw)
+
+    @classmethod
+    def from_checkpoint(cls, generator_path, config, **kw):
+        """A LOCAL generator file and its config.json (path or dict): a BigVGANGenerator when the config has an `activation` key,
+        else a HiFiGANGenerator, built by their from_checkpoint, paired with the codec of the same config."""
+        from .bigvgan import BigVGANGenerator
+        from .hifigan import HiFiGANGenerator, _read_config
+
+        config = _read_config(config)
+        if not isinstance(config, dict):
+            raise TypeError("HiFiGANMelCodec.from_checkpoint needs the generator's config (a local config.json path or a dict)")
+        gen = (BigVGANGenerator if "activation" in config else HiFiGANGenerator).from_checkpoint(generator_path, config=config)
+        return cls.from_config(config, vocoder=gen, **kw).eval()
+
+    @property
+    def downsample_factor(self):
+        return self.hop_size
+
+    @property
+    def latent_dim(self):
+        return self.num_mels
+
+    @property
+    def sampling_rate(self):
+        return self._sampling_rate
+
+    def _encode(self, audio, mean, std):
+        return _melspec(audio, self.n_fft, self.num_mels, self._sampling_rate, self.hop_size, self.win_size, self.fmin, self.fmax, mean,
+                        std, False, "HiFiGANMelCodec.encode")
+
+    def encode(self, audio):
+        """waves [B, T] or [B, 1, T] -> latents fp32 [B, frames, num_mels]; one launch, no host synchronisation"""
+        return self._encode(audio, self.mean, self.std)
+
+    def fit_normalization(self, waves):
+        """sets mean / std to the mean and (population) standard deviation of every plain log-mel value of `waves`, an iterable of
+        device waves [B, T] (lengths may differ between items); plain torch reductions in fp64, one host read at the end"""
+        n, s, ss = 0, None, None
+        for w in waves:
+            x = self._encode(w, None, None).double()
+            n += x.numel()
+            s = x.sum() if s is None else s + x.sum()
+            ss = (x * x).sum() if ss is None else ss + (x * x).sum()
+        if not n:
+            raise ValueError("fit_normalization needs at least one wave")
+        mean = float(s) / n
+        self.set_normalization(mean, math.sqrt(max(float(ss) / n - mean * mean, 0.0)))
+        return self.mean, self.std
+
+    def decode(self, latents):
+        """latents [B, frames, num_mels] -> vocoder(log mel [B, num_mels, frames]), the normalisation undone"""
+        voc = self.vocoder
+        if voc is None:
+            raise NotImplementedError("HiFiGANMelCodec.decode needs a vocoder (log mel [B, num_mels, frames] -> wave): pass vocoder= "
+                                      "(HiFiGANGenerator, BigVGANGenerator)")
+        if getattr(voc, "input_log", False):
+            raise ValueError("HiFiGANMelCodec hands LOG mels: build the vocoder with input_log=False")
+        if getattr(voc, "n_mels", self.num_mels) != self.num_mels:
+            raise ValueError(f"the vocoder takes {voc.n_mels} mel bins, the codec makes {self.num_mels}")
+        if getattr(voc, "hop_length", self.hop_size) != self.hop_size:
+            raise ValueError(f"the vocoder makes {voc.hop_length} samples per frame, the codec's hop_size is {self.hop_size}")
+        if latents.ndim != 3 or latents.shape[2] != self.num_mels:
+            raise ValueError(f"decode takes latents (batch, frames, num_mels = {self.num_mels}), got {tuple(latents.shape)}")
+        mel = latents.transpose(1, 2)
+        if self.mean is not None:
+            mel = mel * self.std + self.mean
+        return voc(mel)
 
 
 RVQ_BANDWIDTH_QUANTIZERS = (2, 4, 8, 16)  # EnCodec 24 kHz: bandwidth ids 0 .. 3 (1.5, 3, 6, 12 kbps) -> codebooks in use
