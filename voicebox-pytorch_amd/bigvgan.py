@@ -26,14 +26,14 @@ precision contract of include/vbx.h: activations fp16 channel-last, rounded once
 sinf, in one documented order of operations; weights fp16, weight norm folded in fp32; sums fp32; no atomics.  Inference only.
 """
 import math
-import os
 
 import torch
 from torch import nn
 
 from . import _lib
-from ._packing import PackedWeights, tensors_key
-from .hifigan import HiFiGANGenerator, _read_config, _WNConv, _WNConvTr, pack_convtr_weight
+from ._melgen import _MelGenerator
+from ._packing import tensors_key
+from ._wnconv import WNConv, read_config
 
 ACTIVATIONS = ("snake", "snakebeta")
 FILTER_TAPS = 12
@@ -84,19 +84,19 @@ class _Activation1d(nn.Module):
 class _AMPBlock1(nn.Module):
     def __init__(self, ch, k, dilations, act):
         super().__init__()
-        self.convs1 = nn.ModuleList([_WNConv(ch, ch, k, d) for d in dilations])
-        self.convs2 = nn.ModuleList([_WNConv(ch, ch, k, 1) for _ in dilations])
+        self.convs1 = nn.ModuleList([WNConv(ch, ch, k, d) for d in dilations])
+        self.convs2 = nn.ModuleList([WNConv(ch, ch, k, 1) for _ in dilations])
         self.activations = nn.ModuleList([act(ch) for _ in range(2 * len(dilations))])  # interleaved: 2m before convs1[m], 2m + 1 before convs2[m]
 
 
 class _AMPBlock2(nn.Module):
     def __init__(self, ch, k, dilations, act):
         super().__init__()
-        self.convs = nn.ModuleList([_WNConv(ch, ch, k, d) for d in dilations])
+        self.convs = nn.ModuleList([WNConv(ch, ch, k, d) for d in dilations])
         self.activations = nn.ModuleList([act(ch) for _ in dilations])
 
 
-class BigVGANGenerator(PackedWeights, nn.Module):
+class BigVGANGenerator(_MelGenerator):
     """mel [B, n_mels, frames] (any float dtype, on the GPU; amplitude mels with input_log=True: log(clamp(mel, 1e-5)) is taken as the
     input is packed) -> wave fp32 [B, frames * hop_length].
 
@@ -109,7 +109,8 @@ class BigVGANGenerator(PackedWeights, nn.Module):
     than 2 * rate; a residual kernel that is even or outside 3 .. 11; a dilation outside 1 .. 12; other than 1 .. 3 residual blocks per
     stage or 1 .. 3 dilations per block; resblock other than "1" / "2"; an activation other than "snake" / "snakebeta"; an
     Activation1d other than ratio 2 / 2 with 12 / 12 taps.  GPU tensors only (a CPU tensor raises VbxError); a forward on a device
-    other than the parameters' MOVES THE MODULE there.
+    other than the parameters' MOVES THE MODULE there.  load_state_dict loads the filter buffers and USES them; one of another shape
+    than [1, 1, 12] raises ValueError.
 
     fuse_act_max_channels: up to this width a residual convolution computes its Activation1d while it stages its span
     (vbx_bigvgan_conv); above it the activation is a launch of its own (vbx_bigvgan_act) and the activated tensor goes through
@@ -133,94 +134,51 @@ class BigVGANGenerator(PackedWeights, nn.Module):
     FUSE_ACT_MAX_CHANNELS = 384
     FUSE_ACT_MAX_ELEMENTS = 4 << 20  # B * L * C of the convolution's input; applies only while fuse_act_max_channels is a number
 
+    MAX_STAGES, MAX_CHANNELS = 6, 1536
+    TILE_ENTRY = "vbx_bigvgan_conv_tile"
+    UP_KEY = "ups.{}.0"
+    LAYOUT = "a BigVGAN generator layout (conv_pre, ups, resblocks, activation_post, conv_post)"
+    PRE_SLOPE = 1.0
+
     def __init__(self, n_mels=100, upsample_initial_channel=512, upsample_rates=(8, 8, 2, 2), upsample_kernel_sizes=(16, 16, 4, 4),
                  resblock="1", resblock_kernel_sizes=(3, 7, 11), resblock_dilation_sizes=((1, 3, 5),) * 3, activation="snakebeta",
                  snake_logscale=True, use_tanh_at_final=True, use_bias_at_final=True, input_log=False, up_ratio=2, down_ratio=2,
                  up_kernel_size=FILTER_TAPS, down_kernel_size=FILTER_TAPS):
         super().__init__()
-        no = lambda what: NotImplementedError(f"BigVGANGenerator: {what} is not built")
-        rates, uks = tuple(int(r) for r in upsample_rates), tuple(int(k) for k in upsample_kernel_sizes)
-        rks = tuple(int(k) for k in resblock_kernel_sizes)
-        dils = tuple(tuple(int(d) for d in ds) for ds in resblock_dilation_sizes)
-        resblock = str(resblock)
-        if resblock not in ("1", "2"):
-            raise no(f'resblock="{resblock}" (only "1" and "2")')
         if activation not in ACTIVATIONS:
-            raise no(f'activation="{activation}" (only "snake" and "snakebeta")')
+            raise self._no(f'activation="{activation}" (only "snake" and "snakebeta")')
         if (up_ratio, down_ratio, up_kernel_size, down_kernel_size) != (2, 2, FILTER_TAPS, FILTER_TAPS):
-            raise no(f"an Activation1d with ratios {up_ratio} / {down_ratio} and {up_kernel_size} / {down_kernel_size} taps (only 2 / 2, 12 / 12)")
-        if not 1 <= n_mels <= 512:
-            raise no(f"n_mels={n_mels} (1 .. 512)")
-        if not 1 <= len(rates) <= 6:
-            raise no(f"{len(rates)} upsampling stages (1 .. 6)")
-        if len(uks) != len(rates):
-            raise ValueError("BigVGANGenerator: upsample_rates and upsample_kernel_sizes differ in length")
-        for u, k in zip(rates, uks):
-            if u % 2 or not 2 <= u <= 8:
-                raise no(f"upsample rate {u} (even, 2 .. 8)")
-            if k != 2 * u:
-                raise no(f"upsample kernel {k} at rate {u} (only kernel = 2 * rate)")
-        c0, unit = int(upsample_initial_channel), 8 * 2 ** len(rates)
-        if c0 <= 0 or c0 % unit or c0 > 1536:
-            raise no(f"upsample_initial_channel={c0} (a multiple of 8 * 2^stages = {unit}, at most 1536)")
-        if not 1 <= len(rks) <= 3:
-            raise no(f"{len(rks)} residual blocks per stage (1 .. 3)")
-        if len(dils) != len(rks):
-            raise ValueError("BigVGANGenerator: resblock_kernel_sizes and resblock_dilation_sizes differ in length")
-        for k, ds in zip(rks, dils):
-            if k % 2 == 0 or not 3 <= k <= 11:
-                raise no(f"residual kernel {k} (odd, 3 .. 11)")
-            if not 1 <= len(ds) <= 3:
-                raise no(f"{len(ds)} dilations per residual block (1 .. 3)")
-            if any(not 1 <= d <= 12 for d in ds):
-                raise no(f"dilations {ds} (each 1 .. 12)")
-        self.n_mels, self.upsample_initial_channel, self.upsample_rates, self.upsample_kernel_sizes = int(n_mels), c0, rates, uks
-        self.resblock, self.resblock_kernel_sizes, self.resblock_dilation_sizes, self.input_log = resblock, rks, dils, bool(input_log)
+            raise self._no(f"an Activation1d with ratios {up_ratio} / {down_ratio} and {up_kernel_size} / {down_kernel_size} taps (only 2 / 2, 12 / 12)")
         self.activation, self.snake_logscale = activation, bool(snake_logscale)
         self.use_tanh_at_final, self.use_bias_at_final = bool(use_tanh_at_final), bool(use_bias_at_final)
-        self.num_kernels, self.fuse_act_max_channels = len(rks), self.FUSE_ACT_MAX_CHANNELS
-        act = lambda ch: _Activation1d(ch, activation == "snakebeta", self.snake_logscale)
-        block = _AMPBlock1 if resblock == "1" else _AMPBlock2
-        self.conv_pre = _WNConv(self.n_mels, c0, 7)
-        self.ups, self.resblocks, ch = nn.ModuleList(), nn.ModuleList(), c0
-        for u, k in zip(rates, uks):
-            self.ups.append(nn.ModuleList([_WNConvTr(ch, ch // 2, k, stride=u)]))  # the published name is ups.{i}.0
-            ch //= 2
-            for rk, ds in zip(rks, dils):
-                self.resblocks.append(block(ch, rk, ds, act))
-        self.activation_post = act(ch)
-        self.conv_post = _WNConv(ch, 1, 7)
+        self.fuse_act_max_channels = self.FUSE_ACT_MAX_CHANNELS
+        self._build(n_mels, upsample_initial_channel, upsample_rates, upsample_kernel_sizes, resblock, resblock_kernel_sizes,
+                    resblock_dilation_sizes, input_log)
+
+    def _act(self, ch):
+        return _Activation1d(ch, self.activation == "snakebeta", self.snake_logscale)
+
+    def _up(self, conv):
+        return nn.ModuleList([conv])  # the published name is ups.{i}.0
+
+    def _block(self, ch, k, dilations):
+        return (_AMPBlock1 if self.resblock == "1" else _AMPBlock2)(ch, k, dilations, self._act)
+
+    def _post_layers(self, ch):
+        self.activation_post = self._act(ch)
+        super()._post_layers(ch)
         if not self.use_bias_at_final:
             self.conv_post.bias = None
-        if os.path.exists(_lib.LIB_PATH):  # whatever the convolution kernel cannot tile is refused here, not at the first forward
-            for m in self.modules():
-                if isinstance(m, _WNConv) and not m.transposed and m is not self.conv_post:
-                    try:
-                        _lib.call_value("vbx_bigvgan_conv_tile", -(-m.cin // 8) * 8, m.k, m.dilation)
-                    except _lib.VbxError as e:
-                        raise no(f"a convolution {m.cin} -> {m.cout}, kernel {m.k}, dilation {m.dilation} ({e})") from None
-
-    @property
-    def hop_length(self):
-        return math.prod(self.upsample_rates)
 
     # -- state
-    _canonical = staticmethod(HiFiGANGenerator._canonical)
-
-    def load_state_dict(self, state_dict, strict=True, **kw):
-        """weight_g / weight_v, parametrizations.weight.original0 / 1, or plain `weight` per convolution, as HiFiGANGenerator takes
-        them.  The filter buffers are loaded and USED; one of another shape than [1, 1, 12] raises ValueError."""
-        sd = self._canonical(state_dict)
+    def _check_state(self, sd):
         for k, v in sd.items():
             if k.endswith(".filter") and tuple(v.shape) != (1, 1, FILTER_TAPS):
                 raise ValueError(f"BigVGANGenerator: the filter buffer {k} has shape {tuple(v.shape)}; only [1, 1, {FILTER_TAPS}] is built")
-        for name, m in self.named_modules():
-            if isinstance(m, _WNConv):
-                if f"{name}.weight" in sd:
-                    m.plain_(True)
-                elif f"{name}.weight_g" in sd:
-                    m.plain_(False)
-        return super().load_state_dict(sd, strict=strict, **kw)
+
+    @staticmethod
+    def _is_layout(sd):
+        return "conv_pre.bias" in sd and any(k.startswith("conv_post.") for k in sd) and any(k.startswith("activation_post.") for k in sd)
 
     @classmethod
     def from_state_dict(cls, sd, config=None, **kw):
@@ -231,44 +189,16 @@ class BigVGANGenerator(PackedWeights, nn.Module):
         snake_logscale=False.  **kw: constructor keywords no file tells (input_log)."""
         if config is None:
             raise ValueError(_CONFIG_REQUIRED)
-        sd, config = cls._canonical(sd), _read_config(config)
-        err = lambda what: ValueError(f"BigVGANGenerator.from_state_dict: {what}")
+        sd, config = cls._canonical(sd), read_config(config)
         for key in ("resblock_dilation_sizes", "activation"):
             if key not in config:
-                raise err(f"config[{key!r}] is missing")
-        shape = lambda name: tuple(sd[f"{name}.weight_v" if f"{name}.weight_v" in sd else f"{name}.weight"].shape)
-        count = lambda prefix: 1 + max((int(k[len(prefix):].split(".")[0]) for k in sd if k.startswith(prefix)), default=-1)
-        stages, blocks = count("ups."), count("resblocks.")
-        if "conv_pre.bias" not in sd or not any(k.startswith("conv_post.") for k in sd) or not stages or not blocks or blocks % stages \
-                or not any(k.startswith("activation_post.") for k in sd):
-            raise RuntimeError("BigVGANGenerator.from_state_dict: not a BigVGAN generator layout (conv_pre, ups, resblocks, activation_post, conv_post)")
-        c0, n_mels, _ = shape("conv_pre")
-        uks = tuple(shape(f"ups.{i}.0")[2] for i in range(stages))
-        resblock = "1" if any(k.startswith("resblocks.0.convs1.") for k in sd) else "2"
-        convs = "convs1" if resblock == "1" else "convs"
-        nk = blocks // stages
-        rks = tuple(shape(f"resblocks.{j}.{convs}.0")[2] for j in range(nk))
-        depth = tuple(count(f"resblocks.{j}.{convs}.") for j in range(nk))
-        found = dict(resblock=resblock, num_mels=n_mels, upsample_initial_channel=c0, upsample_kernel_sizes=uks, resblock_kernel_sizes=rks,
-                     upsample_rates=tuple(k // 2 for k in uks),
-                     activation="snakebeta" if "activation_post.act.beta" in sd else "snake",
-                     use_bias_at_final="conv_post.bias" in sd)
-        given = dict(config)
-        given.setdefault("use_bias_at_final", True)
-        for key, val in found.items():
-            if key in given:
-                g = given[key] if isinstance(val, (int, str, bool)) else tuple(given[key])
-                if (str(g) if key == "resblock" else g) != val:
-                    raise err(f"config[{key!r}] = {given[key]} but the state dict has {val}")
-        dils = tuple(tuple(ds) for ds in config["resblock_dilation_sizes"])
-        if tuple(len(ds) for ds in dils) != depth:
-            raise err(f"the state dict has {depth} convolutions per residual block, the dilations {dils} say otherwise")
-        self = cls(n_mels=n_mels, upsample_initial_channel=c0, upsample_rates=found["upsample_rates"], upsample_kernel_sizes=uks,
-                   resblock=resblock, resblock_kernel_sizes=rks, resblock_dilation_sizes=dils, activation=found["activation"],
-                   snake_logscale=bool(config.get("snake_logscale", False)), use_tanh_at_final=bool(config.get("use_tanh_at_final", True)),
-                   use_bias_at_final=found["use_bias_at_final"], **kw)
-        self.load_state_dict(sd)
-        return self.eval()
+                raise ValueError(f"BigVGANGenerator.from_state_dict: config[{key!r}] is missing")
+        found, depth = cls._read_layout(sd)
+        found.update(activation="snakebeta" if "activation_post.act.beta" in sd else "snake", use_bias_at_final="conv_post.bias" in sd)
+        cls._check_config(found, dict({"use_bias_at_final": True}, **config))
+        return cls._from_layout(sd, found, depth, tuple(tuple(ds) for ds in config["resblock_dilation_sizes"]), activation=found["activation"],
+                                snake_logscale=bool(config.get("snake_logscale", False)),
+                                use_tanh_at_final=bool(config.get("use_tanh_at_final", True)), use_bias_at_final=found["use_bias_at_final"], **kw)
 
     @classmethod
     def from_checkpoint(cls, path, config=None, **kw):
@@ -276,22 +206,11 @@ class BigVGANGenerator(PackedWeights, nn.Module):
         config.json (a LOCAL path or a dict), REQUIRED -- see from_state_dict."""
         if config is None:  # before the file is read
             raise ValueError(_CONFIG_REQUIRED)
-        return cls.from_state_dict(torch.load(path, map_location="cpu", weights_only=True), config=config, **kw)
+        return super().from_checkpoint(path, config=config, **kw)
 
     # -- operand copies
     def _weights_key(self):
         return tensors_key(list(self.parameters()) + list(self.buffers()))  # the filters are buffers
-
-    def folded_weights(self):
-        """the folded fp32 weights by module path, e.g. 'ups.0.0' -> [Ci, Co, k]: what the state-dict layouts agree on"""
-        return {name: m.folded() for name, m in self.named_modules() if isinstance(m, _WNConv)}
-
-    def packed_ops(self):
-        return self._cached(self._build_ops)
-
-    @staticmethod
-    def _conv_op(m):
-        return HiFiGANGenerator._conv_op(m, -(-m.cin // 8) * 8)  # the input channels zero-padded to a multiple of 8 (conv_pre)
 
     def _act_op(self, a):
         """alpha and 1 / (beta + 1e-9) as the kernels take them: fp32, single torch operations"""
@@ -303,79 +222,41 @@ class BigVGANGenerator(PackedWeights, nn.Module):
         return dict(alpha=alpha.contiguous(), invb=(1.0 / (beta + 1e-9)).contiguous(), fu=f(a.upsample.filter).reshape(-1).contiguous(),
                     fd=f(a.downsample.lowpass.filter).reshape(-1).contiguous())
 
-    def _build_ops(self):
-        f = lambda t: t.detach().float().contiguous()
-        ops = dict(pre=self._conv_op(self.conv_pre), stages=[])
-        for i, (up,) in enumerate(self.ups):
-            blocks = []
-            for rb in self.resblocks[i * self.num_kernels:(i + 1) * self.num_kernels]:
-                acts = [self._act_op(a) for a in rb.activations]
-                if self.resblock == "1":
-                    blocks.append([(acts[2 * m], self._conv_op(c1), acts[2 * m + 1], self._conv_op(c2))
-                                   for m, (c1, c2) in enumerate(zip(rb.convs1, rb.convs2))])
-                else:
-                    blocks.append([(acts[m], self._conv_op(c), None, None) for m, c in enumerate(rb.convs)])
-            ops["stages"].append(dict(w=pack_convtr_weight(up.folded(), up.stride).half().contiguous(), b=f(up.bias), C=up.cin, r=up.stride,
-                                      blocks=blocks))
-        post = self.conv_post
-        ops["post"] = dict(w=f(post.folded()[0].t()), b=None if post.bias is None else f(post.bias), C=post.cin, k=post.k,
-                           act=self._act_op(self.activation_post))  # fp32 [k, C]
-        return ops
+    def _block_ops(self, rb):
+        acts = [self._act_op(a) for a in rb.activations]
+        if self.resblock == "1":
+            return [(acts[2 * m], self._conv_op(c1), acts[2 * m + 1], self._conv_op(c2)) for m, (c1, c2) in enumerate(zip(rb.convs1, rb.convs2))]
+        return [(acts[m], self._conv_op(c), None, None) for m, c in enumerate(rb.convs)]
 
-    def forward(self, mel):
-        if mel.ndim != 3 or mel.shape[1] != self.n_mels or not mel.is_floating_point():
-            raise ValueError(f"BigVGANGenerator takes float mels (batch, {self.n_mels}, frames), got {tuple(mel.shape)} {mel.dtype}")
-        if mel.shape[0] < 1 or mel.shape[2] < 1:
-            raise ValueError("BigVGANGenerator: empty mel (at least one frame)")
-        dev = mel.device
-        if dev.type != "cuda":
-            raise _lib.VbxError(f"BigVGANGenerator runs only on an MI355X (gfx950) through libvbx_hip.so; the mel is on '{dev}'")
-        if self.conv_pre.bias.device != dev:
-            self.to(dev)
-        with torch.inference_mode():
-            return self._generate(mel)
+    def _build_ops(self):
+        ops = super()._build_ops()
+        ops["post"]["act"] = self._act_op(self.activation_post)
+        return ops
 
     def _act_conv(self, a, op, x, res, B, L, st):
         """conv(A(x)) + bias (+ res): one launch up to fuse_act_max_channels, else the activation on its own first; the same bits"""
-        y = torch.empty(B, L, op["Co"], dtype=torch.float16, device=x.device)
         fuse = self.fuse_act_max_channels
         if fuse is None or (op["C"] <= fuse and B * L * op["C"] <= self.FUSE_ACT_MAX_ELEMENTS):
+            y = torch.empty(B, L, op["Co"], dtype=torch.float16, device=x.device)
             _lib.call("vbx_bigvgan_conv", x, a["alpha"], a["invb"], a["fu"], a["fd"], op["w"], op["b"], res, y, B, L, op["C"], op["Co"], op["k"],
                       op["dil"], st)
             return y
         h = torch.empty_like(x)
         _lib.call("vbx_bigvgan_act", x, None, None, 1, a["alpha"], a["invb"], a["fu"], a["fd"], h, B, L, op["C"], st)
-        _lib.call("vbx_hifigan_conv", h, op["w"], op["b"], res, y, B, L, op["C"], op["Co"], op["k"], op["dil"], 0, 1.0, st)
-        return y
+        return self._conv(op, h, res, B, L, st, 0, 1.0)
 
-    def _generate(self, mel):
-        B, M, L = mel.shape
-        dev, st = mel.device, _lib.current_stream()
-        ops = self.packed_ops()
-        mel32 = mel.detach().to(torch.float32).contiguous()
-        pre = ops["pre"]
-        x = torch.empty(B, L, pre["C"], dtype=torch.float16, device=dev)
-        _lib.call("vbx_hifigan_pack", mel32, x, B, M, L, int(self.input_log), st)
-        y = torch.empty(B, L, pre["Co"], dtype=torch.float16, device=dev)
-        _lib.call("vbx_hifigan_conv", x, pre["w"], pre["b"], None, y, B, L, pre["C"], pre["Co"], pre["k"], pre["dil"], 0, 1.0, st)
-        xs = [y]
-        pad = lambda xs: (xs + [None, None])[:3]
-        for stage in ops["stages"]:
-            C, r = stage["C"], stage["r"]
-            up = torch.empty(B, L * r, C // 2, dtype=torch.float16, device=dev)
-            _lib.call("vbx_bigvgan_convtr", *pad(xs), len(xs), stage["w"], stage["b"], up, B, L, C, r, st)
-            L, C, xs = L * r, C // 2, []
-            for block in stage["blocks"]:
-                h = up
-                for a1, c1, a2, c2 in block:
-                    if c2 is None:  # AMPBlock2
-                        h = self._act_conv(a1, c1, h, h, B, L, st)
-                    else:
-                        h = self._act_conv(a2, c2, self._act_conv(a1, c1, h, None, B, L, st), h, B, L, st)
-                xs.append(h)
-        post = ops["post"]
+    def _upsample(self, xs, n, stage, up, B, L, st):
+        _lib.call("vbx_bigvgan_convtr", *xs, n, stage["w"], stage["b"], up, B, L, stage["C"], stage["r"], st)
+
+    def _run_block(self, block, h, B, L, C, st):
+        for a1, c1, a2, c2 in block:
+            if c2 is None:  # AMPBlock2
+                h = self._act_conv(a1, c1, h, h, B, L, st)
+            else:
+                h = self._act_conv(a2, c2, self._act_conv(a1, c1, h, None, B, L, st), h, B, L, st)
+        return h
+
+    def _post(self, xs, n, post, wave, B, L, st):
         a = post["act"]
-        wave = torch.empty(B, L, dtype=torch.float32, device=dev)
-        _lib.call("vbx_bigvgan_post", *pad(xs), len(xs), a["alpha"], a["invb"], a["fu"], a["fd"], post["w"], post["b"], wave, B, L, post["C"],
-                  post["k"], 0 if self.use_tanh_at_final else 1, st)
-        return wave
+        _lib.call("vbx_bigvgan_post", *xs, n, a["alpha"], a["invb"], a["fu"], a["fd"], post["w"], post["b"], wave, B, L, post["C"], post["k"],
+                  0 if self.use_tanh_at_final else 1, st)

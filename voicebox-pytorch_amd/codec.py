@@ -30,6 +30,7 @@ from torch import nn
 
 from . import _lib
 from ._packing import PackedWeights, read_checkpoint, tensors_key
+from ._wnconv import read_config
 from .masks import take_draw
 
 
@@ -564,9 +565,7 @@ class HiFiGANMelCodec(AudioEncoderDecoder):
         """config: a LOCAL config.json path or a dict with HiFi-GAN's / BigVGAN's keys num_mels, n_fft, hop_size, win_size,
         sampling_rate, fmin, fmax (null: sampling_rate / 2); every other key (fmax_for_loss, the generator's) is ignored.
         **kw: mean, std."""
-        from .hifigan import _read_config
-
-        config = _read_config(config)
+        config = read_config(config)
         keys = ("num_mels", "n_fft", "hop_size", "win_size", "sampling_rate", "fmin", "fmax")
         missing = [k for k in keys if k not in config]
         if missing:
@@ -578,9 +577,9 @@ class HiFiGANMelCodec(AudioEncoderDecoder):
         """A LOCAL generator file and its config.json (path or dict): a BigVGANGenerator when the config has an `activation` key,
         else a HiFiGANGenerator, built by their from_checkpoint, paired with the codec of the same config."""
         from .bigvgan import BigVGANGenerator
-        from .hifigan import HiFiGANGenerator, _read_config
+        from .hifigan import HiFiGANGenerator
 
-        config = _read_config(config)
+        config = read_config(config)
         if not isinstance(config, dict):
             raise TypeError("HiFiGANMelCodec.from_checkpoint needs the generator's config (a local config.json path or a dict)")
         gen = (BigVGANGenerator if "activation" in config else HiFiGANGenerator).from_checkpoint(generator_path, config=config)

@@ -38,36 +38,15 @@ from torch import nn
 
 from . import _lib
 from ._packing import PackedWeights, read_checkpoint
-
-_PARAM = "parametrizations.weight.original"
-
-
-class _Conv(nn.Module):
-    """the innermost `conv` of SConv1d -> NormConv1d -> nn.Conv1d: weight_g / weight_v / bias under weight norm, weight / bias
-    without; initialised as nn.Conv1d initialises itself"""
-
-    def __init__(self, cin, cout, k, norm):
-        super().__init__()
-        ref = nn.Conv1d(cin, cout, k)
-        if norm == "weight_norm":
-            self.weight_g = nn.Parameter(ref.weight.detach().flatten(1).norm(dim=1).reshape(cout, 1, 1))
-            self.weight_v = nn.Parameter(ref.weight.detach().clone())
-        else:
-            self.weight = nn.Parameter(ref.weight.detach().clone())
-        self.bias = nn.Parameter(ref.bias.detach().clone())
-
-    def folded(self):
-        """fp32 [Co, Ci, k]: w = g * v / |v|, the norm over (Ci, k) per output channel"""
-        if hasattr(self, "weight"):
-            return self.weight.detach().float()
-        v = self.weight_v.detach().float()
-        return self.weight_g.detach().float() * v / v.flatten(1).norm(dim=1).reshape(-1, 1, 1)
+from ._wnconv import WNConv, weight_norm_key
 
 
 class _NormConv(nn.Module):
-    def __init__(self, *a):
+    """NormConv1d: its `conv` is the nn.Conv1d, under weight norm or (norm="none") plain"""
+
+    def __init__(self, cin, cout, k, norm):
         super().__init__()
-        self.conv = _Conv(*a)
+        self.conv = WNConv(cin, cout, k, weight_norm=norm == "weight_norm")
 
 
 class _SConv(nn.Module):
@@ -105,32 +84,13 @@ class _SLSTM(nn.Module):
         self.lstm = _LSTMParams(dim, layers)
 
 
-class _ConvTr(nn.Module):
-    """the innermost `convtr` of SConvTranspose1d -> NormConvTranspose1d -> nn.ConvTranspose1d: weight [Cin, Cout, k]; torch's weight
-    norm at its default dim=0 gives it weight_g [Cin, 1, 1], the norm over (Cout, k) per INPUT channel"""
+class _NormConvTr(nn.Module):
+    """NormConvTranspose1d: its `convtr` is the nn.ConvTranspose1d, weight [Cin, Cout, k]; torch's weight norm at its default dim=0
+    gives it weight_g [Cin, 1, 1], the norm over (Cout, k) per INPUT channel"""
 
     def __init__(self, cin, cout, k, stride, norm):
         super().__init__()
-        ref = nn.ConvTranspose1d(cin, cout, k, stride=stride)
-        if norm == "weight_norm":
-            self.weight_g = nn.Parameter(ref.weight.detach().flatten(1).norm(dim=1).reshape(cin, 1, 1))
-            self.weight_v = nn.Parameter(ref.weight.detach().clone())
-        else:
-            self.weight = nn.Parameter(ref.weight.detach().clone())
-        self.bias = nn.Parameter(ref.bias.detach().clone())
-
-    def folded(self):
-        """fp32 [Ci, Co, k]: w = g * v / |v|, the norm over (Co, k) per input channel"""
-        if hasattr(self, "weight"):
-            return self.weight.detach().float()
-        v = self.weight_v.detach().float()
-        return self.weight_g.detach().float() * v / v.flatten(1).norm(dim=1).reshape(-1, 1, 1)
-
-
-class _NormConvTr(nn.Module):
-    def __init__(self, *a):
-        super().__init__()
-        self.convtr = _ConvTr(*a)
+        self.convtr = WNConv(cin, cout, k, stride=stride, transposed=True, weight_norm=norm == "weight_norm")
 
 
 class _SConvTr(nn.Module):
@@ -223,11 +183,7 @@ class _SEANet(PackedWeights, nn.Module):
         for k, v in state_dict.items():
             if k.startswith(("encoder.", "decoder.", "quantizer.")):
                 continue
-            if k.endswith(_PARAM + "0"):
-                k = k[:-len(_PARAM) - 1] + "weight_g"
-            elif k.endswith(_PARAM + "1"):
-                k = k[:-len(_PARAM) - 1] + "weight_v"
-            out[k] = v
+            out[weight_norm_key(k)] = v
         return out
 
     def load_state_dict(self, state_dict, strict=True, **kw):
