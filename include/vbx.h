@@ -1279,6 +1279,69 @@ size_t vbx_model_precise_wpack_bytes(const vbx_model* m);
 size_t vbx_model_precise_scratch_bytes(const vbx_model* m);
 int vbx_model_pack_weights_precise(const vbx_model* m, void* stream);
 
+/* ------------------------------------------------------------------ HuBERT + k-means (csrc/hubert.hip, voicebox-pytorch_amd/hubert.py)
+ * HuBERT base (feat_extract_norm "group", post-LN encoder, no convolution bias) up to one encoder layer, then the nearest row of a
+ * k-means codebook: what audiolm_pytorch's HubertWithKmeans computes, inference only.  The encoder layers run on vbx_gemm
+ * (NT, f16 = 1, VBX_EPI_F32 / VBX_EPI_GELU) and vbx_attn_fwd (mask NULL) as they are; the entry points below are what sits between.
+ * WHERE A TENSOR IS ROUNDED (tests/hubert_ref.py, emulate=True, rounds exactly here and nowhere else):
+ *  - the wave, the first convolution's weights and its fmaf chain are fp32; GroupNorm's statistics are taken over those unrounded
+ *    values; (v - mean) * rstd * gamma + beta and erf-GELU are fp32; the result is rounded ONCE to fp16 [B, L0, C];
+ *  - every later convolution: fp16 input as stored, weights rounded to fp16, fp32 sum, erf-GELU in fp32, rounded once to fp16;
+ *  - feature_projection.layer_norm reads the fp16 rows, works in fp32 and rounds its result to fp16 (the projection's operand); the
+ *    projection's weight is rounded to fp16, its sum and bias are fp32 and the result x stays fp32;
+ *  - the positional convolution rounds x to fp16 as it stages it and its weight (weight norm folded in fp32) to fp16; sum, bias,
+ *    erf-GELU and the + x (the UNROUNDED fp32 x) are fp32 and the result stays fp32;
+ *  - every encoder LayerNorm reads fp32 and writes fp32 (the residual stream, never rounded) plus an fp16 copy (the operand of the
+ *    next product);
+ *  - per layer: the q | k | v, out_proj, intermediate_dense and output_dense weights are rounded to fp16; q | k | v sum + bias is
+ *    fp32, then q * vbx_attn_q_prescale(dim_head ** -0.5), k and v are each rounded once to fp16; the attention output is fp16
+ *    (vbx_attn_fwd's own contract: its probabilities are fp16 operands of P.V inside the kernel, which the emulation does not
+ *    mirror); out_proj / output_dense: fp32 sum + bias + fp32 residual, not rounded; gelu(intermediate_dense) is rounded to fp16
+ *    (VBX_EPI_GELU: erf by Abramowitz-Stegun 7.1.26, |error| <= 6e-7);
+ *  - vbx_kmeans_assign is fp32 throughout.
+ * Every entry point is a plain launch (or two), without atomics: reruns give the same bits, and a batch row's result is bit-equal to
+ * that row computed alone. */
+/* The first convolution (1 -> C, kernel k0 <= 16, stride s0 <= 16, no padding, no bias: L0 = (T - k0) / s0 + 1 positions) and the
+ * statistics of GroupNorm(C, C): per (row, channel) the mean and biased variance over TIME of the fp32 value
+ * v[t][c] = fmaf chain over tap = 0 .. k0 - 1 of w[c][tap] * wave[t * s0 + tap], started at 0.  One record (K, S1, S2) per (row, chunk
+ * of 256 positions, channel): K the chunk's first value, S1 = sum(v - K), S2 = sum((v - K)^2) in fp32 -- shifted, so a large mean
+ * costs nothing; a second launch combines the records of a (row, channel) in ascending order in fp64 (Chan et al.'s pairwise update)
+ * into stats[b][c] = (mean, 1 / sqrt(var + eps)).  wave fp32 [B, T]; w fp32 [C, k0]; records fp32 [B, vbx_hubert_conv0_chunks(L0), C, 3]
+ * (scratch); stats fp32 [B, C, 2].  C a multiple of 8 up to 512. */
+int vbx_hubert_conv0_chunks(int L0);
+int vbx_hubert_conv0_stats(const float* wave, const float* w, float* records, float* stats, int B, long T, int C, int k0, int s0,
+                           float eps, void* stream);
+/* ... and the pass that writes y fp16 [B, L0, C] = gelu((v - mean) * rstd * gamma + beta): v is computed again by the same chain (the
+ * same bits as in the statistics pass); the fp32 pre-norm tensor is never stored. */
+int vbx_hubert_conv0_apply(const float* wave, const float* w, const float* stats, const float* gamma, const float* beta, void* y_f16,
+                           int B, long T, int C, int k0, int s0, void* stream);
+/* Conv1d(C, C, k, stride 2, no padding, no bias) + erf-GELU on the implicit-GEMM tile core (csrc/seanet_tile.hpp): x fp16 [B, L, C],
+ * w fp16 [C, k * C] (row = output channel, column tap * C + c), y fp16 [B, (L - k) / 2 + 1, C].  k 2 or 3, C a multiple of 16 up to
+ * 512, L >= k.  vbx_hubert_conv_tile: the output positions a workgroup owns before a short row shrinks it (tests stand on both sides). */
+int vbx_hubert_conv_tile(int C, int k);
+int vbx_hubert_conv(const void* x_f16, const void* w_f16, void* y_f16, int B, int L, int C, int k, void* stream);
+/* LayerNorm over the last axis, one wave per row, two passes (mean, then squared deviations), fp32: x fp32 [M, D] -> y_f32 and / or
+ * y_f16 (either may be NULL; the fp16 copy saturates at +-65504).  vbx_hubert_layernorm16 reads fp16 rows and writes fp16. */
+int vbx_hubert_layernorm(const float* x, const float* gamma, const float* beta, float* y_f32, void* y_f16, long M, int D, float eps,
+                         void* stream);
+int vbx_hubert_layernorm16(const void* x_f16, const float* gamma, const float* beta, void* y_f16, long M, int D, float eps, void* stream);
+/* HubertPositionalConvEmbedding + the residual: y = gelu(conv(x)[:N] + bias) + x with conv = Conv1d(D, D, k, padding k / 2, groups),
+ * k even, so that of the N + 1 positions the convolution has the last is dropped -- it is never computed.  One product per (tile of
+ * positions, group) with K = k * D / groups; the zero padding is resolved while the span is staged from x fp32 [B, N, D] (rounded to
+ * fp16 there).  w fp16 [D, k * D / groups]: row = output channel, column tap * (D / groups) + input channel within the group, weight
+ * norm folded by the caller.  bias fp32 [D]; y fp32 [B, N, D], not x.  D / groups a multiple of 8; vbx_hubert_posconv_tile:
+ * positions per workgroup, or VBX_EINVAL where 16 positions do not fit the LDS. */
+int vbx_hubert_posconv_tile(int channels_per_group, int k);
+int vbx_hubert_posconv(const float* x, const void* w_f16, const float* bias, float* y, int B, int N, int D, int groups, int k, void* stream);
+/* qkv fp32 [B * N, 3 * H * 64] (columns [q | k | v], bias already added) -> q16 = fp16(q * q_prescale), k16, v16 fp16 [B, H, N, 64]:
+ * vbx_attn_fwd's operands (q_prescale = vbx_attn_q_prescale(scale), its contract).  Each element rounded once, saturating. */
+int vbx_hubert_split_heads(const float* qkv, void* q16, void* k16, void* v16, int B, int N, int H, float q_prescale, void* stream);
+/* ids[r] = argmin_k |h[r] - centers[k]|^2, fp32 throughout: d = sum_i (h_i - c_i)^2 as differences (no |h|^2 - 2 h.c + |c|^2
+ * cancellation), summed in a fixed order per (row, code).  CONTRACT: d(ids[r]) - min_k d(k), both evaluated exactly, is at most
+ * (D + 2) * 2^-23 * (|h[r]| + max_k |c_k|)^2, and among codes whose computed distances are equal the lowest index wins (duplicate
+ * rows of the codebook: the first).  h fp32 [M, D], centers fp32 [K, D], ids int64 [M].  D a multiple of 8 up to 2048, K 1 .. 4096. */
+int vbx_kmeans_assign(const float* h, const float* centers, long long* ids, long M, int D, int K, void* stream);
+
 /* ------------------------------------------------------------------ in-situ stage timing (measurement only)
  * While enabled, vbx_model_forward / vbx_model_backward_* bracket each MFMA stage of a layer (to_qkv, attention forward, to_out,
  * ff_in, ff_out, the four dgrads, attention backward, the weight-gradient launch) with a pair of HIP events recorded on the

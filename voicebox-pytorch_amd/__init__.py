@@ -15,7 +15,9 @@ aligner_attention (the alignment network itself, forward and backward on the dev
 HiFiGANGenerator (HiFi-GAN's generator on the device: mels into waves, a `vocoder=` of LogMelCodec; weights are the user's, from a
 local checkpoint), BigVGANGenerator (BigVGAN's generator on the device, its anti-aliased snake activations in HIP: the same call
 shape; a local checkpoint and its config.json), HiFiGANMelCodec / mel_spectrogram (the mel front end those two generators were
-trained on -- Slaney filters, magnitude, ln, center=False -- in one kernel: the codec published HiFi-GAN / BigVGAN weights want).
+trained on -- Slaney filters, magnitude, ln, center=False -- in one kernel: the codec published HiFi-GAN / BigVGAN weights want),
+HubertWithKmeans (HuBERT base up to one encoder layer plus a k-means codebook on the device: waves into semantic token ids, the
+`wav2vec=` of ConditionalFlowMatcherWrapper; weights and centres are the user's, from local files).
 """
 from . import _lib  # noqa: F401
 
@@ -31,6 +33,7 @@ try:  # model classes need torch; keep `_lib` importable on its own
     from .seanet import CausalSEANetDecoder, CausalSEANetEncoder, SEANetDecoder, SEANetEncoder  # noqa: F401
     from .hifigan import HiFiGANGenerator  # noqa: F401
     from .bigvgan import BigVGANGenerator  # noqa: F401
+    from .hubert import HubertWithKmeans  # noqa: F401
     from .align import maximum_path, forward_sum_loss, ForwardSumLoss, Aligner, aligner_attention  # noqa: F401
     from .engine import precise_mode, set_precise, precise_enabled  # noqa: F401
     from .dp import ema_decay_at  # noqa: F401  (the decay schedule of dp.TrainStep(ema_decay=))
@@ -39,7 +42,7 @@ try:  # model classes need torch; keep `_lib` importable on its own
     __all__ += ["VoiceBox", "ConditionalFlowMatcherWrapper", "Transformer", "Attend", "VoiceBoxTrainer", "DurationPredictor", "mask_from_frac_lengths",
                 "mask_from_start_end_indices", "prob_mask_like", "reduce_masks_with_and", "precise_mode", "set_precise", "precise_enabled",
                 "AudioEncoderDecoder", "LogMelCodec", "griffin_lim", "resample", "Resample", "VocosDecoder", "VocosEncodecDecoder", "ResidualVQ", "EncodecVocoCodec", "SEANetEncoder", "SEANetDecoder",
-                "CausalSEANetEncoder", "CausalSEANetDecoder", "HiFiGANGenerator", "BigVGANGenerator", "HiFiGANMelCodec", "mel_spectrogram",
+                "CausalSEANetEncoder", "CausalSEANetDecoder", "HiFiGANGenerator", "BigVGANGenerator", "HubertWithKmeans", "HiFiGANMelCodec", "mel_spectrogram",
                 "maximum_path", "forward_sum_loss", "ForwardSumLoss", "Aligner", "aligner_attention", "lora", "ema_decay_at"]
 except ModuleNotFoundError as _e:  # pragma: no cover - only while the package is being bootstrapped
     if "masks" not in str(_e) and "model" not in str(_e):

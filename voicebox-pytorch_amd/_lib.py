@@ -111,6 +111,17 @@ _PROTOS = {
     "vbx_bigvgan_conv": [P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, P],
     "vbx_bigvgan_convtr": [P, P, P, I, P, P, P, I, I, I, I, P],
     "vbx_bigvgan_post": [P, P, P, I, P, P, P, P, P, P, P, I, I, I, I, I, P],
+    "vbx_hubert_conv0_chunks": [I],
+    "vbx_hubert_conv0_stats": [P, P, P, P, I, L, I, I, I, F, P],
+    "vbx_hubert_conv0_apply": [P, P, P, P, P, P, I, L, I, I, I, P],
+    "vbx_hubert_conv_tile": [I, I],
+    "vbx_hubert_conv": [P, P, P, I, I, I, I, P],
+    "vbx_hubert_layernorm": [P, P, P, P, P, L, I, F, P],
+    "vbx_hubert_layernorm16": [P, P, P, P, L, I, F, P],
+    "vbx_hubert_posconv_tile": [I, I],
+    "vbx_hubert_posconv": [P, P, P, P, I, I, I, I, I, P],
+    "vbx_hubert_split_heads": [P, P, P, P, I, I, I, F, P],
+    "vbx_kmeans_assign": [P, P, P, L, I, I, P],
     "vbx_maximum_path": [P, P, P, P, P, P, I, I, I, P],
     "vbx_forward_sum_fwd": [P, P, P, F, P, P, P, P, I, I, I, P],
     "vbx_forward_sum_bwd": [P, P, P, F, P, P, P, P, P, I, I, I, P],

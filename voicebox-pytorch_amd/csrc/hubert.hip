@@ -1,0 +1,465 @@
+// HubertWithKmeans (voicebox-pytorch_amd/hubert.py): HuBERT base (Hsu et al. 2021, "HuBERT: self-supervised speech representation
+// learning by masked prediction of hidden units") up to one encoder layer, then a k-means codebook: waves into semantic token ids on
+// the device, inference only.  The launch sequence of one call at the base widths:
+//
+//   vbx_hubert_conv0_stats   wave fp32 [B, T] -> one (shift, sum, sum of squares) record per (row, chunk of 256 positions, channel) of
+//                            the 1 -> C first convolution, then mean / rstd per (row, channel): the records combined in fp64, in order
+//   vbx_hubert_conv0_apply   the same 10-tap fmaf chain again, GroupNorm(C, C) (over time), erf-GELU -> fp16 [B, L0, C]
+//   vbx_hubert_conv  x 6     k 2 / 3, stride 2, no padding, no bias, erf-GELU: the implicit-GEMM tile core of seanet_tile.hpp
+//   vbx_hubert_layernorm16   feature_projection.layer_norm over the fp16 rows -> fp16
+//   vbx_gemm                 NT, VBX_EPI_F32: the projection C -> D with its bias -> x fp32 [B * N, D]
+//   vbx_hubert_posconv       the grouped positional convolution (one product per group, K = k * D / groups, zero padding resolved as
+//                            the span is staged, the dropped last sample never computed), bias, erf-GELU, + x -> fp32
+//   vbx_hubert_layernorm     encoder.layer_norm -> fp32 rows and their fp16 copy (the next product's operand)
+//   per layer 1 .. output_layer:
+//     vbx_gemm               NT, VBX_EPI_F32: [q | k | v] = x16 . [Wq | Wk | Wv]^T + bias -> fp32 [B * N, 3D]
+//     vbx_hubert_split_heads q16 (times vbx_attn_q_prescale(dim_head ** -0.5)), k16, v16 fp16 [B, H, N, 64]
+//     vbx_attn_fwd           no mask
+//     vbx_gemm               NT, VBX_EPI_F32: out_proj with bias and the residual;  vbx_hubert_layernorm
+//     vbx_gemm               NT, VBX_EPI_GELU: intermediate_dense;  vbx_gemm NT, VBX_EPI_F32: output_dense with bias and the residual
+//     vbx_hubert_layernorm
+//   vbx_kmeans_assign        the Euclidean argmin over the codebook, fp32 throughout -> int64 [B, N]
+//
+// Precision contract (include/vbx.h): fp16 channel-last activations rounded once where they are stored, fp16 weights, every product's
+// sum fp32 on v_mfma_f32_16x16x32_f16 in ascending k, norms / GELU (libm's erff) / statistics fp32.  Plain launches, no atomics, no
+// workgroup waits for another: the same bits on every run, and a batch row's result does not depend on its neighbours.
+#include "seanet_tile.hpp"  // sn_tile_product, sn_pick_tile, sn_blocks_per_item, sn_launch
+
+namespace {
+
+constexpr int HB_CHUNK = 256;                          // positions per statistics record
+constexpr int HB_MAX_K0 = 16, HB_MAX_S0 = 16, HB_MAX_C = 512;  // the first convolution's taps and stride, the extractor's channels
+constexpr int HB_KM_ROWS = 4, HB_KM_MAX_D = 2048, HB_KM_MAX_K = 4096;
+
+// ---------------------------------------------------------------------------------------------------- conv0 + GroupNorm
+// The value both passes compute for (position t, channel c): acc = 0; acc = fmaf(w[c][tap], x[t * s0 + tap], acc) for tap = 0 .. k0 - 1.
+// Workgroup (chunk, row): thread c walks the chunk's positions for channels c and c + 256.  A record is (K, S1, S2): K the chunk's first
+// value, S1 = sum(v - K), S2 = sum((v - K)^2) -- shifted sums: a row with a large mean loses nothing to cancellation.
+__global__ __launch_bounds__(256) void hubert_conv0_stats_kernel(const float* __restrict__ x, const float* __restrict__ w, float* __restrict__ rec,
+                                                                 int T, int L0, int C, int k0, int s0, int chunks) {
+  __shared__ float sw[HB_MAX_K0 * HB_MAX_C];                        // [tap][C]
+  __shared__ float sx[(HB_CHUNK - 1) * HB_MAX_S0 + HB_MAX_K0];
+  const int tid = threadIdx.x, chunk = blockIdx.x, b = blockIdx.y;
+  const int t0 = chunk * HB_CHUNK;
+  const int n = min(HB_CHUNK, L0 - t0);
+  const int span = (n - 1) * s0 + k0;
+  const float* xb = x + (long)b * T + (long)t0 * s0;  // the last tap read is (L0 - 1) * s0 + k0 - 1 <= T - 1
+  for (int e = tid; e < span; e += 256) sx[e] = xb[e];
+  for (int e = tid; e < k0 * C; e += 256) {
+    const int tap = e / C, c = e - tap * C;
+    sw[e] = w[c * k0 + tap];
+  }
+  __syncthreads();
+  for (int c = tid; c < C; c += 256) {
+    float K = 0.f, S1 = 0.f, S2 = 0.f;
+    for (int t = 0; t < n; t++) {
+      float acc = 0.f;
+      for (int tap = 0; tap < k0; tap++) acc = fmaf(sw[tap * C + c], sx[t * s0 + tap], acc);
+      if (t == 0) K = acc;
+      const float d = acc - K;
+      S1 += d;
+      S2 = fmaf(d, d, S2);
+    }
+    float* r = rec + (((long)b * chunks + chunk) * C + c) * 3;
+    r[0] = K, r[1] = S1, r[2] = S2;
+  }
+}
+
+// one thread per (row, channel): the chunk records in ascending order, in fp64 -> (mean, 1 / sqrt(biased variance + eps))
+__global__ __launch_bounds__(256) void hubert_conv0_finalize_kernel(const float* __restrict__ rec, float* __restrict__ stats, int BC, int L0, int C,
+                                                                    int chunks, float eps) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= BC) return;
+  const int b = i / C, c = i - b * C;
+  const float* r = rec + ((long)b * chunks * C + c) * 3;
+  double sum = 0.0;
+  for (int ch = 0; ch < chunks; ch++) {
+    const int n = min(HB_CHUNK, L0 - ch * HB_CHUNK);
+    const float* q = r + (long)ch * C * 3;
+    sum += (double)n * (double)q[0] + (double)q[1];
+  }
+  const double mean = sum / (double)L0;
+  double m2 = 0.0;
+  for (int ch = 0; ch < chunks; ch++) {
+    const int n = min(HB_CHUNK, L0 - ch * HB_CHUNK);
+    const float* q = r + (long)ch * C * 3;
+    const double s1 = (double)q[1], mc = (double)q[0] + s1 / (double)n, dm = mc - mean;
+    m2 += ((double)q[2] - s1 * s1 / (double)n) + (double)n * dm * dm;  // Chan et al.: M2 = sum M2_i + sum n_i (mean_i - mean)^2
+  }
+  const double var = m2 > 0.0 ? m2 / (double)L0 : 0.0;
+  stats[2 * (long)i] = (float)mean;
+  stats[2 * (long)i + 1] = (float)(1.0 / sqrt(var + (double)eps));
+}
+
+// one thread per (position, eight channels): the fmaf chain again (the pre-norm tensor is never stored), normalise, affine, GELU, fp16
+__global__ __launch_bounds__(256) void hubert_conv0_apply_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ stats,
+                                                                 const float* __restrict__ gamma, const float* __restrict__ beta, u16* __restrict__ y,
+                                                                 int T, int L0, int C, int k0, int s0) {
+  __shared__ float sw[HB_MAX_K0 * HB_MAX_C];
+  const int tid = threadIdx.x, b = blockIdx.y;
+  for (int e = tid; e < k0 * C; e += 256) {
+    const int tap = e / C, c = e - tap * C;
+    sw[e] = w[c * k0 + tap];
+  }
+  __syncthreads();
+  const int groups = C >> 3;
+  const long e = (long)blockIdx.x * 256 + tid;
+  if (e >= (long)L0 * groups) return;
+  const int pos = (int)(e / groups), c0 = (int)(e - (long)pos * groups) * 8;
+  const float* xb = x + (long)b * T + (long)pos * s0;
+  float acc[8];
+#pragma unroll
+  for (int j = 0; j < 8; j++) acc[j] = 0.f;
+  for (int tap = 0; tap < k0; tap++) {
+    const float xv = xb[tap];
+#pragma unroll
+    for (int j = 0; j < 8; j++) acc[j] = fmaf(sw[tap * C + c0 + j], xv, acc[j]);
+  }
+  const float* st = stats + 2 * ((long)b * C + c0);
+#pragma unroll
+  for (int j = 0; j < 8; j++) acc[j] = gelu_erf_libm(fmaf((acc[j] - st[2 * j]) * st[2 * j + 1], gamma[c0 + j], beta[c0 + j]));
+  *reinterpret_cast<uint4*>(y + ((long)b * L0 + pos) * C + c0) =
+      make_uint4(pack_f16x2(acc[0], acc[1]), pack_f16x2(acc[2], acc[3]), pack_f16x2(acc[4], acc[5]), pack_f16x2(acc[6], acc[7]));
+}
+
+// ---------------------------------------------------------------------------------------------------- the strided convolutions
+struct HbConv {
+  const u16* x;  // [B, L, C]
+  const u16* w;  // [C, k * C], column tap * C + c
+  u16* y;        // [B, Lout, C]
+  int L, Lout, C, k, TT;
+};
+
+// A workgroup owns TT consecutive output positions of one batch row and all C channels: it stages positions 2 t0 .. 2 (t0 + TT - 1) + k - 1
+// (zeros past the row: only outputs past Lout read them, and those are not stored) and runs the product on the span in place.
+template <int MG>
+__global__ __launch_bounds__(256) void hubert_conv_kernel(HbConv p) {
+  extern __shared__ __attribute__((aligned(16))) u16 hb_lds[];
+  const int tid = threadIdx.x, b = blockIdx.y, t0 = blockIdx.x * p.TT;
+  const int ld = p.C + SN_PADH, c8 = p.C >> 3;
+  const int span = (p.TT - 1) * 2 + p.k;
+  const u16* xb = p.x + (long)b * p.L * p.C;
+  for (int e = tid; e < span * c8; e += 256) {
+    const int pos = e / c8, c = (e - pos * c8) * 8;
+    const int i = t0 * 2 + pos;
+    *reinterpret_cast<uint4*>(hb_lds + pos * ld + c) = i < p.L ? *reinterpret_cast<const uint4*>(xb + (long)i * p.C + c) : make_uint4(0u, 0u, 0u, 0u);
+  }
+  __syncthreads();
+  auto rows = [&](int kk, const u16*& base, int& ldr) __attribute__((always_inline)) {
+    const int tap = kk / p.C, c = kk - tap * p.C;
+    base = hb_lds + tap * ld + c, ldr = 2 * ld;
+  };
+  auto store = [&](int n) __attribute__((always_inline)) {
+    return [&, n](int m, float v) __attribute__((always_inline)) {
+      const int t = t0 + m;
+      if (t < p.Lout) p.y[((long)b * p.Lout + t) * p.C + n] = f32_to_f16(gelu_erf_libm(v));
+    };
+  };
+  sn_tile_product<MG, true>(p.w, p.C, p.k * p.C, p.TT >> 4, rows, store);  // k 3 at C = 16 (mod 32): K = 48 has a tail
+}
+
+size_t hb_conv_lds(int TT, int C, int k) { return (size_t)((TT - 1) * 2 + k) * (C + SN_PADH) * sizeof(u16); }
+int hb_conv_tile(int C, int k) {
+  return sn_pick_tile([&](int TT) { return hb_conv_lds(TT, C, k); });
+}
+int hb_conv_check(int C, int k) {
+  VBX_REQUIRE(C >= 16 && C % 16 == 0 && C <= HB_MAX_C, "vbx_hubert_conv: channels must be a multiple of 16 up to %d (got %d)", HB_MAX_C, C);
+  VBX_REQUIRE(k == 2 || k == 3, "vbx_hubert_conv: kernel_size must be 2 or 3 (got %d)", k);
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------- LayerNorm
+// one wave per row: mean, then the sum of squared deviations, then the affine; fp32 throughout.  IN16: the row is fp16.
+template <bool IN16>
+__global__ __launch_bounds__(256) void hubert_layernorm_kernel(const void* __restrict__ xv, const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                               float* __restrict__ y32, u16* __restrict__ y16, long M, int D, float eps) {
+  const int lane = threadIdx.x & 63;
+  const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= M) return;
+  const float* x32 = reinterpret_cast<const float*>(xv) + row * D;
+  const u16* x16 = reinterpret_cast<const u16*>(xv) + row * D;
+  auto at = [&](int i) __attribute__((always_inline)) { return IN16 ? f16_to_f32(x16[i]) : x32[i]; };
+  float s = 0.f;
+  for (int i = lane; i < D; i += 64) s += at(i);
+  const float mean = wave_sum(s) / (float)D;
+  float q = 0.f;
+  for (int i = lane; i < D; i += 64) {
+    const float d = at(i) - mean;
+    q = fmaf(d, d, q);
+  }
+  const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)D + eps);
+  for (int i = lane; i < D; i += 64) {
+    const float v = fmaf((at(i) - mean) * rstd, gamma[i], beta[i]);
+    if (y32) y32[row * D + i] = v;
+    if (y16) y16[row * D + i] = f32_to_f16_sat(v);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------- the positional convolution
+struct HbPos {
+  const float* x;     // [B, N, D] fp32: rounded to fp16 as it is staged, and the residual added in the epilogue
+  const u16* w;       // [D, k * Dg], row = output channel, column tap * Dg + ci (weight norm folded)
+  const float* bias;  // [D]
+  float* y;           // [B, N, D] = gelu(conv + bias) + x
+  int N, D, Dg, G, k, TT;
+};
+
+// Workgroup (tile, group, row): out[t][o] = sum_{tap, ci} w[o][tap * Dg + ci] x[t + tap - k / 2][g * Dg + ci] for t0 <= t < t0 + TT, the
+// Dg output channels of group g.  Positions t0 - k / 2 .. t0 + TT - 1 + k / 2 - 1 of the group's channels sit in the LDS, zeros outside
+// [0, N): Conv1d(padding = k / 2) computes N + 1 positions of which the module drops the last -- position N is simply never asked for.
+template <int MG>
+__global__ __launch_bounds__(256) void hubert_posconv_kernel(HbPos p) {
+  extern __shared__ __attribute__((aligned(16))) u16 hb_lds[];
+  const int tid = threadIdx.x, b = blockIdx.y;
+  const int g = blockIdx.x % p.G, t0 = (blockIdx.x / p.G) * p.TT;
+  const int ld = p.Dg + SN_PADH, c8 = p.Dg >> 3;
+  const int span = p.TT - 1 + p.k, pad = p.k >> 1;
+  const float* xb = p.x + (long)b * p.N * p.D + g * p.Dg;
+  for (int e = tid; e < span * c8; e += 256) {
+    const int pos = e / c8, c = (e - pos * c8) * 8;
+    const int i = t0 - pad + pos;
+    uint4 v = make_uint4(0u, 0u, 0u, 0u);
+    if (i >= 0 && i < p.N) {
+      const float4 lo = *reinterpret_cast<const float4*>(xb + (long)i * p.D + c), hi = *reinterpret_cast<const float4*>(xb + (long)i * p.D + c + 4);
+      v = make_uint4(pack_f16x2_sat(lo.x, lo.y), pack_f16x2_sat(lo.z, lo.w), pack_f16x2_sat(hi.x, hi.y), pack_f16x2_sat(hi.z, hi.w));
+    }
+    *reinterpret_cast<uint4*>(hb_lds + pos * ld + c) = v;
+  }
+  __syncthreads();
+  auto rows = [&](int kk, const u16*& base, int& ldr) __attribute__((always_inline)) {
+    const int tap = kk / p.Dg, c = kk - tap * p.Dg;
+    base = hb_lds + tap * ld + c, ldr = ld;
+  };
+  auto store = [&](int n) __attribute__((always_inline)) {
+    return [&, n, bv = p.bias[g * p.Dg + n]](int m, float v) __attribute__((always_inline)) {
+      const int t = t0 + m;
+      if (t >= p.N) return;
+      const long o = ((long)b * p.N + t) * p.D + g * p.Dg + n;
+      p.y[o] = gelu_erf_libm(v + bv) + p.x[o];
+    };
+  };
+  sn_tile_product<MG, true>(p.w + (long)g * p.Dg * p.k * p.Dg, p.Dg, p.k * p.Dg, p.TT >> 4, rows, store);
+}
+
+size_t hb_pos_lds(int TT, int Dg, int k) { return (size_t)(TT - 1 + k) * (Dg + SN_PADH) * sizeof(u16); }
+int hb_pos_tile(int Dg, int k) {
+  return sn_pick_tile([&](int TT) { return hb_pos_lds(TT, Dg, k); });
+}
+int hb_pos_check(int Dg, int k) {
+  VBX_REQUIRE(Dg >= 8 && Dg % 8 == 0, "vbx_hubert_posconv: channels per group must be a multiple of 8 (got %d)", Dg);
+  VBX_REQUIRE(k >= 2 && k % 2 == 0 && k <= 256, "vbx_hubert_posconv: kernel_size must be even, 2 .. 256 (got %d)", k);
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------- head split
+// qkv fp32 [M, 3D] (M = B * N; columns [q | k | v], each H heads of 64) -> fp16 [B, H, N, 64]; one thread per eight elements
+__global__ __launch_bounds__(256) void hubert_split_heads_kernel(const float* __restrict__ qkv, u16* __restrict__ q16, u16* __restrict__ k16,
+                                                                 u16* __restrict__ v16, long M, int N, int H, float q_prescale) {
+  const int D = H * 64, per_row = 3 * D / 8;
+  const long e = (long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= M * per_row) return;
+  const long row = e / per_row;
+  const int col = (int)(e - row * per_row) * 8;
+  const int which = col / D, h = (col - which * D) >> 6, d = col & 63;
+  const long bi = row / N, n = row - bi * N;
+  const float4 lo = *reinterpret_cast<const float4*>(qkv + row * 3 * D + col), hi = *reinterpret_cast<const float4*>(qkv + row * 3 * D + col + 4);
+  const float s = which == 0 ? q_prescale : 1.0f;
+  u16* dst = (which == 0 ? q16 : (which == 1 ? k16 : v16)) + ((bi * H + h) * N + n) * 64 + d;
+  *reinterpret_cast<uint4*>(dst) = make_uint4(pack_f16x2_sat(lo.x * s, lo.y * s), pack_f16x2_sat(lo.z * s, lo.w * s),
+                                              pack_f16x2_sat(hi.x * s, hi.y * s), pack_f16x2_sat(hi.z * s, hi.w * s));
+}
+
+// ---------------------------------------------------------------------------------------------------- k-means
+// A workgroup holds HB_KM_ROWS feature rows in the LDS; wave w walks codes w, w + 4, ...: d = sum_i (h_i - c_i)^2 with lane l summing
+// i = 4 l + 256 j in ascending j, then the xor tree over the lanes -- a fixed order per (row, code), whatever the batch.  The first
+// strictly smaller distance wins inside a wave (ascending codes); across the four waves the smaller distance, then the lower index.
+__global__ __launch_bounds__(256) void hubert_kmeans_kernel(const float* __restrict__ h, const float* __restrict__ cent, long long* __restrict__ ids,
+                                                            long M, int D, int K) {
+  __shared__ __attribute__((aligned(16))) float sh[HB_KM_ROWS * HB_KM_MAX_D];
+  __shared__ float sd[4][HB_KM_ROWS];
+  __shared__ int sk[4][HB_KM_ROWS];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const long r0 = (long)blockIdx.x * HB_KM_ROWS;
+  const int nr = (int)min((long)HB_KM_ROWS, M - r0);
+  for (int e = tid; e < HB_KM_ROWS * D; e += 256) {
+    const int r = e / D;
+    sh[e] = r < nr ? h[(r0 + r) * D + (e - r * D)] : 0.f;
+  }
+  __syncthreads();
+  float best[HB_KM_ROWS];
+  int bk[HB_KM_ROWS];
+#pragma unroll
+  for (int r = 0; r < HB_KM_ROWS; r++) best[r] = INFINITY, bk[r] = K;
+  for (int k = wave; k < K; k += 4) {
+    const float* c = cent + (long)k * D;
+    float acc[HB_KM_ROWS];
+#pragma unroll
+    for (int r = 0; r < HB_KM_ROWS; r++) acc[r] = 0.f;
+    for (int i = lane * 4; i < D; i += 256) {
+      const float4 cv = *reinterpret_cast<const float4*>(c + i);
+#pragma unroll
+      for (int r = 0; r < HB_KM_ROWS; r++) {
+        const float4 hv = *reinterpret_cast<const float4*>(sh + r * D + i);
+        const float d0 = hv.x - cv.x, d1 = hv.y - cv.y, d2 = hv.z - cv.z, d3 = hv.w - cv.w;
+        acc[r] = fmaf(d3, d3, fmaf(d2, d2, fmaf(d1, d1, fmaf(d0, d0, acc[r]))));
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < HB_KM_ROWS; r++) {
+      const float d = wave_sum(acc[r]);
+      if (d < best[r] || bk[r] == K) best[r] = d, bk[r] = k;  // bk == K: nothing taken yet (a NaN distance still yields a valid index)
+    }
+  }
+  if (lane == 0) {
+#pragma unroll
+    for (int r = 0; r < HB_KM_ROWS; r++) sd[wave][r] = best[r], sk[wave][r] = bk[r];
+  }
+  __syncthreads();
+  if (tid < nr) {
+    float d = sd[0][tid];
+    int k = sk[0][tid];
+    for (int w = 1; w < 4; w++) {
+      const float dw = sd[w][tid];
+      const int kw = sk[w][tid];
+      if (kw < K && (k >= K || dw < d || (dw == d && kw < k))) d = dw, k = kw;
+    }
+    ids[r0 + tid] = (long long)k;
+  }
+}
+
+}  // namespace
+
+extern "C" int vbx_hubert_conv0_chunks(int L0) { return L0 >= 1 ? cdiv(L0, HB_CHUNK) : 0; }
+
+static int hb_conv0_check(const char* who, int B, long T, int C, int k0, int s0, long* L0) {
+  VBX_REQUIRE(B >= 1 && B <= 65535, "%s: need B in 1 .. 65535", who);
+  VBX_REQUIRE(C >= 8 && C % 8 == 0 && C <= HB_MAX_C, "%s: channels must be a multiple of 8 up to %d (got %d)", who, HB_MAX_C, C);
+  VBX_REQUIRE(k0 >= 1 && k0 <= HB_MAX_K0 && s0 >= 1 && s0 <= HB_MAX_S0, "%s: kernel_size in 1 .. %d and stride in 1 .. %d (got %d, %d)", who,
+              HB_MAX_K0, HB_MAX_S0, k0, s0);
+  VBX_REQUIRE(T >= k0 && T < (1L << 31), "%s: the wave is shorter than one kernel, or too long", who);
+  *L0 = (T - k0) / s0 + 1;
+  return 0;
+}
+
+extern "C" int vbx_hubert_conv0_stats(const float* wave, const float* w, float* records, float* stats, int B, long T, int C, int k0, int s0,
+                                      float eps, void* stream) {
+  VBX_REQUIRE(wave && w && records && stats, "vbx_hubert_conv0_stats: null operand");
+  long L0;
+  if (int rc = hb_conv0_check("vbx_hubert_conv0_stats", B, T, C, k0, s0, &L0)) return rc;
+  const int chunks = cdiv(L0, HB_CHUNK);
+  hipLaunchKernelGGL(hubert_conv0_stats_kernel, dim3(chunks, B), dim3(256), 0, (hipStream_t)stream, wave, w, records, (int)T, (int)L0, C, k0, s0, chunks);
+  VBX_LAUNCH_CHECK();
+  hipLaunchKernelGGL(hubert_conv0_finalize_kernel, dim3(cdiv((long)B * C, 256)), dim3(256), 0, (hipStream_t)stream, records, stats, B * C, (int)L0, C,
+                     chunks, eps);
+  VBX_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int vbx_hubert_conv0_apply(const float* wave, const float* w, const float* stats, const float* gamma, const float* beta, void* y_f16,
+                                      int B, long T, int C, int k0, int s0, void* stream) {
+  VBX_REQUIRE(wave && w && stats && gamma && beta && y_f16, "vbx_hubert_conv0_apply: null operand");
+  long L0;
+  if (int rc = hb_conv0_check("vbx_hubert_conv0_apply", B, T, C, k0, s0, &L0)) return rc;
+  hipLaunchKernelGGL(hubert_conv0_apply_kernel, dim3(cdiv(L0 * (C / 8), 256), B), dim3(256), 0, (hipStream_t)stream, wave, w, stats, gamma, beta,
+                     (u16*)y_f16, (int)T, (int)L0, C, k0, s0);
+  VBX_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int vbx_hubert_conv_tile(int C, int k) {
+  if (int rc = hb_conv_check(C, k)) return rc;
+  return hb_conv_tile(C, k);  // never 0: 16 positions of 512 channels at k 3 take 34 KiB
+}
+
+extern "C" int vbx_hubert_conv(const void* x_f16, const void* w_f16, void* y_f16, int B, int L, int C, int k, void* stream) {
+  VBX_REQUIRE(x_f16 && w_f16 && y_f16, "vbx_hubert_conv: null operand");
+  VBX_REQUIRE(B >= 1 && B <= 65535 && L >= k && L < (1 << 30), "vbx_hubert_conv: need B in 1 .. 65535 and kernel_size <= L < 2^30");
+  if (int rc = hb_conv_check(C, k)) return rc;
+  HbConv p;
+  p.x = (const u16*)x_f16, p.w = (const u16*)w_f16, p.y = (u16*)y_f16, p.L = L, p.Lout = (L - k) / 2 + 1, p.C = C, p.k = k;
+  int TT = hb_conv_tile(C, k);
+  while (TT > 16 && TT / 2 >= p.Lout) TT >>= 1;  // a short row: no tile of absent positions is staged or multiplied
+  p.TT = TT;
+  const size_t bytes = hb_conv_lds(TT, C, k);
+  const int MG = sn_blocks_per_item(C / 16, TT / 16), blocks = cdiv(p.Lout, TT);
+  if (MG == 4) return sn_launch<hubert_conv_kernel<4>>("vbx_hubert_conv", p, blocks, B, bytes, (hipStream_t)stream);
+  if (MG == 2) return sn_launch<hubert_conv_kernel<2>>("vbx_hubert_conv", p, blocks, B, bytes, (hipStream_t)stream);
+  return sn_launch<hubert_conv_kernel<1>>("vbx_hubert_conv", p, blocks, B, bytes, (hipStream_t)stream);
+}
+
+static int hb_ln_check(const char* who, const void* x, const float* g, const float* b, long M, int D) {
+  VBX_REQUIRE(x && g && b, "%s: null operand", who);
+  VBX_REQUIRE(M >= 1 && M < (1L << 31) && D >= 1 && D <= 8192, "%s: need rows >= 1 and D in 1 .. 8192", who);
+  return 0;
+}
+
+extern "C" int vbx_hubert_layernorm(const float* x, const float* gamma, const float* beta, float* y_f32, void* y_f16, long M, int D, float eps,
+                                    void* stream) {
+  if (int rc = hb_ln_check("vbx_hubert_layernorm", x, gamma, beta, M, D)) return rc;
+  VBX_REQUIRE(y_f32 || y_f16, "vbx_hubert_layernorm: no output");
+  hipLaunchKernelGGL(hubert_layernorm_kernel<false>, dim3(cdiv(M, 4)), dim3(256), 0, (hipStream_t)stream, (const void*)x, gamma, beta, y_f32,
+                     (u16*)y_f16, M, D, eps);
+  VBX_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int vbx_hubert_layernorm16(const void* x_f16, const float* gamma, const float* beta, void* y_f16, long M, int D, float eps, void* stream) {
+  if (int rc = hb_ln_check("vbx_hubert_layernorm16", x_f16, gamma, beta, M, D)) return rc;
+  VBX_REQUIRE(y_f16, "vbx_hubert_layernorm16: no output");
+  hipLaunchKernelGGL(hubert_layernorm_kernel<true>, dim3(cdiv(M, 4)), dim3(256), 0, (hipStream_t)stream, x_f16, gamma, beta, (float*)nullptr,
+                     (u16*)y_f16, M, D, eps);
+  VBX_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int vbx_hubert_posconv_tile(int Dg, int k) {
+  if (int rc = hb_pos_check(Dg, k)) return rc;
+  const int TT = hb_pos_tile(Dg, k);
+  if (!TT) {
+    vbx_set_error("vbx_hubert_posconv: 16 output positions of this convolution do not fit the LDS");
+    return VBX_EINVAL;
+  }
+  return TT;
+}
+
+extern "C" int vbx_hubert_posconv(const float* x, const void* w_f16, const float* bias, float* y, int B, int N, int D, int groups, int k,
+                                  void* stream) {
+  VBX_REQUIRE(x && w_f16 && bias && y && x != y, "vbx_hubert_posconv: null operand, or y aliases x");
+  VBX_REQUIRE(B >= 1 && B <= 65535 && N >= 1 && N < (1 << 24), "vbx_hubert_posconv: need B in 1 .. 65535 and N in 1 .. 2^24");
+  VBX_REQUIRE(groups >= 1 && D >= groups && D % groups == 0, "vbx_hubert_posconv: groups must divide D");
+  const int Dg = D / groups;
+  if (int rc = hb_pos_check(Dg, k)) return rc;
+  int TT = hb_pos_tile(Dg, k);
+  VBX_REQUIRE(TT > 0, "vbx_hubert_posconv: 16 output positions of this convolution do not fit the LDS");
+  while (TT > 16 && TT / 2 >= N) TT >>= 1;
+  HbPos p;
+  p.x = x, p.w = (const u16*)w_f16, p.bias = bias, p.y = y, p.N = N, p.D = D, p.Dg = Dg, p.G = groups, p.k = k, p.TT = TT;
+  const long blocks = (long)cdiv(N, TT) * groups;
+  VBX_REQUIRE(blocks < (1L << 31), "vbx_hubert_posconv: too many tiles");
+  const size_t bytes = hb_pos_lds(TT, Dg, k);
+  const int MG = sn_blocks_per_item((Dg + 15) / 16, TT / 16);
+  if (MG == 4) return sn_launch<hubert_posconv_kernel<4>>("vbx_hubert_posconv", p, (int)blocks, B, bytes, (hipStream_t)stream);
+  if (MG == 2) return sn_launch<hubert_posconv_kernel<2>>("vbx_hubert_posconv", p, (int)blocks, B, bytes, (hipStream_t)stream);
+  return sn_launch<hubert_posconv_kernel<1>>("vbx_hubert_posconv", p, (int)blocks, B, bytes, (hipStream_t)stream);
+}
+
+extern "C" int vbx_hubert_split_heads(const float* qkv, void* q16, void* k16, void* v16, int B, int N, int H, float q_prescale, void* stream) {
+  VBX_REQUIRE(qkv && q16 && k16 && v16, "vbx_hubert_split_heads: null operand");
+  VBX_REQUIRE(B >= 1 && N >= 1 && H >= 1 && q_prescale > 0.f, "vbx_hubert_split_heads: bad dims");
+  const long M = (long)B * N, items = M * (3 * H * 8);
+  VBX_REQUIRE(items / 256 < (1L << 31) - 1, "vbx_hubert_split_heads: too large");
+  hipLaunchKernelGGL(hubert_split_heads_kernel, dim3(cdiv(items, 256)), dim3(256), 0, (hipStream_t)stream, qkv, (u16*)q16, (u16*)k16, (u16*)v16, M, N, H,
+                     q_prescale);
+  VBX_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int vbx_kmeans_assign(const float* h, const float* centers, long long* ids, long M, int D, int K, void* stream) {
+  VBX_REQUIRE(h && centers && ids, "vbx_kmeans_assign: null operand");
+  VBX_REQUIRE(D >= 8 && D % 8 == 0 && D <= HB_KM_MAX_D, "vbx_kmeans_assign: D must be a multiple of 8 up to %d (got %d)", HB_KM_MAX_D, D);
+  VBX_REQUIRE(K >= 1 && K <= HB_KM_MAX_K, "vbx_kmeans_assign: K must be in 1 .. %d (got %d)", HB_KM_MAX_K, K);
+  VBX_REQUIRE(M >= 1 && M < (1L << 31), "vbx_kmeans_assign: need 1 <= rows < 2^31");
+  hipLaunchKernelGGL(hubert_kmeans_kernel, dim3(cdiv(M, HB_KM_ROWS)), dim3(256), 0, (hipStream_t)stream, h, centers, ids, M, D, K);
+  VBX_LAUNCH_CHECK();
+  return 0;
+}

@@ -773,6 +773,9 @@ class TrainStep:
             # the frames added up to length_bucket below lie past every length: key_lens is unchanged by that padding
             key_lens = train_lens.key_lens(lens, vb._cfg["R"])
         # a wave batch of a codec model (voicebox_pytorch.py:1349-1371), resampled first when the wrapper says so; latents pass through
+        if cond_token_ids is None and vb.condition_on_text and getattr(w, "wav2vec", None) is not None and x1.ndim in (2, 3) \
+                and (x1.ndim == 2 or x1.shape[1] == 1):
+            cond_token_ids = w.wav2vec_token_ids(x1, input_sampling_rate)  # :1386-1388: semantic ids of the wave itself
         x1, _ = w.encode_raw_audio(x1, None, input_sampling_rate)
         x1 = x1.to(dev, torch.float32).contiguous()
         B, N, _ = x1.shape

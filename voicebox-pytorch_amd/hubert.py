@@ -1,0 +1,378 @@
+"""HubertWithKmeans: HuBERT base (Hsu et al. 2021) up to one encoder layer plus a k-means codebook on the device -- waves into
+semantic token ids, the module the reference calls `wav2vec` ("hubert usually", voicebox_pytorch.py:1374-1390, :1213-1257) and
+audiolm_pytorch ships as HubertWithKmeans: forward(wav_input, flatten=True, input_sample_hz=None) -> int64 [B, frames].
+
+The network is the BASE form only (feat_extract_norm="group", do_stable_layer_norm=False, conv_bias=False): a 1 -> C convolution with
+GroupNorm(C, C) over time and erf-GELU, six strided C -> C convolutions with erf-GELU, LayerNorm + Linear(C, D), a grouped weight-normed
+positional convolution (one norm per tap, the last output sample dropped), encoder.layer_norm, post-LN transformer layers
+1 .. output_layer (later layers are loaded, never packed or launched), then the Euclidean argmin over `cluster_centers`.  The
+parameters carry transformers.HubertModel's names and shapes, so its state_dict() loads as is; fairseq's names and the old
+weight_g / weight_v pair are translated.  Neither library nor any weights are part of this package and nothing here reaches a hub:
+from_checkpoint reads LOCAL files.
+
+PARITY PINNED against transformers: tests/hubert_ref.py restates the network in fp64 and tests/test_hubert_cpu.py holds that
+restatement to transformers.HubertModel (fp64, eager attention) within 1e-10 at every hidden state; the kernels are tested against
+the restatement (tests/test_hubert_gpu.py, profiles/hubert_parity.txt).  fairseq and audiolm_pytorch themselves stay unpinned (absent),
+including the claim that fairseq's output_layer = L is hidden_states[L].
+
+Device path (csrc/hubert.hip, csrc/gemm.hip, csrc/attn.hip): a fixed launch sequence without host synchronisation; where each tensor
+is rounded is stated in include/vbx.h.  Inference only, GPU tensors only, rows of a batch of equal length (no padding mask).
+"""
+import math
+
+import torch
+from torch import nn
+
+from . import _lib
+from ._packing import PackedWeights
+
+_G0, _G1 = "encoder.pos_conv_embed.conv.parametrizations.weight.original0", "encoder.pos_conv_embed.conv.parametrizations.weight.original1"
+_LDS_MAX = 160 * 1024  # csrc/seanet_tile.hpp: SN_LDS_MAX
+
+
+class _Box(nn.Module):
+    """a bare container: the parameters below carry transformers.HubertModel's dotted names"""
+
+
+def _ln(dim):
+    b = _Box()
+    b.weight, b.bias = nn.Parameter(torch.ones(dim)), nn.Parameter(torch.zeros(dim))
+    return b
+
+
+def _linear(out, inp):
+    b = _Box()
+    b.weight, b.bias = nn.Parameter(torch.randn(out, inp) / math.sqrt(inp)), nn.Parameter(torch.zeros(out))
+    return b
+
+
+_FAIRSEQ = (("self_attn_layer_norm.", "layer_norm."), ("self_attn.", "attention."), ("fc1.", "feed_forward.intermediate_dense."),
+            ("fc2.", "feed_forward.output_dense."))
+_SKIPPED = ("masked_spec_embed", "mask_emb", "label_embs_concat", "final_proj.")
+
+
+def convert_state_dict(sd):
+    """transformers' names from any of: a transformers.HubertModel state dict (optionally under `hubert.`), fairseq's names, the old
+    weight_g / weight_v pair, a file's {'model': sd}.  masked_spec_embed / mask_emb / label_embs_concat / final_proj are skipped."""
+    if isinstance(sd, dict) and "model" in sd and isinstance(sd["model"], dict):
+        sd = sd["model"]
+    out = {}
+    for k, v in sd.items():
+        if k.startswith("hubert."):
+            k = k[len("hubert."):]
+        if k.startswith(_SKIPPED):
+            continue
+        parts = k.split(".")
+        if k.startswith("feature_extractor.conv_layers.") and len(parts) == 5 and parts[3] == "0" and parts[4] == "weight":
+            k = f"feature_extractor.conv_layers.{parts[2]}.conv.weight"  # fairseq: Sequential(conv, dropout, norm, gelu)
+        elif k.startswith("feature_extractor.conv_layers.") and len(parts) == 5 and parts[3] == "2":
+            k = f"feature_extractor.conv_layers.{parts[2]}.layer_norm.{parts[4]}"
+        elif k.startswith("layer_norm."):
+            k = "feature_projection." + k
+        elif k.startswith("post_extract_proj."):
+            k = "feature_projection.projection." + k[len("post_extract_proj."):]
+        elif k.startswith("encoder.pos_conv.0."):
+            k = "encoder.pos_conv_embed.conv." + k[len("encoder.pos_conv.0."):]
+        elif k.startswith("encoder.layers."):
+            for a, b in _FAIRSEQ:
+                if "." + a in k:
+                    k = k.replace("." + a, "." + b)
+                    break
+        if k == "encoder.pos_conv_embed.conv.weight_g":
+            k = _G0
+        elif k == "encoder.pos_conv_embed.conv.weight_v":
+            k = _G1
+        out[k] = v
+    return out
+
+
+def load_kmeans(path):
+    """cluster centres fp32 [K, D] from a LOCAL file: a torch.save'd tensor, a .npy array, or a joblib-pickled sklearn estimator
+    with cluster_centers_ (joblib / sklearn are imported only then)"""
+    path = str(path)
+    if path.endswith(".npy"):
+        import numpy as np
+
+        c = torch.from_numpy(np.load(path))
+    else:
+        try:
+            c = torch.load(path, map_location="cpu", weights_only=True)
+        except Exception:
+            import joblib
+
+            c = joblib.load(path)
+        if not isinstance(c, torch.Tensor):
+            c = torch.as_tensor(c.cluster_centers_ if hasattr(c, "cluster_centers_") else c)
+    if c.ndim != 2:
+        raise ValueError(f"HubertWithKmeans: cluster centres must be [K, D] (got {tuple(c.shape)})")
+    return c.float().contiguous()
+
+
+class HubertWithKmeans(PackedWeights, nn.Module):
+    """wave fp32 [B, T] (or [B, 1, T]) at target_sample_hz -> ids int64 [B, frames]; features(wave) -> fp32 [B, frames, hidden_size],
+    the output of encoder layer `output_layer` (transformers' hidden_states[output_layer]).  input_sample_hz: the wave is first
+    resampled on the device with the package's resample(); seq_len_multiple_of then curtails it to a multiple (audiolm_pytorch's
+    order).  frames: L <- (L - k) // s + 1 per convolution.
+
+    Raises NotImplementedError, before any launch, for what is not served: feat_extract_norm="layer", do_stable_layer_norm=True (the
+    large models), conv_bias=True; hidden_size / num_attention_heads != 64 (x-large); hidden_size not a multiple of 64 or above 2048;
+    conv_dim not constant, not a multiple of 16 or above 512; conv_kernel[0] or conv_stride[0] above 16, later kernels outside 2 .. 3,
+    later strides other than 2; hidden_size / groups not a multiple of 8, an odd num_conv_pos_embeddings, a positional convolution whose
+    16-position span does not fit the LDS; codebook_size outside 2 .. 4096; output_layer outside 1 .. num_hidden_layers; a wave shorter than
+    one frame; an attention / padding mask.  A CPU tensor raises VbxError."""
+
+    def __init__(self, hidden_size=768, num_hidden_layers=12, num_attention_heads=12, intermediate_size=3072, conv_dim=(512,) * 7,
+                 conv_kernel=(10, 3, 3, 3, 3, 2, 2), conv_stride=(5, 2, 2, 2, 2, 2, 2), num_conv_pos_embeddings=128,
+                 num_conv_pos_embedding_groups=16, layer_norm_eps=1e-5, output_layer=9, codebook_size=500, target_sample_hz=16000,
+                 seq_len_multiple_of=None, feat_extract_norm="group", do_stable_layer_norm=False, conv_bias=False):
+        super().__init__()
+        who = "HubertWithKmeans"
+        conv_dim, conv_kernel, conv_stride = tuple(conv_dim), tuple(conv_kernel), tuple(conv_stride)
+        if feat_extract_norm != "group":
+            raise NotImplementedError(f'{who}: feat_extract_norm="{feat_extract_norm}" is not built here (only "group", the base form)')
+        if do_stable_layer_norm:
+            raise NotImplementedError(f"{who}: do_stable_layer_norm=True (the pre-LN encoder of the large models) is not built here")
+        if conv_bias:
+            raise NotImplementedError(f"{who}: conv_bias=True is not built here")
+        D, H, G, k = hidden_size, num_attention_heads, num_conv_pos_embedding_groups, num_conv_pos_embeddings
+        if H < 1 or D != 64 * H:
+            raise NotImplementedError(f"{who}: hidden_size / num_attention_heads must be 64, the head size the attention kernels serve (got {D} / {H})")
+        if D % 64 or D > 2048:
+            raise NotImplementedError(f"{who}: hidden_size must be a multiple of 64, at most 2048 (got {D})")
+        if not (len(conv_dim) == len(conv_kernel) == len(conv_stride) >= 1):
+            raise ValueError("conv_dim, conv_kernel and conv_stride must have one entry per convolution")
+        C = conv_dim[0]
+        if any(c != C for c in conv_dim) or C % 16 or not 16 <= C <= 512:
+            raise NotImplementedError(f"{who}: conv_dim must be constant, a multiple of 16, at most 512 (got {conv_dim})")
+        if not 1 <= conv_kernel[0] <= 16 or not 1 <= conv_stride[0] <= 16:
+            raise NotImplementedError(f"{who}: conv_kernel[0] and conv_stride[0] must be at most 16 (got {conv_kernel[0]}, {conv_stride[0]})")
+        if any(kk not in (2, 3) for kk in conv_kernel[1:]):
+            raise NotImplementedError(f"{who}: conv_kernel after the first must be 2 or 3 (got {conv_kernel})")
+        if any(s != 2 for s in conv_stride[1:]):
+            raise NotImplementedError(f"{who}: conv_stride must be (s0, 2, 2, ...) (got {conv_stride})")
+        if G < 1 or D % G or (D // G) % 8:
+            raise NotImplementedError(f"{who}: hidden_size / num_conv_pos_embedding_groups must be a multiple of 8 (got {D} / {G})")
+        if k < 2 or k % 2:
+            raise NotImplementedError(f"{who}: num_conv_pos_embeddings must be even (got {k})")
+        if (15 + k) * (D // G + 8) * 2 > _LDS_MAX:
+            raise NotImplementedError(f"{who}: 16 positions of the positional convolution ({k} taps of {D // G} channels) do not fit the LDS")
+        if not 2 <= codebook_size <= 4096:
+            raise NotImplementedError(f"{who}: codebook_size must be in 2 .. 4096 (got {codebook_size})")
+        if not 1 <= output_layer <= num_hidden_layers:
+            raise NotImplementedError(f"{who}: output_layer must be in 1 .. num_hidden_layers = {num_hidden_layers} (got {output_layer})")
+        if intermediate_size < 8 or intermediate_size % 8:
+            raise NotImplementedError(f"{who}: intermediate_size must be a multiple of 8 (got {intermediate_size})")
+        self.hidden_size, self.num_hidden_layers, self.num_attention_heads, self.intermediate_size = D, num_hidden_layers, H, intermediate_size
+        self.conv_dim, self.conv_kernel, self.conv_stride = conv_dim, conv_kernel, conv_stride
+        self.num_conv_pos_embeddings, self.num_conv_pos_embedding_groups, self.layer_norm_eps = k, G, float(layer_norm_eps)
+        self.output_layer, self.codebook_size, self.target_sample_hz = output_layer, codebook_size, target_sample_hz
+        self.seq_len_multiple_of, self.groups = seq_len_multiple_of, 1
+        self.downsample_factor = math.prod(conv_stride)
+
+        self.feature_extractor = _Box()
+        self.feature_extractor.conv_layers = nn.ModuleList()
+        cin = 1
+        for i, kk in enumerate(conv_kernel):
+            layer = _Box()
+            layer.conv = _Box()
+            layer.conv.weight = nn.Parameter(torch.randn(C, cin, kk) * math.sqrt(2.0 / (cin * kk)))
+            if i == 0:
+                layer.layer_norm = _ln(C)
+            self.feature_extractor.conv_layers.append(layer)
+            cin = C
+        self.feature_projection = _Box()
+        self.feature_projection.layer_norm, self.feature_projection.projection = _ln(C), _linear(D, C)
+        self.encoder = _Box()
+        pce = _Box()
+        pce.conv = _Box()
+        pce.conv.bias = nn.Parameter(torch.zeros(D))
+        pce.conv.parametrizations = _Box()
+        pce.conv.parametrizations.weight = _Box()
+        v = torch.randn(D, D // G, k) * (2.0 * math.sqrt(1.0 / (k * D)))
+        pce.conv.parametrizations.weight.original0 = nn.Parameter(v.norm(dim=(0, 1), keepdim=True))  # [1, 1, k]: one norm per tap
+        pce.conv.parametrizations.weight.original1 = nn.Parameter(v)
+        self.encoder.pos_conv_embed = pce
+        self.encoder.layer_norm = _ln(D)
+        self.encoder.layers = nn.ModuleList()
+        for _ in range(num_hidden_layers):
+            l = _Box()
+            l.attention = _Box()
+            l.attention.q_proj, l.attention.k_proj, l.attention.v_proj, l.attention.out_proj = (_linear(D, D) for _ in range(4))
+            l.layer_norm = _ln(D)
+            l.feed_forward = _Box()
+            l.feed_forward.intermediate_dense, l.feed_forward.output_dense = _linear(intermediate_size, D), _linear(D, intermediate_size)
+            l.final_layer_norm = _ln(D)
+            self.encoder.layers.append(l)
+        self.register_buffer("cluster_centers", torch.randn(codebook_size, D))
+        self.requires_grad_(False)
+        self.eval()
+
+    # -- state
+    def load_state_dict(self, state_dict, strict=True, **kw):
+        sd = convert_state_dict(state_dict)
+        sd.setdefault("cluster_centers", self.cluster_centers)  # a HuBERT state dict holds no codebook: the buffer stays
+        return super().load_state_dict(sd, strict=strict, **kw)
+
+    def set_cluster_centers(self, centers):
+        c = torch.as_tensor(centers).detach().float()
+        if tuple(c.shape) != (self.codebook_size, self.hidden_size):
+            raise ValueError(f"HubertWithKmeans: cluster centres must be [{self.codebook_size}, {self.hidden_size}] (got {tuple(c.shape)})")
+        self.cluster_centers = c.to(self.cluster_centers.device).contiguous()
+
+    @classmethod
+    def from_state_dict(cls, sd, cluster_centers, *, output_layer=9, conv_stride=None, target_sample_hz=16000, seq_len_multiple_of=None):
+        """A HuBERT state dict already in memory (any layout convert_state_dict takes) and cluster centres [K, D].  Every width is read
+        off the shapes; the strides are not in a state dict (default (5, 2, 2, ...), the published models')."""
+        sd = convert_state_dict(sd)
+        n_conv = 1 + max(int(k.split(".")[2]) for k in sd if k.startswith("feature_extractor.conv_layers."))
+        convs = [sd[f"feature_extractor.conv_layers.{i}.conv.weight"] for i in range(n_conv)]
+        n_layers = 1 + max(int(k.split(".")[2]) for k in sd if k.startswith("encoder.layers."))
+        D = sd["feature_projection.projection.weight"].shape[0]
+        v = sd[_G1]
+        cluster_centers = torch.as_tensor(cluster_centers)
+        for name, what in (("feature_extractor.conv_layers.0.conv.bias", "conv_bias=True"),
+                           ("feature_extractor.conv_layers.1.layer_norm.weight", 'feat_extract_norm="layer"')):
+            if name in sd:
+                raise NotImplementedError(f"HubertWithKmeans: this state dict is of a model with {what}, which is not built here")
+        self = cls(hidden_size=D, num_hidden_layers=n_layers, num_attention_heads=max(D // 64, 1),
+                   intermediate_size=sd["encoder.layers.0.feed_forward.intermediate_dense.weight"].shape[0],
+                   conv_dim=tuple(w.shape[0] for w in convs), conv_kernel=tuple(w.shape[2] for w in convs),
+                   conv_stride=tuple(conv_stride) if conv_stride is not None else (5,) + (2,) * (n_conv - 1),
+                   num_conv_pos_embeddings=v.shape[2], num_conv_pos_embedding_groups=D // v.shape[1], output_layer=output_layer,
+                   codebook_size=cluster_centers.shape[0], target_sample_hz=target_sample_hz, seq_len_multiple_of=seq_len_multiple_of)
+        self.load_state_dict(sd)
+        self.set_cluster_centers(cluster_centers)
+        return self.eval()
+
+    @classmethod
+    def from_checkpoint(cls, checkpoint_path, kmeans_path, *, output_layer=9, conv_stride=None, target_sample_hz=16000, seq_len_multiple_of=None):
+        """LOCAL files only: a torch.save'd state dict (transformers' or fairseq's names, or {'model': sd}) and the k-means file
+        (load_kmeans)."""
+        sd = torch.load(checkpoint_path, map_location="cpu", weights_only=True)
+        return cls.from_state_dict(sd, load_kmeans(kmeans_path), output_layer=output_layer, conv_stride=conv_stride,
+                                   target_sample_hz=target_sample_hz, seq_len_multiple_of=seq_len_multiple_of)
+
+    # -- operand copies
+    def _pack(self):
+        """fp16 product operands and fp32 vectors as the launch sequence reads them, layers 1 .. output_layer only; kept per
+        parameter version (PackedWeights)"""
+        f = lambda t: t.detach().float().contiguous()
+        h = lambda t: t.detach().float().half().contiguous()
+        fe, fp, enc = self.feature_extractor.conv_layers, self.feature_projection, self.encoder
+        D, k = self.hidden_size, self.num_conv_pos_embeddings
+        convs = [h(l.conv.weight.permute(0, 2, 1).reshape(l.conv.weight.shape[0], -1)) for l in list(fe)[1:]]  # column tap * C + c
+        pw = enc.pos_conv_embed.conv.parametrizations.weight
+        g, v = pw.original0.detach().float(), pw.original1.detach().float()
+        posw = v * (g / v.norm(dim=(0, 1), keepdim=True))  # weight norm at dim=2 folded in fp32, then rounded once
+        layers = []
+        for l in list(enc.layers)[:self.output_layer]:
+            a, ff = l.attention, l.feed_forward
+            layers.append(dict(
+                wqkv=h(torch.cat([a.q_proj.weight, a.k_proj.weight, a.v_proj.weight])), bqkv=f(torch.cat([a.q_proj.bias, a.k_proj.bias, a.v_proj.bias])),
+                wo=h(a.out_proj.weight), bo=f(a.out_proj.bias), n1w=f(l.layer_norm.weight), n1b=f(l.layer_norm.bias),
+                w1=h(ff.intermediate_dense.weight), b1=f(ff.intermediate_dense.bias), w2=h(ff.output_dense.weight), b2=f(ff.output_dense.bias),
+                n2w=f(l.final_layer_norm.weight), n2b=f(l.final_layer_norm.bias)))
+        return dict(w0=f(fe[0].conv.weight[:, 0, :]), gnw=f(fe[0].layer_norm.weight), gnb=f(fe[0].layer_norm.bias), convs=convs,
+                    fplw=f(fp.layer_norm.weight), fplb=f(fp.layer_norm.bias), fpw=h(fp.projection.weight), fpb=f(fp.projection.bias),
+                    posw=h(posw.permute(0, 2, 1).reshape(D, -1)), posb=f(enc.pos_conv_embed.conv.bias),
+                    elw=f(enc.layer_norm.weight), elb=f(enc.layer_norm.bias), layers=layers)
+
+    @staticmethod
+    def _gemm(epi, M, N, K, A, B, C, bias, resid=None):
+        d = _lib.GemmDesc()
+        d.mode, d.epilogue, d.M, d.N, d.K, d.lda, d.ldb, d.ldc, d.f16 = _lib.VBX_GEMM_NT, epi, M, N, K, K, K, N, 1
+        d.A, d.B, d.C, d.bias = A.data_ptr(), B.data_ptr(), C.data_ptr(), bias.data_ptr()
+        d.resid = None if resid is None else resid.data_ptr()
+        rc = _lib.lib().vbx_gemm(d, _lib.current_stream())
+        if rc != 0:
+            raise _lib.VbxError(f"vbx_gemm failed (rc={rc}): {_lib.lib().vbx_last_error().decode()}")
+
+    def frames(self, samples):
+        """frames of a wave of `samples` samples at target_sample_hz (0 or less: shorter than one frame)"""
+        for k, s in zip(self.conv_kernel, self.conv_stride):
+            samples = (samples - k) // s + 1 if samples >= k else 0
+        return samples
+
+    def _prepare(self, wave, input_sample_hz, attention_mask):
+        if attention_mask is not None:
+            raise NotImplementedError("HubertWithKmeans: an attention / padding mask is not served: rows of a batch are of equal length")
+        if not isinstance(wave, torch.Tensor) or wave.ndim not in (2, 3) or (wave.ndim == 3 and wave.shape[1] != 1):
+            raise ValueError("HubertWithKmeans takes a wave (batch, samples) or (batch, 1, samples)")
+        if wave.device.type != "cuda":
+            raise _lib.VbxError(f"HubertWithKmeans runs only on an MI355X (gfx950) through libvbx_hip.so; the wave is on '{wave.device}'")
+        if wave.ndim == 3:
+            wave = wave[:, 0]
+        wave = wave.detach().to(torch.float32)
+        if input_sample_hz is not None and input_sample_hz != self.target_sample_hz:
+            from .codec import resample
+
+            wave = resample(wave, input_sample_hz, self.target_sample_hz)
+        if self.seq_len_multiple_of is not None:
+            wave = wave[:, :wave.shape[1] // self.seq_len_multiple_of * self.seq_len_multiple_of]
+        if self.frames(wave.shape[1]) < 1:
+            raise NotImplementedError(f"HubertWithKmeans: a wave of {wave.shape[1]} samples is shorter than one frame")
+        if self.cluster_centers.device != wave.device:
+            self.to(wave.device)
+        return wave.contiguous()
+
+    @torch.no_grad()
+    def features(self, wav_input, input_sample_hz=None, attention_mask=None):
+        return self._features(self._prepare(wav_input, input_sample_hz, attention_mask))
+
+    def _features(self, wave):
+        w = self._cached(self._pack)
+        st, dev, eps = _lib.current_stream(), wave.device, self.layer_norm_eps
+        B, T = wave.shape
+        C, D, H, I = self.conv_dim[0], self.hidden_size, self.num_attention_heads, self.intermediate_size
+        f16 = lambda *s: torch.empty(*s, dtype=torch.float16, device=dev)
+        f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
+        k0, s0 = self.conv_kernel[0], self.conv_stride[0]
+        L = (T - k0) // s0 + 1
+        rec, stats = f32(B, _lib.lib().vbx_hubert_conv0_chunks(L), C, 3), f32(B, C, 2)
+        _lib.call("vbx_hubert_conv0_stats", wave, w["w0"], rec, stats, B, T, C, k0, s0, eps, st)
+        a = f16(B, L, C)
+        _lib.call("vbx_hubert_conv0_apply", wave, w["w0"], stats, w["gnw"], w["gnb"], a, B, T, C, k0, s0, st)
+        for kk, wc in zip(self.conv_kernel[1:], w["convs"]):
+            Lo = (L - kk) // 2 + 1
+            y = f16(B, Lo, C)
+            _lib.call("vbx_hubert_conv", a, wc, y, B, L, C, kk, st)
+            a, L = y, Lo
+        N, M = L, B * L
+        a16 = f16(M, C)
+        _lib.call("vbx_hubert_layernorm16", a, w["fplw"], w["fplb"], a16, M, C, eps, st)
+        xa, xb, x16 = f32(M, D), f32(M, D), f16(M, D)  # the residual stream ping-pongs; x16: the operand copy of the current one
+        self._gemm(_lib.VBX_EPI_F32, M, D, C, a16, w["fpw"], xa, w["fpb"])
+        _lib.call("vbx_hubert_posconv", xa, w["posw"], w["posb"], xb, B, N, D, self.num_conv_pos_embedding_groups, self.num_conv_pos_embeddings, st)
+        _lib.call("vbx_hubert_layernorm", xb, w["elw"], w["elb"], xa, x16, M, D, eps, st)
+        if not w["layers"]:
+            return xa.view(B, N, D)
+        qkv, q16, k16, v16 = f32(M, 3 * D), f16(B, H, N, 64), f16(B, H, N, 64), f16(B, H, N, 64)
+        o16, lse, g16 = f16(M, D), f32(B, H, N), f16(M, I)
+        scale = 64 ** -0.5
+        pre = _lib.lib().vbx_attn_q_prescale(scale)
+        for l in w["layers"]:
+            self._gemm(_lib.VBX_EPI_F32, M, 3 * D, D, x16, l["wqkv"], qkv, l["bqkv"])
+            _lib.call("vbx_hubert_split_heads", qkv, q16, k16, v16, B, N, H, pre, st)
+            _lib.call("vbx_attn_fwd", q16, k16, v16, None, o16, None, lse, B, H, N, scale, st)
+            self._gemm(_lib.VBX_EPI_F32, M, D, D, o16, l["wo"], xb, l["bo"], resid=xa)
+            _lib.call("vbx_hubert_layernorm", xb, l["n1w"], l["n1b"], xa, x16, M, D, eps, st)
+            self._gemm(_lib.VBX_EPI_GELU, M, I, D, x16, l["w1"], g16, l["b1"])
+            self._gemm(_lib.VBX_EPI_F32, M, D, I, g16, l["w2"], xb, l["b2"], resid=xa)
+            _lib.call("vbx_hubert_layernorm", xb, l["n2w"], l["n2b"], xa, x16, M, D, eps, st)
+        return xa.view(B, N, D)
+
+    def assign(self, feats):
+        """vbx_kmeans_assign of features fp32 [.., D] -> int64 [..]"""
+        if feats.device.type != "cuda":
+            raise _lib.VbxError(f"HubertWithKmeans runs only on an MI355X (gfx950) through libvbx_hip.so; the features are on '{feats.device}'")
+        if self.cluster_centers.device != feats.device:
+            self.to(feats.device)
+        h = feats.detach().to(torch.float32).contiguous()
+        ids = torch.empty(h.shape[:-1], dtype=torch.int64, device=h.device)
+        _lib.call("vbx_kmeans_assign", h, self.cluster_centers, ids, h.numel() // h.shape[-1], h.shape[-1], self.codebook_size, _lib.current_stream())
+        return ids
+
+    @torch.no_grad()
+    def forward(self, wav_input, flatten=True, input_sample_hz=None, attention_mask=None):
+        """ids int64 [B, frames] (`flatten` is audiolm_pytorch's keyword: with groups = 1 both of its shapes are this one)"""
+        return self.assign(self._features(self._prepare(wav_input, input_sample_hz, attention_mask)))

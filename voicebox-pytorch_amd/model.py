@@ -672,7 +672,7 @@ ODE_METHODS = ("euler", "midpoint", "rk4", "dopri5")  # torchdiffeq methods the 
 
 class ConditionalFlowMatcherWrapper(nn.Module):
     def __init__(self, voicebox, text_to_semantic=None, duration_predictor=None, sigma=0., ode_atol=1e-5, ode_rtol=1e-5,
-                 use_torchode=False, torchdiffeq_ode_method='midpoint', torchode_method_klass=None, cond_drop_prob=0., resample_input=False):
+                 use_torchode=False, torchdiffeq_ode_method='midpoint', torchode_method_klass=None, cond_drop_prob=0., resample_input=False, wav2vec=None):
         super().__init__()
         assert isinstance(voicebox, VoiceBox)
         self.sigma = sigma
@@ -693,6 +693,18 @@ class ConditionalFlowMatcherWrapper(nn.Module):
             raise NotImplementedError(f"torchdiffeq_ode_method={torchdiffeq_ode_method!r} is not built; the device solvers serve "
                                       f"{', '.join(repr(m) for m in ODE_METHODS)}")
         self.text_to_semantic = None
+        # wav2vec (not a reference keyword: there it hangs off text_to_semantic): the module that turns waves into semantic token ids
+        # -- HubertWithKmeans, or anything with target_sample_hz, downsample_factor and forward(wave) -> ids.  A frozen submodule: a
+        # text-conditioned forward on raw audio without ids computes them with it (:1381-1390), and sample() sizes cond by its
+        # frame rate (:1247-1257).  Without it nothing changes.
+        if exists(wav2vec):
+            assert self.condition_on_text, 'wav2vec should not be passed in if not conditioning on text'
+            for attr in ("target_sample_hz", "downsample_factor"):
+                if not hasattr(wav2vec, attr):
+                    raise TypeError(f"wav2vec needs .{attr} (and forward(wave) -> ids): got {type(wav2vec).__name__}")
+            if isinstance(wav2vec, nn.Module):
+                wav2vec.requires_grad_(False)
+        self.wav2vec = wav2vec
         self.duration_predictor = duration_predictor  # a submodule, as in the reference (:1147): its weights are in state_dict()
         self.cond_drop_prob = cond_drop_prob
         # resample_input (not a reference keyword): True resamples waves given with an input_sampling_rate other than the codec's
@@ -795,6 +807,11 @@ class ConditionalFlowMatcherWrapper(nn.Module):
                     _, cond_token_ids = self.duration_predictor.forward_with_cond_scale(
                         cond=cond, phoneme_ids=phoneme_ids, return_aligned_phoneme_ids=True)
             target_len = cond_token_ids.shape[-1]
+            if exists(cond) and exists(self.wav2vec) and exists(semantic_token_ids):
+                # :1247-1255: semantic ids run at wav2vec's frame rate, cond at the codec's -- the same stretch of time in both
+                assert exists(codec), 'audio_enc_dec must be set on VoiceBox to size cond from semantic token ids'
+                target_len = math.ceil((target_len * self.wav2vec.target_sample_hz / self.wav2vec.downsample_factor)
+                                       / (codec.sampling_rate / codec.downsample_factor))
             if exists(cond):  # curtail_or_pad(cond, cond_target_length) (:109-119, :1253)
                 n = cond.shape[-2]
                 cond = cond[..., :target_len, :] if n > target_len else torch.nn.functional.pad(cond, (0, 0, 0, target_len - n))
@@ -921,6 +938,23 @@ class ConditionalFlowMatcherWrapper(nn.Module):
                 cond = codec.encode(cond)
         return x1, cond
 
+    def wav2vec_token_ids(self, raw_audio, input_sampling_rate=None):
+        """voicebox_pytorch.py:1386-1388: semantic_token_ids = wav2vec(resample(raw_audio, input_sampling_rate or the codec's rate,
+        wav2vec.target_sample_hz)) on this wrapper's device, without gradients, wav2vec in eval mode.  What forward, TrainStep and
+        the trainer call when a text-conditioned model gets a wave and no ids."""
+        w2v = self.wav2vec
+        assert exists(w2v), 'no wav2vec on this wrapper: pass semantic_token_ids, or build it with wav2vec='
+        assert is_probably_audio_from_shape(raw_audio), 'wav2vec takes raw audio (batch, samples) or (batch, 1, samples)'
+        codec = self.voicebox.audio_enc_dec
+        rate = input_sampling_rate if exists(input_sampling_rate) else (codec.sampling_rate if exists(codec) else w2v.target_sample_hz)
+        with torch.no_grad():
+            if isinstance(w2v, nn.Module):
+                w2v.eval()
+            wave = raw_audio.to(self.device)
+            if rate != w2v.target_sample_hz:
+                wave = resample(wave, rate, w2v.target_sample_hz)
+            return w2v(wave).clone()
+
     def forward(self, x1, *, mask=None, lens=None, semantic_token_ids=None, phoneme_ids=None, cond=None, cond_mask=None,
                 input_sampling_rate=None):  # voicebox_pytorch.py:1332-1427
         """lens (not a reference keyword): a list, a CPU int tensor or a device int tensor [B] of frame counts, 1 <= len_b <= N -- the
@@ -939,6 +973,7 @@ class ConditionalFlowMatcherWrapper(nn.Module):
             train_lens.refuse_with_mask(lens, mask, who)
             train_lens.refuse_raw_audio(lens, x1, who)
             lens = train_lens.frame_lens(lens, x1.shape[0], x1.shape[1], self.device)
+        raw_audio = x1 if is_probably_audio_from_shape(x1) else None
         x1, cond = self.encode_raw_audio(x1, cond, input_sampling_rate)
         assert self.condition_on_text or not (exists(semantic_token_ids) or exists(phoneme_ids)), \
             'semantic or phoneme ids should not be passed in if not conditioning on text'
@@ -954,10 +989,12 @@ class ConditionalFlowMatcherWrapper(nn.Module):
         _lib.call("vbx_cfm_inputs", x1, x0.contiguous(), times.contiguous(), float(self.sigma), w, flow, batch,
                   x1[0].numel(), _lib.current_stream())  # :1408-1410
         cond_token_ids = None
-        if self.condition_on_text:  # :1374-1390 (no TextToSemantic module here: ids are given)
+        if self.condition_on_text:  # :1374-1390 (no TextToSemantic module here: ids are given, or wav2vec makes them from the wave)
             if exists(semantic_token_ids):
                 assert not exists(phoneme_ids), 'phoneme ids are not needed for conditioning with spear-tts text-to-semantic'
                 cond_token_ids = semantic_token_ids
+            elif exists(self.wav2vec) and exists(raw_audio) and not exists(phoneme_ids):
+                cond_token_ids = self.wav2vec_token_ids(raw_audio, input_sampling_rate)
             else:
                 assert exists(phoneme_ids)
                 cond_token_ids = phoneme_ids
