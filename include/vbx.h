@@ -838,6 +838,35 @@ int vbx_masked_mse_bwd(const float* pred, const float* target, const uint8_t* lo
 /* CFM inputs (voicebox_pytorch.py:1404-1410): w = (1-(1-sigma)t)x0 + t x1 ; flow = x1-(1-sigma)x0 */
 int vbx_cfm_inputs(const float* x1, const float* x0, const float* times, float sigma, float* w, float* flow, int B,
                    long per_batch, void* stream);
+/* Span mask and loss mask of the CFM objective from the drawn numbers (voicebox_pytorch.py:121-150, :1099), as masks.py computes
+ * them with torch, operation by operation in the same types -- equal byte for byte:
+ *   lengths = trunc(frac[b] * N) (one fp32 product), start = max(fp32(N - lengths) * rand[b], 0), end = start + fp32(lengths),
+ *   cond_mask[b][n] = trunc(start) <= n < trunc(end);  loss_mask = cond_mask & pad_mask & (n < key_lens[b] - R).
+ * frac, rand fp32 [B]; pad_mask uint8 [B, N] or NULL; key_lens int32 [B] (R + the row's frame count, vbx_io.key_lens) or NULL;
+ * cond_mask, loss_mask uint8 [B, N] (0 / 1; loss_mask may be NULL).  vbx_cfm_inputs_masks is vbx_cfm_inputs and vbx_span_masks in one
+ * launch (per_batch = N * the latent width); both leave what the separate launches leave. */
+int vbx_span_masks(const float* frac, const float* rand, const uint8_t* pad_mask, const int* key_lens, int R, int B, int N,
+                   uint8_t* cond_mask, uint8_t* loss_mask, void* stream);
+int vbx_cfm_inputs_masks(const float* x1, const float* x0, const float* times, float sigma, float* w, float* flow, int B, long per_batch,
+                         const float* frac, const float* rand, const uint8_t* pad_mask, const int* key_lens, int R, int N,
+                         uint8_t* cond_mask, uint8_t* loss_mask, void* stream);
+/* The finishing kernels of vbx_model_backward_embed in two launches, each job with the body, the block indices and so the bits of
+ * its own kernel:
+ *   vbx_embed_bwd_tail1 = the d(register tokens) launch of vbx_convpos_bwd (dreg [R, D] from dxs [B, Np, D]; R = 0: none),
+ *                         vbx_conv_wgrad_finalize(wpart, chunks, D, ksize, dw, db) and the first two launches of vbx_time_embed_bwd
+ *                         (dw1, db1; the d(four) partials into tscratch, vbx_time_embed_bwd_scratch_floats(B, D) floats);
+ *   vbx_embed_bwd_tail2 = vbx_splitk_reduce(slabs, splits, M, N, dst, M, N, N, 0, 0, 0), the second stage of vbx_colsum_f32 over
+ *                         the slabs vbx_colsum_f32_partials left in cs_scratch (C columns -> dbias) and the third launch of
+ *                         vbx_time_embed_bwd (d(four) = the sum of the partials, into tscratch[0 .. B * D));
+ *   vbx_time_embed_bwd_wsin = the fourth launch of vbx_time_embed_bwd (dfour = tscratch). */
+int vbx_embed_bwd_tail1(const float* dxs, float* dreg, int B, int Np, int R, int D, const float* wpart, int chunks, int ksize, float* dw,
+                        float* db, const float* four, const float* pre, const float* dtemb, const float* w1, float* dw1, float* db1,
+                        float* tscratch, int Th, void* stream);
+int vbx_embed_bwd_tail2(const float* slabs, int splits, int M, int N, float* dst, const float* cs_scratch, int C, float* dbias,
+                        float* tscratch, int B, int D, void* stream);
+int vbx_time_embed_bwd_wsin(const float* times, const float* four, const float* dfour, float* dw_sin, int B, int D, void* stream);
+/* first stage of vbx_colsum_f32 only: scratch[vbx_colsum_slabs()][C] */
+int vbx_colsum_f32_partials(const float* in, int M, int C, int ld, float* scratch, void* stream);
 /* y_out = y + coef[idx] * f   (ODE midpoint axpy; coef device-resident so graphs hold no host scalars) */
 int vbx_axpy_dev(const float* y, const float* f, const float* coef, int idx, float* out, long n, void* stream);
 /* hipGraph-replayable ODE step helpers (replace the host-side loop of torchdiffeq.odeint, call site
@@ -1226,6 +1255,10 @@ int vbx_model_backward_embed(const vbx_model* m, const vbx_io* io, void* stream)
  * while vbx_prof_enable(1) is on, and with vbx_wgrad_overlap(0) (environment VBX_WGRAD_OVERLAP=0 presets it; 1 = default).
  * Not thread safe; call between backwards. */
 int vbx_wgrad_overlap(int on);
+/* vbx_model_backward_embed runs its finishing kernels in two multi-job launches (vbx_embed_bwd_tail1 / _tail2; models without
+ * proj_in): 1 = default.  0: one launch each, as before.  The grouped form stores the bits of the separate launches; the switch exists
+ * for A/B timing and for the test that compares the two. */
+int vbx_embed_tail_grouped(int on);
 /* how many layers this process has submitted to the side stream so far (tests: the path that ran is the path that was meant) */
 int vbx_wgrad_overlap_forks(void);
 /* tests only: one idle wave (vbx_stream_delay) of side_us microseconds in front of every side-stream submission and of main_us at

@@ -38,6 +38,7 @@ _PROTOS = {
     "vbx_prof_enable": [I],
     "vbx_wgrad_overlap": [I],
     "vbx_wgrad_overlap_forks": [],
+    "vbx_embed_tail_grouped": [I],
     "vbx_wgrad_overlap_delay": [F, F],
     "vbx_gemm_tn_splitk_grouped": [C.POINTER(GemmDesc), I, P],
     "vbx_splitk_reduce": [P, I, I, I, P, I, I, I, I, I, I, P],
@@ -181,6 +182,12 @@ _PROTOS = {
     "vbx_masked_mse_fwd": [P, P, P, P, P, I, I, I, P],
     "vbx_masked_mse_bwd": [P, P, P, P, P, P, P, I, I, I, P],
     "vbx_cfm_inputs": [P, P, P, F, P, P, I, L, P],
+    "vbx_embed_bwd_tail1": [P, P, I, I, I, I, P, I, I, P, P, P, P, P, P, P, P, P, I, P],
+    "vbx_embed_bwd_tail2": [P, I, I, I, P, P, I, P, P, I, I, P],
+    "vbx_time_embed_bwd_wsin": [P, P, P, P, I, I, P],
+    "vbx_colsum_f32_partials": [P, I, I, I, P, P],
+    "vbx_span_masks": [P, P, P, P, I, I, I, P, P, P],
+    "vbx_cfm_inputs_masks": [P, P, P, F, P, P, I, L, P, P, P, P, I, I, P, P, P],
     "vbx_axpy_dev": [P, P, P, I, P, L, P],
     "vbx_axpy_ctr": [P, P, P, P, I, P, L, P],
     "vbx_counter_add": [P, I, P],

@@ -754,17 +754,7 @@ int launch(GemmParams p, const Epi& epi, int splits, int kernel, hipStream_t st)
 
 __global__ void splitk_reduce_kernel(const float* __restrict__ slabs, int splits, int M, int N, float* __restrict__ dst,
                                      int dst_rows, int dst_cols, long dst_ld, int rowmap, int F, int accumulate) {
-  const long total = (long)M * N;
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    const int r = (int)(i / N), c = (int)(i - (long)r * N);
-    int dr = r;
-    if (rowmap == 1) dr = geglu_row_unmap(r, F);
-    if (dr < 0 || dr >= dst_rows || c >= dst_cols) continue;
-    float s = 0.f;
-    for (int k = 0; k < splits; k++) s += slabs[(long)k * total + i];
-    float* o = dst + (long)dr * dst_ld + c;
-    *o = accumulate ? (*o + s) : s;
-  }
+  splitk_reduce_role(blockIdx.x, gridDim.x, slabs, splits, M, N, dst, dst_rows, dst_cols, dst_ld, rowmap, F, accumulate);  // reduce_roles.hpp
 }
 
 // several split-K reductions in one launch (the four weight gradients of a layer): job j owns blocks [block0, next block0)

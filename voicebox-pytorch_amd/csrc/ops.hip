@@ -430,9 +430,9 @@ __global__ __launch_bounds__(256) void convpos_bwd_kernel(const float* __restric
 }
 
 // dw[d][k] = sum_chunk wpart[chunk][d][k] (k < ks) ; db[d] = sum_chunk wpart[chunk][d][63]
-__global__ void conv_wgrad_finalize_kernel(const float* __restrict__ wpart, int chunks, int D, int ks, float* __restrict__ dw,
-                                           float* __restrict__ db) {
-  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+VBX_DEV void conv_wgrad_finalize_role(int bid, const float* __restrict__ wpart, int chunks, int D, int ks, float* __restrict__ dw,
+                                      float* __restrict__ db) {
+  const int idx = bid * blockDim.x + threadIdx.x;
   if (idx >= D * 64) return;
   const int d = idx >> 6, k = idx & 63;
   if (k >= ks && k != 63) return;
@@ -449,13 +449,20 @@ __global__ void conv_wgrad_finalize_kernel(const float* __restrict__ wpart, int 
   if (k == 63) db[d] = s;
   else dw[(long)d * ks + k] = s;
 }
+__global__ void conv_wgrad_finalize_kernel(const float* __restrict__ wpart, int chunks, int D, int ks, float* __restrict__ dw,
+                                           float* __restrict__ db) {
+  conv_wgrad_finalize_role(blockIdx.x, wpart, chunks, D, ks, dw, db);
+}
 
-__global__ void dreg_kernel(const float* __restrict__ dxs, float* __restrict__ dreg, int B, int Np, int R, int D) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+VBX_DEV void dreg_role(int bid, const float* __restrict__ dxs, float* __restrict__ dreg, int B, int Np, int R, int D) {
+  const int i = bid * blockDim.x + threadIdx.x;
   if (i >= R * D) return;
   float s = 0.f;
   for (int b = 0; b < B; b++) s += dxs[(long)b * Np * D + i];
   dreg[i] = s;
+}
+__global__ void dreg_kernel(const float* __restrict__ dxs, float* __restrict__ dreg, int B, int Np, int R, int D) {
+  dreg_role(blockIdx.x, dxs, dreg, B, Np, R, D);
 }
 
 // ---------------------------------------------------------------- time embedding
@@ -491,10 +498,9 @@ VBX_DEV float silu_grad(float p) {
   const float sg = 1.0f / (1.0f + expf(-p));
   return sg * (1.0f + p * (1.0f - sg));
 }
-__global__ void time_bwd_w1_kernel(const float* __restrict__ four, const float* __restrict__ pre,
-                                   const float* __restrict__ dtemb, float* __restrict__ dw1, float* __restrict__ db1, int B,
-                                   int D, int Th) {
-  const long idx = blockIdx.x * (long)blockDim.x + threadIdx.x;
+VBX_DEV void time_bwd_w1_role(int bid, const float* __restrict__ four, const float* __restrict__ pre, const float* __restrict__ dtemb,
+                              float* __restrict__ dw1, float* __restrict__ db1, int B, int D, int Th) {
+  const long idx = bid * (long)blockDim.x + threadIdx.x;
   if (idx >= (long)Th * D) return;
   const int i = (int)(idx / D), j = (int)(idx - (long)i * D);
   float s = 0.f, sb = 0.f;
@@ -506,17 +512,49 @@ __global__ void time_bwd_w1_kernel(const float* __restrict__ four, const float* 
   dw1[idx] = s;
   if (j == 0) db1[i] = sb;
 }
+__global__ void time_bwd_w1_kernel(const float* __restrict__ four, const float* __restrict__ pre,
+                                   const float* __restrict__ dtemb, float* __restrict__ dw1, float* __restrict__ db1, int B,
+                                   int D, int Th) {
+  time_bwd_w1_role(blockIdx.x, four, pre, dtemb, dw1, db1, B, D, Th);
+}
 // partial[slice][b][j] = sum_{i in slice} dtemb[b,i] silu'(pre[b,i]) W1[i,j]; grid (D/64, B, TB_SLICES), 64 threads
 constexpr int TB_SLICES = 32;
-__global__ void time_bwd_four_kernel(const float* __restrict__ w1, const float* __restrict__ pre,
-                                     const float* __restrict__ dtemb, float* __restrict__ partial, int B, int D, int Th) {
-  const int j = blockIdx.x * 64 + threadIdx.x, b = blockIdx.y, sl = blockIdx.z;
+// (bx, b, sl): the 64-thread block of the stand-alone grid that this wave stands in for; t = its thread index
+VBX_DEV void time_bwd_four_role(int bx, int b, int sl, int t, const float* __restrict__ w1, const float* __restrict__ pre,
+                                const float* __restrict__ dtemb, float* __restrict__ partial, int B, int D, int Th) {
+  const int j = bx * 64 + t;
   if (j >= D) return;
   const int per = (Th + TB_SLICES - 1) / TB_SLICES;
   const int ib = sl * per, ie = min(Th, ib + per);
   float s = 0.f;
   for (int i = ib; i < ie; i++) s += dtemb[(long)b * Th + i] * silu_grad(pre[(long)b * Th + i]) * w1[(long)i * D + j];
   partial[((long)sl * B + b) * D + j] = s;
+}
+__global__ void time_bwd_four_kernel(const float* __restrict__ w1, const float* __restrict__ pre,
+                                     const float* __restrict__ dtemb, float* __restrict__ partial, int B, int D, int Th) {
+  time_bwd_four_role(blockIdx.x, blockIdx.y, blockIdx.z, threadIdx.x, w1, pre, dtemb, partial, B, D, Th);
+}
+// vbx_model_backward_embed, first group: four finishing kernels that depend on nothing but what ran before them (the register-token
+// gradient, the conv weight gradient's records, the time MLP's weight gradient and d(four) partials) as block ranges of one grid.
+// Every range runs the body of its own kernel with the block index it would have had there.
+struct EmbedTail1 {
+  int nb_dreg, nb_conv, nb_w1, nb_four;  // blocks of 256 threads per job, in this order (nb_four: four 64-thread blocks of the original each)
+  const float* dxs; float* dreg; int B, Np, R, D;
+  const float* wpart; int chunks, ks; float *dw, *db;
+  const float *four, *pre, *dtemb, *w1; float *dw1, *db1, *partial; int Th;
+};
+__global__ __launch_bounds__(256) void embed_tail1_kernel(const EmbedTail1 a) {
+  int bid = blockIdx.x;  // every branch is block-uniform
+  if (bid < a.nb_dreg) { dreg_role(bid, a.dxs, a.dreg, a.B, a.Np, a.R, a.D); return; }
+  bid -= a.nb_dreg;
+  if (bid < a.nb_conv) { conv_wgrad_finalize_role(bid, a.wpart, a.chunks, a.D, a.ks, a.dw, a.db); return; }
+  bid -= a.nb_conv;
+  if (bid < a.nb_w1) { time_bwd_w1_role(bid, a.four, a.pre, a.dtemb, a.dw1, a.db1, a.B, a.D, a.Th); return; }
+  bid -= a.nb_w1;
+  const int vb = bid * 4 + (threadIdx.x >> 6), nx = (a.D + 63) / 64;  // grid (nx, B, TB_SLICES), x fastest
+  if (vb >= nx * a.B * TB_SLICES) return;
+  const int bx = vb % nx, b = (vb / nx) % a.B, sl = vb / (nx * a.B);
+  time_bwd_four_role(bx, b, sl, threadIdx.x & 63, a.w1, a.pre, a.dtemb, a.partial, a.B, a.D, a.Th);
 }
 __global__ void time_bwd_wsin_kernel(const float* __restrict__ times, const float* __restrict__ four,
                                      const float* __restrict__ dfour, float* __restrict__ dwsin, int B, int D) {
@@ -918,11 +956,10 @@ __global__ __launch_bounds__(1024) void sum_rows_wide_kernel(const float* __rest
 
 // out[j] (+)= sum_i in[i*ld + j]
 // block = 64 columns x 4 row lanes (launch with 256 threads, grid = cdiv(cols, 64))
-__global__ __launch_bounds__(256) void sum_rows_kernel(const float* __restrict__ in, long rows, long ld, float* __restrict__ out,
-                                                        long cols, int accumulate) {
-  __shared__ float red[4][64];
+VBX_DEV void sum_rows_role(int bid, const float* __restrict__ in, long rows, long ld, float* __restrict__ out, long cols, int accumulate,
+                           float (*red)[64]) {
   const int cl = threadIdx.x & 63, rl = threadIdx.x >> 6;
-  const long j = blockIdx.x * 64L + cl;
+  const long j = bid * 64L + cl;
   float s = 0.f;
   if (j < cols) {
     long i = rl;
@@ -941,6 +978,11 @@ __global__ __launch_bounds__(256) void sum_rows_kernel(const float* __restrict__
     const float t = red[0][cl] + red[1][cl] + red[2][cl] + red[3][cl];
     out[j] = accumulate ? out[j] + t : t;
   }
+}
+__global__ __launch_bounds__(256) void sum_rows_kernel(const float* __restrict__ in, long rows, long ld, float* __restrict__ out,
+                                                        long cols, int accumulate) {
+  __shared__ float red[4][64];
+  sum_rows_role(blockIdx.x, in, rows, ld, out, cols, accumulate, red);
 }
 
 // ---------------------------------------------------------------- column sums
@@ -1068,9 +1110,8 @@ __global__ __launch_bounds__(1024) void layer_reduce_kernel(vbx_skr_jobs sj, vbx
   const vbx_mr_job jb = mj.job[j];
   mr_role(jb, bx - jb.block0, red);
 }
-__global__ void colsum_stage2(const float* __restrict__ scratch, int C, float* __restrict__ out, int out_len, int rowmap,
-                              int F) {
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+VBX_DEV void colsum_stage2_role(int bid, const float* __restrict__ scratch, int C, float* __restrict__ out, int out_len, int rowmap, int F) {
+  const int c = bid * blockDim.x + threadIdx.x;
   if (c >= C) return;
   int dc = c;
   if (rowmap == 1) dc = geglu_row_unmap(c, F);
@@ -1085,6 +1126,28 @@ __global__ void colsum_stage2(const float* __restrict__ scratch, int C, float* _
     for (int u = 0; u < 4; u++) s += v[u];
   }
   out[dc] = s;
+}
+__global__ void colsum_stage2(const float* __restrict__ scratch, int C, float* __restrict__ out, int out_len, int rowmap,
+                              int F) {
+  colsum_stage2_role(blockIdx.x, scratch, C, out, out_len, rowmap, F);
+}
+// vbx_model_backward_embed, second group: the finishers of three two-stage reductions whose first stages have run -- the split-K slabs
+// of the embed weight gradient, the column-sum slabs of its bias gradient, the d(four) partials of the time MLP -- as block ranges
+// of one grid, each with the body and the block index of its own kernel.
+struct EmbedTail2 {
+  int nb_skr, nb_cs, nb_rows;
+  const float* slabs; int splits, M, N; float* dst; int dst_rows, dst_cols; long dst_ld;
+  const float* cs; int C; float* bias;
+  const float* partial; long rows, cols; float* dfour;
+};
+__global__ __launch_bounds__(256) void embed_tail2_kernel(const EmbedTail2 a) {
+  __shared__ float red[4][64];
+  int bid = blockIdx.x;  // every branch is block-uniform
+  if (bid < a.nb_skr) { splitk_reduce_role(bid, a.nb_skr, a.slabs, a.splits, a.M, a.N, a.dst, a.dst_rows, a.dst_cols, a.dst_ld, 0, 0, 0); return; }
+  bid -= a.nb_skr;
+  if (bid < a.nb_cs) { colsum_stage2_role(bid, a.cs, a.C, a.bias, a.C, 0, 0); return; }
+  bid -= a.nb_cs;
+  sum_rows_role(bid, a.partial, a.rows, a.cols, a.dfour, a.cols, 0, red);
 }
 
 // ---------------------------------------------------------------- masked MSE
@@ -1157,16 +1220,57 @@ __global__ void mse_bwd_kernel(const float* __restrict__ pred, const float* __re
 }
 
 // ---------------------------------------------------------------- CFM inputs / ODE axpy
-__global__ void cfm_inputs_kernel(const float* __restrict__ x1, const float* __restrict__ x0, const float* __restrict__ times,
-                                  float sigma, float* __restrict__ w, float* __restrict__ flow, int B, long per) {
+// block `bid` of a grid-stride pass of `nb` blocks over B * per elements
+VBX_DEV void cfm_inputs_role(int bid, int nb, const float* __restrict__ x1, const float* __restrict__ x0, const float* __restrict__ times,
+                             float sigma, float* __restrict__ w, float* __restrict__ flow, int B, long per) {
   const long total = (long)B * per;
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+  for (long i = bid * (long)blockDim.x + threadIdx.x; i < total; i += (long)nb * blockDim.x) {
     const float t = times[i / per];
     const float a = x0[i], c = x1[i];
     // w = (1 - (1 - sigma) t) x0 + t x1 ; flow = x1 - (1 - sigma) x0     (voicebox_pytorch.py:1408,1410)
     w[i] = (1.0f - (1.0f - sigma) * t) * a + t * c;
     flow[i] = c - (1.0f - sigma) * a;
   }
+}
+__global__ void cfm_inputs_kernel(const float* __restrict__ x1, const float* __restrict__ x0, const float* __restrict__ times,
+                                  float sigma, float* __restrict__ w, float* __restrict__ flow, int B, long per) {
+  cfm_inputs_role(blockIdx.x, gridDim.x, x1, x0, times, sigma, w, flow, B, per);
+}
+// Span mask and loss mask of the CFM objective (voicebox_pytorch.py:121-150, :1099), the torch expressions of masks.py operation by
+// operation in their own types: lengths = trunc(frac * N) (fp32 product), start = max((N - lengths) as fp32 * rand, 0),
+// end = start + lengths as fp32, cond = trunc(start) <= n < trunc(end); loss = cond & pad & (n < key_lens[b] - R).  One byte (0 / 1) per
+// frame; every product and sum is rounded on its own (no contraction: the torch ops are separate kernels).
+struct SpanMaskArgs {
+  const float *frac, *rand;
+  const uint8_t* pad;    // [B, N] or NULL
+  const int* key_lens;   // [B] (= R + frames of the row) or NULL
+  uint8_t *cond, *loss;  // [B, N]; loss may be NULL
+  int B, N, R;
+};
+VBX_DEV void span_masks_role(int bid, int nb, const SpanMaskArgs& a) {
+  const long total = (long)a.B * a.N;
+  for (long i = bid * (long)blockDim.x + threadIdx.x; i < total; i += (long)nb * blockDim.x) {
+    const int b = (int)(i / a.N), n = (int)(i - (long)b * a.N);
+    const long len = (long)__fmul_rn(a.frac[b], (float)a.N);
+    const float start = fmaxf(__fmul_rn((float)((long)a.N - len), a.rand[b]), 0.0f);
+    const float end = __fadd_rn(start, (float)len);
+    const bool c = (long)n >= (long)start && (long)n < (long)end;
+    a.cond[i] = c ? 1 : 0;
+    if (a.loss) {
+      bool l = c;
+      if (a.pad) l = l && a.pad[i] != 0;
+      if (a.key_lens) l = l && n < a.key_lens[b] - a.R;
+      a.loss[i] = l ? 1 : 0;
+    }
+  }
+}
+__global__ void span_masks_kernel(const SpanMaskArgs a) { span_masks_role(blockIdx.x, gridDim.x, a); }
+// vbx_cfm_inputs and the masks in one grid: blocks [0, nb_cfm) run the first, the rest the second
+__global__ void cfm_inputs_masks_kernel(const float* __restrict__ x1, const float* __restrict__ x0, const float* __restrict__ times,
+                                        float sigma, float* __restrict__ w, float* __restrict__ flow, int B, long per, int nb_cfm,
+                                        const SpanMaskArgs a) {
+  if ((int)blockIdx.x < nb_cfm) cfm_inputs_role(blockIdx.x, nb_cfm, x1, x0, times, sigma, w, flow, B, per);  // block-uniform
+  else span_masks_role(blockIdx.x - nb_cfm, gridDim.x - nb_cfm, a);
 }
 __global__ void axpy_dev_kernel(const float* __restrict__ y, const float* __restrict__ f, const float* __restrict__ coef,
                                 int idx, float* __restrict__ out, long n4) {
@@ -1924,6 +2028,56 @@ extern "C" int vbx_time_embed_bwd(const float* times, const float* w_sin, const 
   return 0;
 }
 
+extern "C" int vbx_time_embed_bwd_wsin(const float* times, const float* four, const float* dfour, float* dw_sin, int B, int D, void* stream) {
+  VBX_REQUIRE(times && four && dfour && dw_sin && D % 2 == 0, "vbx_time_embed_bwd_wsin: bad args");
+  hipLaunchKernelGGL(time_bwd_wsin_kernel, dim3(cdiv(D / 2, 256)), dim3(256), 0, ST, times, four, dfour, dw_sin, B, D);
+  VBX_LAUNCH_CHECK();
+  return 0;
+}
+extern "C" int vbx_colsum_f32_partials(const float* in, int M, int C, int ld, float* scratch, void* stream) {
+  VBX_REQUIRE(in && scratch && C % 4 == 0 && ld % 4 == 0, "vbx_colsum_f32_partials: C and ld must be multiples of 4");
+  hipLaunchKernelGGL(colsum_stage1<false>, dim3(cdiv(C, 64 * 4), CS_SLABS), dim3(256), 0, ST, (const void*)in, (long)M, C, (long)ld, scratch);
+  VBX_LAUNCH_CHECK();
+  return 0;
+}
+// The finishing kernels of vbx_model_backward_embed in two launches (include/vbx.h): group 1 = the dreg launch of vbx_convpos_bwd,
+// vbx_conv_wgrad_finalize and the first two launches of vbx_time_embed_bwd; group 2 = vbx_splitk_reduce, the second stage of
+// vbx_colsum_f32 and the third launch of vbx_time_embed_bwd.  vbx_time_embed_bwd_wsin is its fourth.
+extern "C" int vbx_embed_bwd_tail1(const float* dxs, float* dreg, int B, int Np, int R, int D, const float* wpart, int chunks, int ksize,
+                                   float* dw, float* db, const float* four, const float* pre, const float* dtemb, const float* w1,
+                                   float* dw1, float* db1, float* tscratch, int Th, void* stream) {
+  VBX_REQUIRE(dxs && wpart && dw && db && four && pre && dtemb && w1 && dw1 && db1 && tscratch && ksize < 63 && B > 0 && D > 0 && Th > 0 &&
+                  R >= 0 && (R == 0 || dreg), "vbx_embed_bwd_tail1: bad args");
+  EmbedTail1 a{};
+  a.nb_dreg = R > 0 ? cdiv((long)R * D, 256) : 0;
+  a.nb_conv = cdiv((long)D * 64, 256);
+  a.nb_w1 = cdiv((long)Th * D, 256);
+  a.nb_four = cdiv((long)cdiv(D, 64) * B * TB_SLICES, 4);
+  a.dxs = dxs; a.dreg = dreg; a.B = B; a.Np = Np; a.R = R; a.D = D;
+  a.wpart = wpart; a.chunks = chunks; a.ks = ksize; a.dw = dw; a.db = db;
+  a.four = four; a.pre = pre; a.dtemb = dtemb; a.w1 = w1; a.dw1 = dw1; a.db1 = db1; a.partial = tscratch + (long)B * D; a.Th = Th;
+  hipLaunchKernelGGL(embed_tail1_kernel, dim3(a.nb_dreg + a.nb_conv + a.nb_w1 + a.nb_four), dim3(256), 0, ST, a);
+  VBX_LAUNCH_CHECK();
+  return 0;
+}
+extern "C" int vbx_embed_bwd_tail2(const float* slabs, int splits, int M, int N, float* dst, const float* cs_scratch, int C, float* dbias,
+                                   float* tscratch, int B, int D, void* stream) {
+  VBX_REQUIRE(slabs && dst && cs_scratch && dbias && tscratch && splits >= 1 && M > 0 && N > 0 && C > 0 && B > 0 && D > 0,
+              "vbx_embed_bwd_tail2: bad args");
+  EmbedTail2 a{};
+  const long total = (long)M * N;
+  a.nb_skr = (int)((total + 255) / 256);
+  if (a.nb_skr > 4096) a.nb_skr = 4096;  // (vbx_splitk_reduce's grid)
+  a.nb_cs = cdiv(C, 256);
+  a.nb_rows = cdiv((long)B * D, 64);
+  a.slabs = slabs; a.splits = splits; a.M = M; a.N = N; a.dst = dst; a.dst_rows = M; a.dst_cols = N; a.dst_ld = N;
+  a.cs = cs_scratch; a.C = C; a.bias = dbias;
+  a.partial = tscratch + (long)B * D; a.rows = TB_SLICES; a.cols = (long)B * D; a.dfour = tscratch;
+  hipLaunchKernelGGL(embed_tail2_kernel, dim3(a.nb_skr + a.nb_cs + a.nb_rows), dim3(256), 0, ST, a);
+  VBX_LAUNCH_CHECK();
+  return 0;
+}
+
 extern "C" int vbx_adaln_proj_fwd(const float* temb, const void* w_bf16, const float* bias, float* ada, int B, int Th, int J,
                                   int group, void* stream) {
   VBX_REQUIRE(temb && w_bf16 && bias && ada && Th % 8 == 0, "vbx_adaln_proj_fwd: bad args");
@@ -2097,6 +2251,33 @@ extern "C" int vbx_cfm_inputs(const float* x1, const float* x0, const float* tim
   VBX_REQUIRE(x1 && x0 && times && w && flow, "vbx_cfm_inputs: null pointer");
   hipLaunchKernelGGL(cfm_inputs_kernel, dim3(grid_for((long)B * per_batch)), dim3(256), 0, ST, x1, x0, times, sigma, w, flow,
                      B, per_batch);
+  VBX_LAUNCH_CHECK();
+  return 0;
+}
+
+static int span_mask_args(const char* who, SpanMaskArgs& a, const float* frac, const float* rand, const uint8_t* pad, const int* key_lens,
+                          int R, int B, int N, uint8_t* cond, uint8_t* loss) {
+  VBX_REQUIRE(frac && rand && cond && B > 0 && N > 0 && R >= 0, "%s: bad mask arguments", who);
+  a.frac = frac; a.rand = rand; a.pad = pad; a.key_lens = key_lens; a.cond = cond; a.loss = loss; a.B = B; a.N = N; a.R = R;
+  return 0;
+}
+extern "C" int vbx_span_masks(const float* frac, const float* rand, const uint8_t* pad_mask, const int* key_lens, int R, int B, int N,
+                              uint8_t* cond_mask, uint8_t* loss_mask, void* stream) {
+  SpanMaskArgs a;
+  if (const int rc = span_mask_args("vbx_span_masks", a, frac, rand, pad_mask, key_lens, R, B, N, cond_mask, loss_mask)) return rc;
+  hipLaunchKernelGGL(span_masks_kernel, dim3(grid_for((long)B * N)), dim3(256), 0, ST, a);
+  VBX_LAUNCH_CHECK();
+  return 0;
+}
+extern "C" int vbx_cfm_inputs_masks(const float* x1, const float* x0, const float* times, float sigma, float* w, float* flow, int B,
+                                    long per_batch, const float* frac, const float* rand, const uint8_t* pad_mask, const int* key_lens,
+                                    int R, int N, uint8_t* cond_mask, uint8_t* loss_mask, void* stream) {
+  VBX_REQUIRE(x1 && x0 && times && w && flow, "vbx_cfm_inputs_masks: null pointer");
+  SpanMaskArgs a;
+  if (const int rc = span_mask_args("vbx_cfm_inputs_masks", a, frac, rand, pad_mask, key_lens, R, B, N, cond_mask, loss_mask)) return rc;
+  const int nb_cfm = grid_for((long)B * per_batch), nb_mask = grid_for((long)B * N);
+  hipLaunchKernelGGL(cfm_inputs_masks_kernel, dim3(nb_cfm + nb_mask), dim3(256), 0, ST, x1, x0, times, sigma, w, flow, B, per_batch,
+                     nb_cfm, a);
   VBX_LAUNCH_CHECK();
   return 0;
 }

@@ -39,6 +39,22 @@ VBX_DEV float skr_role(const vbx_skr_job& jb, long i4) {
   return sq;
 }
 
+// split-K slab reduction, one element per thread step: block `bid` of a grid-stride pass of `nb` blocks (vbx_splitk_reduce)
+VBX_DEV void splitk_reduce_role(int bid, int nb, const float* __restrict__ slabs, int splits, int M, int N, float* __restrict__ dst,
+                                int dst_rows, int dst_cols, long dst_ld, int rowmap, int F, int accumulate) {
+  const long total = (long)M * N;
+  for (long i = bid * (long)blockDim.x + threadIdx.x; i < total; i += (long)nb * blockDim.x) {
+    const int r = (int)(i / N), c = (int)(i - (long)r * N);
+    int dr = r;
+    if (rowmap == 1) dr = geglu_row_unmap(r, F);
+    if (dr < 0 || dr >= dst_rows || c >= dst_cols) continue;
+    float s = 0.f;
+    for (int k = 0; k < splits; k++) s += slabs[(long)k * total + i];
+    float* o = dst + (long)dr * dst_ld + c;
+    *o = accumulate ? (*o + s) : s;
+  }
+}
+
 // Block sum in a FIXED order (wave butterfly, then the wave partials in index order): the same value on every run.  Every thread of
 // the block must call it; the result is valid in thread 0.  wsum: >= blockDim.x / 64 floats of LDS.
 VBX_DEV float block_sum_fixed(float v, float* wsum) {

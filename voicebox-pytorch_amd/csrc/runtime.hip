@@ -437,6 +437,9 @@ struct WgoGuard {
   }
 };
 // LayerPlan::defer (below), for the stages outside the layers: a backward that defers indexes the copies of Acts::copy by layer
+// vbx_model_backward_embed groups its finishing kernels into two launches (vbx_embed_tail_grouped; on by default).  The grouped form
+// stores the bits of the separate launches, so the switch is a measuring and testing aid only.
+bool g_embed_grouped = true;
 bool defers(const vbx_model* m) { return m->defer_reduce && !m->gateloop && !m->unet && (m->plain_norm || m->adaln_factors); }
 // tests / debug: which copy of dxb / dqkv the most recent backward stage of this arena wrote (vbx_model_debug_ptr)
 struct { const void* act = nullptr; int dxb = 0, dqkv = 0; } g_last_copy;
@@ -1116,6 +1119,34 @@ extern "C" int vbx_model_backward_embed(const vbx_model* m, const vbx_io* io, vo
     }
     return guard.done(wgo_sync(guard.sd, st, wgrad_overlap::PT_EMBED_END, -1, d.L));
   }
+  if (g_embed_grouped && !d.Lc) {
+    // The same kernels with their finishers grouped by what they wait for (7 launches instead of 12 for a plain model):
+    //   conv backward (2 launches)  ->  group 1: d(registers), conv weight gradient, time MLP weight gradient and d(four) partials
+    //   embed weight-gradient GEMM, column-sum slabs of d(e)  ->  group 2: their reductions and the d(four) sum  ->  d(sin weights)
+    // (proj_in models keep the sequence below: their second split-K GEMM takes the slabs over before group 2 could run)
+    CK(vbx_convpos_bwd(a.e, P + G[VBX_P_CONVW], P + G[VBX_P_CONVB], io->attn_mask, a.dx, a.dpre, a.de, a.deb, a.wpart, nullptr, d.B, d.N,
+                       d.R, d.D, d.ks, stream));
+    CK(vbx_embed_bwd_tail1(a.dx, d.R ? Gd + G[VBX_P_REG] : nullptr, d.B, d.Np, d.R, d.D, a.wpart, vbx_convpos_bwd_chunks(d.B, d.N), d.ks,
+                           Gd + G[VBX_P_CONVW], Gd + G[VBX_P_CONVB], a.four, a.pre, a.dtemb, P + G[VBX_P_T1W], Gd + G[VBX_P_T1W],
+                           Gd + G[VBX_P_T1B], a.tscratch, d.Th, stream));
+    vbx_gemm_desc g{};
+    g.mode = VBX_GEMM_TN; g.epilogue = VBX_EPI_SPLITK; g.M = d.D; g.N = d.Ke; g.K = (int)d.M0; g.lda = d.D; g.ldb = d.Ke;
+    g.A = a.deb; g.B = a.embed_in; g.C = a.slabs; g.splits = wgrad_splits(d.D, d.Ke, d.M0);
+    { ProfScope ps("wgrad (separate)", st); CK(vbx_gemm(&g, st)); }
+    if (d.E) {  // (as below)
+      CK(gemm_nn_bf16(a.deb, d.D, w.embb + d.Din, d.Ke, (int)d.M0, d.E, d.D, a.demb, d.E, st));
+      if (hipMemsetAsync(Gd + G[VBX_P_CEMB], 0, (size_t)m->V1 * d.E * sizeof(float), st) != hipSuccess) {
+        vbx_set_error("vbx_model_backward_embed: memset of the embedding gradient failed");
+        return VBX_EINVAL;
+      }
+      CK(vbx_cond_emb_bwd(a.demb, d.E, io->cond_ids, io->T, io->drop_mask, io->null_id, Gd + G[VBX_P_CEMB], d.B, d.N, d.E, stream));
+    }
+    CK(vbx_colsum_f32_partials(a.de, (int)d.M0, d.D, d.D, a.cs_scratch, stream));
+    CK(vbx_embed_bwd_tail2(a.slabs, g.splits, d.D, d.Ke, Gd + G[VBX_P_EMBW], a.cs_scratch, d.D, Gd + G[VBX_P_EMBB], a.tscratch, d.B, d.D,
+                           stream));
+    CK(vbx_time_embed_bwd_wsin(io->times, a.four, a.tscratch, Gd + G[VBX_P_SINW], d.B, d.D, stream));
+    return guard.done(wgo_sync(guard.sd, st, wgrad_overlap::PT_EMBED_END, -1, d.L));
+  }
   CK(vbx_convpos_bwd(a.e, P + G[VBX_P_CONVW], P + G[VBX_P_CONVB], io->attn_mask, a.dx, a.dpre, a.de, a.deb, a.wpart,
                      d.R ? Gd + G[VBX_P_REG] : nullptr, d.B, d.N, d.R, d.D, d.ks, stream));
   CK(vbx_conv_wgrad_finalize(a.wpart, vbx_convpos_bwd_chunks(d.B, d.N), d.D, d.ks, Gd + G[VBX_P_CONVW], Gd + G[VBX_P_CONVB], stream));
@@ -1229,6 +1260,11 @@ extern "C" int vbx_wgrad_overlap(int on) {
   return 0;
 }
 extern "C" int vbx_wgrad_overlap_forks(void) { return g_wgo_forks; }
+extern "C" int vbx_embed_tail_grouped(int on) {
+  VBX_REQUIRE(on == 0 || on == 1, "vbx_embed_tail_grouped: 0 separate launches, 1 grouped");
+  g_embed_grouped = on != 0;
+  return 0;
+}
 extern "C" int vbx_wgrad_overlap_delay(float side_us, float main_us) {
   VBX_REQUIRE(side_us >= 0.f && side_us <= 2000.f && main_us >= 0.f && main_us <= 2000.f, "vbx_wgrad_overlap_delay: 0 .. 2000 us each");
   g_wgo_delay[0] = side_us;

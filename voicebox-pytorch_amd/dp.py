@@ -12,7 +12,7 @@ import torch
 import torch.distributed as dist
 
 from . import _lib
-from .masks import mask_from_frac_lengths, take_draw
+from .masks import take_draw
 
 
 def force_dist():
@@ -786,13 +786,13 @@ class TrainStep:
         x0 = torch.randn_like(x1) if x0 is None else x0.to(dev, torch.float32)
         times = take_draw("times")
         times = torch.rand((B,), dtype=torch.float32, device=dev) if times is None else times.to(dev, torch.float32)
-        wt, flow = torch.empty_like(x1), torch.empty_like(x1)
-        _lib.call("vbx_cfm_inputs", x1, x0.contiguous(), times.contiguous(), float(w.sigma), wt, flow, B, x1[0].numel(), st())
         vb.train()
         frac = take_draw("frac_lengths")
         if frac is None:
-            frac = torch.zeros((B,), device=dev).float().uniform_(*vb.frac_lengths_mask)
-        cond_mask = mask_from_frac_lengths(N, frac.to(dev))
+            frac = torch.empty((B,), dtype=torch.float32, device=dev).uniform_(*vb.frac_lengths_mask)
+        # a bool [B, N] padding mask joins the launch; any other (token resolution, another dtype) takes the torch expression below
+        pad_in = mask is not None and mask.dtype == torch.bool and tuple(mask.shape) == (B, N)
+        wt, flow, cond_mask, loss_mask = self._cfm_inputs_and_masks(x1, x0, times, frac.to(dev), mask if pad_in else None, key_lens)
         text = None
         if vb.condition_on_text:  # cond_drop_prob draw comes after the span-mask draws (voicebox_pytorch.py:1025,1040-1041)
             from .masks import prob_mask_like
@@ -808,7 +808,8 @@ class TrainStep:
                 m4 = mask.float()[:, None, :, None]
                 mask = torch.nn.functional.interpolate(m4, (N, 1), mode="bilinear")[:, 0, :, 0].to(torch.bool)
             text = (ids, vb.null_cond_id, drop, vb.null_cond)
-        loss_mask = cond_mask if mask is None else (cond_mask & mask)  # reduce_masks_with_and (:1099)
+        if mask is not None and not pad_in:
+            loss_mask = cond_mask & mask  # reduce_masks_with_and (:1099)
         if self.length_bucket > 0 and N % self.length_bucket and text is None:  # (token ids are resized to the frame count: :1055-1062)
             Nb = -(-N // self.length_bucket) * self.length_bucket
             pad = Nb - N
@@ -830,6 +831,27 @@ class TrainStep:
         eng.backward(self.gflat, gscale=None, on_stage=on_stage, adaln_factors=adaln_factors, sq_partials=sq)
         self._last_eng = eng
         return loss
+
+    def _cfm_inputs_and_masks(self, x1, x0, times, frac, mask, key_lens):
+        """(w, flow, cond_mask, loss_mask) of the CFM objective from the drawn numbers: w and flow (:1404-1410), the span mask
+        mask_from_frac_lengths(N, frac) with its `rand` draw (:146) and loss_mask = cond_mask & mask (reduce_masks_with_and, :1099) in ONE
+        launch, vbx_cfm_inputs_masks -- byte for byte what masks.py computes with a dozen torch launches."""
+        w, dev = self.wrapper, x1.device
+        B, N, _ = x1.shape
+        wt, flow = torch.empty_like(x1), torch.empty_like(x1)
+        rand = take_draw("rand")  # the draw of mask_from_frac_lengths, at the same place in the order of draws
+        rand = torch.empty((B,), dtype=torch.float32, device=dev).uniform_(0, 1) if rand is None else rand.to(dev).float()
+        frac = frac.float().contiguous()
+        pad = None
+        if mask is not None:
+            assert mask.dtype == torch.bool and tuple(mask.shape) == (B, N), (mask.dtype, tuple(mask.shape), (B, N))
+            pad = mask.contiguous()
+        cond_mask = torch.empty((B, N), dtype=torch.bool, device=dev)
+        loss_mask = cond_mask if pad is None else torch.empty((B, N), dtype=torch.bool, device=dev)
+        _lib.call("vbx_cfm_inputs_masks", x1, x0.contiguous(), times.contiguous(), float(w.sigma), wt, flow, B, x1[0].numel(), frac,
+                  rand.contiguous(), pad, key_lens if pad is not None else None, self.vb._cfg["R"], N, cond_mask,
+                  loss_mask if pad is not None else None, _lib.current_stream())
+        return wt, flow, cond_mask, loss_mask
 
     def _clip_adam_sharded(self, eng, lr, red):
         """grad_mode="shard": this rank holds the summed gradient of its chunks only (red.owned).  Global norm = sum over ranks of
