@@ -294,6 +294,41 @@ int vbx_attn_bwd_fused_lens(const void* q16, const void* k16, const void* qb, co
 #define VBX_PACK_ALIGN 128
 int vbx_attn_fwd_segs(const void* q16, const void* k16, const void* v16, const int* seg_start, const int* seg_klen,
                       const int* tile_seg, void* out16, void* out_bf16, float* lse, int H, int Mp, float scale, void* stream);
+/* ------------------------------------------------------------------ ragged waves (the front ends' lens=; wrapper(wave, wave_lens=))
+ * A padded batch of waves [B, T] whose row b holds lens[b] real samples.  The *_lens entries below are their plain siblings with one
+ * more argument, a DEVICE table const int* lens [B] in the units of that launch's INPUT, and the contract
+ *  - row b is read only at positions < lens[b] (what lies behind may be anything, NaN included);
+ *  - every padding (reflection, zero fill, pad1d's short-input rule, `extra`) is resolved about lens[b], by the arithmetic the plain
+ *    entry applies to T;
+ *  - outputs at or past the row's own output length are STORED as exactly 0.0 (never skipped: the buffers are not cleared);
+ *  - so row b of the result, up to its own output length, is bit-equal to the plain entry on the row alone, x[b, :lens[b]].
+ * The grids, the tiles and the pitches of the buffers are those of the plain entry at T; a workgroup wholly behind its row only
+ * stores zeros.  An entry of lens outside the range the plain entry accepts for T is CLAMPED into it by the kernel (the host
+ * wrappers validate or clamp before; no bound reaches an address unchecked).  Plain vector loads and stores, no atomics, no
+ * workgroup waits for another: reruns are bit-identical.  The plain entries launch the instantiations they always launched.
+ *   vbx_logmel_lens        frames_b = 1 + lens[b] / hop, reflection p >= len -> 2 (len - 1) - p; n_fft / 2 < lens[b] <= T.  A frame
+ *                          f >= frames_b is staged as zeros, as frames past the end always were (it shares a complex transform
+ *                          with frame f - 1 when f is odd).
+ *   vbx_melspec_lens       frames_b = 1 + (lens[b] + 2 pad - n_fft) / hop; max(pad + 1, n_fft - 2 pad) <= lens[b] <= T.
+ *   vbx_resample_lens      zero fill from lens[r] on; outputs from ceil(nw lens[r] / orig) on are 0.0; Lout = ceil(nw L / orig);
+ *                          1 <= lens[r] <= L.
+ *   vbx_seanet_conv0_lens  L_b = lens[b], 1 <= L_b <= T: Lz (the length pad1d reflects about) from L_b; rows from L_b on are 0.
+ *   vbx_seanet_conv_lens   L_b = lens[b], Lout_b = ceil(L_b / stride), `extra` and Lz from them; pad_left does not depend on L.  The
+ *                          second input (x2) is read at t < L_b; positions from Lout_b on are 0.  The NEXT launch takes the table
+ *                          ceil(lens / stride).
+ * vbx_lstm needs no such entry: the recurrence runs forward, steps below the row's length cannot see what follows them. */
+int vbx_logmel_lens(const float* audio, const int* lens, float* out, const float* window, const float* tw_re, const float* tw_im,
+                    const int* fb_start, const int* fb_len, const int* fb_off, const float* fb_w, int B, long T, int n_fft, int hop,
+                    int n_mels, int log_out, void* stream);
+int vbx_melspec_lens(const float* audio, const int* lens, float* out, const float* window, const float* tw_re, const float* tw_im,
+                     const int* fb_start, const int* fb_len, const int* fb_off, const float* fb_w, int B, long T, int n_fft, int hop,
+                     int pad, int n_mels, float mean, float inv_std, int channel_first, void* stream);
+int vbx_resample_lens(const float* x, const int* lens, float* y, const float* taps, const int* start, const int* len, int rows, long L,
+                      long Lout, int orig, int nw, int width, int K, int run_max, void* stream);
+int vbx_seanet_conv0_lens(const float* wave, const int* lens, const float* w, const float* bias, void* y_f16, int B, int T, int nf, int k,
+                          int causal, void* stream);
+int vbx_seanet_conv_lens(const void* x1_f16, const void* x2_f16, const int* lens, const void* w_f16, const float* bias, void* y, int B,
+                         int L, int C1, int C2, int Co, int k, int stride, int dilation, int elu1, int out_f32, int causal, void* stream);
 int vbx_attn_fwd_dropout(const void* q16, const void* k16, const void* v16, const uint8_t* mask, void* out16, void* out_bf16,
                          float* lse, int B, int H, int Np, float scale, const void* bits_rm, float p, void* stream);
 int vbx_attn_bwd_dropout(const void* q16, const void* k16, const void* qb, const void* kb, const void* v, const uint8_t* mask,

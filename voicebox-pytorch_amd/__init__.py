@@ -17,7 +17,8 @@ local checkpoint), BigVGANGenerator (BigVGAN's generator on the device, its anti
 shape; a local checkpoint and its config.json), HiFiGANMelCodec / mel_spectrogram (the mel front end those two generators were
 trained on -- Slaney filters, magnitude, ln, center=False -- in one kernel: the codec published HiFi-GAN / BigVGAN weights want),
 HubertWithKmeans (HuBERT base up to one encoder layer plus a k-means codebook on the device: waves into semantic token ids, the
-`wav2vec=` of ConditionalFlowMatcherWrapper; weights and centres are the user's, from local files).
+`wav2vec=` of ConditionalFlowMatcherWrapper; weights and centres are the user's, from local files), AudioDataset (a folder of audio
+files as a dataset of waves) and resample_lens (the length arithmetic of resample(lens=): ragged wave batches, `wave_lens=`).
 """
 from . import _lib  # noqa: F401
 
@@ -29,6 +30,8 @@ try:  # model classes need torch; keep `_lib` importable on its own
     from .duration import DurationPredictor  # noqa: F401
     from .codec import AudioEncoderDecoder, LogMelCodec, griffin_lim, resample, Resample, ResidualVQ, EncodecVocoCodec  # noqa: F401
     from .codec import HiFiGANMelCodec, mel_spectrogram  # noqa: F401
+    from .codec import resample_lens  # noqa: F401  (the per-row lengths behind resample(lens=): ragged waves, wave_lens.py)
+    from .data import AudioDataset  # noqa: F401
     from .vocos import VocosDecoder, VocosEncodecDecoder  # noqa: F401
     from .seanet import CausalSEANetDecoder, CausalSEANetEncoder, SEANetDecoder, SEANetEncoder  # noqa: F401
     from .hifigan import HiFiGANGenerator  # noqa: F401
@@ -43,7 +46,8 @@ try:  # model classes need torch; keep `_lib` importable on its own
                 "mask_from_start_end_indices", "prob_mask_like", "reduce_masks_with_and", "precise_mode", "set_precise", "precise_enabled",
                 "AudioEncoderDecoder", "LogMelCodec", "griffin_lim", "resample", "Resample", "VocosDecoder", "VocosEncodecDecoder", "ResidualVQ", "EncodecVocoCodec", "SEANetEncoder", "SEANetDecoder",
                 "CausalSEANetEncoder", "CausalSEANetDecoder", "HiFiGANGenerator", "BigVGANGenerator", "HubertWithKmeans", "HiFiGANMelCodec", "mel_spectrogram",
-                "maximum_path", "forward_sum_loss", "ForwardSumLoss", "Aligner", "aligner_attention", "lora", "ema_decay_at"]
+                "maximum_path", "forward_sum_loss", "ForwardSumLoss", "Aligner", "aligner_attention", "lora", "ema_decay_at", "resample_lens",
+                "AudioDataset"]
 except ModuleNotFoundError as _e:  # pragma: no cover - only while the package is being bootstrapped
     if "masks" not in str(_e) and "model" not in str(_e):
         raise

@@ -75,6 +75,11 @@ _PROTOS = {
     "vbx_copy_cols_f32": [P, I, P, L, I, P],
     "vbx_logmel": [P, P, P, P, P, P, P, P, P, I, L, I, I, I, I, P],
     "vbx_melspec": [P, P, P, P, P, P, P, P, P, I, L, I, I, I, I, F, F, I, P],
+    "vbx_logmel_lens": [P, P, P, P, P, P, P, P, P, P, I, L, I, I, I, I, P],
+    "vbx_melspec_lens": [P, P, P, P, P, P, P, P, P, P, I, L, I, I, I, I, F, F, I, P],
+    "vbx_resample_lens": [P, P, P, P, P, P, I, L, L, I, I, I, I, I, P],
+    "vbx_seanet_conv0_lens": [P, P, P, P, P, I, I, I, I, I, P],
+    "vbx_seanet_conv_lens": [P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, P],
     "vbx_mel_to_mag": [P, P, P, I, I, I, I, I, P],
     "vbx_griffinlim_lds_bytes": [I, I, I],
     "vbx_griffinlim": [P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, F, P],

@@ -32,6 +32,7 @@ from . import _lib
 from ._packing import PackedWeights, read_checkpoint, tensors_key
 from ._wnconv import read_config
 from .masks import take_draw
+from .wave_lens import device_lens, map_lens, resample_lens, zero_dead_frames  # noqa: F401  (resample_lens: part of this module's API)
 
 
 class AudioEncoderDecoder(nn.Module):
@@ -272,7 +273,8 @@ def _resample_tables(orig, new, lpw, rolloff, method, beta, device):
     return hit
 
 
-def resample(waveform, orig_freq, new_freq, lowpass_filter_width=6, rolloff=0.99, resampling_method="sinc_interp_hann", beta=None):
+def resample(waveform, orig_freq, new_freq, lowpass_filter_width=6, rolloff=0.99, resampling_method="sinc_interp_hann", beta=None,
+             lens=None):
     """torchaudio.functional.resample on the device (csrc/resample.hip, one launch): waveform [..., L] at orig_freq -> [...,
     ceil(new L / orig)] at new_freq (orig : new reduced by their gcd), bandlimited interpolation with the filter bank of
     resample_bank.  PARITY UNPINNED: torchaudio is not a dependency and no vector of it is committed; this follows its published
@@ -280,8 +282,19 @@ def resample(waveform, orig_freq, new_freq, lowpass_filter_width=6, rolloff=0.99
 
     Leading dimensions are flattened to rows and restored.  Compute is fp32: other floating dtypes are converted on the way in and
     the result is converted back.  Equal rates return `waveform` itself and launch nothing.  Banks are cached per (rates, filter
-    arguments, device).  Runs only on the GPU, like griffin_lim; no gradient is taken through it."""
+    arguments, device).  Runs only on the GPU, like griffin_lim; no gradient is taken through it.
+
+    lens (not a torchaudio keyword): per-row sample counts of a padded batch [B, L] or [B, 1, L], 1 <= len_b <= L (a list or CPU
+    tensor is validated, a device tensor clamped) -- row b is resampled as the row alone: zeros from len_b on instead of whatever
+    the padding holds, bit-equal to resample(waveform[b:b+1, :len_b]) up to resample_lens(lens, orig_freq, new_freq)[b] and exactly
+    0.0 past it (vbx_resample_lens)."""
     orig, new = _check_resample_args(orig_freq, new_freq, lowpass_filter_width, resampling_method)
+    if lens is not None:
+        if waveform.ndim not in (2, 3) or (waveform.ndim == 3 and waveform.shape[1] != 1):
+            raise ValueError(f"resample(lens=) takes a padded batch (batch, samples) or (batch, 1, samples), got {tuple(waveform.shape)}")
+        if waveform.shape[-1] < 1:
+            raise ValueError("resample(lens=): empty waveform")
+        lens = device_lens(lens, waveform.shape[0], waveform.shape[-1], 1, waveform.device, "resample")
     if orig == new:
         return waveform
     if not waveform.is_floating_point():
@@ -296,7 +309,10 @@ def resample(waveform, orig_freq, new_freq, lowpass_filter_width=6, rolloff=0.99
     Lout = -(-new * L // orig)
     x = waveform.detach().reshape(-1, L).to(torch.float32).contiguous()
     y = torch.empty(x.shape[0], Lout, dtype=torch.float32, device=x.device)
-    if y.numel():
+    if y.numel() and lens is not None:
+        _lib.call("vbx_resample_lens", x, lens, y, taps, start, length, x.shape[0], L, Lout, orig, new, width, K, run_max,
+                  _lib.current_stream())
+    elif y.numel():
         _lib.call("vbx_resample", x, y, taps, start, length, x.shape[0], L, Lout, orig, new, width, K, run_max, _lib.current_stream())
     return y.reshape(*lead, Lout).to(waveform.dtype)
 
@@ -312,9 +328,9 @@ class Resample(nn.Module):
         self.orig_freq, self.new_freq, self.resampling_method = orig_freq, new_freq, resampling_method
         self.lowpass_filter_width, self.rolloff, self.beta = lowpass_filter_width, rolloff, beta
 
-    def forward(self, waveform):
+    def forward(self, waveform, lens=None):
         return resample(waveform, self.orig_freq, self.new_freq, self.lowpass_filter_width, self.rolloff, self.resampling_method,
-                        self.beta)
+                        self.beta, lens=lens)
 
 
 class LogMelCodec(AudioEncoderDecoder):
@@ -358,13 +374,21 @@ class LogMelCodec(AudioEncoderDecoder):
     def sampling_rate(self):
         return self._sampling_rate
 
-    def encode(self, audio):
+    def frame_lens(self, sample_lens):
+        """frames of a row of that many samples, 1 + l // hop_length: a list, a CPU tensor or a device tensor; the same kind back"""
+        return map_lens(sample_lens, lambda l: 1 + l // self.hop_length)
+
+    def encode(self, audio, lens=None):
+        """lens: per-row sample counts of a padded batch, n_fft // 2 < len_b <= T (a list or CPU tensor is validated, a device tensor
+        clamped): row b is the row alone -- bit-equal to encode(audio[b:b+1, :len_b])[0] up to frame_lens(lens)[b], 0.0 past it."""
         if audio.ndim == 3 and audio.shape[1] == 1:
             audio = audio[:, 0]
         if audio.ndim != 2:
             raise ValueError(f"encode takes waves (batch, samples), got {tuple(audio.shape)}")
         if audio.shape[1] <= self.n_fft // 2:
             raise RuntimeError(f"reflect padding of n_fft // 2 = {self.n_fft // 2} samples needs a longer wave (got {audio.shape[1]} samples)")
+        if lens is not None:  # checked (host values) or clamped (a device tensor) before anything else
+            lens = device_lens(lens, audio.shape[0], audio.shape[1], self.n_fft // 2 + 1, audio.device, "LogMelCodec.encode")
         if audio.device.type != "cuda":
             raise _lib.VbxError(f"LogMelCodec.encode runs only on an MI355X (gfx950) through libvbx_hip.so; the wave is on '{audio.device}'")
         if self.window.device != audio.device:
@@ -372,6 +396,10 @@ class LogMelCodec(AudioEncoderDecoder):
         audio = audio.detach().to(torch.float32).contiguous()
         B, T = audio.shape
         out = torch.empty(B, 1 + T // self.hop_length, self.n_mels, dtype=torch.float32, device=audio.device)
+        if lens is not None:
+            _lib.call("vbx_logmel_lens", audio, lens, out, self.window, self.tw_re, self.tw_im, self.fb_start, self.fb_len, self.fb_off,
+                      self.fb_w, B, T, self.n_fft, self.hop_length, self.n_mels, int(bool(self.log)), _lib.current_stream())
+            return out
         _lib.call("vbx_logmel", audio, out, self.window, self.tw_re, self.tw_im, self.fb_start, self.fb_len, self.fb_off, self.fb_w,
                   B, T, self.n_fft, self.hop_length, self.n_mels, int(bool(self.log)), _lib.current_stream())
         return out
@@ -486,8 +514,14 @@ def _melspec_tables(n_fft, num_mels, sampling_rate, win_size, fmin, fmax, device
     return hit
 
 
-def _melspec(y, n_fft, num_mels, sampling_rate, hop_size, win_size, fmin, fmax, mean, std, channel_first, who):
-    """one launch of vbx_melspec over waves [B, T] or [B, 1, T]; the arguments are already checked"""
+def melspec_min_samples(n_fft, hop_size):
+    """the shortest wave vbx_melspec takes: longer than the reflect pad, and one whole frame with it"""
+    pad = melspec_pad(n_fft, hop_size)
+    return max(pad + 1, n_fft - 2 * pad)
+
+
+def _melspec(y, n_fft, num_mels, sampling_rate, hop_size, win_size, fmin, fmax, mean, std, channel_first, who, lens=None):
+    """one launch of vbx_melspec (lens: vbx_melspec_lens) over waves [B, T] or [B, 1, T]; the arguments are already checked"""
     if y.ndim == 3 and y.shape[1] == 1:
         y = y[:, 0]
     if y.ndim != 2 or not y.is_floating_point():
@@ -498,13 +532,18 @@ def _melspec(y, n_fft, num_mels, sampling_rate, hop_size, win_size, fmin, fmax, 
         raise RuntimeError(f"reflect padding of (n_fft - hop_size) / 2 = {pad} samples needs a longer wave (got {T} samples)")
     if T + 2 * pad < n_fft:
         raise RuntimeError(f"{T} samples and {pad} of padding on each side do not fill one frame of n_fft = {n_fft}")
+    if lens is not None:  # checked (host values) or clamped (a device tensor) before anything else
+        lens = device_lens(lens, B, T, melspec_min_samples(n_fft, hop_size), y.device, who)
     if y.device.type != "cuda":
         raise _lib.VbxError(f"{who} runs only on an MI355X (gfx950) through libvbx_hip.so; the wave is on '{y.device}'")
     tables = _melspec_tables(n_fft, num_mels, sampling_rate, win_size, fmin, fmax, y.device)
     y = y.detach().to(torch.float32).contiguous()
     frames = melspec_frames(T, n_fft, hop_size)
     out = torch.empty((B, num_mels, frames) if channel_first else (B, frames, num_mels), dtype=torch.float32, device=y.device)
-    if B:
+    if B and lens is not None:
+        _lib.call("vbx_melspec_lens", y, lens, out, *tables, B, T, n_fft, hop_size, pad, num_mels, 0.0 if mean is None else float(mean),
+                  1.0 if std is None else 1.0 / float(std), int(channel_first), _lib.current_stream())
+    elif B:
         _lib.call("vbx_melspec", y, out, *tables, B, T, n_fft, hop_size, pad, num_mels, 0.0 if mean is None else float(mean),
                   1.0 if std is None else 1.0 / float(std), int(channel_first), _lib.current_stream())
     return out
@@ -597,13 +636,19 @@ class HiFiGANMelCodec(AudioEncoderDecoder):
     def sampling_rate(self):
         return self._sampling_rate
 
-    def _encode(self, audio, mean, std):
+    def _encode(self, audio, mean, std, lens=None):
         return _melspec(audio, self.n_fft, self.num_mels, self._sampling_rate, self.hop_size, self.win_size, self.fmin, self.fmax, mean,
-                        std, False, "HiFiGANMelCodec.encode")
+                        std, False, "HiFiGANMelCodec.encode", lens=lens)
 
-    def encode(self, audio):
-        """waves [B, T] or [B, 1, T] -> latents fp32 [B, frames, num_mels]; one launch, no host synchronisation"""
-        return self._encode(audio, self.mean, self.std)
+    def frame_lens(self, sample_lens):
+        """melspec_frames of each length: a list, a CPU tensor or a device tensor; the same kind back"""
+        return map_lens(sample_lens, lambda l: melspec_frames(l, self.n_fft, self.hop_size))
+
+    def encode(self, audio, lens=None):
+        """waves [B, T] or [B, 1, T] -> latents fp32 [B, frames, num_mels]; one launch, no host synchronisation.  lens: per-row
+        sample counts of a padded batch, melspec_min_samples(n_fft, hop_size) <= len_b <= T (a list or CPU tensor is validated, a
+        device tensor clamped): row b is the row alone up to frame_lens(lens)[b], exactly 0.0 (not the log floor) past it."""
+        return self._encode(audio, self.mean, self.std, lens=lens)
 
     def fit_normalization(self, waves):
         """sets mean / std to the mean and (population) standard deviation of every plain log-mel value of `waves`, an iterable of
@@ -897,13 +942,30 @@ class EncodecVocoCodec(AudioEncoderDecoder):
         table = self.rvq if self.feature_rvq is None else self.feature_rvq
         return table._gather(codes, codes_qn=True, channel_first=True, check=check, who="EncodecVocoCodec.codes_to_features")
 
-    def encode(self, audio):
+    def frame_lens(self, sample_lens):
+        """the encoder's frame counts: a list, a CPU tensor or a device tensor; the same kind back"""
+        if not callable(getattr(self.encoder, "frame_lens", None)):
+            raise NotImplementedError(f"EncodecVocoCodec.frame_lens needs an encoder with frame_lens (SEANetEncoder), got "
+                                      f"{type(self.encoder).__name__}")
+        return self.encoder.frame_lens(sample_lens)
+
+    def encode(self, audio, lens=None):
+        """lens: per-row sample counts of a padded batch, 1 <= len_b <= T, handed to the encoder (SEANetEncoder.forward(lens=)): row b
+        is the row alone up to frame_lens(lens)[b]; the quantizer is per frame, and the frames past it are zero-filled after it."""
         if self.encoder is None:
             raise NotImplementedError("EncodecVocoCodec.encode needs an encoder (audio [B, T] -> latents [B, frames, dim]): EnCodec's "
                                       "SEANet encoder is not built; pass encoder=")
+        if lens is None:
+            with torch.no_grad():
+                z = self.encoder(audio)
+            return self.codes_to_latents(self.decode_to_codes(z), check=False)
+        self.frame_lens([1])  # the encoder must serve lengths: NotImplementedError before anything is launched
+        T = audio.shape[-1]
+        lens = device_lens(lens, audio.shape[0], T, 1, audio.device, "EncodecVocoCodec.encode")
         with torch.no_grad():
-            z = self.encoder(audio)
-        return self.codes_to_latents(self.decode_to_codes(z), check=False)
+            z = self.encoder(audio, lens=lens)
+            lat = self.codes_to_latents(self.decode_to_codes(z), check=False)
+            return zero_dead_frames(lat, self.frame_lens(lens))
 
     def decode(self, latents):
         """the reference loops over the batch and stacks (voicebox_pytorch.py:577-584); the same arithmetic, batched"""

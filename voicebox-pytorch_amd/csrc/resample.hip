@@ -22,10 +22,13 @@ constexpr int RS_LDS_FLOATS = 16384;   // 64 KiB: the span of a tile, and so the
 // frames of orig input samples that T consecutive outputs can touch beyond their first one, whatever phase the tile starts at
 inline long rs_extra_frames(int T, int nw) { return ((long)nw - 1 + T - 1) / nw; }
 
+// LENS (vbx_resample_lens, include/vbx.h "ragged waves"): row r is the wave of lens[r] samples it would be alone -- staged as zeros
+// from lens[r] on, its outputs from ceil(nw lens[r] / orig) on stored as 0.0.
+template <bool LENS>
 __global__ __launch_bounds__(RS_THREADS) void resample_kernel(const float* __restrict__ x, float* __restrict__ y,
                                                               const float* __restrict__ taps, const int* __restrict__ start,
                                                               const int* __restrict__ len, int rows, long L, long Lout, int orig,
-                                                              int nw, int width, int K, int run_max, int T) {
+                                                              int nw, int width, int K, int run_max, int T, const int* __restrict__ lens) {
   extern __shared__ float xs[];
   const int tid = threadIdx.x;
   const long o0 = (long)blockIdx.x * T;                       // first output sample of the tile
@@ -36,9 +39,19 @@ __global__ __launch_bounds__(RS_THREADS) void resample_kernel(const float* __res
   const long in0 = q_lo * orig - width;                       // input sample held by xs[0]; negative at the head of a row
   for (int row = blockIdx.y; row < rows; row += gridDim.y) {
     const float* xr = x + (long)row * L;
+    long Lb = L, Lob = Lout;
+    if (LENS) {
+      const long l = lens[row];
+      Lb = l < 1 ? 1 : (l > L ? L : l);
+      Lob = (Lb * nw + orig - 1) / orig;  // <= Lout: the host checked Lout = ceil(nw L / orig)
+      if (o0 >= Lob) {  // a tile wholly behind the row (the same for every thread: no barrier is skipped by some)
+        for (int j = tid; j < nout; j += RS_THREADS) y[(long)row * Lout + o0 + j] = 0.f;
+        continue;
+      }
+    }
     for (int i = tid; i < span; i += RS_THREADS) {
       const long g = in0 + i;
-      xs[i] = (g >= 0 && g < L) ? xr[g] : 0.f;
+      xs[i] = (g >= 0 && g < Lb) ? xr[g] : 0.f;
     }
     __syncthreads();
     for (int j = tid; j < nout; j += RS_THREADS) {
@@ -58,7 +71,7 @@ __global__ __launch_bounds__(RS_THREADS) void resample_kernel(const float* __res
         acc = fmaf(h3, xp[i + 3], acc);
       }
       for (; i < n; i++) acc = fmaf(hp[(long)i * nw], xp[i], acc);
-      y[(long)row * Lout + o0 + j] = acc;
+      y[(long)row * Lout + o0 + j] = (LENS && o0 + j >= Lob) ? 0.f : acc;
     }
     __syncthreads();
   }
@@ -68,7 +81,7 @@ __global__ __launch_bounds__(RS_THREADS) void resample_kernel(const float* __res
 
 extern "C" int vbx_resample_max_taps(void) { return RS_LDS_FLOATS; }
 
-extern "C" int vbx_resample(const float* x, float* y, const float* taps, const int* start, const int* len, int rows, long L, long Lout,
+static int resample_launch(const int* lens, const float* x, float* y, const float* taps, const int* start, const int* len, int rows, long L, long Lout,
                             int orig, int nw, int width, int K, int run_max, void* stream) {
   VBX_REQUIRE(x && y && taps && start && len && rows > 0, "vbx_resample: bad args");
   VBX_REQUIRE(L > 0 && L <= 2147483647L, "vbx_resample: rows of 1 .. 2^31 - 1 samples (got %ld)", L);
@@ -81,8 +94,26 @@ extern "C" int vbx_resample(const float* x, float* y, const float* taps, const i
   const long span = rs_extra_frames(T, nw) * orig + K;  // T = 1: no extra frame, K floats
   const long tiles = (Lout + T - 1) / T;
   VBX_REQUIRE(span <= RS_LDS_FLOATS && tiles <= 2147483647L, "vbx_resample: too many output tiles (%ld)", tiles);
-  hipLaunchKernelGGL(resample_kernel, dim3((unsigned)tiles, rows < 65535 ? rows : 65535), dim3(RS_THREADS), (size_t)span * sizeof(float),
-                     (hipStream_t)stream, x, y, taps, start, len, rows, L, Lout, orig, nw, width, K, run_max, T);
+  const dim3 grid((unsigned)tiles, rows < 65535 ? rows : 65535);
+  if (lens) {
+    VBX_REQUIRE(Lout == (L * nw + orig - 1) / orig, "vbx_resample_lens: Lout must be ceil(nw * L / orig) (got %ld)", Lout);
+    hipLaunchKernelGGL(resample_kernel<true>, grid, dim3(RS_THREADS), (size_t)span * sizeof(float), (hipStream_t)stream, x, y, taps, start,
+                       len, rows, L, Lout, orig, nw, width, K, run_max, T, lens);
+  } else {
+    hipLaunchKernelGGL(resample_kernel<false>, grid, dim3(RS_THREADS), (size_t)span * sizeof(float), (hipStream_t)stream, x, y, taps, start,
+                       len, rows, L, Lout, orig, nw, width, K, run_max, T, (const int*)nullptr);
+  }
   VBX_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int vbx_resample(const float* x, float* y, const float* taps, const int* start, const int* len, int rows, long L, long Lout,
+                            int orig, int nw, int width, int K, int run_max, void* stream) {
+  return resample_launch(nullptr, x, y, taps, start, len, rows, L, Lout, orig, nw, width, K, run_max, stream);
+}
+
+extern "C" int vbx_resample_lens(const float* x, const int* lens, float* y, const float* taps, const int* start, const int* len, int rows,
+                                 long L, long Lout, int orig, int nw, int width, int K, int run_max, void* stream) {
+  VBX_REQUIRE(lens, "vbx_resample_lens: lens is NULL (vbx_resample is the entry without lengths)");
+  return resample_launch(lens, x, y, taps, start, len, rows, L, Lout, orig, nw, width, K, run_max, stream);
 }

@@ -43,6 +43,8 @@ struct SnConv {
   const float* bias;  // [Co]
   void* y;            // [B, Lout, Co] fp16 or fp32
   int L, Lout, C1, C2, Co, k, stride, dil, pad_left, Lz, elu1, out_f32, TT, Ktot;
+  const int* lens;    // [B] or NULL (the LENS instantiations only): the rows' own input lengths, see "ragged waves" in include/vbx.h
+  int causal;
 };
 
 VBX_DEV float sn_elu(float x) { return x > 0.f ? x : expm1f(x); }
@@ -66,13 +68,46 @@ VBX_DEV int sn_src(int q, int pad_left, int L, int Lz) {
   return i < L ? i : -1;
 }
 
+// SConv1d's padding: (k_eff - stride) split with the larger half on the left -- causal: all of it on the left --, `extra` on the
+// right so that the last window is whole; Lz is the length pad1d reflects about (sn_src)
+struct SnPads { int left, Lz; };
+__host__ __device__ inline SnPads sn_pads(int k, int stride, int dil, int L, int Lout, int causal) {
+  const int total = (k - 1) * dil + 1 - stride, extra = Lout * stride - L;
+  const int right = causal ? 0 : total / 2, left = total - right, maxpad = left > right + extra ? left : right + extra;
+  return SnPads{left, L > maxpad ? L : maxpad + 1};
+}
+
+// LENS (vbx_seanet_conv_lens): L, Lout, Lz are the row's own, by the arithmetic of sn_pads from lens[b]; p.L / p.Lout stay the
+// pitches of the buffers.  The row is read below its length only and positions from its Lout on are stored as zeros.
 // A workgroup owns TT consecutive output positions of one batch row and all Co channels: it stages the input span ((TT - 1) * stride
 // + k_eff positions, channel-last, padding resolved, ELU applied) and the second input's TT positions, then runs the product.
-template <int MG>
+template <int MG, bool LENS = false>
 __global__ __launch_bounds__(256) void seanet_conv_kernel(SnConv p) {
   extern __shared__ __attribute__((aligned(16))) u16 sn_lds[];
   const int tid = threadIdx.x;
   const int b = blockIdx.y, t0 = blockIdx.x * p.TT;
+  int L = p.L, Lout = p.Lout, Lz = p.Lz;
+  if (LENS) {
+    const int l = p.lens[b];
+    L = l < 1 ? 1 : (l > p.L ? p.L : l);
+    Lout = (L + p.stride - 1) / p.stride;
+    Lz = sn_pads(p.k, p.stride, p.dil, L, Lout, p.causal).Lz;
+    if (t0 >= Lout) {  // a tile wholly behind the row
+      const int n = (p.Lout - t0 < p.TT ? p.Lout - t0 : p.TT) * p.Co;
+      const long o = ((long)b * p.Lout + t0) * p.Co;
+      const int esz = p.out_f32 ? 4 : 2;
+      if ((p.Co * esz) % 16 == 0 && (reinterpret_cast<size_t>(p.y) & 15) == 0) {  // whole 16-byte pieces from an aligned start
+        uint4* dst = reinterpret_cast<uint4*>(reinterpret_cast<char*>(p.y) + o * esz);
+        for (int e = tid; e < n * esz / 16; e += 256) dst[e] = make_uint4(0u, 0u, 0u, 0u);
+      } else {
+        for (int e = tid; e < n; e += 256) {
+          if (p.out_f32) reinterpret_cast<float*>(p.y)[o + e] = 0.f;
+          else reinterpret_cast<u16*>(p.y)[o + e] = 0;
+        }
+      }
+      return;
+    }
+  }
   const int ld1 = p.C1 + SN_PADH, ld2 = p.C2 + SN_PADH;
   const int keff = (p.k - 1) * p.dil + 1;
   const int span = (p.TT - 1) * p.stride + keff;
@@ -82,13 +117,13 @@ __global__ __launch_bounds__(256) void seanet_conv_kernel(SnConv p) {
   {
     const int c8 = p.C1 >> 3;
     const u16* xb = p.x1 + (long)b * p.L * p.C1;
-    const int padded = (p.Lout - 1) * p.stride + keff;  // = L + padding_total + extra
+    const int padded = (Lout - 1) * p.stride + keff;  // = L + padding_total + extra
     for (int e = tid; e < span * c8; e += 256) {
       const int pos = e / c8, c = (e - pos * c8) * 8;
       const int q = t0 * p.stride + pos;
       uint4 v = zero;
       if (q < padded) {
-        const int i = sn_src(q, p.pad_left, p.L, p.Lz);
+        const int i = sn_src(q, p.pad_left, L, Lz);
         if (i >= 0) {
           v = *reinterpret_cast<const uint4*>(xb + (long)i * p.C1 + c);
           if (p.elu1) v = sn_elu8(v);
@@ -103,7 +138,7 @@ __global__ __launch_bounds__(256) void seanet_conv_kernel(SnConv p) {
     for (int e = tid; e < p.TT * c8; e += 256) {
       const int pos = e / c8, c = (e - pos * c8) * 8;
       const int t = t0 + pos;
-      *reinterpret_cast<uint4*>(s2 + pos * ld2 + c) = t < p.L ? *reinterpret_cast<const uint4*>(xb + (long)t * p.C2 + c) : zero;
+      *reinterpret_cast<uint4*>(s2 + pos * ld2 + c) = t < L ? *reinterpret_cast<const uint4*>(xb + (long)t * p.C2 + c) : zero;
     }
   }
   __syncthreads();
@@ -123,6 +158,11 @@ __global__ __launch_bounds__(256) void seanet_conv_kernel(SnConv p) {
       const int t = t0 + m;
       if (t >= p.Lout) return;
       const long o = ((long)b * p.Lout + t) * p.Co + n;
+      if (LENS && t >= Lout) {
+        if (p.out_f32) reinterpret_cast<float*>(p.y)[o] = 0.f;
+        else reinterpret_cast<u16*>(p.y)[o] = 0;
+        return;
+      }
       if (p.out_f32) reinterpret_cast<float*>(p.y)[o] = v + bv;
       else reinterpret_cast<u16*>(p.y)[o] = f32_to_f16(v + bv);
     };
@@ -131,9 +171,10 @@ __global__ __launch_bounds__(256) void seanet_conv_kernel(SnConv p) {
 }
 
 // the first convolution: one thread per (position, eight output channels), the k taps as an fmaf chain on the bias in tap order
+template <bool LENS>
 __global__ __launch_bounds__(256) void seanet_conv0_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                            const float* __restrict__ bias, u16* __restrict__ y, int T, int nf, int k,
-                                                           int pad_left, int Lz) {
+                                                           int pad_left, int Lz, const int* __restrict__ lens, int causal) {
   __shared__ float sw[SN_MAX_K * 64 + 64];  // [k][nf] taps, then the bias
   const int tid = threadIdx.x, b = blockIdx.y;
   for (int e = tid; e < k * nf; e += 256) {
@@ -147,11 +188,21 @@ __global__ __launch_bounds__(256) void seanet_conv0_kernel(const float* __restri
   if (e >= (long)T * groups) return;
   const int pos = (int)(e / groups), c0 = (int)(e - (long)pos * groups) * 8;
   const float* xb = x + (long)b * T;
+  int Tb = T;
+  if (LENS) {  // the row's own length and the length its padding reflects about; past it the row is stored as zeros
+    const int l = lens[b];
+    Tb = l < 1 ? 1 : (l > T ? T : l);
+    Lz = sn_pads(k, 1, 1, Tb, Tb, causal).Lz;
+    if (pos >= Tb) {
+      *reinterpret_cast<uint4*>(y + ((long)b * T + pos) * nf + c0) = make_uint4(0u, 0u, 0u, 0u);
+      return;
+    }
+  }
   float acc[8];
 #pragma unroll
   for (int j = 0; j < 8; j++) acc[j] = sw[k * nf + c0 + j];
   for (int tap = 0; tap < k; tap++) {
-    const int i = sn_src(pos + tap, pad_left, T, Lz);
+    const int i = sn_src(pos + tap, pad_left, Tb, Lz);
     const float xv = i >= 0 ? xb[i] : 0.f;
 #pragma unroll
     for (int j = 0; j < 8; j++) acc[j] = fmaf(sw[tap * nf + c0 + j], xv, acc[j]);
@@ -367,15 +418,6 @@ int sn_convtr_tile(int C) {
   return sn_pick_tile([=](int TT) { return sn_convtr_lds(TT, C); });
 }
 
-// SConv1d's padding: (k_eff - stride) split with the larger half on the left -- causal: all of it on the left --, `extra` on the
-// right so that the last window is whole; Lz is the length pad1d reflects about (sn_src)
-struct SnPads { int left, Lz; };
-SnPads sn_pads(int k, int stride, int dil, int L, int Lout, int causal) {
-  const int total = (k - 1) * dil + 1 - stride, extra = Lout * stride - L;
-  const int right = causal ? 0 : total / 2, left = total - right, maxpad = left > right + extra ? left : right + extra;
-  return SnPads{left, L > maxpad ? L : maxpad + 1};
-}
-
 int sn_lstm_check(const SnLstm& p) {
   VBX_REQUIRE(p.xproj && p.w0 && p.h0 && p.c && p.x && p.y16, "vbx_lstm: null operand");
   VBX_REQUIRE(p.layers == 1 || (p.layers == 2 && p.w1 && p.bias1 && p.h1), "vbx_lstm: 1 or 2 layers, the second with its operands");
@@ -397,7 +439,7 @@ extern "C" int vbx_seanet_conv_tile(int C1, int C2, int k, int stride, int dilat
   return TT;
 }
 
-extern "C" int vbx_seanet_conv_c(const void* x1_f16, const void* x2_f16, const void* w_f16, const float* bias, void* y, int B, int L, int C1,
+static int sn_conv_launch(const int* lens, const void* x1_f16, const void* x2_f16, const void* w_f16, const float* bias, void* y, int B, int L, int C1,
                                  int C2, int Co, int k, int stride, int dilation, int elu1, int out_f32, int causal, void* stream) {
   VBX_REQUIRE(x1_f16 && w_f16 && bias && y && (x2_f16 || !C2), "vbx_seanet_conv: null operand");
   VBX_REQUIRE(B >= 1 && B <= 65535 && L >= 1 && Co >= 1 && Co <= 4096, "vbx_seanet_conv: need B in 1 .. 65535, L >= 1, Co in 1 .. 4096");
@@ -411,12 +453,30 @@ extern "C" int vbx_seanet_conv_c(const void* x1_f16, const void* x2_f16, const v
   const SnPads pads = sn_pads(k, stride, dilation, L, p.Lout, causal);
   p.pad_left = pads.left, p.Lz = pads.Lz;
   p.elu1 = elu1 ? 1 : 0, p.out_f32 = out_f32 ? 1 : 0, p.TT = TT, p.Ktot = k * C1 + C2;
+  p.lens = lens, p.causal = causal ? 1 : 0;
   VBX_REQUIRE((long)L * stride < (1L << 30), "vbx_seanet_conv: row too long");
   const size_t bytes = sn_conv_lds(TT, C1, C2, k, stride, dilation);
   const int MG = sn_blocks_per_item((Co + 15) / 16, TT / 16), blocks = cdiv(p.Lout, TT);
+  if (lens) {
+    if (MG == 4) return sn_launch<seanet_conv_kernel<4, true>>("vbx_seanet_conv_lens", p, blocks, B, bytes, (hipStream_t)stream);
+    if (MG == 2) return sn_launch<seanet_conv_kernel<2, true>>("vbx_seanet_conv_lens", p, blocks, B, bytes, (hipStream_t)stream);
+    return sn_launch<seanet_conv_kernel<1, true>>("vbx_seanet_conv_lens", p, blocks, B, bytes, (hipStream_t)stream);
+  }
   if (MG == 4) return sn_launch<seanet_conv_kernel<4>>("vbx_seanet_conv", p, blocks, B, bytes, (hipStream_t)stream);
   if (MG == 2) return sn_launch<seanet_conv_kernel<2>>("vbx_seanet_conv", p, blocks, B, bytes, (hipStream_t)stream);
   return sn_launch<seanet_conv_kernel<1>>("vbx_seanet_conv", p, blocks, B, bytes, (hipStream_t)stream);
+}
+
+extern "C" int vbx_seanet_conv_c(const void* x1_f16, const void* x2_f16, const void* w_f16, const float* bias, void* y, int B, int L, int C1,
+                                 int C2, int Co, int k, int stride, int dilation, int elu1, int out_f32, int causal, void* stream) {
+  return sn_conv_launch(nullptr, x1_f16, x2_f16, w_f16, bias, y, B, L, C1, C2, Co, k, stride, dilation, elu1, out_f32, causal, stream);
+}
+
+extern "C" int vbx_seanet_conv_lens(const void* x1_f16, const void* x2_f16, const int* lens, const void* w_f16, const float* bias, void* y,
+                                    int B, int L, int C1, int C2, int Co, int k, int stride, int dilation, int elu1, int out_f32, int causal,
+                                    void* stream) {
+  VBX_REQUIRE(lens, "vbx_seanet_conv_lens: lens is NULL (vbx_seanet_conv_c is the entry without lengths)");
+  return sn_conv_launch(lens, x1_f16, x2_f16, w_f16, bias, y, B, L, C1, C2, Co, k, stride, dilation, elu1, out_f32, causal, stream);
 }
 
 extern "C" int vbx_seanet_conv(const void* x1_f16, const void* x2_f16, const void* w_f16, const float* bias, void* y, int B, int L, int C1,
@@ -424,17 +484,33 @@ extern "C" int vbx_seanet_conv(const void* x1_f16, const void* x2_f16, const voi
   return vbx_seanet_conv_c(x1_f16, x2_f16, w_f16, bias, y, B, L, C1, C2, Co, k, stride, dilation, elu1, out_f32, 0, stream);
 }
 
-extern "C" int vbx_seanet_conv0_c(const float* wave, const float* w, const float* bias, void* y_f16, int B, int T, int nf, int k,
+static int sn_conv0_launch(const int* lens, const float* wave, const float* w, const float* bias, void* y_f16, int B, int T, int nf, int k,
                                   int causal, void* stream) {
   VBX_REQUIRE(wave && w && bias && y_f16 && B >= 1 && B <= 65535 && T >= 1, "vbx_seanet_conv0: bad args");
   VBX_REQUIRE(nf >= 8 && nf % 8 == 0 && nf <= 64, "vbx_seanet_conv0: n_filters must be a multiple of 8 up to 64 (got %d)", nf);
   VBX_REQUIRE(k >= 1 && k <= SN_MAX_K && (k & 1), "vbx_seanet_conv0: kernel_size must be odd, at most %d (got %d)", SN_MAX_K - 1, k);
   VBX_REQUIRE((long)T * (nf / 8) < (1L << 31) * 256, "vbx_seanet_conv0: row too long");
   const SnPads pads = sn_pads(k, 1, 1, T, T, causal);
-  hipLaunchKernelGGL(seanet_conv0_kernel, dim3(cdiv((long)T * (nf / 8), 256), B), dim3(256), 0, (hipStream_t)stream, wave, w, bias,
-                     (u16*)y_f16, T, nf, k, pads.left, pads.Lz);
+  const dim3 grid(cdiv((long)T * (nf / 8), 256), B);
+  if (lens)
+    hipLaunchKernelGGL(seanet_conv0_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, wave, w, bias, (u16*)y_f16, T, nf, k, pads.left,
+                       pads.Lz, lens, causal ? 1 : 0);
+  else
+    hipLaunchKernelGGL(seanet_conv0_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, wave, w, bias, (u16*)y_f16, T, nf, k, pads.left,
+                       pads.Lz, (const int*)nullptr, causal ? 1 : 0);
   VBX_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int vbx_seanet_conv0_c(const float* wave, const float* w, const float* bias, void* y_f16, int B, int T, int nf, int k,
+                                  int causal, void* stream) {
+  return sn_conv0_launch(nullptr, wave, w, bias, y_f16, B, T, nf, k, causal, stream);
+}
+
+extern "C" int vbx_seanet_conv0_lens(const float* wave, const int* lens, const float* w, const float* bias, void* y_f16, int B, int T, int nf,
+                                     int k, int causal, void* stream) {
+  VBX_REQUIRE(lens, "vbx_seanet_conv0_lens: lens is NULL (vbx_seanet_conv0_c is the entry without lengths)");
+  return sn_conv0_launch(lens, wave, w, bias, y_f16, B, T, nf, k, causal, stream);
 }
 
 extern "C" int vbx_seanet_conv0(const float* wave, const float* w, const float* bias, void* y_f16, int B, int T, int nf, int k,

@@ -646,7 +646,7 @@ class TrainStep:
 
     # -- gradient accumulation with a deferred exchange (VoiceBoxTrainer.train_step, trainer.py:258-272: every micro-batch but
     #    the last runs under accelerator.no_sync, the loss is divided by grad_accum_every)
-    def accumulate(self, x1, weight, mask=None, cond_token_ids=None, input_sampling_rate=None, lens=None):
+    def accumulate(self, x1, weight, mask=None, cond_token_ids=None, input_sampling_rate=None, lens=None, wave_lens=None):
         """forward + backward of one micro-batch; gradients * weight are added to the accumulation buffer (no exchange).
         lens: see step."""
         self._refuse_inside_ema_weights("accumulate")
@@ -655,7 +655,8 @@ class TrainStep:
             self.gacc = torch.zeros_like(self.gflat)
             self.acc_coef = torch.zeros(1, device=self.gflat.device)
             self.acc_pending = False
-        loss = self._forward_backward(x1, mask, cond_token_ids, on_stage=None, input_sampling_rate=input_sampling_rate, lens=lens)
+        loss = self._forward_backward(x1, mask, cond_token_ids, on_stage=None, input_sampling_rate=input_sampling_rate, lens=lens,
+                                      wave_lens=wave_lens)
         self.acc_coef.fill_(float(weight))
         n = self.gflat.numel()
         _lib.call("vbx_axpy_dev", self.gacc, self.gflat, self.acc_coef, 0, self.gacc, n, _lib.current_stream())
@@ -714,7 +715,8 @@ class TrainStep:
                                              dada_all.shape[1], Th, J4, 0, st), "vbx_adaln_expand_dw")
         self._keep_factors = (dada_all, temb_all)  # alive until the launches have run
 
-    def accumulate_last_and_apply(self, x1, weight, mask=None, cond_token_ids=None, lr=None, input_sampling_rate=None, lens=None):
+    def accumulate_last_and_apply(self, x1, weight, mask=None, cond_token_ids=None, lr=None, input_sampling_rate=None, lens=None,
+                                  wave_lens=None):
         """The LAST micro-batch of an accumulation window, with the exchange overlapped with its backward (DDP leaves `no_sync`
         for exactly this micro-batch, trainer.py:258-272): as each backward stage completes, its slice of the accumulator is
         folded in (g = acc + weight * g) and the bucketed all-reduce of that slice starts while earlier layers are still running --
@@ -732,7 +734,8 @@ class TrainStep:
             if self.exchange:
                 red.stage_done(i, rng)
 
-        loss = self._forward_backward(x1, mask, cond_token_ids, on_stage=on_stage, input_sampling_rate=input_sampling_rate, lens=lens)
+        loss = self._forward_backward(x1, mask, cond_token_ids, on_stage=on_stage, input_sampling_rate=input_sampling_rate, lens=lens,
+                                      wave_lens=wave_lens)
         red.finish()
         self._stage_buf = red.stage_buf
         self.gacc.zero_()
@@ -758,11 +761,17 @@ class TrainStep:
         self._clip_adam(self._last_eng, lr)
 
     def _forward_backward(self, x1, mask, cond_token_ids, on_stage, adaln_factors=False, sq_fold=False, input_sampling_rate=None,
-                          lens=None):
+                          lens=None, wave_lens=None):
         vb, w = self.vb, self.wrapper
         dev = self.fp.flat.device
         st = _lib.current_stream
         key_lens = None
+        if wave_lens is not None:  # a ragged batch of WAVES (wave_lens.py): refusals first, rows encoded as the row alone, then lens=
+            from . import wave_lens as wl
+
+            wl.refuse(wave_lens, x1, None, lens, mask, vb.audio_enc_dec, "TrainStep",
+                      wav2vec_ids=cond_token_ids is None and vb.condition_on_text and getattr(w, "wav2vec", None) is not None)
+            x1, _, lens = w.encode_raw_audio(x1, None, input_sampling_rate, wave_lens=wave_lens)
         if lens is not None:  # a ragged batch by lengths (train_lens.py): refusals and host validation before anything is launched
             from . import train_lens
 
@@ -985,13 +994,15 @@ class TrainStep:
             state.needs_apply = True
             state.apply()  # W_eff = W0 + s . B . A into the master slots; bumps the weights epoch: every engine and sampler repacks
 
-    def step(self, x1, mask=None, lr=None, cond_token_ids=None, input_sampling_rate=None, lens=None):
+    def step(self, x1, mask=None, lr=None, cond_token_ids=None, input_sampling_rate=None, lens=None, wave_lens=None):
         """x1: (B_local, frames, dim) on this rank's GPU, or a wave batch (B_local, samples) for a model built with audio_enc_dec
         (cond_token_ids (B_local, tokens) for a text-conditioned model); input_sampling_rate: the rate of such waves, for a wrapper built
         with resample_input=True.
         lens: a list, a CPU int tensor or a device int tensor [B_local] of frame counts instead of mask -- the same step as
         mask = arange(frames) < lens[:, None], bit for bit, with the attention forward and backward stopping at each row's length
         (ConditionalFlowMatcherWrapper.forward).  With text conditioning it counts frames, not tokens.
+        wave_lens: x1 is a padded batch of waves and row b holds wave_lens[b] real samples at the rate the waves are given in -- every
+        row is encoded as the row alone and the step runs as step(latents, lens=codec.frame_lens(...)); not with lens or mask.
         Returns the (un-synchronised) local loss tensor."""
         # --- backward with overlapped gradient exchange
         self._refuse_inside_ema_weights("step")
@@ -1003,7 +1014,7 @@ class TrainStep:
         # (a partly frozen or adapted model takes the plain path: the fold's partials cover all four big matrices of every layer)
         fold = factors and not self.exchange and os.environ.get("VBX_SUMSQ_FOLD", "1") != "0" and self._filter is None
         loss = self._forward_backward(x1, mask, cond_token_ids, on_stage=red.stage_done if self.exchange else None, adaln_factors=factors,
-                                      sq_fold=fold, input_sampling_rate=input_sampling_rate, lens=lens)
+                                      sq_fold=fold, input_sampling_rate=input_sampling_rate, lens=lens, wave_lens=wave_lens)
         if factors and self.exchange:  # the factors travel (one small all-gather) while the last buckets are still in flight
             self._exchange_adaln_factors(self._last_eng)
         red.finish()

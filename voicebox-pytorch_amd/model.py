@@ -14,7 +14,7 @@ import torch
 from torch import nn
 
 from . import _lib
-from .codec import resample
+from .codec import resample, resample_lens
 from .engine import Engine, FlatParams, precise_enabled
 from .masks import mask_from_frac_lengths, prob_mask_like, reduce_masks_with_and, take_draw
 
@@ -731,6 +731,7 @@ class ConditionalFlowMatcherWrapper(nn.Module):
     def sample(self, *, cond=None, texts=None, text_token_ids=None, semantic_token_ids=None, phoneme_ids=None,
                cond_mask=None, steps=3, cond_scale=1., decode_to_audio=True, decode_to_codes=False,
                max_semantic_token_ids=2048, spec_decode=False, spec_decode_gamma=5, use_graph=True, lens=None, length_bucket=None,
+               wave_lens=None,
                pack=False, pack_bucket=None):
         """voicebox_pytorch.py:1175-1330 with torchdiffeq.odeint replaced by the built-in device solvers (solver.py), per
         torchdiffeq_ode_method: 'midpoint' (the default), 'euler' and 'rk4' on the fixed grid linspace(0, 1, steps) -- 2, 1 and 4
@@ -745,6 +746,10 @@ class ConditionalFlowMatcherWrapper(nn.Module):
         phonemes, and -1 padding phonemes get no frames.  length_bucket (with lens): the sampler runs at N rounded up to a multiple
         of it, the extra frames masked like any padding, so that calls whose N share a bucket share one sampler and one graph.
 
+        wave_lens (not a reference keyword): cond is a padded batch of WAVES at the codec's rate and row b holds wave_lens[b] real
+        samples -- every row is encoded as the row alone (codec.encode(lens=)) and the call runs as sample(cond=latents,
+        lens=codec.frame_lens(wave_lens)); length_bucket and pack=True then work unchanged.  Not with lens.
+
         pack=True (with lens; opt-in): the same call and the same result contract, but the batch runs as ONE packed row stream of
         Mp = sum_b align(R + len_b, 128) rows (sample_pack.py, include/vbx.h "packed rows") -- padding frames go through no GEMM, norm
         or attention tile, and attention walks each row's own keys without a mask.  euler / midpoint / rk4, eager or captured, one
@@ -756,9 +761,9 @@ class ConditionalFlowMatcherWrapper(nn.Module):
         from .sample_lens import bucketed, decode_rows, durations_lens, mask_codes, pad_frames, validate_lens
         from .sample_pack import check_pack_bucket
 
-        if exists(length_bucket) and not exists(lens):
+        if exists(length_bucket) and not exists(lens) and not exists(wave_lens):
             raise ValueError("length_bucket needs lens: without lengths the frames added up to the bucket could not be masked")
-        if pack and not exists(lens):
+        if pack and not exists(lens) and not exists(wave_lens):
             raise ValueError("pack=True needs lens: the packed layout is built from the per-row lengths -- pass lens=, or drop pack")
         if exists(pack_bucket) and not pack:
             raise ValueError("pack_bucket only applies to pack=True -- pass pack=True, or use length_bucket with lens= alone")
@@ -780,7 +785,17 @@ class ConditionalFlowMatcherWrapper(nn.Module):
             raise ValueError(f"lens={lens!r}: the only named source of lengths is 'durations', on the phoneme_ids + duration_predictor path")
 
         codec = self.voicebox.audio_enc_dec
-        if is_probably_audio_from_shape(cond):  # :1192-1201
+        if exists(wave_lens):  # cond is a padded batch of waves: rows encoded as the row alone, then sample(cond=latents, lens=frame_lens)
+            from . import wave_lens as wl
+
+            wl.refuse(wave_lens, cond, None, lens, None, codec, "ConditionalFlowMatcherWrapper.sample", what="cond")
+            codec.eval()
+            if torch.is_tensor(wave_lens):
+                wave_lens = wave_lens.to(self.device)
+            with torch.no_grad():
+                cond = codec.encode(cond.to(self.device), lens=wave_lens)
+            lens = codec.frame_lens(wave_lens)
+        elif is_probably_audio_from_shape(cond):  # :1192-1201
             assert exists(codec), 'audio_enc_dec must be set on VoiceBox to condition on raw audio'
             codec.eval()
             cond = codec.encode(cond.to(self.device))
@@ -909,12 +924,21 @@ class ConditionalFlowMatcherWrapper(nn.Module):
         wave, self.last_sample_lens = decode_rows(codec, out, lens)
         return wave
 
-    def encode_raw_audio(self, x1, cond=None, input_sampling_rate=None):
+    def encode_raw_audio(self, x1, cond=None, input_sampling_rate=None, wave_lens=None):
         """voicebox_pytorch.py:1349-1371: a 2-D tensor, or a 3-D one with a middle dimension of 1, is a wave -- encoded by the codec
         (in eval mode, without gradients).  Latents pass through.  With resample_input=True a wave given at an input_sampling_rate
         other than the codec's is resampled to it first, on this wrapper's device (:1359-1371); equal rates or None launch nothing.
-        sample() keeps the reference's signature: resample its `cond` with voicebox_pytorch_amd.resample beforehand."""
+        sample() keeps the reference's signature: resample its `cond` with voicebox_pytorch_amd.resample beforehand.
+
+        wave_lens (not a reference keyword): samples per row of the padded wave batch x1, at the rate the waves are given in (a list,
+        a CPU int tensor or a device int tensor [B]).  Every row is then encoded as the row alone -- resample(lens=) /
+        resample_lens, codec.encode(lens=) / codec.frame_lens -- a raw-audio cond with the same lengths, and THREE values come back:
+        (x1, cond, frame_lens), frame_lens of the kind wave_lens was, ready for lens=."""
         in_raw, cond_raw = is_probably_audio_from_shape(x1), is_probably_audio_from_shape(cond)
+        if exists(wave_lens):
+            from . import wave_lens as wl
+
+            wl.refuse(wave_lens, x1, cond, None, None, self.voicebox.audio_enc_dec, "ConditionalFlowMatcherWrapper.encode_raw_audio")
         if not (in_raw or cond_raw):
             return x1, cond
         codec = self.voicebox.audio_enc_dec
@@ -926,6 +950,16 @@ class ConditionalFlowMatcherWrapper(nn.Module):
                                       "waves first (voicebox_pytorch_amd.resample)")
         with torch.no_grad():
             codec.eval()
+            if exists(wave_lens):
+                if torch.is_tensor(wave_lens):
+                    wave_lens = wave_lens.to(self.device)
+                lens_c = resample_lens(wave_lens, input_sampling_rate, codec.sampling_rate) if differs else wave_lens
+                enc = lambda t: codec.encode(resample(t.to(self.device), input_sampling_rate, codec.sampling_rate, lens=wave_lens)
+                                             if differs else t.to(self.device), lens=lens_c)
+                x1 = enc(x1)
+                if cond_raw:
+                    cond = enc(cond)
+                return x1, cond, codec.frame_lens(lens_c)
             if in_raw:
                 x1 = x1.to(self.device)
                 if differs:
@@ -956,12 +990,17 @@ class ConditionalFlowMatcherWrapper(nn.Module):
             return w2v(wave).clone()
 
     def forward(self, x1, *, mask=None, lens=None, semantic_token_ids=None, phoneme_ids=None, cond=None, cond_mask=None,
-                input_sampling_rate=None):  # voicebox_pytorch.py:1332-1427
+                input_sampling_rate=None, wave_lens=None):  # voicebox_pytorch.py:1332-1427
         """lens (not a reference keyword): a list, a CPU int tensor or a device int tensor [B] of frame counts, 1 <= len_b <= N -- the
         batch is ragged, row b has len_b real frames.  It means exactly mask = arange(N)[None] < lens[:, None] (same loss, same
         gradients, bit for bit), and the attention forward and backward stop at each row's length instead of masking the padding
         after the products.  Not with mask, not with raw audio (encode first, or pass mask).  A list or CPU tensor is validated on the
-        host; a device tensor is clamped into 1 .. N on the device without a host synchronisation."""
+        host; a device tensor is clamped into 1 .. N on the device without a host synchronisation.
+
+        wave_lens (not a reference keyword): x1 is a padded batch of WAVES and row b holds wave_lens[b] real samples, at the rate
+        the waves are given in.  Every row is encoded as the row alone (encode_raw_audio(wave_lens=)), and the step runs as
+        forward(latents, lens=codec.frame_lens(...)).  Not with latents, lens or mask; needs a codec with frame_lens and
+        encode(lens=); token ids are passed (semantic_token_ids), not taken from wav2vec=."""
         if self.voicebox._lora is not None and torch.is_grad_enabled() and any(p.requires_grad for p in self.voicebox.parameters()):
             from .lora import refuse_autograd
 
@@ -974,7 +1013,16 @@ class ConditionalFlowMatcherWrapper(nn.Module):
             train_lens.refuse_raw_audio(lens, x1, who)
             lens = train_lens.frame_lens(lens, x1.shape[0], x1.shape[1], self.device)
         raw_audio = x1 if is_probably_audio_from_shape(x1) else None
-        x1, cond = self.encode_raw_audio(x1, cond, input_sampling_rate)
+        if exists(wave_lens):  # every refusal before anything is launched; then the frame lengths take the lens= path
+            from . import train_lens, wave_lens as wl
+
+            wl.refuse(wave_lens, x1, cond, lens, mask, self.voicebox.audio_enc_dec, "ConditionalFlowMatcherWrapper.forward",
+                      wav2vec_ids=self.condition_on_text and exists(self.wav2vec) and not exists(semantic_token_ids)
+                      and not exists(phoneme_ids))
+            x1, cond, lens = self.encode_raw_audio(x1, cond, input_sampling_rate, wave_lens=wave_lens)
+            lens = train_lens.frame_lens(lens, x1.shape[0], x1.shape[1], self.device)
+        else:
+            x1, cond = self.encode_raw_audio(x1, cond, input_sampling_rate)
         assert self.condition_on_text or not (exists(semantic_token_ids) or exists(phoneme_ids)), \
             'semantic or phoneme ids should not be passed in if not conditioning on text'
         dev = self.device

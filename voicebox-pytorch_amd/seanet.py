@@ -39,6 +39,7 @@ from torch import nn
 from . import _lib
 from ._packing import PackedWeights, read_checkpoint
 from ._wnconv import WNConv, weight_norm_key
+from .wave_lens import device_lens, map_lens
 
 
 class _NormConv(nn.Module):
@@ -237,7 +238,11 @@ class _SEANet(PackedWeights, nn.Module):
             op["b1"] = (f(l.bias_ih_l1) + f(l.bias_hh_l1)).contiguous()
         return op
 
-    def _conv(self, op, x1, x2, y, B, L, st):
+    def _conv(self, op, x1, x2, y, B, L, st, lens=None):
+        if lens is not None:
+            _lib.call("vbx_seanet_conv_lens", x1, x2, lens, op["w"], op["b"], y, B, L, op["C1"], op["C2"], op["Co"], op["k"], op["stride"],
+                      op["dil"], int(op["elu"]), int(op["out_f32"]), int(self.causal), st)
+            return
         _lib.call("vbx_seanet_conv_c", x1, x2, op["w"], op["b"], y, B, L, op["C1"], op["C2"], op["Co"], op["k"], op["stride"], op["dil"],
                   int(op["elu"]), int(op["out_f32"]), int(self.causal), st)
 
@@ -359,7 +364,19 @@ class SEANetEncoder(_SEANet):
                 elu = False
         return ops
 
-    def forward(self, audio):
+    def frame_lens(self, sample_lens):
+        """frames() of each length, the ceil chain over reversed(ratios): a list, a CPU tensor or a device tensor; the same kind back"""
+        def chain(l):
+            for r in reversed(self.ratios):
+                l = (l + (r - 1)) // r
+            return l
+        return map_lens(sample_lens, chain)
+
+    def forward(self, audio, lens=None):
+        """lens: per-row sample counts of a padded batch, 1 <= len_b <= T (a list or CPU tensor is validated, a device tensor
+        clamped): row b is the row alone -- every convolution pads about the row's own length (vbx_seanet_conv0_lens /
+        vbx_seanet_conv_lens; the per-layer tables are integer torch ops on the device, no host read), bit-equal to
+        forward(audio[b:b+1, :len_b])[0] up to frame_lens(lens)[b] and exactly 0.0 past it."""
         if audio.ndim == 3 and audio.shape[1] == 1:
             audio = audio[:, 0]
         if audio.ndim != 2 or not audio.is_floating_point():
@@ -367,19 +384,23 @@ class SEANetEncoder(_SEANet):
         if audio.shape[0] < 1 or audio.shape[1] < 1:
             raise ValueError("SEANetEncoder: empty audio")
         dev = audio.device
+        if lens is not None:  # checked (host values) or clamped (a device tensor) before anything else
+            lens = device_lens(lens, audio.shape[0], audio.shape[1], 1, dev, "SEANetEncoder")
         if dev.type != "cuda":
             raise _lib.VbxError(f"SEANetEncoder runs only on an MI355X (gfx950) through libvbx_hip.so; the audio is on '{dev}'")
         if self.model[0].inner.bias.device != dev:
             self.to(dev)
         with torch.inference_mode():
-            return self._encode(audio)
+            return self._encode(audio, lens)
 
-    def _encode(self, audio):
+    def _encode(self, audio, lens=None):
         B, L = audio.shape
         dev, st = audio.device, _lib.current_stream()
         ops = self.packed_ops()
         wave = audio.detach().to(torch.float32).contiguous()
         x = torch.empty(B, L, ops[0]["nf"], dtype=torch.float16, device=dev)
+        if lens is not None:
+            return self._encode_lens(wave, x, lens, ops, st)
         _lib.call("vbx_seanet_conv0_c", wave, ops[0]["w"], ops[0]["b"], x, B, L, ops[0]["nf"], ops[0]["k"], int(self.causal), st)
         kept = None
         for op in ops[1:]:
@@ -394,6 +415,26 @@ class SEANetEncoder(_SEANet):
                 self._conv(op, x, None, y, B, L, st)
                 if op.get("keep"):
                     kept = x
+            x, L = y, Lout
+        return x
+
+
+    def _encode_lens(self, wave, x, lens, ops, st):
+        """_encode with the rows' own lengths: `lens` int32 [B] on the device, in the units of each launch's input"""
+        B, L = wave.shape
+        _lib.call("vbx_seanet_conv0_lens", wave, lens, ops[0]["w"], ops[0]["b"], x, B, L, ops[0]["nf"], ops[0]["k"], int(self.causal), st)
+        kept = None
+        for op in ops[1:]:
+            if op["op"] == "lstm":  # runs over the zero rows past a row's length too; the next convolution does not read them
+                x = self.lstm_forward(op, x, B, L, st)
+                continue
+            Lout = -(-L // op["stride"])
+            y = torch.empty(B, Lout, op["Co"], dtype=torch.float32 if op["out_f32"] else torch.float16, device=x.device)
+            self._conv(op, x, kept if op["op"] == "tail" else None, y, B, L, st, lens=lens)
+            if op.get("keep"):
+                kept = x
+            if op["stride"] > 1:
+                lens = ((lens + (op["stride"] - 1)) // op["stride"]).to(torch.int32)
             x, L = y, Lout
         return x
 

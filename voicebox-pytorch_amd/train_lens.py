@@ -17,7 +17,7 @@ def refuse_raw_audio(lens, x1, who):
     """a wave batch: [B, samples] or [B, 1, samples] (model.is_probably_audio_from_shape)"""
     if lens is not None and torch.is_tensor(x1) and (x1.ndim == 2 or (x1.ndim == 3 and x1.shape[1] == 1)):
         raise ValueError(f"{who}: lens counts frames, and x1 is raw audio whose frame count is the codec's business -- encode first "
-                         f"(wrapper.encode_raw_audio) and pass lens in frames, or pass mask")
+                         f"(wrapper.encode_raw_audio) and pass lens in frames, or pass mask, or pass wave_lens= (samples per row)")
 
 
 def frame_lens(lens, B, N, device):

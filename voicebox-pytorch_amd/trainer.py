@@ -88,6 +88,7 @@ class VoiceBoxTrainer(nn.Module):
                  valid_frac=0.05, random_split_seed=42, log_every=10, save_results_every=100, save_model_every=1000,
                  results_folder='./results', force_clear_prev_results=None, split_batches=False, drop_last=False,
                  accelerate_kwargs: dict = dict(), length_bucket=64, input_sampling_rate=None, mask_padding=False,
+                 mask_wave_padding=False,
                  ema_decay=None, ema_update_after_step=0, ema_inv_gamma=1.0, ema_power=None):
         # length_bucket (not a reference keyword): batches of a varying-length dataset are padded with masked frames to the next
         # multiple of it, so that training runs on a handful of activation arenas (dp.TrainStep); 0 = exact lengths
@@ -97,12 +98,19 @@ class VoiceBoxTrainer(nn.Module):
         # function also returns each item's length, and every train and validation step passes lens= -- padding frames are masked in the
         # convolution, the attention and the loss, and the attention kernels stop at each row's length.  Latent datasets only: with a
         # dataset of waves the first batch raises ValueError (the frame count is the codec's business).
+        # mask_wave_padding (not a reference keyword; opt-in): the same for a dataset of WAVES -- the collate function's lengths are samples
+        # per row and go to every train and validation step as wave_lens=: every row is encoded as the row alone and its padding
+        # frames are masked (wave_lens.py).  With a dataset of latents the first batch raises ValueError naming mask_padding.
         # ema_decay / ema_update_after_step / ema_inv_gamma / ema_power (not reference keywords): handed to dp.TrainStep, which keeps an
         # exponential moving average of the weights inside its Adam launches.  save() then adds 'ema_model' (TrainStep.ema_state_dict())
         # and 'ema' (the four hyper-parameters) beside the reference's three keys, load() restores the average from them (or resets it
         # to the loaded weights when the file has none), and the rank-0 validation also logs the loss of the averaged model.
         super().__init__()
         self.mask_padding = bool(mask_padding)
+        self.mask_wave_padding = bool(mask_wave_padding)
+        if self.mask_padding and self.mask_wave_padding:
+            raise ValueError("VoiceBoxTrainer: mask_padding (a dataset of latents, lengths in frames) and mask_wave_padding (a dataset of "
+                             "waves, lengths in samples) both given -- pass one of them")
         self.input_sampling_rate = input_sampling_rate
         assert isinstance(cfm_wrapper, ConditionalFlowMatcherWrapper)
         self.wd = float(wd)  # > 0: AdamW with decay on the ndim >= 2 parameters (get_optimizer, optimizer.py:10-35)
@@ -143,8 +151,9 @@ class VoiceBoxTrainer(nn.Module):
         if self.world > 1:  # what accelerator.prepare(dl) does: each rank sees its own shard
             sampler = torch.utils.data.distributed.DistributedSampler(self.ds, num_replicas=self.world, rank=self.rank, shuffle=True)
         self.dl = get_dataloader(self.ds, batch_size=self.rank_batch_size, shuffle=sampler is None, sampler=sampler, drop_last=drop_last,
-                                 with_lens=self.mask_padding)
-        self.valid_dl = get_dataloader(self.valid_ds, batch_size=batch_size, shuffle=True, drop_last=drop_last, with_lens=self.mask_padding)
+                                 with_lens=self.mask_padding or self.mask_wave_padding)
+        self.valid_dl = get_dataloader(self.valid_ds, batch_size=batch_size, shuffle=True, drop_last=drop_last,
+                                       with_lens=self.mask_padding or self.mask_wave_padding)
         self.dl_iter, self.valid_dl_iter = cycle(self.dl, sampler), cycle(self.valid_dl)
         self.log_every, self.save_model_every, self.save_results_every = log_every, save_model_every, save_results_every
         self.results_folder = Path(results_folder)
@@ -299,6 +308,12 @@ class VoiceBoxTrainer(nn.Module):
                                  "in samples, and the frame count is the codec's business -- encode the dataset first, or leave "
                                  "mask_padding off")
             kw['lens'] = lens
+        elif getattr(self, "mask_wave_padding", False):  # the same entry, counting samples
+            batch, lens = batch[:-1], batch[-1]
+            if not (x.ndim == 2 or (x.ndim == 3 and x.shape[1] == 1)):
+                raise ValueError("VoiceBoxTrainer(mask_wave_padding=True) needs a dataset of waves (samples,): the lengths of latents are "
+                                 "in frames -- pass mask_padding=True for them")
+            kw['wave_lens'] = lens
         if len(batch) > 1 and self.cfm_wrapper.condition_on_text:
             kw['cond_token_ids'] = batch[1]
         return x, kw
@@ -335,7 +350,7 @@ class VoiceBoxTrainer(nn.Module):
                 self.cfm_wrapper.eval()
                 ids = kw.get('cond_token_ids')
                 valid_loss = self.cfm_wrapper(x.to(self.device), input_sampling_rate=self.input_sampling_rate,
-                                              **({'lens': kw['lens']} if 'lens' in kw else {}),
+                                              **{k: kw[k] for k in ('lens', 'wave_lens') if k in kw},
                                               **({'semantic_token_ids': ids.to(self.device)} if ids is not None else {}))
             self.print(f'{steps}: valid loss {float(valid_loss):0.3f}')
             logs['valid_loss'] = float(valid_loss)
@@ -347,7 +362,7 @@ class VoiceBoxTrainer(nn.Module):
                     if rng[1] is not None:
                         torch.cuda.set_rng_state(rng[1], dev)
                     valid_loss_ema = self.cfm_wrapper(x.to(self.device), input_sampling_rate=self.input_sampling_rate,
-                                                      **({'lens': kw['lens']} if 'lens' in kw else {}),
+                                                      **{k: kw[k] for k in ('lens', 'wave_lens') if k in kw},
                                                       **({'semantic_token_ids': ids.to(self.device)} if ids is not None else {}))
                 self.print(f'{steps}: valid loss (ema) {float(valid_loss_ema):0.3f}')
                 logs['valid_loss_ema'] = float(valid_loss_ema)
