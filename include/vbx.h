@@ -239,7 +239,9 @@ int vbx_dropout_rows_f32(float* x, long rows, int cols, int ld, unsigned long lo
  * ceil(key_lens[b] / 64) key tiles instead of ceil(Np / 64) (the DMA ring prefetches against the same bound); a 128-row query tile
  * wholly at or past key_lens[b] writes zeros and lse 1e30 and leaves.  Every output row and lse of a query < key_lens[b] is bit-equal
  * to vbx_attn_fwd with the prefix mask: a skipped tile would add +0 to l and O, and max(m, -inf) = m.  Rows >= key_lens[b] are
- * padding.  The benchmark's kernel is a separate instantiation and is not changed by this one. */
+ * padding.  The forward clamps key_lens[b] into [0, Np] (the backward entry points below into [1, Np]): at 0 every tile of the batch
+ * row is dead, so all its rows are zeros with lse 1e30 and no K or V row is read; callers pass >= 1.
+ * The benchmark's kernel is a separate instantiation and is not changed by this one. */
 int vbx_attn_fwd_lens(const void* q16, const void* k16, const void* v16, const uint8_t* mask, const int* key_lens, void* out16,
                       void* out_bf16, float* lse, int B, int H, int Np, float scale, void* stream);
 /* ------------------------------------------------------------------ attention backward with prefix lengths (training, lens=)

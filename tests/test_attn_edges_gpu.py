@@ -16,7 +16,7 @@ import math
 import pytest
 import torch
 
-from attn_check import BOUNDS, Checks, max_err, qpre, rel_err, rot_tables
+from attn_check import BOUNDS, Checks, L_tiles, all_nan, bf, heads, max_err, qpre, rel_err, rot_tables, same_bits
 from oracle import restate
 
 pytestmark = pytest.mark.gpu
@@ -50,25 +50,8 @@ def st():
     return torch.cuda.current_stream().cuda_stream
 
 
-def bf(x):
-    return x.to(torch.bfloat16)
-
-
 def nans(shape, dtype):
     return torch.full(shape, float("nan"), dtype=dtype, device=dev)
-
-
-def all_nan(t):
-    return bool(torch.isnan(t.float()).all())
-
-
-def same_bits(a, b):
-    it = {torch.float32: torch.int32, torch.float16: torch.int16, torch.bfloat16: torch.int16}[a.dtype]
-    return torch.equal(a.view(it), b.view(it))
-
-
-def heads(t, B, Np, H):  # token-major [B * Np, H * 64] -> [B, H, Np, 64]
-    return t.reshape(B, Np, H, 64).permute(0, 2, 1, 3)
 
 
 # ----------------------------------------------------------------------------- inputs
@@ -276,10 +259,6 @@ class Case:
                 for b in range(B):
                     if not bool(self.mask[b].any()):
                         chk.true(f"gamma partials of masked batch {b} are 0", bool((gp[:, b * tiles:(b + 1) * tiles] == 0).all()))
-
-
-def L_tiles(Np):
-    return -(-Np // 128)
 
 
 def run_fwd_bwd(L, c, chk, bounds):
