@@ -318,7 +318,31 @@ int vbx_attn_fwd_segs(const void* q16, const void* k16, const void* v16, const i
  *   vbx_seanet_conv_lens   L_b = lens[b], Lout_b = ceil(L_b / stride), `extra` and Lz from them; pad_left does not depend on L.  The
  *                          second input (x2) is read at t < L_b; positions from Lout_b on are 0.  The NEXT launch takes the table
  *                          ceil(lens / stride).
- * vbx_lstm needs no such entry: the recurrence runs forward, steps below the row's length cannot see what follows them. */
+ * vbx_lstm needs no such entry: the recurrence runs forward, steps below the row's length cannot see what follows them.
+ *
+ * HubertWithKmeans(wave, lens=) -- the one front end whose FIRST layer is not local: GroupNorm(C, C) takes its statistics over time.
+ *   vbx_hubert_conv0_stats_lens   lens[b] samples, k0 <= lens[b] <= T: row b's statistics run over L0_b = (lens[b] - k0) / s0 + 1
+ *                          positions.  The chunks are the plain entry's 256-position chunks from position 0; a workgroup whose chunk
+ *                          starts at or past L0_b leaves before it reads anything, the last live chunk takes n = L0_b - t0, and the
+ *                          finalize pass combines the live chunks alone, in the same ascending fp64 order, and divides by L0_b: the
+ *                          statistics are bit-equal to those of the row alone.  records keeps the pitch vbx_hubert_conv0_chunks(L0).
+ *   vbx_hubert_conv0_apply_lens   the plain apply's arithmetic at positions < L0_b; a position at or past L0_b stores fp16 zeros and
+ *                          reads neither the wave nor the statistics -- this is what frees the result of the padding's content.
+ *   vbx_hubert_conv        runs UNCHANGED.  It has no padding: with L_b live inputs and Lout_b = (L_b - k) / 2 + 1 live outputs, the
+ *                          last live output reads inputs up to 2 (Lout_b - 1) + k - 1 <= L_b - 1, so a live output reads live
+ *                          inputs only.  Outputs at or past Lout_b read stored zeros and at most k - 1 live values: finite, and read
+ *                          by no live position of any later layer, by the same argument one layer on.  The caller maps the table
+ *                          through (l - k) / 2 + 1 alongside.
+ *   vbx_hubert_posconv_lens       lens[b] = N_b frames, 1 <= N_b <= N: positions >= N_b (not >= N) are staged as zeros, which is what
+ *                          Conv1d(padding = k / 2) of the row alone sees there, whatever x holds; output rows N_b .. N - 1 are
+ *                          stored as 0.0 without a product and a tile wholly past N_b stages nothing.  The tile is the plain
+ *                          entry's at N.
+ *   the encoder layers     vbx_attn_fwd_lens with key_lens = the frame lengths and mask NULL; the products, the LayerNorms and
+ *                          vbx_hubert_split_heads are row-wise and run as they are.  Dead rows stay finite and feed no live row.
+ *                          The caller zero-fills the dead frames of the last layer's output and the dead ids after
+ *                          vbx_kmeans_assign (id 0: always a valid index of an embedding table).
+ * Bit-equality to the row alone holds where vbx_gemm_route answers the same for M = B * N and M = N_b (it changes kernel at tile
+ * counts of 96, 256 and 384 only) -- the tile core of the convolutions gives the same bits at every tile height. */
 int vbx_logmel_lens(const float* audio, const int* lens, float* out, const float* window, const float* tw_re, const float* tw_im,
                     const int* fb_start, const int* fb_len, const int* fb_off, const float* fb_w, int B, long T, int n_fft, int hop,
                     int n_mels, int log_out, void* stream);
@@ -331,6 +355,12 @@ int vbx_seanet_conv0_lens(const float* wave, const int* lens, const float* w, co
                           int causal, void* stream);
 int vbx_seanet_conv_lens(const void* x1_f16, const void* x2_f16, const int* lens, const void* w_f16, const float* bias, void* y, int B,
                          int L, int C1, int C2, int Co, int k, int stride, int dilation, int elu1, int out_f32, int causal, void* stream);
+int vbx_hubert_conv0_stats_lens(const float* wave, const int* lens, const float* w, float* records, float* stats, int B, long T, int C,
+                                int k0, int s0, float eps, void* stream);
+int vbx_hubert_conv0_apply_lens(const float* wave, const int* lens, const float* w, const float* stats, const float* gamma,
+                                const float* beta, void* y_f16, int B, long T, int C, int k0, int s0, void* stream);
+int vbx_hubert_posconv_lens(const float* x, const int* lens, const void* w_f16, const float* bias, float* y, int B, int N, int D,
+                            int groups, int k, void* stream);
 int vbx_attn_fwd_dropout(const void* q16, const void* k16, const void* v16, const uint8_t* mask, void* out16, void* out_bf16,
                          float* lse, int B, int H, int Np, float scale, const void* bits_rm, float p, void* stream);
 int vbx_attn_bwd_dropout(const void* q16, const void* k16, const void* qb, const void* kb, const void* v, const uint8_t* mask,
@@ -379,6 +409,25 @@ int vbx_proj_in_embed(const float* x, const float* cond, const void* w_f16, cons
 /* columns [col0, col0 + E) of the same rows (row stride ld): cond_emb as vbx_pack_embed_input_text computes it */
 int vbx_embed_text_cols(const uint8_t* drop_mask, const long* ids, int T, const float* table, int E, long null_id, void* out_f16,
                         void* out_bf16, int B, int N, int col0, int ld, void* stream);
+/* ---- per-row token resize (ragged batches with token ids at another frame rate; vbx_io.tok_lens)
+ * vbx_pack_embed_input_text, vbx_embed_text_cols and vbx_cond_emb_bwd stretch T tokens to N frames with ONE ratio T / N for the batch.  Their *_lens
+ * siblings stretch row b's own T_b = tok_lens[b] tokens to its own N_b = key_lens[b] - R frames, as the row alone would:
+ *  - frame n < N_b: the same interpolate_1d source (i0, i1, lam) computed from (n, N_b, T_b) over ids[b, :T_b]; T_b == N_b is the
+ *    identity, as T == N is above.  Bit-equal to the plain entry on the row alone (B = 1, N = N_b, T = T_b, ids[b, :T_b]).
+ *  - frame n >= N_b: the cond_emb columns are 0; the x and cond' columns (vbx_pack_embed_input_text_lens) are written as ever.  The
+ *    backward adds nothing to the table for such a frame.
+ *  - tok_lens [B] and key_lens [B] int32 on the device; the kernels clamp T_b into 1 .. T and N_b into 1 .. N, so no value of a
+ *    table becomes an out-of-range index.  R: the register rows key_lens counts in front of the frames (0: key_lens holds frames).
+ *  - drop_mask / null_id as above.  Second kernels: the plain entries launch the kernels they always launched. */
+int vbx_pack_embed_input_text_lens(const float* x, const float* cond, const uint8_t* cond_mask, const uint8_t* drop_mask,
+                                   const float* null_cond, const long* ids, int T, const int* tok_lens, const int* key_lens, int R,
+                                   const float* table, int E, long null_id, void* out_f16, void* out_bf16, int B, int N, int D,
+                                   void* stream);
+int vbx_embed_text_cols_lens(const uint8_t* drop_mask, const long* ids, int T, const int* tok_lens, const int* key_lens, int R,
+                             const float* table, int E, long null_id, void* out_f16, void* out_bf16, int B, int N, int col0, int ld,
+                             void* stream);
+int vbx_cond_emb_bwd_lens(const void* demb_bf16, int ld, const long* ids, int T, const int* tok_lens, const int* key_lens, int R,
+                          const uint8_t* drop_mask, long null_id, float* gtable, int B, int N, int E, void* stream);
 /* split-K slabs [splits][D][Kp] of dY^T . xc  ->  dw fp32 [D, L], db fp32 [D] */
 int vbx_proj_in_wgrad_reduce(const float* slabs, int splits, int D, int L, float* dw, float* db, void* stream);
 /* vbx_masked_mse_fwd / _bwd with the prediction (and d(pred), bf16, pad columns zeroed) in rows of ldp >= D floats, any D */
@@ -1258,6 +1307,11 @@ typedef struct {
   const int* seg_start;         /* vbx_model.packed only (NULL otherwise): the device tables of "packed rows", validated by the caller: */
   const int* seg_klen;          /* seg_start / seg_klen int32 [segments], tile_seg int32 [Mp / 128]                                    */
   const int* tile_seg;
+  const int* tok_lens;          /* NULL, or [B] int32 on the device, 1 <= tok_lens[b] <= T; requires key_lens.  Row b's T_b = tok_lens[b]
+                                   token ids are resized to its own N_b = key_lens[b] - R frames (vbx_pack_embed_input_text_lens,
+                                   vbx_embed_text_cols_lens, vbx_cond_emb_bwd_lens) instead of T ids to N frames.  Must stay alive
+                                   until the backward.  VBX_EINVAL in precise mode and on packed rows.  LAST: zero-initialised
+                                   callers built against the struct without it keep their meaning. */
 } vbx_io;
 
 size_t vbx_model_wpack_bytes(const vbx_model* m);

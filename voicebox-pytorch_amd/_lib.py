@@ -66,6 +66,9 @@ _PROTOS = {
     "vbx_pack_embed_input": [P, P, P, P, P, I, I, I, P],
     "vbx_pack_embed_input_text": [P, P, P, P, P, P, I, P, I, L, P, P, I, I, I, P],
     "vbx_cond_emb_bwd": [P, I, P, I, P, L, P, I, I, I, P],
+    "vbx_pack_embed_input_text_lens": [P, P, P, P, P, P, I, P, P, I, P, I, L, P, P, I, I, I, P],
+    "vbx_embed_text_cols_lens": [P, P, I, P, P, I, P, I, L, P, P, I, I, I, I, P],
+    "vbx_cond_emb_bwd_lens": [P, I, P, I, P, P, I, P, L, P, I, I, I, P],
     "vbx_proj_in_kp": [I],
     "vbx_proj_in_embed": [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, P],
     "vbx_embed_text_cols": [P, P, I, P, I, L, P, P, I, I, I, I, P],
@@ -127,6 +130,9 @@ _PROTOS = {
     "vbx_hubert_posconv_tile": [I, I],
     "vbx_hubert_posconv": [P, P, P, P, I, I, I, I, I, P],
     "vbx_hubert_split_heads": [P, P, P, P, I, I, I, F, P],
+    "vbx_hubert_conv0_stats_lens": [P, P, P, P, P, I, L, I, I, I, F, P],
+    "vbx_hubert_conv0_apply_lens": [P, P, P, P, P, P, P, I, L, I, I, I, P],
+    "vbx_hubert_posconv_lens": [P, P, P, P, P, I, I, I, I, I, P],
     "vbx_kmeans_assign": [P, P, P, L, I, I, P],
     "vbx_maximum_path": [P, P, P, P, P, P, I, I, I, P],
     "vbx_forward_sum_fwd": [P, P, P, F, P, P, P, P, I, I, I, P],

@@ -103,6 +103,36 @@ __global__ void embed_text_cols_kernel(const uint8_t* __restrict__ drop, const l
   }
 }
 
+// embed_text_cols_kernel with the row's own token and frame counts (include/vbx.h, vbx_io.tok_lens; the resize of
+// pack_embed_text_lens_kernel, ops.hip): both clamped here, zeros from frame N_b on
+__global__ void embed_text_cols_lens_kernel(const uint8_t* __restrict__ drop, const long* __restrict__ ids, int T,
+                                            const int* __restrict__ tok_lens, const int* __restrict__ key_lens, int R,
+                                            const float* __restrict__ table, int E, long null_id, u16* __restrict__ out,
+                                            u16* __restrict__ outb, int B, int N, int col0, int Ke) {
+  const long total = (long)B * N * E;
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const long row = i / E;
+    const int e = (int)(i - row * E);
+    const int b = (int)(row / N), n = (int)(row - (long)b * N);
+    const int Tb = min(max(tok_lens[b], 1), T), Nb = min(max(key_lens[b] - R, 1), N);
+    const long oo = row * Ke + col0 + e;
+    if (n >= Nb) {
+      out[oo] = 0;
+      if (outb) outb[oo] = 0;
+      continue;
+    }
+    const bool dropped = drop && drop[b];
+    int i0, i1;
+    float lam;
+    interp_src(n, Nb, Tb, i0, i1, lam);
+    const long id0 = dropped ? null_id : ids[(long)b * T + i0], id1 = dropped ? null_id : ids[(long)b * T + i1];
+    const float r0 = table[id0 * E + e], r1 = table[id1 * E + e];
+    const float v = (Tb == Nb) ? r0 : ((1.0f - lam) * r0 + lam * r1);
+    out[oo] = f32_to_f16_sat(v);
+    if (outb) outb[oo] = f32_to_bf16(v);
+  }
+}
+
 // slabs [splits][D][Kp] of dY^T . xcb  ->  d(proj_in.weight) [D, L] (columns 0..L-1) and d(proj_in.bias) [D] (column L)
 __global__ void proj_in_wgrad_reduce_kernel(const float* __restrict__ slabs, int splits, int D, int Kp, int L,
                                             float* __restrict__ dw, float* __restrict__ db) {
@@ -217,6 +247,17 @@ extern "C" int vbx_embed_text_cols(const uint8_t* drop_mask, const long* ids, in
   VBX_REQUIRE(ids && table && out_f16 && T > 0 && E > 0 && col0 >= 0 && ld >= col0 + E, "vbx_embed_text_cols: bad args");
   hipLaunchKernelGGL(embed_text_cols_kernel, dim3(grid_for((long)B * N * E)), dim3(256), 0, ST, drop_mask, ids, T, table, E, null_id,
                      (u16*)out_f16, (u16*)out_bf16, B, N, col0, ld);
+  VBX_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int vbx_embed_text_cols_lens(const uint8_t* drop_mask, const long* ids, int T, const int* tok_lens, const int* key_lens, int R,
+                                        const float* table, int E, long null_id, void* out_f16, void* out_bf16, int B, int N, int col0,
+                                        int ld, void* stream) {
+  VBX_REQUIRE(ids && table && out_f16 && T > 0 && E > 0 && col0 >= 0 && ld >= col0 + E, "vbx_embed_text_cols_lens: bad args");
+  VBX_REQUIRE(tok_lens && key_lens && R >= 0, "vbx_embed_text_cols_lens: needs tok_lens and key_lens (vbx_embed_text_cols is the entry without)");
+  hipLaunchKernelGGL(embed_text_cols_lens_kernel, dim3(grid_for((long)B * N * E)), dim3(256), 0, ST, drop_mask, ids, T, tok_lens, key_lens, R,
+                     table, E, null_id, (u16*)out_f16, (u16*)out_bf16, B, N, col0, ld);
   VBX_LAUNCH_CHECK();
   return 0;
 }

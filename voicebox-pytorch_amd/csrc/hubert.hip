@@ -327,6 +327,167 @@ __global__ __launch_bounds__(256) void hubert_kmeans_kernel(const float* __restr
   }
 }
 
+// ---------------------------------------------------------------------------------------------------- ragged waves (include/vbx.h)
+// Second kernels beside the plain ones above, which are not touched: the same arithmetic in the same order about the row's own
+// length.  lens[b] is clamped here, so no value of the table can become an address.
+VBX_DEV int hb_row_l0(const int* __restrict__ lens, int b, int T, int k0, int s0) {
+  return (min(max(lens[b], k0), T) - k0) / s0 + 1;  // 1 .. L0
+}
+
+// hubert_conv0_stats_kernel over the first L0_b positions: the same 256-position chunks from position 0.  A chunk at or past L0_b
+// leaves before it reads anything (its record is never read either); the last live chunk takes n = L0_b - t0.
+__global__ __launch_bounds__(256) void hubert_conv0_stats_lens_kernel(const float* __restrict__ x, const int* __restrict__ lens,
+                                                                      const float* __restrict__ w, float* __restrict__ rec, int T, int C, int k0,
+                                                                      int s0, int chunks) {
+  __shared__ float sw[HB_MAX_K0 * HB_MAX_C];                        // [tap][C]
+  __shared__ float sx[(HB_CHUNK - 1) * HB_MAX_S0 + HB_MAX_K0];
+  const int tid = threadIdx.x, chunk = blockIdx.x, b = blockIdx.y;
+  const int L0 = hb_row_l0(lens, b, T, k0, s0);
+  const int t0 = chunk * HB_CHUNK;
+  if (t0 >= L0) return;  // uniform over the workgroup
+  const int n = min(HB_CHUNK, L0 - t0);
+  const int span = (n - 1) * s0 + k0;
+  const float* xb = x + (long)b * T + (long)t0 * s0;  // the last tap read is (L0_b - 1) * s0 + k0 - 1 <= lens[b] - 1
+  for (int e = tid; e < span; e += 256) sx[e] = xb[e];
+  for (int e = tid; e < k0 * C; e += 256) {
+    const int tap = e / C, c = e - tap * C;
+    sw[e] = w[c * k0 + tap];
+  }
+  __syncthreads();
+  for (int c = tid; c < C; c += 256) {
+    float K = 0.f, S1 = 0.f, S2 = 0.f;
+    for (int t = 0; t < n; t++) {
+      float acc = 0.f;
+      for (int tap = 0; tap < k0; tap++) acc = fmaf(sw[tap * C + c], sx[t * s0 + tap], acc);
+      if (t == 0) K = acc;
+      const float d = acc - K;
+      S1 += d;
+      S2 = fmaf(d, d, S2);
+    }
+    float* r = rec + (((long)b * chunks + chunk) * C + c) * 3;
+    r[0] = K, r[1] = S1, r[2] = S2;
+  }
+}
+
+// hubert_conv0_finalize_kernel over the row's live chunks only, divided by L0_b; `chunks` is the pitch of the records
+__global__ __launch_bounds__(256) void hubert_conv0_finalize_lens_kernel(const float* __restrict__ rec, const int* __restrict__ lens,
+                                                                         float* __restrict__ stats, int BC, int T, int C, int k0, int s0, int chunks,
+                                                                         float eps) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= BC) return;
+  const int b = i / C, c = i - b * C;
+  const int L0 = hb_row_l0(lens, b, T, k0, s0);
+  const int live = (L0 + HB_CHUNK - 1) / HB_CHUNK;  // <= chunks
+  const float* r = rec + ((long)b * chunks * C + c) * 3;
+  double sum = 0.0;
+  for (int ch = 0; ch < live; ch++) {
+    const int n = min(HB_CHUNK, L0 - ch * HB_CHUNK);
+    const float* q = r + (long)ch * C * 3;
+    sum += (double)n * (double)q[0] + (double)q[1];
+  }
+  const double mean = sum / (double)L0;
+  double m2 = 0.0;
+  for (int ch = 0; ch < live; ch++) {
+    const int n = min(HB_CHUNK, L0 - ch * HB_CHUNK);
+    const float* q = r + (long)ch * C * 3;
+    const double s1 = (double)q[1], mc = (double)q[0] + s1 / (double)n, dm = mc - mean;
+    m2 += ((double)q[2] - s1 * s1 / (double)n) + (double)n * dm * dm;
+  }
+  const double var = m2 > 0.0 ? m2 / (double)L0 : 0.0;
+  stats[2 * (long)i] = (float)mean;
+  stats[2 * (long)i + 1] = (float)(1.0 / sqrt(var + (double)eps));
+}
+
+// hubert_conv0_apply_kernel; a position at or past L0_b stores fp16 zeros and reads neither the wave nor the statistics
+__global__ __launch_bounds__(256) void hubert_conv0_apply_lens_kernel(const float* __restrict__ x, const int* __restrict__ lens,
+                                                                      const float* __restrict__ w, const float* __restrict__ stats,
+                                                                      const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                                      u16* __restrict__ y, int T, int L0, int C, int k0, int s0) {
+  __shared__ float sw[HB_MAX_K0 * HB_MAX_C];
+  const int tid = threadIdx.x, b = blockIdx.y;
+  for (int e = tid; e < k0 * C; e += 256) {
+    const int tap = e / C, c = e - tap * C;
+    sw[e] = w[c * k0 + tap];
+  }
+  __syncthreads();
+  const int groups = C >> 3;
+  const long e = (long)blockIdx.x * 256 + tid;
+  if (e >= (long)L0 * groups) return;
+  const int pos = (int)(e / groups), c0 = (int)(e - (long)pos * groups) * 8;
+  u16* yo = y + ((long)b * L0 + pos) * C + c0;
+  if (pos >= hb_row_l0(lens, b, T, k0, s0)) {
+    *reinterpret_cast<uint4*>(yo) = make_uint4(0u, 0u, 0u, 0u);
+    return;
+  }
+  const float* xb = x + (long)b * T + (long)pos * s0;
+  float acc[8];
+#pragma unroll
+  for (int j = 0; j < 8; j++) acc[j] = 0.f;
+  for (int tap = 0; tap < k0; tap++) {
+    const float xv = xb[tap];
+#pragma unroll
+    for (int j = 0; j < 8; j++) acc[j] = fmaf(sw[tap * C + c0 + j], xv, acc[j]);
+  }
+  const float* st = stats + 2 * ((long)b * C + c0);
+#pragma unroll
+  for (int j = 0; j < 8; j++) acc[j] = gelu_erf_libm(fmaf((acc[j] - st[2 * j]) * st[2 * j + 1], gamma[c0 + j], beta[c0 + j]));
+  *reinterpret_cast<uint4*>(yo) =
+      make_uint4(pack_f16x2(acc[0], acc[1]), pack_f16x2(acc[2], acc[3]), pack_f16x2(acc[4], acc[5]), pack_f16x2(acc[6], acc[7]));
+}
+
+// hubert_posconv_kernel with the row's own frame count N_b = lens[b] (clamped into 1 .. N): positions >= N_b are staged as zeros, as
+// Conv1d(padding = k / 2) of the row alone sees them, whatever x holds there; output rows N_b .. N - 1 are stored as 0.0 without a
+// product, and a tile wholly past N_b stages nothing.
+struct HbPosLens : HbPos {
+  const int* lens;  // [B] frames
+};
+template <int MG>
+__global__ __launch_bounds__(256) void hubert_posconv_lens_kernel(HbPosLens p) {
+  extern __shared__ __attribute__((aligned(16))) u16 hb_lds[];
+  const int tid = threadIdx.x, b = blockIdx.y;
+  const int g = blockIdx.x % p.G, t0 = (blockIdx.x / p.G) * p.TT;
+  const int Nb = min(max(p.lens[b], 1), p.N);
+  if (t0 >= Nb) {  // uniform over the workgroup
+    const int rows = min(p.TT, p.N - t0), c4 = p.Dg >> 2;
+    for (int e = tid; e < rows * c4; e += 256) {
+      const int r = e / c4, c = (e - r * c4) * 4;
+      *reinterpret_cast<float4*>(p.y + ((long)b * p.N + t0 + r) * p.D + g * p.Dg + c) = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    return;
+  }
+  const int ld = p.Dg + SN_PADH, c8 = p.Dg >> 3;
+  const int span = p.TT - 1 + p.k, pad = p.k >> 1;
+  const float* xb = p.x + (long)b * p.N * p.D + g * p.Dg;
+  for (int e = tid; e < span * c8; e += 256) {
+    const int pos = e / c8, c = (e - pos * c8) * 8;
+    const int i = t0 - pad + pos;
+    uint4 v = make_uint4(0u, 0u, 0u, 0u);
+    if (i >= 0 && i < Nb) {
+      const float4 lo = *reinterpret_cast<const float4*>(xb + (long)i * p.D + c), hi = *reinterpret_cast<const float4*>(xb + (long)i * p.D + c + 4);
+      v = make_uint4(pack_f16x2_sat(lo.x, lo.y), pack_f16x2_sat(lo.z, lo.w), pack_f16x2_sat(hi.x, hi.y), pack_f16x2_sat(hi.z, hi.w));
+    }
+    *reinterpret_cast<uint4*>(hb_lds + pos * ld + c) = v;
+  }
+  __syncthreads();
+  auto rows = [&](int kk, const u16*& base, int& ldr) __attribute__((always_inline)) {
+    const int tap = kk / p.Dg, c = kk - tap * p.Dg;
+    base = hb_lds + tap * ld + c, ldr = ld;
+  };
+  auto store = [&](int n) __attribute__((always_inline)) {
+    return [&, n, bv = p.bias[g * p.Dg + n]](int m, float v) __attribute__((always_inline)) {
+      const int t = t0 + m;
+      if (t >= p.N) return;
+      const long o = ((long)b * p.N + t) * p.D + g * p.Dg + n;
+      if (t >= Nb) {
+        p.y[o] = 0.f;
+        return;
+      }
+      p.y[o] = gelu_erf_libm(v + bv) + p.x[o];
+    };
+  };
+  sn_tile_product<MG, true>(p.w + (long)g * p.Dg * p.k * p.Dg, p.Dg, p.k * p.Dg, p.TT >> 4, rows, store);
+}
+
 }  // namespace
 
 extern "C" int vbx_hubert_conv0_chunks(int L0) { return L0 >= 1 ? cdiv(L0, HB_CHUNK) : 0; }
@@ -462,4 +623,55 @@ extern "C" int vbx_kmeans_assign(const float* h, const float* centers, long long
   hipLaunchKernelGGL(hubert_kmeans_kernel, dim3(cdiv(M, HB_KM_ROWS)), dim3(256), 0, (hipStream_t)stream, h, centers, ids, M, D, K);
   VBX_LAUNCH_CHECK();
   return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------- ragged waves: the entries
+extern "C" int vbx_hubert_conv0_stats_lens(const float* wave, const int* lens, const float* w, float* records, float* stats, int B, long T, int C,
+                                           int k0, int s0, float eps, void* stream) {
+  VBX_REQUIRE(wave && w && records && stats, "vbx_hubert_conv0_stats_lens: null operand");
+  VBX_REQUIRE(lens, "vbx_hubert_conv0_stats_lens: lens is NULL (vbx_hubert_conv0_stats is the entry without lengths)");
+  long L0;
+  if (int rc = hb_conv0_check("vbx_hubert_conv0_stats_lens", B, T, C, k0, s0, &L0)) return rc;
+  const int chunks = cdiv(L0, HB_CHUNK);
+  hipLaunchKernelGGL(hubert_conv0_stats_lens_kernel, dim3(chunks, B), dim3(256), 0, (hipStream_t)stream, wave, lens, w, records, (int)T, C, k0, s0,
+                     chunks);
+  VBX_LAUNCH_CHECK();
+  hipLaunchKernelGGL(hubert_conv0_finalize_lens_kernel, dim3(cdiv((long)B * C, 256)), dim3(256), 0, (hipStream_t)stream, records, lens, stats, B * C,
+                     (int)T, C, k0, s0, chunks, eps);
+  VBX_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int vbx_hubert_conv0_apply_lens(const float* wave, const int* lens, const float* w, const float* stats, const float* gamma,
+                                           const float* beta, void* y_f16, int B, long T, int C, int k0, int s0, void* stream) {
+  VBX_REQUIRE(wave && w && stats && gamma && beta && y_f16, "vbx_hubert_conv0_apply_lens: null operand");
+  VBX_REQUIRE(lens, "vbx_hubert_conv0_apply_lens: lens is NULL (vbx_hubert_conv0_apply is the entry without lengths)");
+  long L0;
+  if (int rc = hb_conv0_check("vbx_hubert_conv0_apply_lens", B, T, C, k0, s0, &L0)) return rc;
+  hipLaunchKernelGGL(hubert_conv0_apply_lens_kernel, dim3(cdiv(L0 * (C / 8), 256), B), dim3(256), 0, (hipStream_t)stream, wave, lens, w, stats, gamma,
+                     beta, (u16*)y_f16, (int)T, (int)L0, C, k0, s0);
+  VBX_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int vbx_hubert_posconv_lens(const float* x, const int* lens, const void* w_f16, const float* bias, float* y, int B, int N, int D,
+                                       int groups, int k, void* stream) {
+  VBX_REQUIRE(x && w_f16 && bias && y && x != y, "vbx_hubert_posconv_lens: null operand, or y aliases x");
+  VBX_REQUIRE(lens, "vbx_hubert_posconv_lens: lens is NULL (vbx_hubert_posconv is the entry without lengths)");
+  VBX_REQUIRE(B >= 1 && B <= 65535 && N >= 1 && N < (1 << 24), "vbx_hubert_posconv_lens: need B in 1 .. 65535 and N in 1 .. 2^24");
+  VBX_REQUIRE(groups >= 1 && D >= groups && D % groups == 0, "vbx_hubert_posconv_lens: groups must divide D");
+  const int Dg = D / groups;
+  if (int rc = hb_pos_check(Dg, k)) return rc;
+  int TT = hb_pos_tile(Dg, k);
+  VBX_REQUIRE(TT > 0, "vbx_hubert_posconv_lens: 16 output positions of this convolution do not fit the LDS");
+  while (TT > 16 && TT / 2 >= N) TT >>= 1;  // the plain entry's tile at N: the grid does not depend on the lengths
+  HbPosLens p;
+  p.x = x, p.w = (const u16*)w_f16, p.bias = bias, p.y = y, p.N = N, p.D = D, p.Dg = Dg, p.G = groups, p.k = k, p.TT = TT, p.lens = lens;
+  const long blocks = (long)cdiv(N, TT) * groups;
+  VBX_REQUIRE(blocks < (1L << 31), "vbx_hubert_posconv_lens: too many tiles");
+  const size_t bytes = hb_pos_lds(TT, Dg, k);
+  const int MG = sn_blocks_per_item((Dg + 15) / 16, TT / 16);
+  if (MG == 4) return sn_launch<hubert_posconv_lens_kernel<4>>("vbx_hubert_posconv_lens", p, (int)blocks, B, bytes, (hipStream_t)stream);
+  if (MG == 2) return sn_launch<hubert_posconv_lens_kernel<2>>("vbx_hubert_posconv_lens", p, (int)blocks, B, bytes, (hipStream_t)stream);
+  return sn_launch<hubert_posconv_lens_kernel<1>>("vbx_hubert_posconv_lens", p, (int)blocks, B, bytes, (hipStream_t)stream);
 }

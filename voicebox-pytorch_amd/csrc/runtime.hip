@@ -597,6 +597,9 @@ extern "C" int vbx_model_forward(const vbx_model* m, const vbx_io* io, void* str
   VBX_REQUIRE(!io->target || (io->loss_mask && io->loss), "vbx_model_forward: target needs loss_mask and loss");
   VBX_REQUIRE((io->attn_mask == nullptr) == (io->attn_mask_p == nullptr), "vbx_model_forward: attn_mask and attn_mask_p go together");
   VBX_REQUIRE(!io->key_lens || io->attn_mask_p, "vbx_model_forward: key_lens restates a prefix attn_mask_p, which must be given too");
+  VBX_REQUIRE(!io->tok_lens || io->key_lens, "vbx_model_forward: tok_lens needs key_lens (a row's tokens are resized to its own frames)");
+  VBX_REQUIRE(!io->tok_lens || (!m->precise && !m->packed && !m->stack_only),
+              "vbx_model_forward: tok_lens is not served in precise mode, on packed rows or by a bare stack");
   if (m->packed) {  // (training / precise / gateloop / stack_only: check_model)
     VBX_REQUIRE(!io->attn_mask && !io->attn_mask_p && !io->key_lens && !io->target,
                 "vbx_model_forward: packed rows take no attn_mask, key_lens or target -- the segment tables say which rows are live");
@@ -647,11 +650,20 @@ extern "C" int vbx_model_forward(const vbx_model* m, const vbx_io* io, void* str
                          a.embed_in, a.xcb, d.B, d.N, d.Lc, d.D, d.E, stream));
     if (d.E) {
       VBX_REQUIRE(io->cond_ids && io->T > 0, "vbx_model_forward: a text-conditioned model needs cond_ids");
+      if (io->tok_lens)  // per-row token resize: row b's tok_lens[b] ids over its own key_lens[b] - R frames
+        CK(vbx_embed_text_cols_lens(io->drop_mask, io->cond_ids, io->T, io->tok_lens, io->key_lens, d.R, P + G[VBX_P_CEMB], d.E,
+                                    io->null_id, a.embed_inh, a.embed_in, d.B, d.N, d.D, d.Ke, stream));
+      else
       CK(vbx_embed_text_cols(io->drop_mask, io->cond_ids, io->T, P + G[VBX_P_CEMB], d.E, io->null_id, a.embed_inh, a.embed_in, d.B,
                              d.N, d.D, d.Ke, stream));
     }
   } else if (d.E) {
     VBX_REQUIRE(io->cond_ids && io->T > 0, "vbx_model_forward: a text-conditioned model needs cond_ids");
+    if (io->tok_lens)
+      CK(vbx_pack_embed_input_text_lens(io->x, io->cond, io->cond_mask, io->drop_mask, io->null_cond, io->cond_ids, io->T, io->tok_lens,
+                                        io->key_lens, d.R, P + G[VBX_P_CEMB], d.E, io->null_id, a.embed_inh, a.embed_in, d.B, d.N, d.Din,
+                                        stream));
+    else
     CK(vbx_pack_embed_input_text(io->x, io->cond, io->cond_mask, io->drop_mask, io->null_cond, io->cond_ids, io->T,
                                  P + G[VBX_P_CEMB], d.E, io->null_id, a.embed_inh, a.embed_in, d.B, d.N, d.Din, stream));
   } else {
@@ -1092,6 +1104,15 @@ extern "C" int vbx_model_backward_layer(const vbx_model* m, const vbx_io* io, in
                             a.ada_scratch, d.B, d.Th, 4 * d.D, l == d.L - 1 ? 0 : 1, stream));
 }
 
+// the scatter of d(cond_emb) into the table gradient: through the row's own resize weights when the forward ran with io->tok_lens
+static int cond_emb_bwd_io(const vbx_io* io, const void* demb, int R, float* gtable, int B, int N, int E, void* stream) {
+  if (io->tok_lens) {
+    VBX_REQUIRE(io->key_lens, "vbx_model_backward_embed: tok_lens needs key_lens");
+    return vbx_cond_emb_bwd_lens(demb, E, io->cond_ids, io->T, io->tok_lens, io->key_lens, R, io->drop_mask, io->null_id, gtable, B, N, E, stream);
+  }
+  return vbx_cond_emb_bwd(demb, E, io->cond_ids, io->T, io->drop_mask, io->null_id, gtable, B, N, E, stream);
+}
+
 extern "C" int vbx_model_backward_embed(const vbx_model* m, const vbx_io* io, void* stream) {
   CK(check_model(m));
   VBX_REQUIRE(m->training && m->grads && io && (m->stack_only ? io->dx != nullptr : io->times != nullptr),
@@ -1139,7 +1160,7 @@ extern "C" int vbx_model_backward_embed(const vbx_model* m, const vbx_io* io, vo
         vbx_set_error("vbx_model_backward_embed: memset of the embedding gradient failed");
         return VBX_EINVAL;
       }
-      CK(vbx_cond_emb_bwd(a.demb, d.E, io->cond_ids, io->T, io->drop_mask, io->null_id, Gd + G[VBX_P_CEMB], d.B, d.N, d.E, stream));
+      CK(cond_emb_bwd_io(io, a.demb, d.R, Gd + G[VBX_P_CEMB], d.B, d.N, d.E, stream));
     }
     CK(vbx_colsum_f32_partials(a.de, (int)d.M0, d.D, d.D, a.cs_scratch, stream));
     CK(vbx_embed_bwd_tail2(a.slabs, g.splits, d.D, d.Ke, Gd + G[VBX_P_EMBW], a.cs_scratch, d.D, Gd + G[VBX_P_EMBB], a.tscratch, d.B, d.D,
@@ -1160,7 +1181,7 @@ extern "C" int vbx_model_backward_embed(const vbx_model* m, const vbx_io* io, vo
       vbx_set_error("vbx_model_backward_embed: memset of the embedding gradient failed");
       return VBX_EINVAL;
     }
-    CK(vbx_cond_emb_bwd(a.demb, d.E, io->cond_ids, io->T, io->drop_mask, io->null_id, Gd + G[VBX_P_CEMB], d.B, d.N, d.E, stream));
+    CK(cond_emb_bwd_io(io, a.demb, d.R, Gd + G[VBX_P_CEMB], d.B, d.N, d.E, stream));
   }
   if (d.Lc) {
     // d(x') and d(cond') = de . W_embed[:, 0:D] / [:, D+E:], stacked [2 M0, D]; the rows of cond that pass no gradient are zero in the

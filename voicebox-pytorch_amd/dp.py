@@ -646,7 +646,7 @@ class TrainStep:
 
     # -- gradient accumulation with a deferred exchange (VoiceBoxTrainer.train_step, trainer.py:258-272: every micro-batch but
     #    the last runs under accelerator.no_sync, the loss is divided by grad_accum_every)
-    def accumulate(self, x1, weight, mask=None, cond_token_ids=None, input_sampling_rate=None, lens=None, wave_lens=None):
+    def accumulate(self, x1, weight, mask=None, cond_token_ids=None, input_sampling_rate=None, lens=None, wave_lens=None, token_lens=None):
         """forward + backward of one micro-batch; gradients * weight are added to the accumulation buffer (no exchange).
         lens: see step."""
         self._refuse_inside_ema_weights("accumulate")
@@ -656,7 +656,7 @@ class TrainStep:
             self.acc_coef = torch.zeros(1, device=self.gflat.device)
             self.acc_pending = False
         loss = self._forward_backward(x1, mask, cond_token_ids, on_stage=None, input_sampling_rate=input_sampling_rate, lens=lens,
-                                      wave_lens=wave_lens)
+                                      wave_lens=wave_lens, token_lens=token_lens)
         self.acc_coef.fill_(float(weight))
         n = self.gflat.numel()
         _lib.call("vbx_axpy_dev", self.gacc, self.gflat, self.acc_coef, 0, self.gacc, n, _lib.current_stream())
@@ -716,7 +716,7 @@ class TrainStep:
         self._keep_factors = (dada_all, temb_all)  # alive until the launches have run
 
     def accumulate_last_and_apply(self, x1, weight, mask=None, cond_token_ids=None, lr=None, input_sampling_rate=None, lens=None,
-                                  wave_lens=None):
+                                  wave_lens=None, token_lens=None):
         """The LAST micro-batch of an accumulation window, with the exchange overlapped with its backward (DDP leaves `no_sync`
         for exactly this micro-batch, trainer.py:258-272): as each backward stage completes, its slice of the accumulator is
         folded in (g = acc + weight * g) and the bucketed all-reduce of that slice starts while earlier layers are still running --
@@ -735,7 +735,7 @@ class TrainStep:
                 red.stage_done(i, rng)
 
         loss = self._forward_backward(x1, mask, cond_token_ids, on_stage=on_stage, input_sampling_rate=input_sampling_rate, lens=lens,
-                                      wave_lens=wave_lens)
+                                      wave_lens=wave_lens, token_lens=token_lens)
         red.finish()
         self._stage_buf = red.stage_buf
         self.gacc.zero_()
@@ -761,16 +761,32 @@ class TrainStep:
         self._clip_adam(self._last_eng, lr)
 
     def _forward_backward(self, x1, mask, cond_token_ids, on_stage, adaln_factors=False, sq_fold=False, input_sampling_rate=None,
-                          lens=None, wave_lens=None):
+                          lens=None, wave_lens=None, token_lens=None):
+        from . import wave_lens as wl
+        from .engine import precise_enabled
+
         vb, w = self.vb, self.wrapper
         dev = self.fp.flat.device
         st = _lib.current_stream
         key_lens = None
+        # per-row token counts (wave_lens.py): every refusal, and the host check of the values, before anything is launched
+        wl.refuse_token_lens(token_lens, lens is not None or wave_lens is not None, cond_token_ids if vb.condition_on_text else None,
+                             None, "TrainStep")
+        if token_lens is not None:
+            if precise_enabled():
+                raise NotImplementedError("TrainStep: token_lens is not served in precise mode")
+            token_lens = wl.token_lens_device(token_lens, cond_token_ids.shape[0], cond_token_ids.shape[-1], dev, "TrainStep")
         if wave_lens is not None:  # a ragged batch of WAVES (wave_lens.py): refusals first, rows encoded as the row alone, then lens=
-            from . import wave_lens as wl
-
+            w2v = getattr(w, "wav2vec", None)
+            from_w2v = cond_token_ids is None and vb.condition_on_text and w2v is not None
             wl.refuse(wave_lens, x1, None, lens, mask, vb.audio_enc_dec, "TrainStep",
-                      wav2vec_ids=cond_token_ids is None and vb.condition_on_text and getattr(w, "wav2vec", None) is not None)
+                      wav2vec_ids=from_w2v and wl.wav2vec_lacks(w2v) is not None, wav2vec=w2v)
+            if from_w2v:  # the ids of every row alone and their counts (HubertWithKmeans(lens=)), from the waves as they were given
+                if precise_enabled():
+                    raise NotImplementedError("TrainStep: wave_lens with token ids from wav2vec= resizes each row's ids to its own "
+                                              "frames, which precise mode does not serve")
+                cond_token_ids, token_lens = w.wav2vec_token_ids(x1, input_sampling_rate, wave_lens=wave_lens)
+                token_lens = wl.token_lens_device(token_lens, cond_token_ids.shape[0], cond_token_ids.shape[-1], dev, "TrainStep")
             x1, _, lens = w.encode_raw_audio(x1, None, input_sampling_rate, wave_lens=wave_lens)
         if lens is not None:  # a ragged batch by lengths (train_lens.py): refusals and host validation before anything is launched
             from . import train_lens
@@ -816,7 +832,7 @@ class TrainStep:
                 # voicebox_pytorch.py:1064-1066: the key-padding mask follows the token ids to frame resolution
                 m4 = mask.float()[:, None, :, None]
                 mask = torch.nn.functional.interpolate(m4, (N, 1), mode="bilinear")[:, 0, :, 0].to(torch.bool)
-            text = (ids, vb.null_cond_id, drop, vb.null_cond)
+            text = (ids, vb.null_cond_id, drop, vb.null_cond, token_lens)
         if mask is not None and not pad_in:
             loss_mask = cond_mask & mask  # reduce_masks_with_and (:1099)
         if self.length_bucket > 0 and N % self.length_bucket and text is None:  # (token ids are resized to the frame count: :1055-1062)
@@ -994,7 +1010,7 @@ class TrainStep:
             state.needs_apply = True
             state.apply()  # W_eff = W0 + s . B . A into the master slots; bumps the weights epoch: every engine and sampler repacks
 
-    def step(self, x1, mask=None, lr=None, cond_token_ids=None, input_sampling_rate=None, lens=None, wave_lens=None):
+    def step(self, x1, mask=None, lr=None, cond_token_ids=None, input_sampling_rate=None, lens=None, wave_lens=None, token_lens=None):
         """x1: (B_local, frames, dim) on this rank's GPU, or a wave batch (B_local, samples) for a model built with audio_enc_dec
         (cond_token_ids (B_local, tokens) for a text-conditioned model); input_sampling_rate: the rate of such waves, for a wrapper built
         with resample_input=True.
@@ -1002,7 +1018,10 @@ class TrainStep:
         mask = arange(frames) < lens[:, None], bit for bit, with the attention forward and backward stopping at each row's length
         (ConditionalFlowMatcherWrapper.forward).  With text conditioning it counts frames, not tokens.
         wave_lens: x1 is a padded batch of waves and row b holds wave_lens[b] real samples at the rate the waves are given in -- every
-        row is encoded as the row alone and the step runs as step(latents, lens=codec.frame_lens(...)); not with lens or mask.
+        row is encoded as the row alone and the step runs as step(latents, lens=codec.frame_lens(...)); not with lens or mask.  A
+        text-conditioned model without cond_token_ids takes them, and token_lens, from a wav2vec= that serves lengths.
+        token_lens: with lens or wave_lens and cond_token_ids, the token count of each row -- row b's first token_lens[b] ids are
+        resized to row b's own frames (ConditionalFlowMatcherWrapper.forward).
         Returns the (un-synchronised) local loss tensor."""
         # --- backward with overlapped gradient exchange
         self._refuse_inside_ema_weights("step")
@@ -1014,7 +1033,8 @@ class TrainStep:
         # (a partly frozen or adapted model takes the plain path: the fold's partials cover all four big matrices of every layer)
         fold = factors and not self.exchange and os.environ.get("VBX_SUMSQ_FOLD", "1") != "0" and self._filter is None
         loss = self._forward_backward(x1, mask, cond_token_ids, on_stage=red.stage_done if self.exchange else None, adaln_factors=factors,
-                                      sq_fold=fold, input_sampling_rate=input_sampling_rate, lens=lens, wave_lens=wave_lens)
+                                      sq_fold=fold, input_sampling_rate=input_sampling_rate, lens=lens, wave_lens=wave_lens,
+                                      token_lens=token_lens)
         if factors and self.exchange:  # the factors travel (one small all-gather) while the last buckets are still in flight
             self._exchange_adaln_factors(self._last_eng)
         red.finish()

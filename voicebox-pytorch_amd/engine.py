@@ -30,7 +30,7 @@ class VbxIO(C.Structure):
                 ("times", P), ("target", P), ("pred", P), ("loss", P), ("cond_ids", P), ("T", I), ("null_id", C.c_long),
                 ("drop_mask", P), ("null_cond", P), ("dx", P), ("dcond", P), ("dropout", I), ("drop_seed", C.c_ulonglong),
                 ("ada_table", P), ("ada_counter", P), ("ada_slot", I), ("ada_stride", I), ("key_lens", P),
-                ("seg_start", P), ("seg_klen", P), ("tile_seg", P)]
+                ("seg_start", P), ("seg_klen", P), ("tile_seg", P), ("tok_lens", P)]
 
 
 class VbxAdamSeg(C.Structure):
@@ -500,7 +500,8 @@ class Engine:
                 attn_mask_p=None, key_lens=None, segs=None):
         """All tensors on self.device, fp32 contiguous / bool.  Returns the loss tensor (1,) if target is given,
         else the prediction (B,N,D).  text (text-conditioned models): (ids int64 (B,T), null_id, drop_mask bool (B,) or None,
-        null_cond fp32 (D,)).  ada (inference, the sampler): (table fp32 [stride * intervals, L, 4 * D], counter int32 [1], slot, stride) --
+        null_cond fp32 (D,)[, tok_lens int32 (B,) or None: row b's own token count, resized to its own key_lens[b] - R frames
+        (vbx_io.tok_lens); needs key_lens]).  ada (inference, the sampler): (table fp32 [stride * intervals, L, 4 * D], counter int32 [1], slot, stride) --
         the adaLN projections of every time point of the ODE grid, precomputed (stride >= 1 time points per interval, this forward at
         row stride * counter + slot); `times` is then not read.  attn_mask_p (the sampler, with attn_mask): the caller's own uint8
         [B, N + R] copy of attn_mask behind R ones -- a static buffer whose address a captured graph may keep -- instead of the copy
@@ -551,14 +552,19 @@ class Engine:
             pred = pred_out if pred_out is not None else torch.empty(B, N, D, dtype=torch.float32, device=self.device)
             io.pred = pred.data_ptr()
         if self.cfg.get("E", 0):
-            ids, null_id, drop, null_cond = text
+            ids, null_id, drop, null_cond, tok_lens = text if len(text) == 5 else tuple(text) + (None,)
             ids = ids.to(torch.int64).contiguous()
+            if tok_lens is not None:
+                if self.precise or self.packed:
+                    raise NotImplementedError("token_lens is not served in precise mode or on packed rows")
+                assert key_lens is not None and tok_lens.dtype == torch.int32 and tok_lens.shape == (B,) and tok_lens.is_contiguous()
+            io.tok_lens = tok_lens.data_ptr() if tok_lens is not None else None
             drop8 = _u8(drop) if drop is not None else None
             null_cond = null_cond.detach().to(torch.float32).contiguous()
             io.cond_ids, io.T, io.null_id = ids.data_ptr(), int(ids.shape[1]), int(null_id)
             io.drop_mask = drop8.data_ptr() if drop8 is not None else None
             io.null_cond = null_cond.data_ptr()
-            text = (ids, drop8, null_cond)
+            text = (ids, drop8, null_cond, tok_lens)
         self._keep = (x, cond, cm, am, amp, lm, times, target, pred, text, ada, key_lens)  # keep inputs alive until backward
         self.generation += 1
         self._draw_dropout_seed()
@@ -620,7 +626,7 @@ class Engine:
         io.cond_mask = io.times = io.target = io.loss_mask = io.loss = io.dx = io.dcond = None
         io.attn_mask = am.data_ptr() if am is not None else None
         io.attn_mask_p = amp.data_ptr() if amp is not None else None
-        io.key_lens = None
+        io.key_lens = io.tok_lens = None
         io.pred = out.data_ptr()
         self._keep = (x, cond, am, amp, out)
         self.generation += 1

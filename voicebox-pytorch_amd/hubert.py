@@ -16,7 +16,8 @@ the restatement (tests/test_hubert_gpu.py, profiles/hubert_parity.txt).  fairseq
 including the claim that fairseq's output_layer = L is hidden_states[L].
 
 Device path (csrc/hubert.hip, csrc/gemm.hip, csrc/attn.hip): a fixed launch sequence without host synchronisation; where each tensor
-is rounded is stated in include/vbx.h.  Inference only, GPU tensors only, rows of a batch of equal length (no padding mask).
+is rounded is stated in include/vbx.h.  Inference only, GPU tensors only.  Rows of unequal length: lens= (per-row sample counts; include/vbx.h
+"ragged waves") makes every row of a padded batch the row it would be alone; a padding / attention mask is not served.
 """
 import math
 
@@ -25,6 +26,7 @@ from torch import nn
 
 from . import _lib
 from ._packing import PackedWeights
+from .wave_lens import device_lens, map_lens, resample_lens
 
 _G0, _G1 = "encoder.pos_conv_embed.conv.parametrizations.weight.original0", "encoder.pos_conv_embed.conv.parametrizations.weight.original1"
 _LDS_MAX = 160 * 1024  # csrc/seanet_tile.hpp: SN_LDS_MAX
@@ -287,39 +289,107 @@ class HubertWithKmeans(PackedWeights, nn.Module):
         if rc != 0:
             raise _lib.VbxError(f"vbx_gemm failed (rc={rc}): {_lib.lib().vbx_last_error().decode()}")
 
+    def _products(self):
+        """the matrix products of a call, name -> (epilogue, N, K, adds a residual): the one table both the launches (_product) and
+        gemm_routes read"""
+        C, D, I = self.conv_dim[0], self.hidden_size, self.intermediate_size
+        return {"projection": (_lib.VBX_EPI_F32, D, C, False), "qkv": (_lib.VBX_EPI_F32, 3 * D, D, False),
+                "out_proj": (_lib.VBX_EPI_F32, D, D, True), "intermediate": (_lib.VBX_EPI_GELU, I, D, False),
+                "output": (_lib.VBX_EPI_F32, D, I, True)}
+
+    def _product(self, name, M, A, B, C, bias, resid=None):
+        epi, N, K, adds = self._products()[name]
+        assert adds == (resid is not None), name
+        self._gemm(epi, M, N, K, A, B, C, bias, resid=resid)
+
+    def gemm_routes(self, rows):
+        """vbx_gemm_route's answer for each product of a call with `rows` = batch * frames rows, in the order of _products().  A row
+        of a batch under lens= is bit-equal to the row alone where both calls get the same answers (include/vbx.h, "ragged waves")."""
+        out = []
+        for epi, N, K, adds in self._products().values():
+            d = _lib.GemmDesc()
+            d.mode, d.epilogue, d.M, d.N, d.K, d.lda, d.ldb, d.ldc, d.f16 = _lib.VBX_GEMM_NT, epi, rows, N, K, K, K, N, 1
+            d.A = d.B = d.C = d.bias = 4096  # the route looks at pointers for null and alignment only
+            d.resid = 4096 if adds else None
+            out.append(_lib.call_value("vbx_gemm_route", d))
+        return tuple(out)
+
     def frames(self, samples):
         """frames of a wave of `samples` samples at target_sample_hz (0 or less: shorter than one frame)"""
         for k, s in zip(self.conv_kernel, self.conv_stride):
             samples = (samples - k) // s + 1 if samples >= k else 0
         return samples
 
-    def _prepare(self, wave, input_sample_hz, attention_mask):
+    def min_samples(self):
+        """the smallest sample count that gives one frame"""
+        n = 1
+        for k, s in zip(reversed(self.conv_kernel), reversed(self.conv_stride)):
+            n = (n - 1) * s + k
+        return n
+
+    def frame_lens(self, lens):
+        """frames of rows of that many samples at target_sample_hz: floored to seq_len_multiple_of as the wave is curtailed, then
+        through the convolution chain.  A list, a CPU tensor or a device tensor; the same kind back."""
+        m = self.seq_len_multiple_of
+
+        def chain(l):
+            if m is not None:
+                l = l // m * m
+            for k, s in zip(self.conv_kernel, self.conv_stride):
+                l = (l - k) // s + 1
+            return l
+        return map_lens(lens, chain)
+
+    def _target_lens(self, lens, B, T, resampled, input_sample_hz, device):
+        """lens at the rate the wave [B, T] is given in -> int32 [B] on the device at target_sample_hz, curtailed like the wave, inside
+        min_samples() .. the prepared wave's length: host values are checked (ValueError naming the row), a device tensor is clamped"""
+        m = self.seq_len_multiple_of
+        if resampled:
+            lens, T = resample_lens(lens, input_sample_hz, self.target_sample_hz), resample_lens([T], input_sample_hz, self.target_sample_hz)[0]
+        if m is not None:
+            lens, T = map_lens(lens, lambda l: l // m * m), T // m * m
+        if self.frames(T) < 1:
+            raise NotImplementedError(f"HubertWithKmeans: a wave of {T} samples is shorter than one frame")
+        return device_lens(lens, B, T, self.min_samples(), device, "HubertWithKmeans")
+
+    def _prepare(self, wave, input_sample_hz, attention_mask, lens=None):
+        """-> (wave fp32 [B, T] at target_sample_hz, lens int32 [B] on the device at that rate, or None)"""
         if attention_mask is not None:
             raise NotImplementedError("HubertWithKmeans: an attention / padding mask is not served: rows of a batch are of equal length")
         if not isinstance(wave, torch.Tensor) or wave.ndim not in (2, 3) or (wave.ndim == 3 and wave.shape[1] != 1):
             raise ValueError("HubertWithKmeans takes a wave (batch, samples) or (batch, 1, samples)")
-        if wave.device.type != "cuda":
-            raise _lib.VbxError(f"HubertWithKmeans runs only on an MI355X (gfx950) through libvbx_hip.so; the wave is on '{wave.device}'")
         if wave.ndim == 3:
             wave = wave[:, 0]
+        resampled = input_sample_hz is not None and input_sample_hz != self.target_sample_hz
+        lens_in = lens
+        if lens is not None:  # checked (host values) or clamped (a device tensor) before anything else
+            if resampled:
+                lens_in = device_lens(lens, wave.shape[0], wave.shape[1], 1, wave.device, "HubertWithKmeans")
+            lens = self._target_lens(lens, wave.shape[0], wave.shape[1], resampled, input_sample_hz, wave.device)
+        if wave.device.type != "cuda":
+            raise _lib.VbxError(f"HubertWithKmeans runs only on an MI355X (gfx950) through libvbx_hip.so; the wave is on '{wave.device}'")
         wave = wave.detach().to(torch.float32)
-        if input_sample_hz is not None and input_sample_hz != self.target_sample_hz:
+        if resampled:
             from .codec import resample
 
-            wave = resample(wave, input_sample_hz, self.target_sample_hz)
+            wave = resample(wave, input_sample_hz, self.target_sample_hz, lens=lens_in)
         if self.seq_len_multiple_of is not None:
             wave = wave[:, :wave.shape[1] // self.seq_len_multiple_of * self.seq_len_multiple_of]
         if self.frames(wave.shape[1]) < 1:
             raise NotImplementedError(f"HubertWithKmeans: a wave of {wave.shape[1]} samples is shorter than one frame")
         if self.cluster_centers.device != wave.device:
             self.to(wave.device)
-        return wave.contiguous()
+        return wave.contiguous(), lens
 
     @torch.no_grad()
-    def features(self, wav_input, input_sample_hz=None, attention_mask=None):
-        return self._features(self._prepare(wav_input, input_sample_hz, attention_mask))
+    def features(self, wav_input, input_sample_hz=None, attention_mask=None, lens=None):
+        """lens: per-row sample counts of a padded batch at the rate the wave is given in (a list or CPU tensor is validated, a
+        device tensor clamped; no host synchronisation): row b is the row alone -- bit-equal to features(wave[b:b+1, :len_b])[0] up to
+        frame_lens(...)[b] frames, exactly 0.0 past them, whatever the padding holds."""
+        return self._features(*self._prepare(wav_input, input_sample_hz, attention_mask, lens))[0]
 
-    def _features(self, wave):
+    def _features(self, wave, lens=None):
+        """-> (features fp32 [B, N, D], dead bool [B, N] -- the frames at or past each row's own count, zero-filled -- or None)"""
         w = self._cached(self._pack)
         st, dev, eps = _lib.current_stream(), wave.device, self.layer_norm_eps
         B, T = wave.shape
@@ -329,9 +399,14 @@ class HubertWithKmeans(PackedWeights, nn.Module):
         k0, s0 = self.conv_kernel[0], self.conv_stride[0]
         L = (T - k0) // s0 + 1
         rec, stats = f32(B, _lib.lib().vbx_hubert_conv0_chunks(L), C, 3), f32(B, C, 2)
-        _lib.call("vbx_hubert_conv0_stats", wave, w["w0"], rec, stats, B, T, C, k0, s0, eps, st)
         a = f16(B, L, C)
-        _lib.call("vbx_hubert_conv0_apply", wave, w["w0"], stats, w["gnw"], w["gnb"], a, B, T, C, k0, s0, st)
+        if lens is None:
+            _lib.call("vbx_hubert_conv0_stats", wave, w["w0"], rec, stats, B, T, C, k0, s0, eps, st)
+            _lib.call("vbx_hubert_conv0_apply", wave, w["w0"], stats, w["gnw"], w["gnb"], a, B, T, C, k0, s0, st)
+        else:  # ragged waves (include/vbx.h): statistics over the row's own positions, zeros past them
+            _lib.call("vbx_hubert_conv0_stats_lens", wave, lens, w["w0"], rec, stats, B, T, C, k0, s0, eps, st)
+            _lib.call("vbx_hubert_conv0_apply_lens", wave, lens, w["w0"], stats, w["gnw"], w["gnb"], a, B, T, C, k0, s0, st)
+            flens = self.frame_lens(lens).contiguous()  # int32 [B] on the device, 1 .. N
         for kk, wc in zip(self.conv_kernel[1:], w["convs"]):
             Lo = (L - kk) // 2 + 1
             y = f16(B, Lo, C)
@@ -341,25 +416,39 @@ class HubertWithKmeans(PackedWeights, nn.Module):
         a16 = f16(M, C)
         _lib.call("vbx_hubert_layernorm16", a, w["fplw"], w["fplb"], a16, M, C, eps, st)
         xa, xb, x16 = f32(M, D), f32(M, D), f16(M, D)  # the residual stream ping-pongs; x16: the operand copy of the current one
-        self._gemm(_lib.VBX_EPI_F32, M, D, C, a16, w["fpw"], xa, w["fpb"])
-        _lib.call("vbx_hubert_posconv", xa, w["posw"], w["posb"], xb, B, N, D, self.num_conv_pos_embedding_groups, self.num_conv_pos_embeddings, st)
+        self._product("projection", M, a16, w["fpw"], xa, w["fpb"])
+        if lens is None:
+            _lib.call("vbx_hubert_posconv", xa, w["posw"], w["posb"], xb, B, N, D, self.num_conv_pos_embedding_groups, self.num_conv_pos_embeddings, st)
+        else:
+            _lib.call("vbx_hubert_posconv_lens", xa, flens, w["posw"], w["posb"], xb, B, N, D, self.num_conv_pos_embedding_groups,
+                      self.num_conv_pos_embeddings, st)
         _lib.call("vbx_hubert_layernorm", xb, w["elw"], w["elb"], xa, x16, M, D, eps, st)
         if not w["layers"]:
-            return xa.view(B, N, D)
+            return self._finish(xa.view(B, N, D), flens if lens is not None else None)
         qkv, q16, k16, v16 = f32(M, 3 * D), f16(B, H, N, 64), f16(B, H, N, 64), f16(B, H, N, 64)
         o16, lse, g16 = f16(M, D), f32(B, H, N), f16(M, I)
         scale = 64 ** -0.5
         pre = _lib.lib().vbx_attn_q_prescale(scale)
         for l in w["layers"]:
-            self._gemm(_lib.VBX_EPI_F32, M, 3 * D, D, x16, l["wqkv"], qkv, l["bqkv"])
+            self._product("qkv", M, x16, l["wqkv"], qkv, l["bqkv"])
             _lib.call("vbx_hubert_split_heads", qkv, q16, k16, v16, B, N, H, pre, st)
-            _lib.call("vbx_attn_fwd", q16, k16, v16, None, o16, None, lse, B, H, N, scale, st)
-            self._gemm(_lib.VBX_EPI_F32, M, D, D, o16, l["wo"], xb, l["bo"], resid=xa)
+            if lens is None:
+                _lib.call("vbx_attn_fwd", q16, k16, v16, None, o16, None, lse, B, H, N, scale, st)
+            else:  # keys at or past the row's frames are never walked: live queries are those of the row alone
+                _lib.call("vbx_attn_fwd_lens", q16, k16, v16, None, flens, o16, None, lse, B, H, N, scale, st)
+            self._product("out_proj", M, o16, l["wo"], xb, l["bo"], resid=xa)
             _lib.call("vbx_hubert_layernorm", xb, l["n1w"], l["n1b"], xa, x16, M, D, eps, st)
-            self._gemm(_lib.VBX_EPI_GELU, M, I, D, x16, l["w1"], g16, l["b1"])
-            self._gemm(_lib.VBX_EPI_F32, M, D, I, g16, l["w2"], xb, l["b2"], resid=xa)
+            self._product("intermediate", M, x16, l["w1"], g16, l["b1"])
+            self._product("output", M, g16, l["w2"], xb, l["b2"], resid=xa)
             _lib.call("vbx_hubert_layernorm", xb, l["n2w"], l["n2b"], xa, x16, M, D, eps, st)
-        return xa.view(B, N, D)
+        return self._finish(xa.view(B, N, D), flens if lens is not None else None)
+
+    @staticmethod
+    def _finish(h, flens):
+        if flens is None:
+            return h, None
+        dead = torch.arange(h.shape[1], device=h.device)[None, :] >= flens[:, None]  # built once: forward fills the ids with it too
+        return h.masked_fill_(dead[:, :, None], 0.0), dead
 
     def assign(self, feats):
         """vbx_kmeans_assign of features fp32 [.., D] -> int64 [..]"""
@@ -373,6 +462,10 @@ class HubertWithKmeans(PackedWeights, nn.Module):
         return ids
 
     @torch.no_grad()
-    def forward(self, wav_input, flatten=True, input_sample_hz=None, attention_mask=None):
-        """ids int64 [B, frames] (`flatten` is audiolm_pytorch's keyword: with groups = 1 both of its shapes are this one)"""
-        return self.assign(self._features(self._prepare(wav_input, input_sample_hz, attention_mask)))
+    def forward(self, wav_input, flatten=True, input_sample_hz=None, attention_mask=None, lens=None):
+        """ids int64 [B, frames] (`flatten` is audiolm_pytorch's keyword: with groups = 1 both of its shapes are this one).  lens: as
+        in features(); the ids at or past frame_lens(...)[b] are 0, a valid index of any embedding table."""
+        wave, lens = self._prepare(wav_input, input_sample_hz, attention_mask, lens)
+        h, dead = self._features(wave, lens)
+        ids = self.assign(h)
+        return ids if dead is None else ids.masked_fill_(dead, 0)

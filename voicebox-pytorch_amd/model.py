@@ -580,13 +580,23 @@ class VoiceBox(nn.Module):
         return null_logits + (logits - null_logits) * cond_scale
 
     def forward(self, x, *, times, cond_token_ids, self_attn_mask=None, cond_drop_prob=0.1, target=None, cond=None,
-                cond_mask=None, self_attn_lens=None):  # voicebox_pytorch.py:987-1115
+                cond_mask=None, self_attn_lens=None, cond_token_lens=None):  # voicebox_pytorch.py:987-1115
         """self_attn_lens (not a reference keyword): a list, a CPU int tensor or a device int tensor [B] of frame counts -- exactly
         self_attn_mask = arange(N)[None] < self_attn_lens[:, None], and the attention forward and backward do not walk the tiles past
-        a row's length (train_lens.py).  Not together with self_attn_mask."""
-        from . import train_lens
+        a row's length (train_lens.py).  Not together with self_attn_mask.
+        cond_token_lens (not a reference keyword; needs self_attn_lens): the same three kinds, token counts 1 <= T_b <= tokens -- row
+        b's first T_b ids are resized to ITS self_attn_lens[b] frames, as the row alone would be, instead of all `tokens` ids to all
+        N frames (vbx_io.tok_lens); cond_emb is zero on the frames past the row's length."""
+        from . import train_lens, wave_lens as wl
 
         train_lens.refuse_with_mask(self_attn_lens, self_attn_mask, "VoiceBox.forward", "self_attn_lens", "self_attn_mask")
+        wl.refuse_token_lens(cond_token_lens, exists(self_attn_lens), cond_token_ids if self.condition_on_text else None, None,
+                             "VoiceBox.forward", name="cond_token_lens")
+        if exists(cond_token_lens):
+            if precise_enabled():
+                raise NotImplementedError("VoiceBox.forward: cond_token_lens is not served in precise mode")
+            cond_token_lens = wl.token_lens_device(cond_token_lens, cond_token_ids.shape[0], cond_token_ids.shape[-1], self.device,
+                                                   "VoiceBox.forward", name="cond_token_lens")
         cond = default(cond, target)  # :1003
         assert exists(cond), "either cond or target must be given"
         batch, seq_len, cond_dim = cond.shape
@@ -631,7 +641,7 @@ class VoiceBox(nn.Module):
                 # :1064-1066 (interpolate_1d on the boolean mask, the reference's own torch ops)
                 m4 = self_attn_mask.float()[:, None, :, None]
                 self_attn_mask = torch.nn.functional.interpolate(m4, (seq_len, 1), mode="bilinear")[:, 0, :, 0].to(torch.bool)
-            text = (ids, self.null_cond_id, drop, self.null_cond)
+            text = (ids, self.null_cond_id, drop, self.null_cond, cond_token_lens)
         if not exists(target):
             eng = self.engine(batch, seq_len, training=False)
             return eng.forward(x, cond, cond_mask, times, attn_mask=self_attn_mask, text=text, key_lens=key_lens)
@@ -951,8 +961,7 @@ class ConditionalFlowMatcherWrapper(nn.Module):
         with torch.no_grad():
             codec.eval()
             if exists(wave_lens):
-                if torch.is_tensor(wave_lens):
-                    wave_lens = wave_lens.to(self.device)
+                # (a list or CPU tensor stays on the host: resample and the codec validate it there, naming the row)
                 lens_c = resample_lens(wave_lens, input_sampling_rate, codec.sampling_rate) if differs else wave_lens
                 enc = lambda t: codec.encode(resample(t.to(self.device), input_sampling_rate, codec.sampling_rate, lens=wave_lens)
                                              if differs else t.to(self.device), lens=lens_c)
@@ -972,10 +981,13 @@ class ConditionalFlowMatcherWrapper(nn.Module):
                 cond = codec.encode(cond)
         return x1, cond
 
-    def wav2vec_token_ids(self, raw_audio, input_sampling_rate=None):
+    def wav2vec_token_ids(self, raw_audio, input_sampling_rate=None, wave_lens=None):
         """voicebox_pytorch.py:1386-1388: semantic_token_ids = wav2vec(resample(raw_audio, input_sampling_rate or the codec's rate,
         wav2vec.target_sample_hz)) on this wrapper's device, without gradients, wav2vec in eval mode.  What forward, TrainStep and
-        the trainer call when a text-conditioned model gets a wave and no ids."""
+        the trainer call when a text-conditioned model gets a wave and no ids.
+        wave_lens (not a reference keyword): samples per row at the rate the waves are given in -- resample(lens=) to the wav2vec's
+        rate, then wav2vec(wave, lens=L): the ids of every row alone, and TWO values come back, (ids, wav2vec.frame_lens(L)), the
+        second ready for token_lens=.  Needs a wav2vec that serves lengths (wave_lens.wav2vec_lacks)."""
         w2v = self.wav2vec
         assert exists(w2v), 'no wav2vec on this wrapper: pass semantic_token_ids, or build it with wav2vec='
         assert is_probably_audio_from_shape(raw_audio), 'wav2vec takes raw audio (batch, samples) or (batch, 1, samples)'
@@ -985,12 +997,24 @@ class ConditionalFlowMatcherWrapper(nn.Module):
             if isinstance(w2v, nn.Module):
                 w2v.eval()
             wave = raw_audio.to(self.device)
+            if exists(wave_lens):
+                from . import wave_lens as wl
+
+                lacks = wl.wav2vec_lacks(w2v)
+                if lacks:
+                    raise NotImplementedError(f"wav2vec_token_ids: wave_lens needs a wav2vec that is the row alone under lengths; "
+                                              f"{type(w2v).__name__} has no {lacks}")
+                L = wave_lens  # a list or CPU tensor stays on the host: validated there (ValueError naming the row), not clamped
+                if rate != w2v.target_sample_hz:
+                    wave = resample(wave, rate, w2v.target_sample_hz, lens=L)
+                    L = resample_lens(L, rate, w2v.target_sample_hz)
+                return w2v(wave, lens=L).clone(), w2v.frame_lens(L)
             if rate != w2v.target_sample_hz:
                 wave = resample(wave, rate, w2v.target_sample_hz)
             return w2v(wave).clone()
 
     def forward(self, x1, *, mask=None, lens=None, semantic_token_ids=None, phoneme_ids=None, cond=None, cond_mask=None,
-                input_sampling_rate=None, wave_lens=None):  # voicebox_pytorch.py:1332-1427
+                input_sampling_rate=None, wave_lens=None, token_lens=None):  # voicebox_pytorch.py:1332-1427
         """lens (not a reference keyword): a list, a CPU int tensor or a device int tensor [B] of frame counts, 1 <= len_b <= N -- the
         batch is ragged, row b has len_b real frames.  It means exactly mask = arange(N)[None] < lens[:, None] (same loss, same
         gradients, bit for bit), and the attention forward and backward stop at each row's length instead of masking the padding
@@ -1000,7 +1024,13 @@ class ConditionalFlowMatcherWrapper(nn.Module):
         wave_lens (not a reference keyword): x1 is a padded batch of WAVES and row b holds wave_lens[b] real samples, at the rate
         the waves are given in.  Every row is encoded as the row alone (encode_raw_audio(wave_lens=)), and the step runs as
         forward(latents, lens=codec.frame_lens(...)).  Not with latents, lens or mask; needs a codec with frame_lens and
-        encode(lens=); token ids are passed (semantic_token_ids), not taken from wav2vec=."""
+        encode(lens=).  A text-conditioned model without semantic_token_ids takes them from wav2vec=, which must serve lengths
+        (HubertWithKmeans(lens=); wave_lens.wav2vec_lacks): the step then IS forward(latents, lens=F, semantic_token_ids=ids,
+        token_lens=TL) with ids, TL = wav2vec_token_ids(waves, rate, wave_lens=).
+
+        token_lens (not a reference keyword; needs lens or wave_lens, and semantic_token_ids): a list, a CPU int tensor or a device
+        int tensor [B] of token counts -- row b's first token_lens[b] ids are resized to row b's own frames, as the row alone would
+        be, not all ids to all frames with the batch's one ratio."""
         if self.voicebox._lora is not None and torch.is_grad_enabled() and any(p.requires_grad for p in self.voicebox.parameters()):
             from .lora import refuse_autograd
 
@@ -1013,12 +1043,26 @@ class ConditionalFlowMatcherWrapper(nn.Module):
             train_lens.refuse_raw_audio(lens, x1, who)
             lens = train_lens.frame_lens(lens, x1.shape[0], x1.shape[1], self.device)
         raw_audio = x1 if is_probably_audio_from_shape(x1) else None
-        if exists(wave_lens):  # every refusal before anything is launched; then the frame lengths take the lens= path
-            from . import train_lens, wave_lens as wl
+        from . import wave_lens as wl
 
+        wl.refuse_token_lens(token_lens, exists(lens) or exists(wave_lens), semantic_token_ids, phoneme_ids,
+                             "ConditionalFlowMatcherWrapper.forward")
+        if exists(token_lens):
+            if precise_enabled():
+                raise NotImplementedError("ConditionalFlowMatcherWrapper.forward: token_lens is not served in precise mode")
+            token_lens = wl.token_lens_device(token_lens, semantic_token_ids.shape[0], semantic_token_ids.shape[-1], self.device,
+                                              "ConditionalFlowMatcherWrapper.forward")
+        if exists(wave_lens):  # every refusal before anything is launched; then the frame lengths take the lens= path
+            from . import train_lens
+
+            from_w2v = self.condition_on_text and exists(self.wav2vec) and not exists(semantic_token_ids) and not exists(phoneme_ids)
             wl.refuse(wave_lens, x1, cond, lens, mask, self.voicebox.audio_enc_dec, "ConditionalFlowMatcherWrapper.forward",
-                      wav2vec_ids=self.condition_on_text and exists(self.wav2vec) and not exists(semantic_token_ids)
-                      and not exists(phoneme_ids))
+                      wav2vec_ids=from_w2v and wl.wav2vec_lacks(self.wav2vec) is not None, wav2vec=self.wav2vec)
+            if from_w2v:  # the ids of every row alone and their counts, from the waves as they were given
+                if precise_enabled():
+                    raise NotImplementedError("ConditionalFlowMatcherWrapper.forward: wave_lens with token ids from wav2vec= resizes "
+                                              "each row's ids to its own frames, which precise mode does not serve")
+                semantic_token_ids, token_lens = self.wav2vec_token_ids(x1, input_sampling_rate, wave_lens=wave_lens)
             x1, cond, lens = self.encode_raw_audio(x1, cond, input_sampling_rate, wave_lens=wave_lens)
             lens = train_lens.frame_lens(lens, x1.shape[0], x1.shape[1], self.device)
         else:
@@ -1048,4 +1092,4 @@ class ConditionalFlowMatcherWrapper(nn.Module):
                 cond_token_ids = phoneme_ids
         self.voicebox.train()  # :1414
         return self.voicebox(w, cond=cond, cond_mask=cond_mask, times=times, target=flow, self_attn_mask=mask, self_attn_lens=lens,
-                             cond_token_ids=cond_token_ids, cond_drop_prob=self.cond_drop_prob)
+                             cond_token_ids=cond_token_ids, cond_drop_prob=self.cond_drop_prob, cond_token_lens=token_lens)
