@@ -1466,6 +1466,54 @@ int vbx_hubert_split_heads(const float* qkv, void* q16, void* k16, void* v16, in
  * rows of the codebook: the first).  h fp32 [M, D], centers fp32 [K, D], ids int64 [M].  D a multiple of 8 up to 2048, K 1 .. 4096. */
 int vbx_kmeans_assign(const float* h, const float* centers, long long* ids, long M, int D, int K, void* stream);
 
+/* ------------------------------------------------------------------ k-means fit (csrc/kmeans.hip, voicebox-pytorch_amd/kmeans.py)
+ * One step of MiniBatchKMeans.partial_fit at reassignment_ratio = 0 (or of Lloyd's algorithm) is
+ *   vbx_kmeans_norms -> vbx_kmeans_search -> vbx_kmeans_accumulate -> vbx_kmeans_update
+ * on one stream: assign with the OLD centres, sum the members of every cluster, move the centres.  fp32 data throughout, no float
+ * atomics, no host synchronisation; every entry point gives the same bits on every run.  x fp32 [M, D] (M = B * N rows), centres fp32
+ * [K, D]; D a multiple of 8 up to 2048, K 1 .. 4096, 1 <= M < 2^31.  lens int32 [B] or NULL: row m = b * N + n LIVES iff n < lens[b]
+ * (NULL: every row); a dead row is never read, whatever it holds. */
+/* norms[k] = |c_k|^2, fp32: lane l of a wave sums components 4 l + 256 j in ascending j by fmaf, then the xor tree over the 64 lanes */
+int vbx_kmeans_norms(const float* centers, float* norms, int K, int D, void* stream);
+/* ids[m] = argmin_k (norms[k] - 2 x_m . c_k) for a live row, the dot product an fp32 fmaf chain on v_mfma_f32_32x32x2_f32 in an
+ * order that is the same for every (row, centre) pair (csrc/kmeans.hip); K for a dead row.  CONTRACT, vbx_kmeans_assign's and
+ * vbx_rvq_encode's: d(ids[m]) - min_k d(k), both evaluated exactly, is at most (D + 2) * 2^-23 * (|x_m| + max_k |c_k|)^2, and among
+ * centres whose computed values are equal the lowest index wins.  mind[m] = sum_i (x_mi - c_i)^2 for the centre taken, by differences
+ * (component 4 l + 256 j in lane l, ascending j, then the xor tree over the 64 lanes); 0.0 for a dead row.  ids int32 [M], mind fp32
+ * [M].  vbx_kmeans_search_tile: the rows a workgroup owns (32; 16 above D = 1024); vbx_kmeans_search_chunk: the components of one
+ * stage of the codebook stream (32 or 16) -- tests stand on both sides of either. */
+int vbx_kmeans_search_tile(int D);
+int vbx_kmeans_search_chunk(int D);
+int vbx_kmeans_search(const float* x, const float* centers, const float* norms, const int* lens, int* ids, float* mind, long M, int N,
+                      int D, int K, void* stream);
+/* sums[k] = sum of the rows with ids[m] == k, counts[k] = their number (ids outside 0 .. K - 1 belong to no cluster: dead rows),
+ * inertia = the sum of mind over those rows.  SUMMATION ORDER: cluster k's members in ascending row index, r = 0 .. n_k - 1;
+ * P_j = ((x_{64 j} + x_{64 j + 1}) + ...) + x_{64 j + 63} and S_k = ((P_0 + P_1) + P_2) + ..., both left to right, per component -- a function of
+ * the members' ranks alone: the same bits for any batch shape that lists the same live rows in the same order, and on every run.
+ * mind takes the same route in fp64 (Q_j); the inertia adds all Q_j, clusters ascending, as lane l: Q_l + Q_{l + 64} + ... then the xor
+ * tree over 64 lanes, and is stored in fp64 and rounded once to fp32.  sums fp32 [K, D] (zeros for an empty cluster), counts int32
+ * [K]; scratch: vbx_kmeans_accumulate_scratch_bytes(M, D, K) bytes, 256-byte aligned (-1: a shape outside the limits). */
+long vbx_kmeans_accumulate_scratch_bytes(long M, int D, int K);
+int vbx_kmeans_accumulate(const float* x, const int* ids, const float* mind, float* sums, int* counts, double* inertia64,
+                          float* inertia32, void* scratch, long M, int D, int K, void* stream);
+/* One launch.  lloyd == 0: c' = (c * (float)w + S) / (float)(w + n) where n = counts[k] > 0, w' = w + n; lloyd != 0: c' = S / (float)n
+ * where n > 0, w' = n.  A centre with n == 0 keeps its bits.  fp32 multiply, add and correctly rounded divide.  The outputs are
+ * buffers of their own (w int64 [K]): nothing written here is read by a launch of the same step. */
+int vbx_kmeans_update(const float* centers, const long long* w, const float* sums, const int* counts, float* centers_out,
+                      long long* w_out, int K, int D, int lloyd, void* stream);
+/* k-means++ (Arthur & Vassilvitskii 2007), plain D^2 sampling, one candidate per step, from given uniforms u fp32 [K] in [0, 1):
+ * 2 K - 1 launches, the chosen index of a step read by the next launch from device memory.  Step 0 takes live row number
+ * floor(u_0 * M_live) (the product in fp64).  Step j: p_i = min over the chosen rows c of sum_d (x_id - x_cd)^2 by differences (mind's
+ * order), exactly 0 for a chosen row and for a dead one; the pick is the first row with p_i > 0 whose running sum reaches
+ * (double)u_j * total.  RUNNING SUM, fp64: block b = rows [64 b, 64 b + 64) has B_b = the xor-tree sum of its p; range t of 1024 =
+ * ceil(blocks / 1024) consecutive blocks added left to right; the ranges by a Hillis-Steele scan; inside a block an inclusive
+ * Hillis-Steele scan over its rows.  total == 0 (every live row coincides with a chosen one): live row floor(u_j * M_live).
+ * chosen int64 [K], centers fp32 [K, D] = the chosen rows; scratch p fp32 [M], bsum fp64 [vbx_kmeans_plusplus_blocks(M)].  Fewer
+ * live rows than K: rows repeat; no live row: row 0 is read (the caller refuses both where it can see lens). */
+long vbx_kmeans_plusplus_blocks(long M);
+int vbx_kmeans_plusplus(const float* x, const int* lens, const float* u, float* p, double* bsum, long long* chosen, float* centers,
+                        long M, int N, int D, int K, void* stream);
+
 /* ------------------------------------------------------------------ in-situ stage timing (measurement only)
  * While enabled, vbx_model_forward / vbx_model_backward_* bracket each MFMA stage of a layer (to_qkv, attention forward, to_out,
  * ff_in, ff_out, the four dgrads, attention backward, the weight-gradient launch) with a pair of HIP events recorded on the

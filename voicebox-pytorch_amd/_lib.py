@@ -134,6 +134,13 @@ _PROTOS = {
     "vbx_hubert_conv0_apply_lens": [P, P, P, P, P, P, P, I, L, I, I, I, P],
     "vbx_hubert_posconv_lens": [P, P, P, P, P, I, I, I, I, I, P],
     "vbx_kmeans_assign": [P, P, P, L, I, I, P],
+    "vbx_kmeans_norms": [P, P, I, I, P],
+    "vbx_kmeans_search_tile": [I],
+    "vbx_kmeans_search_chunk": [I],
+    "vbx_kmeans_search": [P, P, P, P, P, P, L, I, I, I, P],
+    "vbx_kmeans_accumulate": [P, P, P, P, P, P, P, P, L, I, I, P],
+    "vbx_kmeans_update": [P, P, P, P, P, P, I, I, I, P],
+    "vbx_kmeans_plusplus": [P, P, P, P, P, P, P, L, I, I, I, P],
     "vbx_maximum_path": [P, P, P, P, P, P, I, I, I, P],
     "vbx_forward_sum_fwd": [P, P, P, F, P, P, P, P, I, I, I, P],
     "vbx_forward_sum_bwd": [P, P, P, F, P, P, P, P, P, I, I, I, P],
@@ -278,6 +285,10 @@ def lib():
     l.vbx_duration_head_bwd_scratch_floats.restype = C.c_long
     l.vbx_ode_norm_slab_doubles.argtypes = [L]
     l.vbx_ode_norm_slab_doubles.restype = C.c_long
+    l.vbx_kmeans_accumulate_scratch_bytes.argtypes = [L, I, I]
+    l.vbx_kmeans_accumulate_scratch_bytes.restype = C.c_long
+    l.vbx_kmeans_plusplus_blocks.argtypes = [L]
+    l.vbx_kmeans_plusplus_blocks.restype = C.c_long
     _lib = l
     return l
 
@@ -285,7 +296,8 @@ def lib():
 def exported_symbols():
     return sorted(_PROTOS) + ["vbx_last_error", "vbx_attn_bwd_scratch_bytes", "vbx_dropout_keep_scale", "vbx_attn_q_prescale",
                               "vbx_adaln_dtemb_all_scratch_floats", "vbx_ode_norm_slab_doubles",
-                              "vbx_duration_head_bwd_scratch_floats"]  # + the stage-level entries bound in engine.py
+                              "vbx_duration_head_bwd_scratch_floats", "vbx_kmeans_accumulate_scratch_bytes",
+                              "vbx_kmeans_plusplus_blocks"]  # + the stage-level entries bound in engine.py
 
 
 def ptr(t):

@@ -6,7 +6,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "lib", "libvbx_hip.so")
-SOURCES = ["api.hip", "gemm.hip", "gemm3.hip", "gemm4.hip", "gemm5.hip", "attn.hip", "norm.hip", "gateloop.hip", "ops.hip", "codec.hip", "mel.hip", "griffinlim.hip", "vocos.hip", "rvq.hip", "seanet.hip", "hifigan.hip", "bigvgan.hip", "hubert.hip", "align.hip", "aligner.hip", "duration.hip", "resample.hip", "ode.hip", "lora.hip", "precise.hip", "runtime.hip"]
+SOURCES = ["api.hip", "gemm.hip", "gemm3.hip", "gemm4.hip", "gemm5.hip", "attn.hip", "norm.hip", "gateloop.hip", "ops.hip", "codec.hip", "mel.hip", "griffinlim.hip", "vocos.hip", "rvq.hip", "seanet.hip", "hifigan.hip", "bigvgan.hip", "hubert.hip", "kmeans.hip", "align.hip", "aligner.hip", "duration.hip", "resample.hip", "ode.hip", "lora.hip", "precise.hip", "runtime.hip"]
 
 
 # gemm5.hip: its epilogue is hand-slotted into the gaps of the MFMA stream; SLP-packed fp32 (v_pk_mul_f32 / v_pk_fma_f32) costs more beside

@@ -462,6 +462,31 @@ class HubertWithKmeans(PackedWeights, nn.Module):
         return ids
 
     @torch.no_grad()
+    def fit_kmeans(self, batches, n_clusters=None, init="k-means++", seed=0, input_sample_hz=None):
+        """Fits the codebook on the device (kmeans.KMeans): per batch -- a wave batch or (waves, lens), lens as in features() --
+        features(wave, lens=) -> KMeans.partial_fit(h, lens=frame lengths), one MiniBatchKMeans step at reassignment_ratio = 0; the
+        first batch also initialises.  Then set_cluster_centers (codebook_size becomes n_clusters).  No host synchronisation; the
+        KMeans comes back (counts_, inertia_)."""
+        from .kmeans import KMeans
+
+        K = self.codebook_size if n_clusters is None else n_clusters
+        if not isinstance(K, int) or not 2 <= K <= 4096:
+            raise NotImplementedError(f"HubertWithKmeans: codebook_size must be in 2 .. 4096 (got {K})")
+        km = KMeans(K, self.hidden_size, init=init, seed=seed)
+        resampled = input_sample_hz is not None and input_sample_hz != self.target_sample_hz
+        for batch in batches:
+            wave, lens = batch if isinstance(batch, (tuple, list)) else (batch, None)
+            h = self.features(wave, input_sample_hz=input_sample_hz, lens=lens)
+            if lens is not None:
+                lens = self.frame_lens(resample_lens(lens, input_sample_hz, self.target_sample_hz) if resampled else lens)
+            km.partial_fit(h, lens=lens)
+        if km.cluster_centers_ is None:
+            raise ValueError("HubertWithKmeans: fit_kmeans needs at least one batch")
+        self.codebook_size = K
+        self.set_cluster_centers(km.cluster_centers_)
+        return km
+
+    @torch.no_grad()
     def forward(self, wav_input, flatten=True, input_sample_hz=None, attention_mask=None, lens=None):
         """ids int64 [B, frames] (`flatten` is audiolm_pytorch's keyword: with groups = 1 both of its shapes are this one).  lens: as
         in features(); the ids at or past frame_lens(...)[b] are 0, a valid index of any embedding table."""
