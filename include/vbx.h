@@ -1465,6 +1465,58 @@ int vbx_hubert_split_heads(const float* qkv, void* q16, void* k16, void* v16, in
  * (D + 2) * 2^-23 * (|h[r]| + max_k |c_k|)^2, and among codes whose computed distances are equal the lowest index wins (duplicate
  * rows of the codebook: the first).  h fp32 [M, D], centers fp32 [K, D], ids int64 [M].  D a multiple of 8 up to 2048, K 1 .. 4096. */
 int vbx_kmeans_assign(const float* h, const float* centers, long long* ids, long M, int D, int K, void* stream);
+/* THE LARGE FORM (HubertLargeWithKmeans: feat_extract_norm "layer", do_stable_layer_norm, an optional convolution bias -- what
+ * transformers.HubertModel computes for hubert-large-ll60k).  The projection, the positional convolution, the five products, the head
+ * split, the attention and the k-means are the entry points above with their contracts; the sequence is in csrc/hubert.hip's header.
+ * WHERE A TENSOR IS ROUNDED (tests/hubert_large_ref.py, emulate=True, rounds exactly here and nowhere else):
+ *  - vbx_wave_normalize: fp32 in, statistics and (x - mean) * rstd in fp64, rounded once to fp32;
+ *  - the first convolution: fp32 wave, fp32 weights, the fmaf chain of vbx_hubert_conv0_apply, + bias, LayerNorm over the C channels of
+ *    the position in fp32 on those unrounded values, erf-GELU in fp32, rounded ONCE to fp16 [B, L0, C];
+ *  - every later convolution: fp16 input as stored, weights rounded to fp16, fp32 sum, + fp32 bias; LayerNorm over the C channels
+ *    from those fp32 sums (NOTHING is rounded before the norm and no intermediate goes to memory), affine, erf-GELU, rounded once to fp16;
+ *  - feature_projection.layer_norm, the projection and the positional convolution: as in the base form; there is no LayerNorm after
+ *    the positional convolution -- its fp32 result is the residual stream x;
+ *  - per layer: layer_norm(x) and final_layer_norm(x) read the fp32 stream and write ONLY the fp16 operand of the next product
+ *    (vbx_hubert_layernorm with y_f32 NULL: the norm in fp32, rounded once); out_proj / output_dense add the UNNORMALISED fp32 x;
+ *    everything else per layer as in the base form;
+ *  - encoder.layer_norm reads and writes fp32 and runs only where hidden_states[num_hidden_layers] is asked for.
+ * Plain launches without atomics: the same bits on every run, a batch row's result bit-equal to that row alone.  No statistic runs
+ * over time, so ragged waves (lens) need no kernel of their own before the positional convolution: a frame inside a row's count reads
+ * only that row's own samples, and the frames past it are zeroed by vbx_hubert_posconv_lens and at the end. */
+/* y fp16 [B, L0, C] = gelu(LayerNorm_C(v + bias) * gamma + beta), v the fmaf chain of vbx_hubert_conv0_stats, L0 = (T - k0) / s0 + 1.
+ * One launch; LayerNorm two-pass in fp32 (the mean, then the squared deviations) over the C values of a position, one wave per position,
+ * lane l sums its channels 8 l .. 8 l + 7 in ascending order, then the xor tree.  bias fp32 [C] or NULL; gamma, beta fp32 [C].
+ * k0, s0 <= 16; C a multiple of 16 up to 512.  vbx_hubert_conv0_ln_tile: the positions a workgroup owns. */
+int vbx_hubert_conv0_ln_tile(void);
+int vbx_hubert_conv0_ln(const float* wave, const float* w, const float* bias, const float* gamma, const float* beta, void* y_f16, int B,
+                        long T, int C, int k0, int s0, float eps, void* stream);
+/* vbx_hubert_conv with the large form's epilogue: y fp16 [B, (L - k) / 2 + 1, C] = gelu(LayerNorm_C(conv(x) + bias) * gamma + beta).
+ * The workgroup that owns TT positions owns all their C channels: its fp32 sums wait in an fp32 tile [TT][C + 4] in the LDS beside the
+ * staged span, and each position is normalised from them (two-pass, fp32, as above).  The tile is the largest whose span PLUS sums fit
+ * as csrc/seanet_tile.hpp picks (at C = 512: 16 positions, 66 KiB, against vbx_hubert_conv's 32).  bias fp32 [C] or NULL.
+ * vbx_hubert_conv_ln_tile: the positions a workgroup owns before a short row shrinks it. */
+int vbx_hubert_conv_ln_tile(int C, int k);
+int vbx_hubert_conv_ln(const void* x_f16, const void* w_f16, const float* bias, const float* gamma, const float* beta, void* y_f16, int B,
+                       int L, int C, int k, float eps, void* stream);
+/* The same layer as an fp32 intermediate plus a row kernel, for the shapes where that is faster (vbx_hubert_conv_ln_route: 1 where
+ * the fused kernel's tile is smaller than vbx_hubert_conv's AND its grid is more than 512 workgroups, so that twice the workgroups
+ * re-reading the weight from L2 bound it; 0: the fused kernel).  vbx_hubert_conv_f32: vbx_hubert_conv's tile, the fp32 sum + bias
+ * stored UNROUNDED to s fp32 [B, (L - k) / 2 + 1, C].  vbx_hubert_ln_gelu: y fp16 [M, C] = gelu(LayerNorm_C(s) * gamma + beta), one wave
+ * per row, the code of the fused epilogue on the same values.  The sum of an output does not depend on the tile's height, so the pair
+ * and vbx_hubert_conv_ln give the SAME BITS: the route is a matter of speed only, and a row alone may take another route than its
+ * batch.  Nothing is rounded before the norm either way.  C a multiple of 8 (16 for the convolution) up to 512. */
+int vbx_hubert_conv_ln_route(int B, int L, int C, int k);
+int vbx_hubert_conv_f32(const void* x_f16, const void* w_f16, const float* bias, float* s_f32, int B, int L, int C, int k, void* stream);
+int vbx_hubert_ln_gelu(const float* s_f32, const float* gamma, const float* beta, void* y_f16, long M, int C, float eps, void* stream);
+/* y[b][t] = (x[b][t] - mean_b) / sqrt(var_b + eps), biased variance, over the row's T samples -- with lens int32 [B] (or NULL) over
+ * its first len_b = clamp(lens[b], 1, T) samples, and y[b][t] = 0 for t >= len_b (x is not read there).  One record (K, S1, S2) per
+ * (row, chunk of vbx_wave_normalize_chunk() = 4096 samples): K the chunk's first sample, S1 = sum(x - K), S2 = sum((x - K)^2) in fp32
+ * in a fixed order -- shifted, so a DC offset costs nothing; a second launch combines a row's records in ascending order in fp64 into
+ * stats[b] = (mean, 1 / sqrt(var + eps)), kept in fp64; a third computes (x - mean) * rstd in fp64 and rounds once.  A single sample
+ * gives 0.  x, y fp32 [B, T] (y may be x); records fp32 [B, ceil(T / chunk), 3] and stats fp64 [B, 2] are scratch.  No atomics, the
+ * same bits on every run, a row's result independent of its neighbours. */
+int vbx_wave_normalize_chunk(void);
+int vbx_wave_normalize(const float* x, const int* lens, float* y, float* records, double* stats, int B, long T, float eps, void* stream);
 
 /* ------------------------------------------------------------------ k-means fit (csrc/kmeans.hip, voicebox-pytorch_amd/kmeans.py)
  * One step of MiniBatchKMeans.partial_fit at reassignment_ratio = 0 (or of Lloyd's algorithm) is

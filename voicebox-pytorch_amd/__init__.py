@@ -17,7 +17,9 @@ local checkpoint), BigVGANGenerator (BigVGAN's generator on the device, its anti
 shape; a local checkpoint and its config.json), HiFiGANMelCodec / mel_spectrogram (the mel front end those two generators were
 trained on -- Slaney filters, magnitude, ln, center=False -- in one kernel: the codec published HiFi-GAN / BigVGAN weights want),
 HubertWithKmeans (HuBERT base up to one encoder layer plus a k-means codebook on the device: waves into semantic token ids, the
-`wav2vec=` of ConditionalFlowMatcherWrapper; weights are the user's, from local files), KMeans / kmeans_plusplus (fitting that
+`wav2vec=` of ConditionalFlowMatcherWrapper; weights are the user's, from local files), HubertLargeWithKmeans / normalize_wave (the
+same for HuBERT large -- per-layer convolution norms, the pre-LN encoder: hubert-large-ll60k -- and the zero-mean unit-variance wave
+that model was trained on), KMeans / kmeans_plusplus (fitting that
 codebook on the device from features: minibatch and Lloyd steps, D^2 sampling; HubertWithKmeans.fit_kmeans), AudioDataset (a folder of audio
 files as a dataset of waves) and resample_lens (the length arithmetic of resample(lens=): ragged wave batches, `wave_lens=`).
 """
@@ -37,7 +39,7 @@ try:  # model classes need torch; keep `_lib` importable on its own
     from .seanet import CausalSEANetDecoder, CausalSEANetEncoder, SEANetDecoder, SEANetEncoder  # noqa: F401
     from .hifigan import HiFiGANGenerator  # noqa: F401
     from .bigvgan import BigVGANGenerator  # noqa: F401
-    from .hubert import HubertWithKmeans  # noqa: F401
+    from .hubert import HubertWithKmeans, HubertLargeWithKmeans, normalize_wave  # noqa: F401
     from .kmeans import KMeans, kmeans_plusplus  # noqa: F401
     from .align import maximum_path, forward_sum_loss, ForwardSumLoss, Aligner, aligner_attention  # noqa: F401
     from .engine import precise_mode, set_precise, precise_enabled  # noqa: F401
@@ -49,7 +51,7 @@ try:  # model classes need torch; keep `_lib` importable on its own
                 "AudioEncoderDecoder", "LogMelCodec", "griffin_lim", "resample", "Resample", "VocosDecoder", "VocosEncodecDecoder", "ResidualVQ", "EncodecVocoCodec", "SEANetEncoder", "SEANetDecoder",
                 "CausalSEANetEncoder", "CausalSEANetDecoder", "HiFiGANGenerator", "BigVGANGenerator", "HubertWithKmeans", "HiFiGANMelCodec", "mel_spectrogram",
                 "maximum_path", "forward_sum_loss", "ForwardSumLoss", "Aligner", "aligner_attention", "lora", "ema_decay_at", "resample_lens",
-                "AudioDataset", "KMeans", "kmeans_plusplus"]
+                "AudioDataset", "KMeans", "kmeans_plusplus", "HubertLargeWithKmeans", "normalize_wave"]
 except ModuleNotFoundError as _e:  # pragma: no cover - only while the package is being bootstrapped
     if "masks" not in str(_e) and "model" not in str(_e):
         raise

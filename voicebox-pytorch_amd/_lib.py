@@ -133,6 +133,15 @@ _PROTOS = {
     "vbx_hubert_conv0_stats_lens": [P, P, P, P, P, I, L, I, I, I, F, P],
     "vbx_hubert_conv0_apply_lens": [P, P, P, P, P, P, P, I, L, I, I, I, P],
     "vbx_hubert_posconv_lens": [P, P, P, P, P, I, I, I, I, I, P],
+    "vbx_hubert_conv0_ln_tile": [],
+    "vbx_hubert_conv0_ln": [P, P, P, P, P, P, I, L, I, I, I, F, P],
+    "vbx_hubert_conv_ln_tile": [I, I],
+    "vbx_hubert_conv_ln": [P, P, P, P, P, P, I, I, I, I, F, P],
+    "vbx_hubert_conv_ln_route": [I, I, I, I],
+    "vbx_hubert_conv_f32": [P, P, P, P, I, I, I, I, P],
+    "vbx_hubert_ln_gelu": [P, P, P, P, L, I, F, P],
+    "vbx_wave_normalize_chunk": [],
+    "vbx_wave_normalize": [P, P, P, P, P, I, L, F, P],
     "vbx_kmeans_assign": [P, P, P, L, I, I, P],
     "vbx_kmeans_norms": [P, P, I, I, P],
     "vbx_kmeans_search_tile": [I],

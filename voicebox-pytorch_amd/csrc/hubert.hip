@@ -23,6 +23,25 @@
 // Precision contract (include/vbx.h): fp16 channel-last activations rounded once where they are stored, fp16 weights, every product's
 // sum fp32 on v_mfma_f32_16x16x32_f16 in ascending k, norms / GELU (libm's erff) / statistics fp32.  Plain launches, no atomics, no
 // workgroup waits for another: the same bits on every run, and a batch row's result does not depend on its neighbours.
+//
+// HubertLargeWithKmeans (the LARGE form: feat_extract_norm "layer", the pre-LN encoder of do_stable_layer_norm, an optional convolution
+// bias) keeps the projection, the positional convolution, the products, the attention and the k-means of the sequence above; what differs:
+//
+//   vbx_wave_normalize       (normalize_wave=True only) per row (x - mean) / sqrt(var + eps): shifted sums per chunk of 4096 samples,
+//                            combined in order in fp64, applied in fp64 -> fp32; with lens over the row's own samples, zeros past them
+//   vbx_hubert_conv0_ln      the same fmaf chain, + bias, LayerNorm over the C channels of the position (two passes, fp32), erf-GELU
+//                            -> fp16 [B, L0, C]: ONE launch, no statistic over time, no records
+//   vbx_hubert_conv_ln x 6   the tile core as in vbx_hubert_conv; the fp32 sums (+ bias) of the workgroup's TT positions x C channels
+//                            wait in the LDS beside the span, then LayerNorm over each position's channels, erf-GELU -> fp16
+//                            -- or, where vbx_hubert_conv_ln_route says so (long rows at 512 channels), the pair vbx_hubert_conv_f32
+//                            (the fp32 sums to memory, unrounded) + vbx_hubert_ln_gelu (one wave per position): the same bits, faster there
+//   vbx_hubert_layernorm16, vbx_gemm (projection), vbx_hubert_posconv: as above -- and NO encoder.layer_norm here
+//   per layer 1 .. output_layer (eight launches, as above):
+//     vbx_hubert_layernorm   layer_norm(x) -> the fp16 operand only (x, the fp32 residual stream, is never normalised in place)
+//     vbx_gemm q | k | v;  vbx_hubert_split_heads;  vbx_attn_fwd;  vbx_gemm out_proj + bias + x
+//     vbx_hubert_layernorm   final_layer_norm(x) -> the fp16 operand only
+//     vbx_gemm intermediate_dense (GELU);  vbx_gemm output_dense + bias + x
+//   vbx_hubert_layernorm     encoder.layer_norm -> fp32, only where output_layer == num_hidden_layers
 #include "seanet_tile.hpp"  // sn_tile_product, sn_pick_tile, sn_blocks_per_item, sn_launch
 
 namespace {
@@ -488,6 +507,269 @@ __global__ __launch_bounds__(256) void hubert_posconv_lens_kernel(HbPosLens p) {
   sn_tile_product<MG, true>(p.w + (long)g * p.Dg * p.k * p.Dg, p.Dg, p.k * p.Dg, p.TT >> 4, rows, store);
 }
 
+// ---------------------------------------------------------------------------------------------------- the large form (include/vbx.h)
+// conv0 + bias + LayerNorm over the channels + GELU.  Workgroup (tile of HB_LN0_POS positions, row): the tile's samples and the
+// weights sit in the LDS; a wave owns a position at a time, lane l its channels 8 l .. 8 l + 7 (lanes at or past C / 8 hold nothing and
+// add zeros to the two wave sums).  Nothing runs over time: a position reads only its own k0 samples.
+constexpr int HB_LN0_POS = 64;
+__global__ __launch_bounds__(256) void hubert_conv0_ln_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
+                                                              const float* __restrict__ gamma, const float* __restrict__ beta, u16* __restrict__ y,
+                                                              int T, int L0, int C, int k0, int s0, float eps) {
+  __shared__ __attribute__((aligned(16))) float sw[HB_MAX_K0 * HB_MAX_C];  // [tap][C]
+  __shared__ float sx[(HB_LN0_POS - 1) * HB_MAX_S0 + HB_MAX_K0];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.y;
+  const int t0 = blockIdx.x * HB_LN0_POS;
+  const int n = min(HB_LN0_POS, L0 - t0);
+  const int span = (n - 1) * s0 + k0;
+  const float* xb = x + (long)b * T + (long)t0 * s0;  // the last tap read is (L0 - 1) * s0 + k0 - 1 <= T - 1
+  for (int e = tid; e < span; e += 256) sx[e] = xb[e];
+  for (int e = tid; e < k0 * C; e += 256) {
+    const int tap = e / C, c = e - tap * C;
+    sw[e] = w[c * k0 + tap];
+  }
+  __syncthreads();
+  const int c0 = lane * 8;
+  const bool has = c0 < C;
+  float bv[8], gm[8], bt[8];
+#pragma unroll
+  for (int j = 0; j < 8; j++) {
+    bv[j] = (has && bias) ? bias[c0 + j] : 0.f;
+    gm[j] = has ? gamma[c0 + j] : 0.f;
+    bt[j] = has ? beta[c0 + j] : 0.f;
+  }
+  const float invC = 1.0f / (float)C;
+  for (int t = wave; t < n; t += 4) {
+    float acc[8];
+#pragma unroll
+    for (int j = 0; j < 8; j++) acc[j] = 0.f;
+    if (has) {
+      for (int tap = 0; tap < k0; tap++) {
+        const float xv = sx[t * s0 + tap];
+        const float4 lo = *reinterpret_cast<const float4*>(sw + tap * C + c0), hi = *reinterpret_cast<const float4*>(sw + tap * C + c0 + 4);
+        acc[0] = fmaf(lo.x, xv, acc[0]), acc[1] = fmaf(lo.y, xv, acc[1]), acc[2] = fmaf(lo.z, xv, acc[2]), acc[3] = fmaf(lo.w, xv, acc[3]);
+        acc[4] = fmaf(hi.x, xv, acc[4]), acc[5] = fmaf(hi.y, xv, acc[5]), acc[6] = fmaf(hi.z, xv, acc[6]), acc[7] = fmaf(hi.w, xv, acc[7]);
+      }
+    }
+    float s = 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+      acc[j] += bv[j];
+      s += acc[j];
+    }
+    const float mean = wave_sum(s) * invC;
+    float q = 0.f;
+    if (has) {
+#pragma unroll
+      for (int j = 0; j < 8; j++) {
+        const float d = acc[j] - mean;
+        q = fmaf(d, d, q);
+      }
+    }
+    const float rstd = 1.0f / sqrtf(wave_sum(q) * invC + eps);
+    if (has) {
+#pragma unroll
+      for (int j = 0; j < 8; j++) acc[j] = gelu_erf_libm(fmaf((acc[j] - mean) * rstd, gm[j], bt[j]));
+      *reinterpret_cast<uint4*>(y + ((long)b * L0 + t0 + t) * C + c0) =
+          make_uint4(pack_f16x2(acc[0], acc[1]), pack_f16x2(acc[2], acc[3]), pack_f16x2(acc[4], acc[5]), pack_f16x2(acc[6], acc[7]));
+    }
+  }
+}
+
+// LayerNorm over the C <= 512 channels of one position + affine + erf-GELU, by one wave: lane l holds channels 8 l .. 8 l + 7 (lanes at
+// or past C / 8 hold nothing and add zeros), sums them in ascending order, then the xor tree; two passes (the mean, then the squared
+// deviations), fp32; one 16-byte fp16 store per lane.  src: the fp32 pre-norm values of the position (LDS or memory), 16-byte aligned.
+VBX_DEV void hb_row_ln_gelu(const float* src, const float* __restrict__ gamma, const float* __restrict__ beta, u16* __restrict__ dst, int C, float eps,
+                            int lane) {
+  const int c0 = lane * 8;
+  const bool has = c0 < C;
+  const float invC = 1.0f / (float)C;
+  float v[8];
+#pragma unroll
+  for (int j = 0; j < 8; j++) v[j] = 0.f;
+  if (has) {
+    const float4 lo = *reinterpret_cast<const float4*>(src + c0), hi = *reinterpret_cast<const float4*>(src + c0 + 4);
+    v[0] = lo.x, v[1] = lo.y, v[2] = lo.z, v[3] = lo.w, v[4] = hi.x, v[5] = hi.y, v[6] = hi.z, v[7] = hi.w;
+  }
+  float sum = 0.f;
+#pragma unroll
+  for (int j = 0; j < 8; j++) sum += v[j];
+  const float mean = wave_sum(sum) * invC;
+  float q = 0.f;
+  if (has) {
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+      const float d = v[j] - mean;
+      q = fmaf(d, d, q);
+    }
+  }
+  const float rstd = 1.0f / sqrtf(wave_sum(q) * invC + eps);
+  if (has) {
+#pragma unroll
+    for (int j = 0; j < 8; j++) v[j] = gelu_erf_libm(fmaf((v[j] - mean) * rstd, gamma[c0 + j], beta[c0 + j]));
+    *reinterpret_cast<uint4*>(dst + c0) = make_uint4(pack_f16x2(v[0], v[1]), pack_f16x2(v[2], v[3]), pack_f16x2(v[4], v[5]), pack_f16x2(v[6], v[7]));
+  }
+}
+
+// hubert_conv_kernel with the large form's epilogue.  The workgroup owns all C channels of its TT positions, so a position's LayerNorm
+// needs no other workgroup: the tile core hands every fp32 sum (+ bias) to an fp32 tile [TT][C + 4] in the LDS BESIDE the span (other
+// waves still read the span while one stores), and after one barrier a wave normalises a position at a time from those unrounded sums.
+struct HbConvLn : HbConv {
+  const float* bias;   // [C] or null
+  const float* gamma;  // [C]
+  const float* beta;   // [C]
+  float eps;
+};
+constexpr int HB_PADF = 4;  // fp32 elements of padding per row of the sum tile: the four row groups of an MFMA result land 16 banks apart
+
+template <int MG>
+__global__ __launch_bounds__(256) void hubert_conv_ln_kernel(HbConvLn p) {
+  extern __shared__ __attribute__((aligned(16))) u16 hb_lds[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.y, t0 = blockIdx.x * p.TT;
+  const int ld = p.C + SN_PADH, c8 = p.C >> 3, ldf = p.C + HB_PADF;
+  const int span = (p.TT - 1) * 2 + p.k;
+  float* sums = reinterpret_cast<float*>(hb_lds + span * ld);  // span * ld * 2 bytes is a multiple of 16
+  const u16* xb = p.x + (long)b * p.L * p.C;
+  for (int e = tid; e < span * c8; e += 256) {
+    const int pos = e / c8, c = (e - pos * c8) * 8;
+    const int i = t0 * 2 + pos;
+    *reinterpret_cast<uint4*>(hb_lds + pos * ld + c) = i < p.L ? *reinterpret_cast<const uint4*>(xb + (long)i * p.C + c) : make_uint4(0u, 0u, 0u, 0u);
+  }
+  __syncthreads();
+  auto rows = [&](int kk, const u16*& base, int& ldr) __attribute__((always_inline)) {
+    const int tap = kk / p.C, c = kk - tap * p.C;
+    base = hb_lds + tap * ld + c, ldr = 2 * ld;
+  };
+  auto store = [&](int n) __attribute__((always_inline)) {
+    return [&, n, bv = p.bias ? p.bias[n] : 0.f](int m, float v) __attribute__((always_inline)) { sums[m * ldf + n] = v + bv; };
+  };
+  sn_tile_product<MG, true>(p.w, p.C, p.k * p.C, p.TT >> 4, rows, store);
+  __syncthreads();
+  const int live = min(p.TT, p.Lout - t0);
+  for (int m = wave; m < live; m += 4)
+    hb_row_ln_gelu(sums + m * ldf, p.gamma, p.beta, p.y + ((long)b * p.Lout + t0 + m) * p.C, p.C, p.eps, lane);
+}
+
+// The same convolution as an fp32 intermediate plus a row kernel, for the shapes where the fused kernel's smaller tile costs more than
+// the round trip through memory (vbx_hubert_conv_ln_route): hubert_conv_kernel's tile, the fp32 sum (+ bias) stored UNROUNDED to
+// s fp32 [B, Lout, C]; then one wave per position runs hb_row_ln_gelu on it -- the same code on the same values: the same bits.
+struct HbConvF32 : HbConv {
+  const float* bias;  // [C] or null
+  float* s;           // [B, Lout, C]
+};
+template <int MG>
+__global__ __launch_bounds__(256) void hubert_conv_f32_kernel(HbConvF32 p) {
+  extern __shared__ __attribute__((aligned(16))) u16 hb_lds[];
+  const int tid = threadIdx.x, b = blockIdx.y, t0 = blockIdx.x * p.TT;
+  const int ld = p.C + SN_PADH, c8 = p.C >> 3;
+  const int span = (p.TT - 1) * 2 + p.k;
+  const u16* xb = p.x + (long)b * p.L * p.C;
+  for (int e = tid; e < span * c8; e += 256) {
+    const int pos = e / c8, c = (e - pos * c8) * 8;
+    const int i = t0 * 2 + pos;
+    *reinterpret_cast<uint4*>(hb_lds + pos * ld + c) = i < p.L ? *reinterpret_cast<const uint4*>(xb + (long)i * p.C + c) : make_uint4(0u, 0u, 0u, 0u);
+  }
+  __syncthreads();
+  auto rows = [&](int kk, const u16*& base, int& ldr) __attribute__((always_inline)) {
+    const int tap = kk / p.C, c = kk - tap * p.C;
+    base = hb_lds + tap * ld + c, ldr = 2 * ld;
+  };
+  auto store = [&](int n) __attribute__((always_inline)) {
+    return [&, n, bv = p.bias ? p.bias[n] : 0.f](int m, float v) __attribute__((always_inline)) {
+      const int t = t0 + m;
+      if (t < p.Lout) p.s[((long)b * p.Lout + t) * p.C + n] = v + bv;
+    };
+  };
+  sn_tile_product<MG, true>(p.w, p.C, p.k * p.C, p.TT >> 4, rows, store);
+}
+
+__global__ __launch_bounds__(256) void hubert_ln_gelu_kernel(const float* __restrict__ s, const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                             u16* __restrict__ y, long M, int C, float eps) {
+  const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= M) return;  // uniform over the wave
+  hb_row_ln_gelu(s + row * C, gamma, beta, y + row * C, C, eps, threadIdx.x & 63);
+}
+
+size_t hb_conv_ln_lds(int TT, int C, int k) { return hb_conv_lds(TT, C, k) + (size_t)TT * (C + HB_PADF) * sizeof(float); }
+// A 32-position tile in the whole LDS (133 KiB at C = 512, one workgroup per CU) was measured against this pick's 16: 1.94 ms against
+// 2.02 ms at 8 x 15 999 positions, 0.067 against 0.051 ms at 8 x 499 -- no gain.
+int hb_conv_ln_tile(int C, int k) {
+  return sn_pick_tile([&](int TT) { return hb_conv_ln_lds(TT, C, k); });
+}
+
+// ---------------------------------------------------------------------------------------------------- wave normalisation
+// (x - mean) / sqrt(var + eps) per row, biased variance.  Workgroup (chunk of HB_WN_CHUNK samples, row): one record (K, S1, S2) with K
+// the chunk's first sample, S1 = sum(x - K), S2 = sum((x - K)^2) -- thread t sums samples t, t + 256, ... in ascending order, then the
+// xor tree of the wave and the four waves in order.  A second launch combines a row's records in ascending order in fp64 (as
+// hubert_conv0_finalize_kernel) into (mean, 1 / sqrt(var + eps)), kept in fp64; a third applies them in fp64 and rounds once to fp32.
+constexpr int HB_WN_CHUNK = 4096;
+VBX_DEV int hb_wn_len(const int* __restrict__ lens, int b, int T) { return lens ? min(max(lens[b], 1), T) : T; }
+
+__global__ __launch_bounds__(256) void wave_normalize_stats_kernel(const float* __restrict__ x, const int* __restrict__ lens, float* __restrict__ rec,
+                                                                   int T, int chunks) {
+  __shared__ float red[8];
+  const int tid = threadIdx.x, chunk = blockIdx.x, b = blockIdx.y;
+  const int Tb = hb_wn_len(lens, b, T);
+  const long t0 = (long)chunk * HB_WN_CHUNK;
+  if (t0 >= Tb) return;  // uniform over the workgroup; the record is never read
+  const int n = (int)min((long)HB_WN_CHUNK, Tb - t0);
+  const float* xb = x + (long)b * T + t0;
+  const float K = xb[0];
+  float S1 = 0.f, S2 = 0.f;
+  for (int e = tid; e < n; e += 256) {
+    const float d = xb[e] - K;
+    S1 += d;
+    S2 = fmaf(d, d, S2);
+  }
+  S1 = wave_sum(S1), S2 = wave_sum(S2);
+  if ((tid & 63) == 0) red[(tid >> 6) * 2] = S1, red[(tid >> 6) * 2 + 1] = S2;
+  __syncthreads();
+  if (tid == 0) {
+    float* r = rec + ((long)b * chunks + chunk) * 3;
+    r[0] = K, r[1] = ((red[0] + red[2]) + red[4]) + red[6], r[2] = ((red[1] + red[3]) + red[5]) + red[7];
+  }
+}
+
+// one thread per row
+__global__ __launch_bounds__(64) void wave_normalize_finalize_kernel(const float* __restrict__ rec, const int* __restrict__ lens,
+                                                                     double* __restrict__ stats, int B, int T, int chunks, float eps) {
+  const int b = blockIdx.x * 64 + threadIdx.x;
+  if (b >= B) return;
+  const int Tb = hb_wn_len(lens, b, T);
+  const int live = (Tb + HB_WN_CHUNK - 1) / HB_WN_CHUNK;  // <= chunks
+  const float* r = rec + (long)b * chunks * 3;
+  double sum = 0.0;
+  for (int ch = 0; ch < live; ch++) {
+    const int n = min(HB_WN_CHUNK, Tb - ch * HB_WN_CHUNK);
+    sum += (double)n * (double)r[3 * (long)ch] + (double)r[3 * (long)ch + 1];
+  }
+  const double mean = sum / (double)Tb;
+  double m2 = 0.0;
+  for (int ch = 0; ch < live; ch++) {
+    const int n = min(HB_WN_CHUNK, Tb - ch * HB_WN_CHUNK);
+    const float* q = r + 3 * (long)ch;
+    const double s1 = (double)q[1], mc = (double)q[0] + s1 / (double)n, dm = mc - mean;
+    m2 += ((double)q[2] - s1 * s1 / (double)n) + (double)n * dm * dm;
+  }
+  const double var = m2 > 0.0 ? m2 / (double)Tb : 0.0;
+  stats[2 * (long)b] = mean;
+  stats[2 * (long)b + 1] = 1.0 / sqrt(var + (double)eps);
+}
+
+// one thread per four samples; a sample at or past the row's length is written as 0 and not read
+__global__ __launch_bounds__(256) void wave_normalize_apply_kernel(const float* x, const int* __restrict__ lens,
+                                                                   const double* __restrict__ stats, float* y, int T) {
+  const int b = blockIdx.y;
+  const long e0 = ((long)blockIdx.x * 256 + threadIdx.x) * 4;
+  if (e0 >= T) return;
+  const int Tb = hb_wn_len(lens, b, T);
+  const double mean = stats[2 * (long)b], rstd = stats[2 * (long)b + 1];
+  const int n = (int)min(4L, T - e0);
+  for (int j = 0; j < n; j++) {
+    const long o = (long)b * T + e0 + j;
+    y[o] = e0 + j < Tb ? (float)(((double)x[o] - mean) * rstd) : 0.f;
+  }
+}
+
 }  // namespace
 
 extern "C" int vbx_hubert_conv0_chunks(int L0) { return L0 >= 1 ? cdiv(L0, HB_CHUNK) : 0; }
@@ -674,4 +956,97 @@ extern "C" int vbx_hubert_posconv_lens(const float* x, const int* lens, const vo
   if (MG == 4) return sn_launch<hubert_posconv_lens_kernel<4>>("vbx_hubert_posconv_lens", p, (int)blocks, B, bytes, (hipStream_t)stream);
   if (MG == 2) return sn_launch<hubert_posconv_lens_kernel<2>>("vbx_hubert_posconv_lens", p, (int)blocks, B, bytes, (hipStream_t)stream);
   return sn_launch<hubert_posconv_lens_kernel<1>>("vbx_hubert_posconv_lens", p, (int)blocks, B, bytes, (hipStream_t)stream);
+}
+
+// ---------------------------------------------------------------------------------------------------- the large form: the entries
+extern "C" int vbx_hubert_conv0_ln_tile(void) { return HB_LN0_POS; }
+
+extern "C" int vbx_hubert_conv0_ln(const float* wave, const float* w, const float* bias, const float* gamma, const float* beta, void* y_f16, int B,
+                                   long T, int C, int k0, int s0, float eps, void* stream) {
+  VBX_REQUIRE(wave && w && gamma && beta && y_f16, "vbx_hubert_conv0_ln: null operand");
+  long L0;
+  if (int rc = hb_conv0_check("vbx_hubert_conv0_ln", B, T, C, k0, s0, &L0)) return rc;
+  VBX_REQUIRE(C % 16 == 0, "vbx_hubert_conv0_ln: channels must be a multiple of 16 up to %d (got %d)", HB_MAX_C, C);
+  hipLaunchKernelGGL(hubert_conv0_ln_kernel, dim3(cdiv(L0, HB_LN0_POS), B), dim3(256), 0, (hipStream_t)stream, wave, w, bias, gamma, beta,
+                     (u16*)y_f16, (int)T, (int)L0, C, k0, s0, eps);
+  VBX_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int vbx_hubert_conv_ln_tile(int C, int k) {
+  if (int rc = hb_conv_check(C, k)) return rc;
+  return hb_conv_ln_tile(C, k);  // never 0: 16 positions of 512 channels at k 3 take 34 KiB of span and 33 KiB of sums
+}
+
+extern "C" int vbx_hubert_conv_ln(const void* x_f16, const void* w_f16, const float* bias, const float* gamma, const float* beta, void* y_f16, int B,
+                                  int L, int C, int k, float eps, void* stream) {
+  VBX_REQUIRE(x_f16 && w_f16 && gamma && beta && y_f16, "vbx_hubert_conv_ln: null operand");
+  VBX_REQUIRE(B >= 1 && B <= 65535 && L >= k && L < (1 << 30), "vbx_hubert_conv_ln: need B in 1 .. 65535 and kernel_size <= L < 2^30");
+  if (int rc = hb_conv_check(C, k)) return rc;
+  HbConvLn p;
+  p.x = (const u16*)x_f16, p.w = (const u16*)w_f16, p.y = (u16*)y_f16, p.L = L, p.Lout = (L - k) / 2 + 1, p.C = C, p.k = k;
+  p.bias = bias, p.gamma = gamma, p.beta = beta, p.eps = eps;
+  int TT = hb_conv_ln_tile(C, k);
+  while (TT > 16 && TT / 2 >= p.Lout) TT >>= 1;  // a short row: no tile of absent positions is staged or multiplied
+  p.TT = TT;
+  const size_t bytes = hb_conv_ln_lds(TT, C, k);
+  const int MG = sn_blocks_per_item(C / 16, TT / 16), blocks = cdiv(p.Lout, TT);
+  if (MG == 4) return sn_launch<hubert_conv_ln_kernel<4>>("vbx_hubert_conv_ln", p, blocks, B, bytes, (hipStream_t)stream);
+  if (MG == 2) return sn_launch<hubert_conv_ln_kernel<2>>("vbx_hubert_conv_ln", p, blocks, B, bytes, (hipStream_t)stream);
+  return sn_launch<hubert_conv_ln_kernel<1>>("vbx_hubert_conv_ln", p, blocks, B, bytes, (hipStream_t)stream);
+}
+
+extern "C" int vbx_hubert_conv_f32(const void* x_f16, const void* w_f16, const float* bias, float* s_f32, int B, int L, int C, int k, void* stream) {
+  VBX_REQUIRE(x_f16 && w_f16 && s_f32, "vbx_hubert_conv_f32: null operand");
+  VBX_REQUIRE(B >= 1 && B <= 65535 && L >= k && L < (1 << 30), "vbx_hubert_conv_f32: need B in 1 .. 65535 and kernel_size <= L < 2^30");
+  if (int rc = hb_conv_check(C, k)) return rc;
+  HbConvF32 p;
+  p.x = (const u16*)x_f16, p.w = (const u16*)w_f16, p.y = nullptr, p.L = L, p.Lout = (L - k) / 2 + 1, p.C = C, p.k = k, p.bias = bias, p.s = s_f32;
+  int TT = hb_conv_tile(C, k);
+  while (TT > 16 && TT / 2 >= p.Lout) TT >>= 1;
+  p.TT = TT;
+  const size_t bytes = hb_conv_lds(TT, C, k);
+  const int MG = sn_blocks_per_item(C / 16, TT / 16), blocks = cdiv(p.Lout, TT);
+  if (MG == 4) return sn_launch<hubert_conv_f32_kernel<4>>("vbx_hubert_conv_f32", p, blocks, B, bytes, (hipStream_t)stream);
+  if (MG == 2) return sn_launch<hubert_conv_f32_kernel<2>>("vbx_hubert_conv_f32", p, blocks, B, bytes, (hipStream_t)stream);
+  return sn_launch<hubert_conv_f32_kernel<1>>("vbx_hubert_conv_f32", p, blocks, B, bytes, (hipStream_t)stream);
+}
+
+extern "C" int vbx_hubert_ln_gelu(const float* s_f32, const float* gamma, const float* beta, void* y_f16, long M, int C, float eps, void* stream) {
+  VBX_REQUIRE(s_f32 && gamma && beta && y_f16, "vbx_hubert_ln_gelu: null operand");
+  VBX_REQUIRE(M >= 1 && M < (1L << 31), "vbx_hubert_ln_gelu: need 1 <= rows < 2^31");
+  VBX_REQUIRE(C >= 8 && C % 8 == 0 && C <= HB_MAX_C, "vbx_hubert_ln_gelu: channels must be a multiple of 8 up to %d (got %d)", HB_MAX_C, C);
+  hipLaunchKernelGGL(hubert_ln_gelu_kernel, dim3(cdiv(M, 4)), dim3(256), 0, (hipStream_t)stream, s_f32, gamma, beta, (u16*)y_f16, M, C, eps);
+  VBX_LAUNCH_CHECK();
+  return 0;
+}
+
+// 1: the pair (vbx_hubert_conv_f32 + vbx_hubert_ln_gelu) is the faster way at this shape, 0: the fused kernel.  The pair wins where the
+// fp32 sums cost the fused kernel tile height (its tile is smaller than vbx_hubert_conv's) AND the grid is more than HB_PAIR_BLOCKS
+// workgroups.  The rule rests on ONE measured shape on one MI355X (8 x 160 000 samples at C = 512, profiles/hubert_large_times.json):
+// there it falls between layer 4 (8 x 125 = 1000 workgroups, the pair faster) and layer 5 (8 x 63 = 504, the fused kernel faster);
+// no other batch size was measured.  The two routes give the same bits, so only speed hangs on it.
+constexpr long HB_PAIR_BLOCKS = 512;
+extern "C" int vbx_hubert_conv_ln_route(int B, int L, int C, int k) {
+  if (int rc = hb_conv_check(C, k)) return rc;
+  VBX_REQUIRE(B >= 1 && L >= k, "vbx_hubert_conv_ln_route: need B >= 1 and L >= kernel_size");
+  const int TT = hb_conv_ln_tile(C, k);
+  const long Lout = (L - k) / 2 + 1;
+  return (TT < hb_conv_tile(C, k) && (long)B * ((Lout + TT - 1) / TT) > HB_PAIR_BLOCKS) ? 1 : 0;
+}
+
+extern "C" int vbx_wave_normalize_chunk(void) { return HB_WN_CHUNK; }
+
+extern "C" int vbx_wave_normalize(const float* x, const int* lens, float* y, float* records, double* stats, int B, long T, float eps, void* stream) {
+  VBX_REQUIRE(x && y && records && stats, "vbx_wave_normalize: null operand");
+  VBX_REQUIRE(B >= 1 && B <= 65535 && T >= 1 && T < (1L << 31), "vbx_wave_normalize: need B in 1 .. 65535 and 1 <= T < 2^31");
+  VBX_REQUIRE(eps > 0.f, "vbx_wave_normalize: eps must be positive");
+  const int chunks = cdiv(T, HB_WN_CHUNK);
+  hipLaunchKernelGGL(wave_normalize_stats_kernel, dim3(chunks, B), dim3(256), 0, (hipStream_t)stream, x, lens, records, (int)T, chunks);
+  VBX_LAUNCH_CHECK();
+  hipLaunchKernelGGL(wave_normalize_finalize_kernel, dim3(cdiv(B, 64)), dim3(64), 0, (hipStream_t)stream, records, lens, stats, B, (int)T, chunks, eps);
+  VBX_LAUNCH_CHECK();
+  hipLaunchKernelGGL(wave_normalize_apply_kernel, dim3(cdiv(T, 1024), B), dim3(256), 0, (hipStream_t)stream, x, lens, stats, y, (int)T);
+  VBX_LAUNCH_CHECK();
+  return 0;
 }

@@ -18,6 +18,10 @@ including the claim that fairseq's output_layer = L is hidden_states[L].
 Device path (csrc/hubert.hip, csrc/gemm.hip, csrc/attn.hip): a fixed launch sequence without host synchronisation; where each tensor
 is rounded is stated in include/vbx.h.  Inference only, GPU tensors only.  Rows of unequal length: lens= (per-row sample counts; include/vbx.h
 "ragged waves") makes every row of a padded batch the row it would be alone; a padding / attention mask is not served.
+
+HubertLargeWithKmeans (below) is the LARGE form -- feat_extract_norm="layer", the pre-LN encoder of do_stable_layer_norm=True, an
+optional convolution bias: hubert-large-ll60k -- beside it, as CausalSEANetEncoder stands beside SEANetEncoder; tests/hubert_large_ref.py
+is its restatement, pinned to transformers.HubertModel the same way (tests/test_hubert_large_cpu.py).
 """
 import math
 
@@ -65,8 +69,11 @@ def convert_state_dict(sd):
         if k.startswith(_SKIPPED):
             continue
         parts = k.split(".")
-        if k.startswith("feature_extractor.conv_layers.") and len(parts) == 5 and parts[3] == "0" and parts[4] == "weight":
-            k = f"feature_extractor.conv_layers.{parts[2]}.conv.weight"  # fairseq: Sequential(conv, dropout, norm, gelu)
+        if k.startswith("feature_extractor.conv_layers.") and len(parts) == 5 and parts[3] == "0" and parts[4] in ("weight", "bias"):
+            k = f"feature_extractor.conv_layers.{parts[2]}.conv.{parts[4]}"  # fairseq: Sequential(conv, dropout, norm, gelu)
+        elif k.startswith("feature_extractor.conv_layers.") and len(parts) == 6 and parts[3] == "2" and parts[4] == "1":
+            # fairseq, mode "layer_norm": the norm is Sequential(TransposeLast, LayerNorm, TransposeLast) (from memory; unpinned)
+            k = f"feature_extractor.conv_layers.{parts[2]}.layer_norm.{parts[5]}"
         elif k.startswith("feature_extractor.conv_layers.") and len(parts) == 5 and parts[3] == "2":
             k = f"feature_extractor.conv_layers.{parts[2]}.layer_norm.{parts[4]}"
         elif k.startswith("layer_norm."):
@@ -123,19 +130,28 @@ class HubertWithKmeans(PackedWeights, nn.Module):
     16-position span does not fit the LDS; codebook_size outside 2 .. 4096; output_layer outside 1 .. num_hidden_layers; a wave shorter than
     one frame; an attention / padding mask.  A CPU tensor raises VbxError."""
 
+    _NAME = "HubertWithKmeans"
+
+    @classmethod
+    def _check_form(cls, feat_extract_norm, do_stable_layer_norm, conv_bias):
+        """the base form only; the large form is HubertLargeWithKmeans"""
+        who, other = cls._NAME, "HubertLargeWithKmeans serves the large form"
+        if feat_extract_norm != "group":
+            raise NotImplementedError(f'{who}: feat_extract_norm="{feat_extract_norm}" is not built here (only "group", the base form; {other})')
+        if do_stable_layer_norm:
+            raise NotImplementedError(f"{who}: do_stable_layer_norm=True (the pre-LN encoder of the large models) is not built here ({other})")
+        if conv_bias:
+            raise NotImplementedError(f"{who}: conv_bias=True is not built here ({other})")
+
     def __init__(self, hidden_size=768, num_hidden_layers=12, num_attention_heads=12, intermediate_size=3072, conv_dim=(512,) * 7,
                  conv_kernel=(10, 3, 3, 3, 3, 2, 2), conv_stride=(5, 2, 2, 2, 2, 2, 2), num_conv_pos_embeddings=128,
                  num_conv_pos_embedding_groups=16, layer_norm_eps=1e-5, output_layer=9, codebook_size=500, target_sample_hz=16000,
                  seq_len_multiple_of=None, feat_extract_norm="group", do_stable_layer_norm=False, conv_bias=False):
         super().__init__()
-        who = "HubertWithKmeans"
+        who = self._NAME
         conv_dim, conv_kernel, conv_stride = tuple(conv_dim), tuple(conv_kernel), tuple(conv_stride)
-        if feat_extract_norm != "group":
-            raise NotImplementedError(f'{who}: feat_extract_norm="{feat_extract_norm}" is not built here (only "group", the base form)')
-        if do_stable_layer_norm:
-            raise NotImplementedError(f"{who}: do_stable_layer_norm=True (the pre-LN encoder of the large models) is not built here")
-        if conv_bias:
-            raise NotImplementedError(f"{who}: conv_bias=True is not built here")
+        self._check_form(feat_extract_norm, do_stable_layer_norm, conv_bias)
+        self.feat_extract_norm, self.do_stable_layer_norm, self.conv_bias = feat_extract_norm, bool(do_stable_layer_norm), bool(conv_bias)
         D, H, G, k = hidden_size, num_attention_heads, num_conv_pos_embedding_groups, num_conv_pos_embeddings
         if H < 1 or D != 64 * H:
             raise NotImplementedError(f"{who}: hidden_size / num_attention_heads must be 64, the head size the attention kernels serve (got {D} / {H})")
@@ -178,7 +194,9 @@ class HubertWithKmeans(PackedWeights, nn.Module):
             layer = _Box()
             layer.conv = _Box()
             layer.conv.weight = nn.Parameter(torch.randn(C, cin, kk) * math.sqrt(2.0 / (cin * kk)))
-            if i == 0:
+            if conv_bias:
+                layer.conv.bias = nn.Parameter(torch.zeros(C))
+            if i == 0 or feat_extract_norm == "layer":
                 layer.layer_norm = _ln(C)
             self.feature_extractor.conv_layers.append(layer)
             cin = C
@@ -218,13 +236,24 @@ class HubertWithKmeans(PackedWeights, nn.Module):
     def set_cluster_centers(self, centers):
         c = torch.as_tensor(centers).detach().float()
         if tuple(c.shape) != (self.codebook_size, self.hidden_size):
-            raise ValueError(f"HubertWithKmeans: cluster centres must be [{self.codebook_size}, {self.hidden_size}] (got {tuple(c.shape)})")
+            raise ValueError(f"{self._NAME}: cluster centres must be [{self.codebook_size}, {self.hidden_size}] (got {tuple(c.shape)})")
         self.cluster_centers = c.to(self.cluster_centers.device).contiguous()
 
     @classmethod
-    def from_state_dict(cls, sd, cluster_centers, *, output_layer=9, conv_stride=None, target_sample_hz=16000, seq_len_multiple_of=None):
+    def _form_of(cls, sd):
+        """constructor keywords read off a converted state dict's KEYS; raises for a file of the other class"""
+        for name, what in (("feature_extractor.conv_layers.0.conv.bias", "conv_bias=True"),
+                           ("feature_extractor.conv_layers.1.layer_norm.weight", 'feat_extract_norm="layer"')):
+            if name in sd:
+                raise NotImplementedError(f"HubertWithKmeans: this state dict is of a model with {what}, which is not built here "
+                                          f"(HubertLargeWithKmeans loads the large form)")
+        return {}
+
+    @classmethod
+    def from_state_dict(cls, sd, cluster_centers, *, output_layer=9, conv_stride=None, target_sample_hz=16000, seq_len_multiple_of=None, **form):
         """A HuBERT state dict already in memory (any layout convert_state_dict takes) and cluster centres [K, D].  Every width is read
-        off the shapes; the strides are not in a state dict (default (5, 2, 2, ...), the published models')."""
+        off the shapes; the strides are not in a state dict (default (5, 2, 2, ...), the published models').  Further keywords go to
+        the constructor."""
         sd = convert_state_dict(sd)
         n_conv = 1 + max(int(k.split(".")[2]) for k in sd if k.startswith("feature_extractor.conv_layers."))
         convs = [sd[f"feature_extractor.conv_layers.{i}.conv.weight"] for i in range(n_conv)]
@@ -232,27 +261,26 @@ class HubertWithKmeans(PackedWeights, nn.Module):
         D = sd["feature_projection.projection.weight"].shape[0]
         v = sd[_G1]
         cluster_centers = torch.as_tensor(cluster_centers)
-        for name, what in (("feature_extractor.conv_layers.0.conv.bias", "conv_bias=True"),
-                           ("feature_extractor.conv_layers.1.layer_norm.weight", 'feat_extract_norm="layer"')):
-            if name in sd:
-                raise NotImplementedError(f"HubertWithKmeans: this state dict is of a model with {what}, which is not built here")
+        form = dict(cls._form_of(sd), **form)
         self = cls(hidden_size=D, num_hidden_layers=n_layers, num_attention_heads=max(D // 64, 1),
                    intermediate_size=sd["encoder.layers.0.feed_forward.intermediate_dense.weight"].shape[0],
                    conv_dim=tuple(w.shape[0] for w in convs), conv_kernel=tuple(w.shape[2] for w in convs),
                    conv_stride=tuple(conv_stride) if conv_stride is not None else (5,) + (2,) * (n_conv - 1),
                    num_conv_pos_embeddings=v.shape[2], num_conv_pos_embedding_groups=D // v.shape[1], output_layer=output_layer,
-                   codebook_size=cluster_centers.shape[0], target_sample_hz=target_sample_hz, seq_len_multiple_of=seq_len_multiple_of)
+                   codebook_size=cluster_centers.shape[0], target_sample_hz=target_sample_hz, seq_len_multiple_of=seq_len_multiple_of,
+                   **form)
         self.load_state_dict(sd)
         self.set_cluster_centers(cluster_centers)
         return self.eval()
 
     @classmethod
-    def from_checkpoint(cls, checkpoint_path, kmeans_path, *, output_layer=9, conv_stride=None, target_sample_hz=16000, seq_len_multiple_of=None):
+    def from_checkpoint(cls, checkpoint_path, kmeans_path, *, output_layer=9, conv_stride=None, target_sample_hz=16000, seq_len_multiple_of=None,
+                        **form):
         """LOCAL files only: a torch.save'd state dict (transformers' or fairseq's names, or {'model': sd}) and the k-means file
         (load_kmeans)."""
         sd = torch.load(checkpoint_path, map_location="cpu", weights_only=True)
         return cls.from_state_dict(sd, load_kmeans(kmeans_path), output_layer=output_layer, conv_stride=conv_stride,
-                                   target_sample_hz=target_sample_hz, seq_len_multiple_of=seq_len_multiple_of)
+                                   target_sample_hz=target_sample_hz, seq_len_multiple_of=seq_len_multiple_of, **form)
 
     # -- operand copies
     def _pack(self):
@@ -349,25 +377,25 @@ class HubertWithKmeans(PackedWeights, nn.Module):
         if m is not None:
             lens, T = map_lens(lens, lambda l: l // m * m), T // m * m
         if self.frames(T) < 1:
-            raise NotImplementedError(f"HubertWithKmeans: a wave of {T} samples is shorter than one frame")
-        return device_lens(lens, B, T, self.min_samples(), device, "HubertWithKmeans")
+            raise NotImplementedError(f"{self._NAME}: a wave of {T} samples is shorter than one frame")
+        return device_lens(lens, B, T, self.min_samples(), device, self._NAME)
 
     def _prepare(self, wave, input_sample_hz, attention_mask, lens=None):
         """-> (wave fp32 [B, T] at target_sample_hz, lens int32 [B] on the device at that rate, or None)"""
         if attention_mask is not None:
-            raise NotImplementedError("HubertWithKmeans: an attention / padding mask is not served: rows of a batch are of equal length")
+            raise NotImplementedError(f"{self._NAME}: an attention / padding mask is not served: rows of a batch are of equal length")
         if not isinstance(wave, torch.Tensor) or wave.ndim not in (2, 3) or (wave.ndim == 3 and wave.shape[1] != 1):
-            raise ValueError("HubertWithKmeans takes a wave (batch, samples) or (batch, 1, samples)")
+            raise ValueError(f"{self._NAME} takes a wave (batch, samples) or (batch, 1, samples)")
         if wave.ndim == 3:
             wave = wave[:, 0]
         resampled = input_sample_hz is not None and input_sample_hz != self.target_sample_hz
         lens_in = lens
         if lens is not None:  # checked (host values) or clamped (a device tensor) before anything else
             if resampled:
-                lens_in = device_lens(lens, wave.shape[0], wave.shape[1], 1, wave.device, "HubertWithKmeans")
+                lens_in = device_lens(lens, wave.shape[0], wave.shape[1], 1, wave.device, self._NAME)
             lens = self._target_lens(lens, wave.shape[0], wave.shape[1], resampled, input_sample_hz, wave.device)
         if wave.device.type != "cuda":
-            raise _lib.VbxError(f"HubertWithKmeans runs only on an MI355X (gfx950) through libvbx_hip.so; the wave is on '{wave.device}'")
+            raise _lib.VbxError(f"{self._NAME} runs only on an MI355X (gfx950) through libvbx_hip.so; the wave is on '{wave.device}'")
         wave = wave.detach().to(torch.float32)
         if resampled:
             from .codec import resample
@@ -376,7 +404,7 @@ class HubertWithKmeans(PackedWeights, nn.Module):
         if self.seq_len_multiple_of is not None:
             wave = wave[:, :wave.shape[1] // self.seq_len_multiple_of * self.seq_len_multiple_of]
         if self.frames(wave.shape[1]) < 1:
-            raise NotImplementedError(f"HubertWithKmeans: a wave of {wave.shape[1]} samples is shorter than one frame")
+            raise NotImplementedError(f"{self._NAME}: a wave of {wave.shape[1]} samples is shorter than one frame")
         if self.cluster_centers.device != wave.device:
             self.to(wave.device)
         return wave.contiguous(), lens
@@ -453,7 +481,7 @@ class HubertWithKmeans(PackedWeights, nn.Module):
     def assign(self, feats):
         """vbx_kmeans_assign of features fp32 [.., D] -> int64 [..]"""
         if feats.device.type != "cuda":
-            raise _lib.VbxError(f"HubertWithKmeans runs only on an MI355X (gfx950) through libvbx_hip.so; the features are on '{feats.device}'")
+            raise _lib.VbxError(f"{self._NAME} runs only on an MI355X (gfx950) through libvbx_hip.so; the features are on '{feats.device}'")
         if self.cluster_centers.device != feats.device:
             self.to(feats.device)
         h = feats.detach().to(torch.float32).contiguous()
@@ -471,7 +499,7 @@ class HubertWithKmeans(PackedWeights, nn.Module):
 
         K = self.codebook_size if n_clusters is None else n_clusters
         if not isinstance(K, int) or not 2 <= K <= 4096:
-            raise NotImplementedError(f"HubertWithKmeans: codebook_size must be in 2 .. 4096 (got {K})")
+            raise NotImplementedError(f"{self._NAME}: codebook_size must be in 2 .. 4096 (got {K})")
         km = KMeans(K, self.hidden_size, init=init, seed=seed)
         resampled = input_sample_hz is not None and input_sample_hz != self.target_sample_hz
         for batch in batches:
@@ -481,7 +509,7 @@ class HubertWithKmeans(PackedWeights, nn.Module):
                 lens = self.frame_lens(resample_lens(lens, input_sample_hz, self.target_sample_hz) if resampled else lens)
             km.partial_fit(h, lens=lens)
         if km.cluster_centers_ is None:
-            raise ValueError("HubertWithKmeans: fit_kmeans needs at least one batch")
+            raise ValueError(f"{self._NAME}: fit_kmeans needs at least one batch")
         self.codebook_size = K
         self.set_cluster_centers(km.cluster_centers_)
         return km
@@ -494,3 +522,155 @@ class HubertWithKmeans(PackedWeights, nn.Module):
         h, dead = self._features(wave, lens)
         ids = self.assign(h)
         return ids if dead is None else ids.masked_fill_(dead, 0)
+
+
+def normalize_wave(wave, lens=None, eps=1e-7):
+    """Zero mean and unit variance per row on the device (vbx_wave_normalize): (x - mean) / sqrt(var + eps) with the biased variance,
+    what transformers' Wav2Vec2FeatureExtractor(do_normalize=True) does to a wave (its eps is 1e-7).  wave fp32 [B, T] on the device.
+    lens (a list or CPU tensor is validated, a device tensor clamped into 1 .. T): the statistics run over each row's own first
+    lens[b] samples and the samples at or past them come back as 0, whatever they held.  The sums are shifted per chunk and combined in
+    fp64: a DC offset costs nothing; the same bits on every run, and a row does not depend on its neighbours."""
+    if not isinstance(wave, torch.Tensor) or wave.ndim != 2 or wave.shape[1] < 1:
+        raise ValueError("normalize_wave takes a wave (batch, samples)")
+    if not eps > 0:
+        raise ValueError(f"normalize_wave: eps must be positive (got {eps})")
+    B, T = wave.shape
+    if lens is not None:
+        lens = device_lens(lens, B, T, 1, wave.device, "normalize_wave")
+    if wave.device.type != "cuda":
+        raise _lib.VbxError(f"normalize_wave runs only on an MI355X (gfx950) through libvbx_hip.so; the wave is on '{wave.device}'")
+    x = wave.detach().to(torch.float32).contiguous()
+    y = torch.empty_like(x)
+    chunks = -(-T // _lib.call_value("vbx_wave_normalize_chunk"))
+    rec = torch.empty(B, chunks, 3, dtype=torch.float32, device=x.device)
+    stats = torch.empty(B, 2, dtype=torch.float64, device=x.device)
+    _lib.call("vbx_wave_normalize", x, lens, y, rec, stats, B, T, float(eps), _lib.current_stream())
+    return y
+
+
+class HubertLargeWithKmeans(HubertWithKmeans):
+    """HubertWithKmeans for the LARGE form of HuBERT as transformers.HubertModel computes it (feat_extract_norm="layer",
+    do_stable_layer_norm=True, conv_bias either way; the defaults are hubert-large-ll60k's): every convolution of the feature extractor
+    is followed by its bias, LayerNorm over the channels of each position and erf-GELU -- no GroupNorm, no statistic over time --; the
+    encoder is x + gelu(pos_conv(x)) with no LayerNorm after it, then per layer x + out_proj(attn(layer_norm(x))) and
+    x + output_dense(gelu(intermediate_dense(final_layer_norm(x)))).  features() answers hidden_states[output_layer]: the
+    un-normalised residual stream after that layer, and encoder.layer_norm of it only for output_layer == num_hidden_layers.
+
+    The call shapes, lens=, frame_lens, fit_kmeans, assign, gemm_routes and the loaders are the base class's, and so is every limit but
+    the three that name the form: here feat_extract_norm must be "layer" WITH do_stable_layer_norm=True (any other pair raises and names
+    HubertWithKmeans); hidden_size / num_attention_heads == 64 stands, so x-large keeps raising.
+
+    normalize_wave=True normalises the prepared wave (after resampling and seq_len_multiple_of, under lens= each row's own samples) to
+    zero mean and unit variance on the device (normalize_wave(), eps = normalize_eps) before the first convolution.  hubert-large-ll60k
+    WAS TRAINED ON NORMALISED WAVES (its preprocessor has do_normalize=True); the default is False only because audiolm_pytorch's
+    module does not normalise.
+
+    A state dict cannot say whether its encoder is pre-LN (the keys are the same): from_state_dict takes a file with per-layer
+    convolution norms to have the pre-LN encoder, as every published such model does.  fairseq's large layout (bias at
+    conv_layers.{i}.0.bias, the norm at conv_layers.{i}.2.1.*) is translated from memory of that library, which is absent: unpinned."""
+
+    _NAME = "HubertLargeWithKmeans"
+
+    @classmethod
+    def _check_form(cls, feat_extract_norm, do_stable_layer_norm, conv_bias):
+        if feat_extract_norm != "layer" or not do_stable_layer_norm:
+            raise NotImplementedError(f'{cls._NAME}: serves feat_extract_norm="layer" with do_stable_layer_norm=True only (got '
+                                      f'"{feat_extract_norm}", {bool(do_stable_layer_norm)}); HubertWithKmeans serves "group" with False, and '
+                                      f"no model is published in a mixed form")
+
+    def __init__(self, hidden_size=1024, num_hidden_layers=24, num_attention_heads=16, intermediate_size=4096, conv_dim=(512,) * 7,
+                 conv_kernel=(10, 3, 3, 3, 3, 2, 2), conv_stride=(5, 2, 2, 2, 2, 2, 2), num_conv_pos_embeddings=128,
+                 num_conv_pos_embedding_groups=16, layer_norm_eps=1e-5, output_layer=9, codebook_size=500, target_sample_hz=16000,
+                 seq_len_multiple_of=None, feat_extract_norm="layer", do_stable_layer_norm=True, conv_bias=True, normalize_wave=False,
+                 normalize_eps=1e-7):
+        super().__init__(hidden_size=hidden_size, num_hidden_layers=num_hidden_layers, num_attention_heads=num_attention_heads,
+                         intermediate_size=intermediate_size, conv_dim=conv_dim, conv_kernel=conv_kernel, conv_stride=conv_stride,
+                         num_conv_pos_embeddings=num_conv_pos_embeddings, num_conv_pos_embedding_groups=num_conv_pos_embedding_groups,
+                         layer_norm_eps=layer_norm_eps, output_layer=output_layer, codebook_size=codebook_size,
+                         target_sample_hz=target_sample_hz, seq_len_multiple_of=seq_len_multiple_of, feat_extract_norm=feat_extract_norm,
+                         do_stable_layer_norm=do_stable_layer_norm, conv_bias=conv_bias)
+        if not normalize_eps > 0:
+            raise ValueError(f"{self._NAME}: normalize_eps must be positive (got {normalize_eps})")
+        self.normalize_wave, self.normalize_eps = bool(normalize_wave), float(normalize_eps)
+
+    @classmethod
+    def _form_of(cls, sd):
+        if "feature_extractor.conv_layers.1.layer_norm.weight" not in sd and "feature_extractor.conv_layers.0.conv.bias" in sd:
+            raise ValueError(f"{cls._NAME}: this state dict has convolution biases but no feature_extractor.conv_layers.1.layer_norm "
+                             f'(feat_extract_norm="group" with conv_bias=True): neither this class nor HubertWithKmeans serves that form')
+        if "feature_extractor.conv_layers.1.layer_norm.weight" not in sd:
+            raise ValueError(f"{cls._NAME}: this state dict has no feature_extractor.conv_layers.1.layer_norm: it is of the base form "
+                             f'(feat_extract_norm="group"), which HubertWithKmeans loads')
+        return dict(conv_bias="feature_extractor.conv_layers.0.conv.bias" in sd)
+
+    def _pack(self):
+        f = lambda t: t.detach().float().contiguous()
+        w = super()._pack()
+        fe = list(self.feature_extractor.conv_layers)
+        w["cb"] = [f(l.conv.bias) if self.conv_bias else None for l in fe]
+        w["lnw"], w["lnb"] = [f(l.layer_norm.weight) for l in fe], [f(l.layer_norm.bias) for l in fe]
+        return w
+
+    def _prepare(self, wave, input_sample_hz, attention_mask, lens=None):
+        wave, lens = super()._prepare(wave, input_sample_hz, attention_mask, lens)
+        if self.normalize_wave:
+            wave = normalize_wave(wave, lens=lens, eps=self.normalize_eps)
+        return wave, lens
+
+    def _features(self, wave, lens=None):
+        w = self._cached(self._pack)
+        st, dev, eps = _lib.current_stream(), wave.device, self.layer_norm_eps
+        B, T = wave.shape
+        C, D, H, I = self.conv_dim[0], self.hidden_size, self.num_attention_heads, self.intermediate_size
+        f16 = lambda *s: torch.empty(*s, dtype=torch.float16, device=dev)
+        f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
+        k0, s0 = self.conv_kernel[0], self.conv_stride[0]
+        L = (T - k0) // s0 + 1
+        a = f16(B, L, C)
+        # no statistic runs over time: under lens a frame inside a row's count reads only that row's own samples, so the plain
+        # kernels run; what they make of the padding is dropped by vbx_hubert_posconv_lens and never enters a live frame
+        _lib.call("vbx_hubert_conv0_ln", wave, w["w0"], w["cb"][0], w["lnw"][0], w["lnb"][0], a, B, T, C, k0, s0, eps, st)
+        sums = None  # the fp32 intermediate of the layers that take the pair; the first of them is the largest
+        for i, (kk, wc) in enumerate(zip(self.conv_kernel[1:], w["convs"]), 1):
+            Lo = (L - kk) // 2 + 1
+            y = f16(B, Lo, C)
+            if _lib.call_value("vbx_hubert_conv_ln_route", B, L, C, kk):  # the same bits either way (include/vbx.h): speed only
+                sums = f32(B * Lo * C) if sums is None else sums
+                _lib.call("vbx_hubert_conv_f32", a, wc, w["cb"][i], sums, B, L, C, kk, st)
+                _lib.call("vbx_hubert_ln_gelu", sums, w["lnw"][i], w["lnb"][i], y, B * Lo, C, eps, st)
+            else:
+                _lib.call("vbx_hubert_conv_ln", a, wc, w["cb"][i], w["lnw"][i], w["lnb"][i], y, B, L, C, kk, eps, st)
+            a, L = y, Lo
+        N, M = L, B * L
+        flens = self.frame_lens(lens).contiguous() if lens is not None else None  # int32 [B] on the device, 1 .. N
+        a16 = f16(M, C)
+        _lib.call("vbx_hubert_layernorm16", a, w["fplw"], w["fplb"], a16, M, C, eps, st)
+        xa, xb, x16 = f32(M, D), f32(M, D), f16(M, D)  # the residual stream ping-pongs; x16: the normalised operand of the next product
+        self._product("projection", M, a16, w["fpw"], xa, w["fpb"])
+        if lens is None:
+            _lib.call("vbx_hubert_posconv", xa, w["posw"], w["posb"], xb, B, N, D, self.num_conv_pos_embedding_groups, self.num_conv_pos_embeddings, st)
+        else:
+            _lib.call("vbx_hubert_posconv_lens", xa, flens, w["posw"], w["posb"], xb, B, N, D, self.num_conv_pos_embedding_groups,
+                      self.num_conv_pos_embeddings, st)
+        xa, xb = xb, xa  # xa: the stream
+        if w["layers"]:
+            qkv, q16, k16, v16 = f32(M, 3 * D), f16(B, H, N, 64), f16(B, H, N, 64), f16(B, H, N, 64)
+            o16, lse, g16 = f16(M, D), f32(B, H, N), f16(M, I)
+            scale = 64 ** -0.5
+            pre = _lib.lib().vbx_attn_q_prescale(scale)
+        for l in w["layers"]:
+            _lib.call("vbx_hubert_layernorm", xa, l["n1w"], l["n1b"], None, x16, M, D, eps, st)
+            self._product("qkv", M, x16, l["wqkv"], qkv, l["bqkv"])
+            _lib.call("vbx_hubert_split_heads", qkv, q16, k16, v16, B, N, H, pre, st)
+            if lens is None:
+                _lib.call("vbx_attn_fwd", q16, k16, v16, None, o16, None, lse, B, H, N, scale, st)
+            else:
+                _lib.call("vbx_attn_fwd_lens", q16, k16, v16, None, flens, o16, None, lse, B, H, N, scale, st)
+            self._product("out_proj", M, o16, l["wo"], xb, l["bo"], resid=xa)
+            _lib.call("vbx_hubert_layernorm", xb, l["n2w"], l["n2b"], None, x16, M, D, eps, st)
+            self._product("intermediate", M, x16, l["w1"], g16, l["b1"])
+            self._product("output", M, g16, l["w2"], xa, l["b2"], resid=xb)
+        if self.output_layer == self.num_hidden_layers:  # hidden_states[n] alone carries encoder.layer_norm
+            _lib.call("vbx_hubert_layernorm", xa, w["elw"], w["elb"], xb, None, M, D, eps, st)
+            xa = xb
+        return self._finish(xa.view(B, N, D), flens)
